@@ -8,17 +8,22 @@ Headline (default) = BASELINE config 4 AS WORDED ("64 streams ... one
 share of config 5: 64 concurrent synthetic streams per GPU batched through detect (simulated) -> track -> Kalman step -> plan,
 a step = ONE TIME-STEP (one frame of every stream) = one launch of the one-kernel step av_hot_step (launched, not replayed:
 replaying a one-kernel graph costs 5 us more per step than launching the kernel), all inputs resident in HBM.
-value = frames/s over all ranks.  A reported "step" is timed over `inner_reps` back-to-back repetitions so that every figure
-rests on >= 0.2 s of device time (`--steps` is what the driver passes; ms_per_step = time / (steps x inner_reps)).
+value = frames/s over all ranks.  The timed region is exactly `--steps` time-steps after exactly `--warmup` untimed ones
+(N > 1 with the bucketed all-gather: whole buckets of `--gather-every`); ms_per_step = timed wall time / steps.
+`--dump-outputs DIR` writes what the timed path computed in its last step (the arrays its caller reads back) as
+DIR/<name>.npy in float64; inputs are seeded, so the same arguments give the same inputs from run to run.
 
-At N = 1 the same JSON line carries, under "also", the other single-GPU configurations measured in the same process:
+A plain run does only that: set up, warm up, time the steps, dump, print the line.  `--full` adds everything else, in the
+same process: the headline's per-kernel list and roofline (stage kernels timed alone, a serial-launch probe), the CPU
+baselines, and at N = 1, under "also", the other single-GPU configurations (each timed over `inner_reps` x 20 steps so that
+every figure rests on >= `--min-seconds` of device time):
   config4_window256  the throughput form of config 4: 256-frame windows of every stream per step, one hipGraph replay per
                window (needs the window's 256 future measurement frames: an offline / replay mode, not a live loop)
   config3      YOLO-mode detector (MFMA convs) + Canny/Hough lane detector on device-generated 1280x720 frames
   config2      1 stream, simulated detection (latency-bound: one dependent chain)
   config2_w1   config 2 with window 1
 each as a compact summary (value, ms_per_step, dtype, roofline of the stage that dominates that configuration's step, CPU
-baseline); the printed line stays under 8 KB.  The full records -- every configuration's per-stage kernel list (isolated
+baseline); the printed line stays under 8 KB.  With `--full` the full records -- every configuration's per-stage kernel list (isolated
 HIP-event times on the launch stream, share of their sum, what bounds the stage, achieved vs peak) -- go to the side file
 named in "detail_file" (default gpurun_out/bench_detail.json; a builder-run copy is committed as profiles/rNN_bench_kernels.json).
 `traffic` values are PMC counter results read from profiles/*_pmc.json; each of those files carries the hash of the kernel
@@ -62,8 +67,12 @@ def parse():
     ap.add_argument("--window", type=int, default=None, help="frames per stream per step")
     ap.add_argument("--graph", dest="graph", action="store_true", default=None, help="replay the step as a captured hipGraph")
     ap.add_argument("--no-graph", dest="graph", action="store_false")
-    ap.add_argument("--no-also", action="store_true", help="headline configuration only")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel list and roofline, the CPU baselines and the other configurations ('also')")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float64, <= 64 MB in all)")
+    ap.add_argument("--no-also", action="store_true", help="--full: headline configuration only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baselines")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-allgather", action="store_true")
     ap.add_argument("--native-allgather", action="store_true",
@@ -75,7 +84,7 @@ def parse():
     ap.add_argument("--overlap", type=int, default=4, choices=[1, 2, 3, 4],
                     help="window 1: D > 1 = up to D consecutive time-steps in flight (HotLoop(overlap=D): still one launch per step, "
                          "ordered per stream and role by device-side counters); 1 = each launch after the previous one has drained")
-    ap.add_argument("--min-seconds", type=float, default=0.2, help="least device time behind every reported figure")
+    ap.add_argument("--min-seconds", type=float, default=0.2, help="--full: least device time behind every figure under 'also'")
     ap.add_argument("--gather", default="window-end", choices=["window-end", "per-frame"],
                     help="N>1: all-gather the end-of-window table (cheap) or every frame's table of the window")
     ap.add_argument("--no-defer", action="store_true", help="config3: whole lane chain inside its own step")
@@ -85,7 +94,10 @@ def parse():
                     help="also run the maneuver and interaction taggers (SURVEY 8f-3) in every step")
     ap.add_argument("--detail-out", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
                     help="side file for the full per-configuration records (kernel lists)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -236,6 +248,48 @@ def finish_kernel_list(ks):
     return ks
 
 
+DUMP_BYTES = 63 << 20          # --dump-outputs: all arrays together (the .npy headers fit in the last MB of 64)
+
+
+def write_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float64.  Arrays are written whole, smallest first, while each fits in
+    an even share of what is left of DUMP_BYTES; one that does not is cut to a fixed seeded sample of its flattened elements (in
+    index order) and the sample's flat indices go beside it as <name>_sample_index.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, np.float64) for k, v in arrays.items()}
+    left, names = DUMP_BYTES, sorted(arrays, key=lambda k: (arrays[k].size, k))
+    for i, k in enumerate(names):
+        x, share = arrays[k], left // (len(names) - i)
+        if x.nbytes > share:
+            m = share // 16                   # a sampled value and its index, 8 bytes each
+            idx = np.sort(np.random.default_rng(20240).choice(x.size, m, replace=False))
+            np.save(os.path.join(out_dir, k + "_sample_index.npy"), idx.astype(np.float64))
+            x = x.reshape(-1)[idx]
+            left -= 8 * m
+        np.save(os.path.join(out_dir, k + ".npy"), x)
+        left -= x.nbytes
+
+
+def hot_loop_outputs(loop):
+    """What a caller of the hot loop reads back after a step (HotLoop.results() + snapshots()): detections, detection -> track
+    map, vehicle state, the planner's candidates, costs and order, the tracker's rows.  Entries past a stream's count are
+    zeroed (those slots keep whatever an earlier step left there)."""
+    import numpy as np
+    r = loop.results()
+    rows, n = loop.snapshots()
+    live = np.arange(loop.dcap) < r["det_n"][..., None]
+    out = {"det_n": r["det_n"], "det_box": np.where(live[..., None], r["det_box"], 0), "det_cls": np.where(live, r["det_cls"], 0),
+           "det_conf": np.where(live, r["det_conf"], 0), "det2trk": np.where(live, r["det2trk"], 0), "vstate": r["vstate"],
+           "plan_cost": r["cost"], "plan_order": r["order"], "track_n": n}
+    if "wp" in r:
+        out["plan_waypoints"] = r["wp"]
+    held = np.arange(loop.tcap) < n[..., None]
+    for f in rows.dtype.names:
+        out["track_" + f] = np.where(held, rows[f], 0)
+    return out
+
+
 def pick_reps(est_step_s, steps, min_s, world):
     """Inner repetitions per reported step so that the timed region lasts >= min_s; every rank uses rank 0's choice."""
     import torch
@@ -267,7 +321,10 @@ class ChainBroken(RuntimeError):
     """An overlapped HotLoop reported a step that waited in vain for its predecessor (on this rank or another)."""
 
 
-def run_hot_loop(a, world, rank, local, name, S, W, graph, steps, warmup, stage_reps=10, overlap=None):
+def run_hot_loop(a, world, rank, local, name, S, W, graph, steps, warmup, stage_reps=10, overlap=None, headline=False):
+    """headline: exactly `steps` timed time-steps after exactly `warmup` untimed ones, --dump-outputs after them, and the
+    per-kernel list / roofline only with --full.  Otherwise (the configurations under 'also'): `inner_reps` x `steps` timed, sized
+    by --min-seconds, always with the kernel list."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -372,36 +429,75 @@ def run_hot_loop(a, world, rank, local, name, S, W, graph, steps, warmup, stage_
             xchg.flush()                      # (a partially filled bucket)
             xchg.synchronize()
 
-    for _ in range(max(warmup, 1)):
-        one_step()
+    def run_steps(n):
+        """n time-steps in calls of `unit` (the last call shorter; with a bucketed exchange whole buckets) -> steps run"""
+        if ov > 1 and xchg is None:
+            for k in range(0, n, unit):
+                loop.enqueue_steps(min(unit, n - k))
+            return n
+        calls = -(-n // unit)
+        for _ in range(calls):
+            one_step()
+        return calls * unit
+
+    if headline:
+        run_steps(warmup)
+        reps = 1
+    else:
+        for _ in range(max(warmup, 1)):
+            one_step()
     drain()
     torch.cuda.synchronize()
     chain_ok()
-    # a probe of the step's duration (untimed) sizes the inner repetitions: every reported step = `reps` back-to-back steps
-    tp = time.perf_counter()
-    for _ in range(8):
-        one_step()
-    drain()
-    torch.cuda.synchronize()
-    reps = pick_reps((time.perf_counter() - tp) / (8 * unit), steps, a.min_seconds, world)
-    calls = -(-steps * reps // unit)          # whole calls of `unit` time-steps
+    if not headline:
+        # a probe of the step's duration (untimed) sizes the inner repetitions: every reported step = `reps` back-to-back steps
+        tp = time.perf_counter()
+        for _ in range(8):
+            one_step()
+        drain()
+        torch.cuda.synchronize()
+        reps = pick_reps((time.perf_counter() - tp) / (8 * unit), steps, a.min_seconds, world)
     if world > 1:
         dist.barrier()
     t0 = time.perf_counter()
-    for _ in range(calls):
-        one_step()
+    nsteps = run_steps(steps * reps)
     drain()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     el = time.perf_counter() - t0
     el, per_rank_ms = max_over_ranks(el, world)
-    nsteps = calls * unit
     chain_ok()
     # the tracker's sticky overflow flag: a truncated table would silently drop births (parity lost)
     hdr, _, _ = loop.tracker_tables()
     if int(np.abs(hdr[:, 3]).max()) != 0:
         raise RuntimeError("tracker table overflow (hdr[3] != 0): tcap %d too small for this run" % loop.tcap)
+    if headline and a.dump_outputs and rank == 0:
+        write_outputs(a.dump_outputs, hot_loop_outputs(loop))
+    F = S * W
+    out = {"metric": METRIC, "value": round(F * nsteps * world / el, 1), "unit": "frames/s", "n_gpus": world,
+           "steps": steps, "warmup": warmup, "inner_reps": reps, "timed_s": round(el, 4),
+           "ms_per_step": round(el / nsteps * 1e3, 6), "higher_is_better": True,
+           "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+           "config": {"workload": "%s: %d stream(s)/GPU x %d-frame window per step, 1280x720, simulated detection + IoU "
+                                  "tracker + 6-state KF + 21-candidate planner%s" % (name, S, W, ", one hipGraph replay per step" if graph else
+                                                              ((", one launch per step, up to %d consecutive steps in flight" % ov if ov > 1 else ", one launch per step") if W == 1 else "")),
+                      "streams_per_gpu": S, "window": W, "graph": bool(graph), "taggers": bool(a.taggers),
+                      "allgather_track_tables": (("per-frame" if xchg.per_frame else "window-end") if xchg is not None else False),
+                      "allgather_impl": (("av_allgather_tracks (RCCL)" if xchg.native else "torch.distributed") if xchg is not None else None),
+                      "fused_step": bool(loop.fused_step), "overlapped_steps": ov, "steps_per_library_call": unit,
+                      "stream_sets_tried_us_per_step": tuned,
+                      "parallelism": "stream-sharded x%d" % world},
+           "ranks_seen": (dist.get_world_size() if world > 1 else 1), "per_rank_ms": per_rank_ms}
+    if xchg is not None:
+        out["config"]["allgather_bytes_per_rank_per_step"] = xchg.bytes_per_step
+        out["config"]["allgather_every_steps"] = xchg.bucket
+    if W == 1:
+        out["us_per_time_step"] = round(el / nsteps * 1e6, 3)
+    if headline and not a.full:
+        del loop, xchg
+        torch.cuda.empty_cache()
+        return out
     t_inflight = None
     if ov > 1:
         # a launch's own duration while `ov` are in flight (HIP events around every launch on the stream it runs on, the loop
@@ -440,7 +536,6 @@ def run_hot_loop(a, world, rank, local, name, S, W, graph, steps, warmup, stage_
         s = loop._s
 
     # per-stage kernel times, each stage alone on the launch stream
-    F = S * W
     sync = loop.synchronize
     ks = []
     t_det = time_stage(L, nat, s, loop.enqueue_detect, stage_reps, sync)
@@ -517,33 +612,14 @@ def run_hot_loop(a, world, rank, local, name, S, W, graph, steps, warmup, stage_
     if planner_k is not None and not loop.fused_step:
         roof["hbm_bound_kernel_beside_it"] = {k: planner_k[k] for k in ("kernel", "avg_ms", "achieved", "frac", "traffic", "bytes_per_launch")}
     step_bytes = (TRACKER_BYTES + KF_BYTES + SIMDET_BYTES) * F + pb
-    out = {"metric": METRIC, "value": round(F * nsteps * world / el, 1), "unit": "frames/s", "n_gpus": world,
-           "steps": steps, "warmup": warmup, "inner_reps": reps, "timed_s": round(el, 4),
-           "ms_per_step": round(el / nsteps * 1e3, 6), "higher_is_better": True,
-           "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-           "config": {"workload": "%s: %d stream(s)/GPU x %d-frame window per step, 1280x720, simulated detection + IoU "
-                                  "tracker + 6-state KF + 21-candidate planner%s" % (name, S, W, ", one hipGraph replay per step" if graph else
-                                                              ((", one launch per step, up to %d consecutive steps in flight" % ov if ov > 1 else ", one launch per step") if W == 1 else "")),
-                      "streams_per_gpu": S, "window": W, "graph": bool(graph), "taggers": bool(a.taggers),
-                      "allgather_track_tables": (("per-frame" if xchg.per_frame else "window-end") if xchg is not None else False),
-                      "allgather_impl": (("av_allgather_tracks (RCCL)" if xchg.native else "torch.distributed") if xchg is not None else None),
-                      "fused_step": bool(loop.fused_step), "overlapped_steps": ov, "steps_per_library_call": unit,
-                      "stream_sets_tried_us_per_step": tuned,
-                      "parallelism": "stream-sharded x%d" % world},
-           "roofline": roof, "kernels": finish_kernel_list(ks),
-           "step": {"critical_branch": "side (detect+track)" if side > main else "main (kf+plan)",
-                    "side_branch_ms": round(side, 5), "main_branch_ms": round(main, 5),
-                    "algorithmic_bytes": step_bytes,
-                    "hbm_frac_whole_step": round(step_bytes / (el / nsteps) / 1e9 / HBM_PEAK_GBS, 4)},
-           "ranks_seen": (dist.get_world_size() if world > 1 else 1), "per_rank_ms": per_rank_ms}
-    if xchg is not None:
-        out["config"]["allgather_bytes_per_rank_per_step"] = xchg.bytes_per_step
-        out["config"]["allgather_every_steps"] = xchg.bucket
+    out.update({"roofline": roof, "kernels": finish_kernel_list(ks),
+                "step": {"critical_branch": "side (detect+track)" if side > main else "main (kf+plan)",
+                         "side_branch_ms": round(side, 5), "main_branch_ms": round(main, 5),
+                         "algorithmic_bytes": step_bytes,
+                         "hbm_frac_whole_step": round(step_bytes / (el / nsteps) / 1e9 / HBM_PEAK_GBS, 4)}})
     if stage_kernels is not None:
         out["stage_kernels_replaced"] = stage_kernels
     out["traffic_profiles"] = [pmc_stamp("hot_step_pmc.json")] if loop.fused_step else [pmc_stamp("tracker_pmc.json"), pmc_stamp("planner_pmc.json")]
-    if W == 1:
-        out["us_per_time_step"] = round(el / nsteps * 1e6, 3)
     del loop, xchg
     torch.cuda.empty_cache()
     return out
@@ -552,7 +628,8 @@ def run_hot_loop(a, world, rank, local, name, S, W, graph, steps, warmup, stage_
 # ---------------------------------------------------------------------------------------------------------------
 # config 3: YOLO-mode detector + lane detector on device-generated frames
 # ---------------------------------------------------------------------------------------------------------------
-def run_config3(a, world, rank, local, S, steps, warmup, stage_reps=6, precision="fp16"):
+def run_config3(a, world, rank, local, S, steps, warmup, stage_reps=6, precision="fp16", headline=False):
+    """headline: as run_hot_loop's (exact steps and warmup, --dump-outputs, the kernel list only with --full)."""
     import torch
     import torch.distributed as dist
     from multimodal_autonomous_driving_perception_and_planning_amd import _native as nat
@@ -584,16 +661,18 @@ def run_config3(a, world, rank, local, S, steps, warmup, stage_reps=6, precision
         loop.enqueue_detect()
         nat.check(L.av_join(loop.ctx.handle, s))
 
-    for _ in range(max(warmup, 1)):
+    for _ in range(warmup if headline else max(warmup, 1)):
         one_step()
     loop.synchronize()
     torch.cuda.synchronize()
-    tp = time.perf_counter()
-    for _ in range(4):
-        one_step()
-    loop.synchronize()
-    torch.cuda.synchronize()
-    reps = pick_reps((time.perf_counter() - tp) / 4, steps, a.min_seconds, world)
+    reps = 1
+    if not headline:
+        tp = time.perf_counter()
+        for _ in range(4):
+            one_step()
+        loop.synchronize()
+        torch.cuda.synchronize()
+        reps = pick_reps((time.perf_counter() - tp) / 4, steps, a.min_seconds, world)
     nsteps = steps * reps
     if world > 1:
         dist.barrier()
@@ -607,6 +686,30 @@ def run_config3(a, world, rank, local, S, steps, warmup, stage_reps=6, precision
         dist.barrier()
     el = time.perf_counter() - t0
     el, per_rank_ms = max_over_ranks(el, world)
+    if headline and a.dump_outputs and rank == 0:
+        # what the step leaves for its caller: every camera's detections (entries past det_n zeroed: stale slots) and lanes
+        import numpy as np
+        n = loop.det_n.cpu().numpy()
+        live = np.arange(loop.max_det) < n[:, None]
+        write_outputs(a.dump_outputs, {"det_n": n, "det_box": np.where(live[..., None], loop.det_box.cpu().numpy(), 0),
+                                       "det_conf": np.where(live, loop.det_conf.cpu().numpy(), 0),
+                                       "det_cls": np.where(live, loop.det_cls.cpu().numpy(), 0),
+                                       "lane_poly": loop.poly.cpu().numpy(), "lane_pts": loop.pts.cpu().numpy(),
+                                       "lane_info": loop.info.cpu().numpy(), "lane_conf": loop.conf.cpu().numpy(),
+                                       "lane_state": loop.lane_state.cpu().numpy()})
+    out = {"metric": METRIC, "value": round(S * nsteps * world / el, 1), "unit": "frames/s", "n_gpus": world,
+           "steps": steps, "warmup": warmup, "inner_reps": reps, "timed_s": round(el, 4),
+           "ms_per_step": round(el / nsteps * 1e3, 4), "higher_is_better": True,
+           "scaling": "weak", "vs_baseline": None, "dtype": loop.yolo.precision, "data": "synthetic (generated on device)",
+           "config": {"workload": "config3: %d camera streams/GPU, one 1280x720 frame of each per step, YOLO-mode detector "
+                                  "(random-init YOLOv8n topology, letterbox 384x640%s) + Canny/Hough lane detector" % (S, ", float32 operands: the reference's own precision" if fp32 else ", IEEE-half operands"),
+                      "streams_per_gpu": S, "parallelism": "stream-sharded x%d" % world,
+                      "main_stream_candidates_ms": tuned},
+           "ranks_seen": (dist.get_world_size() if world > 1 else 1), "per_rank_ms": per_rank_ms}
+    if headline and not a.full:
+        del loop
+        torch.cuda.empty_cache()
+        return out
 
     if not fp32:
         loop.defer_detector_tail(False)      # the per-stage times below are of whole stages
@@ -653,20 +756,11 @@ def run_config3(a, world, rank, local, S, steps, warmup, stage_reps=6, precision
         roof["flops_per_launch"] = dom["flops_per_launch"]
         if not fp32:
             roof["mfma_busy_pmc_percent"] = pmc_value("yolo_mfma_pmc.json", "overall_mfma_busy_percent")
-    out = {"metric": METRIC, "value": round(S * nsteps * world / el, 1), "unit": "frames/s", "n_gpus": world,
-           "steps": steps, "warmup": warmup, "inner_reps": reps, "timed_s": round(el, 4),
-           "ms_per_step": round(el / nsteps * 1e3, 4), "higher_is_better": True,
-           "scaling": "weak", "vs_baseline": None, "dtype": loop.yolo.precision, "data": "synthetic (generated on device)",
-           "config": {"workload": "config3: %d camera streams/GPU, one 1280x720 frame of each per step, YOLO-mode detector "
-                                  "(random-init YOLOv8n topology, letterbox 384x640%s) + Canny/Hough lane detector" % (S, ", float32 operands: the reference's own precision" if fp32 else ", IEEE-half operands"),
-                      "streams_per_gpu": S, "parallelism": "stream-sharded x%d" % world,
-                      "main_stream_candidates_ms": tuned},
-           "roofline": roof, "kernels": finish_kernel_list(ks),
-           "lane_chain": {"avg_ms": round(lane_ms, 5), "bytes_per_launch": lane_total,
-                          "achieved": round(lane_total / (lane_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                          "frac": round(lane_total / (lane_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                          "note": "SURVEY 8d: 7*W*H algorithmic bytes per frame over pixel stages + Hough + fit"},
-           "ranks_seen": (dist.get_world_size() if world > 1 else 1), "per_rank_ms": per_rank_ms}
+    out.update({"roofline": roof, "kernels": finish_kernel_list(ks),
+                "lane_chain": {"avg_ms": round(lane_ms, 5), "bytes_per_launch": lane_total,
+                               "achieved": round(lane_total / (lane_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": round(lane_total / (lane_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                               "note": "SURVEY 8d: 7*W*H algorithmic bytes per frame over pixel stages + Hough + fit"}})
     out["traffic_profiles"] = [pmc_stamp("lane_pmc.json"), pmc_stamp("yolo_mfma_pmc.json"), pmc_stamp("yolo_hbm_pmc.json")]
     del loop
     torch.cuda.empty_cache()
@@ -780,8 +874,9 @@ def compact_summary(v):
 def compact_line(head):
     """The printed line: the headline in full except its long texts, `also` as compact summaries."""
     line = {k: v for k, v in head.items() if k not in ("also", "kernels", "stage_kernels_replaced")}
-    line["kernels"] = [{k: (_short(x, 100) if isinstance(x, str) else x) for k, x in kk.items() if k not in ("why", "peak", "unit", "branch")}
-                       for kk in head.get("kernels", [])]
+    if "kernels" in head:
+        line["kernels"] = [{k: (_short(x, 100) if isinstance(x, str) else x) for k, x in kk.items() if k not in ("why", "peak", "unit", "branch")}
+                           for kk in head["kernels"]]
     if "roofline" in line and "note" in line["roofline"]:
         line["roofline"] = dict(line["roofline"], note=_short(line["roofline"]["note"], 120))
     if "cpu_baseline" in line and "sample" in line["cpu_baseline"]:
@@ -803,7 +898,7 @@ def main():
 
     # CPU legs first: nothing has touched the GPU yet, so child processes are safe to start
     cpu_hot = cpu_pix = None
-    if world == 1 and not a.no_cpu_baseline:
+    if world == 1 and a.full and not a.no_cpu_baseline:
         cpu_hot = cpu_hot_loop(a.cpu_seconds)
         if not a.no_also or a.workload == "config3":
             cpu_pix = cpu_pixel_path(a.cpu_seconds)
@@ -826,26 +921,28 @@ def main():
                 line["cpu_baseline"]["gpu_over_cpu_nproc"] = round(line["value"] / cpu["nproc"]["value"], 1)
         return line
 
-    def hot(name, S, W, graph, steps, warmup, overlap=None):
+    def hot(name, S, W, graph, steps, warmup, overlap=None, headline=False):
         try:
-            return run_hot_loop(a, world, rank, local, name, S, W, graph, steps, warmup, overlap=overlap)
+            return run_hot_loop(a, world, rank, local, name, S, W, graph, steps, warmup, overlap=overlap, headline=headline)
         except ChainBroken as e:
             # (raised on every rank together) the same measurement with serial launches
-            r = run_hot_loop(a, world, rank, local, name, S, W, graph, steps, warmup, overlap=1)
+            r = run_hot_loop(a, world, rank, local, name, S, W, graph, steps, warmup, overlap=1, headline=headline)
             r["config"]["overlap_fallback"] = str(e)[:200]
             return r
 
     if a.workload == "config3":
-        head = with_cpu(run_config3(a, world, rank, local, a.streams or 64, a.steps, a.warmup, precision=a.precision), cpu_pix)
+        head = with_cpu(run_config3(a, world, rank, local, a.streams or 64, a.steps, a.warmup, precision=a.precision, headline=True),
+                        cpu_pix)
     elif a.workload == "config2":
         g = bool(a.graph) if a.graph is not None else False
-        head = with_cpu(hot("config2", a.streams or 1, a.window or 131072, g, a.steps, a.warmup), cpu_hot)
+        head = with_cpu(hot("config2", a.streams or 1, a.window or 131072, g, a.steps, a.warmup, headline=True), cpu_hot)
     else:
         W = a.window or 1                                              # as worded: one launch per time-step
         g = (W != 1) if a.graph is None else bool(a.graph)             # window 1 is one kernel: launched, not replayed
-        head = with_cpu(hot("config4" if W == 1 else "config4 (%d-frame windows)" % W, a.streams or 64, W, g, a.steps, a.warmup), cpu_hot)
+        head = with_cpu(hot("config4" if W == 1 else "config4 (%d-frame windows)" % W, a.streams or 64, W, g, a.steps, a.warmup,
+                            headline=True), cpu_hot)
 
-    if world == 1 and not a.no_also and a.workload == "config4":
+    if world == 1 and a.full and not a.no_also and a.workload == "config4":
         also = {}
         if (a.window or 1) == 1:
             if head["config"].get("overlapped_steps", 1) > 1:
@@ -870,15 +967,16 @@ def main():
         head["also"] = also
 
     if rank == 0:
-        # full records (kernel lists) -> side file; the printed line carries compact per-configuration summaries (< 8 KB)
-        detail = json.loads(json.dumps(head))
-        try:
-            os.makedirs(os.path.dirname(a.detail_out), exist_ok=True)
-            with open(a.detail_out, "w") as f:
-                json.dump(detail, f, indent=1)
-            head["detail_file"] = os.path.relpath(a.detail_out, ROOT)
-        except OSError:
-            head["detail_file"] = None
+        if a.full:
+            # full records (kernel lists) -> side file; the printed line carries compact per-configuration summaries (< 8 KB)
+            detail = json.loads(json.dumps(head))
+            try:
+                os.makedirs(os.path.dirname(a.detail_out), exist_ok=True)
+                with open(a.detail_out, "w") as f:
+                    json.dump(detail, f, indent=1)
+                head["detail_file"] = os.path.relpath(a.detail_out, ROOT)
+            except OSError:
+                head["detail_file"] = None
         print(json.dumps(compact_line(head)), flush=True)
     if world > 1:
         dist.destroy_process_group()

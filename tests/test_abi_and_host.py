@@ -404,3 +404,24 @@ def test_step_flag_layout_matches_the_header_and_step_numbers_wrap():
         assert eval(m.group(1).replace("(n_streams)", str(S))) == nat.step_flag_ints(S)
     assert int(re.search(r"#define AV_STEP_MAX_DEPTH (\d+)", hdr).group(1)) == 4
     assert [nat.step_i32(v) for v in (0, 5, 2 ** 31 - 1, 2 ** 31, 2 ** 32 - 1, 2 ** 32, 2 ** 32 + 3)] == [0, 5, 2 ** 31 - 1, -2 ** 31, -1, 0, 3]
+
+
+def test_bench_output_dump_fits_64_mb_with_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: one float64 .npy per array; an array too large for the 64 MB budget becomes a fixed seeded sample
+    of its flattened elements (in index order) with the sample's indices beside it -- the same sample on every run."""
+    import bench
+    big = np.arange(12_000_000, dtype=np.int32).reshape(3000, 4000)        # 96 MB in float64
+    small = np.array([[1, 2], [3, 4]], np.int32)
+    for d in ("a", "b"):
+        bench.write_outputs(str(tmp_path / d), {"big": big, "small": small})
+    a, b = tmp_path / "a", tmp_path / "b"
+    names = sorted(p.name for p in a.iterdir())
+    assert names == ["big.npy", "big_sample_index.npy", "small.npy"]
+    assert sum(p.stat().st_size for p in a.iterdir()) <= 64 << 20
+    for n in names:
+        x = np.load(a / n)
+        assert x.dtype == np.float64 and np.array_equal(x, np.load(b / n)), n
+    idx = np.load(a / "big_sample_index.npy").astype(np.int64)
+    assert idx.size > 1_000_000 and (np.diff(idx) > 0).all()
+    assert np.array_equal(np.load(a / "big.npy"), big.reshape(-1)[idx].astype(np.float64))
+    assert np.array_equal(np.load(a / "small.npy"), small.astype(np.float64))

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Reads bench.py's JSON line on stdin and prints value, ms/step and the per-stage times (tuning aid)."""
+"""Reads the JSON line of `bench.py --full` on stdin and prints value, ms/step and the per-stage times (tuning aid)."""
 import json, sys
 tag = sys.argv[1] if len(sys.argv) > 1 else ""
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])

@@ -12,7 +12,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 trace() { name=$1; shift; rocprofv3 --kernel-trace -d $OUT/$name -o t -- "$@" > $OUT/$name.log 2>&1; echo "trace $name done"; }
 pmc() { name=$1; ctr=$2; shift 2; rocprofv3 --kernel-trace --pmc $ctr -d $OUT/$name -o p -- "$@" > $OUT/$name.log 2>&1; echo "pmc $name done"; }
 if [ "$ONLY" = yolo ]; then
-  trace bench_config3 python3 bench.py --no-also --no-cpu-baseline --workload config3 --min-seconds 0.02
+  trace bench_config3 python3 bench.py --full --no-also --no-cpu-baseline --workload config3
   trace yolo_b64 python3 tools/ybench.py --batch 64 --reps 5
   pmc yolo_mfma "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE" python3 tools/ybench.py --batch 64 --reps 3
   ls $OUT; exit 0
@@ -20,10 +20,10 @@ fi
 # the headline (config 4 as worded: one hot_step_kernel launch per time-step, up to four in flight), the same with serial launches,
 # and the 256-frame-window throughput form
 if [ "$ONLY" != rest ]; then
-trace bench_config4 python3 bench.py --no-also --no-cpu-baseline --min-seconds 0.02
-trace bench_config4_serial python3 bench.py --no-also --no-cpu-baseline --overlap 1 --min-seconds 0.02
-trace bench_config4_window256 python3 bench.py --no-also --no-cpu-baseline --window 256 --min-seconds 0.02
-trace bench_config2 python3 bench.py --no-also --no-cpu-baseline --workload config2 --steps 4 --warmup 1 --window 32768 --min-seconds 0.02
+trace bench_config4 python3 bench.py --full --no-also --no-cpu-baseline --steps 5600
+trace bench_config4_serial python3 bench.py --full --no-also --no-cpu-baseline --overlap 1 --steps 2000
+trace bench_config4_window256 python3 bench.py --full --no-also --no-cpu-baseline --window 256 --steps 100
+trace bench_config2 python3 bench.py --full --no-also --no-cpu-baseline --workload config2 --steps 4 --warmup 1 --window 32768
 fi
 # (counter passes run kernels one after the other in any order: the overlapped steps are launched one at a time, tools/stepsync.py)
 pmc step_fetch FETCH_SIZE python3 tools/stepsync.py 300
@@ -31,7 +31,7 @@ pmc step_write WRITE_SIZE python3 tools/stepsync.py 300
 pmc trk_fetch FETCH_SIZE python3 tools/kbench.py --streams 64 --window 256 --stages detect,track --reps 2
 pmc trk_write WRITE_SIZE python3 tools/kbench.py --streams 64 --window 256 --stages detect,track --reps 2
 if [ "$ONLY" = hot ]; then ls $OUT; exit 0; fi
-trace bench_config3 python3 bench.py --no-also --no-cpu-baseline --workload config3 --min-seconds 0.02
+trace bench_config3 python3 bench.py --full --no-also --no-cpu-baseline --workload config3
 trace lane_S64 python3 tools/lbench.py --reps 5
 trace yolo_b64 python3 tools/ybench.py --batch 64 --reps 5
 pmc lane_fetch FETCH_SIZE python3 tools/lbench.py --reps 2
