@@ -225,7 +225,8 @@ typedef struct {
 
 #define AV_WP_DOUBLES 6          /* x y heading velocity timestamp curvature */
 /* Builds the per-configuration constant tables (timestamps, 1-exp(-t), quintic blend, lateral
- * offsets) on the host and uploads them.  n_points = int(H/dt)+1 <= 1024, candidates <= 192. */
+ * offsets) on the host and uploads them.  n_points = int(H/dt)+1 <= 256, candidates <= 192;
+ * av_planner_plan plans every configuration this call accepts. */
 int av_planner_configure(av_ctx* ctx, const av_planner_cfg* cfg);
 int av_planner_dims(const av_ctx* ctx, int* n_points, int* n_candidates);   /* host out */
 /* One plan() per start state.  n_states = S*W.
@@ -479,6 +480,10 @@ int av_hot_step(av_ctx* ctx, av_stream_t stream, const av_tracker_cfg* tracker_c
                 double* det_conf, int32_t* det_status, void* tracker_state, av_track_row* snap, int32_t* snap_n, int32_t* det2trk,
                 const double* z, double* kf_state, double* vstate, double* plan_state, double* waypoints, double* cost,
                 int32_t* order, void* wire, int stream0, int frame0);
+/* AV_OK when the one-launch step can run n_streams streams with the planner configured now and `depth` launches in flight (1 for
+ * av_hot_step, D for av_hot_step_seq); AV_EINVAL where it cannot (the planner's per-wave tiles do not fit the LDS even with eight
+ * waves per workgroup, e.g. 126 waypoints at 21 candidates), and the caller keeps the four stage calls. */
+int av_hot_step_fits(av_ctx* ctx, int n_streams, int dcap, int tcap, int depth);
 
 /* Consecutive time-steps OVERLAPPED (still one launch per step, same results bit for bit).  The reference's loop runs frame t + 1
  * after frame t (demo.py:97-120); what frame t + 1 needs of frame t is the stream's tracker table (tracker role) and its filter

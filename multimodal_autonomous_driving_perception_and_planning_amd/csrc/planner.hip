@@ -97,7 +97,9 @@ __device__ __forceinline__ void wave_lds_fence() {
 //            back were 6 of the kernel's 14 us for one start state)
 //   phase 2  each wave takes whole trajectories; lane = waypoint (positions, tangent heading by atan2_fast, curvature, cost terms;
 //            AoS image assembled in a per-wave LDS tile and streamed out as 16-byte-per-lane stores); per-trajectory sums by DPP
-//   phase 3  costs assembled in the reference's order of accumulation, stable rank of the C costs (== Python's stable sort, :300)
+//   phase 3  costs assembled from the per-trajectory sums as ([reference path] + velocity + acceleration) + curvature + obstacles.
+//            The reference adds every per-waypoint term into one running sum (:224-259), so the two agree to rounding, not bit
+//            for bit (nor do the headings: atan2_fast vs libm); then the stable rank of the C costs (== Python's stable sort, :300)
 template <int G, int NW>
 __device__ __forceinline__ void plan_block(const PlanParams& p, int f0, int n_states, const double* __restrict__ state,
                                            const double* __restrict__ ref, int n_ref, const double* __restrict__ obs, int n_obs,
@@ -113,7 +115,7 @@ __device__ __forceinline__ void plan_block(const PlanParams& p, int f0, int n_st
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     double* stage = stage_all + (size_t)wid * n * 6;
     constexpr int P = G * 3;                           // (state, speed) pairs
-    static_assert(P <= NW || NW == 4, "one wave per pair keeps the cost terms in its registers");
+    static_assert(NW >= 2, "the heading terms take the last wave");   // (fast, P <= NW: one wave per pair keeps its terms in registers)
 
     auto bcast = [&](double x, int i) {
         const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)__double_as_longlong(x), i);
@@ -808,9 +810,12 @@ int av_planner_plan(av_ctx* ctx, av_stream_t stream, int n_states, const double*
         }
     }
     int G = n_states >= 4096 ? 8 : (n_states >= 1024 ? 4 : (n_states >= 512 ? 2 : 1));
-    const int NW = G == 1 ? 8 : 4;                      // one state per workgroup: its 3 C trajectories over eight waves
-    while (G > 1 && plan_lds_doubles(G, n, C, NW) * 8 > 48 * 1024) G >>= 1;
-    const size_t lds = plan_lds_doubles(G, n, C, G == 1 ? 8 : 4) * 8;
+    while (G > 1 && plan_lds_doubles(G, n, C, 4) * 8 > 48 * 1024) G >>= 1;
+    // one state per workgroup: its 3 C trajectories over eight waves, or four / two where eight per-wave tiles do not fit
+    // (two fit every configuration av_planner_configure accepts: n = 256, C = 192 needs 41.6 KB)
+    int NW = G == 1 ? 8 : 4;
+    while (G == 1 && NW > 2 && plan_lds_doubles(1, n, C, NW) * 8 > 64 * 1024) NW >>= 1;
+    const size_t lds = plan_lds_doubles(G, n, C, NW) * 8;
     AV_REQUIRE(lds <= 64 * 1024, AV_EINVAL, "av_planner_plan: configuration needs %zu B of LDS", lds);
     const int grid = (n_states + G - 1) / G;
 #define AV_PLAN_LAUNCH(GG, NWV)                                                                                        \
@@ -820,7 +825,11 @@ int av_planner_plan(av_ctx* ctx, av_stream_t stream, int n_states, const double*
         case 8: AV_PLAN_LAUNCH(8, 4); break;
         case 4: AV_PLAN_LAUNCH(4, 4); break;
         case 2: AV_PLAN_LAUNCH(2, 4); break;
-        default: AV_PLAN_LAUNCH(1, 8); break;
+        default:
+            if (NW == 8) AV_PLAN_LAUNCH(1, 8);
+            else if (NW == 4) AV_PLAN_LAUNCH(1, 4);
+            else AV_PLAN_LAUNCH(1, 2);
+            break;
     }
 #undef AV_PLAN_LAUNCH
     AV_LAUNCH_CHECK();

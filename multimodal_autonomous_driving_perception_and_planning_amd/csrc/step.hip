@@ -256,6 +256,60 @@ __global__ void __launch_bounds__(PW * 64) hot_step_kernel(StepArgs a) {
 
 }  // namespace
 
+// dynamic LDS of the tracker role: av_tracker_update's layout for one staged frame (eight replicas), then the copy of the stream's
+// header and rows the tracker role runs on, from byte stage_off on
+static size_t hot_step_tracker_lds(int dcap, int tcap, int& stage_off) {
+    const int fc = 1;
+    const size_t chunk_bytes = (size_t)((fc + 3) & ~3) * 4 + (size_t)fc * dcap * 16 + (((size_t)fc * dcap + 1) & ~size_t(1)) * 4 +
+                               (size_t)fc * dcap * 16 + 16;
+    const size_t rep_bytes = ((sizeof(Shared) + 63) & ~size_t(63)) + (size_t)tcap * sizeof(av_track_row);
+    size_t lds_t = rep_bytes * STEP_NW + chunk_bytes + 2 * 576;
+    lds_t = (lds_t + 15) & ~size_t(15);
+    stage_off = (int)lds_t;
+    return lds_t + HDR_INTS * 4 + (size_t)tcap * sizeof(av_track_row);
+}
+
+static size_t hot_step_static_lds(const void* kernel) {
+    hipFuncAttributes fa{};
+    return hipFuncGetAttributes(&fa, kernel) == hipSuccess ? (size_t)fa.sharedSizeBytes : (size_t)16384;
+}
+
+// dynamic LDS (the larger of the tracker role's and the planner's) and waves per workgroup of the one-launch step; AV_EINVAL where
+// neither sixteen nor eight waves fit
+static int hot_step_shape(const av_ctx* ctx, int n_streams, size_t lds_t, int depth, size_t& lds_out, int& pw_out) {
+    // Waves per workgroup: sixteen (the planner's 21 trajectories in two rounds) unless the planner's sixteen per-wave tiles do not fit
+    // the LDS (n > 66 at 21 candidates) or that many launches in flight would not all be resident -- every one of them may be waiting
+    // for the one before it, so `depth` launches of 2 S workgroups must fit on the device together -- in which case eight (three
+    // rounds, twice the workgroups per CU).  AVHOT_STEP_PW=8|16 forces one.
+    // static __shared__ of the kernel (the Kalman bodies' arrays) counts against the same 64 KB
+    static const size_t lds_static16 = hot_step_static_lds(reinterpret_cast<const void*>(hot_step_kernel<16>));
+    static const size_t lds_static8 = hot_step_static_lds(reinterpret_cast<const void*>(hot_step_kernel<8>));
+    const char* pwe = getenv("AVHOT_STEP_PW");
+    int pw = pwe && atoi(pwe) == 8 ? 8 : 16;
+    size_t lds = 0;
+    for (;;) {
+        const size_t lds_p = plan_lds_doubles(1, ctx->n_points, ctx->n_cand, pw) * 8;
+        lds = lds_t > lds_p ? lds_t : lds_p;
+        const size_t lds_static = pw == 16 ? lds_static16 : lds_static8;
+        if (lds + lds_static > 64 * 1024) {
+            AV_REQUIRE(pw == 16 && !pwe, AV_EINVAL,
+                       "av_hot_step: configuration needs %zu B of dynamic + %zu B of static LDS (limit 65536)", lds, lds_static);
+            pw = 8;
+            continue;
+        }
+        if (depth <= 1) break;
+        int per_cu = 0;
+        if (pw == 16) AV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hot_step_kernel<16>, 16 * 64, lds));
+        else AV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hot_step_kernel<8>, 8 * 64, lds));
+        if ((long long)depth * 2 * n_streams <= (long long)per_cu * ctx->n_cus) break;
+        AV_REQUIRE(pw == 16 && !pwe, AV_EINVAL, "av_hot_step: %d launches of %d workgroups in flight do not fit the device (%d per CU x %d CUs)",
+                   depth, 2 * n_streams, per_cu, ctx->n_cus);
+        pw = 8;
+    }
+    lds_out = lds, pw_out = pw;
+    return AV_OK;
+}
+
 // validates one step's arguments and fills its kernel arguments (lds: dynamic LDS bytes, pw: waves per workgroup)
 static int hot_step_args(av_ctx* ctx, const av_tracker_cfg* tcfg, const av_kf_cfg* kcfg, int n_streams, int h,
                            int w, int dcap, int tcap, int32_t* frame_count, int32_t* det_n, int32_t* det_box, int32_t* det_cls,
@@ -289,42 +343,10 @@ static int hot_step_args(av_ctx* ctx, const av_tracker_cfg* tcfg, const av_kf_cf
     a.spin = spe ? atoi(spe) : (1 << 22);
     const char* fe = seq_flags ? getenv("AVHOT_STEP_FENCE") : nullptr;
     a.fence = fe ? atoi(fe) : 0;     // (debug: 1 = full agent-scope acquire in every role, the form the comment above prices)
-    // dynamic LDS: the larger of the tracker's (av_tracker_update's layout for one staged frame, eight replicas) and the planner's
-    const int fc = 1;
-    const size_t chunk_bytes = (size_t)((fc + 3) & ~3) * 4 + (size_t)fc * dcap * 16 + (((size_t)fc * dcap + 1) & ~size_t(1)) * 4 +
-                               (size_t)fc * dcap * 16 + 16;
-    const size_t rep_bytes = ((sizeof(Shared) + 63) & ~size_t(63)) + (size_t)tcap * sizeof(av_track_row);
-    size_t lds_t = rep_bytes * STEP_NW + chunk_bytes + 2 * 576;
-    lds_t = (lds_t + 15) & ~size_t(15);      // + the copy of the stream's header and rows the tracker role runs on
-    a.stage_off = (int)lds_t;
-    lds_t += HDR_INTS * 4 + (size_t)tcap * sizeof(av_track_row);
-    // Waves per workgroup: sixteen (the planner's 21 trajectories in two rounds) unless that many launches in flight would not all be
-    // resident -- every one of them may be waiting for the one before it, so `depth` launches of 2 S workgroups must fit on the
-    // device together -- in which case eight (three rounds, twice the workgroups per CU).  AVHOT_STEP_PW=8|16 forces one.
-    const char* pwe = getenv("AVHOT_STEP_PW");
-    int pw = pwe && atoi(pwe) == 8 ? 8 : 16;
-    size_t lds = 0;
-    for (;;) {
-        const size_t lds_p = plan_lds_doubles(1, ctx->n_points, ctx->n_cand, pw) * 8;
-        lds = lds_t > lds_p ? lds_t : lds_p;
-        if (depth <= 1) break;
-        int per_cu = 0;
-        if (pw == 16) AV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hot_step_kernel<16>, 16 * 64, lds));
-        else AV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hot_step_kernel<8>, 8 * 64, lds));
-        if ((long long)depth * 2 * n_streams <= (long long)per_cu * ctx->n_cus) break;
-        AV_REQUIRE(pw == 16 && !pwe, AV_EINVAL, "av_hot_step: %d launches of %d workgroups in flight do not fit the device (%d per CU x %d CUs)",
-                   depth, 2 * n_streams, per_cu, ctx->n_cus);
-        pw = 8;
-    }
-    // static __shared__ of the kernel (the Kalman bodies' arrays) counts against the same 64 KB
-    static const size_t lds_static = [] {
-        hipFuncAttributes fa{};
-        return hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(hot_step_kernel<16>)) == hipSuccess ? (size_t)fa.sharedSizeBytes : (size_t)16384;
-    }();
-    AV_REQUIRE(lds + lds_static <= 64 * 1024, AV_EINVAL, "av_hot_step: configuration needs %zu B of dynamic + %zu B of static LDS (limit 65536)",
-               lds, lds_static);
-    lds_out = lds, pw_out = pw;
-    return AV_OK;
+    int stage_off = 0;
+    const size_t lds_t = hot_step_tracker_lds(dcap, tcap, stage_off);
+    a.stage_off = stage_off;
+    return hot_step_shape(ctx, n_streams, lds_t, depth, lds_out, pw_out);
 }
 
 static int hot_step_go(const StepArgs& a, size_t lds, int pw, av_stream_t stream) {
@@ -347,6 +369,17 @@ static int hot_step_launch(av_ctx* ctx, av_stream_t stream, const av_tracker_cfg
                                  tracker_state, snap, snap_n, det2trk, z, kf_state, vstate, plan_state, waypoints, cost, order, wire, stream0,
                                  frame0, seq_flags, seq, a, lds, pw, depth);
     return rc != AV_OK ? rc : hot_step_go(a, lds, pw, stream);
+}
+
+extern "C" int av_hot_step_fits(av_ctx* ctx, int n_streams, int dcap, int tcap, int depth) {
+    AV_REQUIRE(ctx && n_streams > 0 && depth >= 1, AV_EINVAL, "av_hot_step_fits: bad argument");
+    AV_REQUIRE(ctx->planner_ready, AV_ESTATE, "av_hot_step_fits: call av_planner_configure first");
+    AV_REQUIRE(tcap == 64 && dcap >= 7 && dcap <= 8, AV_EINVAL, "av_hot_step_fits: needs tcap 64, dcap 7..8");
+    AV_HIP(hipSetDevice(ctx->device));
+    int stage_off = 0;
+    size_t lds = 0;
+    int pw = 0;
+    return hot_step_shape(ctx, n_streams, hot_step_tracker_lds(dcap, tcap, stage_off), depth, lds, pw);
 }
 
 extern "C" int av_hot_step(av_ctx* ctx, av_stream_t stream, const av_tracker_cfg* tcfg, const av_kf_cfg* kcfg, int n_streams, int h,

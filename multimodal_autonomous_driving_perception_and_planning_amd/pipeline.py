@@ -24,7 +24,8 @@ class HotLoop:
                  ctx=None, fused_step=None, overlap=1):
         """fused_step: with window 1, run a time-step as ONE launch (av_hot_step: role-split workgroups running the stage
         kernels' own device code, same results bit for bit) instead of the four stage launches.  None = whenever the
-        configuration allows it (window 1, tcap 64, dcap 7..8, iou_threshold > 0).
+        configuration allows it (window 1, tcap 64, dcap 7..8, iou_threshold > 0, and planner settings whose tiles fit the
+        step's LDS: av_hot_step_fits); True where it does not raises ValueError.
         overlap=2 (fused step only): consecutive steps are launched alternately on two HIP streams and ordered per stream and
         role on the device (av_hot_step_seq), so step t + 1 starts while step t's planner is still writing.  The per-step
         buffers (det_*, snap, snap_n, det2trk, z, vstate, plan_state, wp, cost, order) then exist twice; the attributes always
@@ -80,6 +81,14 @@ class HotLoop:
         can_fuse = window == 1 and tcap == 64 and 7 <= dcap <= 8 and self.tcfg.iou_threshold > 0
         if fused_step and not can_fuse:
             raise ValueError("fused_step needs window 1, tcap 64, dcap 7..8 and iou_threshold > 0")
+        if can_fuse and fused_step is not False:
+            # the planner's settings decide whether its tiles fit the one-launch step's LDS: decided here, not at the first step()
+            # (whether overlap=D launches are all resident is the trial step's question below)
+            rc = self.L.av_hot_step_fits(self.ctx.handle, S, dcap, tcap, 1)
+            if rc != 0:
+                if fused_step:
+                    raise ValueError("fused_step: %s" % self.L.av_last_error_string().decode())
+                can_fuse = False
         self.fused_step = can_fuse if fused_step is None else bool(fused_step)
         self.wire = None                  # set_wire(): the fused step also writes every stream's table in wire format
         self._wire_ids = (0, 0)

@@ -1,21 +1,46 @@
 import numpy as np
 
 
-def orders_equivalent(cost_ref, order_ref, order_got, rtol=1e-9):
-    """Two stable ascending orders agree up to permutations inside groups of (near-)equal cost.
+def order_mismatch(cost_ref, order_ref, cost_got, order_got, rtol=1e-9):
+    """Why a device ranking (cost_got, order_got) is not the oracle's (cost_ref, order_ref), or None when it is.
 
-    Exact ties must keep generation order; near-ties (|dc| <= rtol*|c|) may swap because they are decided
-    by the last bits of exp/sin/cos/atan2, which differ between libm/SVML and the device math library.
+    Both orders are stable ascending sorts, order[r] = generation index of the r-th cheapest candidate.
+      - candidates whose ORACLE costs are bit-equal (an exact tie) and whose DEVICE costs are bit-equal too must keep generation
+        order in the device's ranking;
+      - inside an exact oracle tie the device costs may differ only by a near-tie, |dc| <= rtol * |c|: the device's headings
+        come from a polynomial atan2 within 2 ulp of libm's, and mirrored candidates that tie exactly through libm's roundings
+        can come out an ulp apart (the device then ranks them by its own costs);
+      - two candidates may swap places only when their oracle costs are a near-tie, 0 < |dc| <= rtol * |c|, or an exact tie
+        the device split as above.
     """
-    order_ref = np.asarray(order_ref)
-    order_got = np.asarray(order_got)
-    if np.array_equal(order_ref, order_got):
-        return True
-    if sorted(order_ref.tolist()) != sorted(order_got.tolist()):
-        return False
-    cr = np.asarray(cost_ref)[order_ref]
-    cg = np.asarray(cost_ref)[order_got]
-    return bool(np.allclose(cr, cg, rtol=rtol, atol=1e-12))
+    cost_ref, cost_got = np.asarray(cost_ref, np.float64), np.asarray(cost_got, np.float64)
+    order_ref, order_got = np.asarray(order_ref), np.asarray(order_got)
+    C = len(cost_ref)
+    if sorted(order_got.tolist()) != list(range(C)):
+        return "device order is not a permutation of 0..%d" % (C - 1)
+    near = lambda a, b: np.abs(a - b) <= rtol * np.maximum(np.abs(a), np.abs(b))
+    srt = np.sort(cost_ref, kind="stable")
+    for v in np.unique(srt[:-1][srt[1:] == srt[:-1]]):
+        grp = np.nonzero(cost_ref == v)[0]
+        cg = cost_got[grp]
+        if not near(cg.min(), cg.max()):
+            return "oracle tie %s has device costs %s" % (grp.tolist(), cg.tolist())
+    pos_ref, pos_got = np.empty(C, np.int64), np.empty(C, np.int64)
+    pos_ref[order_ref], pos_got[order_got] = np.arange(C), np.arange(C)
+    i, j = np.nonzero((pos_ref[:, None] < pos_ref[None, :]) & (pos_got[:, None] > pos_got[None, :]))   # swapped pairs
+    tie = cost_ref[i] == cost_ref[j]
+    bad = np.where(tie, cost_got[i] == cost_got[j], ~near(cost_ref[i], cost_ref[j]))
+    if bad.any():
+        k = int(np.nonzero(bad)[0][0])
+        return "candidates %d and %d swapped (oracle costs %r, %r; device costs %r, %r)" % (
+            i[k], j[k], cost_ref[i[k]], cost_ref[j[k]], cost_got[i[k]], cost_got[j[k]])
+    return None
+
+
+def orders_equivalent(cost_ref, order_ref, cost_got, order_got, rtol=1e-9):
+    """order_mismatch(...) is None: exact ties in generation order unless the device split them by a near-tie, only near-ties
+    swapped."""
+    return order_mismatch(cost_ref, order_ref, cost_got, order_got, rtol) is None
 
 
 def match_detections(got_box, got_cls, want_box, want_cls, px=1.0):

@@ -57,7 +57,7 @@ def _check_window(r, rows, n, want, f0, W, where):
         np.testing.assert_allclose(r["vstate"][s], w["state"][sl], rtol=1e-9, atol=1e-9, err_msg="%s stream %d" % (where, s))
         np.testing.assert_allclose(r["cost"][s], w["cost"][sl], rtol=1e-9, err_msg="%s stream %d" % (where, s))
         for f in range(W):
-            assert orders_equivalent(w["cost"][f0 + f], w["order"][f0 + f], r["order"][s, f]), (where, s, f)
+            assert orders_equivalent(w["cost"][f0 + f], w["order"][f0 + f], r["cost"][s, f], r["order"][s, f]), (where, s, f)
             np.testing.assert_allclose(r["wp"][s, f, r["order"][s, f, 0]], w["best_wp"][f0 + f], rtol=1e-9, atol=1e-9)
 
 
@@ -377,7 +377,7 @@ def test_overlapped_loop_headline_size_against_the_oracle_and_its_bucketed_gathe
                 for s in range(0, S, 7):
                     np.testing.assert_allclose(r["vstate"][s, 0], want[s]["state"][T - 1], rtol=1e-9, atol=1e-9, err_msg="%s %d" % (mode, s))
                     np.testing.assert_allclose(r["cost"][s, 0], want[s]["cost"][T - 1], rtol=1e-9, err_msg="%s %d" % (mode, s))
-                    assert orders_equivalent(want[s]["cost"][T - 1], want[s]["order"][T - 1], r["order"][s, 0]), (mode, s)
+                    assert orders_equivalent(want[s]["cost"][T - 1], want[s]["order"][T - 1], r["cost"][s, 0], r["order"][s, 0]), (mode, s)
             finally:
                 x.close()
     finally:

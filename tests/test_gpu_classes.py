@@ -2,7 +2,7 @@
 import numpy as np
 import pytest
 
-from tests._util import orders_equivalent
+from tests._util import order_mismatch
 
 pytestmark = pytest.mark.gpu
 
@@ -125,21 +125,36 @@ def test_vehicle_state_estimator(api):
         est.update([1.0, 2.0])
 
 
+_TYPE_NAMES = {0: "lane_keep", 1: "lane_change_left", 2: "lane_change_right"}
+
+
+def _check_ranked(cands, want_cost, want_order, want_wp, want_types, where):
+    """plan()'s ranked candidates against the reference's plan: the ranking with the strict tie rule (tests/_util.order_mismatch),
+    then the cost, trajectory_type and waypoints of the candidate at every rank."""
+    got_wp = np.array([t._arr for t in cands])
+    gen = [int(np.argmin(np.abs(want_wp - w).reshape(len(want_wp), -1).max(axis=1))) for w in got_wp]   # generation index
+    assert sorted(gen) == list(range(len(want_wp))), where
+    got_cost = np.empty(len(gen))
+    got_cost[gen] = [t.cost for t in cands]
+    why = order_mismatch(want_cost, want_order, got_cost, gen)
+    assert why is None, "%s: %s" % (where, why)
+    for r, t in enumerate(cands):
+        c = gen[r]
+        assert t.cost == pytest.approx(want_cost[c], rel=1e-12, abs=1e-12), (where, r)
+        assert t.trajectory_type == _TYPE_NAMES[int(want_types[c])], (where, r)
+        np.testing.assert_allclose(t._arr, want_wp[c], rtol=1e-12, atol=1e-11, err_msg="%s rank %d" % (where, r))
+
+
 def test_motion_planner(api, golden):
+    from oracle.planner_ref import PlannerRef
     PL = api[3]
     g = golden("planner")
     p = PL.MotionPlanner()
-    for s in (0, 2, 5):
+    ref = PlannerRef()
+    for s in range(8):
         opt, cands = p.plan(tuple(g["states"][s]))
         assert len(cands) == 21 and opt is cands[0] and len(opt.waypoints) == 51
-        costs = np.array([t.cost for t in cands])
-        assert np.all(np.diff(costs) >= 0)
-        np.testing.assert_allclose(np.sort(costs), np.sort(g["cost"][s]), rtol=1e-12)
-        names = {0: "lane_keep", 1: "lane_change_left", 2: "lane_change_right"}
-        gen_types = [names[t] for t in g["types"][s]]
-        assert sorted(t.trajectory_type for t in cands) == sorted(gen_types)
-        w = np.array([[q.x, q.y, q.heading, q.velocity, q.timestamp, q.curvature] for q in opt.waypoints])
-        np.testing.assert_allclose(w, g["wp_first8"][s][g["order"][s][0]], rtol=1e-12, atol=1e-11)
+        _check_ranked(cands, g["cost"][s], g["order"][s], g["wp_first8"][s], g["types"][s], "default state %d" % s)
         assert opt.length == pytest.approx(g["length"][s][g["order"][s][0]], rel=1e-12)
         assert opt.duration == pytest.approx(5.0)
         assert cands[1] != opt and opt == opt
@@ -149,21 +164,29 @@ def test_motion_planner(api, golden):
     np.testing.assert_allclose(w, g["wp_first8"][2][0], rtol=1e-12, atol=1e-11)
     assert p.evaluate_trajectory_cost(t) == pytest.approx(g["cost"][2][0], rel=1e-12)
     assert p.evaluate_trajectory_cost(PL.Trajectory(waypoints=[])) == float("inf")
-    # reference path + obstacles
+    # reference path and / or obstacles: all 12 golden states of each (waypoints from the oracle, bit-exact with the reference)
     obs = [tuple(o) for o in g["obstacles"]]
-    p.set_reference_path([tuple(r) for r in g["ref_path"]])
-    np.testing.assert_allclose([w.heading for w in p.reference_trajectory.waypoints], g["ref_heading"], rtol=1e-14)
-    for s in range(4):
-        opt, cands = p.plan(tuple(g["states"][s]), obs)
-        np.testing.assert_allclose(sorted(t.cost for t in cands), np.sort(g["cost_refobs"][s]), rtol=1e-12)
-        assert p.evaluate_trajectory_cost(cands[3], obs) == pytest.approx(cands[3].cost, rel=1e-12)
+    for tag, use_ref, use_obs in (("ref", True, False), ("obs", False, True), ("refobs", True, True)):
+        p.reset()
+        if use_ref:
+            p.set_reference_path([tuple(r) for r in g["ref_path"]])
+            np.testing.assert_allclose([w.heading for w in p.reference_trajectory.waypoints], g["ref_heading"], rtol=1e-14)
+        for s in range(12):
+            opt, cands = p.plan(tuple(g["states"][s]), obs if use_obs else None)
+            _check_ranked(cands, g["cost_" + tag][s], g["order_" + tag][s], ref.plan(g["states"][s])["wp"], g["types"][s],
+                          "%s state %d" % (tag, s))
+            if use_obs:
+                assert p.evaluate_trajectory_cost(cands[3], obs) == pytest.approx(cands[3].cost, rel=1e-12)
     p.reset()
     assert p.reference_trajectory is None
-    # non-default construction
+    # non-default construction: all 6 golden states
     q = PL.MotionPlanner(planning_horizon=3.0, dt=0.2, num_samples=5)
-    opt, cands = q.plan(tuple(g["states"][1]))
-    assert len(cands) == 15 and len(opt.waypoints) == 16
-    np.testing.assert_allclose(sorted(t.cost for t in cands), np.sort(g["alt_cost"][1]), rtol=1e-12)
+    alt = PlannerRef(planning_horizon=3.0, dt=0.2, num_samples=5)
+    for s in range(6):
+        opt, cands = q.plan(tuple(g["states"][s]))
+        assert len(cands) == 15 and len(opt.waypoints) == 16
+        _check_ranked(cands, g["alt_cost"][s], g["alt_order"][s], g["alt_wp"][s], alt.plan(g["states"][s])["types"],
+                      "alt state %d" % s)
     # the first planner still works after another configuration used the shared context
     opt, _ = p.plan(tuple(g["states"][0]))
     assert len(opt.waypoints) == 51

@@ -139,7 +139,7 @@ def test_planner_matches_reference_goldens(hot, golden):
     np.testing.assert_allclose(wp[:8], g["wp_first8"], rtol=1e-12, atol=1e-11)
     np.testing.assert_allclose(wp.sum(axis=(1, 2)), g["wp_checksum"], rtol=1e-12, atol=1e-9)
     for s in range(S):
-        assert orders_equivalent(g["cost"][s], g["order"][s], order[s]), s
+        assert orders_equivalent(g["cost"][s], g["order"][s], cost[s], order[s]), s
         assert np.all(np.diff(cost[s][order[s]]) >= 0)
     # exact +/- symmetric ties keep generation order (state 0 has heading 0)
     assert cost[0][0] == cost[0][18] and list(order[0]).index(0) < list(order[0]).index(18)
@@ -171,6 +171,6 @@ def test_full_loop_matches_cpu_oracle(hot):
             np.testing.assert_allclose(r["vstate"][s], ws["state"][sl], rtol=1e-9, atol=1e-9)
             np.testing.assert_allclose(r["cost"][s], ws["cost"][sl], rtol=1e-9)
             for f in range(W):
-                assert orders_equivalent(ws["cost"][k * W + f], ws["order"][k * W + f], r["order"][s, f])
+                assert orders_equivalent(ws["cost"][k * W + f], ws["order"][k * W + f], r["cost"][s, f], r["order"][s, f])
                 best = ws["order"][k * W + f][0]          # the oracle's optimal candidate
                 np.testing.assert_allclose(r["wp"][s, f, best], ws["best_wp"][k * W + f], rtol=1e-9, atol=1e-8)
