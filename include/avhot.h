@@ -286,7 +286,9 @@ int av_lane_workspace_view(int what, int n_streams, int h, int w, int max_segmen
  *              (no Hough, no fit); bit4: skip the pixel stages and run Hough + fit on what the last bit1 call left
  *              in the workspace -- the two halves of a frame can then be enqueued apart, e.g. the Hough half beside
  *              the next frame's LDS-free kernels (it holds most of a CU's LDS); bit5 (with bit4): fit only, on the
- *              segment list already in the workspace (views 5 / 6) -- a test hook for the least-squares stage */
+ *              segment list already in the workspace (views 5 / 6) -- a test hook for the least-squares stage; bit6: Canny of
+ *              the u8 image the caller left in view 0 (no gray / blur / median) with the thresholds it left in view 4
+ *              (lo, hi as doubles), then the ROI and compaction as usual (the scene stage: full-frame roi_rows) */
 int av_lane_detect(av_ctx* ctx, av_stream_t stream, const av_lane_cfg* cfg, int n_streams, int h, int w,
                    const uint8_t* bgr, const int32_t* roi_rows, void* workspace, double* lane_state,
                    double* poly, int32_t* pts, int32_t* info, double* conf, int stages);
@@ -336,6 +338,67 @@ int av_yolo_keep_logits(av_yolo* h, int enable);
  * anchor as the head wrote them: box float32 [A][4], confidence float32 [A], class int32 [A]; 120-122 = the same from the
  * stand-alone decode of the kept logits). */
 int av_yolo_tensor(const av_yolo* h, int id, void** ptr, int* H, int* W, int* C, int* cstride, int* coff);
+
+/* ---- T3: scene classifier (road type, conditions, lane count) -------------------------------------------
+ * Replaces SceneClassifier.classify and its helpers (src/tagging/scene_classifier.py:76-303): BGR2GRAY, Canny(50, 150)
+ * and HoughLinesP(1, pi/180, 100, minLineLength=100, maxLineGap=10) on the whole frame, the BGR2HSV green mask
+ * inRange((35,40,40), (85,255,255)), np.mean(gray), Laplacian(ksize=1, BORDER_REFLECT_101).var(), the road-type scores
+ * and decision rules (:128-202), conditions (:231-259), lane count (:261-280) and the 5-deep road-type vote (:282-298).
+ * Per call and stream: scene_front (one read of the frame: gray into the lane workspace, integer pixel sums), the lane
+ * chain's Canny with stages bit 6 on the full-frame ROI, the centre edge count on its point list, the lane chain's
+ * PPHT, scene_decide.  Enum indices below follow the reference's definition order:
+ *   road type  0 unknown 1 intersection 2 highway 3 urban 4 residential 5 parking
+ *   condition  0 clear 1 congested 2 night 3 day 4 rain 5 fog */
+#define AV_SCENE_STATE_BYTES 64            /* per stream: frame_count, history length, road types of the last 5 frames */
+#define AV_SCENE_CAT_TRAFFIC 1             /* category bits of av_scene_classify's per-class table */
+#define AV_SCENE_CAT_VEHICLE 2
+#define AV_SCENE_CAT_PEDESTRIAN 4
+typedef struct av_scene_row {
+    uint64_t gray_sum;                     /* sum of the gray image                     */
+    uint64_t green_count;                  /* pixels inside the HSV green range         */
+    int64_t lap_sum;                       /* sum and sum of squares of the Laplacian   */
+    uint64_t lap_sumsq;
+    int32_t center_count;                  /* edge pixels in [h/3, 2h/3) x [w/3, 2w/3)  */
+    int32_t n_lines;                       /* len(lines) (at most max_segments)         */
+    double avg_length;                     /* np.mean of the line lengths (0 without lines) */
+    double mean, green_ratio, center_density, lap_var;
+    double scores[6];                      /* normalised road-type scores               */
+    int32_t road_type_raw;                 /* this frame's decision before the vote      */
+    int32_t road_type;                     /* after the vote                             */
+    double confidence;
+    int32_t n_conditions;
+    int32_t conditions[3];
+    double condition_conf[3];
+    int32_t lane_count;
+    int32_t has_pedestrian;
+    int32_t n_traffic;                     /* detections of a traffic class (traffic_light / stop_sign) */
+    int32_t overflow;                      /* 1: the segment list filled up; the line statistics may be short */
+    double timestamp;                      /* frame_count / 30.0                         */
+    int32_t frame_count;
+    int32_t history_len;
+    int32_t history[5];                    /* the vote's history after this frame, oldest first */
+    int32_t reserved;
+} av_scene_row;                            /* 240 bytes */
+size_t av_scene_state_bytes(int n_streams);
+int av_scene_reset(av_ctx* ctx, av_stream_t stream, int n_streams, void* state);
+/* Scratch of one scene stage: its own lane workspace (views of av_lane_workspace_view with the same S, h, w, max_segments),
+ * the pixel sums and the lane outputs it does not use.  av_scene_workspace_init zero-fills it (required before first use). */
+size_t av_scene_workspace_bytes(int n_streams, int h, int w, int max_segments);
+int av_scene_workspace_init(av_ctx* ctx, av_stream_t stream, int n_streams, int h, int w, int max_segments, void* workspace);
+/*   bgr         u8 [S][h][w][3]
+ *   max_segments  capacity of the per-frame segment list (OpenCV has none; a full list sets row.overflow)
+ *   det_n       int32 [S] (0: detections empty or None); det_cls int32 [S][max_det]; cat u8 [n_cat] AV_SCENE_CAT_* bits per
+ *               class id (ids outside the table: no category).  det_n may be NULL (no detections).
+ *   speed       f64 [S] ego speed, NaN = no vehicle_state; NULL = none for every stream
+ *   lanes       f64 [S][4] {mode, left_x, right_x, 0}: mode 0 = lanes falsy, 1 = a lane is None, 2 = both present with the
+ *               lanes' x at the bottom row; ignored when lane_info is given
+ *   lane_info, lane_poly   the lane detector's info [S][8] / poly [S][2][3] (av_lane_detect): mode 2 when both sides are
+ *               valid, else 1; x = (c2 h + c1) h + c0.  May be NULL.
+ *   state       av_scene_state_bytes(S), advanced in place;  rows  av_scene_row [S] */
+int av_scene_classify(av_ctx* ctx, av_stream_t stream, int n_streams, int h, int w, const uint8_t* bgr, void* workspace,
+                      int max_segments, const int32_t* det_n, const int32_t* det_cls, int max_det, const uint8_t* cat, int n_cat,
+                      const double* speed, const double* lanes, const int32_t* lane_info, const double* lane_poly, void* state,
+                      av_scene_row* rows);
 
 /* ---- T1: maneuver tags ------------------------------------------------------
  * Replaces ManeuverDetector.detect (src/tagging/maneuver_detector.py:105-262): lateral / longitudinal /

@@ -55,6 +55,17 @@ INTERACTION_SUMMARY_FIELDS = [("agent_count", "<i4"), ("pedestrian_count", "<i4"
                               ("min_ttc", "<f8"), ("timestamp", "<f8")]
 INTERACTION_SUMMARY_BYTES = 56
 
+SCENE_STATE_BYTES = 64
+SCENE_ROW_FIELDS = [("gray_sum", "<u8"), ("green_count", "<u8"), ("lap_sum", "<i8"), ("lap_sumsq", "<u8"),
+                    ("center_count", "<i4"), ("n_lines", "<i4"), ("avg_length", "<f8"), ("mean", "<f8"), ("green_ratio", "<f8"),
+                    ("center_density", "<f8"), ("lap_var", "<f8"), ("scores", "<f8", (6,)), ("road_type_raw", "<i4"),
+                    ("road_type", "<i4"), ("confidence", "<f8"), ("n_conditions", "<i4"), ("conditions", "<i4", (3,)),
+                    ("condition_conf", "<f8", (3,)), ("lane_count", "<i4"), ("has_pedestrian", "<i4"), ("n_traffic", "<i4"),
+                    ("overflow", "<i4"), ("timestamp", "<f8"), ("frame_count", "<i4"), ("history_len", "<i4"),
+                    ("history", "<i4", (5,)), ("reserved", "<i4")]
+SCENE_ROW_BYTES = 240
+SCENE_CAT_TRAFFIC, SCENE_CAT_VEHICLE, SCENE_CAT_PEDESTRIAN = 1, 2, 4
+
 
 class BevCfg(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("pixels_per_meter", C.c_double), ("x_min", C.c_double),
@@ -147,6 +158,12 @@ _SIGS = [
     ("av_yolo_tensor", C.c_int, [vp, C.c_int, C.POINTER(vp)] + [C.POINTER(C.c_int)] * 5),
     ("av_lane_detect", C.c_int, [vp, vp, C.POINTER(LaneCfg), C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp,
                                  vp, C.c_int]),
+    ("av_scene_state_bytes", C.c_size_t, [C.c_int]),
+    ("av_scene_reset", C.c_int, [vp, vp, C.c_int, vp]),
+    ("av_scene_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("av_scene_workspace_init", C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    ("av_scene_classify", C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp,
+                                    vp, vp, vp, vp]),
 ]
 
 # entry points added by later translation units; bound when present in the header list below

@@ -155,6 +155,15 @@ __global__ void __launch_bounds__(256) thresholds_kernel(int h, int w, unsigned*
     }
 }
 
+// stages bit 6: the caller wrote the u8 image (view 0) and the thresholds (view 4); clears what thresholds_kernel would have
+__global__ void __launch_bounds__(256) given_clear_kernel(int h, unsigned* __restrict__ hist, int* __restrict__ rowcnt,
+                                                          int* __restrict__ npts, int* __restrict__ nseg) {
+    const int s = blockIdx.x, tid = threadIdx.x;
+    hist[(size_t)s * 256 + tid] = 0;
+    for (int i = tid; i < h; i += 256) rowcnt[(size_t)s * h + i] = 0;
+    if (tid == 0) npts[s] = 0, nseg[s] = 0;
+}
+
 // ---- L2b: Sobel + NMS -> map, union-find seeds ----------------------------------------------------------------
 __global__ void __launch_bounds__(256) sobel_nms_kernel(const uint8_t* __restrict__ blur, int h, int w,
                                                         const double* __restrict__ thr, uint8_t* __restrict__ map,
@@ -3011,7 +3020,8 @@ int av_lane_detect(av_ctx* ctx, av_stream_t stream, const av_lane_cfg* cfg, int 
     if (!(stages & 16)) {                                          // bit 4: Hough + fit only, on the point lists already in the workspace
         // fused = one streaming pass BGR -> non-maximum-suppressed magnitudes (thresholds applied by the hysteresis pass);
         // other shapes take the two-pass kernels with the blurred image in memory between them
-        const bool fused = streamp && fastp && !getenv("AVHOT_LANE_TWO_PASS");
+        const bool given = (stages & 64) != 0;                       // bit 6: image and thresholds already in views 0 / 4
+        const bool fused = !given && streamp && fastp && !getenv("AVHOT_LANE_TWO_PASS");
         if (fused) {
             const char* fe = getenv("AVHOT_LANE_FROWS");
             const int fr = fe ? atoi(fe) : 48;                       // front_stream at 720p, 64 frames: 45 rows 122 us, 72 rows 128, 90 rows 123
@@ -3054,11 +3064,15 @@ int av_lane_detect(av_ctx* ctx, av_stream_t stream, const av_lane_cfg* cfg, int 
             AV_LAUNCH_CHECK();
         } else {
             const dim3 sgrid((((w + SW - 1) / SW) * ((h + SROWS - 1) / SROWS) + 3) / 4, 1, n_streams);      // waves = strips x bands
-            if (streamp) hipLaunchKernelGGL(gray_blur_hist_stream, sgrid, dim3(256), 0, st, bgr, h, w, blur, hist);
-            else if (fastp) hipLaunchKernelGGL(gray_blur_hist_fast, tiles, dim3(256), 0, st, bgr, h, w, blur, hist);
-            else hipLaunchKernelGGL(gray_blur_hist_kernel, tiles, dim3(256), 0, st, bgr, h, w, blur, hist);
-            AV_LAUNCH_CHECK();
-            hipLaunchKernelGGL(thresholds_kernel, dim3(n_streams), dim3(256), 0, st, h, w, hist, thr, rowcnt, npts, nseg);
+            if (given) {
+                hipLaunchKernelGGL(given_clear_kernel, dim3(n_streams), dim3(256), 0, st, h, hist, rowcnt, npts, nseg);
+            } else {
+                if (streamp) hipLaunchKernelGGL(gray_blur_hist_stream, sgrid, dim3(256), 0, st, bgr, h, w, blur, hist);
+                else if (fastp) hipLaunchKernelGGL(gray_blur_hist_fast, tiles, dim3(256), 0, st, bgr, h, w, blur, hist);
+                else hipLaunchKernelGGL(gray_blur_hist_kernel, tiles, dim3(256), 0, st, bgr, h, w, blur, hist);
+                AV_LAUNCH_CHECK();
+                hipLaunchKernelGGL(thresholds_kernel, dim3(n_streams), dim3(256), 0, st, h, w, hist, thr, rowcnt, npts, nseg);
+            }
             AV_LAUNCH_CHECK();
             if (streamp) hipLaunchKernelGGL(sobel_nms_stream, sgrid, dim3(256), 0, st, blur, h, w, thr, map, labels);
             else if (fastp) hipLaunchKernelGGL(sobel_nms_fast, tiles, dim3(256), 0, st, blur, h, w, thr, map, labels);

@@ -606,6 +606,45 @@ class PerceptionLoop:
     def synchronize(self):
         self.stream.synchronize()
 
+    def enqueue_scene(self, stream=None, speeds=None, max_segments=4096):
+        """Opt-in scene stage (SceneClassifier.classify for every camera, av_scene_classify) on the frames, detections and
+        lane outputs in HBM: call it after step() (after flush_lanes() in the deferred mode), so that det_* and info / poly
+        describe the current frames.  speeds: ego speed per camera (NaN = no vehicle state), or None for none.  The stage
+        has its own workspace and 5-deep road-type history per camera; rows land in self.scene_rows."""
+        from .tagging.scene_classifier import category_table
+        S, d = self.S, self.dev
+        if getattr(self, "scene_ws", None) is None or self.scene_cap != max_segments:
+            self.scene_cap = int(max_segments)
+            self.scene_ws = torch.empty(int(self.L.av_scene_workspace_bytes(S, self.h, self.w, self.scene_cap)), dtype=torch.uint8,
+                                        device=d)
+            nat.check(self.L.av_scene_workspace_init(self.ctx.handle, self._s, S, self.h, self.w, self.scene_cap,
+                                                     nat.ptr(self.scene_ws)))
+            if getattr(self, "scene_state", None) is None:
+                self.scene_state = torch.zeros(int(self.L.av_scene_state_bytes(S)), dtype=torch.uint8, device=d)
+                self.scene_rows = torch.zeros(S, nat.SCENE_ROW_BYTES, dtype=torch.uint8, device=d)
+                cat = category_table(self.yolo.names)
+                self.scene_cat = torch.as_tensor(cat).to(d)
+                self.scene_speed = torch.full((S,), float("nan"), dtype=torch.float64, device=d)
+        sp = None
+        if speeds is not None:
+            with torch.cuda.stream(self.stream):
+                self.scene_speed.copy_(torch.as_tensor(np.asarray(speeds, np.float64).reshape(S)))
+            sp = nat.ptr(self.scene_speed)
+        nat.check(self.L.av_scene_classify(self.ctx.handle, stream or self._s, S, self.h, self.w, nat.ptr(self.frames),
+                                           nat.ptr(self.scene_ws), self.scene_cap, nat.ptr(self.det_n), nat.ptr(self.det_cls),
+                                           self.max_det, nat.ptr(self.scene_cat), int(self.scene_cat.numel()), sp, None,
+                                           nat.ptr(self.info), nat.ptr(self.poly), nat.ptr(self.scene_state),
+                                           nat.ptr(self.scene_rows)))
+
+    def scene_results(self):
+        """The last enqueue_scene's av_scene_row per camera (structured NumPy array; synchronises)."""
+        self.synchronize()
+        return self.scene_rows.cpu().numpy().view(nat.SCENE_ROW_FIELDS).reshape(self.S)
+
+    def reset_scene(self):
+        if getattr(self, "scene_state", None) is not None:
+            nat.check(self.L.av_scene_reset(self.ctx.handle, self._s, self.S, nat.ptr(self.scene_state)))
+
 
 def _yolo_flops(H, W):
     """2*MACs of the YOLOv8n graph at input H x W (per frame), walking the same layer list as the library."""

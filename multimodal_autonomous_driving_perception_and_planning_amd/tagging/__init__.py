@@ -1,7 +1,11 @@
+from .auto_tagger import AutoTagger, FrameTags, TaggingSession  # noqa: F401
 from .interaction_detector import (Interaction, InteractionDetector, InteractionTags, InteractionType,  # noqa: F401
                                    RiskLevel)
 from .maneuver_detector import (LateralManeuver, LongitudinalManeuver, ManeuverDetector, ManeuverTags,  # noqa: F401
                                 TurningManeuver)
+from .scene_classifier import Condition, RoadType, SceneClassifier, SceneTags, TrafficElement  # noqa: F401
 
 __all__ = ["ManeuverDetector", "ManeuverTags", "LateralManeuver", "LongitudinalManeuver", "TurningManeuver",
-           "InteractionDetector", "InteractionTags", "Interaction", "InteractionType", "RiskLevel"]
+           "InteractionDetector", "InteractionTags", "Interaction", "InteractionType", "RiskLevel",
+           "SceneClassifier", "SceneTags", "RoadType", "TrafficElement", "Condition",
+           "AutoTagger", "FrameTags", "TaggingSession"]
