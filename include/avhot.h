@@ -283,7 +283,8 @@ int av_lane_workspace_view(int what, int n_streams, int h, int w, int max_segmen
  *   info       int32 [S][8]    valid_left valid_right n_left_segments n_right_segments n_segments n_points lo hi
  *   conf       double [S][2]   min(1, n_side_segments / 10)
  *   stages     bit0: also write the pre-ROI Canny edge map (view 2); bit1: stop after the pixel stages
- *              (no Hough, no fit); bit4: skip the pixel stages and run Hough + fit on what the last bit1 call left
+ *              (no Hough, no fit); bit2: reserved, ignored; bit3: Hough by the generic PPHT kernel alone, then the
+ *              fit (no theta-sharded or single-workgroup LDS kernel; the Hough kernels' test hook); bit4: skip the pixel stages and run Hough + fit on what the last bit1 call left
  *              in the workspace -- the two halves of a frame can then be enqueued apart, e.g. the Hough half beside
  *              the next frame's LDS-free kernels (it holds most of a CU's LDS); bit5 (with bit4): fit only, on the
  *              segment list already in the workspace (views 5 / 6) -- a test hook for the least-squares stage; bit6: Canny of

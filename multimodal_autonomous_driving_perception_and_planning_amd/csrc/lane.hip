@@ -323,148 +323,6 @@ __global__ void __launch_bounds__(256) finalize_kernel(const uint8_t* __restrict
     if ((tid & 63) == 0 && cnt) atomicAdd(&rowcnt[(size_t)s * h + y], cnt);
 }
 
-// ===== fast paths (w % 16 == 0, 16-byte aligned frames): every global access is a 16-byte vector ===========
-
-// 16 sub-histograms (lane & 15) cut same-bin LDS-atomic conflicts from 64-way to 4-way on flat image areas.
-__device__ __forceinline__ void hist_add(unsigned* lh16, int lane, int v, unsigned n) {
-    atomicAdd(&lh16[(lane & 15) * 256 + v], n);
-}
-
-__global__ void __launch_bounds__(256) gray_blur_hist_fast(const uint8_t* __restrict__ bgr, int h, int w,
-                                                           uint8_t* __restrict__ blur, unsigned* __restrict__ hist) {
-    constexpr int RAWB = 432;                               // >= (TW + 4) * 3 + 15, multiple of 16
-    __shared__ __attribute__((aligned(16))) uint8_t raw[TH + 4][RAWB];
-    __shared__ uint8_t g[TH + 4][TW + 8];
-    __shared__ unsigned short t[TH + 4][TW];
-    __shared__ unsigned lh[16 * 256];
-    const int s = blockIdx.z, x0 = blockIdx.x * TW, y0 = blockIdx.y * TH, tid = threadIdx.x, lane = tid & 63;
-    const uint8_t* img = bgr + (size_t)s * h * w * 3;
-    for (int i = tid; i < 16 * 256; i += 256) lh[i] = 0;
-    // in-image column range this tile needs, as a 16-byte aligned byte range of the row
-    const int cxa = x0 - 2 < 0 ? 0 : x0 - 2, cxb = x0 + TW + 2 > w ? w : x0 + TW + 2;
-    const int b0 = (cxa * 3) & ~15, b1 = (cxb * 3 + 15) & ~15;          // w*3 % 16 == 0 -> b1 <= row bytes
-    const int nch = (b1 - b0) >> 4;
-    for (int i = tid; i < (TH + 4) * nch; i += 256) {
-        const int r = i / nch, c = i - r * nch;
-        const int yy = reflect101(y0 + r - 2, h);
-        *reinterpret_cast<uint4*>(&raw[r][c * 16]) =
-            *reinterpret_cast<const uint4*>(img + (size_t)yy * w * 3 + b0 + c * 16);
-    }
-    __syncthreads();
-    for (int i = tid; i < (TH + 4) * (TW + 4); i += 256) {
-        const int r = i / (TW + 4), c = i - r * (TW + 4);
-        const int xx = reflect101(x0 + c - 2, w);
-        const uint8_t* p = &raw[r][xx * 3 - b0];
-        g[r][c] = (uint8_t)((1868 * p[0] + 9617 * p[1] + 4899 * p[2] + 8192) >> 14);
-    }
-    __syncthreads();
-    for (int i = tid; i < (TH + 4) * TW; i += 256) {
-        const int r = i / TW, c = i - r * TW;
-        t[r][c] = (unsigned short)(g[r][c] + 4 * g[r][c + 1] + 6 * g[r][c + 2] + 4 * g[r][c + 3] + g[r][c + 4]);
-    }
-    __syncthreads();
-    const int r = tid >> 3, c0 = (tid & 7) * 16;
-    const int y = y0 + r;
-    if (y < h && x0 + c0 < w) {
-        uint8_t o[16];
-        int run_v = -1;
-        unsigned run_n = 0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const int c = c0 + k;
-            const int v = (t[r][c] + 4 * t[r + 1][c] + 6 * t[r + 2][c] + 4 * t[r + 3][c] + t[r + 4][c] + 128) >> 8;
-            o[k] = (uint8_t)v;
-            if (v == run_v) ++run_n;
-            else {
-                if (run_n) hist_add(lh, lane, run_v, run_n);
-                run_v = v, run_n = 1;
-            }
-        }
-        hist_add(lh, lane, run_v, run_n);
-        *reinterpret_cast<uint4*>(blur + ((size_t)s * h + y) * w + x0 + c0) = *reinterpret_cast<const uint4*>(o);
-    }
-    __syncthreads();
-    unsigned tot = 0;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) tot += lh[q * 256 + tid];
-    if (tot) atomicAdd(&hist[(size_t)s * 256 + tid], tot);
-}
-
-__global__ void __launch_bounds__(256) sobel_nms_fast(const uint8_t* __restrict__ blur, int h, int w,
-                                                      const double* __restrict__ thr, uint8_t* __restrict__ map,
-                                                      unsigned* __restrict__ labels) {
-    constexpr int RB = TW + 32;                              // tile row bytes incl. 16-byte aligned halo
-    __shared__ __attribute__((aligned(16))) uint8_t b[TH + 4][RB];
-    __shared__ short gx[TH + 2][TW + 2], gy[TH + 2][TW + 2];
-    __shared__ unsigned short mg[TH + 2][TW + 2];
-    const int s = blockIdx.z, x0 = blockIdx.x * TW, y0 = blockIdx.y * TH, tid = threadIdx.x;
-    const uint8_t* img = blur + (size_t)s * h * w;
-    int lo = (int)thr[(size_t)s * 4], hi = (int)thr[(size_t)s * 4 + 1];
-    if (lo > hi) { const int q = lo; lo = hi; hi = q; }
-    // b[r][16 + c] holds image column x0 + c; chunks x0-16 .. x0+TW+15 (clamped chunks duplicate the border)
-    constexpr int NCH = RB / 16;
-    for (int i = tid; i < (TH + 4) * NCH; i += 256) {
-        const int r = i / NCH, c = i - r * NCH;
-        const int yy = clampi(y0 + r - 2, h);
-        int xs = x0 - 16 + c * 16;
-        xs = xs < 0 ? 0 : (xs > w - 16 ? w - 16 : xs);
-        *reinterpret_cast<uint4*>(&b[r][c * 16]) = *reinterpret_cast<const uint4*>(img + (size_t)yy * w + xs);
-    }
-    __syncthreads();
-    auto px = [&](int r, int xx) -> int {                     // BORDER_REPLICATE column lookup inside the tile
-        const int xc = clampi(xx, w);
-        int off = xc - x0 + 16;
-        if (x0 == 0 && off < 16) off = xc + 16;               // left chunk was clamped to columns 0..15
-        if (x0 + TW >= w && off >= 16 + TW) off = xc - (w - 16) + 16 + TW;   // right chunk clamped to w-16..w-1
-        return b[r][off];
-    };
-    for (int i = tid; i < (TH + 2) * (TW + 2); i += 256) {
-        const int r = i / (TW + 2), c = i - r * (TW + 2);
-        const int yy = y0 + r - 1, xx = x0 + c - 1;
-        const int a00 = px(r, xx - 1), a01 = px(r, xx), a02 = px(r, xx + 1);
-        const int a10 = px(r + 1, xx - 1), a12 = px(r + 1, xx + 1);
-        const int a20 = px(r + 2, xx - 1), a21 = px(r + 2, xx), a22 = px(r + 2, xx + 1);
-        const int dx = (a02 + 2 * a12 + a22) - (a00 + 2 * a10 + a20);
-        const int dy = (a20 + 2 * a21 + a22) - (a00 + 2 * a01 + a02);
-        const bool inside = yy >= 0 && yy < h && xx >= 0 && xx < w;
-        gx[r][c] = (short)dx, gy[r][c] = (short)dy;
-        mg[r][c] = inside ? (unsigned short)(abs(dx) + abs(dy)) : 0;
-    }
-    __syncthreads();
-    const int r = tid >> 3, c0 = (tid & 7) * 16;
-    const int y = y0 + r;
-    if (y >= h || x0 + c0 >= w) return;
-    uint8_t o[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const int c = c0 + k, rr = r + 1, cc = c + 1;
-        const int m = mg[rr][cc];
-        int v = 1;
-        if (m > lo) {
-            const int xs = gx[rr][cc], ys = gy[rr][cc];
-            const int ax = abs(xs), ay = abs(ys) << 15;
-            const int tg22x = ax * 13573;
-            bool is_max;
-            if (ay < tg22x) is_max = m > mg[rr][cc - 1] && m >= mg[rr][cc + 1];
-            else {
-                const int tg67x = tg22x + (ax << 16);
-                if (ay > tg67x) is_max = m > mg[rr - 1][cc] && m >= mg[rr + 1][cc];
-                else {
-                    const int sg = (xs ^ ys) < 0 ? -1 : 1;
-                    is_max = m > mg[rr - 1][cc - sg] && m > mg[rr + 1][cc + sg];
-                }
-            }
-            if (is_max) v = m > hi ? 2 : 0;
-        }
-        o[k] = (uint8_t)v;
-        if (v != 1) {
-            const unsigned idx = (unsigned)(y * w + x0 + c);
-            labels[(size_t)s * h * w + idx] = v == 2 ? idx : (idx | 0x80000000u);
-        }
-    }
-    *reinterpret_cast<uint4*>(map + ((size_t)s * h + y) * w + x0 + c0) = *reinterpret_cast<const uint4*>(o);
-}
-
 // ===== streaming kernels (w % 4 == 0): no LDS tiles; a lane owns 4 adjacent pixels of a column strip and
 // slides down the rows, exchanging row neighbours with DPP.  A wave covers 64 chunks = 256 columns of which
 // lanes 0 and 63 are halo (strip pitch 248 columns); image borders are resolved by permuting the edge lane's
@@ -701,23 +559,6 @@ __global__ void __launch_bounds__(256) sobel_nms_stream(const uint8_t* __restric
 }
 
 
-// ---- fused front end: BGR -> gray -> 5x5 blur (+ histogram) -> Sobel -> non-maximum suppression, ONE pass ---------
-// Canny's thresholds come from the median of the whole blurred frame, which is why the reference's order forces the
-// blurred image out to memory and back.  But the thresholds are not needed to decide WHETHER a pixel is a maximum
-// along its gradient, only to classify the maxima afterwards: so this kernel streams a frame once, keeps the blurred
-// rows in a register ring, and writes
-//     nm[y][x] = 0                    if the pixel is not a local maximum along its gradient direction
-//              = min(m / 2, 255)      if it is, m = |gx| + |gy|
-// m is always EVEN (gx and gy are both congruent to the sum of the four corner pixels modulo 2), and the thresholds
-// are at most 255, so "m > lo" == "m/2 > lo/2" and a value saturated at 255 compares like the full magnitude: the
-// hysteresis pass classifies with  candidate = nm > (lo >> 1),  strong = nm > (hi >> 1)  -- exactly cv::Canny's sets.
-// That removes one full-frame write and one read (the blurred image) and the second pass's reloads.
-// Same streaming scheme as the two kernels it replaces (lane = 4 adjacent pixels of a 248-column strip, neighbours
-// by DPP); rows: gray rows feed a 5-deep ring of horizontal sums -> blurred row b -> Sobel of row b-1 -> NMS of row
-// b-2.  Border rules as in OpenCV: reflect-101 for the blur, replicate for Sobel's reads of the blurred image
-// (blurred(-1) == blurred(0): the same register row is pushed again), magnitude 0 outside the image.
-// output rows per wave: a template parameter (8 halo rows are recomputed per band; 45 gives 1280x720 frames 16 bands)
-
 // packed 16-bit helpers (VOP3P): a register holds two pixels, X02 = (x0 | x2 << 16), X13 = (x1 | x3 << 16) -- with this
 // interleaving the right neighbours of pixels (0,2) are exactly register X13 and the left neighbours of (1,3) exactly X02
 __device__ __forceinline__ unsigned pk_addu(unsigned a, unsigned b) {
@@ -757,162 +598,27 @@ __device__ __forceinline__ unsigned opaque(unsigned v) {
     return v;
 }
 
-template <bool KEEP_BLUR, int FROWS>
-__global__ void __launch_bounds__(256) front_stream(const uint8_t* __restrict__ bgr, int h, int w, uint8_t* __restrict__ blur,
-                                                    uint8_t* __restrict__ nm, unsigned* __restrict__ hist) {
-    __shared__ unsigned lh[16 * 256];
-    const int s = blockIdx.z, tid = threadIdx.x, lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);          // wave-uniform: rows, bounds and row tests stay scalar
-    for (int i = tid; i < 16 * 256; i += 256) lh[i] = 0;
-    __syncthreads();
-    const int nstrips = (w + SW - 1) / SW, wv = blockIdx.x * 4 + wid;
-    const int strip = wv % nstrips, x0 = strip * SW - 4;
-    const int yb = (wv / nstrips) * FROWS;
-    const int x = x0 + 4 * lane;
-    const bool xin = x >= 0 && x + 4 <= w;
-    const bool out_lane = lane >= 1 && lane <= 62 && xin;
-    const bool at_left = x == 0, at_right = x + 4 == w;
-    const unsigned lane_mask = xin ? 0xFFFFFFFFu : 0u;
-    const uint8_t* img = bgr + (size_t)s * h * w * 3;
-    const size_t fo = (size_t)s * h * w;
-    if (yb < h) {
-        const int y_end = (yb + FROWS < h ? yb + FROWS : h);
-        // Iteration r consumes gray row r (reflect-101) and completes: horizontal sums H[r], U[r-1] = H[r-2] + 2 H[r-1] + H[r],
-        // blurred row b = r-2 = (U[r-3] + 2 U[r-2] + U[r-1] + 128) >> 8   ((1 2 1) * (1 2 1) = 1 4 6 4 1),
-        // Sobel + direction class of row r-3, NMS of row r-4.  Every ring is three deep and the loop is unrolled by
-        // three, so ring slots are compile-time registers and nothing is ever moved.
-        const int r_first = yb - 4, r_last = y_end + 3;
-        unsigned H02[3] = {0, 0, 0}, H13[3] = {0, 0, 0}, U02[3] = {0, 0, 0}, U13[3] = {0, 0, 0};
-        unsigned P02[3] = {0, 0, 0}, P13[3] = {0, 0, 0}, PE[3] = {0, 0, 0};
-        unsigned M02[3] = {0, 0, 0}, M13[3] = {0, 0, 0}, ME[3] = {0, 0, 0};
-        unsigned HZ02[3] = {0, 0, 0}, HZ13[3] = {0, 0, 0}, VT02[3] = {0, 0, 0}, VT13[3] = {0, 0, 0}, NG02[3] = {0, 0, 0},
-                 NG13[3] = {0, 0, 0};
-        unsigned fa[3], fb[3], fc[3];                                    // the next three BGR rows, in flight
-        const uint8_t* col = img + (size_t)(xin ? x : 0) * 3;
-        const unsigned pitch = (unsigned)w * 3u;
-        auto fetch = [&](int yy, unsigned& a, unsigned& b, unsigned& c) {
-            const int ys = reflect101_once(yy < r_last ? yy : r_last, h);
-            const unsigned* p = reinterpret_cast<const unsigned*>(col + (size_t)ys * pitch);
-            a = p[0], b = p[1], c = p[2];
-        };
-#pragma unroll
-        for (int q = 0; q < 3; ++q) fetch(r_first + q, fa[q], fb[q], fc[q]);
-        unsigned* hl = lh + (lane & 15) * 256;
-        for (int r0 = r_first; r0 <= r_last; r0 += 3) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const int r = r0 + k;                                    // (up to two rows past r_last: nothing they produce is kept)
-                const int k1 = (k + 2) % 3, k2 = (k + 1) % 3;            // slots of the previous and the one before
-                // ---- gray row r: 4 pixels -> pairs G02, G13 -----------------------------------------------------
-                const unsigned a = fa[k], b = fb[k], c = fc[k];          // B0 G0 R0 B1 | G1 R1 B2 G2 | R2 B3 G3 R3
-                fetch(r + 3, fa[k], fb[k], fc[k]);
-                const u16x2_t wbg = {1868, 9617};
-                auto gray = [&](unsigned bg_pair, unsigned rr) {
-                    return __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2_t, bg_pair), wbg, (unsigned)__umul24(4899u, rr) + 8192u, false) >> 14;
-                };
-                const unsigned g0 = gray(__builtin_amdgcn_perm(0u, a, 0x0C010C00u), (a >> 16) & 255u);
-                const unsigned g1 = gray(__builtin_amdgcn_perm(b, a, 0x0C040C03u), (b >> 8) & 255u);
-                const unsigned g2 = gray(__builtin_amdgcn_perm(0u, b, 0x0C030C02u), c & 255u);
-                const unsigned g3 = gray(__builtin_amdgcn_perm(0u, c, 0x0C020C01u), c >> 24);
-                const unsigned G02 = g0 | (g2 << 16), G13 = g1 | (g3 << 16);
-                // ---- horizontal 1 4 6 4 1 with the neighbours' pixels (reflect-101 at the image's left / right edge) ----
-                const unsigned R21 = hi_lo(G02, G13);                    // (g2, g1): columns -2,-1 and w,w+1 mirror to these
-                unsigned gprev = dpp_prev_u32(hi_hi(G02, G13));          // the previous lane's (g2, g3) = columns x-2, x-1
-                unsigned gnext = dpp_next_u32(lo_lo(G02, G13));          // the next lane's (g0, g1) = columns x+4, x+5
-                gprev = at_left ? R21 : gprev, gnext = at_right ? R21 : gnext;
-                const unsigned L2 = lo_lo(gprev, G02), L1 = hi_lo(gprev, G13);      // (g-2, g0), (g-1, g1)
-                const unsigned R2 = hi_lo(G02, gnext), R3 = hi_hi(G13, gnext);      // (g2, g4), (g3, g5)
-                H02[k] = pk_addu(pk_addu(L2, R2), pk_addu(pk_shlu(pk_addu(L1, G13), 2), pk_mulu(G02, 6)));
-                H13[k] = pk_addu(pk_addu(L1, R3), pk_addu(pk_shlu(pk_addu(G02, R2), 2), pk_mulu(G13, 6)));
-                // ---- vertical: U[r-1], then blurred row b = r-2 -------------------------------------------------
-                U02[k] = pk_addu(pk_addu(H02[k2], H02[k]), pk_shlu(H02[k1], 1));
-                U13[k] = pk_addu(pk_addu(H13[k2], H13[k]), pk_shlu(H13[k1], 1));
-                const unsigned V02 = pk_addu(pk_addu(U02[k2], U02[k]), pk_addu(pk_shlu(U02[k1], 1), 0x00800080u));
-                const unsigned V13 = pk_addu(pk_addu(U13[k2], U13[k]), pk_addu(pk_shlu(U13[k1], 1), 0x00800080u));
-                const unsigned p02 = pk_shru(V02, 8), p13 = pk_shru(V13, 8);        // (o0, o2), (o1, o3)
-                P02[k] = p02, P13[k] = p13;
-                const int bl = r - 2;
-                if (bl >= yb && bl < y_end) {                            // this wave owns the blurred row: histogram (+ debug copy)
-                    if (out_lane) {
-                        const unsigned o0 = p02 & 0xFFFFu, o2 = p02 >> 16, o1 = p13 & 0xFFFFu, o3 = p13 >> 16;
-                        if (KEEP_BLUR) *reinterpret_cast<unsigned*>(blur + fo + (size_t)bl * w + x) = p02 | (p13 << 8);
-                        if (p02 == p13 && o0 == o2) atomicAdd(&hl[o0], 4u);
-                        else atomicAdd(&hl[o0], 1u), atomicAdd(&hl[o1], 1u), atomicAdd(&hl[o2], 1u), atomicAdd(&hl[o3], 1u);
-                    }
-                }
-                {   // blurred neighbours across the lane border: PE = (column x-1 | column x+4 << 16), replicated at the image edge
-                    unsigned dp = dpp_prev_u32(p13), dn = dpp_next_u32(p02);        // .hi = o3 of the previous lane, .lo = o0 of the next
-                    dp = at_left ? (p02 << 16) : dp, dn = at_right ? (p13 >> 16) : dn;
-                    PE[k] = hi_lo(dp, dn);
-                }
-                // ---- Sobel of row ym = r-3 from blurred rows r-4, r-3, r-2 (replicated at the image's top / bottom) ----
-                const int ym = r - 3;
-                {
-                    unsigned t02 = P02[k2], t13 = P13[k2], te = PE[k2], b02 = P02[k], b13 = P13[k], be = PE[k];
-                    const unsigned c02 = P02[k1], c13 = P13[k1], ce = PE[k1];
-                    if (ym == 0) t02 = c02, t13 = c13, te = ce;
-                    if (ym == h - 1) b02 = c02, b13 = c13, be = ce;
-                    const unsigned v02 = pk_addu(pk_addu(t02, b02), pk_shlu(c02, 1)), v13 = pk_addu(pk_addu(t13, b13), pk_shlu(c13, 1)),
-                                   ve = pk_addu(pk_addu(te, be), pk_shlu(ce, 1));
-                    const unsigned d02 = pk_sub16(b02, t02), d13 = pk_sub16(b13, t13), de = pk_sub16(be, te);
-                    const unsigned dx02 = pk_sub16(v13, lo_lo(ve, v13));                       // V[k+1] - V[k-1] for pixels 0, 2
-                    const unsigned dx13 = pk_sub16(hi_hi(v02, ve), v02);                       //                  for pixels 1, 3
-                    const unsigned dy02 = pk_add16(pk_add16(lo_lo(de, d13), pk_add16(d02, d02)), d13);
-                    const unsigned dy13 = pk_add16(pk_add16(d02, pk_add16(d13, d13)), hi_hi(d02, de));
-                    const unsigned ax02 = pk_abs16(dx02), ax13 = pk_abs16(dx13), ay02 = pk_abs16(dy02), ay13 = pk_abs16(dy13);
-                    const unsigned inm = (ym >= 0 && ym < h) ? lane_mask : 0u;                 // magnitude is 0 outside the image
-                    const unsigned m02 = (ax02 + ay02) & inm, m13 = (ax13 + ay13) & inm;       // <= 2040 per half: plain add
-                    M02[k] = m02, M13[k] = m13;
-                    ME[k] = hi_lo(dpp_prev_u32(m13), dpp_next_u32(m02));                       // (m of column x-1 | m of column x+4 << 16)
-                    // direction class, cv::Canny's fixed-point tests in 16 bits: with t22 = floor(|gx| * 13573 / 2^15)
-                    //   |gy| * 2^15 <  |gx| * 13573           <=>  |gy| <= t22         (|gx| > 0; at |gx| = 0 both sides need |gy| = 0,
-                    //                                                                   where the magnitude is 0 and nothing is a maximum)
-                    //   |gy| * 2^15 >  |gx| * (13573 + 2^16)  <=>  |gy| >  t22 + 2 |gx|
-                    // 13573 = 53 * 256 + 5, so t22 = (53 |gx| + ((5 |gx|) >> 8)) >> 7 without leaving 16 bits (|gx| <= 1020)
-                    const unsigned t02q = pk_shru(pk_addu(pk_mulu(ax02, 53), pk_shru(pk_mulu(ax02, 5), 8)), 7);
-                    const unsigned t13q = pk_shru(pk_addu(pk_mulu(ax13, 53), pk_shru(pk_mulu(ax13, 5), 8)), 7);
-                    HZ02[k] = opaque(pk_sar15(pk_sub16(pk_sub16(ay02, t02q), 0x00010001u)));           // |gy| - t22 - 1 < 0
-                    HZ13[k] = opaque(pk_sar15(pk_sub16(pk_sub16(ay13, t13q), 0x00010001u)));
-                    VT02[k] = opaque(pk_sar15(pk_sub16(pk_addu(t02q, pk_shlu(ax02, 1)), ay02)));        // t22 + 2|gx| - |gy| < 0
-                    VT13[k] = opaque(pk_sar15(pk_sub16(pk_addu(t13q, pk_shlu(ax13, 1)), ay13)));
-                    NG02[k] = opaque(pk_sar15(dx02 ^ dy02)), NG13[k] = opaque(pk_sar15(dx13 ^ dy13));          // gradient signs differ
-                }
-                // ---- NMS of row yo = r-4: magnitude rows r-5 (slot k2), r-4 (k1), r-3 (k); class masks of row r-4 (k1) ----
-                const int yo = r - 4;
-                if (yo >= yb && yo < y_end) {
-                    const unsigned mT02 = M02[k2], mT13 = M13[k2], mTE = ME[k2], mC02 = M02[k1], mC13 = M13[k1], mCE = ME[k1],
-                                   mB02 = M02[k], mB13 = M13[k], mBE = ME[k];
-                    // pixels 0,2: left (m-1, m1), right M13; pixels 1,3: left M02, right (m2, m4); same for the rows above / below
-                    const unsigned l02 = lo_lo(mCE, mC13), r13 = hi_hi(mC02, mCE);
-                    const unsigned ul02 = lo_lo(mTE, mT13), ur13 = hi_hi(mT02, mTE), dl02 = lo_lo(mBE, mB13), dr13 = hi_hi(mB02, mBE);
-                    const unsigned hz02 = HZ02[k1], hz13 = HZ13[k1], vt02 = VT02[k1], vt13 = VT13[k1], ng02 = NG02[k1], ng13 = NG13[k1];
-                    // first neighbour (must be strictly smaller): left | up | up-right (signs differ) | up-left
-                    const unsigned n1a = bsel(hz02, l02, bsel(vt02, mT02, bsel(ng02, mT13, ul02)));
-                    const unsigned n1b = bsel(hz13, mC02, bsel(vt13, mT13, bsel(ng13, ur13, mT02)));
-                    // second neighbour: right | down (these two may be equal) | down-left (signs differ) | down-right
-                    const unsigned n2a = bsel(hz02, mC13, bsel(vt02, mB02, bsel(ng02, dl02, mB13)));
-                    const unsigned n2b = bsel(hz13, r13, bsel(vt13, mB13, bsel(ng13, mB02, dr13)));
-                    // m > n1 and (m >= n2 on the horizontal / vertical classes, m > n2 on the diagonals): m - mask adds 1 where mask = 0xFFFF
-                    const unsigned ea = pk_minu(pk_subsat(mC02, n1a), pk_subsat(pk_sub16(mC02, hz02 | vt02), n2a));
-                    const unsigned eb = pk_minu(pk_subsat(mC13, n1b), pk_subsat(pk_sub16(mC13, hz13 | vt13), n2b));
-                    const unsigned ca = pk_minu(pk_shru(mC02, 1), 0x00FF00FFu);
-                    const unsigned cb = pk_minu(pk_shru(mC13, 1), 0x00FF00FFu);
-                    const unsigned oa = __builtin_bit_cast(unsigned, __builtin_bit_cast(u16x2_t, ca) * __builtin_bit_cast(u16x2_t, opaque(pk_minu(ea, 0x00010001u))));
-                    const unsigned ob = __builtin_bit_cast(unsigned, __builtin_bit_cast(u16x2_t, cb) * __builtin_bit_cast(u16x2_t, opaque(pk_minu(eb, 0x00010001u))));
-                    if (out_lane) *reinterpret_cast<unsigned*>(nm + fo + (size_t)yo * w + x) = oa | (ob << 8);
-                }
-            }
-        }
-    }
-    __syncthreads();
-    unsigned tot = 0;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) tot += lh[q * 256 + tid];
-    if (tot) atomicAdd(&hist[(size_t)s * 256 + tid], tot);
-}
-
-// ---- packed-strip front end (front_pack): the same one-pass BGR -> nm pipeline as front_stream, rebuilt around what a
-// calibration of the vector pipe (tools/wvalu.hip) and in-kernel clocks (tools/ltime.py) showed about front_stream:
+// ---- fused front end (front_pack): BGR -> gray -> 5x5 blur (+ histogram) -> Sobel -> non-maximum suppression, ONE pass -------
+// Canny's thresholds come from the median of the whole blurred frame, which is why the reference's order forces the
+// blurred image out to memory and back.  But the thresholds are not needed to decide WHETHER a pixel is a maximum
+// along its gradient, only to classify the maxima afterwards: so this kernel streams a frame once, keeps the blurred
+// rows in a register ring, and writes
+//     nm[y][x] = 0                    if the pixel is not a local maximum along its gradient direction
+//              = min(m / 2, 255)      if it is, m = |gx| + |gy|
+// m is always EVEN (gx and gy are both congruent to the sum of the four corner pixels modulo 2), and the thresholds
+// are at most 255, so "m > lo" == "m/2 > lo/2" and a value saturated at 255 compares like the full magnitude: the
+// hysteresis pass classifies with  candidate = nm > (lo >> 1),  strong = nm > (hi >> 1)  -- exactly cv::Canny's sets.
+// That removes one full-frame write and one read (the blurred image) and the second pass's reloads.
+// Same streaming scheme as the two-pass kernels (lane = 4 adjacent pixels of a 248-column strip, neighbours by DPP).
+// Iteration r consumes gray row r (reflect-101) and completes: horizontal sums H[r], U[r-1] = H[r-2] + 2 H[r-1] + H[r],
+// blurred row b = r-2 = (U[r-3] + 2 U[r-2] + U[r-1] + 128) >> 8   ((1 2 1) * (1 2 1) = 1 4 6 4 1), Sobel + direction
+// class of row r-3, NMS of row r-4.  Every ring is three deep and the loop is unrolled by three, so ring slots are
+// compile-time registers and nothing is ever moved.  Border rules as in OpenCV: reflect-101 for the blur, replicate for
+// Sobel's reads of the blurred image, magnitude 0 outside the image.  Output rows per wave: FROWS (8 halo rows are
+// recomputed per band).
+//
+// Round 3 rebuilt the first one-pass kernel (front_stream, four waves per workgroup, since removed) around what a calibration
+// of the vector pipe (tools/wvalu.hip) and in-kernel clocks (also removed; findings in DESIGN section A.1) showed about it:
 //  * it is bound by vector-instruction issue (196 per 4-pixel row, ~3.5 cycles each with six waves per SIMD), so every
 //    instruction that could go went: weights x4 so that gray is byte 2 of the accumulator (no shifts, one v_perm packs a
 //    pair), x + 2y and x*6 + y as v_pk_mad_u16 (hipcc emits shift + add), the rounding constant inside a v_add3, LDS
@@ -957,15 +663,13 @@ __device__ __forceinline__ void lds_add(unsigned byte_addr, unsigned v) {
     asm volatile("ds_add_u32 %0, %1" : : "v"(byte_addr), "v"(v) : "memory");
 }
 
-template <bool KEEP_BLUR, int FROWS, bool TIMED, int ABL = 0>
+template <bool KEEP_BLUR, int FROWS>
 __global__ void __launch_bounds__(64, 5) front_pack(const uint8_t* __restrict__ bgr, int h, int w, FrontGeo geo, uint8_t* __restrict__ blur,
                                                  uint8_t* __restrict__ nm, unsigned* __restrict__ hist) {
     // One wave per workgroup: 5328 equal work items on 256 CUs are 20.8 per CU -- in four-wave workgroups that was 5 or 6
     // workgroups per CU and the CUs with six set the kernel's time (100 us against 79 on the others).
     extern __shared__ unsigned lh[];                                     // geo.nc histogram copies of 256 bins
     __builtin_amdgcn_s_setprio(3);
-    unsigned long long tm0 = 0, tr0 = 0, sect = 0;
-    if (TIMED) tm0 = __builtin_amdgcn_s_memtime(), tr0 = __builtin_amdgcn_s_memrealtime();
     const int lane = threadIdx.x;
     for (int i = lane; i < geo.nc * 256; i += 64) lh[i] = 0;
     const int C = w >> 2, per_frame = geo.nb * geo.nfull;
@@ -997,7 +701,6 @@ __global__ void __launch_bounds__(64, 5) front_pack(const uint8_t* __restrict__ 
         hcopy = lane_on ? gi * cpg + li % cpg : 0;
         edge = true;
     }
-    const bool wave_on = true;
     band = __builtin_amdgcn_readfirstlane(band), s0 = __builtin_amdgcn_readfirstlane(s0);
     edge = __builtin_amdgcn_readfirstlane((int)edge) != 0;
     const bool xin = lane_on && cidx >= 0 && cidx < C;
@@ -1005,11 +708,11 @@ __global__ void __launch_bounds__(64, 5) front_pack(const uint8_t* __restrict__ 
     const bool at_left = xin && cidx == 0, at_right = xin && cidx == C - 1;
     const unsigned lane_mask = xin ? 0xFFFFFFFFu : 0u;
     const unsigned xs = xin ? 4u * (unsigned)cidx : 0u, sl = lane_on ? (unsigned)s_l : (unsigned)s0;
-    const unsigned voff_in = sl * ((unsigned)h * (unsigned)w * 3u) + xs * 3u;      // host checked: S*h*w*3 < 2^32
+    const unsigned voff_in = sl * ((unsigned)h * (unsigned)w * 3u) + xs * 3u;      // the host launches groups with S*h*w*3 < 2^32
     const unsigned voff_out = sl * ((unsigned)h * (unsigned)w) + xs;
     const unsigned hbase = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned*)lh + (unsigned)hcopy * 1024u;      // LDS byte address of this lane's histogram copy
     const int yb = band * FROWS;
-    if (wave_on && yb < h) {
+    if (yb < h) {
         const int y_end = (yb + FROWS < h ? yb + FROWS : h);
         const int r_first = yb - 4, r_last = y_end + 3;
         const unsigned pitch = (unsigned)w * 3u;
@@ -1023,7 +726,6 @@ __global__ void __launch_bounds__(64, 5) front_pack(const uint8_t* __restrict__ 
             unsigned fa[3], fb[3], fc[3];                                // BGR rows in flight: slot r % 3 holds row r, loaded two rows ahead (three: 12 spilled registers, 137 us)
             // kernel-argument base + one 32-bit offset (row term scalar): a single add and a load with a scalar base
             auto fetch_at = [&](unsigned ys, unsigned& a, unsigned& b, unsigned& c) {
-                if (ABL & 2) { a = ys * 0x01010101u + (unsigned)lane * 0x00030201u; b = a ^ 0x05050505u; c = a + 0x00010203u; return; }
                 const unsigned* p = reinterpret_cast<const unsigned*>(bgr + (voff_in + ys * pitch));
                 a = p[0], b = p[1], c = p[2];
             };
@@ -1076,9 +778,9 @@ __global__ void __launch_bounds__(64, 5) front_pack(const uint8_t* __restrict__ 
                     const unsigned v1 = (unsigned)__builtin_amdgcn_readlane((int)p02, 1);
                     const bool flat = full && (v1 & 0xFFFFu) == (v1 >> 16) && __ballot(out_lane && (p02 != v1 || p13 != v1)) == 0ull;
                     if (KEEP_BLUR && out_lane) *reinterpret_cast<unsigned*>(blur + (voff_out + (unsigned)bl * (unsigned)w)) = p02 | (p13 << 8);
-                    if (flat && !(ABL & 1)) {
+                    if (flat) {
                         if (lane == 1) lds_add(mad_lo16x4(p02, hbase), flat_count);
-                    } else if (out_lane && !(ABL & 1)) {
+                    } else if (out_lane) {
                         unsigned t0, t1, t2, t3;                         // LDS addresses straight from the packed halves
                         asm volatile("v_mad_u32_u16 %0, %4, 4, %6\n\tv_mad_u32_u16 %1, %4, 4, %6 op_sel:[1,0,0,0]\n\t"
                                      "v_mad_u32_u16 %2, %5, 4, %6\n\tv_mad_u32_u16 %3, %5, 4, %6 op_sel:[1,0,0,0]\n\t"
@@ -1103,8 +805,6 @@ __global__ void __launch_bounds__(64, 5) front_pack(const uint8_t* __restrict__ 
                 }
                 // ---- Sobel of row ym = r-3 from blurred rows r-4 (slot k2), r-3 (k1), r-2 (k) ----
                 const int ym = r - 3;
-                unsigned long long ts0 = 0;
-                if (TIMED) ts0 = __builtin_amdgcn_s_memtime();
                 {
                     const unsigned t02 = P02[k2], t13 = P13[k2], te = PE[k2], b02 = P02[k], b13 = P13[k], be = PE[k];
                     const unsigned c02 = P02[k1], c13 = P13[k1], ce = PE[k1];
@@ -1123,7 +823,11 @@ __global__ void __launch_bounds__(64, 5) front_pack(const uint8_t* __restrict__ 
                     }
                     M02[k] = m02, M13[k] = m13;
                     ME[k] = hi_lo(dpp_prev_u32(m13), dpp_next_u32(m02));                           // (m of column x-1 | m of column x+4 << 16)
-                    // direction classes: see front_stream
+                    // direction class, cv::Canny's fixed-point tests in 16 bits: with t22 = floor(|gx| * 13573 / 2^15)
+                    //   |gy| * 2^15 <  |gx| * 13573           <=>  |gy| <= t22         (|gx| > 0; at |gx| = 0 both sides need |gy| = 0,
+                    //                                                                   where the magnitude is 0 and nothing is a maximum)
+                    //   |gy| * 2^15 >  |gx| * (13573 + 2^16)  <=>  |gy| >  t22 + 2 |gx|
+                    // 13573 = 53 * 256 + 5, so t22 = (53 |gx| + ((5 |gx|) >> 8)) >> 7 without leaving 16 bits (|gx| <= 1020)
                     const unsigned t02q = pk_shru(pk_madk<53>(ax02, pk_shru(pk_mulu(ax02, 5), 8)), 7);
                     const unsigned t13q = pk_shru(pk_madk<53>(ax13, pk_shru(pk_mulu(ax13, 5), 8)), 7);
                     HZ02[k] = opaque(pk_sar15(pk_add16(ay02, ~t02q)));                              // |gy| - t22 - 1 < 0
@@ -1131,10 +835,6 @@ __global__ void __launch_bounds__(64, 5) front_pack(const uint8_t* __restrict__ 
                     VT02[k] = opaque(pk_sar15(pk_sub16(pk_madk<2>(ax02, t02q), ay02)));             // t22 + 2|gx| - |gy| < 0
                     VT13[k] = opaque(pk_sar15(pk_sub16(pk_madk<2>(ax13, t13q), ay13)));
                     NG02[k] = opaque(pk_sar15(dx02 ^ dy02)), NG13[k] = opaque(pk_sar15(dx13 ^ dy13));              // gradient signs differ
-                }
-                if (TIMED) {
-                    asm volatile("" :: "v"(NG13[k]), "v"(VT13[k]), "v"(HZ13[k]), "v"(ME[k]));
-                    sect += __builtin_amdgcn_s_memtime() - ts0;
                 }
                 // ---- NMS of row yo = r-4: magnitude rows r-5 (slot k2), r-4 (k1), r-3 (k); class masks of row r-4 (k1) ----
                 const int yo = r - 4;
@@ -1153,7 +853,7 @@ __global__ void __launch_bounds__(64, 5) front_pack(const uint8_t* __restrict__ 
                     const unsigned ca = pk_minu(pk_shru(mC02, 1), 0x00FF00FFu);
                     const unsigned cb = pk_minu(pk_shru(mC13, 1), 0x00FF00FFu);
                     const unsigned oa = pk_mulv(ca, pk_min1(ea)), ob = pk_mulv(cb, pk_min1(eb));
-                    if ((ABL & 4) ? (out_lane && (oa ^ ob) == 0x12345678u) : out_lane) *reinterpret_cast<unsigned*>(nm + (voff_out + (unsigned)yo * (unsigned)w)) = oa | (ob << 8);
+                    if (out_lane) *reinterpret_cast<unsigned*>(nm + (voff_out + (unsigned)yo * (unsigned)w)) = oa | (ob << 8);
                 }
             };
             const int n_trips = (r_last - r_first + 3) / 3, trip_p2 = r_first + 3 * (n_trips / 2),
@@ -1181,15 +881,6 @@ __global__ void __launch_bounds__(64, 5) front_pack(const uint8_t* __restrict__ 
         };
         if (edge) run(std::true_type{});
         else run(std::false_type{});
-    }
-    if (TIMED) {
-        const unsigned long long tm1 = __builtin_amdgcn_s_memtime(), tr1 = __builtin_amdgcn_s_memrealtime();
-        if (lane == 0) {
-            unsigned long long* dbg = reinterpret_cast<unsigned long long*>(blur) + (size_t)bx * 4;
-            dbg[0] = tm1 - tm0, dbg[1] = tr1 - tr0, dbg[2] = tr0;
-            dbg[3] = (unsigned long long)__builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11)) |
-                     ((unsigned long long)(__builtin_amdgcn_s_getreg(20 | (0 << 6) | (31 << 11)) & 15) << 32) | (sect << 36);
-        }
     }
     // the wave's own LDS operations complete in order: its histogram is final here
     if (full) {
@@ -2259,11 +1950,9 @@ __global__ void __launch_bounds__((HVW + 1) * 64) houghp_shard(int h, int w, int
                                                    const int* __restrict__ npts, int* __restrict__ accum_all,
                                                    const float* __restrict__ trig, int* __restrict__ segs,
                                                    int* __restrict__ nseg, int* __restrict__ fallback, int spin_limit,
-                                                   int drop_frame, int* __restrict__ path, int timed, int xcd_local) {
+                                                   int drop_frame, int* __restrict__ path) {
     // spin_limit: iterations an exchange waits for a partner before the frame is handed to houghp_fast; drop_frame (tests only,
-    // AVHOT_HOUGH_DROP): workgroup HG-1 of that frame never publishes its first exchange word, so its partners run into the limit;
-    // timed (AVHOT_HOUGH_TIMED, tools/htime.py): wave 0 of workgroup 0 adds up s_memtime cycles per phase and leaves them behind
-    // the frame's exchange words (accumulator view, 64-bit words 32 .. 47)
+    // AVHOT_HOUGH_DROP): workgroup HG-1 of that frame never publishes its first exchange word, so its partners run into the limit
     __shared__ unsigned acc_all[HVW][HS_ACCW];
     __shared__ unsigned nz[HS_NZ];
     __shared__ unsigned bm[HS_BMW];
@@ -2276,9 +1965,9 @@ __global__ void __launch_bounds__((HVW + 1) * 64) houghp_shard(int h, int w, int
     __shared__ unsigned sh_hit[HVW], sh_key[HVW];
     __shared__ int sh_nb, sh_head, sh_tail, sh_count, sh_big, sh_hits, sh_fail, sh_er[8];
     // Workgroups go round-robin over the 8 XCDs (blockIdx % 8): the four workgroups of a frame are given the same blockIdx % 8, so that
-    // their exchange words meet in one XCD's L2 (AVHOT_HOUGH_XCD=0: consecutive workgroups per frame).  Placement only: any map is correct.
+    // their exchange words meet in one XCD's L2 (other grid sizes: consecutive workgroups per frame).  Placement only: any map is correct.
     int s = blockIdx.x / HG, g = blockIdx.x % HG;
-    if (xcd_local && (gridDim.x % (8 * HG)) == 0) {
+    if ((gridDim.x % (8 * HG)) == 0) {
         const int b = blockIdx.x, blk = b / (8 * HG), r = b - blk * (8 * HG);
         s = blk * 8 + (r & 7), g = r >> 3;
     }
@@ -2297,13 +1986,6 @@ __global__ void __launch_bounds__((HVW + 1) * 64) houghp_shard(int h, int w, int
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
     };
     constexpr int NTH = (HVW + 1) * 64;
-    unsigned long long tph[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast = timed ? __builtin_amdgcn_s_memtime() : 0ull;
-    auto lap = [&](int k) {                        // cycles since the previous lap -> phase k
-        if (timed) {
-            const unsigned long long t = __builtin_amdgcn_s_memtime();
-            tph[k] += t - tlast, tlast = t;
-        }
-    };
     // the LDS clears do not depend on the point list: they run while its loads are in flight
     for (int i = (int)threadIdx.x; i < HVW * HS_ACCW; i += NTH) (&acc_all[0][0])[i] = HS_BIAS | (HS_BIAS << 16);
     for (int i = (int)threadIdx.x; i < HS_BMW; i += NTH) bm[i] = 0;
@@ -2525,7 +2207,6 @@ __global__ void __launch_bounds__((HVW + 1) * 64) houghp_shard(int h, int w, int
     int nlines = 0;
     if (wv == HVW) top_up(true);
     __syncthreads();
-    lap(0);                                        // set-up
     // Phases of one batch; every wave passes the same barriers (B1 .. B6), all tests between them are workgroup-uniform (LDS words).
     for (;;) {
         // ---- wave 0: form the batch: pop up to HB points that are still live ------------------------------------------------------
@@ -2559,7 +2240,6 @@ __global__ void __launch_bounds__((HVW + 1) * 64) houghp_shard(int h, int w, int
             }
             if (lane == 0) sh_head = head, sh_nb = nb;
         }
-        lap(1);                                    // batch forming
         __syncthreads();                           // B1: the batch is in LDS
         const int nb = sh_nb;
         if (nb == 0) break;
@@ -2586,8 +2266,6 @@ __global__ void __launch_bounds__((HVW + 1) * 64) houghp_shard(int h, int w, int
             top_up(true);
         }
         __syncthreads();                           // B2: hit masks of the four voting waves, FIFO refilled
-        lap(2);                                    // votes (and the helper's top-up) incl. both barriers
-        tph[10] += 1;
         if (wv == 0) {
             unsigned hitbits = 0;
 #pragma unroll
@@ -2599,7 +2277,6 @@ __global__ void __launch_bounds__((HVW + 1) * 64) houghp_shard(int h, int w, int
             if (lane == 0) sh_hits = (int)hits, sh_fail = ok ? 0 : 1;
         }
         __syncthreads();                           // B3: the frame's hit mask
-        lap(3);                                    // first exchange
         if (sh_fail) {
             give_up();
             return;
@@ -2625,8 +2302,6 @@ __global__ void __launch_bounds__((HVW + 1) * 64) houghp_shard(int h, int w, int
             }
         }
         __syncthreads();                           // B4: the workgroup's best keys
-        lap(4);                                    // keys, withdrawn votes
-        tph[11] += 1;
         if (wv == 0) {
             unsigned lbest = 0;
 #pragma unroll
@@ -2635,7 +2310,6 @@ __global__ void __launch_bounds__((HVW + 1) * 64) houghp_shard(int h, int w, int
             const bool ok = exchange(1, lbest, got);
             unsigned best = wave_max_u32(got);
             best ^= 0x80000000u;
-            lap(5);                                // second exchange
             if (lane == 0) {
                 int head = sh_head;
                 for (int b = nb - 1; b > bs; --b) fifo[(--head) & (FIFO - 1)] = bpt[b];
@@ -2722,7 +2396,6 @@ __global__ void __launch_bounds__((HVW + 1) * 64) houghp_shard(int h, int w, int
             }
         }
         __syncthreads();                           // B5: the line
-        lap(6);                                    // line walk
         if (sh_fail) {
             give_up();
             return;
@@ -2730,15 +2403,11 @@ __global__ void __launch_bounds__((HVW + 1) * 64) houghp_shard(int h, int w, int
         if (wv == 0) erase_bitmap(0);              // this wave direction 0, the helper direction 1
         else if (wv == HVW) erase_bitmap(1);
         __syncthreads();                           // B6: the erased pixels' bits
-        lap(7);                                    // erase, bitmap part
         const bool good = sh_er[5] != 0;
         if (good && voter) erase_votes();          // (runs beside wave 0's next batch forming: the rows are this wave's own)
-        lap(8);                                    // erase, accumulator part
         if (good && ++nlines >= cfg.max_segments) break;
     }
     if (wv == 0 && g == 0 && lane == 0) nseg[s] = nlines, path[s] = 1;
-    if (timed && wv == 0 && g == 0 && lane == 0)
-        for (int k = 0; k < 12; ++k) xw[32 + k] = tph[k];
 }
 
 // ---- L5-L7: slope split, quadratic fit, EMA, resampling ------------------------------------------------------
@@ -2919,6 +2588,47 @@ struct LaneCtx {
     int roi_h = 0, roi_w = 0;
 };
 
+// ---- what one av_lane_detect call runs, decided from its shape and stage bits alone --------------------------------------------
+enum class Front {
+    Fused,              // front_pack: one pass BGR -> non-maximum-suppressed magnitudes (the hysteresis pass applies the thresholds)
+    Stream,             // two passes, streaming kernels (w % 4 == 0): gray_blur_hist_stream, thresholds_kernel, sobel_nms_stream
+    Generic,            // two passes, LDS tiles: gray_blur_hist_kernel, thresholds_kernel, sobel_nms_kernel
+    GivenStream,        // stage bit 6: u8 image and thresholds already in views 0 / 4, then sobel_nms_stream
+    GivenGeneric,       //              ... then sobel_nms_kernel
+};
+struct LanePlan {
+    Front front;
+    int frows;          // band height of front_pack
+    bool tiled;         // tiled hysteresis + chunk-box resolve / compaction (w % 16 == 0, 16-byte aligned buffers)
+    bool bitpath;       // the ROI is resolved through the bit maps: no masked byte map (the generic Hough kernel rebuilds it)
+    Roi roi;            // the default trapezoid, lane_detector.py:55-60
+    int bx0, by0, bcw, bch;             // chunk box the resolve / compaction passes visit: first chunk column, first row, chunks, rows
+};
+
+LanePlan lane_plan(int stages, int S, int h, int w, const void* bgr, const void* ws, const int32_t* roi_rows) {
+    LanePlan p{};
+    const bool aligned = (((size_t)bgr | (size_t)ws) & 15) == 0;
+    p.tiled = (w % 16 == 0) && w >= 32 && aligned && (long long)h * (w >> 4) < (1ll << 24);     // chunk_xy's exact range
+    const bool streamp = (w % 4 == 0) && w >= 8 && aligned;
+    if (stages & 64) p.front = streamp ? Front::GivenStream : Front::GivenGeneric;
+    else p.front = p.tiled ? Front::Fused : (streamp ? Front::Stream : Front::Generic);
+    // a few frames per launch (the per-frame class calls): short bands, so that a frame is hundreds of waves instead of 96
+    p.frows = (stages & 1) ? 72 : (S <= 8 ? 15 : 48);
+    p.roi.x0 = (int)(w * 0.1), p.roi.x1 = (int)(w * 0.4), p.roi.x2 = (int)(w * 0.6), p.roi.x3 = (int)(w * 0.9);
+    p.roi.yt = (int)(h * 0.6);
+    // the debug edge map (bit 0) or a caller-defined ROI: every chunk, byte-map resolve; else the default trapezoid's bounding
+    // box (rows yt .. h-1, columns x0 .. x3).  Bit 0 concerns the pixel stages only: a Hough-only call (bit 4) follows a
+    // production pixel call of the same shape and takes that call's decision.
+    p.bx0 = 0, p.by0 = 0, p.bcw = w >> 4, p.bch = h;
+    const bool trapezoid = p.tiled && !roi_rows && (!(stages & 1) || (stages & 16));
+    if (trapezoid) {
+        p.by0 = p.roi.yt < h ? p.roi.yt : h - 1, p.bch = h - p.by0;
+        p.bx0 = p.roi.x0 >> 4, p.bcw = (((p.roi.x3 < w ? p.roi.x3 : w - 1) >> 4) - p.bx0) + 1;
+    }
+    p.bitpath = trapezoid && p.roi.yt < h && (h - p.roi.yt) <= CB_ROWS;
+    return p;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3009,87 +2719,64 @@ int av_lane_detect(av_ctx* ctx, av_stream_t stream, const av_lane_cfg* cfg, int 
     unsigned* tedge = (unsigned*)(ws + L.tedge);
     unsigned* rbits = (unsigned*)(ws + L.rbits);
     unsigned* kbits = (unsigned*)(ws + L.kbits);
-    bool bitpath = false;            // this call resolved the ROI through the bit maps (no masked byte map written)
+    const LanePlan P = lane_plan(stages, n_streams, h, w, bgr, workspace, roi_rows);
     bool prepped = false;            // the compaction pass cleared the sharded Hough kernel's exchange words and fallback flags
     const char* shard_env = getenv("AVHOT_HOUGH_SHARD");
     const bool use_shard = !(stages & 8) && !(shard_env && atoi(shard_env) == 0);      // AVHOT_HOUGH_SHARD=0 skips the sharded kernel
-    const dim3 tiles((w + TW - 1) / TW, (h + TH - 1) / TH, n_streams);
-    const bool fastp = (w % 16 == 0) && w >= 32 && (((size_t)bgr | (size_t)workspace) & 15) == 0 &&
-                       (long long)h * (w >> 4) < (1ll << 24);             // chunk_xy's exact range
-    const bool streamp = (w % 4 == 0) && w >= 8 && (((size_t)bgr | (size_t)workspace) & 15) == 0 && !(stages & 4);
     if (!(stages & 16)) {                                          // bit 4: Hough + fit only, on the point lists already in the workspace
-        // fused = one streaming pass BGR -> non-maximum-suppressed magnitudes (thresholds applied by the hysteresis pass);
-        // other shapes take the two-pass kernels with the blurred image in memory between them
-        const bool given = (stages & 64) != 0;                       // bit 6: image and thresholds already in views 0 / 4
-        const bool fused = !given && streamp && fastp && !getenv("AVHOT_LANE_TWO_PASS");
+        const bool fused = P.front == Front::Fused;
         if (fused) {
-            const char* fe = getenv("AVHOT_LANE_FROWS");
-            const int fr = fe ? atoi(fe) : 48;                       // front_stream at 720p, 64 frames: 45 rows 122 us, 72 rows 128, 90 rows 123
-            // a few frames per launch (the per-frame class calls): short bands, so that a frame is hundreds of waves instead of 96
-            const int frows = (stages & 1) ? 72 : (fe ? (fr == 72 ? 72 : (fr == 90 ? 90 : (fr == 15 ? 15 : (fr == 48 ? 48 : 45)))) : (n_streams <= 8 ? 15 : 48));
-            const int sfrows = frows == 48 ? 45 : frows;           // front_stream has no 48-row instantiation
-            const dim3 fgrid((((w + SW - 1) / SW) * ((h + sfrows - 1) / sfrows) + 3) / 4, 1, n_streams);     // front_stream: waves = strips x bands
-            const bool packed = (unsigned long long)n_streams * h * w * 3ull < (1ull << 32) && !getenv("AVHOT_LANE_STRIP_FRONT");
-            if (packed) {
+            // front_pack's per-lane offsets are 32-bit: a batch whose BGR spans 2^32 bytes or more runs in groups of frames
+            // (one frame always fits: h, w < 32768)
+            const size_t fpx = (size_t)h * w;
+            const int group = (int)(0xFFFFFFFFull / (fpx * 3));
+            for (int s0 = 0; s0 < n_streams; s0 += group) {
+                const int n = n_streams - s0 < group ? n_streams - s0 : group;
                 // work geometry of front_pack: full strips of 62 chunks, the remainder chunks of G frames share one wave
                 FrontGeo g{};
                 const int C = w >> 2;
-                g.S = n_streams, g.nb = (h + frows - 1) / frows, g.nfull = C / 62, g.rem = C - 62 * g.nfull;
+                g.S = n, g.nb = (h + P.frows - 1) / P.frows, g.nfull = C / 62, g.rem = C - 62 * g.nfull;
                 g.G = g.rem ? 64 / (g.rem + 2) : 0;
                 if (g.G > 16) g.G = 16;
                 g.nc = g.G > 6 ? g.G : 6;                              // 6 KB of LDS per wave: 26 waves fit a CU
-                const int ngr = g.G ? (n_streams + g.G - 1) / g.G : 0;
-                const dim3 pgrid((unsigned)(n_streams * g.nb * g.nfull + ngr * g.nb));      // one wave per workgroup
+                const int ngr = g.G ? (n + g.G - 1) / g.G : 0;
+                const dim3 pgrid((unsigned)(n * g.nb * g.nfull + ngr * g.nb));      // one wave per workgroup
                 const size_t lds = (size_t)g.nc * 1024;
-                const bool timed = getenv("AVHOT_LANE_TIMED") != nullptr && !(stages & 1);
-                if (stages & 1) hipLaunchKernelGGL((front_pack<true, 72, false>), pgrid, dim3(64), lds, st, bgr, h, w, g, blur, map, hist);
-                else if (timed && frows == 48 && getenv("AVHOT_ABL") && atoi(getenv("AVHOT_ABL")) == 1) hipLaunchKernelGGL((front_pack<false, 48, true, 1>), pgrid, dim3(64), lds, st, bgr, h, w, g, blur, map, hist);
-                else if (timed && frows == 48 && getenv("AVHOT_ABL") && atoi(getenv("AVHOT_ABL")) == 2) hipLaunchKernelGGL((front_pack<false, 48, true, 2>), pgrid, dim3(64), lds, st, bgr, h, w, g, blur, map, hist);
-                else if (timed && frows == 48 && getenv("AVHOT_ABL") && atoi(getenv("AVHOT_ABL")) == 6) hipLaunchKernelGGL((front_pack<false, 48, true, 6>), pgrid, dim3(64), lds, st, bgr, h, w, g, blur, map, hist);
-                else if (timed && frows == 48 && getenv("AVHOT_ABL") && atoi(getenv("AVHOT_ABL")) == 7) hipLaunchKernelGGL((front_pack<false, 48, true, 7>), pgrid, dim3(64), lds, st, bgr, h, w, g, blur, map, hist);
-                else if (timed && frows == 48) hipLaunchKernelGGL((front_pack<false, 48, true>), pgrid, dim3(64), lds, st, bgr, h, w, g, blur, map, hist);
-                else if (frows == 48) hipLaunchKernelGGL((front_pack<false, 48, false>), pgrid, dim3(64), lds, st, bgr, h, w, g, blur, map, hist);
-                else if (frows == 45) hipLaunchKernelGGL((front_pack<false, 45, false>), pgrid, dim3(64), lds, st, bgr, h, w, g, blur, map, hist);
-                else if (frows == 90) hipLaunchKernelGGL((front_pack<false, 90, false>), pgrid, dim3(64), lds, st, bgr, h, w, g, blur, map, hist);
-                else if (frows == 15) hipLaunchKernelGGL((front_pack<false, 15, false>), pgrid, dim3(64), lds, st, bgr, h, w, g, blur, map, hist);
-                else hipLaunchKernelGGL((front_pack<false, 72, false>), pgrid, dim3(64), lds, st, bgr, h, w, g, blur, map, hist);
-            } else
-            if (stages & 1) hipLaunchKernelGGL((front_stream<true, 72>), fgrid, dim3(256), 0, st, bgr, h, w, blur, map, hist);
-            else if (frows == 45 || frows == 48) hipLaunchKernelGGL((front_stream<false, 45>), fgrid, dim3(256), 0, st, bgr, h, w, blur, map, hist);
-            else if (frows == 90) hipLaunchKernelGGL((front_stream<false, 90>), fgrid, dim3(256), 0, st, bgr, h, w, blur, map, hist);
-            else if (frows == 15) hipLaunchKernelGGL((front_stream<false, 15>), fgrid, dim3(256), 0, st, bgr, h, w, blur, map, hist);
-            else hipLaunchKernelGGL((front_stream<false, 72>), fgrid, dim3(256), 0, st, bgr, h, w, blur, map, hist);
-            AV_LAUNCH_CHECK();
+                const uint8_t* gb = bgr + s0 * fpx * 3;
+                uint8_t *gl = blur + s0 * fpx, *gm = map + s0 * fpx;
+                unsigned* gh = hist + (size_t)s0 * 256;
+                if (stages & 1) hipLaunchKernelGGL((front_pack<true, 72>), pgrid, dim3(64), lds, st, gb, h, w, g, gl, gm, gh);
+                else if (P.frows == 48) hipLaunchKernelGGL((front_pack<false, 48>), pgrid, dim3(64), lds, st, gb, h, w, g, gl, gm, gh);
+                else hipLaunchKernelGGL((front_pack<false, 15>), pgrid, dim3(64), lds, st, gb, h, w, g, gl, gm, gh);
+                AV_LAUNCH_CHECK();
+            }
             hipLaunchKernelGGL(thresholds_kernel, dim3(n_streams), dim3(256), 0, st, h, w, hist, thr, rowcnt, npts, nseg);
             AV_LAUNCH_CHECK();
         } else {
+            // two passes with the blurred image in memory between them
+            const bool streamk = P.front == Front::Stream || P.front == Front::GivenStream;
             const dim3 sgrid((((w + SW - 1) / SW) * ((h + SROWS - 1) / SROWS) + 3) / 4, 1, n_streams);      // waves = strips x bands
-            if (given) {
+            const dim3 tiles((w + TW - 1) / TW, (h + TH - 1) / TH, n_streams);
+            if (P.front == Front::GivenStream || P.front == Front::GivenGeneric) {
                 hipLaunchKernelGGL(given_clear_kernel, dim3(n_streams), dim3(256), 0, st, h, hist, rowcnt, npts, nseg);
             } else {
-                if (streamp) hipLaunchKernelGGL(gray_blur_hist_stream, sgrid, dim3(256), 0, st, bgr, h, w, blur, hist);
-                else if (fastp) hipLaunchKernelGGL(gray_blur_hist_fast, tiles, dim3(256), 0, st, bgr, h, w, blur, hist);
+                if (streamk) hipLaunchKernelGGL(gray_blur_hist_stream, sgrid, dim3(256), 0, st, bgr, h, w, blur, hist);
                 else hipLaunchKernelGGL(gray_blur_hist_kernel, tiles, dim3(256), 0, st, bgr, h, w, blur, hist);
                 AV_LAUNCH_CHECK();
                 hipLaunchKernelGGL(thresholds_kernel, dim3(n_streams), dim3(256), 0, st, h, w, hist, thr, rowcnt, npts, nseg);
             }
             AV_LAUNCH_CHECK();
-            if (streamp) hipLaunchKernelGGL(sobel_nms_stream, sgrid, dim3(256), 0, st, blur, h, w, thr, map, labels);
-            else if (fastp) hipLaunchKernelGGL(sobel_nms_fast, tiles, dim3(256), 0, st, blur, h, w, thr, map, labels);
+            if (streamk) hipLaunchKernelGGL(sobel_nms_stream, sgrid, dim3(256), 0, st, blur, h, w, thr, map, labels);
             else hipLaunchKernelGGL(sobel_nms_kernel, tiles, dim3(256), 0, st, blur, h, w, thr, map, labels);
             AV_LAUNCH_CHECK();
         }
-        Roi roi;
-        roi.x0 = (int)(w * 0.1), roi.x1 = (int)(w * 0.4), roi.x2 = (int)(w * 0.6), roi.x3 = (int)(w * 0.9);
-        roi.yt = (int)(h * 0.6);                                       // lane_detector.py:55-60
-        int cbox[4] = {0, 0, w >> 4, h}, cbox_rows = h;               // chunk box of the resolve / compaction passes
         BitBox bb{0, 0, 0, 0, 0};
-        if (fastp) {
+        if (P.tiled) {
             // default ROI, no debug edge map: the tile pass leaves the ROI's candidates as one bit per pixel of the ROI's chunk box and
-            // the resolve / compaction passes work on bit maps (AVHOT_LANE_BYTE_RESOLVE=1: the byte-map passes of round 3)
-            bitpath = !(stages & 1) && !roi_rows && roi.yt < h && (h - roi.yt) <= CB_ROWS && !getenv("AVHOT_LANE_BYTE_RESOLVE");
-            if (bitpath) {
+            // the resolve / compaction passes work on bit maps
+            if (P.bitpath) {
                 if (!lc->d_roi || lc->roi_h != h || lc->roi_w != w) {
+                    const Roi& roi = P.roi;
                     std::vector<int> tab(2 * (size_t)h);
                     for (int y = 0; y < h; ++y) {
                         int xl = 1, xr = 0;
@@ -3106,12 +2793,10 @@ int av_lane_detect(av_ctx* ctx, av_stream_t stream, const av_lane_cfg* cfg, int 
                     AV_HIP(hipMemcpy(lc->d_roi, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
                     lc->roi_h = h, lc->roi_w = w;
                 }
-                bb.by0 = roi.yt, bb.bch = h - roi.yt;
-                bb.bx0 = roi.x0 >> 4, bb.bcw = (((roi.x3 < w ? roi.x3 : w - 1) >> 4) - bb.bx0) + 1;
-                bb.pw = (bb.bcw + 1) / 2;
+                bb = BitBox{P.bx0, P.by0, P.bcw, P.bch, (P.bcw + 1) / 2};
             }
             const dim3 tgrid((w + CT_C - 1) / CT_C, ((h + CT_R - 1) / CT_R + CT_STACK - 1) / CT_STACK, n_streams);
-            const int* rt = bitpath ? lc->d_roi : nullptr;
+            const int* rt = P.bitpath ? lc->d_roi : nullptr;
             if (fused) hipLaunchKernelGGL(ccl_tile_kernel<true>, tgrid, dim3(256), 0, st, map, h, w, thr, labels, tedge, rt, (uint16_t*)rbits, bb);
             else hipLaunchKernelGGL(ccl_tile_kernel<false>, tgrid, dim3(256), 0, st, map, h, w, thr, labels, tedge, rt, (uint16_t*)rbits, bb);
             const int nbh = (h - 1) / CT_R, nbv = (w - 1) / CT_C, span = (w > h ? w : h);
@@ -3120,38 +2805,30 @@ int av_lane_detect(av_ctx* ctx, av_stream_t stream, const av_lane_cfg* cfg, int 
                 hipLaunchKernelGGL(ccl_border_kernel, bgrid, dim3(256), 0, st, h, w, nbh, tedge, (int)tgrid.x, (int)tgrid.y, labels);
             }
             AV_LAUNCH_CHECK();
-            // chunk box the resolve pass visits: everything for the debug edge map or a caller-defined ROI, else the
-            // default trapezoid's bounding box (rows yt .. h-1, columns x0 .. x3)
-            int bx0 = 0, by0 = 0, bcw = w >> 4, bch = h;
-            if (!(stages & 1) && !roi_rows) {
-                by0 = roi.yt < h ? roi.yt : h - 1, bch = h - by0;
-                bx0 = roi.x0 >> 4, bcw = (((roi.x3 < w ? roi.x3 : w - 1) >> 4) - bx0) + 1;
-            }
-            cbox[0] = bx0, cbox[1] = by0, cbox[2] = bcw, cbox[3] = bch, cbox_rows = bch;
-            const unsigned fchunks = (unsigned)bch * (unsigned)bcw;
+            const unsigned fchunks = (unsigned)P.bch * (unsigned)P.bcw;
             const dim3 ngrid((fchunks + 256 * FCK - 1) / (256 * FCK), n_streams);
-            if (bitpath)
+            if (P.bitpath)
                 hipLaunchKernelGGL(resolve_bits_kernel, dim3(((unsigned)(bb.bch * bb.pw) + 255) / 256, n_streams), dim3(256), 0, st, h, w,
                                    labels, rbits, kbits, rowcnt, bb);
             else if (fused)
-                hipLaunchKernelGGL(finalize_fast<true>, ngrid, dim3(256), 0, st, map, h, w, thr, labels, roi, roi_rows,
-                                   (stages & 1) ? edges : nullptr, masked, rowcnt, bx0, by0, bcw, bch);
+                hipLaunchKernelGGL(finalize_fast<true>, ngrid, dim3(256), 0, st, map, h, w, thr, labels, P.roi, roi_rows,
+                                   (stages & 1) ? edges : nullptr, masked, rowcnt, P.bx0, P.by0, P.bcw, P.bch);
             else
-                hipLaunchKernelGGL(finalize_fast<false>, ngrid, dim3(256), 0, st, map, h, w, thr, labels, roi, roi_rows,
-                                   (stages & 1) ? edges : nullptr, masked, rowcnt, bx0, by0, bcw, bch);
+                hipLaunchKernelGGL(finalize_fast<false>, ngrid, dim3(256), 0, st, map, h, w, thr, labels, P.roi, roi_rows,
+                                   (stages & 1) ? edges : nullptr, masked, rowcnt, P.bx0, P.by0, P.bcw, P.bch);
         } else {
             hipLaunchKernelGGL(ccl_merge_kernel, dim3((w + 63) / 64, (h + 3) / 4, n_streams), dim3(256), 0, st, map, h, w, labels);
             AV_LAUNCH_CHECK();
-            hipLaunchKernelGGL(finalize_kernel, dim3((w + 1023) / 1024, h, n_streams), dim3(256), 0, st, map, h, w, labels, roi,
+            hipLaunchKernelGGL(finalize_kernel, dim3((w + 1023) / 1024, h, n_streams), dim3(256), 0, st, map, h, w, labels, P.roi,
                                roi_rows, (stages & 1) ? edges : nullptr, masked, rowcnt);
         }
         AV_LAUNCH_CHECK();
         // (the fallback flags overlay the first n_streams row counters of frame 0: cleared by this pass only when those lie above the
         // box rows it reads, and only when the Hough stage follows in this call)
-        const bool prep_here = bitpath && use_shard && !(stages & 2) && n_streams <= cbox[1] && fastp && cbox_rows <= CB_ROWS;
-        if (fastp && cbox_rows <= CB_ROWS)
-            hipLaunchKernelGGL(compact_box_kernel, dim3(n_streams, 4), dim3(1024), (size_t)cbox_rows * sizeof(int), st, masked, h, w,
-                               rowcnt, nz, npts, cbox[0], cbox[1], cbox[2], cbox[3], bitpath ? kbits : nullptr, bb.pw,
+        const bool prep_here = P.bitpath && use_shard && !(stages & 2) && n_streams <= P.by0;
+        if (P.tiled && P.bch <= CB_ROWS)
+            hipLaunchKernelGGL(compact_box_kernel, dim3(n_streams, 4), dim3(1024), (size_t)P.bch * sizeof(int), st, masked, h, w,
+                               rowcnt, nz, npts, P.bx0, P.by0, P.bcw, P.bch, P.bitpath ? kbits : nullptr, bb.pw,
                                prep_here ? accum : nullptr, (size_t)NUMANGLE * L.numrho, 8 * HG, rowcnt);
         else hipLaunchKernelGGL(compact_kernel, dim3(h, n_streams), dim3(256), 0, st, masked, h, w, rowcnt, nz, npts);
         AV_LAUNCH_CHECK();
@@ -3165,9 +2842,7 @@ int av_lane_detect(av_ctx* ctx, av_stream_t stream, const av_lane_cfg* cfg, int 
         AV_LAUNCH_CHECK();
         return AV_OK;
     }
-    // Hough-only calls (stage bit 4) follow a pixel-stage call of the same shape: the same path decision
-    const bool rebuild = (stages & 16) ? (fastp && !roi_rows && (int)(h * 0.6) < h && (h - (int)(h * 0.6)) <= CB_ROWS && !getenv("AVHOT_LANE_BYTE_RESOLVE"))
-                                       : bitpath;
+    const bool rebuild = P.bitpath;     // no masked byte map: the generic Hough kernel rebuilds it from the point list
     int* fb = rowcnt;       // the per-row counters are dead after compaction: their first n_streams words are the fallback flags,
     int* hpath = rowcnt + n_streams;   // the next n_streams say which kernel made a frame's segments (1 shard, 2 fast, 3 generic)
     const bool use_fast = !(stages & 8);
@@ -3184,8 +2859,7 @@ int av_lane_detect(av_ctx* ctx, av_stream_t stream, const av_lane_cfg* cfg, int 
             const char* dr = getenv("AVHOT_HOUGH_DROP");
             const int spin = sp && atoi(sp) > 0 ? atoi(sp) : HS_SPIN;
             hipLaunchKernelGGL(houghp_shard, dim3(n_streams * HG), dim3((HVW + 1) * 64), 0, st, h, w, L.numrho, hc, nz, npts, accum,
-                               lc->d_trig, segs, nseg, fb, spin, dr ? atoi(dr) : -1, hpath, getenv("AVHOT_HOUGH_TIMED") ? 1 : 0,
-                               (getenv("AVHOT_HOUGH_XCD") && atoi(getenv("AVHOT_HOUGH_XCD")) == 0) ? 0 : 1);
+                               lc->d_trig, segs, nseg, fb, spin, dr ? atoi(dr) : -1, hpath);
             AV_LAUNCH_CHECK();
         }
         hipLaunchKernelGGL(hough_tail_kernel, dim3(n_streams), dim3(192), 0, st, masked, h, w, L.numrho, hc, nz, npts, accum, lc->d_trig,

@@ -2,6 +2,8 @@
 import numpy as np
 import pytest
 
+from tests._util import LaneBatch
+
 pytestmark = pytest.mark.gpu
 
 
@@ -157,44 +159,23 @@ def test_batched_frames_take_all_three_hough_paths(LaneDetector):
     are sized so that the theta-sharded LDS kernel handles some, gives others up to the single-workgroup kernel
     (more than 4096 ROI edge points) and those give the densest one up to the generic kernel (more than 12288):
     every frame must still give the oracle's edge map, segments and fit."""
-    import ctypes as C
-    import torch
-    from multimodal_autonomous_driving_perception_and_planning_amd import _native as nat
     from oracle.lane_ref import LaneRef, synthetic_frame
     h, w, MS = 720, 1280, 2048
     frames = [synthetic_frame(h, w, 0, 0), synthetic_frame(h, w, 5, 9), _hatched(h, w, 160), synthetic_frame(h, w, 2, 33),
               np.full((h, w, 3), 90, np.uint8), _hatched(h, w, 48), synthetic_frame(h, w, 7, 2)]
     S = len(frames)
-    ctx, L, sh = nat.default_context(0), nat.lib(), nat.stream_handle()
-    dev = torch.device("cuda", 0)
-    bgr = torch.as_tensor(np.stack(frames)).to(dev)
-    ws = torch.empty(int(L.av_lane_workspace_bytes(S, h, w, MS)), dtype=torch.uint8, device=dev)
-    nat.check(L.av_lane_workspace_init(ctx.handle, sh, S, h, w, MS, nat.ptr(ws)))
-    state = torch.zeros(S, 8, dtype=torch.float64, device=dev)
-    poly = torch.zeros(S, 2, 3, dtype=torch.float64, device=dev)
-    pts = torch.zeros(S, 2, 50, 2, dtype=torch.int32, device=dev)
-    info = torch.zeros(S, 8, dtype=torch.int32, device=dev)
-    conf = torch.zeros(S, 2, dtype=torch.float64, device=dev)
-    cfg = nat.LaneCfg(50, 50, 150, MS, 0.7)
-
-    def view(what, dtype, shape):
-        off, nb = C.c_size_t(), C.c_size_t()
-        nat.check(L.av_lane_workspace_view(what, S, h, w, MS, C.byref(off), C.byref(nb)))
-        return ws[off.value:off.value + nb.value].cpu().numpy().view(dtype).reshape(shape)
-
+    lb = LaneBatch(S, h, w, MS, frames)
     refs = [LaneRef() for _ in range(S)]
     npts = []
     for rep in range(4):
         # reps 0-2: debug shape (stage bit 0: pre-ROI edge map kept, byte-map resolve); rep 3: the production shape (bit-map resolve,
         # no masked byte map -- the generic Hough kernel rebuilds its mask from the point list), EMA state carried on
-        nat.check(L.av_lane_detect(ctx.handle, sh, C.byref(cfg), S, h, w, nat.ptr(bgr), None, nat.ptr(ws), nat.ptr(state),
-                                   nat.ptr(poly), nat.ptr(pts), nat.ptr(info), nat.ptr(conf), 1 if rep < 3 else 0))
-        torch.cuda.synchronize()
-        edges = view(2, np.uint8, (S, h, w))
+        lb.run(1 if rep < 3 else 0)
+        edges = lb.view(2, np.uint8, (S, h, w))
         if rep == 3:
-            assert sorted(set(view(8, np.int32, (S,)).tolist())) == [1, 2, 3]        # all three Hough kernels, production shape
-        segs, nseg = view(5, np.int32, (S, MS, 4)), view(6, np.int32, (S,))
-        inf, po, pt, cf = info.cpu().numpy(), poly.cpu().numpy(), pts.cpu().numpy(), conf.cpu().numpy()
+            assert sorted(set(lb.view(8, np.int32, (S,)).tolist())) == [1, 2, 3]        # all three Hough kernels, production shape
+        segs, nseg = lb.view(5, np.int32, (S, MS, 4)), lb.view(6, np.int32, (S,))
+        inf, po, pt, cf = lb.info.cpu().numpy(), lb.poly.cpu().numpy(), lb.pts.cpu().numpy(), lb.conf.cpu().numpy()
         for s in range(S):
             want = refs[s].detect(frames[s])
             if rep == 0:
@@ -223,9 +204,6 @@ def test_front_end_work_geometries_in_batches(LaneDetector, h, w, S):
     15- or 48-row bands -- at widths that give every case (no full strip; no remainder; 2, 3, 5, 16 frames per remainder
     wave; frame counts that leave the last group short) through the PRODUCTION call (no debug copies): thresholds and the
     ROI-masked edge points of every frame of the batch against the oracle."""
-    import ctypes as C
-    import torch
-    from multimodal_autonomous_driving_perception_and_planning_amd import _native as nat
     from oracle.lane_ref import LaneRef
     rng = np.random.RandomState(h * 7 + w + S)
     frames = []
@@ -234,29 +212,10 @@ def test_front_end_work_geometries_in_batches(LaneDetector, h, w, S):
         f[:, : w // 3] = (f[:, : w // 3] // 32) * 32 + s                      # plateaus: ties and flat rows as well as noise
         f[h // 2:, w // 2:] = 40 + 3 * s
         frames.append(f)
-    MS = 256
-    ctx, L, sh = nat.default_context(0), nat.lib(), nat.stream_handle()
-    dev = torch.device("cuda", 0)
-    bgr = torch.as_tensor(np.stack(frames)).to(dev)
-    ws = torch.empty(int(L.av_lane_workspace_bytes(S, h, w, MS)), dtype=torch.uint8, device=dev)
-    nat.check(L.av_lane_workspace_init(ctx.handle, sh, S, h, w, MS, nat.ptr(ws)))
-    state = torch.zeros(S, 8, dtype=torch.float64, device=dev)
-    poly = torch.zeros(S, 2, 3, dtype=torch.float64, device=dev)
-    pts = torch.zeros(S, 2, 50, 2, dtype=torch.int32, device=dev)
-    info = torch.zeros(S, 8, dtype=torch.int32, device=dev)
-    conf = torch.zeros(S, 2, dtype=torch.float64, device=dev)
-    cfg = nat.LaneCfg(50, 50, 150, MS, 0.7)
-
-    def view(what, dtype, shape):
-        off, nb = C.c_size_t(), C.c_size_t()
-        nat.check(L.av_lane_workspace_view(what, S, h, w, MS, C.byref(off), C.byref(nb)))
-        return ws[off.value:off.value + nb.value].cpu().numpy().view(dtype).reshape(shape)
-
+    lb = LaneBatch(S, h, w, 256, frames)
     for rep in range(2):                                                       # the second call finds the workspace used
-        nat.check(L.av_lane_detect(ctx.handle, sh, C.byref(cfg), S, h, w, nat.ptr(bgr), None, nat.ptr(ws), nat.ptr(state),
-                                   nat.ptr(poly), nat.ptr(pts), nat.ptr(info), nat.ptr(conf), 2))
-        torch.cuda.synchronize()
-        thr, nz, npts = view(4, np.float64, (S, 4)), view(9, np.uint32, (S, h * w)), view(10, np.int32, (S,))
+        lb.run(2)
+        thr, nz, npts = lb.view(4, np.float64, (S, 4)), lb.view(9, np.uint32, (S, h * w)), lb.view(10, np.int32, (S,))
         for s in range(S):
             want = LaneRef().stages(frames[s])
             assert (thr[s, 0], thr[s, 1], thr[s, 2]) == (want["lo"], want["hi"], want["median"]), (rep, s)
@@ -266,47 +225,57 @@ def test_front_end_work_geometries_in_batches(LaneDetector, h, w, S):
             assert np.array_equal(nz[s, :npts[s]], xs.astype(np.uint32) | (ys.astype(np.uint32) << 16)), (rep, s)
 
 
+def test_front_end_past_32_bit_frame_offsets(LaneDetector):
+    """1 560 frames of 720p in one production call: the batch's BGR spans more than 2^32 bytes, past the range of the fused front
+    end's 32-bit per-lane offsets (1 553 frames), so the call runs it over groups of frames.  Frames on both sides of that split,
+    and the last one, must give the oracle's thresholds and ROI edge points.  The batch repeats four distinct frames, built on the
+    device; only the checked frames' slices are read back (the workspace is about 22 GB)."""
+    import torch
+    from oracle.lane_ref import LaneRef, synthetic_frame
+    h, w, S = 720, 1280, 1560
+    distinct = [synthetic_frame(h, w, s, 5 * s) for s in range(4)]
+    bgr = torch.as_tensor(np.stack(distinct)).to("cuda").repeat(S // 4, 1, 1, 1)              # frame s = distinct[s % 4]
+    lb = LaneBatch(S, h, w, 64, bgr)
+    lb.run(2)
+    o4, _ = lb.span(4)
+    o9, _ = lb.span(9)
+    o10, _ = lb.span(10)
+    wants = [LaneRef().stages(f) for f in distinct]
+    for s in (0, 1552, 1553, 1554, 1559):
+        want = wants[s % 4]
+        thr = lb.ws[o4 + 32 * s:o4 + 32 * (s + 1)].cpu().numpy().view(np.float64)
+        assert (thr[0], thr[1], thr[2]) == (want["lo"], want["hi"], want["median"]), s
+        ys, xs = np.nonzero(want["masked"])
+        n = int(lb.ws[o10 + 4 * s:o10 + 4 * (s + 1)].cpu().numpy().view(np.int32)[0])
+        assert n == len(ys), s
+        base = o9 + 4 * s * h * w
+        got = lb.ws[base:base + 4 * n].cpu().numpy().view(np.uint32)
+        assert np.array_equal(got, xs.astype(np.uint32) | (ys.astype(np.uint32) << 16)), s
+    del lb, bgr
+    torch.cuda.empty_cache()
+
+
 def test_sharded_hough_repeats_itself(LaneDetector):
     """The theta-sharded PPHT runs several waves per workgroup and four workgroups per frame that only meet through barriers and
     exchange words: 40 re-runs of the Hough stage on the same point lists (av_lane_detect stage bits 16: Hough + fit only) must
     give the first run's segments every time.  (A variant with two waves voting concurrently passed every single-shot parity
     test and differed in one run out of five here: a vote's returned count must include exactly the batch's earlier points.)"""
-    import ctypes as C
-    import torch
-    from multimodal_autonomous_driving_perception_and_planning_amd import _native as nat
     from oracle.lane_ref import LaneRef, synthetic_frame
     h, w, MS = 720, 1280, 512
     frames = [synthetic_frame(h, w, 0, 0), synthetic_frame(h, w, 5, 9), synthetic_frame(h, w, 2, 33), synthetic_frame(h, w, 7, 2),
               synthetic_frame(h, w, 3, 17), synthetic_frame(h, w, 11, 40)]
     S = len(frames)
-    ctx, L, sh = nat.default_context(0), nat.lib(), nat.stream_handle()
-    dev = torch.device("cuda", 0)
-    bgr = torch.as_tensor(np.stack(frames)).to(dev)
-    ws = torch.empty(int(L.av_lane_workspace_bytes(S, h, w, MS)), dtype=torch.uint8, device=dev)
-    nat.check(L.av_lane_workspace_init(ctx.handle, sh, S, h, w, MS, nat.ptr(ws)))
-    state = torch.zeros(S, 8, dtype=torch.float64, device=dev)
-    poly = torch.zeros(S, 2, 3, dtype=torch.float64, device=dev)
-    pts = torch.zeros(S, 2, 50, 2, dtype=torch.int32, device=dev)
-    info = torch.zeros(S, 8, dtype=torch.int32, device=dev)
-    conf = torch.zeros(S, 2, dtype=torch.float64, device=dev)
-    cfg = nat.LaneCfg(50, 50, 150, MS, 0.7)
-
-    def view(what, dtype, shape):
-        off, nb = C.c_size_t(), C.c_size_t()
-        nat.check(L.av_lane_workspace_view(what, S, h, w, MS, C.byref(off), C.byref(nb)))
-        return ws[off.value:off.value + nb.value].cpu().numpy().view(dtype).reshape(shape)
+    lb = LaneBatch(S, h, w, MS, frames)
 
     def run(stages):
-        nat.check(L.av_lane_detect(ctx.handle, sh, C.byref(cfg), S, h, w, nat.ptr(bgr), None, nat.ptr(ws), nat.ptr(state),
-                                   nat.ptr(poly), nat.ptr(pts), nat.ptr(info), nat.ptr(conf), stages))
-        torch.cuda.synchronize()
-        return view(6, np.int32, (S,)).copy(), view(5, np.int32, (S, MS, 4)).copy()
+        lb.run(stages)
+        return lb.view(6, np.int32, (S,)).copy(), lb.view(5, np.int32, (S, MS, 4)).copy()
 
     n0, s0 = run(0)
     for s in range(S):
         want = LaneRef().detect(frames[s])["segments"]
         assert n0[s] == len(want) and np.array_equal(s0[s, :n0[s]], want), s
-    assert info.cpu().numpy()[:, 5].max() <= 4096
+    assert lb.info.cpu().numpy()[:, 5].max() <= 4096
     for rep in range(40):
         n, sg = run(16)
         assert np.array_equal(n, n0), (rep, n, n0)
@@ -321,39 +290,21 @@ def test_fit_rank_cutoff_deviation_is_confined_to_degenerate_inputs(LaneDetector
     for endpoint rows 5 .. 120 pixels apart (segments that pass the |slope| >= 0.3 filter cannot be packed closer; what
     HoughLinesP returns with minLineLength 50 spans >= 14 rows) the fitted curves differ by at most 2e-6 pixel, printed
     per spacing: the different cut-off never decides a rank here."""
-    import ctypes as C
     import warnings
     import torch
-    from multimodal_autonomous_driving_perception_and_planning_amd import _native as nat
     h, w, MS, S = 720, 1280, 64, 1
-    ctx, L, sh = nat.default_context(0), nat.lib(), nat.stream_handle()
-    dev = torch.device("cuda", 0)
-    ws = torch.zeros(int(L.av_lane_workspace_bytes(S, h, w, MS)), dtype=torch.uint8, device=dev)
-    state = torch.zeros(S, 8, dtype=torch.float64, device=dev)
-    poly = torch.zeros(S, 2, 3, dtype=torch.float64, device=dev)
-    pts = torch.zeros(S, 2, 50, 2, dtype=torch.int32, device=dev)
-    info = torch.zeros(S, 8, dtype=torch.int32, device=dev)
-    conf = torch.zeros(S, 2, dtype=torch.float64, device=dev)
-    cfg = nat.LaneCfg(50, 50, 150, MS, 0.7)
-    frame = torch.zeros(S, h, w, 3, dtype=torch.uint8, device=dev)
-
-    def view_off(what):
-        off, nb = C.c_size_t(), C.c_size_t()
-        nat.check(L.av_lane_workspace_view(what, S, h, w, MS, C.byref(off), C.byref(nb)))
-        return off.value, nb.value
+    lb = LaneBatch(S, h, w, MS, torch.zeros(S, h, w, 3, dtype=torch.uint8, device="cuda"))
 
     def device_fit(segs):
-        o5, n5 = view_off(5)
-        o6, _ = view_off(6)
+        o5, n5 = lb.span(5)
+        o6, _ = lb.span(6)
         buf = np.zeros((MS, 4), np.int32)
         buf[:len(segs)] = segs
-        ws[o5:o5 + n5].copy_(torch.as_tensor(buf.view(np.uint8).reshape(-1)))
-        ws[o6:o6 + 4].copy_(torch.as_tensor(np.array([len(segs)], np.int32).view(np.uint8)))
-        state.zero_()
-        nat.check(L.av_lane_detect(ctx.handle, sh, C.byref(cfg), S, h, w, nat.ptr(frame), None, nat.ptr(ws), nat.ptr(state),
-                                   nat.ptr(poly), nat.ptr(pts), nat.ptr(info), nat.ptr(conf), 16 | 32))
-        torch.cuda.synchronize()
-        return poly.cpu().numpy()[0, 0].copy(), int(info.cpu().numpy()[0, 0])
+        lb.ws[o5:o5 + n5].copy_(torch.as_tensor(buf.view(np.uint8).reshape(-1)))
+        lb.ws[o6:o6 + 4].copy_(torch.as_tensor(np.array([len(segs)], np.int32).view(np.uint8)))
+        lb.state.zero_()
+        lb.run(16 | 32)
+        return lb.poly.cpu().numpy()[0, 0].copy(), int(lb.info.cpu().numpy()[0, 0])
 
     worst = {}
     for spread in (1, 2, 3, 5, 8, 14, 40, 120):
