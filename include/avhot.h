@@ -301,7 +301,12 @@ int av_lane_detect(av_ctx* ctx, av_stream_t stream, const av_lane_cfg* cfg, int 
  * the parameter order documented in perception/yolo.py (per conv: weight[cout][cin][k][k], then BN
  * gamma, beta, running_mean, running_var or, for the two plain Conv2d of each head branch, bias);
  * BatchNorm is folded and everything is converted to IEEE half at creation (float32 accumulation).  All activation and NMS scratch
- * is allocated here, once. */
+ * is allocated here, once, and the launches of a forward are planned here: a shape that no kernel serves fails at creation.
+ * Test hooks, read from the environment once per forward (a change re-plans the launches; outputs stay bit-identical, which is what
+ * tests/test_gpu_yolo.py asserts with them): AVHOT_YOLO_NO_FUSE (one launch per layer: no fused front end, no fused C2f blocks, no
+ * virtual Upsample + Concat), AVHOT_CONV_GENERIC80 (the 80-channel layers of the class branch on the generic kernels),
+ * AVHOT_CONV_NO_GEMM (no GEMM-form convolution), AVHOT_CONV_NO_GEMM_1X1 (none for the 1x1 layers), AVHOT_YOLO_GENERIC_PRE (the
+ * generic letterbox kernel for every frame shape).  The library reads no other variable for this stage. */
 typedef struct av_yolo av_yolo;
 size_t av_yolo_param_count(void);
 int av_yolo_create(av_ctx* ctx, int batch, int in_h, int in_w, const float* weights, size_t n_weights,

@@ -16,8 +16,10 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -63,10 +65,8 @@ __device__ __forceinline__ float silu(float v) {
 
 // Progress-ordered wave priority for the persistent tile loops (lane.hip, front_pack, and DESIGN.md section 4 "front end"): waves of
 // equal priority are served oldest first, so workgroups that share a CU finish one after the other and the last one runs at low
-// occupancy.  A workgroup lowers its priority as its tiles go by (3 -> 0); AVHOT_YOLO_PRIO=0 in the environment disables it.
-__device__ int g_yolo_prio = 1;
+// occupancy.  A workgroup lowers its priority as its tiles go by (3 -> 0).
 __device__ __forceinline__ void progress_prio(int t, int n_tiles) {
-    if (!g_yolo_prio) return;
     const int q = (4 * t) / (n_tiles > 0 ? n_tiles : 1);            // t runs over the whole grid's tiles: same fraction for every workgroup
     if (q <= 0) __builtin_amdgcn_s_setprio(3);
     else if (q == 1) __builtin_amdgcn_s_setprio(2);
@@ -1573,21 +1573,6 @@ __global__ void __launch_bounds__(FR_NTH, 4) front_fused_kernel(FrontArgs a) {
     }
 }
 
-__global__ void maxpool5_kernel(const half_t* in, int cs_in, int coff_in, half_t* out, int cs_out, int coff_out, int B,
-                                int H, int W, int C) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= B * H * W * C) return;
-    const int c = i % C, p = i / C, n = p / (H * W), r = p - n * H * W, y = r / W, x = r - y * W;
-    float m = -INFINITY;
-    for (int dy = -2; dy <= 2; ++dy)
-        for (int dx = -2; dx <= 2; ++dx) {
-            const int yy = y + dy, xx = x + dx;
-            if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
-            m = fmaxf(m, h2f(in[((size_t)(n * H + yy) * W + xx) * cs_in + coff_in + c]));
-        }
-    out[(size_t)p * cs_out + coff_out + c] = f2h(m);
-}
-
 // SPPF's three chained 5x5/stride-1 max-pools (padding -inf) in one pass: pool(pool(x)) is the 9x9 window of x
 // and the third the 13x13 one, so all three come from one LDS copy of the map, separably (row maxima of
 // radius 2/4/6, then column maxima).  Workgroup = (image, 8-channel slab), thread = pixel, 16-byte accesses.
@@ -2183,14 +2168,116 @@ __global__ void upsample2_f32_kernel(const float* in, int cs_in, int coff_in, fl
 struct Buf { half_t* p = nullptr; int C = 0, H = 0, W = 0; };     // (reference-precision mode: the same pointer holds float elements)
 struct Slice { int buf, coff, c; };
 
+enum OpKind { OP_CONV, OP_STEM, OP_POOLS, OP_MAXPOOL, OP_UPSAMPLE, OP_CONV_F32 };     // OP_POOLS: SPPF's three pools in one launch (half); OP_MAXPOOL: one of them (float32)
+
+// Test hooks from the environment, read once per forward (tests/test_gpu_yolo.py flips them between two forwards of one handle to
+// pin a fast kernel bit for bit against a generic one).  They are the only environment this file reads.
+struct Hooks {
+    bool no_fuse, generic80, no_gemm, no_gemm_1x1, generic_pre;
+    bool operator==(const Hooks& o) const { return memcmp(this, &o, sizeof o) == 0; }
+};
+Hooks read_hooks() {
+    Hooks h;
+    h.no_fuse = getenv("AVHOT_YOLO_NO_FUSE") != nullptr;            // one launch per layer: no front / C2f fusion, no virtual Upsample + Concat
+    h.generic80 = getenv("AVHOT_CONV_GENERIC80") != nullptr;        // the cin = 80 layers on the generic kernels
+    h.no_gemm = getenv("AVHOT_CONV_NO_GEMM") != nullptr;            // no conv_gemm128_kernel at all
+    h.no_gemm_1x1 = getenv("AVHOT_CONV_NO_GEMM_1X1") != nullptr;    // no conv_gemm128_kernel for the 1x1 layers
+    h.generic_pre = getenv("AVHOT_YOLO_GENERIC_PRE") != nullptr;    // preprocess_kernel for every frame shape
+    return h;
+}
+
+// Every kernel instantiation that a launch is chosen from or that needs more dynamic LDS than the default 64 KB: the choosers below
+// find their kernel here and nowhere else, and av_yolo_create_ex raises the limits from the same rows -- so a variant that is not
+// listed cannot be launched, and a listed one has its limit.  lds_limit 0: the default is enough.
+enum Family { K_MFMA, K_GEMM128, K_LDS, K_WS3, K_WS1, K_GEMM_F32, K_STEM_F32, K_FIXED };     // K_FIXED: launched by name from one place
+struct Variant { Family fam; int p[6]; const void* fn; int lds_limit; };
+#define AV_KT(fam, limit, kernel, ...) {fam, {__VA_ARGS__}, reinterpret_cast<const void*>(&kernel<__VA_ARGS__>), limit}
+#define AV_K(limit, kernel) {K_FIXED, {}, reinterpret_cast<const void*>(&kernel), limit}
+const Variant kVariants[] = {
+    // generic fallback, any shape
+    AV_KT(K_MFMA, 0, conv_mfma_kernel, 2, 2), AV_KT(K_MFMA, 0, conv_mfma_kernel, 4, 2), AV_KT(K_MFMA, 0, conv_mfma_kernel, 5, 2),
+    {K_GEMM128, {}, reinterpret_cast<const void*>(&conv_gemm128_kernel), 160 * 1024},
+    // <MT, KS>
+    AV_KT(K_LDS, 100 * 1024, conv_lds_kernel, 4, 1), AV_KT(K_LDS, 100 * 1024, conv_lds_kernel, 4, 3), AV_KT(K_LDS, 100 * 1024, conv_lds_kernel, 5, 3),
+    // <MT, NT, NW, CINP, RES, S>: stride 1 with 8 or 16 tile rows, with and without residual; stride 2
+    AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 1, 1, 8, 32, false, 1), AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 1, 1, 8, 32, true, 1),
+    AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 1, 2, 8, 32, false, 1), AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 1, 2, 8, 32, true, 1),
+    AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 2, 1, 8, 32, false, 1), AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 2, 1, 8, 32, true, 1),
+    AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 2, 2, 8, 32, false, 1), AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 2, 2, 8, 32, true, 1),
+    AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 4, 1, 8, 64, false, 1), AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 4, 1, 8, 64, true, 1),
+    AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 4, 2, 8, 64, false, 1), AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 4, 2, 8, 64, true, 1),
+    AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 5, 1, 8, 64, false, 1), AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 5, 2, 8, 64, false, 1),
+    AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 5, 1, 8, 80, false, 1),
+    AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 2, 1, 8, 32, false, 2), AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 4, 1, 8, 32, false, 2),
+    AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 4, 1, 8, 64, false, 2),
+    // <MT, KS, TAIL16, DEC>: the head's last box / class convolutions with the decode in their epilogue, then the plain ones
+    AV_KT(K_WS1, 0, conv1x1_ws_kernel, 4, 2, false, 1), AV_KT(K_WS1, 0, conv1x1_ws_kernel, 5, 2, true, 2),
+    AV_KT(K_WS1, 100 * 1024, conv1x1_ws_kernel, 2, 1, false, 0), AV_KT(K_WS1, 100 * 1024, conv1x1_ws_kernel, 4, 2, false, 0),
+    AV_KT(K_WS1, 100 * 1024, conv1x1_ws_kernel, 4, 3, false, 0), AV_KT(K_WS1, 100 * 1024, conv1x1_ws_kernel, 4, 4, false, 0),
+    AV_KT(K_WS1, 100 * 1024, conv1x1_ws_kernel, 4, 6, false, 0), AV_KT(K_WS1, 100 * 1024, conv1x1_ws_kernel, 4, 8, false, 0),
+    AV_KT(K_WS1, 100 * 1024, conv1x1_ws_kernel, 4, 12, false, 0), AV_KT(K_WS1, 100 * 1024, conv1x1_ws_kernel, 4, 16, false, 0),
+    // float32 chain <AR, BR, KC>; its stem <MT, NT, CB, D>
+    AV_KT(K_GEMM_F32, 100 * 1024, conv_gemm_f32_kernel, 128, 64, 32), AV_KT(K_GEMM_F32, 100 * 1024, conv_gemm_f32_kernel, 64, 128, 32),
+    AV_KT(K_GEMM_F32, 100 * 1024, conv_gemm_f32_kernel, 80, 128, 32), AV_KT(K_GEMM_F32, 100 * 1024, conv_gemm_f32_kernel, 80, 128, 16),
+    AV_KT(K_GEMM_F32, 0, conv_gemm_f32_kernel, 32, 128, 32), AV_KT(K_GEMM_F32, 0, conv_gemm_f32_kernel, 32, 128, 16),
+    AV_KT(K_GEMM_F32, 0, conv_gemm_f32_kernel, 16, 128, 16),
+    AV_KT(K_STEM_F32, 0, conv_f32_kernel, 1, 1, 4, 2), AV_KT(K_STEM_F32, 0, conv_f32_kernel, 1, 2, 4, 2), AV_KT(K_STEM_F32, 0, conv_f32_kernel, 1, 4, 4, 2),
+    AV_K(C2F_LDS, c2f16_fused_kernel), AV_K(FR_LDS, front_fused_kernel), AV_K(F32H_LDS, c2f32_head_kernel),
+    AV_K(f32t_lds(96), (c2f32_tail_kernel<96, true>)), AV_K(f32t_lds(64), (c2f32_tail_kernel<64, false>)),
+    AV_K((int)rs_lds(7, 8), nms_sort_kernel<8>), AV_K((int)rs_lds(8, 7), nms_sort_kernel<7>),
+};
+#undef AV_KT
+#undef AV_K
+
+const Variant* find_variant(Family fam, const int (&p)[6]) {
+    for (const Variant& v : kVariants)
+        if (v.fam == fam && std::equal(p, p + 6, v.p)) return &v;
+    return nullptr;
+}
+
+// One launch of the network part of a forward: the kernel's address, the launch dimensions and the kernel's parameters by value, in
+// its order, the way hipLaunchKernel takes them.
+enum When { ALWAYS, BGR_ALIGNED, BGR_UNALIGNED };      // the frame pointer's 4-byte alignment is the one input to a choice that a call brings
+template <typename T> struct as_is { using type = T; };
+struct Step {
+    const void* fn = nullptr;
+    dim3 grid, block;
+    size_t lds = 0;
+    When when = ALWAYS;
+    int lane = 0;                        // 1: the side stream
+    bool head = false;                   // the Detect head begins here: everything before it is one dependency chain
+    bool takes_bgr = false;              // the kernel's first parameter begins with the frame pointer, which every call brings
+    alignas(16) unsigned char params[384];
+    int off[12], nargs = 0;
+    template <typename... A>
+    void args(const A&... a) {
+        static_assert((sizeof(A) + ... + 0) + 16 * sizeof...(A) <= sizeof(Step::params) && sizeof...(A) <= 12, "parameters fit");
+        size_t pos = 0;
+        nargs = 0;
+        auto put = [&](const auto& v) {
+            static_assert(std::is_trivially_copyable<std::decay_t<decltype(v)>>::value, "kernel parameters are plain data");
+            pos = (pos + alignof(decltype(v)) - 1) / alignof(decltype(v)) * alignof(decltype(v));
+            memcpy(params + pos, &v, sizeof v);
+            off[nargs++] = (int)pos, pos += sizeof v;
+        };
+        (put(a), ...);
+    }
+    // a kernel known by name: the parameters are converted to its own types, as a <<< >>> launch would
+    template <typename... P>
+    void kernel(void (*k)(P...), dim3 g, dim3 b, size_t l, const typename as_is<P>::type&... a) {
+        fn = reinterpret_cast<const void*>(k), grid = g, block = b, lds = l;
+        args<P...>(a...);
+    }
+};
+
 struct Yolo {
     av_ctx* ctx = nullptr;
     int B = 0, inH = 0, inW = 0, H = 0, W = 0, nh = 0, nw = 0, top = 0, left = 0, A = 0, words = 0;
     float gain = 1.f;
     std::vector<Buf> bufs;
     float* f32_zeros = nullptr;
-    bool f32 = false;                    // reference-precision mode: float32 tensors and weights, conv_f32_kernel, no fusion
-    struct Op { int kind; ConvArgs ca; ConvArgsF cf; int mt; Slice in, out; int H, W, C; int lane = 0; int fuse = 0; int dec = 0, dec_level = 0; int vcat = -1; };   // lane 1: internal side stream;
+    bool f32 = false;                    // reference-precision mode: float32 tensors and weights, conv_gemm_f32_kernel, no fusion
+    struct Op { OpKind kind; ConvArgs ca; ConvArgsF cf; int mt; Slice in, out; int H, W, C; int lane = 0; int fuse = 0; int dec = 0, dec_level = 0; int vcat = -1; };   // lane 1: internal side stream;
     // vcat >= 0 (an upsample op): op index of the 1x1 convolution that can read this upsample's source directly (virtual Upsample + Concat);
     // fuse 1: this op and the next three are a C2f block c2f16_fused_kernel can run in one launch; 2 / 3: 32-channel blocks (c2f32_*); dec 1 / 2: the head's last box /
     // class convolution of level dec_level (its epilogue can do the decode)
@@ -2200,12 +2287,16 @@ struct Yolo {
     // of forward k+1 -- they occupy one workgroup per image and ~0.25 ms, the latency-bound end of an otherwise
     // chip-wide chain.  Outputs are complete after av_yolo_join_tail().
     hipStream_t tail = nullptr;
-    hipEvent_t ev_heads = nullptr, ev_decoded = nullptr, ev_tail = nullptr;
+    hipEvent_t ev_heads = nullptr, ev_tail = nullptr;
     bool defer_tail = false, tail_pending = false;
     bool keep_logits = false;            // test hook: also write the float32 head logits and run decode_kernel on them
     int dbg_cat = -1;                    // test hook: layer 4's concat buffer (tensor id 40)
-    int head_begin = -1;                 // first op of the head (everything before it is one dependency chain)
+    int head_begin = -1;                 // first op of the head
     std::vector<Op> ops;
+    // the launches of a forward, and what they were planned for: rebuilt only when a hook or keep_logits changes
+    std::vector<Step> plan;
+    Hooks plan_hooks{};
+    bool plan_keep_logits = false;
     std::vector<void*> allocs;
     float* head_box[3] = {nullptr, nullptr, nullptr};
     float* head_cls[3] = {nullptr, nullptr, nullptr};
@@ -2225,6 +2316,14 @@ bool dev_alloc(Yolo& y, void** p, size_t bytes) {
     return true;
 }
 
+template <typename T>
+T* upload(Yolo& y, const std::vector<T>& v) {
+    T* d;
+    if (!dev_alloc(y, (void**)&d, v.size() * sizeof(T))) return nullptr;
+    (void)hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+    return d;
+}
+
 int new_buf(Yolo& y, int H, int W, int C) {
     Buf b;
     b.C = C, b.H = H, b.W = W;
@@ -2233,123 +2332,124 @@ int new_buf(Yolo& y, int H, int W, int C) {
     return (int)y.bufs.size() - 1;
 }
 
+// the next nw weights and their bias (cout values) or BatchNorm parameters (4 cout) from the parameter blob
+bool take_params(Yolo& y, size_t nw, int cout, bool bn_act, const float*& w, const float*& bp) {
+    const size_t nb = bn_act ? 4 * (size_t)cout : (size_t)cout;
+    if (y.wpos + nw + nb > y.wtotal) return false;
+    w = y.wsrc + y.wpos, bp = w + nw;
+    y.wpos += nw + nb;
+    return true;
+}
+
+// BatchNorm (eval) of output channel co as a scale of its weights and a bias, in float32 as ultralytics' fuse() does; a layer
+// without BatchNorm has a plain bias
+void fold_bn(const float* bp, int cout, bool bn_act, int co, float& scale, float& shift) {
+    scale = 1.f, shift = bp[co];
+    if (bn_act) {
+        const float g = bp[co], be = bp[cout + co], mu = bp[2 * cout + co], var = bp[3 * cout + co];
+        scale = g / std::sqrt(var + 1e-3f);
+        shift = be - mu * scale;
+    }
+}
+
+int mt_of(int cout) { return (cout % 64 == 0) ? 4 : ((cout % 80 == 0) ? 5 : ((cout % 32 == 0) ? 2 : 1)); }
+
+// what ConvArgs and ConvArgsF share: input, output and residual slices (an `out` without a buffer: the caller sets the output), sizes
+template <typename Args>
+void conv_geometry(const Yolo& y, Args& a, Slice in, Slice out, int k, int s, bool bn_act, const Slice* res) {
+    using T = std::remove_pointer_t<decltype(a.out)>;
+    auto at = [&](int buf) { return reinterpret_cast<T*>(y.bufs[buf].p); };
+    const Buf& bi = y.bufs[in.buf];
+    a.in = at(in.buf), a.in_cs = bi.C, a.in_coff = in.coff, a.cin = in.c, a.H = bi.H, a.W = bi.W;
+    a.ksz = k, a.stride = s, a.cout = out.c;
+    a.Ho = (bi.H + 2 * (k / 2) - k) / s + 1, a.Wo = (bi.W + 2 * (k / 2) - k) / s + 1;
+    if (out.buf >= 0) a.out = at(out.buf), a.out_cs = y.bufs[out.buf].C, a.out_coff = out.coff;
+    if (res) a.res = at(res->buf), a.res_cs = y.bufs[res->buf].C, a.res_coff = res->coff;
+    a.act = bn_act ? 1 : 0, a.npix = y.B * a.Ho * a.Wo;
+}
+
 // consumes one conv's parameters, folds BN, uploads half [cout][kpad] + f32 bias, appends the op
-bool add_conv(Yolo& y, Slice in, Slice out, int k, int s, bool bn_act, float* out32, int out32_cs, const Slice* res) {
-    const int cin_real = in.c;
+bool add_conv_half(Yolo& y, Slice in, Slice out, int k, int s, bool bn_act, float* out32, int out32_cs, const Slice* res) {
     const int cin = in.c, cout = out.c, taps = k * k;
     const int kreal = taps * cin, kpad = (kreal + 31) & ~31;
-    const size_t nw = (size_t)cout * cin_real * taps, nb = bn_act ? 4 * (size_t)cout : (size_t)cout;
-    if (y.wpos + nw + nb > y.wtotal) return false;
-    const float* w = y.wsrc + y.wpos;
-    const float* bp = w + nw;
-    y.wpos += nw + nb;
-    if (y.f32) {
-        // float32 weights [cout][tap][cin] with BatchNorm folded in float32 (gamma / sqrt(var + eps) applied to the weights, as
-        // ultralytics' fuse() does); an input of 4 channels whose parameters have 3 (the stem) gets a zero fourth channel
-        const int cin_w = (cin == 4 && k == 3 && s == 2 && y.ops.empty()) ? 3 : cin;
-        const size_t nwf = (size_t)cout * cin_w * taps;
-        y.wpos -= nw + nb;
-        if (y.wpos + nwf + nb > y.wtotal) return false;
-        const float* bpf = w + nwf;
-        y.wpos += nwf + nb;
-        std::vector<float> wf((size_t)cout * taps * cin, 0.f), bias(cout);
-        for (int co = 0; co < cout; ++co) {
-            float scale = 1.f, sh = bpf[co];
-            if (bn_act) {
-                const float g = bpf[co], be = bpf[cout + co], mu = bpf[2 * cout + co], var = bpf[3 * cout + co];
-                scale = g / std::sqrt(var + 1e-3f);
-                sh = be - mu * scale;
-            }
-            bias[co] = sh;
-            for (int ci = 0; ci < cin_w; ++ci)
-                for (int t = 0; t < taps; ++t) wf[((size_t)co * taps + t) * cin + ci] = w[((size_t)co * cin_w + ci) * taps + t] * scale;
-        }
-        float *dw, *db;
-        if (!dev_alloc(y, (void**)&dw, wf.size() * 4) || !dev_alloc(y, (void**)&db, bias.size() * 4)) return false;
-        (void)hipMemcpy(dw, wf.data(), wf.size() * 4, hipMemcpyHostToDevice);
-        (void)hipMemcpy(db, bias.data(), bias.size() * 4, hipMemcpyHostToDevice);
-        const Buf& bi = y.bufs[in.buf];
-        Yolo::Op op{};
-        op.kind = 10;
-        ConvArgsF& a = op.cf;
-        a.in = reinterpret_cast<const float*>(bi.p), a.in_cs = bi.C, a.in_coff = in.coff, a.cin = cin, a.H = bi.H, a.W = bi.W;
-        a.wgt = dw, a.bias = db, a.ksz = k, a.stride = s;
-        a.Ho = (bi.H + 2 * (k / 2) - k) / s + 1, a.Wo = (bi.W + 2 * (k / 2) - k) / s + 1;
-        if (out32) a.out = out32, a.out_cs = out32_cs, a.out_coff = 0;
-        else a.out = reinterpret_cast<float*>(y.bufs[out.buf].p), a.out_cs = y.bufs[out.buf].C, a.out_coff = out.coff;
-        a.cout = cout;
-        a.res = nullptr, a.res_cs = 0, a.res_coff = 0;
-        if (res) a.res = reinterpret_cast<const float*>(y.bufs[res->buf].p), a.res_cs = y.bufs[res->buf].C, a.res_coff = res->coff;
-        a.act = bn_act ? 1 : 0, a.npix = y.B * a.Ho * a.Wo;
-        if (!y.f32_zeros && !dev_alloc(y, (void**)&y.f32_zeros, 64)) return false;      // (dev_alloc clears)
-        a.zeros = y.f32_zeros;
-        op.mt = (cout % 64 == 0) ? 4 : ((cout % 80 == 0) ? 5 : ((cout % 32 == 0) ? 2 : 1));
-        y.ops.push_back(op);
-        return true;
-    }
+    const float *w, *bp;
+    if (!take_params(y, (size_t)cout * cin * taps, cout, bn_act, w, bp)) return false;
     std::vector<half_t> wb((size_t)cout * kpad, (half_t)0);
     std::vector<float> bias(cout);
     for (int co = 0; co < cout; ++co) {
-        float scale = 1.f, sh = bp[co];
-        if (bn_act) {
-            const float g = bp[co], be = bp[cout + co], mu = bp[2 * cout + co], var = bp[3 * cout + co];
-            scale = g / std::sqrt(var + 1e-3f);
-            sh = be - mu * scale;
-        }
-        bias[co] = sh;
-        for (int ci = 0; ci < cin_real; ++ci)
+        float scale;
+        fold_bn(bp, cout, bn_act, co, scale, bias[co]);
+        for (int ci = 0; ci < cin; ++ci)
             for (int t = 0; t < taps; ++t)
-                wb[(size_t)co * kpad + t * cin + ci] = f2h(w[((size_t)co * cin_real + ci) * taps + t] * scale);
+                wb[(size_t)co * kpad + t * cin + ci] = f2h(w[((size_t)co * cin + ci) * taps + t] * scale);
     }
-    half_t* dw;
-    float* db;
-    if (!dev_alloc(y, (void**)&dw, wb.size() * 2) || !dev_alloc(y, (void**)&db, bias.size() * 4)) return false;
-    (void)hipMemcpy(dw, wb.data(), wb.size() * 2, hipMemcpyHostToDevice);
-    (void)hipMemcpy(db, bias.data(), bias.size() * 4, hipMemcpyHostToDevice);
-    const Buf& bi = y.bufs[in.buf];
+    const half_t* dw = upload(y, wb);
+    const float* db = upload(y, bias);
+    if (!dw || !db) return false;
     Yolo::Op op{};
-    op.kind = 0;
+    op.kind = OP_CONV;
     ConvArgs& a = op.ca;
-    a.in = bi.p, a.in_cs = bi.C, a.in_coff = in.coff, a.cin = cin, a.H = bi.H, a.W = bi.W;
-    a.wgt = dw, a.bias = db, a.kpad = kpad, a.kreal = kreal, a.ksz = k, a.stride = s;
-    a.Ho = (bi.H + 2 * (k / 2) - k) / s + 1, a.Wo = (bi.W + 2 * (k / 2) - k) / s + 1;
+    conv_geometry(y, a, in, out, k, s, bn_act, res);
+    a.wgt = dw, a.bias = db, a.kpad = kpad, a.kreal = kreal;
     if (out32) a.out = nullptr, a.out32 = out32, a.out_cs = out32_cs, a.out_coff = 0;
-    else a.out = y.bufs[out.buf].p, a.out32 = nullptr, a.out_cs = y.bufs[out.buf].C, a.out_coff = out.coff;
-    a.cout = cout;
-    a.res = nullptr, a.res_cs = 0, a.res_coff = 0;
-    if (res) a.res = y.bufs[res->buf].p, a.res_cs = y.bufs[res->buf].C, a.res_coff = res->coff;
-    a.act = bn_act ? 1 : 0, a.npix = y.B * a.Ho * a.Wo;
-    a.in2 = nullptr, a.in2_cs = 0, a.in2_coff = 0, a.k1 = 0;
-    op.mt = (cout % 64 == 0) ? 4 : ((cout % 80 == 0) ? 5 : ((cout % 32 == 0) ? 2 : 1));
+    op.mt = mt_of(cout);
     y.ops.push_back(op);
     return true;
+}
+
+// the same for the reference-precision chain: float32 weights [cout][tap][cin]; an input of 4 channels whose parameters have 3 (the
+// stem) gets a zero fourth channel
+bool add_conv_f32(Yolo& y, Slice in, Slice out, int k, int s, bool bn_act, float* out32, int out32_cs, const Slice* res) {
+    const int cin = in.c, cout = out.c, taps = k * k;
+    const int cin_w = (cin == 4 && k == 3 && s == 2 && y.ops.empty()) ? 3 : cin;
+    const float *w, *bp;
+    if (!take_params(y, (size_t)cout * cin_w * taps, cout, bn_act, w, bp)) return false;
+    std::vector<float> wf((size_t)cout * taps * cin, 0.f), bias(cout);
+    for (int co = 0; co < cout; ++co) {
+        float scale;
+        fold_bn(bp, cout, bn_act, co, scale, bias[co]);
+        for (int ci = 0; ci < cin_w; ++ci)
+            for (int t = 0; t < taps; ++t) wf[((size_t)co * taps + t) * cin + ci] = w[((size_t)co * cin_w + ci) * taps + t] * scale;
+    }
+    const float* dw = upload(y, wf);
+    const float* db = upload(y, bias);
+    if (!dw || !db) return false;
+    Yolo::Op op{};
+    op.kind = OP_CONV_F32;
+    ConvArgsF& a = op.cf;
+    conv_geometry(y, a, in, out, k, s, bn_act, res);
+    a.wgt = dw, a.bias = db;
+    if (out32) a.out = out32, a.out_cs = out32_cs, a.out_coff = 0;
+    if (!y.f32_zeros && !dev_alloc(y, (void**)&y.f32_zeros, 64)) return false;      // (dev_alloc clears)
+    a.zeros = y.f32_zeros;
+    op.mt = mt_of(cout);
+    y.ops.push_back(op);
+    return true;
+}
+
+bool add_conv(Yolo& y, Slice in, Slice out, int k, int s, bool bn_act, float* out32, int out32_cs, const Slice* res) {
+    return y.f32 ? add_conv_f32(y, in, out, k, s, bn_act, out32, out32_cs, res) : add_conv_half(y, in, out, k, s, bn_act, out32, out32_cs, res);
 }
 
 // the stem's parameters (Conv 3 -> 16, k3 s2, BN, SiLU) packed for stem_conv_kernel: half [16][64], k = ky*16 + kx*4 + c
 bool add_stem(Yolo& y, Slice in, Slice out) {
     const int cout = 16, cin_real = 3, taps = 9;
-    const size_t nw = (size_t)cout * cin_real * taps, nb = 4 * (size_t)cout;
-    if (out.c != cout || y.wpos + nw + nb > y.wtotal) return false;
-    const float* w = y.wsrc + y.wpos;
-    const float* bp = w + nw;
-    y.wpos += nw + nb;
+    const float *w, *bp;
+    if (out.c != cout || !take_params(y, (size_t)cout * cin_real * taps, cout, true, w, bp)) return false;
     std::vector<half_t> wb((size_t)cout * 64, (half_t)0);
     std::vector<float> bias(cout);
     for (int co = 0; co < cout; ++co) {
-        const float g = bp[co], be = bp[cout + co], mu = bp[2 * cout + co], var = bp[3 * cout + co];
-        const float scale = g / std::sqrt(var + 1e-3f);
-        bias[co] = be - mu * scale;
+        float scale;
+        fold_bn(bp, cout, true, co, scale, bias[co]);
         for (int ci = 0; ci < cin_real; ++ci)
             for (int t = 0; t < taps; ++t)
                 wb[(size_t)co * 64 + (t / 3) * 16 + (t % 3) * 4 + ci] = f2h(w[((size_t)co * cin_real + ci) * taps + t] * scale);
     }
-    half_t* dw;
-    float* db;
-    if (!dev_alloc(y, (void**)&dw, wb.size() * 2) || !dev_alloc(y, (void**)&db, bias.size() * 4)) return false;
-    (void)hipMemcpy(dw, wb.data(), wb.size() * 2, hipMemcpyHostToDevice);
-    (void)hipMemcpy(db, bias.data(), bias.size() * 4, hipMemcpyHostToDevice);
+    const half_t* dw = upload(y, wb);
+    const float* db = upload(y, bias);
+    if (!dw || !db) return false;
     Yolo::Op op{};
-    op.kind = 4;
+    op.kind = OP_STEM;
     ConvArgs& a = op.ca;
     a.in = y.bufs[in.buf].p, a.in_cs = 4, a.in_coff = 0, a.cin = 4, a.H = y.H, a.W = y.W;      // H, W: without the frame
     a.wgt = dw, a.bias = db, a.kpad = 64, a.kreal = 27, a.ksz = 3, a.stride = 2;
@@ -2381,7 +2481,7 @@ bool add_c2f(Yolo& y, Slice in, Slice out, int n, bool shortcut) {
     return true;
 }
 
-void add_simple(Yolo& y, int kind, Slice in, Slice out, int H, int W, int C) {
+void add_simple(Yolo& y, OpKind kind, Slice in, Slice out, int H, int W, int C) {
     Yolo::Op op{};
     op.kind = kind, op.in = in, op.out = out, op.H = H, op.W = W, op.C = C;
     y.ops.push_back(op);
@@ -2397,248 +2497,17 @@ void letterbox(int h, int w, float& r, int& nh, int& nw, int& top, int& left, in
     H = nh + top + bottom, W = nw + left + right;
 }
 
-// one layer of the network, for all B images, on stream st
-int launch_op(Yolo& y, const Yolo::Op& op, hipStream_t st, int B, bool force_direct) {
-    if (op.kind == 4) {
-        const ConvArgs& a = op.ca;
-        hipLaunchKernelGGL(stem_conv_kernel, dim3((a.npix + 255) / 256), dim3(256), 0, st, a, a.npix);
-    } else if (op.kind == 0) {
-        const ConvArgs& a = op.ca;
-        // measured per layer (profiles/r01_yolo_b64_*): the LDS kernel wins for stride-1 3x3 (any cin >= 16, the tail of
-        // a partial 32-channel chunk is zero-filled) and for 1x1 with whole chunks; stride 2 and the rest stay direct
-        const bool lds_ok = a.stride == 1 && ((a.ksz == 3 && a.cin >= 16 && a.cin % 8 == 0) || (a.ksz == 1 && a.cin % LT_CK == 0));
-        DecArgs dec{};
-        if (op.dec) {
-            int aoff = 0;
-            for (int i = 0; i < op.dec_level; ++i) aoff += y.lvH[i] * y.lvW[i];
-            dec = DecArgs{y.cbox, y.cconf, y.ccls, y.A, aoff, 8 << op.dec_level, y.keep_logits ? 1 : 0};
-        }
-        // the head's last convolutions, with the decode in their epilogue: box 64 -> 64 (two whole steps), class 80 -> 80 (two
-        // whole steps + a 16-channel tail); float32 logits only on request
-        if (op.dec == 1 && a.cin == 64 && a.cout == 64 && op.mt == 4 && !force_direct) {
-            const size_t lds = (((size_t)64 * ws_stride(128) + 15) & ~size_t(15)) + (size_t)2 * 16 * DEC_ROW * sizeof(float);
-            const int n_tiles = (a.npix + 31) / 32;
-            hipLaunchKernelGGL((conv1x1_ws_kernel<4, 2, false, 1>), dim3((unsigned)std::max(1, std::min((n_tiles + 1) / 2, 2048))), dim3(128), lds,
-                               st, a, n_tiles, dec);
-            AV_LAUNCH_CHECK();
-            return AV_OK;
-        }
-        const bool generic80 = a.cin == 80 && getenv("AVHOT_CONV_GENERIC80");      // test hook: the cin = 80 layers on the generic kernels
-        if (a.ksz == 1 && a.stride == 1 && a.cin == 80 && a.cout == 80 && op.mt == 5 && !a.res && !force_direct && !generic80) {
-            const size_t lds = (size_t)80 * ws_stride(160);
-            const int n_tiles = (a.npix + 31) / 32;
-            const dim3 g((unsigned)std::max(1, std::min((n_tiles + 3) / 4, 1024)));
-            if (op.dec == 2) hipLaunchKernelGGL((conv1x1_ws_kernel<5, 2, true, 2>), g, dim3(256), lds, st, a, n_tiles, dec);
-            else hipLaunchKernelGGL((conv1x1_ws_kernel<5, 2, true>), g, dim3(256), lds, st, a, n_tiles, dec);
-            AV_LAUNCH_CHECK();
-            return AV_OK;
-        }
-        // 1x1 with cin a multiple of 64 and cout of 128 (the cv1 / cv2 of the P4 and P5 blocks, SPPF): a GEMM over flattened pixels,
-        // conv_gemm128_kernel.  Measured against conv1x1_ws_kernel / conv_lds_kernel on all eleven such layers at 64 frames: 7.0-15.6
-        // against 8.0-20.3 us, every one faster, 22 us per forward together.  AVHOT_CONV_NO_GEMM_1X1: the kernels below (test hook)
-        if (a.ksz == 1 && a.stride == 1 && a.cin % CG_SC == 0 && a.cout % 128 == 0 && !a.res && !a.in2 && !op.dec && a.kreal == a.cin &&
-            !force_direct && !getenv("AVHOT_CONV_NO_GEMM") && !getenv("AVHOT_CONV_NO_GEMM_1X1")) {
-            hipLaunchKernelGGL(conv_gemm128_kernel, dim3((a.npix + 63) / 64, a.cout / 128), dim3(256), (size_t)2 * (128 + 64) * CG_ROWB, st, a);
-            AV_LAUNCH_CHECK();
-            return AV_OK;
-        }
-        // 1x1 with whole 32-channel steps: weights resident in LDS, pixel fragments straight from global memory
-        if (a.ksz == 1 && a.stride == 1 && a.cin % 32 == 0 && !a.res && a.cout == 16 * op.mt * (a.cout / (16 * op.mt)) &&
-            (op.mt == 2 || op.mt == 4) && !force_direct && !getenv("AVHOT_CONV_NO_1X1")) {
-            const int ks = a.cin / 32;
-            const bool ks_ok = ks == 1 || ks == 2 || ks == 3 || ks == 4 || ks == 6 || ks == 8 || ks == 12 || ks == 16;
-            // measured per layer at 64 frames (profiles/README.md): wins on the small maps (P5 any cin, P4 up to 192 channels) and for
-            // cin <= 64 anywhere; the big maps with long K stay with conv_lds_kernel, which is within 20 % of their HBM floor
-            const bool pays = a.npix <= 20000 || (a.npix <= 70000 && ks <= 6) || ks <= 2;
-            if (ks_ok && pays) {
-                const size_t lds = (size_t)16 * op.mt * ws_stride(a.cin * 2);
-                const int n_tiles = (a.npix + 31) / 32, gy = a.cout / (16 * op.mt);
-                const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / lds));
-                const dim3 g1((unsigned)std::max(1, std::min((n_tiles + 3) / 4, 256 * per_cu / gy)), gy);
-#define AV_C1(MTV, KSV) hipLaunchKernelGGL((conv1x1_ws_kernel<MTV, KSV>), g1, dim3(256), lds, st, a, n_tiles, dec)
-#define AV_C1K(MTV)                                                                                                                \
-    switch (ks) {                                                                                                                  \
-    case 1: AV_C1(MTV, 1); break;                                                                                              \
-    case 2: AV_C1(MTV, 2); break;                                                                                              \
-    case 3: AV_C1(MTV, 3); break;                                                                                              \
-    case 4: AV_C1(MTV, 4); break;                                                                                              \
-    case 6: AV_C1(MTV, 6); break;                                                                                              \
-    case 8: AV_C1(MTV, 8); break;                                                                                              \
-    case 12: AV_C1(MTV, 12); break;                                                                                            \
-    default: AV_C1(MTV, 16); break;                                                                                            \
-    }
-                if (op.mt == 2) { AV_C1K(2) } else { AV_C1K(4) }
-#undef AV_C1K
-#undef AV_C1
-                AV_LAUNCH_CHECK();
-                return AV_OK;
-            }
-        }
-        // the same kernel for the stride-2 layers whose weights fit (cin <= 64): 8 x 16 output tiles, 17 x 33 patches
-        if (a.stride == 2 && a.ksz == 3 && a.cin % 8 == 0 && !a.res && !force_direct && !getenv("AVHOT_CONV_NO_WS")) {
-            const int cp = (a.cin + 31) & ~31, gy = a.cout / (16 * op.mt);
-            const bool shape2 = a.cout == 16 * op.mt * gy && ((cp == 32 && (op.mt == 2 || op.mt == 4)) || (cp == 64 && op.mt == 4));
-            if (shape2) {
-                const size_t lds = (((size_t)16 * op.mt * ws_stride(9 * cp * 2) + 15) & ~size_t(15)) + (size_t)17 * 33 * (cp * 2 + 16);
-                const int tiles_x = (a.Wo + LT_W - 1) / LT_W, tiles_y = (a.Ho + 7) / 8;
-                const int n_tiles = tiles_x * tiles_y * B;
-                const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, (160 * 1024) / lds));
-                const dim3 wgrid((unsigned)std::max(1, std::min(n_tiles, 256 * per_cu / gy)), gy);
-                if (cp == 32 && op.mt == 2) hipLaunchKernelGGL((conv3x3_ws_kernel<2, 1, 8, 32, false, 2>), wgrid, dim3(512), lds, st, a, tiles_x, tiles_y, n_tiles);
-                else if (cp == 32) hipLaunchKernelGGL((conv3x3_ws_kernel<4, 1, 8, 32, false, 2>), wgrid, dim3(512), lds, st, a, tiles_x, tiles_y, n_tiles);
-                else hipLaunchKernelGGL((conv3x3_ws_kernel<4, 1, 8, 64, false, 2>), wgrid, dim3(512), lds, st, a, tiles_x, tiles_y, n_tiles);
-                AV_LAUNCH_CHECK();
-                return AV_OK;
-            }
-        }
-        // weight-stationary persistent kernel: 3x3 stride 1, the whole weight matrix + one all-channel patch in LDS
-        const int cinp = a.cin == 80 ? 80 : (a.cin + 31) & ~31;       // channels per pixel in the LDS image
-        const bool ws_shape = a.stride == 1 && a.ksz == 3 && a.cin % 8 == 0 && a.cout == 16 * op.mt &&
-                              ((cinp == 32 && op.mt <= 2) || (cinp == 64 && (op.mt == 4 || op.mt == 5)) || (cinp == 80 && op.mt == 5));
-        if (ws_shape && !force_direct && !generic80 && !getenv("AVHOT_CONV_NO_WS")) {
-            const long tiles16 = (long)((a.Wo + LT_W - 1) / LT_W) * ((a.Ho + 15) / 16) * B;
-            int TR = tiles16 >= 512 ? 16 : 8;                   // tile rows
-            auto lds_of = [&](int tr) {
-                return (((size_t)16 * op.mt * ws_stride(9 * cinp * 2) + 15) & ~size_t(15)) + (size_t)(tr + 2) * (LT_W + 2) * ws_stride(cinp * 2);
-            };
-            if (TR == 16 && lds_of(16) > 156 * 1024) TR = 8;
-            const size_t lds = lds_of(TR);
-            if (lds <= 156 * 1024) {
-                const int tiles_x = (a.Wo + LT_W - 1) / LT_W, tiles_y = (a.Ho + TR - 1) / TR;
-                const int n_tiles = tiles_x * tiles_y * B;
-                const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, (160 * 1024) / lds));
-                const dim3 wgrid((unsigned)std::min(n_tiles, 256 * per_cu), 1);
-#define AV_WS_GO(MTV, NTV, NWV, CP)                                                                                                 \
-    do {                                                                                                                           \
-    if (a.res) hipLaunchKernelGGL((conv3x3_ws_kernel<MTV, NTV, NWV, CP, true>), wgrid, dim3(NWV * 64), lds, st, a, tiles_x, tiles_y, n_tiles); \
-    else hipLaunchKernelGGL((conv3x3_ws_kernel<MTV, NTV, NWV, CP, false>), wgrid, dim3(NWV * 64), lds, st, a, tiles_x, tiles_y, n_tiles);   \
-    } while (0)
-#define AV_CONV_WS(MTV, CP)                                                                                                        \
-    do {                                                                                                                           \
-    if (TR == 16) AV_WS_GO(MTV, 2, 8, CP);                                                                                     \
-    else AV_WS_GO(MTV, 1, 8, CP);                                                                                              \
-    } while (0)
-                switch (op.mt) {
-                    case 1: AV_CONV_WS(1, 32); break;
-                    case 2: AV_CONV_WS(2, 32); break;
-                    case 4: AV_CONV_WS(4, 64); break;
-                    default:
-                        if (cinp == 80) AV_CONV_WS(5, 80);
-                        else AV_CONV_WS(5, 64);
-                        break;
-                }
-#undef AV_WS_GO
-#undef AV_CONV_WS
-                AV_LAUNCH_CHECK();
-                return AV_OK;
-            }
-        }
-        if (lds_ok && !force_direct) {
-            const int tiles_x = (a.Wo + LT_W - 1) / LT_W, tiles_y = (a.Ho + LT_H - 1) / LT_H;
-            const int taps = a.ksz * a.ksz;
-            const int PH = (LT_H - 1) * a.stride + a.ksz, PW = (LT_W - 1) * a.stride + a.ksz;
-            const size_t lds = (((size_t)PH * PW * LT_PIXB + 15) & ~size_t(15)) + (size_t)16 * op.mt * (taps * LT_CK * 2 + 32);
-            const dim3 lgrid(tiles_x * tiles_y * B, a.cout / (16 * op.mt));
-#define AV_CONV_LDS(MTV)                                                                                         \
-    do {                                                                                                         \
-    if (a.ksz == 1) hipLaunchKernelGGL((conv_lds_kernel<MTV, 1>), lgrid, dim3(256), lds, st, a, tiles_x, tiles_y); \
-    else hipLaunchKernelGGL((conv_lds_kernel<MTV, 3>), lgrid, dim3(256), lds, st, a, tiles_x, tiles_y);          \
-    } while (0)
-            if (op.mt == 4) AV_CONV_LDS(4);
-            else if (op.mt == 5) AV_CONV_LDS(5);
-            else if (op.mt == 2) AV_CONV_LDS(2);
-            else AV_CONV_LDS(1);
-#undef AV_CONV_LDS
-            AV_LAUNCH_CHECK();
-            return AV_OK;
-        }
-        if (a.ksz == 3 && a.stride == 2 && a.cin == 128 && a.cout % 128 == 0 && !a.res && a.kreal == 9 * a.cin &&
-            !force_direct && !getenv("AVHOT_CONV_NO_GEMM")) {
-            hipLaunchKernelGGL(conv_gemm128_kernel, dim3((a.npix + 63) / 64, a.cout / 128), dim3(256), (size_t)2 * (128 + 64) * CG_ROWB, st, a);
-            AV_LAUNCH_CHECK();
-            return AV_OK;
-        }
-        constexpr int NT = 2;
-        const dim3 grid((a.npix + 16 * NT * 4 - 1) / (16 * NT * 4), a.cout / (16 * op.mt));
-        if (op.mt == 4) hipLaunchKernelGGL((conv_mfma_kernel<4, NT>), grid, dim3(256), 0, st, a);
-        else if (op.mt == 5) hipLaunchKernelGGL((conv_mfma_kernel<5, NT>), grid, dim3(256), 0, st, a);
-        else if (op.mt == 2) hipLaunchKernelGGL((conv_mfma_kernel<2, NT>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((conv_mfma_kernel<1, NT>), grid, dim3(256), 0, st, a);
-    } else {
-        const Buf &bi = y.bufs[op.in.buf], &bo = y.bufs[op.out.buf];
-        if (op.kind == 1) {
-            const int n = B * op.H * op.W * op.C;
-            hipLaunchKernelGGL(maxpool5_kernel, dim3((n + 255) / 256), dim3(256), 0, st, bi.p, bi.C, op.in.coff, bo.p, bo.C,
-                               op.out.coff, B, op.H, op.W, op.C);
-        } else if (op.kind == 3) {
-            const int hw = op.H * op.W;
-            hipLaunchKernelGGL(sppf_pools_kernel, dim3(B, op.C / 8), dim3((hw + 63) / 64 * 64), (size_t)hw * 64, st, bi.p, bi.C,
-                               op.in.coff, bo.p, bo.C, op.out.coff, op.H, op.W, op.C);
-        } else {
-            const int n = B * 4 * op.H * op.W * (op.C / 8);
-            hipLaunchKernelGGL(upsample2_kernel, dim3((n + 255) / 256), dim3(256), 0, st, bi.p, bi.C, op.in.coff, bo.p, bo.C,
-                               op.out.coff, B, op.H, op.W, op.C);
-        }
-    }
-    AV_LAUNCH_CHECK();
-    return AV_OK;
-}
-
-}  // namespace
-
-struct av_yolo { Yolo y; };
-
-extern "C" {
-
-int av_yolo_ctx_free(av_ctx*) { return AV_OK; }
-
-size_t av_yolo_param_count(void) {
-    // must equal oracle/yolo_ref.py: param_count()
-    return 3167776;
-}
-
-int av_yolo_destroy(av_yolo* h) {
-    if (!h) return AV_OK;
-    for (void* p : h->y.allocs) (void)hipFree(p);
-    if (h->y.side) (void)hipStreamDestroy(h->y.side);
-    if (h->y.tail) (void)hipStreamDestroy(h->y.tail);
-    if (h->y.ev_heads) (void)hipEventDestroy(h->y.ev_heads);
-    if (h->y.ev_decoded) (void)hipEventDestroy(h->y.ev_decoded);
-    if (h->y.ev_tail) (void)hipEventDestroy(h->y.ev_tail);
-    if (h->y.ev_fork) (void)hipEventDestroy(h->y.ev_fork);
-    if (h->y.ev_join) (void)hipEventDestroy(h->y.ev_join);
-    delete h;
-    return AV_OK;
-}
-
-int av_yolo_create(av_ctx* ctx, int batch, int in_h, int in_w, const float* weights, size_t n_weights, av_yolo** out) {
-    return av_yolo_create_ex(ctx, batch, in_h, in_w, weights, n_weights, AV_YOLO_FP16, out);
-}
-
-int av_yolo_create_ex(av_ctx* ctx, int batch, int in_h, int in_w, const float* weights, size_t n_weights, int precision, av_yolo** out) {
-    AV_REQUIRE(ctx && weights && out, AV_EINVAL, "av_yolo_create: null argument");
-    AV_REQUIRE(precision == AV_YOLO_FP16 || precision == AV_YOLO_FP32, AV_EINVAL, "av_yolo_create_ex: unknown precision %d", precision);
-    AV_REQUIRE(batch > 0 && in_h >= 32 && in_w >= 32, AV_EINVAL, "av_yolo_create: bad shape");
-    AV_REQUIRE(n_weights == av_yolo_param_count(), AV_EINVAL, "av_yolo_create: expected %zu parameters, got %zu",
-               av_yolo_param_count(), n_weights);
-    AV_HIP(hipSetDevice(ctx->device));
-    av_yolo* h = new (std::nothrow) av_yolo();
-    AV_REQUIRE(h, AV_ENOMEM, "av_yolo_create: out of host memory");
-    Yolo& y = h->y;
-    y.ctx = ctx, y.B = batch, y.inH = in_h, y.inW = in_w, y.wsrc = weights, y.wtotal = n_weights;
-    y.f32 = precision == AV_YOLO_FP32;
-    letterbox(in_h, in_w, y.gain, y.nh, y.nw, y.top, y.left, y.H, y.W);
+// buffers, parameters and ops of the whole network (yolov8.yaml layer numbers in the margin)
+int build_graph(Yolo& y) {
     bool ok = true;
-    const int H = y.H, W = y.W;
+    const int H = y.H, W = y.W, batch = y.B;
     auto nb = [&](int hh, int ww, int c) { const int b = new_buf(y, hh, ww, c); ok = ok && b >= 0; return b; };
     const int x0 = y.f32 ? nb(H, W, 4) : nb(H + 2, W + 2, 4), b0 = nb(H / 2, W / 2, 16), b1 = nb(H / 4, W / 4, 32), b2 = nb(H / 4, W / 4, 32);
     const int cat14 = nb(H / 8, W / 8, 192), cat11 = nb(H / 16, W / 16, 384), cat20 = nb(H / 32, W / 32, 384);
     const int cat17 = nb(H / 16, W / 16, 192);
     const int b3 = nb(H / 8, W / 8, 64), b5 = nb(H / 16, W / 16, 128), b7 = nb(H / 32, W / 32, 256), b8 = nb(H / 32, W / 32, 256);
     const int spp = nb(H / 32, W / 32, 512), p3 = nb(H / 8, W / 8, 64), p4 = nb(H / 16, W / 16, 128), p5 = nb(H / 32, W / 32, 256);
-    const int d16 = 0;
-    (void)d16;
-    if (!ok) { av_yolo_destroy(h); av_set_error("av_yolo_create: device allocation failed"); return AV_ENOMEM; }
+    AV_REQUIRE(ok, AV_ENOMEM, "av_yolo_create: device allocation failed");
 #define CV(...) ok = ok && add_conv(y, __VA_ARGS__)
     if (y.f32) CV(Slice{x0, 0, 4}, Slice{b0, 0, 16}, 3, 2, true, nullptr, 0, nullptr);           // 0 (4-channel input, fourth channel zero)
     else ok = ok && add_stem(y, Slice{x0, 0, 4}, Slice{b0, 0, 16});                               // 0
@@ -2651,16 +2520,17 @@ int av_yolo_create_ex(av_ctx* ctx, int batch, int in_h, int in_w, const float* w
     CV(Slice{cat11, 256, 128}, Slice{b7, 0, 256}, 3, 2, true, nullptr, 0, nullptr);               // 7
     ok = ok && add_c2f(y, Slice{b7, 0, 256}, Slice{b8, 0, 256}, 1, true);                          // 8
     CV(Slice{b8, 0, 256}, Slice{spp, 0, 128}, 1, 1, true, nullptr, 0, nullptr);                   // 9 SPPF cv1
-    if ((H / 32) * (W / 32) <= 1024 && !y.f32) {       // all three pools from one LDS copy of the map
-        add_simple(y, 3, Slice{spp, 0, 128}, Slice{spp, 128, 384}, H / 32, W / 32, 128);
-    } else {
-        for (int i = 0; i < 3; ++i) add_simple(y, 1, Slice{spp, 128 * i, 128}, Slice{spp, 128 * (i + 1), 128}, H / 32, W / 32, 128);
+    if (y.f32) {
+        for (int i = 0; i < 3; ++i) add_simple(y, OP_MAXPOOL, Slice{spp, 128 * i, 128}, Slice{spp, 128 * (i + 1), 128}, H / 32, W / 32, 128);
+    } else {                                               // all three pools from one LDS copy of the map (at most 20 x 20 pixels: letterbox())
+        ok = ok && (H / 32) * (W / 32) <= 1024;
+        add_simple(y, OP_POOLS, Slice{spp, 0, 128}, Slice{spp, 128, 384}, H / 32, W / 32, 128);
     }
     CV(Slice{spp, 0, 512}, Slice{cat20, 128, 256}, 1, 1, true, nullptr, 0, nullptr);              // 9 SPPF cv2 -> cat20[128:384]
-    add_simple(y, 2, Slice{cat20, 128, 256}, Slice{cat11, 0, 256}, H / 32, W / 32, 256);           // 10 upsample -> cat11[0:256]
+    add_simple(y, OP_UPSAMPLE, Slice{cat20, 128, 256}, Slice{cat11, 0, 256}, H / 32, W / 32, 256); // 10 upsample -> cat11[0:256]
     y.ops.back().vcat = (int)y.ops.size();                                                          // (its only reader: layer 12's cv1, the next op)
     ok = ok && add_c2f(y, Slice{cat11, 0, 384}, Slice{cat17, 64, 128}, 1, false);                  // 12 -> cat17[64:192]
-    add_simple(y, 2, Slice{cat17, 64, 128}, Slice{cat14, 0, 128}, H / 16, W / 16, 128);            // 13 upsample -> cat14[0:128]
+    add_simple(y, OP_UPSAMPLE, Slice{cat17, 64, 128}, Slice{cat14, 0, 128}, H / 16, W / 16, 128);  // 13 upsample -> cat14[0:128]
     y.ops.back().vcat = (int)y.ops.size();                                                          // (layer 15's cv1)
     ok = ok && add_c2f(y, Slice{cat14, 0, 192}, Slice{p3, 0, 64}, 1, false);                       // 15
     CV(Slice{p3, 0, 64}, Slice{cat17, 0, 64}, 3, 2, true, nullptr, 0, nullptr);                   // 16 -> cat17[0:64]
@@ -2700,54 +2570,345 @@ int av_yolo_create_ex(av_ctx* ctx, int batch, int in_h, int in_w, const float* w
                {15, Slice{p3, 0, 64}}, {18, Slice{p4, 0, 128}}, {21, Slice{p5, 0, 256}}, {7, Slice{b7, 0, 256}}, {19, Slice{cat20, 0, 128}}};
     if (y.dbg_cat >= 0) y.named.push_back({40, Slice{y.dbg_cat, 0, y.bufs[y.dbg_cat].C}});
     y.wsrc = nullptr;
-    if (!ok) {
-        av_yolo_destroy(h);
-        av_set_error("av_yolo_create: graph construction failed (parameter blob / capacity mismatch)");
-        return AV_EINVAL;
+    AV_REQUIRE(ok, AV_EINVAL, "av_yolo_create: graph construction failed (parameter blob / capacity mismatch)");
+    return AV_OK;
+}
+
+// ---- host side: the plan of a forward ----------------------------------------------------------------------------
+
+// `s` becomes a launch of variant <p...> of family `fam`; a variant that kVariants does not list, or more LDS than its limit, is an error
+int use_variant(Step& s, Family fam, const int (&p)[6], dim3 grid, dim3 block, size_t lds) {
+    const Variant* v = find_variant(fam, p);
+    AV_REQUIRE(v, AV_EINVAL, "av_yolo: no kernel of family %d for <%d,%d,%d,%d,%d,%d>", (int)fam, p[0], p[1], p[2], p[3], p[4], p[5]);
+    AV_REQUIRE(lds <= (size_t)std::max(v->lds_limit, 64 * 1024), AV_EINVAL, "av_yolo: %zu bytes of LDS for a kernel limited to %d", lds, v->lds_limit);
+    s.fn = v->fn, s.grid = grid, s.block = block, s.lds = lds;
+    return AV_OK;
+}
+
+// The launch of one stand-alone convolution of the half-precision chain: the only place that decides between conv_gemm128_kernel,
+// conv1x1_ws_kernel, conv3x3_ws_kernel, conv_lds_kernel and conv_mfma_kernel.  a.in2 set (virtual Upsample + Concat: a 1x1 layer with
+// mt = 4 and whole 32-channel chunks whose input is split into `in` / `in2`): only conv_gemm128_kernel and conv_lds_kernel<4,1> read that.
+int choose_conv(const ConvArgs& a, int mt, int dec, const DecArgs& dec_args, int B, Hooks hk, Step& s) {
+    AV_REQUIRE(a.cout % (16 * mt) == 0, AV_EINVAL, "av_yolo: convolution with %d output channels in tiles of %d", a.cout, 16 * mt);
+    const int gy = a.cout / (16 * mt), n32 = (a.npix + 31) / 32;
+    const bool one = a.ksz == 1 && a.stride == 1, split = a.in2 != nullptr;
+    auto gemm128 = [&] { s.args(a); return use_variant(s, K_GEMM128, {}, dim3((a.npix + 63) / 64, a.cout / 128), dim3(256), (size_t)2 * (128 + 64) * CG_ROWB); };
+    auto lds_tiled = [&] {
+        const int tiles_x = (a.Wo + LT_W - 1) / LT_W, tiles_y = (a.Ho + LT_H - 1) / LT_H, taps = a.ksz * a.ksz;
+        const int PH = (LT_H - 1) * a.stride + a.ksz, PW = (LT_W - 1) * a.stride + a.ksz;
+        s.args(a, tiles_x, tiles_y);
+        return use_variant(s, K_LDS, {mt, a.ksz}, dim3(tiles_x * tiles_y * B, gy), dim3(256),
+                           (((size_t)PH * PW * LT_PIXB + 15) & ~size_t(15)) + (size_t)16 * mt * (taps * LT_CK * 2 + 32));
+    };
+    // 1x1 with cin a multiple of 64 and cout of 128 (the cv1 / cv2 of the P4 and P5 blocks, SPPF; layer 12's cv1 with both its sources): a
+    // GEMM over flattened pixels.  Measured against conv1x1_ws_kernel / conv_lds_kernel on all eleven such layers at 64 frames: 7.0-15.6
+    // against 8.0-20.3 us, every one faster, 22 us per forward together.
+    const bool gemm1x1 = one && a.cin % CG_SC == 0 && a.cout % 128 == 0 && !a.res && !dec && a.kreal == a.cin && (!split || a.k1 % CG_SC == 0) &&
+                         !hk.no_gemm && !hk.no_gemm_1x1;
+    if (split) return gemm1x1 ? gemm128() : lds_tiled();
+    // the head's last convolutions, with the decode in their epilogue: box 64 -> 64 (two whole steps), class 80 -> 80 (two whole steps + a
+    // 16-channel tail); float32 logits only on request
+    if (dec == 1 && a.cin == 64 && a.cout == 64 && mt == 4) {
+        s.args(a, n32, dec_args);
+        return use_variant(s, K_WS1, {4, 2, false, 1}, dim3((unsigned)std::max(1, std::min((n32 + 1) / 2, 2048))), dim3(128),
+                           (((size_t)64 * ws_stride(128) + 15) & ~size_t(15)) + (size_t)2 * 16 * DEC_ROW * sizeof(float));
     }
-    if (!getenv("AVHOT_YOLO_SERIAL")) {
+    const bool generic80 = a.cin == 80 && hk.generic80;
+    if (one && a.cin == 80 && a.cout == 80 && mt == 5 && !a.res && !generic80) {
+        s.args(a, n32, dec_args);
+        return use_variant(s, K_WS1, {5, 2, true, dec == 2 ? 2 : 0}, dim3((unsigned)std::max(1, std::min((n32 + 3) / 4, 1024))), dim3(256),
+                           (size_t)80 * ws_stride(160));
+    }
+    if (gemm1x1) return gemm128();
+    // 1x1 with whole 32-channel steps: weights resident in LDS, pixel fragments straight from global memory
+    if (one && a.cin % 32 == 0 && !a.res && (mt == 2 || mt == 4)) {
+        const int ks = a.cin / 32;
+        const bool ks_ok = ks == 1 || ks == 2 || ks == 3 || ks == 4 || ks == 6 || ks == 8 || ks == 12 || ks == 16;
+        // measured per layer at 64 frames (profiles/README.md): wins on the small maps (P5 any cin, P4 up to 192 channels) and for
+        // cin <= 64 anywhere; the big maps with long K stay with conv_lds_kernel, which is within 20 % of their HBM floor
+        const bool pays = a.npix <= 20000 || (a.npix <= 70000 && ks <= 6) || ks <= 2;
+        if (ks_ok && pays) {
+            const size_t lds = (size_t)16 * mt * ws_stride(a.cin * 2);
+            const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / lds));
+            s.args(a, n32, dec_args);
+            return use_variant(s, K_WS1, {mt, ks, false, 0}, dim3((unsigned)std::max(1, std::min((n32 + 3) / 4, 256 * per_cu / gy)), gy), dim3(256), lds);
+        }
+    }
+    // weight-stationary persistent kernel for the stride-2 layers whose weights fit (cin <= 64): 8 x 16 output tiles, 17 x 33 patches
+    if (a.stride == 2 && a.ksz == 3 && a.cin % 8 == 0 && !a.res) {
+        const int cp = (a.cin + 31) & ~31;
+        if ((cp == 32 && (mt == 2 || mt == 4)) || (cp == 64 && mt == 4)) {
+            const size_t lds = (((size_t)16 * mt * ws_stride(9 * cp * 2) + 15) & ~size_t(15)) + (size_t)17 * 33 * (cp * 2 + 16);
+            const int tiles_x = (a.Wo + LT_W - 1) / LT_W, tiles_y = (a.Ho + 7) / 8, n_tiles = tiles_x * tiles_y * B;
+            const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, (160 * 1024) / lds));
+            s.args(a, tiles_x, tiles_y, n_tiles);
+            return use_variant(s, K_WS3, {mt, 1, 8, cp, false, 2}, dim3((unsigned)std::max(1, std::min(n_tiles, 256 * per_cu / gy)), gy), dim3(512), lds);
+        }
+    }
+    // the same for 3x3 stride 1: the whole weight matrix + one all-channel patch in LDS
+    const int cinp = a.cin == 80 ? 80 : (a.cin + 31) & ~31;       // channels per pixel in the LDS image
+    const bool ws_shape = a.stride == 1 && a.ksz == 3 && a.cin % 8 == 0 && a.cout == 16 * mt &&
+                          ((cinp == 32 && mt <= 2) || (cinp == 64 && (mt == 4 || mt == 5)) || (cinp == 80 && mt == 5));
+    if (ws_shape && !generic80) {
+        const long tiles16 = (long)((a.Wo + LT_W - 1) / LT_W) * ((a.Ho + 15) / 16) * B;
+        auto lds_of = [&](int tr) {
+            return (((size_t)16 * mt * ws_stride(9 * cinp * 2) + 15) & ~size_t(15)) + (size_t)(tr + 2) * (LT_W + 2) * ws_stride(cinp * 2);
+        };
+        const int TR = tiles16 >= 512 && lds_of(16) <= 156 * 1024 ? 16 : 8;          // tile rows
+        const size_t lds = lds_of(TR);
+        if (lds <= 156 * 1024) {
+            const int tiles_x = (a.Wo + LT_W - 1) / LT_W, tiles_y = (a.Ho + TR - 1) / TR, n_tiles = tiles_x * tiles_y * B;
+            const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, (160 * 1024) / lds));
+            s.args(a, tiles_x, tiles_y, n_tiles);
+            return use_variant(s, K_WS3, {mt, TR / 8, 8, cinp, a.res != nullptr, 1}, dim3((unsigned)std::min(n_tiles, 256 * per_cu)), dim3(512), lds);
+        }
+    }
+    // measured per layer (profiles/r01_yolo_b64_*): the LDS kernel wins for stride-1 3x3 (any cin >= 16, the tail of
+    // a partial 32-channel chunk is zero-filled) and for 1x1 with whole chunks
+    if (a.stride == 1 && ((a.ksz == 3 && a.cin >= 16 && a.cin % 8 == 0) || (a.ksz == 1 && a.cin % LT_CK == 0))) return lds_tiled();
+    // the two cin = 128 stride-2 layers
+    if (a.ksz == 3 && a.stride == 2 && a.cin == 128 && a.cout % 128 == 0 && !a.res && a.kreal == 9 * a.cin && !hk.no_gemm) return gemm128();
+    s.args(a);
+    return use_variant(s, K_MFMA, {mt, 2}, dim3((a.npix + 16 * 2 * 4 - 1) / (16 * 2 * 4), gy), dim3(256), 0);
+}
+
+// the same for the float32 chain: the LDS-tiled GEMM form for every layer but the stem (cin = 4)
+int choose_conv_f32(const ConvArgsF& a, int mt, Step& s) {
+    s.args(a);
+    if ((a.cout % 128 == 0 || a.cout == 64 || a.cout == 80 || a.cout == 32 || a.cout == 16) && a.cin % 16 == 0) {
+        const int AR = a.cout % 128 == 0 ? 128 : a.cout, BR = AR == 128 ? 64 : 128, KC = a.cin % 32 == 0 ? 32 : 16;
+        return use_variant(s, K_GEMM_F32, {AR, BR, KC}, dim3((a.npix + BR - 1) / BR, a.cout / AR), dim3(256), (size_t)2 * (AR + BR) * (KC * 4 + 32));
+    }
+    AV_REQUIRE(a.cin == 4 && a.cout == 16 * mt, AV_EINVAL, "av_yolo: no float32 kernel for a convolution %d -> %d", a.cin, a.cout);
+    // pixels per wave (16 NT): small maps need small tiles to fill the chip
+    const int nt = a.npix >= 200000 ? 4 : (a.npix >= 50000 ? 2 : 1);
+    return use_variant(s, K_STEM_F32, {mt, nt, 4, 2}, dim3((a.npix + 64 * nt - 1) / (64 * nt), 1), dim3(256), 0);
+}
+
+// the 1x1 convolution cv can fetch its first channels from upsample op's half-resolution source itself
+bool reads_upsample(const Yolo& y, const Yolo::Op& op, const Yolo::Op& cv) {
+    const ConvArgs& c = cv.ca;
+    const Buf& bo = y.bufs[op.out.buf];
+    return cv.kind == OP_CONV && c.ksz == 1 && c.stride == 1 && c.cin % LT_CK == 0 && op.C % LT_CK == 0 && c.in == bo.p && c.in_coff == op.out.coff &&
+           c.in_cs == bo.C && c.H == 2 * op.H && c.W == 2 * op.W && cv.mt == 4 && c.cout % 64 == 0 && c.cin > op.C && !c.res;
+}
+
+// a 32-channel C2f block of np bottleneck pairs as the c2f32 kernels expect it: cv1 = c1, first 3x3 layer b1, cv2 = c2 reading the whole concat buffer
+bool c2f32_shapes(const ConvArgs& c1, const ConvArgs& b1, const ConvArgs& c2, int np) {
+    return c2.kpad == 32 * (np + 2) && b1.kpad == 288 && c2.in == c1.out && c2.in_coff == c1.out_coff && c2.in_cs == c1.out_cs;
+}
+
+// C2f32Args of a 32-channel block whose cv1 is c1, for the bottleneck pair b1 / b2 that reads concat channels [32 np, 32 np + 32)
+C2f32Args c2f32_args(const ConvArgs& c1, const ConvArgs& b1, const ConvArgs& b2, int np, int B) {
+    C2f32Args fa{};
+    fa.H = c1.H, fa.W = c1.W, fa.tiles_x = (c1.W + 15) / 16, fa.tiles_y = (c1.H + 15) / 16, fa.n_tiles = fa.tiles_x * fa.tiles_y * B;
+    fa.cat = c1.out, fa.cat_cs = c1.out_cs, fa.cat_coff = c1.out_coff;
+    fa.in = c1.out, fa.in_cs = c1.out_cs, fa.in_coff = c1.out_coff + 32 * np;
+    fa.w_b1 = b1.wgt, fa.w_b2 = b2.wgt, fa.bs_b1 = b1.bias, fa.bs_b2 = b2.bias, fa.kb = b1.kpad;
+    return fa;
+}
+
+// Every launch of a forward from the frame to the head's candidates (float32: to its logits), in order.  Which kernel runs a layer
+// depends on the layer shapes and the batch (fixed at create), the hooks and keep_logits -- and on the frame pointer's alignment,
+// for which the plan holds both forms of the front (Step::when).
+int plan_forward(const Yolo& y, Hooks hk, bool keep_logits, std::vector<Step>& plan) {
+    const int B = y.B, n = B * y.H * y.W;
+    plan.clear();
+    auto add = [&](When when = ALWAYS) -> Step& {
+        plan.emplace_back();
+        plan.back().when = when;
+        return plan.back();
+    };
+    auto preprocess = [&](auto kernel, int threads, When when, auto* out) {       // (the walker puts the frame pointer in)
+        Step& s = add(when);
+        s.kernel(kernel, dim3((threads + 255) / 256), dim3(256), 0, nullptr, B, y.inH, y.inW, y.H, y.W, y.nh, y.nw, y.top, y.left, out);
+        s.takes_bgr = true;
+    };
+    if (y.f32) {
+        // reference-precision chain: one lane, one launch per layer, float32 logits, stand-alone decode
+        preprocess(preprocess_f32_kernel, n, ALWAYS, reinterpret_cast<float*>(y.bufs[0].p));
+        for (const Yolo::Op& op : y.ops) {
+            if (op.kind == OP_CONV_F32) {
+                const int rc = choose_conv_f32(op.cf, op.mt, add());
+                if (rc != AV_OK) return rc;
+                continue;
+            }
+            AV_REQUIRE(op.kind == OP_MAXPOOL || op.kind == OP_UPSAMPLE, AV_EINVAL, "av_yolo: op kind %d has no float32 form", (int)op.kind);
+            const Buf &bi = y.bufs[op.in.buf], &bo = y.bufs[op.out.buf];
+            const int threads = op.kind == OP_MAXPOOL ? B * op.H * op.W * op.C : B * 4 * op.H * op.W * (op.C / 4);
+            add().kernel(op.kind == OP_MAXPOOL ? maxpool5_f32_kernel : upsample2_f32_kernel, dim3((threads + 255) / 256), dim3(256), 0,
+                         reinterpret_cast<const float*>(bi.p), bi.C, op.in.coff, reinterpret_cast<float*>(bo.p), bo.C, op.out.coff, B, op.H, op.W, op.C);
+        }
+        return AV_OK;
+    }
+    // the 2:1 letterbox kernels read dwords: they need a 4-byte aligned frame pointer
+    const bool twice = y.inH == 2 * y.nh && y.inW == 2 * y.nw && y.inW % 4 == 0 && y.left % 2 == 0 && y.nw % 2 == 0 && y.W % 2 == 0 && !hk.generic_pre;
+    // letterbox + stem + layer 1 in one launch (front_fused_kernel); with keep_logits (test hook) the three launches run, so that
+    // the network input and the stem's map exist for inspection
+    const bool front = twice && y.left == 0 && y.nw == y.W && y.H % 4 == 0 && y.W % 4 == 0 && y.ops.size() > 2 && y.ops[0].kind == OP_STEM &&
+                       y.ops[1].kind == OP_CONV && y.ops[1].ca.cin == 16 && y.ops[1].ca.cout == 32 && y.ops[1].ca.stride == 2 && !keep_logits && !hk.no_fuse;
+    if (front) {
+        const ConvArgs &c0 = y.ops[0].ca, &c1 = y.ops[1].ca;
+        FrontArgs fa;
+        fa.bgr = nullptr, fa.fh = y.inH, fa.fw = y.inW, fa.H = y.H, fa.W = y.W, fa.top = y.top, fa.nh = y.nh;
+        fa.w_stem = c0.wgt, fa.bs_stem = c0.bias, fa.w_l1 = c1.wgt, fa.bs_l1 = c1.bias, fa.kpad1 = c1.kpad;
+        fa.out = c1.out, fa.out_cs = c1.out_cs, fa.out_coff = c1.out_coff, fa.Ho = c1.Ho, fa.Wo = c1.Wo;
+        fa.tiles_x = (c1.Wo + 15) / 16, fa.tiles_y = (c1.Ho + 7) / 8, fa.n_tiles = fa.tiles_x * fa.tiles_y * B;
+        static_assert(offsetof(FrontArgs, bgr) == 0, "Step::takes_bgr");
+        Step& s = add(BGR_ALIGNED);
+        s.kernel(front_fused_kernel, dim3((unsigned)std::min(fa.n_tiles, 512)), dim3(FR_NTH), FR_LDS, fa);
+        s.takes_bgr = true;
+    } else if (twice) {
+        preprocess(preprocess2_kernel, n / 2, BGR_ALIGNED, y.bufs[0].p);
+    }
+    preprocess(preprocess_kernel, n, twice ? BGR_UNALIGNED : ALWAYS, y.bufs[0].p);
+    // (Walking the chain with 2 or 4 sub-batches of the frames on as many streams was measured, to let one group's per-launch
+    // latency hide behind another's work: 1.78 -> 1.80 / 1.99 ms at 64 frames -- every launch already occupies the whole chip,
+    // so the groups only queue behind each other; dropped, DESIGN.md section 6.)
+    for (size_t oi = 0; oi < y.ops.size(); ++oi) {
+        const Yolo::Op& op = y.ops[oi];
+        const size_t at = oi, first = plan.size();
+        auto conv = [&](const Yolo::Op& o, const ConvArgs& a) {
+            DecArgs dec{};
+            if (o.dec) {
+                int aoff = 0;
+                for (int i = 0; i < o.dec_level; ++i) aoff += y.lvH[i] * y.lvW[i];
+                dec = DecArgs{y.cbox, y.cconf, y.ccls, y.A, aoff, 8 << o.dec_level, keep_logits ? 1 : 0};
+            }
+            return choose_conv(a, o.mt, o.dec, dec, B, hk, add());
+        };
+        auto c2f32 = [&](auto kernel, size_t lds, const C2f32Args& fa) {
+            add().kernel(kernel, dim3((unsigned)std::min(fa.n_tiles, 256)), dim3(F32_NTH), lds, fa);
+        };
+        int rc = AV_OK;
+        if (op.fuse == 1 && !hk.no_fuse) {                 // cv1, 3x3, 3x3 + shortcut, cv2 in one launch
+            const ConvArgs &c1 = op.ca, &b1 = y.ops[oi + 1].ca, &b2 = y.ops[oi + 2].ca, &c2 = y.ops[oi + 3].ca;
+            C2f16Args fa;
+            fa.in = c1.in, fa.in_cs = c1.in_cs, fa.in_coff = c1.in_coff;
+            fa.out = c2.out, fa.out_cs = c2.out_cs, fa.out_coff = c2.out_coff;
+            fa.H = c1.H, fa.W = c1.W, fa.tiles_x = (c1.W + 15) / 16, fa.tiles_y = (c1.H + 15) / 16;
+            fa.n_tiles = fa.tiles_x * fa.tiles_y * B;
+            fa.w_cv1 = c1.wgt, fa.w_b1 = b1.wgt, fa.w_b2 = b2.wgt, fa.w_cv2 = c2.wgt;
+            fa.bs_cv1 = c1.bias, fa.bs_b1 = b1.bias, fa.bs_b2 = b2.bias, fa.bs_cv2 = c2.bias;
+            fa.kb = b1.kpad, fa.kc = c2.kpad;
+            add().kernel(c2f16_fused_kernel, dim3((unsigned)std::min(fa.n_tiles, 512)), dim3(C2F_NTH), C2F_LDS, fa);
+            oi += 3;
+        } else if (op.kind == OP_UPSAMPLE && op.vcat == (int)oi + 1 && !hk.no_fuse && reads_upsample(y, op, y.ops[oi + 1])) {
+            // virtual Upsample + Concat: the upsample launch is skipped and its only reader, a 1x1 convolution, fetches the first k1 input
+            // channels from the half-resolution source itself (same values: bit-identical output)
+            const Yolo::Op& cv = y.ops[oi + 1];
+            const ConvArgs& c1 = cv.ca;
+            const Buf& bi = y.bufs[op.in.buf];
+            ConvArgs v = c1;
+            v.in = bi.p, v.in_cs = bi.C, v.in_coff = op.in.coff;                            // channels [0, k1): the upsample's source, half resolution
+            v.in2 = c1.in, v.in2_cs = c1.in_cs, v.in2_coff = c1.in_coff + op.C, v.k1 = op.C;   // channels [k1, cin): the concat buffer's own part
+            rc = conv(cv, v);
+            oi += 1;
+            const ConvArgs* c2 = cv.fuse == 3 ? &y.ops[oi + 3].ca : nullptr;
+            if (rc == AV_OK && c2 && c2f32_shapes(c1, y.ops[oi + 1].ca, *c2, 1)) {
+                // layer 15's block continues with its bottleneck pair + cv2 in one launch (otherwise: with the unfused bottlenecks)
+                C2f32Args fa = c2f32_args(c1, y.ops[oi + 1].ca, y.ops[oi + 2].ca, 1, B);
+                fa.w_cv2 = c2->wgt, fa.bs_cv2 = c2->bias, fa.kc = c2->kpad;
+                fa.out = c2->out, fa.out_cs = c2->out_cs, fa.out_coff = c2->out_coff;
+                c2f32(c2f32_tail_kernel<64, false>, f32t_lds(64), fa);
+                oi += 3;
+            }
+        } else if (op.fuse == 2 && !hk.no_fuse && op.ca.kpad == 64 && c2f32_shapes(op.ca, y.ops[oi + 1].ca, y.ops[oi + 5].ca, 2)) {
+            // layer 4: cv1 + the first bottleneck pair, then the second pair + cv2
+            const ConvArgs &c1 = op.ca, &c2 = y.ops[oi + 5].ca;
+            C2f32Args fh = c2f32_args(c1, y.ops[oi + 1].ca, y.ops[oi + 2].ca, 1, B);
+            fh.in = c1.in, fh.in_cs = c1.in_cs, fh.in_coff = c1.in_coff;
+            fh.w_cv1 = c1.wgt, fh.bs_cv1 = c1.bias, fh.k1 = c1.kpad;
+            c2f32(c2f32_head_kernel, F32H_LDS, fh);
+            C2f32Args ft = c2f32_args(c1, y.ops[oi + 3].ca, y.ops[oi + 4].ca, 2, B);
+            ft.w_cv2 = c2.wgt, ft.bs_cv2 = c2.bias, ft.kc = c2.kpad;
+            ft.out = c2.out, ft.out_cs = c2.out_cs, ft.out_coff = c2.out_coff;
+            c2f32(c2f32_tail_kernel<96, true>, f32t_lds(96), ft);
+            oi += 5;
+        } else if (op.kind == OP_CONV) {
+            rc = conv(op, op.ca);
+        } else if (op.kind == OP_STEM) {
+            add().kernel(stem_conv_kernel, dim3((op.ca.npix + 255) / 256), dim3(256), 0, op.ca, op.ca.npix);
+        } else {
+            AV_REQUIRE(op.kind == OP_POOLS || op.kind == OP_UPSAMPLE, AV_EINVAL, "av_yolo: op kind %d has no half-precision form", (int)op.kind);
+            const Buf &bi = y.bufs[op.in.buf], &bo = y.bufs[op.out.buf];
+            const int hw = op.H * op.W;
+            if (op.kind == OP_POOLS)
+                add().kernel(sppf_pools_kernel, dim3(B, op.C / 8), dim3((hw + 63) / 64 * 64), (size_t)hw * 64, bi.p, bi.C, op.in.coff, bo.p, bo.C,
+                             op.out.coff, op.H, op.W, op.C);
+            else
+                add().kernel(upsample2_kernel, dim3((B * 4 * hw * (op.C / 8) + 255) / 256), dim3(256), 0, bi.p, bi.C, op.in.coff, bo.p, bo.C,
+                             op.out.coff, B, op.H, op.W, op.C);
+        }
+        if (rc != AV_OK) return rc;
+        for (size_t q = first; q < plan.size(); ++q) {
+            plan[q].lane = op.lane;
+            if (front && at < 2) plan[q].when = BGR_UNALIGNED;       // the stem and layer 1, where front_fused_kernel cannot run
+        }
+        if ((int)at == y.head_begin) plan[first].head = true;
+    }
+    return AV_OK;
+}
+
+}  // namespace
+
+struct av_yolo { Yolo y; };
+
+extern "C" {
+
+int av_yolo_ctx_free(av_ctx*) { return AV_OK; }
+
+size_t av_yolo_param_count(void) {
+    // must equal oracle/yolo_ref.py: param_count()
+    return 3167776;
+}
+
+int av_yolo_destroy(av_yolo* h) {
+    if (!h) return AV_OK;
+    for (void* p : h->y.allocs) (void)hipFree(p);
+    if (h->y.side) (void)hipStreamDestroy(h->y.side);
+    if (h->y.tail) (void)hipStreamDestroy(h->y.tail);
+    if (h->y.ev_heads) (void)hipEventDestroy(h->y.ev_heads);
+    if (h->y.ev_tail) (void)hipEventDestroy(h->y.ev_tail);
+    if (h->y.ev_fork) (void)hipEventDestroy(h->y.ev_fork);
+    if (h->y.ev_join) (void)hipEventDestroy(h->y.ev_join);
+    delete h;
+    return AV_OK;
+}
+
+int av_yolo_create(av_ctx* ctx, int batch, int in_h, int in_w, const float* weights, size_t n_weights, av_yolo** out) {
+    return av_yolo_create_ex(ctx, batch, in_h, in_w, weights, n_weights, AV_YOLO_FP16, out);
+}
+
+int av_yolo_create_ex(av_ctx* ctx, int batch, int in_h, int in_w, const float* weights, size_t n_weights, int precision, av_yolo** out) {
+    AV_REQUIRE(ctx && weights && out, AV_EINVAL, "av_yolo_create: null argument");
+    AV_REQUIRE(precision == AV_YOLO_FP16 || precision == AV_YOLO_FP32, AV_EINVAL, "av_yolo_create_ex: unknown precision %d", precision);
+    AV_REQUIRE(batch > 0 && in_h >= 32 && in_w >= 32, AV_EINVAL, "av_yolo_create: bad shape");
+    AV_REQUIRE(n_weights == av_yolo_param_count(), AV_EINVAL, "av_yolo_create: expected %zu parameters, got %zu",
+               av_yolo_param_count(), n_weights);
+    AV_HIP(hipSetDevice(ctx->device));
+    av_yolo* h = new (std::nothrow) av_yolo();
+    AV_REQUIRE(h, AV_ENOMEM, "av_yolo_create: out of host memory");
+    Yolo& y = h->y;
+    y.ctx = ctx, y.B = batch, y.inH = in_h, y.inW = in_w, y.wsrc = weights, y.wtotal = n_weights;
+    y.f32 = precision == AV_YOLO_FP32;
+    letterbox(in_h, in_w, y.gain, y.nh, y.nw, y.top, y.left, y.H, y.W);
+    const int rc = [&]() -> int {
+        const int rg = build_graph(y);
+        if (rg != AV_OK) return rg;
         AV_HIP(hipStreamCreateWithFlags(&y.side, hipStreamNonBlocking));
         AV_HIP(hipEventCreateWithFlags(&y.ev_fork, hipEventDisableTiming));
         AV_HIP(hipEventCreateWithFlags(&y.ev_join, hipEventDisableTiming));
+        for (const Variant& v : kVariants)
+            if (v.lds_limit) AV_HIP(hipFuncSetAttribute(v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds_limit));
+        // the first plan: a shape that no kernel serves fails here, not at the first forward
+        y.plan_hooks = read_hooks(), y.plan_keep_logits = y.keep_logits;
+        return plan_forward(y, y.plan_hooks, y.plan_keep_logits, y.plan);
+    }();
+    if (rc != AV_OK) {
+        av_yolo_destroy(h);
+        return rc;
     }
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_lds_kernel<4, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_lds_kernel<4, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_lds_kernel<5, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_lds_kernel<5, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_lds_kernel<2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_lds_kernel<2, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_lds_kernel<1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_lds_kernel<1, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(c2f16_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, C2F_LDS));
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(front_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS));
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(c2f32_head_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, F32H_LDS));
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(c2f32_tail_kernel<96, true>), hipFuncAttributeMaxDynamicSharedMemorySize, f32t_lds(96)));
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(c2f32_tail_kernel<64, false>), hipFuncAttributeMaxDynamicSharedMemorySize, f32t_lds(64)));
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(nms_sort_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rs_lds(7, 8)));
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(nms_sort_kernel<7>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rs_lds(8, 7)));
-#define AV_C1_ATTR(KSV) \
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_ws_kernel<2, KSV>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024)); \
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_ws_kernel<4, KSV>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024))
-    AV_C1_ATTR(1); AV_C1_ATTR(2); AV_C1_ATTR(3); AV_C1_ATTR(4); AV_C1_ATTR(6); AV_C1_ATTR(8); AV_C1_ATTR(12); AV_C1_ATTR(16);
-#undef AV_C1_ATTR
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_ws_kernel<2, 1, 8, 32, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_ws_kernel<4, 1, 8, 32, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_ws_kernel<4, 1, 8, 64, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_gemm128_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_gemm_f32_kernel<128, 64, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_gemm_f32_kernel<64, 128, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_gemm_f32_kernel<80, 128, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_gemm_f32_kernel<128, 64, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_gemm_f32_kernel<64, 128, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_gemm_f32_kernel<80, 128, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-#define AV_WS_ATTR1(MTV, NTV, NWV, CP) \
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_ws_kernel<MTV, NTV, NWV, CP, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-    AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_ws_kernel<MTV, NTV, NWV, CP, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
-#define AV_WS_ATTR(MTV, CP) \
-    AV_WS_ATTR1(MTV, 2, 8, CP); AV_WS_ATTR1(MTV, 1, 8, CP)
-    AV_WS_ATTR(1, 32); AV_WS_ATTR(2, 32); AV_WS_ATTR(4, 64); AV_WS_ATTR(5, 64); AV_WS_ATTR(5, 80);
-#undef AV_WS_ATTR1
-#undef AV_WS_ATTR
     (void)hipDeviceSynchronize();
     *out = h;
     return AV_OK;
@@ -2795,240 +2956,39 @@ int av_yolo_forward(av_yolo* h, av_stream_t stream, const uint8_t* bgr, float co
     AV_REQUIRE(max_det > 0 && max_det <= 2500 && conf_thres > 0.f, AV_EINVAL,
                "av_yolo_forward: max_det must be in [1,2500] (kept boxes live in LDS) and conf_thres > 0");
     Yolo& y = h->y;
-    hipStream_t st = as_stream(stream);
-    const hipStream_t st_main = st;
+    AV_REQUIRE(!(y.f32 && y.defer_tail), AV_ESTATE, "av_yolo_forward: the float32 mode has no deferred tail");
+    const hipStream_t st_main = as_stream(stream);
     const int B = y.B;
-    const bool force_direct = getenv("AVHOT_CONV_DIRECT") != nullptr;      // tuning aid, read once per forward
-    {
-        static int prio_state = -1;                                            // progress_prio() on / off, set once per process
-        const char* e = getenv("AVHOT_YOLO_PRIO");
-        const int want = e ? (atoi(e) != 0) : 1;
-        if (want != prio_state) {
-            AV_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_yolo_prio), &want, sizeof(int)));
-            prio_state = want;
+    const Hooks hk = read_hooks();
+    if (y.plan.empty() || !(hk == y.plan_hooks) || y.keep_logits != y.plan_keep_logits) {
+        y.plan_hooks = hk, y.plan_keep_logits = y.keep_logits;
+        const int rc = plan_forward(y, hk, y.keep_logits, y.plan);
+        if (rc != AV_OK) {
+            y.plan.clear();
+            return rc;
         }
     }
-    size_t first_op = 0;
-    if (y.f32) {
-        // reference-precision chain: one lane, one launch per layer, float32 logits, stand-alone decode
-        AV_REQUIRE(!y.defer_tail, AV_ESTATE, "av_yolo_forward: the float32 mode has no deferred tail");
-        const int n = B * y.H * y.W;
-        hipLaunchKernelGGL(preprocess_f32_kernel, dim3((n + 255) / 256), dim3(256), 0, st, bgr, B, y.inH, y.inW, y.H, y.W, y.nh, y.nw, y.top,
-                           y.left, reinterpret_cast<float*>(y.bufs[0].p));
-        AV_LAUNCH_CHECK();
-        for (const Yolo::Op& op : y.ops) {
-            if (op.kind == 10) {
-                const ConvArgsF& a = op.cf;
-                // every layer but the stem (cin = 4): LDS-tiled GEMM form
-                if ((a.cout % 128 == 0 || a.cout == 64 || a.cout == 80 || a.cout == 32 || a.cout == 16) && a.cin % 16 == 0 && !getenv("AVHOT_F32_DIRECT")) {
-                    const bool k32 = a.cin % 32 == 0;
-#define AV_GF(ARV, BRV, KCV)                                                                                                       \
-    hipLaunchKernelGGL((conv_gemm_f32_kernel<ARV, BRV, KCV>), dim3((a.npix + BRV - 1) / BRV, a.cout / ARV), dim3(256),             \
-                       (size_t)2 * (ARV + BRV) * (KCV * 4 + 32), st, a)
-                    if (a.cout % 128 == 0) { if (k32) AV_GF(128, 64, 32); else AV_GF(128, 64, 16); }
-                    else if (a.cout == 64) { if (k32) AV_GF(64, 128, 32); else AV_GF(64, 128, 16); }
-                    else if (a.cout == 32) { if (k32) AV_GF(32, 128, 32); else AV_GF(32, 128, 16); }
-                    else if (a.cout == 16) { if (k32) AV_GF(16, 128, 32); else AV_GF(16, 128, 16); }
-                    else { if (k32) AV_GF(80, 128, 32); else AV_GF(80, 128, 16); }
-#undef AV_GF
-                    AV_LAUNCH_CHECK();
-                    continue;
-                }
-                // pixels per wave (16 NT): the small maps need small tiles to fill the chip -- a P5 layer of 64 frames is 15 360 pixels,
-                // 60 workgroups at NT = 4 (160-390 us per layer), 240 at NT = 1
-                // (80 output channels at NT = 4 take 186 registers -- one wave per SIMD: NT = 2 there)
-                const int nt = a.npix >= 200000 ? (op.mt == 5 ? 2 : 4) : (a.npix >= 50000 ? 2 : 1);
-                const dim3 grid((a.npix + 64 * nt - 1) / (64 * nt), a.cout / (16 * op.mt));
-#define AV_CF3(MTV, NTV)                                                                                     \
-    do {                                                                                                     \
-        if (a.cin % 16 == 0) hipLaunchKernelGGL((conv_f32_kernel<MTV, NTV, 16, (NTV == 4 ? 3 : 4)>), grid, dim3(256), 0, st, a); \
-        else hipLaunchKernelGGL((conv_f32_kernel<MTV, NTV, 4, 2>), grid, dim3(256), 0, st, a);               \
-    } while (0)
-#define AV_CF(MTV)                                                                                           \
-    do {                                                                                                     \
-        if (nt == 4) AV_CF3(MTV, 4);                                                                         \
-        else if (nt == 2) AV_CF3(MTV, 2);                                                                    \
-        else AV_CF3(MTV, 1);                                                                                 \
-    } while (0)
-                AV_REQUIRE(a.cin % 16 == 0 || a.cin == 4, AV_EINVAL, "av_yolo_forward: float32 convolution with %d input channels", a.cin);
-                AV_REQUIRE(a.cout == 16 * op.mt * (int)grid.y, AV_EINVAL, "av_yolo_forward: float32 convolution with %d output channels", a.cout);
-                if (op.mt == 4) AV_CF(4);
-                else if (op.mt == 5) AV_CF(5);
-                else if (op.mt == 2) AV_CF(2);
-                else AV_CF(1);
-#undef AV_CF
-#undef AV_CF3
-            } else {
-                const Buf &bi = y.bufs[op.in.buf], &bo = y.bufs[op.out.buf];
-                const float* src = reinterpret_cast<const float*>(bi.p);
-                float* dst = reinterpret_cast<float*>(bo.p);
-                if (op.kind == 1) {
-                    const int m = B * op.H * op.W * op.C;
-                    hipLaunchKernelGGL(maxpool5_f32_kernel, dim3((m + 255) / 256), dim3(256), 0, st, src, bi.C, op.in.coff, dst, bo.C, op.out.coff,
-                                       B, op.H, op.W, op.C);
-                } else if (op.kind == 2) {
-                    const int m = B * 4 * op.H * op.W * (op.C / 4);
-                    hipLaunchKernelGGL(upsample2_f32_kernel, dim3((m + 255) / 256), dim3(256), 0, st, src, bi.C, op.in.coff, dst, bo.C, op.out.coff,
-                                       B, op.H, op.W, op.C);
-                } else {
-                    av_set_error("av_yolo_forward: op kind %d has no float32 form", op.kind);
-                    return AV_EINVAL;
-                }
-            }
-            AV_LAUNCH_CHECK();
-        }
-        first_op = y.ops.size();
-    } else
-    {
-        const int n = B * y.H * y.W;
-        const bool twice = y.inH == 2 * y.nh && y.inW == 2 * y.nw && y.inW % 4 == 0 && (reinterpret_cast<uintptr_t>(bgr) & 3) == 0 &&
-                           y.left % 2 == 0 && y.nw % 2 == 0 && y.W % 2 == 0 && !getenv("AVHOT_YOLO_GENERIC_PRE");
-        // letterbox + stem + layer 1 in one launch (front_fused_kernel); with keep_logits (test hook) the three launches run, so that
-        // the network input and the stem's map exist for inspection
-        const bool front = twice && y.left == 0 && y.nw == y.W && y.H % 4 == 0 && y.W % 4 == 0 && y.ops.size() > 2 && y.ops[0].kind == 4 &&
-                           y.ops[1].kind == 0 && y.ops[1].ca.cin == 16 && y.ops[1].ca.cout == 32 && y.ops[1].ca.stride == 2 && !y.keep_logits &&
-                           !force_direct && !getenv("AVHOT_YOLO_NO_FUSE") && !getenv("AVHOT_CONV_NO_WS");
-        if (front) {
-            const ConvArgs &c0 = y.ops[0].ca, &c1 = y.ops[1].ca;
-            FrontArgs fa;
-            fa.bgr = bgr, fa.fh = y.inH, fa.fw = y.inW, fa.H = y.H, fa.W = y.W, fa.top = y.top, fa.nh = y.nh;
-            fa.w_stem = c0.wgt, fa.bs_stem = c0.bias, fa.w_l1 = c1.wgt, fa.bs_l1 = c1.bias, fa.kpad1 = c1.kpad;
-            fa.out = c1.out, fa.out_cs = c1.out_cs, fa.out_coff = c1.out_coff, fa.Ho = c1.Ho, fa.Wo = c1.Wo;
-            fa.tiles_x = (c1.Wo + 15) / 16, fa.tiles_y = (c1.Ho + 7) / 8, fa.n_tiles = fa.tiles_x * fa.tiles_y * B;
-            hipLaunchKernelGGL(front_fused_kernel, dim3((unsigned)std::min(fa.n_tiles, 512)), dim3(FR_NTH), FR_LDS, st, fa);
-            first_op = 2;
-        } else if (twice)
-            hipLaunchKernelGGL(preprocess2_kernel, dim3((n / 2 + 255) / 256), dim3(256), 0, st, bgr, B, y.inH, y.inW, y.H, y.W, y.nh,
-                               y.nw, y.top, y.left, y.bufs[0].p);
-        else
-            hipLaunchKernelGGL(preprocess_kernel, dim3((n + 255) / 256), dim3(256), 0, st, bgr, B, y.inH, y.inW, y.H, y.W, y.nh,
-                               y.nw, y.top, y.left, y.bufs[0].p);
-        AV_LAUNCH_CHECK();
-    }
-    // (Walking the chain with 2 or 4 sub-batches of the frames on as many streams was measured, to let one group's per-launch
-    // latency hide behind another's work: 1.78 -> 1.80 / 1.99 ms at 64 frames -- every launch already occupies the whole chip,
-    // so the groups only queue behind each other; dropped, DESIGN.md section 6.)
-    for (size_t oi = first_op; oi < y.ops.size(); ++oi) {
-        const Yolo::Op& op = y.ops[oi];
-        if ((int)oi == y.head_begin && y.tail_pending)     // the previous forward's sort + NMS must be done with the candidates the head rewrites
-            AV_HIP(hipStreamWaitEvent(st_main, y.ev_tail, 0));
-        if (y.side && (int)oi == y.head_begin) {           // backbone + neck done on the caller's stream: open the side lane
-            AV_HIP(hipEventRecord(y.ev_fork, st_main));
+    const When skip = (reinterpret_cast<uintptr_t>(bgr) & 3) == 0 ? BGR_UNALIGNED : BGR_ALIGNED;
+    bool forked = false;
+    for (Step& s : y.plan) {
+        if (s.when == skip) continue;
+        if (s.head) {
+            if (y.tail_pending)                            // the previous forward's sort + NMS must be done with the candidates the head rewrites
+                AV_HIP(hipStreamWaitEvent(st_main, y.ev_tail, 0));
+            AV_HIP(hipEventRecord(y.ev_fork, st_main));    // backbone + neck done on the caller's stream: open the side lane
             AV_HIP(hipStreamWaitEvent(y.side, y.ev_fork, 0));
+            forked = true;
         }
-        if (op.fuse == 1 && !force_direct && !getenv("AVHOT_YOLO_NO_FUSE")) {      // cv1, 3x3, 3x3 + shortcut, cv2 in one launch
-            const ConvArgs &c1 = op.ca, &b1 = y.ops[oi + 1].ca, &b2 = y.ops[oi + 2].ca, &c2 = y.ops[oi + 3].ca;
-            C2f16Args fa;
-            fa.in = c1.in, fa.in_cs = c1.in_cs, fa.in_coff = c1.in_coff;
-            fa.out = c2.out, fa.out_cs = c2.out_cs, fa.out_coff = c2.out_coff;
-            fa.H = c1.H, fa.W = c1.W, fa.tiles_x = (c1.W + 15) / 16, fa.tiles_y = (c1.H + 15) / 16;
-            fa.n_tiles = fa.tiles_x * fa.tiles_y * B;
-            fa.w_cv1 = c1.wgt, fa.w_b1 = b1.wgt, fa.w_b2 = b2.wgt, fa.w_cv2 = c2.wgt;
-            fa.bs_cv1 = c1.bias, fa.bs_b1 = b1.bias, fa.bs_b2 = b2.bias, fa.bs_cv2 = c2.bias;
-            fa.kb = b1.kpad, fa.kc = c2.kpad;
-            hipLaunchKernelGGL(c2f16_fused_kernel, dim3((unsigned)std::min(fa.n_tiles, 512)), dim3(C2F_NTH), C2F_LDS, st_main, fa);
-            AV_LAUNCH_CHECK();
-            oi += 3;
-            continue;
-        }
-        // virtual Upsample + Concat: the upsample launch is skipped and its only reader, a 1x1 convolution on conv_lds_kernel, fetches
-        // the first k1 input channels from the half-resolution source itself (same values: bit-identical output)
-        if (op.kind == 2 && op.vcat == (int)oi + 1 && !force_direct && !getenv("AVHOT_YOLO_NO_FUSE")) {
-            const Yolo::Op& cv = y.ops[oi + 1];
-            const ConvArgs& c = cv.ca;
-            const Buf &bi = y.bufs[op.in.buf], &bo = y.bufs[op.out.buf];
-            const bool lds1x1 = cv.kind == 0 && c.ksz == 1 && c.stride == 1 && c.cin % LT_CK == 0 && op.C % LT_CK == 0 && c.in == bo.p &&
-                                c.in_coff == op.out.coff && c.in_cs == bo.C && c.H == 2 * op.H && c.W == 2 * op.W && cv.mt == 4 && c.cout % 64 == 0 &&
-                                c.cin > op.C && !c.res;
-            if (lds1x1) {
-                ConvArgs v = c;
-                v.in = bi.p, v.in_cs = bi.C, v.in_coff = op.in.coff;                       // channels [0, k1): the upsample's source, half resolution
-                v.in2 = c.in, v.in2_cs = c.in_cs, v.in2_coff = c.in_coff + op.C, v.k1 = op.C;   // channels [k1, cin): the concat buffer's own part
-                const int tiles_x = (v.Wo + LT_W - 1) / LT_W, tiles_y = (v.Ho + LT_H - 1) / LT_H;
-                const size_t lds = (((size_t)LT_H * LT_W * LT_PIXB + 15) & ~size_t(15)) + (size_t)64 * (LT_CK * 2 + 32);
-                if (v.cin % CG_SC == 0 && v.k1 % CG_SC == 0 && v.cout % 128 == 0 && v.kreal == v.cin && !cv.dec && !getenv("AVHOT_CONV_NO_GEMM") &&
-                    !getenv("AVHOT_CONV_NO_GEMM_1X1"))     // layer 12's cv1 (384 -> 128): the GEMM form, both sources
-                    hipLaunchKernelGGL(conv_gemm128_kernel, dim3((v.npix + 63) / 64, v.cout / 128), dim3(256), (size_t)2 * (128 + 64) * CG_ROWB,
-                                       st_main, v);
-                else
-                hipLaunchKernelGGL((conv_lds_kernel<4, 1>), dim3(tiles_x * tiles_y * B, v.cout / 64), dim3(256), lds, st_main, v, tiles_x, tiles_y);
-                AV_LAUNCH_CHECK();
-                oi += 1;                                                                    // the cv1 op is done too
-                if (cv.fuse != 3) continue;
-                // layer 15's block continues with the fused pair + cv2: same code as below, cv1 already launched
-                {
-                    const ConvArgs& c1 = cv.ca;
-                    const ConvArgs& c2 = y.ops[oi + 3].ca;
-                    const bool shapes = c2.kpad == 96 && y.ops[oi + 1].ca.kpad == 288 && c2.in == c1.out && c2.in_coff == c1.out_coff && c2.in_cs == c1.out_cs &&
-                                        !getenv("AVHOT_CONV_NO_WS");
-                    if (!shapes) continue;                                                  // (the loop goes on with the unfused bottlenecks)
-                    C2f32Args fa{};
-                    fa.H = c1.H, fa.W = c1.W, fa.tiles_x = (c1.W + 15) / 16, fa.tiles_y = (c1.H + 15) / 16, fa.n_tiles = fa.tiles_x * fa.tiles_y * B;
-                    fa.cat = c1.out, fa.cat_cs = c1.out_cs, fa.cat_coff = c1.out_coff;
-                    const ConvArgs &b1 = y.ops[oi + 1].ca, &b2 = y.ops[oi + 2].ca;
-                    fa.in = c1.out, fa.in_cs = c1.out_cs, fa.in_coff = c1.out_coff + 32;
-                    fa.w_b1 = b1.wgt, fa.w_b2 = b2.wgt, fa.bs_b1 = b1.bias, fa.bs_b2 = b2.bias, fa.kb = b1.kpad;
-                    fa.w_cv2 = c2.wgt, fa.bs_cv2 = c2.bias, fa.kc = c2.kpad;
-                    fa.out = c2.out, fa.out_cs = c2.out_cs, fa.out_coff = c2.out_coff;
-                    hipLaunchKernelGGL((c2f32_tail_kernel<64, false>), dim3((unsigned)std::min(fa.n_tiles, 256)), dim3(F32_NTH), f32t_lds(64), st_main, fa);
-                    AV_LAUNCH_CHECK();
-                    oi += 3;
-                    continue;
-                }
-            }
-        }
-        if ((op.fuse == 2 || op.fuse == 3) && !force_direct && !getenv("AVHOT_YOLO_NO_FUSE") && !getenv("AVHOT_CONV_NO_WS")) {
-            const ConvArgs& c1 = op.ca;
-            const int np = op.fuse == 2 ? 2 : 1;                                   // bottleneck pairs in the block
-            const ConvArgs& c2 = y.ops[oi + 1 + 2 * np].ca;
-            C2f32Args fa{};
-            fa.H = c1.H, fa.W = c1.W, fa.tiles_x = (c1.W + 15) / 16, fa.tiles_y = (c1.H + 15) / 16, fa.n_tiles = fa.tiles_x * fa.tiles_y * B;
-            fa.cat = c1.out, fa.cat_cs = c1.out_cs, fa.cat_coff = c1.out_coff;
-            const dim3 grid((unsigned)std::min(fa.n_tiles, 256));
-            bool shapes = c2.kpad == 32 * (np + 2) && y.ops[oi + 1].ca.kpad == 288 && c2.in == c1.out && c2.in_coff == c1.out_coff && c2.in_cs == c1.out_cs;
-            if (op.fuse == 2) shapes = shapes && c1.kpad == 64;
-            if (shapes) {
-                const char* dbg = getenv("AVHOT_C2F32_DBG");
-                if (op.fuse == 2 && dbg && dbg[0] == '1') {
-                    for (int q = 0; q < 3; ++q) { const int rc = launch_op(y, y.ops[oi + q], st_main, B, force_direct); if (rc != AV_OK) return rc; }
-                } else
-                if (op.fuse == 2) {                                                  // cv1 + first pair
-                    const ConvArgs &b1 = y.ops[oi + 1].ca, &b2 = y.ops[oi + 2].ca;
-                    fa.in = c1.in, fa.in_cs = c1.in_cs, fa.in_coff = c1.in_coff;
-                    fa.w_cv1 = c1.wgt, fa.bs_cv1 = c1.bias, fa.k1 = c1.kpad;
-                    fa.w_b1 = b1.wgt, fa.w_b2 = b2.wgt, fa.bs_b1 = b1.bias, fa.bs_b2 = b2.bias, fa.kb = b1.kpad;
-                    hipLaunchKernelGGL(c2f32_head_kernel, grid, dim3(F32_NTH), F32H_LDS, st_main, fa);
-                    AV_LAUNCH_CHECK();
-                } else {
-                    const int rc = launch_op(y, op, st_main, B, force_direct);       // cv1 keeps its own launch (cin 192: no halo recompute)
-                    if (rc != AV_OK) return rc;
-                }
-                if (op.fuse == 2 && dbg && dbg[0] == '3') { const int rc = launch_op(y, y.ops[oi], st_main, B, force_direct); if (rc != AV_OK) return rc; }
-                if (op.fuse == 2 && dbg && (dbg[0] == '2' || dbg[0] == '3')) {
-                    for (int q = 3; q < 6; ++q) { const int rc = launch_op(y, y.ops[oi + q], st_main, B, force_direct); if (rc != AV_OK) return rc; }
-                    oi += 5;
-                    continue;
-                }
-                const ConvArgs &b1 = y.ops[oi + 2 * np - 1].ca, &b2 = y.ops[oi + 2 * np].ca;      // the last pair + cv2
-                fa.in = c1.out, fa.in_cs = c1.out_cs, fa.in_coff = c1.out_coff + 32 * np;
-                fa.w_b1 = b1.wgt, fa.w_b2 = b2.wgt, fa.bs_b1 = b1.bias, fa.bs_b2 = b2.bias, fa.kb = b1.kpad;
-                fa.w_cv2 = c2.wgt, fa.bs_cv2 = c2.bias, fa.kc = c2.kpad;
-                fa.out = c2.out, fa.out_cs = c2.out_cs, fa.out_coff = c2.out_coff;
-                if (op.fuse == 2) hipLaunchKernelGGL((c2f32_tail_kernel<96, true>), grid, dim3(F32_NTH), f32t_lds(96), st_main, fa);
-                else hipLaunchKernelGGL((c2f32_tail_kernel<64, false>), grid, dim3(F32_NTH), f32t_lds(64), st_main, fa);
-                AV_LAUNCH_CHECK();
-                oi += 1 + 2 * np;
-                continue;
-            }
-        }
-        const int rc = launch_op(y, op, (y.side && op.lane) ? y.side : st_main, B, force_direct);
-        if (rc != AV_OK) return rc;
+        if (s.takes_bgr) memcpy(s.params, &bgr, sizeof bgr);
+        void* argv[12];
+        for (int i = 0; i < s.nargs; ++i) argv[i] = s.params + s.off[i];
+        AV_HIP(hipLaunchKernel(s.fn, s.grid, s.block, argv, s.lds, s.lane ? y.side : st_main));
     }
-    if (y.side && y.head_begin >= 0 && !y.f32) {           // the decode reads both branches
+    if (forked) {                                          // the decode reads both branches
         AV_HIP(hipEventRecord(y.ev_join, y.side));
         AV_HIP(hipStreamWaitEvent(st_main, y.ev_join, 0));
     }
-    st = st_main;
+    hipStream_t st = st_main;
     if (y.defer_tail) {                                    // the rest goes to the tail stream, behind the head
         AV_HIP(hipEventRecord(y.ev_heads, st_main));
         AV_HIP(hipStreamWaitEvent(y.tail, y.ev_heads, 0));
@@ -3092,7 +3052,6 @@ int av_yolo_defer_tail(av_yolo* h, int enable) {
     if (enable && !y.tail) {
         AV_HIP(hipStreamCreateWithFlags(&y.tail, hipStreamNonBlocking));
         AV_HIP(hipEventCreateWithFlags(&y.ev_heads, hipEventDisableTiming));
-        AV_HIP(hipEventCreateWithFlags(&y.ev_decoded, hipEventDisableTiming));
         AV_HIP(hipEventCreateWithFlags(&y.ev_tail, hipEventDisableTiming));
     }
     y.defer_tail = enable != 0;

@@ -385,6 +385,33 @@ def test_batch_of_different_frames_matches_single_image_runs(setup):
     batched.close()
 
 
+def test_unaligned_frame_pointer_gives_the_same_detections(setup):
+    """The 2:1 letterbox kernels (front_fused_kernel, preprocess2_kernel) read dwords and need a 4-byte aligned frame pointer; the
+    alignment is the one thing a forward decides per call.  The same frames at an odd address go through preprocess_kernel +
+    stem + layer 1 and must give the same detections bit for bit."""
+    import torch
+    Y, R, frame, feats, model, got = setup
+    from oracle.lane_ref import synthetic_frame
+    frames = np.stack([frame, synthetic_frame(720, 1280, 3, 11)])
+    m = Y.YoloV8n("random:0", batch=2)
+    m._prepare(720, 1280)
+    m._frames.copy_(torch.as_tensor(frames))
+    assert m._frames.data_ptr() % 4 == 0
+    m.forward_device(m._frames)
+    torch.cuda.synchronize()
+    want = [t.cpu().numpy().copy() for t in (m._n, m._box, m._conf, m._cls)]
+    assert want[0].min() > 0
+    raw = torch.empty(frames.size + 1, dtype=torch.uint8, device=m._frames.device)
+    odd = raw[1:].view(frames.shape)
+    odd.copy_(torch.as_tensor(frames))
+    assert odd.data_ptr() % 4 == 1
+    m.forward_device(odd)
+    torch.cuda.synchronize()
+    for a, b in zip(want, (m._n, m._box, m._conf, m._cls)):
+        assert np.array_equal(a, b.cpu().numpy())
+    m.close()
+
+
 def test_perception_loop_step_matches_per_frame_paths(setup):
     """bench config3's step -- frames generated on the device, lane chain forked beside the detector, join -- gives
     per camera what the per-frame paths give: the oracle's lanes on the oracle's frame (EMA over the steps) and the
@@ -458,7 +485,7 @@ def test_two_to_one_preprocess_equals_generic_kernel(setup, monkeypatch):
 
 def test_gemm_form_stride2_layers_equal_streaming_kernel(setup, monkeypatch):
     """The two cin = 128 stride-2 convolutions (layer 7: 128 -> 256 into P5; layer 19: 128 -> 128 in the neck) run as an LDS-tiled
-    GEMM over flattened output pixels (conv_gemm128_kernel); AVHOT_CONV_NO_GEMM (read per launch) sends them through
+    GEMM over flattened output pixels (conv_gemm128_kernel); AVHOT_CONV_NO_GEMM (read per forward) sends them through
     conv_mfma_kernel, whose K order, padding and epilogue are the same: their outputs and the detections must be the same bits
     (a batch whose 240-pixel maps do not fill the last 128-pixel tile: 5 images = 1200 pixels)."""
     import torch
@@ -488,7 +515,7 @@ def test_gemm_form_stride2_layers_equal_streaming_kernel(setup, monkeypatch):
 
 def test_gemm_form_1x1_layers_equal_weight_stationary_kernels(setup, monkeypatch):
     """conv_gemm128_kernel also takes the 1 x 1 convolutions with cin a multiple of 64 and cout of 128 (cv1 / cv2 of the P4 / P5 blocks,
-    SPPF); AVHOT_CONV_NO_GEMM_1X1 (read per launch) sends them through conv1x1_ws_kernel / conv_lds_kernel instead -- same chunk
+    SPPF); AVHOT_CONV_NO_GEMM_1X1 (read per forward) sends them through conv1x1_ws_kernel / conv_lds_kernel instead -- same chunk
     order, same epilogue.  The outputs of the blocks they sit in (layers 6, 8, 9, 12, 18, 21) and the detections must be the same bits."""
     import torch
     Y, R, frame, feats, model, _ = setup
