@@ -138,7 +138,12 @@ int av_tracker_reset(av_ctx* ctx, av_stream_t stream, int n_streams, int tcap, i
 /* tcap in {64,128,...,1024}; dcap <= 64.
  *   snap    [S][W][tcap]   table after each frame (rows >= snap_n are unspecified); may be NULL
  *   snap_n  [S][W]         live rows after each frame; may be NULL iff snap is NULL
- *   det2trk [S][W][dcap]   id of the track detection j was matched to or born as (-1 beyond det_n) */
+ *   det2trk [S][W][dcap]   id of the track detection j was matched to or born as (-1 beyond det_n)
+ * Test hooks, read from the environment on every call (they choose the kernel; outputs stay bit-identical, which is what
+ * tests/test_gpu_kernels.py and tests/test_gpu_more.py assert with them): AVHOT_TRACKER_REP=1 (tcap 64, dcap <= 8: the one-wave
+ * kernel, not eight waves that split the association by detection column), AVHOT_TRACKER_PIPE=0 / 1 (the column waves without /
+ * with the ninth wave that keeps the complete rows one frame behind them; unset: with it for windows of 16 frames or more).
+ * The library reads no other variable for this stage. */
 int av_tracker_update(av_ctx* ctx, av_stream_t stream, const av_tracker_cfg* cfg, int n_streams,
                       int n_frames, int dcap, const int32_t* det_n, const int32_t* det_box,
                       const int32_t* det_cls, const double* det_conf, int tcap, void* state,

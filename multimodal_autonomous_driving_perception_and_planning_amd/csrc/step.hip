@@ -256,15 +256,11 @@ __global__ void __launch_bounds__(PW * 64) hot_step_kernel(StepArgs a) {
 
 }  // namespace
 
-// dynamic LDS of the tracker role: av_tracker_update's layout for one staged frame (eight replicas), then the copy of the stream's
-// header and rows the tracker role runs on, from byte stage_off on
+// dynamic LDS of the tracker role: the tracker's layout for one staged frame on eight replica waves (tracker_lds_bytes), then the copy
+// of the stream's header and rows the tracker role runs on, from byte stage_off on
 static size_t hot_step_tracker_lds(int dcap, int tcap, int& stage_off) {
-    const int fc = 1;
-    const size_t chunk_bytes = (size_t)((fc + 3) & ~3) * 4 + (size_t)fc * dcap * 16 + (((size_t)fc * dcap + 1) & ~size_t(1)) * 4 +
-                               (size_t)fc * dcap * 16 + 16;
-    const size_t rep_bytes = ((sizeof(Shared) + 63) & ~size_t(63)) + (size_t)tcap * sizeof(av_track_row);
-    size_t lds_t = rep_bytes * STEP_NW + chunk_bytes + 2 * 576;
-    lds_t = (lds_t + 15) & ~size_t(15);
+    static_assert(STEP_NW == 8, "tracker_lds_bytes sizes the replica kernel's eight column waves");
+    const size_t lds_t = (tracker_lds_bytes(tcap, dcap, 1, true, 0) + 15) & ~size_t(15);
     stage_off = (int)lds_t;
     return lds_t + HDR_INTS * 4 + (size_t)tcap * sizeof(av_track_row);
 }

@@ -23,6 +23,10 @@
 // and does every global write; the others carry just what column ownership needs: boxes, miss counters
 // and the row count, kept in step by the same matches, births and order-preserving compactions.
 // Windows (PIPE): the complete rows move to a ninth wave that trails the column waves by one frame -- see tracker_body.
+//
+// Host side: av_tracker_update validates, asks tracker_plan for the launch -- chunk length, replica waves or not, trailing wave or not,
+// the instantiation (one table of seven), block size, dynamic LDS (tracker_lds_bytes: what the layout takes; what is claimed), wave map
+// -- and launches it.  The environment is read in one function, for two test hooks (AVHOT_TRACKER_REP, AVHOT_TRACKER_PIPE).
 #include <mutex>
 #include "common.h"
 
@@ -90,12 +94,12 @@ __device__ __forceinline__ void lds_sync() {
 // with its own workgroup-to-stream map; smem = the workgroup's dynamic LDS)
 // PIPE (replica kernel, windows): a ninth wave holds the complete rows and runs ONE FRAME BEHIND the eight column waves.  What a
 // frame does to the table is decided by the light state alone (boxes, miss counters, row count); ids, ages, confidences, history
-// rings, the snapshot rows and det2trk are derived from those decisions.  tools/ktime.py: the wave that kept the complete rows was
-// the critical path of every frame (2 820 of 2 900 cycles busy; the others waited 600-800 cycles at the barrier for it).  The
+// rings, the snapshot rows and det2trk are derived from those decisions.  Per-phase cycle counts: the wave that kept the
+// complete rows was the critical path of every frame (2 820 of 2 900 cycles busy; the others waited 600-800 cycles at the barrier for it).  The
 // column waves now publish a frame's decisions (every row's matched column + the taken columns, 65 bytes, by wave 0) and go on;
 // the ninth wave applies them after the next frame's barrier -- the same barrier, no other synchronisation -- from a double-
 // buffered detection chunk.  Same arithmetic on the same values in the same order per row: results are bit-identical.
-template <bool MULTIWAVE, int DREG, int REP, bool TIMED = false, int PIPE = 0>
+template <bool MULTIWAVE, int DREG, int REP, int PIPE = 0>
 __device__ __forceinline__ void tracker_body(const av_tracker_cfg& cfg, int n_frames, int dcap, const int32_t* __restrict__ det_n,
                                const int32_t* __restrict__ det_box, const int32_t* __restrict__ det_cls,
                                const double* __restrict__ det_conf, int tcap, unsigned char* __restrict__ state_all,
@@ -120,7 +124,7 @@ __device__ __forceinline__ void tracker_body(const av_tracker_cfg& cfg, int n_fr
     static_assert(!PIPE || REPL, "the trailing wave belongs to the replica kernel");
     // wave_map: role (column / trailing wave) of every hardware wave, a nibble each.  Waves go to the CU's four SIMDs round-robin, and a
     // lone wave on a SIMD runs its dependent chain fastest: the map pairs the columns that usually hold a detection (0, 1, 2) with the
-    // ones that rarely do, and keeps the trailing wave(s) away from them (launch_replicas).  Identity for every other use.
+    // ones that rarely do, and keeps the trailing wave(s) away from them (tracker_plan).  Identity for every other use.
     const int lane = threadIdx.x & 63;
     const int wid = REPL ? (int)((wave_map >> (4 * __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6))) & 15ull) : (int)(threadIdx.x >> 6);
     const int tid = REPL ? wid * 64 + lane : (int)threadIdx.x;
@@ -215,15 +219,6 @@ __device__ __forceinline__ void tracker_body(const av_tracker_cfg& cfg, int n_fr
     const size_t dsf0 = det_sf0 >= 0 ? (size_t)det_sf0 : (size_t)s * n_frames;
     if (REPL && n_frames > 0 && !det_area) prefetch(dsf0, n_frames < FC ? n_frames : FC);
     int fl = -1;                               // frame within the staged chunk
-    // TIMED (AVHOT_TRACKER_TIMED, tools/ktime.py): cycles of every wave of stream 0 by phase, summed over the window, left in det2trk
-    unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = 0;
-    if (TIMED) tprev = __builtin_amdgcn_s_memtime();
-#define TRK_STAMP(k)                                                   \
-    if (TIMED) {                                                       \
-        const unsigned long long tn_ = __builtin_amdgcn_s_memtime();  \
-        tacc[k] += tn_ - tprev;                                        \
-        tprev = tn_;                                                   \
-    }
     // ---- what a frame does to the table once its association is known (matched column of every row, taken columns) ----------------
     // (a lambda: the frame loop below runs it in place; with PIPE the trailing wave runs it one frame late)
     auto apply = [&](int matched_j, unsigned long long used, int nd, const int* dbox, const int* dcls, const double* dconf, size_t sf) {
@@ -251,7 +246,6 @@ __device__ __forceinline__ void tracker_body(const av_tracker_cfg& cfg, int n_fr
             }
         }
 
-        TRK_STAMP(4)                                        // matched / missed
         // ---- births (:214-225) ------------------------------------------------------------------
         const unsigned long long dmask = nd >= 64 ? ~0ull : ((1ull << nd) - 1ull);
         const unsigned long long unm = ~used & dmask;
@@ -300,7 +294,6 @@ __device__ __forceinline__ void tracker_body(const av_tracker_cfg& cfg, int n_fr
             T += nb_fit;
         }
 
-        TRK_STAMP(5)                                        // births
         // ---- deaths (:228-233): order-preserving compaction --------------------------------------
         const bool live_row = row < T;
         const bool dead = live_row && (r.misses > cfg.max_age);
@@ -363,11 +356,9 @@ __device__ __forceinline__ void tracker_body(const av_tracker_cfg& cfg, int n_fr
             }
         }
 
-        TRK_STAMP(6)                                        // deaths
         // ---- per-frame outputs --------------------------------------------------------------------
         if (full && !publish_flag) emit(sf);
         lds_sync<MULTIWAVE>();          // sh.d* are rewritten by the next frame
-        TRK_STAMP(7)                                        // outputs
     };
     if (PIPE && wid == REP) {
         // ---- the trailing wave: the column waves' barriers of frame f, then frame f - 1 applied to the complete rows ------------------
@@ -381,7 +372,6 @@ __device__ __forceinline__ void tracker_body(const av_tracker_cfg& cfg, int n_fr
                 }
             }
             lds_sync<true>();                              // frame f's exchange barrier (f == n_frames: the closing one)
-            TRK_STAMP(2)
             if (f == 0) continue;
             const int g = f - 1;
             const size_t sg = (size_t)s * n_frames + g;
@@ -394,7 +384,6 @@ __device__ __forceinline__ void tracker_body(const av_tracker_cfg& cfg, int n_fr
             const int mj = (int)rec[(g & 1) * RB + lane];
             const unsigned long long used = (unsigned long long)(unsigned char)rec[(g & 1) * RB + 64];
             lds_sync<false>();
-            TRK_STAMP(3)
             apply(mj, used, nd, c_box + (size_t)gl * dcap * 4, c_cls + (size_t)gl * dcap, c_conf + (size_t)gl * dcap, sg);
         }
     } else
@@ -435,7 +424,6 @@ __device__ __forceinline__ void tracker_body(const av_tracker_cfg& cfg, int n_fr
             __builtin_amdgcn_s_waitcnt(0x0F70);
             lds_sync<MULTIWAVE || REPL>();
         }
-        TRK_STAMP(0)                                        // chunk hand-over
         int nd = c_n[fl];
         const int* dbox = c_box + (size_t)fl * dcap * 4;        // [dcap][4]
         const int* dcls = c_cls + (size_t)fl * dcap;
@@ -510,9 +498,7 @@ __device__ __forceinline__ void tracker_body(const av_tracker_cfg& cfg, int n_fr
                 xb[512 + wid] = (unsigned char)(pc ? (1u << wid) : 0u);
                 xb[520 + wid] = (unsigned char)winner;
             }
-            TRK_STAMP(1)                                    // own column tested and published
             lds_sync<true>();
-            TRK_STAMP(2)                                    // barrier
             auto orfold = [](unsigned long long x) {
                 unsigned t = (unsigned)x | (unsigned)(x >> 32);
                 t |= t >> 16;
@@ -666,7 +652,6 @@ __device__ __forceinline__ void tracker_body(const av_tracker_cfg& cfg, int n_fr
             }
         }
 
-        TRK_STAMP(3)                                        // association resolved
         if (PIPE && wid == 0) {                             // the frame's decisions, for the trailing wave
             rec[(f & 1) * RB + lane] = (signed char)matched_j;
             if (lane == 0) rec[(f & 1) * RB + 64] = (signed char)(unsigned char)used;
@@ -674,11 +659,6 @@ __device__ __forceinline__ void tracker_body(const av_tracker_cfg& cfg, int n_fr
         apply(matched_j, used, nd, dbox, dcls, dconf, sf);
     }
     if (PIPE && wid < REP) lds_sync<true>();               // the closing barrier: the last frame's decisions are published
-#undef TRK_STAMP
-    if (TIMED && s == 0 && lane == 0 && det2trk) {
-        __builtin_amdgcn_s_waitcnt(0);
-        for (int k = 0; k < 8; ++k) det2trk[wid * 8 + k] = (int)tacc[k];
-    }
 
     // ---- persist ----------------------------------------------------------------------------------
     if (!full) return;
@@ -719,14 +699,14 @@ __device__ __forceinline__ void tracker_body(const av_tracker_cfg& cfg, int n_fr
     }
 }
 
-template <bool MULTIWAVE, int DREG, int REP, bool TIMED = false, int PIPE = 0>
+template <bool MULTIWAVE, int DREG, int REP, int PIPE = 0>
 __global__ void __launch_bounds__(1024) tracker_kernel(av_tracker_cfg cfg, int n_frames, int dcap, const int32_t* __restrict__ det_n,
                                const int32_t* __restrict__ det_box, const int32_t* __restrict__ det_cls,
                                const double* __restrict__ det_conf, int tcap, unsigned char* __restrict__ state_all,
                                av_track_row* __restrict__ snap, int32_t* __restrict__ snap_n,
                                int32_t* __restrict__ det2trk, int chunk_frames, unsigned long long wave_map) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    tracker_body<MULTIWAVE, DREG, REP, TIMED, PIPE>(cfg, n_frames, dcap, det_n, det_box, det_cls, det_conf, tcap, state_all, snap, snap_n,
+    tracker_body<MULTIWAVE, DREG, REP, PIPE>(cfg, n_frames, dcap, det_n, det_box, det_cls, det_conf, tcap, state_all, snap, snap_n,
                                               det2trk, chunk_frames, blockIdx.x, smem, wave_map);
 }
 
@@ -738,38 +718,87 @@ __global__ void tracker_reset_kernel(int n_streams, size_t bytes_per_stream, uns
     hdr[1] = 1;     // next_id starts at 1 (multi_object_tracker.py:81)
 }
 
-// the windowed replica kernel (eight column waves, + the trailing wave with PIPE); more than 64 KB of dynamic LDS needs the attribute
-template <bool TIMED, int PIPE>
-int launch_replicas(int n_streams, size_t lds, hipStream_t st, const av_tracker_cfg& cfg, int n_frames, int dcap, const int32_t* det_n,
-                    const int32_t* det_box, const int32_t* det_cls, const double* det_conf, int tcap, unsigned char* state,
-                    av_track_row* snap, int32_t* snap_n, int32_t* det2trk, int fc) {
-    // per device (the attribute belongs to the device's copy of the function): once for each device this process launches on
-    static std::mutex mu;
-    static unsigned long long devs_done = 0;
-    int dev = 0;
-    AV_HIP(hipGetDevice(&dev));
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (dev < 0 || dev >= 64 || !((devs_done >> dev) & 1ull)) {
-            AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(tracker_kernel<false, 8, 8, TIMED, PIPE>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            if (dev >= 0 && dev < 64) devs_done |= 1ull << dev;
-        }
-    }
-    // hardware wave -> role.  SIMD of hardware wave h = h % 4.  With the trailing wave: SIMD 0 = column 0 + columns 6, 7; SIMD 1 = the
-    // trailing wave + column 3; SIMD 2 = columns 1, 4; SIMD 3 = columns 2, 5 (0.268 -> 0.260 ms per 64 x 256 frames).
-    // AVHOT_TRACKER_MAP=0: identity
-    const char* map_env = getenv("AVHOT_TRACKER_MAP");
-    unsigned long long wave_map = PIPE == 1 ? 0x754362180ull : 0xFEDCBA9876543210ull;
-    if (map_env && atoi(map_env) == 0) wave_map = 0xFEDCBA9876543210ull;
-    hipLaunchKernelGGL((tracker_kernel<false, 8, 8, TIMED, PIPE>), dim3(n_streams), dim3(64 * (8 + PIPE)), lds, st, cfg, n_frames,
-                       dcap, det_n, det_box, det_cls, det_conf, tcap, state, snap, snap_n, det2trk, fc, wave_map);
-    return AV_OK;
+// ---- host side ---------------------------------------------------------------------------------------------------------------------
+// Dynamic LDS bytes of a tracker workgroup: the one host copy of the layout that tracker_body carves out of smem, which it has to
+// cover -- the replicas of Shared | stage[tcap] (one; eight for the replica kernel, nine with its trailing wave), one detection chunk
+// of fc frames (two with the trailing wave), and for the replica kernel two exchange buffers of 576 B (XB) and, with the trailing
+// wave, two decision records of 80 B (RB).  Where the device rounds a chunk up to 16 bytes this adds 16, and the trailing-wave layout
+// 16 more: never below the device's sum.  (step.hip sizes its tracker role with it: eight replicas, one staged frame.)
+size_t tracker_lds_bytes(int tcap, int dcap, int fc, bool replica, int pipe) {
+    const size_t rep_bytes = ((sizeof(Shared) + 63) & ~size_t(63)) + (size_t)tcap * sizeof(av_track_row);
+    const size_t chunk_bytes = (size_t)((fc + 3) & ~3) * 4 + (size_t)fc * dcap * 16 + (((size_t)fc * dcap + 1) & ~size_t(1)) * 4 +
+                               (size_t)fc * dcap * 16 + 16;
+    if (!replica) return rep_bytes + chunk_bytes;
+    return rep_bytes * (8 + pipe) + (pipe ? 2 : 1) * chunk_bytes + 2 * 576 + (pipe ? 2 * 80 + 16 : 0);
 }
 
 }  // namespace
 
-#ifndef AVHOT_DEVICE_ONLY      // (step.hip includes this file for its device code only)
+#ifndef AVHOT_DEVICE_ONLY      // (step.hip includes this file for its device code and tracker_lds_bytes only)
+
+namespace {
+
+// Every tracker_kernel instantiation there is.  tracker_plan finds its kernel here and nowhere else; lds_raised: the devices on which
+// the kernel's dynamic-LDS limit has been raised above the default 64 KB (av_tracker_update).
+using TrackerKernel = void (*)(av_tracker_cfg, int, int, const int32_t*, const int32_t*, const int32_t*, const double*, int,
+                               unsigned char*, av_track_row*, int32_t*, int32_t*, int, unsigned long long);
+struct TrackerInst { bool multiwave; int dreg, rep, pipe; TrackerKernel fn; unsigned long long lds_raised; };
+#define AV_TRK_INST(MW, DR, RP, PP) {MW, DR, RP, PP, tracker_kernel<MW, DR, RP, PP>, 0}
+TrackerInst tracker_insts[] = {
+    AV_TRK_INST(false, 8, 1, 0), AV_TRK_INST(false, 16, 1, 0), AV_TRK_INST(false, 0, 1, 0),     // one wave (tcap 64): dcap <= 8, <= 16, any
+    AV_TRK_INST(true, 8, 1, 0),  AV_TRK_INST(true, 0, 1, 0),                                    // a wave per 64 rows: dcap <= 8, any
+    AV_TRK_INST(false, 8, 8, 0), AV_TRK_INST(false, 8, 8, 1),                                   // eight column waves; + the trailing wave
+};
+#undef AV_TRK_INST
+
+// Test hooks, read from the environment on every call (the tests change them between two trackers of one process to pin the replica
+// kernel against the one-wave kernel and the trailing wave against the in-place update).  The only environment this file reads.
+struct TrackerHooks { bool one_wave; int pipe; };       // pipe: -1 = not set
+TrackerHooks read_tracker_hooks() {
+    const char* rep_env = getenv("AVHOT_TRACKER_REP");       // <= 1: no replica waves
+    const char* pipe_env = getenv("AVHOT_TRACKER_PIPE");     // 0 / non-zero: without / with the trailing wave, whatever the window
+    return {rep_env && atoi(rep_env) <= 1, pipe_env ? (atoi(pipe_env) != 0 ? 1 : 0) : -1};
+}
+
+// Everything a launch of the tracker is decided by, decided in one place.
+struct TrackerPlan {
+    int fc, block;                     // frames whose detections are staged in LDS at once; threads per workgroup
+    bool replica;                      // eight column waves (REP == 8) ...
+    int pipe;                          // ... 1: and the trailing wave
+    TrackerInst* inst;
+    size_t lds_need, lds_claim;        // dynamic LDS: what the layout takes, what the launch asks for
+    unsigned long long wave_map;       // hardware wave -> role, a nibble each
+};
+TrackerPlan tracker_plan(const av_tracker_cfg& cfg, int n_frames, int dcap, int tcap) {
+    const TrackerHooks hk = read_tracker_hooks();
+    TrackerPlan p{};
+    // chunk of frames whose detections are staged in LDS at once (~16 KB)
+    p.fc = (int)(16384 / (4 + (size_t)dcap * (16 + 4 + 8 + 8)));
+    p.fc = p.fc < 1 ? 1 : (p.fc > 64 ? 64 : p.fc);
+    if (p.fc > n_frames) p.fc = n_frames;
+    // replica waves (one per detection column) for the common table size; windows also get the trailing ninth wave
+    p.replica = tcap == 64 && dcap <= 8 && cfg.iou_threshold > 0.0 && !hk.one_wave;
+    p.pipe = !p.replica ? 0 : (hk.pipe >= 0 ? hk.pipe : (n_frames >= 16 ? 1 : 0));
+    const bool multiwave = tcap > 64;
+    const int dreg = dcap <= 8 ? 8 : (dcap <= 16 && !multiwave ? 16 : 0), rep = p.replica ? 8 : 1;
+    for (TrackerInst& k : tracker_insts)
+        if (k.multiwave == multiwave && k.dreg == dreg && k.rep == rep && k.pipe == p.pipe) p.inst = &k;
+    p.block = p.replica ? 64 * (8 + p.pipe) : tcap;
+    p.lds_need = p.lds_claim = tracker_lds_bytes(tcap, dcap, p.fc, p.replica, p.pipe);
+    // A window of frames is a long per-stream latency chain on one CU per stream; whatever else lands on that CU competes
+    // with it for issue slots and for the CU's memory pipeline.  In the batched step the HBM-bound planner runs on the
+    // other stream: claiming (almost) the whole LDS keeps its workgroups (38 KB each) off the tracker's 64 CUs -- config 4
+    // 0.380 -> 0.352 ms per step (100 KB: no change, two planner workgroups still fit; 125 / 150 KB: 0.357 / 0.352).
+    // 156 KB also keeps the Kalman kernel's one-wave workgroups (8.4 KB of LDS each) off these CUs: 0.306-0.310 against
+    // 0.310-0.313 ms per step.
+    if (p.replica && n_frames >= 16 && p.lds_need < (size_t)156 * 1024) p.lds_claim = (size_t)156 * 1024;
+    // SIMD of hardware wave h = h % 4.  With the trailing wave: SIMD 0 = column 0 + columns 6, 7; SIMD 1 = the trailing wave +
+    // column 3; SIMD 2 = columns 1, 4; SIMD 3 = columns 2, 5 (0.268 -> 0.260 ms per 64 x 256 frames).  Identity otherwise.
+    p.wave_map = p.pipe ? 0x754362180ull : 0xFEDCBA9876543210ull;
+    return p;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -801,57 +830,23 @@ int av_tracker_update(av_ctx* ctx, av_stream_t stream, const av_tracker_cfg* cfg
     AV_REQUIRE(cfg->iou_threshold >= 0.0, AV_EINVAL,
                "av_tracker_update: iou_threshold < 0 never terminates in the reference either");
     AV_REQUIRE((snap == nullptr) == (snap_n == nullptr), AV_EINVAL, "av_tracker_update: snap and snap_n go together");
-    // chunk of frames whose detections are staged in LDS at once (~16 KB)
-    const size_t per_frame = 4 + (size_t)dcap * (16 + 4 + 8 + 8);
-    int fc = (int)(16384 / per_frame);
-    fc = fc < 1 ? 1 : (fc > 64 ? 64 : fc);
-    if (fc > n_frames) fc = n_frames;
-    const size_t chunk_bytes = (size_t)((fc + 3) & ~3) * 4 + (size_t)fc * dcap * 16 + (((size_t)fc * dcap + 1) & ~size_t(1)) * 4 +
-                               (size_t)fc * dcap * 16 + 16;
-    // replica waves (one per detection column) for the common table size; AVHOT_TRACKER_REP=1 keeps one wave
-    constexpr int REPW = 8;
-    const char* rep_env = getenv("AVHOT_TRACKER_REP");
-    const bool rep = tcap == 64 && dcap <= REPW && cfg->iou_threshold > 0.0 && !(rep_env && atoi(rep_env) <= 1);
-    const size_t rep_bytes = ((sizeof(Shared) + 63) & ~size_t(63)) + (size_t)tcap * sizeof(av_track_row);
-    const size_t lds = rep_bytes * (rep ? REPW : 1) + chunk_bytes + (rep ? 2 * 576 : 0);
-#define AV_TRK_LAUNCH(MW, DR, RP)                                                                                  \
-    hipLaunchKernelGGL((tracker_kernel<MW, DR, RP>), dim3(n_streams), dim3(tcap * RP), lds, as_stream(stream), *cfg,   \
-                       n_frames, dcap, det_n, det_box, det_cls, det_conf, tcap, (unsigned char*)state, snap, snap_n, \
-                       det2trk, fc, 0xFEDCBA9876543210ull)
-    if (rep) {
-        // A window of frames is a long per-stream latency chain on one CU per stream; whatever else lands on that CU competes
-        // with it for issue slots and for the CU's memory pipeline.  In the batched step the HBM-bound planner runs on the
-        // other stream: claiming (almost) the whole LDS keeps its workgroups (38 KB each) off the tracker's 64 CUs -- config 4
-        // 0.380 -> 0.352 ms per step (100 KB: no change, two planner workgroups still fit; 125 / 150 KB: 0.357 / 0.352).
-        // 156 KB also keeps the Kalman kernel's one-wave workgroups (8.4 KB of LDS each) off these CUs: 0.306-0.310 against
-        // 0.310-0.313 ms per step.
-        // AVHOT_TRACKER_LDS_KB overrides (0 = only what the kernel needs).
-        // Windows also get the trailing ninth wave (PIPE, see tracker_body); AVHOT_TRACKER_PIPE=0 / 1 overrides.
-        const char* pad_env = getenv("AVHOT_TRACKER_LDS_KB");
-        const char* pipe_env = getenv("AVHOT_TRACKER_PIPE");
-        const int pipe = pipe_env ? (atoi(pipe_env) != 0 ? 1 : 0) : (n_frames >= 16 ? 1 : 0);
-        const bool timed = getenv("AVHOT_TRACKER_TIMED") != nullptr;
-        const size_t want = pad_env ? (size_t)atoi(pad_env) * 1024 : (n_frames >= 16 ? (size_t)156 * 1024 : 0);
-        const size_t lds_need = pipe ? rep_bytes * (REPW + pipe) + 2 * chunk_bytes + 2 * 576 + 2 * 80 + 16 : lds;
-        AV_REQUIRE(lds_need <= 160 * 1024, AV_EINVAL, "av_tracker_update: %zu bytes of LDS", lds_need);
-        const size_t lds_use = want > lds_need && want <= 160 * 1024 ? want : lds_need;
-        int rc;
-#define AV_TRK_REP(TM, PP)                                                                                                            \
-    launch_replicas<TM, PP>(n_streams, lds_use, as_stream(stream), *cfg, n_frames, dcap, det_n, det_box, det_cls, det_conf, tcap, \
-                            (unsigned char*)state, snap, snap_n, det2trk, fc)
-        if (pipe == 1) rc = timed ? AV_TRK_REP(true, 1) : AV_TRK_REP(false, 1);
-        else rc = timed ? AV_TRK_REP(true, 0) : AV_TRK_REP(false, 0);
-#undef AV_TRK_REP
-        if (rc != AV_OK) return rc;
-    } else if (tcap == 64) {
-        if (dcap <= 8) AV_TRK_LAUNCH(false, 8, 1);
-        else if (dcap <= 16) AV_TRK_LAUNCH(false, 16, 1);
-        else AV_TRK_LAUNCH(false, 0, 1);
-    } else {
-        if (dcap <= 8) AV_TRK_LAUNCH(true, 8, 1);
-        else AV_TRK_LAUNCH(true, 0, 1);
+    const TrackerPlan p = tracker_plan(*cfg, n_frames, dcap, tcap);
+    if (p.replica) {
+        AV_REQUIRE(p.lds_need <= 160 * 1024, AV_EINVAL, "av_tracker_update: %zu bytes of LDS", p.lds_need);
+        if (p.lds_claim > 64 * 1024) {
+            // needs the attribute, once for each device this process launches the kernel on (it belongs to the device's copy of the function)
+            static std::mutex mu;
+            int dev = 0;
+            AV_HIP(hipGetDevice(&dev));
+            std::lock_guard<std::mutex> lk(mu);
+            if (dev < 0 || dev >= 64 || !((p.inst->lds_raised >> dev) & 1ull)) {
+                AV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(p.inst->fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                if (dev >= 0 && dev < 64) p.inst->lds_raised |= 1ull << dev;
+            }
+        }
     }
-#undef AV_TRK_LAUNCH
+    hipLaunchKernelGGL(p.inst->fn, dim3(n_streams), dim3(p.block), p.lds_claim, as_stream(stream), *cfg, n_frames, dcap, det_n, det_box,
+                       det_cls, det_conf, tcap, (unsigned char*)state, snap, snap_n, det2trk, p.fc, p.wave_map);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }
