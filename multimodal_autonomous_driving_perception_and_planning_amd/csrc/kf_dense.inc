@@ -4,7 +4,8 @@
 //   KF_FN(name) = name_lds   rolled loops, the filter and every temporary in LDS (KF_LOCAL = __shared__): the fused time-step
 //                            kernel of step.hip, where this path is one lane of one workgroup for one frame and, inlined in its
 //                            register form, set the whole kernel's allocation (256 registers, 111 spilled, scratch on every launch).
-// Same expressions in the same order either way (no FMA contraction): the two give the same bits (tests/test_gpu_step.py).
+// Same expressions in the same order either way (no FMA contraction): the two give the same bits
+// (tests/test_gpu_kf.py::test_dense_kernel_over_windows: a 200-frame window of kf_kernel against one- and two-frame launches).
 __device__ KF_INLINE void KF_FN(predict)(Filter& k, double dt, double hdt2, double q) {
     // x = F x
     KF_LOCAL double x[6];

@@ -175,30 +175,48 @@ def test_probabilistic_hough_against_plain_python():
     assert got_lines >= 6
 
 
-def test_kalman_oracle_against_information_filter():
-    """kf_ref restates filterpy's covariance-form predict / Joseph-form update; the same model as an information filter
-    (Y = P^-1, y = Y x; measurement update adds H^T R^-1 H and H^T R^-1 z) must give the same states and covariances."""
-    from oracle.harness_ref import ego_motion
+def _information_filter_check(cfg, z, missed):
+    """KalmanRef(*cfg) stepped over z against the same model in information form; frames in `missed` are step(None) for the
+    oracle and a predict without the information update for the filter."""
     from oracle.kf_ref import KalmanRef
-    dt = 0.033
+    dt, q, r = cfg
     F = np.eye(6)
     F[0, 2] = F[1, 3] = F[2, 4] = F[3, 5] = dt
     F[0, 4] = F[1, 5] = 0.5 * dt * dt
     H = np.zeros((4, 6))
     H[:4, :4] = np.eye(4)
-    Q = np.diag([0.1, 0.1, 0.1, 0.1, 1.0, 1.0])
-    Rinv = np.eye(4) / 1.0
+    Q = np.diag([q, q, q, q, 10 * q, 10 * q])
+    Rinv = np.eye(4) / r
     x, P = np.zeros(6), np.eye(6) * 10.0
-    ref = KalmanRef()
-    z = ego_motion(120, seed=3)
-    for t in range(120):
+    ref = KalmanRef(dt, q, r)
+    for t in range(len(z)):
         x, P = F @ x, F @ P @ F.T + Q                                    # predict in covariance form
-        Y = np.linalg.inv(P)
-        y = Y @ x
-        Y2, y2 = Y + H.T @ Rinv @ H, y + H.T @ Rinv @ z[t]
-        P = np.linalg.inv(Y2)
-        x = P @ y2
-        st = ref.step(z[t])
+        if t in missed:
+            st = ref.step(None)
+        else:
+            Y = np.linalg.inv(P)
+            y = Y @ x
+            Y2, y2 = Y + H.T @ Rinv @ H, y + H.T @ Rinv @ z[t]
+            P = np.linalg.inv(Y2)
+            x = P @ y2
+            st = ref.step(z[t])
         np.testing.assert_allclose(ref.x, x, rtol=1e-9, atol=1e-9)
         np.testing.assert_allclose(ref.P, P, rtol=1e-8, atol=1e-10)
         assert abs(st[5] - np.hypot(x[2], x[3])) < 1e-9                   # derived speed
+        assert st[8] == ref.time and abs(ref.time - (t + 1) * dt) < 1e-9
+
+
+def test_kalman_oracle_against_information_filter():
+    """kf_ref restates filterpy's covariance-form predict / Joseph-form update; the same model as an information filter
+    (Y = P^-1, y = Y x; measurement update adds H^T R^-1 H and H^T R^-1 z) must give the same states and covariances --
+    with the default settings, with the non-default ones of tests/test_gpu_kf.py (stop-and-go, west-heading measurements),
+    and with missed measurements (step(None): no information update)."""
+    from oracle.harness_ref import ego_motion
+    from tests import kf_cases as K
+    _information_filter_check((0.033, 0.1, 1.0), ego_motion(120, seed=3), ())
+    _information_filter_check((0.033, 0.1, 1.0), ego_motion(120, seed=3), set(range(3, 120, 7)) | {50, 51, 52})
+    for name in ("A", "B", "C", "D", "Z"):
+        cfg = K.SETTINGS[name]
+        z = K.kf_scenario(120, 1, cfg[0])[0]
+        _information_filter_check(cfg, z, ())
+        _information_filter_check(cfg, z, set(range(3, 120, 7)) | {50, 51, 52})
