@@ -327,6 +327,102 @@ __device__ __forceinline__ bool kf_axis_body(const av_kf_cfg& cfg, int n_frames,
     return true;
 }
 
+// ---- the one-frame step of kf_axis_body (n_frames == 1, mode == nullptr: predict + update) in two parts -------------------------------
+// For the fused time-step kernel (step.hip), whose next step waits for this stream's record: the CHAIN part makes what the next step
+// and the planner need -- x, P, prev_heading (= the frame's heading), prev_speed (= its speed), time, and the planner's start state
+// (px, py, heading, speed) -- and nothing else; the TAIL part makes the rest of the frame's output (the predict-time extract, the
+// rates, the uncertainties) on any wave, later.  Both work on the LDS copy of the record.  The expressions, their order and the libm
+// calls are those of kf_axis_body for m = 1, so the two give the same bits (tests/test_gpu_step_roles.py against kf_axis_kernel):
+//   heading = speed_q > 0.1 ? atan2(vy, vx) : h_p,  h_p = speed_p > 0.1 ? atan2(vyp, vxp) : prev_heading
+// -- kf_axis_body evaluates both atan2 and selects; here the chain evaluates the one it hands on (the predict-time one only on the
+// rare path where the post-update speed is held) and the tail the predict-time one again.
+__device__ __forceinline__ double kf_lane_bcast(double x, int i) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)__double_as_longlong(x), i);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)((unsigned long long)__double_as_longlong(x) >> 32), i);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
+constexpr int KF_CARRY_DOUBLES = 4;      // chain -> tail: vxp, vyp (velocities after the predict), prev_heading on entry
+
+// one wave; lanes 0 / 1 are the two axes.  st: the record (LDS), z: the measurement (LDS), start: the planner's start state (LDS),
+// carry: for the tail (LDS).  Returns false -- with st[45] set and nothing else done -- when the stream needs the dense filter.
+__device__ __forceinline__ bool kf_axis_chain1(const av_kf_cfg& cfg, const double* __restrict__ z, double* __restrict__ st,
+                                               double* __restrict__ start, double* __restrict__ carry, const int lane) {
+    bool bad = st[45] != 0.0;
+    if (lane < 36) {
+        const int r = lane / 6, c = lane - r * 6;
+        if (((r ^ c) & 1) && st[6 + lane] != 0.0) bad = true;
+    }
+    if (__ballot(bad) != 0ull) {
+        if (lane == 0) st[45] = 1.0;
+        return false;
+    }
+    const int ax = lane & 1;                       // lanes >= 2 mirror lanes 0/1 (results unused)
+    Axis a;
+    a.x0 = st[ax], a.x1 = st[2 + ax], a.x2 = st[4 + ax];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) a.p[r][c] = st[6 + (2 * r + ax) * 6 + (2 * c + ax)];
+    const double h_in = st[42];
+    double time = st[44];
+    const double zp = z[ax], zv = z[2 + ax];
+    const double dt = cfg.dt, h = 0.5 * (dt * dt), q = cfg.process_noise, rr = cfg.measurement_noise;
+    axis_predict(a, dt, h, q);
+    time += dt;
+    const double vpred = a.x1;
+    double K[3][2];
+    axis_update(a, zp, zv, rr, K);
+    const double px = kf_lane_bcast(a.x0, 0), py = kf_lane_bcast(a.x0, 1), vx = kf_lane_bcast(a.x1, 0), vy = kf_lane_bcast(a.x1, 1);
+    const double sp_q = sqrt(vx * vx + vy * vy);
+    double heading;
+    if (sp_q > 0.1) {
+        heading = atan2(vy, vx);
+    } else {
+        const double vxp = kf_lane_bcast(vpred, 0), vyp = kf_lane_bcast(vpred, 1);
+        const double sp_p = sqrt(vxp * vxp + vyp * vyp);
+        heading = sp_p > 0.1 ? atan2(vyp, vxp) : h_in;
+    }
+    if (lane < 2) {
+        st[ax] = a.x0, st[2 + ax] = a.x1, st[4 + ax] = a.x2;
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) st[6 + (2 * r + ax) * 6 + (2 * c + ax)] = a.p[r][c];
+        carry[ax] = vpred;
+        if (lane == 0) {
+            st[42] = heading, st[43] = sp_q, st[44] = time;
+            carry[2] = h_in;
+            start[0] = px, start[1] = py, start[2] = heading, start[3] = sp_q;
+        }
+    }
+    return true;
+}
+
+// any one wave, after the chain part's LDS writes: the frame's output row (out_state: 12 doubles) and its plan_state (4 doubles)
+__device__ __forceinline__ void kf_axis_tail1(const av_kf_cfg& cfg, const double* __restrict__ st, const double* __restrict__ carry,
+                                              double* __restrict__ out_state, double* __restrict__ plan_state, const int lane) {
+    const double dt = cfg.dt;
+    const double px = st[0], py = st[1], vx = st[2], vy = st[3], heading = st[42], speed = st[43];
+    const double vxp = carry[0], vyp = carry[1], h_in = carry[2];
+    const double sp_p = sqrt(vxp * vxp + vyp * vyp);       // speed at the predict-time extract
+    const double at_p = atan2(vyp, vxp);
+    const double h_p = sp_p > 0.1 ? at_p : h_in;
+    const double acc = dt > 0.0 ? (speed - sp_p) / dt : 0.0;
+    double dh = heading - h_p;
+    const double pi = 3.141592653589793;
+    if (dh > pi) dh -= 2.0 * pi;
+    else if (dh < -pi) dh += 2.0 * pi;
+    const double yaw = dt > 0.0 ? dh / dt : 0.0;
+    if (lane == 0) {
+        double2* dst = reinterpret_cast<double2*>(out_state);
+        dst[0] = make_double2(px, py), dst[1] = make_double2(vx, vy), dst[2] = make_double2(heading, speed);
+        dst[3] = make_double2(acc, yaw), dst[4] = make_double2(st[44], sqrt(st[6] + st[13]));
+        dst[5] = make_double2(sqrt(st[20] + st[27]), 0.0);
+        if (plan_state) *reinterpret_cast<double4*>(plan_state) = make_double4(px, py, heading, speed);
+    }
+}
+
 // DENSE: a stream that turns out not to be separable is finished here, by lane 0 with the dense filter's LDS form (kf_dense.inc),
 // instead of by a second launch of kf_kernel -- the frame-by-frame calls (one or two frames per launch), where that second launch
 // was 5 us of every call.  Windows keep the register form in its own launch.

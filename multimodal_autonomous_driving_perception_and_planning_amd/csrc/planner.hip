@@ -100,11 +100,24 @@ __device__ __forceinline__ void wave_lds_fence() {
 //   phase 3  costs assembled from the per-trajectory sums as ([reference path] + velocity + acceleration) + curvature + obstacles.
 //            The reference adds every per-waypoint term into one running sum (:224-259), so the two agree to rounding, not bit
 //            for bit (nor do the headings: atan2_fast vs libm); then the stable rank of the C costs (== Python's stable sort, :300)
-template <int G, int NW>
+// The fused time-step kernel's variations (all defaults: the planner kernels' own behaviour):
+//   state_f0  index in `state` of start state f0 (default f0: `state` is the batch's array).  The step kernel hands over the four
+//             doubles its Kalman wave left in LDS, index 0, while wp / cost / order stay indexed by the stream
+//   rot       the waves' tasks (phase-1 pair, heading terms, trajectories) are dealt by (wave - rot) mod NW: the step kernel keeps
+//             its Kalman wave free of phase-1 work
+//   after1    called by every wave as after1(task wave id) behind the phase-1 barrier and its cost chains: work with no consumer
+//             inside the planner, on a wave with slack (task waves < 3 G take fewer trajectories)
+struct PlanNoHook {
+    __device__ __forceinline__ void operator()(int) const {}
+};
+
+template <int G, int NW, class Hook = PlanNoHook>
 __device__ __forceinline__ void plan_block(const PlanParams& p, int f0, int n_states, const double* __restrict__ state,
                                            const double* __restrict__ ref, int n_ref, const double* __restrict__ obs, int n_obs,
-                                           double* __restrict__ wp, double* __restrict__ cost, int32_t* __restrict__ order, double* sm) {
+                                           double* __restrict__ wp, double* __restrict__ cost, int32_t* __restrict__ order, double* sm,
+                                           int state_f0 = -1, int rot = 0, Hook after1 = Hook()) {
     const int n = p.n, C = p.C;
+    const int sd = state_f0 < 0 ? 0 : state_f0 - f0;      // start state f is state[(f + sd) * 4 ..]
     double* vs = sm;                                   // [G][3][n][2]  (v, s)
     double* base = vs + (size_t)G * 3 * n * 2;         // [G][3][3]     S_v, S_a, running(S_v then acc terms)
     double* trig = base + even_up(G * 3 * 3);          // [G][8]        x0 y0 cos sin cos(h+pi/2) sin(h+pi/2) h0
@@ -112,8 +125,9 @@ __device__ __forceinline__ void plan_block(const PlanParams& p, int f0, int n_st
     double* stage_all = costs + 3 * even_up(G * C);    // [NW][n*6]
     const int CS = even_up(G * C);
 
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    double* stage = stage_all + (size_t)wid * n * 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    double* stage = stage_all + (size_t)(tid >> 6) * n * 6;
+    const int wid = ((tid >> 6) + NW - rot) % NW;      // the wave's place in the dealing of tasks
     constexpr int P = G * 3;                           // (state, speed) pairs
     static_assert(NW >= 2, "the heading terms take the last wave");   // (fast, P <= NW: one wave per pair keeps its terms in registers)
 
@@ -159,7 +173,7 @@ __device__ __forceinline__ void plan_block(const PlanParams& p, int f0, int n_st
         if (wid < P) {
             const int g = wid / 3, k = wid - g * 3, f = f0 + g;
             if (f < n_states) {
-                const double v0 = state[(size_t)f * 4 + 3];
+                const double v0 = state[(size_t)(f + sd) * 4 + 3];
                 const double vt = 8.0 + 2.0 * (double)k;      // [8.0, 10.0, 12.0]  (:280)
                 const double dv = vt - v0;
                 double* o = vs + ((size_t)(g * 3 + k) * n) * 2;
@@ -181,7 +195,7 @@ __device__ __forceinline__ void plan_block(const PlanParams& p, int f0, int n_st
         for (int pr = wid; pr < P; pr += NW) {
             const int g = pr / 3, k = pr - g * 3, f = f0 + g;
             if (f >= n_states) continue;
-            const double v0 = state[(size_t)f * 4 + 3];
+            const double v0 = state[(size_t)(f + sd) * 4 + 3];
             const double vt = 8.0 + 2.0 * (double)k;
             const double dv = vt - v0;
             double* o = vs + ((size_t)(g * 3 + k) * n) * 2;
@@ -219,7 +233,7 @@ __device__ __forceinline__ void plan_block(const PlanParams& p, int f0, int n_st
     if (wid == NW - 1 && lane < 2 * G) {
         const int g = lane >> 1, f = f0 + g;
         if (f < n_states) {
-            const double h0 = state[(size_t)f * 4 + 2];
+            const double h0 = state[(size_t)(f + sd) * 4 + 2];
             double* tg = trig + g * 8;
             double sn, cs;
             if (lane & 1) {
@@ -227,13 +241,14 @@ __device__ __forceinline__ void plan_block(const PlanParams& p, int f0, int n_st
                 tg[4] = cs, tg[5] = sn;
             } else {
                 sincos(h0, &sn, &cs);
-                tg[0] = state[(size_t)f * 4 + 0], tg[1] = state[(size_t)f * 4 + 1];
+                tg[0] = state[(size_t)(f + sd) * 4 + 0], tg[1] = state[(size_t)(f + sd) * 4 + 1];
                 tg[2] = cs, tg[3] = sn, tg[6] = h0;
             }
         }
     }
     __syncthreads();
     if (k_live) cost_chains(k_velt, k_acct, k_has, base + wid * 3);        // consumed in phase 3
+    after1(wid);
 
     // ---- phase 2 ---------------------------------------------------------------------------------
     // the per-waypoint constants of this lane's first waypoint, loaded once (not once per trajectory behind the LDS fences)

@@ -4,14 +4,17 @@
 // With one frame per stream and launch the four stage kernels are latency chains of a few microseconds each, and a step is
 // their launches: four graph nodes, ~60 us per step of 64 frames, of which ~16 us graph replay and 23 us a planner kernel for 64
 // start states.  Here the step is one kernel with role-split workgroups, every role running the stage kernels' OWN device code
-// (simdet_frame, tracker_body, kf_axis_body / kf_dense_stream, plan_block: this file includes the stage files for their device
-// parts), so the results are those of the separate launches bit for bit (tests/test_gpu_step.py):
+// (simdet_frame, tracker_body, kf_axis_chain1 + kf_axis_tail1 -- kf_axis_body's one-frame step, same expressions -- / kf_dense_stream,
+// plan_block: this file includes the stage files for their device parts), so the results are those of the separate launches bit for
+// bit (tests/test_gpu_step.py, tests/test_gpu_step_roles.py):
 //   workgroups [0, S)      stream s: simulated detections of its next frame (one thread: a 232-byte table row + box arithmetic),
 //                          then the tracker frame on eight replica waves, then -- optionally -- the stream's 32-byte-per-row
 //                          wire table for the all-gather (exchange.hip's format), all from the same workgroup
-//   workgroups [S, 2 S)    stream s: Kalman step in the first wave (axis-separable filter; the dense filter on one lane for a
-//                          stream flagged non-separable), then the 3 C candidate trajectories spread over the workgroup's
-//                          sixteen (or eight) waves (plan_block<1, PW>), cost ranking, outputs
+//   workgroups [S, 2 S)    stream s: Kalman step in the first wave (axis-separable filter in two parts -- kf_axis_chain1: the record
+//                          and the planner's start state, all the next step and the planner wait for; kf_axis_tail1: the rest of
+//                          the frame's output, later, on a planner wave with slack; the dense filter on one lane for a stream
+//                          flagged non-separable), then the 3 C candidate trajectories spread over the workgroup's sixteen (or
+//                          eight) waves (plan_block<1, PW>, start state read from LDS), cost ranking, outputs
 // The two roles of a stream never exchange data (the planner does not consume tracks).
 // av_hot_step launches one such step; av_hot_step_seq / av_hot_steps_seq keep up to four consecutive steps in flight (below).
 #define AVHOT_DEVICE_ONLY
@@ -146,6 +149,11 @@ __global__ void __launch_bounds__(PW * 64) hot_step_kernel(StepArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int go, fc_stage;
     __shared__ __attribute__((aligned(16))) double kf_stage[AV_KF_STATE_DOUBLES + 2];
+    // the Kalman wave's hand-off inside the workgroup: the planner's start state (px, py, heading, speed), what the tail of the
+    // Kalman step needs beside the record, and whether there is a tail to run (the dense filter does everything at once)
+    __shared__ __attribute__((aligned(32))) double kf_start[4];
+    __shared__ __attribute__((aligned(16))) double kf_carry[KF_CARRY_DOUBLES];
+    __shared__ int kf_tail;
     // the step's inputs that do not come from the previous step, in LDS before the wait: the frame's detections (made here, copied
     // to their output arrays by the other threads) and the ego measurement
     __shared__ __attribute__((aligned(16))) int d_box[8 * 4];
@@ -220,6 +228,9 @@ __global__ void __launch_bounds__(PW * 64) hot_step_kernel(StepArgs a) {
         if (tid < 4) z_stage[tid] = a.z[(size_t)s * 4 + tid];
         if (seq && !seq_enter(a, 2 * s + 1, &go)) return;
         ck.mark(1);
+        // The Kalman wave does only what the NEXT STEP waits for before it publishes (kf_axis_chain1: the record and the planner's
+        // start state, left in LDS); the rest of the frame's Kalman output (kf_axis_tail1) is made later by a planner wave with slack.
+        double *vs = a.vstate + (size_t)s * AV_VSTATE_DOUBLES, *ps = a.plan_state + (size_t)s * 4;
         if (tid < 64) {
             double* rec = a.kf_state + (size_t)s * AV_KF_STATE_DOUBLES;
             fetch_record(rec, kf_stage, AV_KF_STATE_DOUBLES, 0, 64, seq);
@@ -227,10 +238,14 @@ __global__ void __launch_bounds__(PW * 64) hot_step_kernel(StepArgs a) {
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
             ck.mark(2);
-            const double* z = z_stage;
-            double *vs = a.vstate + (size_t)s * AV_VSTATE_DOUBLES, *ps = a.plan_state + (size_t)s * 4;
-            const bool separable = kf_axis_body(a.kcfg, 1, z, nullptr, kf_stage, vs, ps, 0, tid);
-            if (!separable && tid == 0) kf_dense_stream_lds(a.kcfg, 0, 1, z, nullptr, kf_stage, vs, ps);   // (LDS form: kf_dense.inc)
+            const bool separable = kf_axis_chain1(a.kcfg, z_stage, kf_stage, kf_start, kf_carry, tid);
+            if (tid == 0) {
+                kf_tail = separable;
+                if (!separable) {     // (LDS form: kf_dense.inc; its plan_state goes to LDS for the planner and from there to its output)
+                    kf_dense_stream_lds(a.kcfg, 0, 1, z_stage, nullptr, kf_stage, vs, kf_start);
+                    *reinterpret_cast<double4*>(ps) = *reinterpret_cast<const double4*>(kf_start);
+                }
+            }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
@@ -242,14 +257,29 @@ __global__ void __launch_bounds__(PW * 64) hot_step_kernel(StepArgs a) {
                     rec[tid] = kf_stage[tid];
             }
         }
-        ck.mark(3);                   // Kalman step + record written
-        if (seq && tid < 64) {        // the Kalman wave publishes its counter itself, behind the acknowledgement of its record stores
+        ck.mark(3);                   // Kalman chain + record stores issued
+        __syncthreads();              // releases the planner: its start state is in LDS (no wait for any global store)
+        ck.mark(4);                   // planner start
+        // The Kalman wave publishes its counter itself, behind the acknowledgement of its record stores -- while the planner's phase 1
+        // runs on other waves: plan_block deals its tasks from wave KF_ROT on, which leaves wave 0 without phase-1 work (it joins the
+        // phase-1 barrier when its counter is stored and takes three trajectories after it)
+        constexpr int KF_ROT = 4;
+        static_assert(KF_ROT + 3 < PW, "wave 0 must not be a phase-1 pair wave nor the heading wave (task wave PW - 1)");
+        if (seq && tid < 64) {
             __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0)
             if (tid == 0) seq_leave(a, 2 * s + 1);
         }
-        ck.mark(4);
-        __syncthreads();              // the planner's start state (plan_state[s]) is in memory and visible to this workgroup
-        plan_block<1, PW>(a.pp, s, a.S, a.plan_state, nullptr, 0, nullptr, 0, a.wp, a.cost, a.order, reinterpret_cast<double*>(smem));
+        ck.mark(5);                   // record acknowledged, counter stored
+        const bool clocks = seq && (a.fence & 8);
+        auto tail = [&](int task_wave) {          // by the first pair wave, behind its cost chain
+            if (task_wave != 0 || !kf_tail) return;
+            const unsigned long long t0 = clocks ? __builtin_amdgcn_s_memrealtime() : 0ull;
+            kf_axis_tail1(a.kcfg, kf_stage, kf_carry, vs, ps, tid & 63);
+            if (clocks && (tid & 63) == 0)
+                atomicAdd(reinterpret_cast<unsigned long long*>(a.flags + flag_stats(a.S)) + 16 + 7, __builtin_amdgcn_s_memrealtime() - t0);
+        };
+        plan_block<1, PW>(a.pp, s, a.S, kf_start, nullptr, 0, nullptr, 0, a.wp, a.cost, a.order, reinterpret_cast<double*>(smem), 0, KF_ROT,
+                          tail);
         ck.mark(6);                   // planner (thread 0's wave)
     }
 }

@@ -4,13 +4,25 @@
 # Output: gpurun_out/<tag>/<name>/*_results.db (rocpd SQLite) -> tools/profiles_from_db.py turns them into profiles/*.csv / *.json
 set -e
 TAG=${1:-r04}
-ONLY=${2:-all}          # "hot": only the config-4 / config-2 traces and the tracker counters (after a change to tracker / kf / step only);
+ONLY=${2:-all}          # "step": only the headline's trace (the plain headline command, with --stats) and the counters of step.hip and
+                        # planner.hip (after a change to the step kernel's Kalman / planner role);
+                        # "hot": only the config-4 / config-2 traces and the tracker counters (after a change to tracker / kf / step only);
                         # "yolo": only the detector's traces and MFMA counters + the config-3 trace (after a change to yolo.hip only)
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-trace() { name=$1; shift; rocprofv3 --kernel-trace -d $OUT/$name -o t -- "$@" > $OUT/$name.log 2>&1; echo "trace $name done"; }
-pmc() { name=$1; ctr=$2; shift 2; rocprofv3 --kernel-trace --pmc $ctr -d $OUT/$name -o p -- "$@" > $OUT/$name.log 2>&1; echo "pmc $name done"; }
+# (every run under a time limit of its own; set -e: nothing more is started after a run that failed or ran out of time)
+LIMIT=${STEP_TIMEOUT:-600}
+trace() { name=$1; shift; timeout -k 10 $LIMIT rocprofv3 --kernel-trace $STATS -d $OUT/$name -o t -- "$@" > $OUT/$name.log 2>&1; echo "trace $name done"; }
+pmc() { name=$1; ctr=$2; shift 2; timeout -k 10 $LIMIT rocprofv3 --kernel-trace --pmc $ctr -d $OUT/$name -o p -- "$@" > $OUT/$name.log 2>&1; echo "pmc $name done"; }
+if [ "$ONLY" = step ]; then
+  STATS=--stats trace bench_config4 python3 bench.py --steps 48000 --warmup 2000
+  pmc step_fetch FETCH_SIZE python3 tools/stepsync.py 300
+  pmc step_write WRITE_SIZE python3 tools/stepsync.py 300
+  pmc plan_fetch FETCH_SIZE python3 tools/kbench.py --streams 64 --window 256 --stages plan --reps 2
+  pmc plan_write WRITE_SIZE python3 tools/kbench.py --streams 64 --window 256 --stages plan --reps 2
+  ls $OUT; exit 0
+fi
 if [ "$ONLY" = yolo ]; then
   trace bench_config3 python3 bench.py --full --no-also --no-cpu-baseline --workload config3
   trace yolo_b64 python3 tools/ybench.py --batch 64 --reps 5

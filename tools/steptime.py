@@ -17,13 +17,15 @@ lp.seq_flags[base:base + 64].zero_(); torch.cuda.synchronize()
 t0 = time.perf_counter(); lp.enqueue_steps(N); lp.synchronize(); dt = (time.perf_counter() - t0) / N * 1e6
 st = lp.seq_flags[base:base + 64].cpu().numpy().view(np.uint64).reshape(2, 16).astype(np.float64)
 print("depth %d: %.2f us per step (with the clock stamps)" % (D, dt))
-names = [["detections", "wait for predecessor", "record -> LDS (+barrier)", "tracker frame, record out + acknowledged, counter, outputs", "-", "-", "-"],
-         ["-", "wait for predecessor", "record -> LDS", "Kalman + record out", "barrier", "-", "publish + planner"]]
+names = [["detections", "wait for predecessor", "record -> LDS (+barrier)", "tracker frame, record out + acknowledged, counter, outputs", "-", "-", "-", "-"],
+         ["-", "wait for predecessor", "record -> LDS", "Kalman chain part, record stores issued", "barrier: planner released (start state in LDS)",
+          "record acknowledged, counter stored", "planner (wave 0: phase-1 barrier, three trajectories)",
+          "Kalman tail part (on the planner's first pair wave; beside the above)"]]
 for r, role in enumerate(("tracker role", "Kalman / planner role")):
     n = st[r, 15]
     print(role, "(%d launches x streams)" % n)
-    for k in range(7):
+    for k in range(8):
         if names[r][k] != "-":
-            print("   %-32s %7.2f us" % (names[r][k], st[r, k] / n * 0.01))
+            print("   %-46s %7.2f us" % (names[r][k], st[r, k] / n * 0.01))
     if st[r, 9]:
         print("   %-32s %7.2f us   (publisher's counter store -> consumer's poll returned; included in the wait)" % ("hand-over latency", st[r, 8] / st[r, 9] * 0.01))
