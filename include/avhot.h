@@ -245,6 +245,37 @@ int av_planner_plan(av_ctx* ctx, av_stream_t stream, int n_states, const double*
                     const double* ref_path, int n_ref, const double* obstacles, int n_obs,
                     double* waypoints, double* cost, int32_t* order);
 
+/* av_planner_plan with per-state inputs: S x W start states are S x W independent MotionPlanners, each with its own
+ * set_reference_path (:93-124) and its own plan(state, obstacles) argument (:264-303).  State f reads obstacle list f and
+ * reference path f / ref_stride (ref_stride = W: one path per stream).
+ *   ref_path  [n_paths][rcap][2], n_ref [n_paths], n_paths = ceil(n_states / ref_stride); both NULL = no paths;
+ *             n_ref[p] < 2 = no path for that group (set_reference_path ignores shorter lists, :100-101); clamped to rcap
+ *   obstacles [n_states][ocap][3], n_obs [n_states] clamped to 0..ocap; both NULL = no obstacles
+ *   waypoints / cost / order as av_planner_plan.  Same kernels and dispatch as av_planner_plan: a state's results are those of
+ *   av_planner_plan with its path and list shared, bit for bit. */
+int av_planner_plan_each(av_ctx* ctx, av_stream_t stream, int n_states, const double* state,
+                         const double* ref_path, const int32_t* n_ref, int rcap, int ref_stride,
+                         const double* obstacles, const int32_t* n_obs, int ocap,
+                         double* waypoints, double* cost, int32_t* order);
+
+/* The tracker's tables as the planner's obstacles: every confirmed track (flags bit0) of a frame, in table order, at the place
+ * the BEV panel draws it (av_bev_build; bev_renderer.py:207-208), carried into the planner's frame by the frame's start state
+ * (x0, y0, h, .) the way a candidate is placed (motion_planner.py:175-180):
+ *   cx = (x1 + x2) / 2, cy = (y1 + y2) / 2;  l = (cx - x_center) * x_scale, f = y_far - cy * y_scale
+ *   ox = (x0 + f cos h) + l cos(h + pi/2), oy = (y0 + f sin h) + l sin(h + pi/2), r = radius[cls]
+ * so an obstacle at (f, l) lies where a candidate of lateral offset l is at arc length f. */
+typedef struct {
+    double x_center, x_scale;   /* 320.0, 0.03: lateral = (cx - x_center) * x_scale   (bev_renderer.py:208) */
+    double y_far, y_scale;      /* 50.0, 0.1:   forward = y_far - cy * y_scale        (bev_renderer.py:207) */
+    double radius[16];          /* per class id; <= 0, or an id outside 0..15: that track is no obstacle */
+} av_obstacle_cfg;              /* 160 bytes */
+/*   snap [n_states][tcap], snap_n [n_states] (av_tracker_update), plan_state [n_states][4] (av_kf_step)
+ *   obstacles [n_states][ocap][3] (x, y, radius), n_obs [n_states]; ocap >= tcap (nothing is ever dropped);
+ *   rows >= n_obs[f] are unspecified */
+int av_track_obstacles(av_ctx* ctx, av_stream_t stream, const av_obstacle_cfg* cfg, int n_states, int tcap,
+                       const av_track_row* snap, const int32_t* snap_n, const double* plan_state,
+                       int ocap, double* obstacles, int32_t* n_obs);
+
 /* generate_polynomial_trajectory for arbitrary (lateral offset, target speed) pairs (:126-204).
  *   state [n_traj][4], end_lateral_offset [n_traj], target_velocity [n_traj] -> waypoints [n_traj][n][6] */
 int av_planner_generate(av_ctx* ctx, av_stream_t stream, int n_traj, const double* state,

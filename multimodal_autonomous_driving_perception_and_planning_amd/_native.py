@@ -29,6 +29,12 @@ class PlannerCfg(C.Structure):
                 ("w_acceleration", C.c_double), ("w_curvature", C.c_double)]
 
 
+class ObstacleCfg(C.Structure):
+    """av_obstacle_cfg: image centre -> road plane (the BEV panel's constants) and the obstacle radius per class id."""
+    _fields_ = [("x_center", C.c_double), ("x_scale", C.c_double), ("y_far", C.c_double), ("y_scale", C.c_double),
+                ("radius", C.c_double * 16)]
+
+
 class LaneCfg(C.Structure):
     _fields_ = [("hough_threshold", C.c_int32), ("min_line_length", C.c_int32), ("max_line_gap", C.c_int32),
                 ("max_segments", C.c_int32), ("smoothing_factor", C.c_double)]
@@ -123,6 +129,8 @@ _SIGS = [
     ("av_planner_configure", C.c_int, [vp, C.POINTER(PlannerCfg)]),
     ("av_planner_dims", C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("av_planner_plan", C.c_int, [vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp]),
+    ("av_planner_plan_each", C.c_int, [vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp]),
+    ("av_track_obstacles", C.c_int, [vp, vp, C.POINTER(ObstacleCfg), C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp]),
     ("av_hot_step", C.c_int, [vp, vp, C.POINTER(TrackerCfg), C.POINTER(KfCfg)] + [C.c_int] * 5 + [vp] * 17 + [vp, C.c_int, C.c_int]),
     ("av_hot_step_fits", C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     ("av_hot_steps_seq", C.c_int, [vp, C.c_int, vp, C.POINTER(TrackerCfg), C.POINTER(KfCfg)] + [C.c_int] * 5 + [vp] * 7 +

@@ -1,0 +1,73 @@
+// Tracker tables -> planner obstacles (av_track_obstacles): the link between the tracking and the planning end of the loop.
+//
+// The reference has none (MotionPlanner.plan is called without obstacles, demo.py:118-120); what it does have
+// is the place where it DRAWS a track in the road plane, BEVRenderer (bev_renderer.py:207-208: forward = 50 - cy * 0.1 m, lateral =
+// (cx - 320) * 0.03 m, the constants of av_bev_build in raster.hip), and the way MotionPlanner places a point of lateral offset d at
+// arc length s ahead of a start state (motion_planner.py:175-180).  Put together: a confirmed track becomes the obstacle a candidate
+// of lateral offset l meets at arc length f.
+//
+// Mapping: one wave per start state (= one frame of one stream), lane = table row, 64 rows per round.  Confirmed rows whose class has
+// a positive radius are compacted in table order by ballot + prefix count; every lane writes its own 24-byte (x, y, radius) row.
+// float64 in the operation order include/avhot.h states (-ffp-contract=off: no FMA), the planner's own for a waypoint.
+#include "common.h"
+
+#include <cmath>
+
+namespace {
+
+__global__ void __launch_bounds__(256) track_obstacles_kernel(av_obstacle_cfg cfg, int n_states, int tcap,
+                                                              const av_track_row* __restrict__ snap,
+                                                              const int32_t* __restrict__ snap_n,
+                                                              const double* __restrict__ plan_state, int ocap,
+                                                              double* __restrict__ obstacles, int32_t* __restrict__ n_obs) {
+    const int lane = threadIdx.x & 63;
+    const long long fl = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (fl >= n_states) return;
+    const int f = (int)fl;
+    int n = snap_n[f];
+    n = n < 0 ? 0 : (n > tcap ? tcap : n);
+    // the start state is the same for every lane: one sincos pair per wave
+    const double x0 = plan_state[(size_t)f * 4], y0 = plan_state[(size_t)f * 4 + 1], h = plan_state[(size_t)f * 4 + 2];
+    double sn, cs, s2, c2;
+    sincos(h, &sn, &cs);
+    sincos(h + 1.5707963267948966, &s2, &c2);                       // heading + np.pi/2  (motion_planner.py:179)
+    const av_track_row* rows = snap + (size_t)f * tcap;
+    double* out = obstacles + (size_t)f * ocap * 3;
+    int count = 0;                                                  // obstacles of the rows before this round
+    for (int b = 0; b < n; b += 64) {
+        const int i = b + lane;
+        bool keep = false;
+        double ox = 0.0, oy = 0.0, rad = 0.0;
+        if (i < n) {
+            const av_track_row r = rows[i];
+#pragma unroll
+            for (int k = 0; k < 16; ++k) rad = r.cls == k ? cfg.radius[k] : rad;      // (ids outside 0..15 keep 0: no obstacle)
+            keep = (r.flags & 1) && rad > 0.0;
+            const double cx = (double)(r.x1 + r.x2) / 2.0, cy = (double)(r.y1 + r.y2) / 2.0;
+            const double l = (cx - cfg.x_center) * cfg.x_scale, fw = cfg.y_far - cy * cfg.y_scale;
+            ox = (x0 + fw * cs) + l * c2;
+            oy = (y0 + fw * sn) + l * s2;
+        }
+        const unsigned long long m = __ballot(keep);
+        if (keep) {
+            double* o = out + (size_t)(count + __popcll(m & ((1ull << lane) - 1ull))) * 3;      // < n <= tcap <= ocap
+            o[0] = ox, o[1] = oy, o[2] = rad;
+        }
+        count += __popcll(m);
+    }
+    if (lane == 0) n_obs[f] = count;
+}
+
+}  // namespace
+
+extern "C" int av_track_obstacles(av_ctx* ctx, av_stream_t stream, const av_obstacle_cfg* cfg, int n_states, int tcap,
+                                  const av_track_row* snap, const int32_t* snap_n, const double* plan_state, int ocap,
+                                  double* obstacles, int32_t* n_obs) {
+    AV_REQUIRE(ctx && cfg && snap && snap_n && plan_state && obstacles && n_obs, AV_EINVAL, "av_track_obstacles: null argument");
+    AV_REQUIRE(n_states > 0 && tcap > 0, AV_EINVAL, "av_track_obstacles: n_states and tcap must be > 0");
+    AV_REQUIRE(ocap >= tcap, AV_EINVAL, "av_track_obstacles: ocap %d < tcap %d (no obstacle is ever dropped)", ocap, tcap);
+    hipLaunchKernelGGL(track_obstacles_kernel, dim3((n_states + 3) / 4), dim3(256), 0, as_stream(stream), *cfg, n_states, tcap, snap,
+                       snap_n, plan_state, ocap, obstacles, n_obs);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}

@@ -111,11 +111,52 @@ struct PlanNoHook {
     __device__ __forceinline__ void operator()(int) const {}
 };
 
-template <int G, int NW, class Hook = PlanNoHook>
-__device__ __forceinline__ void plan_block(const PlanParams& p, int f0, int n_states, const double* __restrict__ state,
-                                           const double* __restrict__ ref, int n_ref, const double* __restrict__ obs, int n_obs,
-                                           double* __restrict__ wp, double* __restrict__ cost, int32_t* __restrict__ order, double* sm,
-                                           int state_f0 = -1, int rot = 0, Hook after1 = Hook()) {
+// Where a start state's reference path and obstacle list come from.  `at(f)` is what state f reads, asked by a whole wave for
+// one state (f wave-uniform); `has_ref(f)` may be asked per lane.  For PlanShared both are the launch's own arguments whatever
+// f is, so those instantiations pay nothing for the lookup.
+struct PlanLists {
+    const double* ref; int n_ref;      // [n_ref][2]
+    const double* obs; int n_obs;      // [n_obs][3]
+};
+// one reference path and one obstacle list for every state of the launch (av_planner_plan)
+struct PlanShared {
+    const double* ref; int n_ref;
+    const double* obs; int n_obs;
+    __device__ __forceinline__ PlanLists at(int) const { return PlanLists{ref, n_ref, obs, n_obs}; }
+    __device__ __forceinline__ bool has_ref(int) const { return n_ref > 0; }
+};
+// state f reads obstacle list f and reference path f / ref_stride (av_planner_plan_each); a null list pointer: none for any state
+struct PlanEach {
+    const double* ref; const int32_t* n_ref;      // [n_paths][rcap][2], [n_paths]
+    const double* obs; const int32_t* n_obs;      // [n_states][ocap][3], [n_states]
+    int rcap, ref_stride, ocap;
+    __device__ __forceinline__ int path_points(int pth) const {
+        const int k = n_ref[pth] > rcap ? rcap : n_ref[pth];
+        return k < 2 ? 0 : k;                                   // set_reference_path ignores lists shorter than two (:100-101)
+    }
+    __device__ __forceinline__ bool has_ref(int f) const { return ref && path_points(f / ref_stride) > 0; }
+    __device__ __forceinline__ PlanLists at(int f) const {
+        f = __builtin_amdgcn_readfirstlane(f);                  // (the same in every lane: counts and lists by scalar loads)
+        PlanLists l{nullptr, 0, nullptr, 0};
+        if (ref) {
+            const int pth = f / ref_stride;
+            l.n_ref = path_points(pth);
+            l.ref = ref + (size_t)pth * rcap * 2;
+        }
+        if (obs) {
+            const int k = n_obs[f];
+            l.n_obs = k < 0 ? 0 : (k > ocap ? ocap : k);
+            l.obs = obs + (size_t)f * ocap * 3;
+        }
+        return l;
+    }
+};
+
+template <int G, int NW, class Hook = PlanNoHook, class Lists = PlanShared>
+__device__ __forceinline__ void plan_block_lists(const PlanParams& p, int f0, int n_states, const double* __restrict__ state,
+                                                 const Lists lists, double* __restrict__ wp, double* __restrict__ cost,
+                                                 int32_t* __restrict__ order, double* sm, int state_f0 = -1, int rot = 0,
+                                                 Hook after1 = Hook()) {
     const int n = p.n, C = p.C;
     const int sd = state_f0 < 0 ? 0 : state_f0 - f0;      // start state f is state[(f + sd) * 4 ..]
     double* vs = sm;                                   // [G][3][n][2]  (v, s)
@@ -253,11 +294,15 @@ __device__ __forceinline__ void plan_block(const PlanParams& p, int f0, int n_st
     // ---- phase 2 ---------------------------------------------------------------------------------
     // the per-waypoint constants of this lane's first waypoint, loaded once (not once per trajectory behind the LDS fences)
     const double q_l = lane < n ? p.q[lane] : 0.0, q_l1 = lane + 1 < n ? p.q[lane + 1] : 0.0, t_l = lane < n ? p.t[lane] : 0.0;
-    const bool extra = n_ref > 0 || n_obs > 0;
     // trajectories are dealt round-robin starting BEHIND the waves that still have cost chains to add up
     for (int j = fast ? (wid - P % NW + NW) % NW : wid; j < G * C; j += NW) {
         const int g = j / C, c = j - g * C, f = f0 + g;
         if (f >= n_states) continue;
+        const PlanLists ls = lists.at(f);                       // this state's reference path and obstacles
+        const double* ref = ls.ref;
+        const double* obs = ls.obs;
+        const int n_ref = ls.n_ref, n_obs = ls.n_obs;
+        const bool extra = n_ref > 0 || n_obs > 0;
         const int li = c / 3, k = c - li * 3;
         const double df = p.lat[li];
         const double* tg = trig + g * 8;
@@ -328,8 +373,9 @@ __device__ __forceinline__ void plan_block(const PlanParams& p, int f0, int n_st
     for (int idx = tid; idx < G * C; idx += NW * 64) {
         const int g = idx / C, c = idx - g * C, k = c % 3;
         const double* b = base + (g * 3 + k) * 3;
+        const bool with_ref = lists.has_ref(f0 + g < n_states ? f0 + g : f0);   // (states past the batch: computed, never stored)
         // reference accumulates [ref-path] -> velocity -> acceleration -> curvature -> obstacles
-        const double va = n_ref > 0 ? (costs[idx] + b[0]) + b[1] : b[2];
+        const double va = with_ref ? (costs[idx] + b[0]) + b[1] : b[2];
         const double total = (va + costs[CS + idx]) + costs[2 * CS + idx];
         costs[idx] = total;
     }
@@ -349,14 +395,21 @@ __device__ __forceinline__ void plan_block(const PlanParams& p, int f0, int n_st
     }
 }
 
-template <int G, int NW>
-__global__ void __launch_bounds__(NW * 64) planner_kernel(PlanParams p, int n_states, const double* __restrict__ state,
-                                                          const double* __restrict__ ref, int n_ref,
-                                                          const double* __restrict__ obs, int n_obs,
+// plan_block_lists with one reference path and one obstacle list for all states: what the fused time-step kernel calls
+template <int G, int NW, class Hook = PlanNoHook>
+__device__ __forceinline__ void plan_block(const PlanParams& p, int f0, int n_states, const double* state, const double* ref, int n_ref,
+                                           const double* obs, int n_obs, double* wp, double* cost, int32_t* order, double* sm,
+                                           int state_f0 = -1, int rot = 0, Hook after1 = Hook()) {
+    plan_block_lists<G, NW, Hook, PlanShared>(p, f0, n_states, state, PlanShared{ref, n_ref, obs, n_obs}, wp, cost, order, sm, state_f0,
+                                              rot, after1);
+}
+
+template <int G, int NW, class Lists = PlanShared>
+__global__ void __launch_bounds__(NW * 64) planner_kernel(PlanParams p, int n_states, const double* __restrict__ state, Lists lists,
                                                           double* __restrict__ wp, double* __restrict__ cost,
                                                           int32_t* __restrict__ order) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
-    plan_block<G, NW>(p, blockIdx.x * G, n_states, state, ref, n_ref, obs, n_obs, wp, cost, order, sm);
+    plan_block_lists<G, NW, PlanNoHook, Lists>(p, blockIdx.x * G, n_states, state, lists, wp, cost, order, sm);
 }
 
 // Output ring of planner_wave_kernel: 256 units of 16 B.  It holds at most 63 carried units + one tile of
@@ -370,11 +423,9 @@ constexpr int RING_UNITS = 256, RING_DOUBLES = RING_UNITS * 2;
 //   1b  3*FPW lanes: the reference's sequential sums (prefix s_i, velocity cost, acceleration cost)
 //   2   for each of the FPW*C trajectories: positions, heading, curvature, cost, AoS tile -> HBM
 //   3   stable rank of each state's C costs
-template <int FPW, bool EXTRA>     // EXTRA: a reference path and/or obstacles take part in the cost
+template <int FPW, bool EXTRA, class Lists = PlanShared>     // EXTRA: a reference path and/or obstacles take part in the cost
 __global__ void __launch_bounds__(256) planner_wave_kernel(PlanParams p, int n_states,
-                                                           const double* __restrict__ state,
-                                                           const double* __restrict__ ref, int n_ref,
-                                                           const double* __restrict__ obs, int n_obs,
+                                                           const double* __restrict__ state, Lists lists,
                                                            double* __restrict__ wp, double* __restrict__ cost,
                                                            int32_t* __restrict__ order) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -482,6 +533,10 @@ __global__ void __launch_bounds__(256) planner_wave_kernel(PlanParams p, int n_s
         const int f = f0 + g;
         const double* tg = trig + g * 8;
         const double x0 = tg[0], y0 = tg[1], cs = tg[2], sn = tg[3], c2 = tg[4], s2 = tg[5], h0 = tg[6];
+        const PlanLists ls = lists.at(f);                            // this state's reference path and obstacles
+        const double* ref = ls.ref;
+        const double* obs = ls.obs;
+        const int n_ref = ls.n_ref, n_obs = ls.n_obs;
         // per speed k: everything the 7 lateral samples share, kept in registers so that the trajectories can
         // be produced in memory order c = li*3 + k (a wave then writes its 51 KB sequentially; the speed-outer
         // order hops 7344 B between tiles and costs a quarter of the write rate -- tools/wpattern.hip)
@@ -709,6 +764,59 @@ static void fill_params(const av_ctx* ctx, PlanParams& p) {
 
 #ifndef AVHOT_DEVICE_ONLY      // (step.hip includes this file for its device code only)
 
+// The one launch plan of av_planner_plan and av_planner_plan_each.  `extra`: a reference path and / or obstacles may take part in
+// the cost (the wave kernel's EXTRA form).
+template <class Lists>
+static int plan_dispatch(av_ctx* ctx, hipStream_t st, int n_states, const double* state, const Lists& lists, bool extra,
+                         double* waypoints, double* cost, int32_t* order, const char* who) {
+    const int n = ctx->n_points, C = ctx->n_cand;
+    PlanParams p;
+    fill_params(ctx, p);
+    if (n <= 64 && n_states >= 1024) {
+        // two states per wave (103-KB output regions); one per wave -- 51-KB regions, twice the waves -- measured the same
+        // (59.4-60.7 % of HBM peak at 16 384 states either way, alternating runs on one box)
+        constexpr int FPW = 2;
+        const size_t per_wave = (size_t)FPW * 3 * n * 2 + RING_DOUBLES + even_up(FPW * C) + FPW * 3 * 4 + FPW * 8;
+        const size_t lds_w = per_wave * 4 * sizeof(double);
+        if (lds_w <= 64 * 1024) {
+            const int grid_w = (n_states + 4 * FPW - 1) / (4 * FPW);
+            if (extra)
+                hipLaunchKernelGGL((planner_wave_kernel<FPW, true, Lists>), dim3(grid_w), dim3(256), lds_w, st, p, n_states, state,
+                                   lists, waypoints, cost, order);
+            else
+                hipLaunchKernelGGL((planner_wave_kernel<FPW, false, Lists>), dim3(grid_w), dim3(256), lds_w, st, p, n_states, state,
+                                   lists, waypoints, cost, order);
+            AV_LAUNCH_CHECK();
+            return AV_OK;
+        }
+    }
+    int G = n_states >= 4096 ? 8 : (n_states >= 1024 ? 4 : (n_states >= 512 ? 2 : 1));
+    while (G > 1 && plan_lds_doubles(G, n, C, 4) * 8 > 48 * 1024) G >>= 1;
+    // one state per workgroup: its 3 C trajectories over eight waves, or four / two where eight per-wave tiles do not fit
+    // (two fit every configuration av_planner_configure accepts: n = 256, C = 192 needs 41.6 KB)
+    int NW = G == 1 ? 8 : 4;
+    while (G == 1 && NW > 2 && plan_lds_doubles(1, n, C, NW) * 8 > 64 * 1024) NW >>= 1;
+    const size_t lds = plan_lds_doubles(G, n, C, NW) * 8;
+    AV_REQUIRE(lds <= 64 * 1024, AV_EINVAL, "%s: configuration needs %zu B of LDS", who, lds);
+    const int grid = (n_states + G - 1) / G;
+#define AV_PLAN_LAUNCH(GG, NWV)                                                                                          \
+    hipLaunchKernelGGL((planner_kernel<GG, NWV, Lists>), dim3(grid), dim3(NWV * 64), lds, st, p, n_states, state, lists, \
+                       waypoints, cost, order)
+    switch (G) {
+        case 8: AV_PLAN_LAUNCH(8, 4); break;
+        case 4: AV_PLAN_LAUNCH(4, 4); break;
+        case 2: AV_PLAN_LAUNCH(2, 4); break;
+        default:
+            if (NW == 8) AV_PLAN_LAUNCH(1, 8);
+            else if (NW == 4) AV_PLAN_LAUNCH(1, 4);
+            else AV_PLAN_LAUNCH(1, 2);
+            break;
+    }
+#undef AV_PLAN_LAUNCH
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
 
 extern "C" {
 
@@ -802,53 +910,21 @@ int av_planner_plan(av_ctx* ctx, av_stream_t stream, int n_states, const double*
     AV_REQUIRE(n_ref >= 0 && n_obs >= 0 && (n_ref == 0 || ref_path) && (n_obs == 0 || obstacles), AV_EINVAL,
                "av_planner_plan: ref_path/obstacles pointer missing");
     AV_REQUIRE(n_ref != 1, AV_EINVAL, "av_planner_plan: a reference path needs >= 2 points (set_reference_path ignores shorter)");
-    const int n = ctx->n_points, C = ctx->n_cand;
-    PlanParams p;
-    fill_params(ctx, p);
-    hipStream_t st = as_stream(stream);
-    if (n <= 64 && n_states >= 1024) {
-        // two states per wave (103-KB output regions); one per wave -- 51-KB regions, twice the waves -- measured the same
-        // (59.4-60.7 % of HBM peak at 16 384 states either way, alternating runs on one box)
-        constexpr int FPW = 2;
-        const size_t per_wave = (size_t)FPW * 3 * n * 2 + RING_DOUBLES + even_up(FPW * C) + FPW * 3 * 4 + FPW * 8;
-        const size_t lds_w = per_wave * 4 * sizeof(double);
-        if (lds_w <= 64 * 1024) {
-            const int grid_w = (n_states + 4 * FPW - 1) / (4 * FPW);
-            if (n_ref > 0 || n_obs > 0)
-                hipLaunchKernelGGL((planner_wave_kernel<FPW, true>), dim3(grid_w), dim3(256), lds_w, st, p, n_states, state,
-                                   ref_path, n_ref, obstacles, n_obs, waypoints, cost, order);
-            else
-                hipLaunchKernelGGL((planner_wave_kernel<FPW, false>), dim3(grid_w), dim3(256), lds_w, st, p, n_states, state,
-                                   ref_path, n_ref, obstacles, n_obs, waypoints, cost, order);
-            AV_LAUNCH_CHECK();
-            return AV_OK;
-        }
-    }
-    int G = n_states >= 4096 ? 8 : (n_states >= 1024 ? 4 : (n_states >= 512 ? 2 : 1));
-    while (G > 1 && plan_lds_doubles(G, n, C, 4) * 8 > 48 * 1024) G >>= 1;
-    // one state per workgroup: its 3 C trajectories over eight waves, or four / two where eight per-wave tiles do not fit
-    // (two fit every configuration av_planner_configure accepts: n = 256, C = 192 needs 41.6 KB)
-    int NW = G == 1 ? 8 : 4;
-    while (G == 1 && NW > 2 && plan_lds_doubles(1, n, C, NW) * 8 > 64 * 1024) NW >>= 1;
-    const size_t lds = plan_lds_doubles(G, n, C, NW) * 8;
-    AV_REQUIRE(lds <= 64 * 1024, AV_EINVAL, "av_planner_plan: configuration needs %zu B of LDS", lds);
-    const int grid = (n_states + G - 1) / G;
-#define AV_PLAN_LAUNCH(GG, NWV)                                                                                        \
-    hipLaunchKernelGGL((planner_kernel<GG, NWV>), dim3(grid), dim3(NWV * 64), lds, st, p, n_states, state, ref_path, n_ref,  \
-                       obstacles, n_obs, waypoints, cost, order)
-    switch (G) {
-        case 8: AV_PLAN_LAUNCH(8, 4); break;
-        case 4: AV_PLAN_LAUNCH(4, 4); break;
-        case 2: AV_PLAN_LAUNCH(2, 4); break;
-        default:
-            if (NW == 8) AV_PLAN_LAUNCH(1, 8);
-            else if (NW == 4) AV_PLAN_LAUNCH(1, 4);
-            else AV_PLAN_LAUNCH(1, 2);
-            break;
-    }
-#undef AV_PLAN_LAUNCH
-    AV_LAUNCH_CHECK();
-    return AV_OK;
+    return plan_dispatch(ctx, as_stream(stream), n_states, state, PlanShared{ref_path, n_ref, obstacles, n_obs}, n_ref > 0 || n_obs > 0,
+                         waypoints, cost, order, "av_planner_plan");
+}
+
+int av_planner_plan_each(av_ctx* ctx, av_stream_t stream, int n_states, const double* state, const double* ref_path,
+                         const int32_t* n_ref, int rcap, int ref_stride, const double* obstacles, const int32_t* n_obs, int ocap,
+                         double* waypoints, double* cost, int32_t* order) {
+    AV_REQUIRE(ctx && state && cost && order, AV_EINVAL, "av_planner_plan_each: null argument");
+    AV_REQUIRE(ctx->planner_ready, AV_ESTATE, "av_planner_plan_each: call av_planner_configure first");
+    AV_REQUIRE(n_states > 0, AV_EINVAL, "av_planner_plan_each: n_states must be > 0");
+    AV_REQUIRE(!ref_path == !n_ref && !obstacles == !n_obs, AV_EINVAL, "av_planner_plan_each: a list and its counts go together");
+    AV_REQUIRE(ref_stride >= 1, AV_EINVAL, "av_planner_plan_each: ref_stride must be >= 1");
+    AV_REQUIRE((!ref_path || rcap >= 0) && (!obstacles || ocap >= 0), AV_EINVAL, "av_planner_plan_each: negative capacity");
+    return plan_dispatch(ctx, as_stream(stream), n_states, state, PlanEach{ref_path, n_ref, obstacles, n_obs, rcap, ref_stride, ocap},
+                         ref_path || obstacles, waypoints, cost, order, "av_planner_plan_each");
 }
 
 }  // extern "C"

@@ -9,6 +9,10 @@ in the reference's per-frame call order (demo.py:97-120).  Tracker and Kalman/pl
 independent (the planner never consumes tracks), so they run as two branches
 of one fork/join, optionally captured into a hipGraph.  PyTorch only provides device memory and
 the stream; every kernel is in libavhot.so.
+
+Opt-in (HotLoop(obstacles="tracks"), set_obstacles, set_reference_paths): every frame plans with its own obstacle
+list and every stream with its own reference path (av_planner_plan_each); with "tracks" the lists are the frame's
+confirmed tracks (av_track_obstacles), and the planner then runs behind the tracker.
 """
 import ctypes as C
 
@@ -21,7 +25,7 @@ from . import _native as nat
 class HotLoop:
     def __init__(self, n_streams=1, window=1, h=720, w=1280, tcap=64, dcap=8, device=0,
                  tracker_kw=None, kf_kw=None, planner_kw=None, keep_waypoints=True, keep_snapshots=True,
-                 ctx=None, fused_step=None, overlap=1):
+                 ctx=None, fused_step=None, overlap=1, obstacles=None, obstacle_kw=None):
         """fused_step: with window 1, run a time-step as ONE launch (av_hot_step: role-split workgroups running the stage
         kernels' own device code, same results bit for bit) instead of the four stage launches.  None = whenever the
         configuration allows it (window 1, tcap 64, dcap 7..8, iou_threshold > 0, and planner settings whose tiles fit the
@@ -30,7 +34,12 @@ class HotLoop:
         role on the device (av_hot_step_seq), so step t + 1 starts while step t's planner is still writing.  The per-step
         buffers (det_*, snap, snap_n, det2trk, z, vstate, plan_state, wp, cost, order) then exist twice; the attributes always
         name the set of the step enqueued LAST (for `z`: the set the NEXT step will read), and that set is next written by
-        the step after the next one.  Same results as overlap=1 bit for bit."""
+        the step after the next one.  Same results as overlap=1 bit for bit.
+        obstacles="tracks": every frame's confirmed tracks become that frame's planner obstacles (av_track_obstacles: where the
+        BEV panel draws them, in the planner's frame) and the planner runs per state (av_planner_plan_each) behind the tracker;
+        self.obstacles [S, W, tcap, 3] / self.n_obs [S, W].  obstacle_kw overrides av_obstacle_cfg's fields (x_center, x_scale,
+        y_far, y_scale, radius: up to 16 per-class radii, default 1.5 for ids 0..5 = car, truck, pedestrian, cyclist, motorcycle,
+        bus and 0 = no obstacle for the rest).  Needs keep_snapshots=True and the stage launches (no fused step, overlap 1)."""
         if not torch.cuda.is_available():
             raise RuntimeError("HotLoop needs a HIP device; this package has no CPU path")
         self.S, self.W, self.h, self.w, self.tcap, self.dcap = n_streams, window, h, w, tcap, dcap
@@ -78,6 +87,23 @@ class HotLoop:
         self.stream = torch.cuda.Stream(device=d)
         self.graph_id = None
         self._graphs = {}
+        if obstacles not in (None, "tracks"):
+            raise ValueError('obstacles is None or "tracks"')
+        if obstacles == "tracks" and (fused_step or overlap != 1 or not keep_snapshots):
+            raise ValueError('obstacles="tracks" needs keep_snapshots=True and the stage launches (fused_step=True and overlap > 1 '
+                             'plan without obstacles)')
+        self._obs_mode = obstacles                # None | "tracks" | "given" (set_obstacles)
+        self.obstacles = self.n_obs = self.ref_paths = self.n_ref = None
+        if obstacles == "tracks":
+            ok = dict(x_center=320.0, x_scale=0.03, y_far=50.0, y_scale=0.1, radius=[1.5] * 6 + [0.0] * 10)
+            ok.update(obstacle_kw or {})
+            rad = [float(r) for r in ok.pop("radius")]
+            if len(rad) > 16:
+                raise ValueError("obstacle_kw: at most 16 per-class radii")
+            self.ocfg = nat.ObstacleCfg(radius=(C.c_double * 16)(*(rad + [0.0] * (16 - len(rad)))), **ok)
+            self.obstacles = torch.zeros(S, W, tcap, 3, dtype=f64, device=d)
+            self.n_obs = torch.zeros(S, W, dtype=i32, device=d)
+            fused_step = False
         can_fuse = window == 1 and tcap == 64 and 7 <= dcap <= 8 and self.tcfg.iou_threshold > 0
         if fused_step and not can_fuse:
             raise ValueError("fused_step needs window 1, tcap 64, dcap 7..8 and iou_threshold > 0")
@@ -253,6 +279,74 @@ class HotLoop:
                                          nat.ptr(self.plan_state), None, 0, None, 0, nat.ptr(self.wp),
                                          nat.ptr(self.cost), nat.ptr(self.order)))
 
+    # ---- per-state planner inputs -------------------------------------------------------------------
+    def _per_state(self):
+        return self._obs_mode is not None or self.ref_paths is not None
+
+    def _need_stage_launches(self, what):
+        if self.overlap != 1 or self.fused_step:
+            raise RuntimeError("%s needs the stage launches, HotLoop(fused_step=False): the one-launch step plans without reference "
+                               "paths and obstacles" % what)
+
+    def _drop_graphs(self):
+        # a captured step has the planner call it makes, and the buffers it reads, baked in
+        for gid in self._graphs.values():
+            nat.check(self.L.av_graph_destroy(self.ctx.handle, gid))
+        self._graphs, self.graph_id = {}, None
+
+    def set_obstacles(self, obstacles, n_obs):
+        """Caller-supplied obstacles for every frame of the window: float64 device tensor [S, W, ocap, 3] (x, y, radius) and int32
+        [S, W] counts, read by every step from now on; None, None: none.  Not together with obstacles="tracks"."""
+        if self._obs_mode == "tracks":
+            raise RuntimeError('set_obstacles: this loop takes its obstacles from the tracker (obstacles="tracks")')
+        if (obstacles is None) != (n_obs is None):
+            raise ValueError("set_obstacles: the list and its counts go together")
+        if obstacles is not None:
+            self._need_stage_launches("set_obstacles")
+            if not (obstacles.dtype == torch.float64 and obstacles.dim() == 4 and tuple(obstacles.shape[:2]) == (self.S, self.W)
+                    and obstacles.shape[3] == 3 and obstacles.is_contiguous() and obstacles.is_cuda):
+                raise ValueError("set_obstacles: obstacles is a contiguous float64 device tensor [S, W, ocap, 3]")
+            if not (n_obs.dtype == torch.int32 and tuple(n_obs.shape) == (self.S, self.W) and n_obs.is_contiguous() and n_obs.is_cuda):
+                raise ValueError("set_obstacles: n_obs is a contiguous int32 device tensor [S, W]")
+        self.obstacles, self.n_obs = obstacles, n_obs
+        self._obs_mode = None if obstacles is None else "given"
+        self._drop_graphs()
+
+    def set_reference_paths(self, paths, n_ref):
+        """One reference path per stream (each stream's MotionPlanner.set_reference_path, motion_planner.py:93-124): float64
+        device tensor [S, rcap, 2] and int32 [S] point counts (fewer than two points: no path for that stream); None, None: none."""
+        if (paths is None) != (n_ref is None):
+            raise ValueError("set_reference_paths: the paths and their counts go together")
+        if paths is not None:
+            self._need_stage_launches("set_reference_paths")
+            if not (paths.dtype == torch.float64 and paths.dim() == 3 and paths.shape[0] == self.S and paths.shape[2] == 2
+                    and paths.is_contiguous() and paths.is_cuda):
+                raise ValueError("set_reference_paths: paths is a contiguous float64 device tensor [S, rcap, 2]")
+            if not (n_ref.dtype == torch.int32 and tuple(n_ref.shape) == (self.S,) and n_ref.is_contiguous() and n_ref.is_cuda):
+                raise ValueError("set_reference_paths: n_ref is a contiguous int32 device tensor [S]")
+        self.ref_paths, self.n_ref = paths, n_ref
+        self._drop_graphs()
+
+    def enqueue_obstacles(self, stream=None):
+        """obstacles="tracks": the window's snapshot tables and start states -> self.obstacles / self.n_obs (av_track_obstacles);
+        call where the tracker's and the Kalman filter's outputs are complete (after the join)."""
+        if self._obs_mode != "tracks":
+            raise RuntimeError('enqueue_obstacles needs HotLoop(obstacles="tracks")')
+        nat.check(self.L.av_track_obstacles(self.ctx.handle, stream or self._s, C.byref(self.ocfg), self.S * self.W, self.tcap,
+                                            nat.ptr(self.snap), nat.ptr(self.snap_n), nat.ptr(self.plan_state), self.tcap,
+                                            nat.ptr(self.obstacles), nat.ptr(self.n_obs)))
+
+    def enqueue_plan_each(self, stream=None):
+        """The planner with per-state inputs (av_planner_plan_each): frame (s, f) reads obstacle list (s, f) and stream s's
+        reference path."""
+        self._serial_only("enqueue_plan_each")
+        rcap = 0 if self.ref_paths is None else int(self.ref_paths.shape[1])
+        ocap = 0 if self.obstacles is None else int(self.obstacles.shape[2])
+        nat.check(self.L.av_planner_plan_each(self.ctx.handle, stream or self._s, self.S * self.W, nat.ptr(self.plan_state),
+                                              nat.ptr(self.ref_paths), nat.ptr(self.n_ref), rcap, self.W,
+                                              nat.ptr(self.obstacles), nat.ptr(self.n_obs), ocap,
+                                              nat.ptr(self.wp), nat.ptr(self.cost), nat.ptr(self.order)))
+
     def set_wire(self, wire, stream0=0, frame0=0):
         """Fused step only: `wire` (uint8 device tensor [S, av_wire_table_bytes(tcap)], or None) receives every stream's
         track table in the all-gather's wire format from the same launch; header.stream = stream0 + s, header.frame =
@@ -362,7 +456,8 @@ class HotLoop:
     def enqueue_step(self):
         """One window of the whole loop: fork{detect; track} || {kf; plan}; join.  Detections only feed the
         tracker, so both sit on the side stream and the Kalman/planner chain starts at once.  With window 1 and
-        fused_step the whole step is one launch instead."""
+        fused_step the whole step is one launch instead.  With per-state planner inputs (obstacles="tracks", set_obstacles,
+        set_reference_paths) the planner runs behind the join as av_planner_plan_each."""
         if self.fused_step:
             return self.enqueue_step_fused()
         h, L, s = self.ctx.handle, self.L, self._s
@@ -370,6 +465,14 @@ class HotLoop:
         self.enqueue_detect(self.ctx.side_stream)
         self.enqueue_track(self.ctx.side_stream)
         self.enqueue_kf()
+        if self._per_state():
+            # per-state planner inputs: fork{detect; track} || {kf}; join; [tracks -> obstacles]; plan.  With obstacles from the
+            # tracker the planner consumes the tables, so it moves behind the join
+            nat.check(L.av_join(h, s))
+            if self._obs_mode == "tracks":
+                self.enqueue_obstacles()
+            self.enqueue_plan_each()
+            return
         self.enqueue_plan()
         nat.check(L.av_join(h, s))
 
@@ -440,6 +543,8 @@ class HotLoop:
                    order=self.order.cpu().numpy().reshape(self.S, self.W, self.n_cand))
         if self.keep_waypoints:
             out["wp"] = self.wp.cpu().numpy().reshape(self.S, self.W, self.n_cand, self.n_points, 6)
+        if self._obs_mode is not None:
+            out["obstacles"], out["n_obs"] = self.obstacles.cpu().numpy(), self.n_obs.cpu().numpy()
         return out
 
     # algorithmic HBM bytes of one planner launch: per start state

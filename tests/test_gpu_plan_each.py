@@ -1,0 +1,477 @@
+"""Per-state planner inputs: av_planner_plan_each, av_track_obstacles and HotLoop(obstacles="tracks").
+
+(a) a state's results from av_planner_plan_each are those of av_planner_plan with its path and list shared, bit for bit, on
+    every kernel path of the dispatch;
+(b) and they are PlannerRef's (oracle/planner_ref.py) at the project's tolerances (tests/test_gpu_planner.py: cost rtol 1e-12 /
+    atol 1e-12, waypoints rtol 1e-12 / atol 1e-11, ranking by tests/_util.order_mismatch + the stable sort of the device's own
+    costs).  The obstacle term is Lipschitz in the waypoint position (1000 per metre in the hard branch, 10 / (dist - r + 0.1)^2
+    in the soft one), so the cost tolerance gains that constant times the position error already accepted,
+    eps_i = sqrt(2) (1e-12 max(|x_i|, |y_i|) + 1e-11), summed over the (waypoint, obstacle) pairs in a branch; the term jumps at
+    dist = 2r and 4r, so the oracle's margin to those is asserted first (>= 1e-6 m);
+(c) av_track_obstacles against tests/obstacles_ref.py: counts and radii exact, positions at a waypoint's tolerance;
+(d) the loop: obstacles from the device's own tables, plans from the device's own obstacles, stage by stage;
+(e) the combinations the loop refuses.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from tests._util import order_mismatch
+from tests.obstacles_ref import track_obstacles
+from tests.test_gpu_planner import CASES as PLAN_CASES, N_OF, OBS, POOL, REF2, U, check_state, configure
+
+gpu = pytest.mark.gpu
+OCAP, RCAP = 64, 40
+_r11 = np.random.default_rng(11)
+FULL = np.stack([_r11.uniform(-60, 60, 64), _r11.uniform(-60, 60, 64), _r11.uniform(0.3, 2.0, 64)], axis=1)
+FAR = np.array([[5000.0, -5000.0, 1.0]])
+LISTS = [np.zeros((0, 3)), OBS[:1], OBS, FULL, FAR]
+_t = np.linspace(0.0, 0.9, 37)
+ARC = np.stack([80.0 * np.sin(_t), 80.0 * (1.0 - np.cos(_t))], axis=1)           # 37 points, leaves the origin along heading 0
+PATHS = [np.zeros((0, 2)), REF2, ARC, np.array([[3.0, 4.0]])]                       # the last: one point = no path
+
+# (n, num_samples, n_states)
+EACH_CASES = [(51, 7, 1), (51, 7, 5), (16, 2, 13), (65, 7, 3), (1, 7, 3), (151, 7, 3), (256, 64, 2), (51, 7, 513), (16, 2, 1023),
+              (65, 2, 1025), (65, 1, 4097), (51, 7, 1025), (64, 7, 1027), (3, 2, 4099), (16, 64, 1024)]
+REQUIRED = {"block<1,8>", "block<1,4>", "block<1,2>", "block<2,4>", "block<4,4>", "block<8,4>", "wave", "wave+extra"}
+
+
+def _lds(G, n, C_, NW):
+    ev = lambda v: (v + 1) & ~1
+    return (G * 3 * n * 2 + ev(G * 9) + G * 8 + 3 * ev(G * C_) + NW * n * 6) * 8
+
+
+def kernel_path(n, C_, S, extra):
+    """The kernel plan_dispatch launches (planner.hip); extra: a list pointer is given (av_planner_plan: a list is)."""
+    if n <= 64 and S >= 1024:
+        return "wave+extra" if extra else "wave"
+    G = 8 if S >= 4096 else 4 if S >= 1024 else 2 if S >= 512 else 1
+    while G > 1 and _lds(G, n, C_, 4) > 48 * 1024:
+        G //= 2
+    NW = 8 if G == 1 else 4
+    while G == 1 and NW > 2 and _lds(1, n, C_, NW) > 64 * 1024:
+        NW //= 2
+    return "block<%d,%d>" % (G, NW)
+
+
+def test_cases_reach_every_kernel_path():
+    """The per-state call (list pointers given) and the shared calls it is compared with (with and without lists) reach all
+    eight kernels between them; the per-state call alone reaches every one that can take a list."""
+    each = {kernel_path(n, 3 * ns, S, True) for n, ns, S in EACH_CASES}
+    assert each == REQUIRED - {"wave"}, (each, REQUIRED)
+    assert REQUIRED <= each | {kernel_path(n, 3 * ns, S, False) for n, ns, S in EACH_CASES}
+
+
+@pytest.fixture(scope="module")
+def env():
+    torch = pytest.importorskip("torch")
+    if not torch.cuda.is_available():
+        pytest.fail("GPU test selected but no HIP device is visible")
+    from multimodal_autonomous_driving_perception_and_planning_amd import _native as nat
+    return torch, nat, nat.lib(), nat.Context(0)
+
+
+def _dev(env, a, dtype):
+    torch = env[0]
+    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype, device=torch.device("cuda", 0))
+
+
+def _bits(t):
+    torch = __import__("torch")
+    return t.contiguous().view(torch.int64 if t.dtype == torch.float64 else t.dtype)
+
+
+def _packed(S, ref_stride):
+    """Per-state tensors of the assignment list f % 5, path (f // ref_stride) % 4; rows past each count are NaN."""
+    obs = np.full((S, OCAP, 3), np.nan)
+    n_obs = np.zeros(S, np.int32)
+    for f in range(S):
+        l = LISTS[f % 5]
+        obs[f, :len(l)], n_obs[f] = l, len(l)
+    n_paths = (S + ref_stride - 1) // ref_stride
+    ref = np.full((n_paths, RCAP, 2), np.nan)
+    n_ref = np.zeros(n_paths, np.int32)
+    for p in range(n_paths):
+        q = PATHS[p % 4]
+        ref[p, :len(q)], n_ref[p] = q, len(q)
+    return obs, n_obs, ref, n_ref
+
+
+def _outputs(env, S, C_, n, wp):
+    torch = env[0]
+    dev = torch.device("cuda", 0)
+    cost = torch.full((S, C_), float("nan"), dtype=torch.float64, device=dev)
+    order = torch.full((S, C_), -1, dtype=torch.int32, device=dev)
+    w = torch.full((S * C_ * n * 6 + 8,), float("nan"), dtype=torch.float64, device=dev) if wp else None
+    return w, cost, order
+
+
+def run_each(env, n, ns, states_t, ref_stride, wp=True):
+    torch, nat, L, ctx = env
+    S, C_ = states_t.shape[0], 3 * ns
+    obs, n_obs, ref, n_ref = (_dev(env, a, dt) for a, dt in zip(_packed(S, ref_stride), (torch.float64, torch.int32) * 2))
+    w, cost, order = _outputs(env, S, C_, n, wp)
+    nat.check(L.av_planner_plan_each(ctx.handle, None, S, nat.ptr(states_t), nat.ptr(ref), nat.ptr(n_ref), RCAP, ref_stride,
+                                     nat.ptr(obs), nat.ptr(n_obs), OCAP, nat.ptr(w), nat.ptr(cost), nat.ptr(order)))
+    torch.cuda.synchronize()
+    if wp:
+        assert torch.isnan(w[-8:]).all()
+        w = w[:-8].view(S, C_, n, 6)
+    return w, cost, order
+
+
+def run_shared(env, n, ns, states_t, li, pi, wp=True):
+    torch, nat, L, ctx = env
+    S, C_ = states_t.shape[0], 3 * ns
+    l, q = LISTS[li], PATHS[pi]
+    obs_t = _dev(env, l, torch.float64) if len(l) else None
+    ref_t = _dev(env, q, torch.float64) if len(q) >= 2 else None
+    w, cost, order = _outputs(env, S, C_, n, wp)
+    nat.check(L.av_planner_plan(ctx.handle, None, S, nat.ptr(states_t), nat.ptr(ref_t), 0 if ref_t is None else len(q),
+                                nat.ptr(obs_t), 0 if obs_t is None else len(l), nat.ptr(w), nat.ptr(cost), nat.ptr(order)))
+    torch.cuda.synchronize()
+    return (w[:-8].view(S, C_, n, 6) if wp else None), cost, order
+
+
+@gpu
+@pytest.mark.parametrize("n,ns,S", EACH_CASES, ids=["n%d-ns%d-S%d" % c for c in EACH_CASES])
+def test_per_state_equals_shared_bit_for_bit(env, n, ns, S):
+    torch = env[0]
+    print("n=%d C=%d n_states=%d -> %s" % (n, 3 * ns, S, kernel_path(n, 3 * ns, S, True)))
+    configure(env, n, ns)
+    states_t = _dev(env, POOL[np.arange(S) % U], torch.float64)
+    f = torch.arange(S, device=states_t.device)
+    each = {rs: (run_each(env, n, ns, states_t, rs), run_each(env, n, ns, states_t, rs, wp=False)) for rs in (1, 4)}
+    for rs in (1, 4):       # without waypoints: the same costs and order
+        assert torch.equal(_bits(each[rs][0][1]), _bits(each[rs][1][1])) and torch.equal(each[rs][0][2], each[rs][1][2])
+    seen = 0
+    for li in range(5):
+        for pi in range(4):
+            masks = {rs: (f % 5 == li) & ((f // rs) % 4 == pi) for rs in (1, 4)}
+            if not any(bool(m.any()) for m in masks.values()):
+                continue
+            sw, sc, so = run_shared(env, n, ns, states_t, li, pi)
+            _, sc2, so2 = run_shared(env, n, ns, states_t, li, pi, wp=False)
+            assert torch.equal(_bits(sc), _bits(sc2)) and torch.equal(so, so2)
+            for rs, m in masks.items():
+                (ew, ec, eo), _ = each[rs]
+                where = "list %d path %d ref_stride %d" % (li, pi, rs)
+                assert torch.equal(_bits(ec[m]), _bits(sc[m])), where
+                assert torch.equal(eo[m], so[m]), where
+                assert torch.equal(_bits(ew[m]), _bits(sw[m])), where
+                seen += int(m.sum())
+    assert seen == 2 * S
+
+
+# ---- (b) against the oracle ------------------------------------------------------------------------------------------------------
+
+def _margin_and_allowance(wp, obstacles):
+    """wp [C, n, 6] of the oracle, obstacles [m, 3] -> (smallest | dist - 2r |, | dist - 4r | over all pairs, allowance [C])."""
+    if len(obstacles) == 0:
+        return np.inf, np.zeros(len(wp))
+    x, y = wp[:, :, 0, None], wp[:, :, 1, None]
+    ox, oy, r = obstacles[:, 0], obstacles[:, 1], obstacles[:, 2]
+    dist = np.sqrt((x - ox) ** 2 + (y - oy) ** 2)                                    # [C, n, m]
+    eps = np.sqrt(2.0) * (1e-12 * np.maximum(np.abs(x), np.abs(y)) + 1e-11)          # [C, n, 1]
+    hard, soft = dist < 2 * r, (dist >= 2 * r) & (dist < 4 * r)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        allow = np.where(hard, 1000.0 * eps, 0.0) + np.where(soft, 10.0 * eps / (dist - r + 0.1) ** 2, 0.0)
+    margin = min(np.abs(dist - 2 * r).min(), np.abs(dist - 4 * r).min())
+    return float(margin), allow.sum(axis=(1, 2))
+
+
+def check_with_obstacles(got_cost, got_order, got_wp, want, allow, where):
+    """check_state of tests/test_gpu_planner.py with the obstacle allowance added to the cost tolerance."""
+    tol = 1e-12 + 1e-12 * np.abs(want["cost"]) + allow
+    assert np.all(np.abs(got_cost - want["cost"]) <= tol), "%s: cost off by %r (tolerance %r)" % (
+        where, np.abs(got_cost - want["cost"]).max(), tol.min())
+    assert np.array_equal(got_order, np.argsort(got_cost, kind="stable")), where
+    why = order_mismatch(want["cost"], want["order"], got_cost, got_order)
+    assert why is None, "%s: %s" % (where, why)
+    if got_wp is not None:
+        np.testing.assert_allclose(got_wp, want["wp"], rtol=1e-12, atol=1e-11, err_msg=where)
+
+
+_OBS_CASES = {(c[0], c[1]) for c in PLAN_CASES if c[3] == "obs"}        # where test_plan_matches_oracle compares the OBS list
+
+
+def _comparable(n, ns, li, pi):
+    """The OBS lists put waypoints exactly on dist = 2r / 4r: compared where tests/test_gpu_planner.py compares them (the full
+    list, no path), and covered by the bit-for-bit test everywhere else."""
+    if li in (1, 2):
+        return li == 2 and pi in (0, 3) and (n, ns) in _OBS_CASES
+    return True
+
+
+@gpu
+@pytest.mark.parametrize("n,ns,S", EACH_CASES, ids=["n%d-ns%d-S%d" % c for c in EACH_CASES])
+def test_per_state_matches_oracle(env, n, ns, S):
+    from oracle.planner_ref import PlannerRef
+    torch = env[0]
+    configure(env, n, ns)
+    states = POOL[np.arange(S) % U]
+    rs = 4
+    w, cost, order = run_each(env, n, ns, _dev(env, states, torch.float64), rs)
+    ok = [f for f in range(S) if _comparable(n, ns, f % 5, (f // rs) % 4)]
+    pick = {ok[-1]}                                      # at most 40 states: up to ten of every list, spread over the batch
+    for li in (0, 2, 3, 4):
+        c = [f for f in ok if f % 5 == li]
+        pick.update(c[::max(1, -(-len(c) // 9))][:9])
+    pick = sorted(pick)
+    assert len(pick) <= 40 and {f % 5 for f in pick} >= ({0, 3, 4} if S >= 5 else {0})
+    idx = torch.as_tensor(pick, device=w.device)
+    cost, order, w = cost[idx].cpu().numpy(), order[idx].cpu().numpy(), w[idx].cpu().numpy()
+    H, dt = N_OF[n]
+    planners = {}
+    for k, f in enumerate(pick):
+        li, pi = f % 5, (f // rs) % 4
+        if pi not in planners:
+            planners[pi] = PlannerRef(planning_horizon=H, dt=dt, num_samples=ns)
+            planners[pi].set_reference_path(PATHS[pi])                # (ignores the empty and the one-point list)
+        want = planners[pi].plan(states[f], [tuple(o) for o in LISTS[li]])
+        margin, allow = _margin_and_allowance(want["wp"], LISTS[li])
+        where = "state %d list %d path %d" % (f, li, pi)
+        if li == 3:
+            assert margin >= 1e-6, "%s: the oracle is %g m from a branch boundary" % (where, margin)
+        check_with_obstacles(cost[k], order[k], w[k], want, allow, where)
+
+
+# ---- (c) av_track_obstacles ------------------------------------------------------------------------------------------------------
+
+RADIUS = [1.5, 2.0, 0.5, 0.75, 0.0, 2.5, -1.0, 0.0, 0.25, 1.0, 3.0, 0.0, 1.25, -0.5, 0.6, 0.7]
+OBS_CFG = dict(x_center=320.0, x_scale=0.03, y_far=50.0, y_scale=0.1, radius=RADIUS)
+
+
+def _tables(nat, n_states, tcap):
+    """Hand-built tables: empty / all unconfirmed / all rows confirmed / interleaved / every class id (and two outside the
+    radius table) / a few rows, by state; odd and even coordinate sums (half-integer centres)."""
+    rng = np.random.default_rng(100 + tcap)
+    rows = np.zeros((n_states, tcap), np.dtype(nat.TRACK_ROW_FIELDS))
+    n = np.zeros(n_states, np.int32)
+    rows["x1"], rows["y1"] = rng.integers(0, 1200, rows.shape), rng.integers(0, 650, rows.shape)
+    rows["x2"], rows["y2"] = rows["x1"] + rng.integers(1, 80, rows.shape), rows["y1"] + rng.integers(1, 70, rows.shape)
+    rows["id"] = np.arange(n_states * tcap).reshape(rows.shape)
+    rows["cls"] = rng.integers(0, 6, rows.shape)
+    rows["flags"] = 1
+    for f in range(n_states):
+        kind = f % 6
+        if kind == 0:
+            n[f] = 0
+        elif kind == 1:
+            n[f], rows["flags"][f] = tcap // 2 + 3, 0
+        elif kind == 2:
+            n[f] = tcap                                   # every row confirmed, radius > 0 for classes 0..3 and 5
+            rows["cls"][f] = rng.choice([0, 1, 2, 3, 5], tcap)
+        elif kind == 3:
+            n[f] = tcap - 5
+            rows["flags"][f] = (np.arange(tcap) % 3 != 1) * 1 + 2 * (np.arange(tcap) % 2)      # (bit 1 set on some: ignored)
+        elif kind == 4:
+            n[f] = min(tcap, 70)
+            rows["cls"][f] = (np.arange(tcap) % 18) - 1   # -1, 0 .. 15, 16
+        else:
+            n[f] = 1 + f % 5
+    return rows, n
+
+
+@gpu
+@pytest.mark.parametrize("tcap,extra", [(64, 0), (64, 3), (128, 0), (128, 3)])
+def test_track_obstacles_matches_restatement(env, tcap, extra):
+    torch, nat, L, ctx = env
+    S, ocap = 37, tcap + extra
+    rows, n = _tables(nat, S, tcap)
+    rng = np.random.default_rng(5)
+    ps = np.stack([rng.uniform(-200, 200, S), rng.uniform(-200, 200, S), rng.uniform(-np.pi, np.pi, S), rng.uniform(0, 20, S)], axis=1)
+    ps[2:12, 2] = [0.0, np.pi / 2, -np.pi / 2, np.pi, 0.05, 0.0, 0.0, np.pi / 2, -np.pi / 2, np.pi]     # the rest: random
+    ps[2:6, :2] = 0.0
+    cfg = nat.ObstacleCfg(OBS_CFG["x_center"], OBS_CFG["x_scale"], OBS_CFG["y_far"], OBS_CFG["y_scale"], (C.c_double * 16)(*RADIUS))
+    dev = torch.device("cuda", 0)
+    snap = torch.as_tensor(rows.view(np.uint8).reshape(S, tcap, 64)).to(dev)
+    out = torch.full((S * ocap * 3 + 16,), float("nan"), dtype=torch.float64, device=dev)
+    cnt = torch.full((S + 8,), -7, dtype=torch.int32, device=dev)
+    n_t, ps_t = _dev(env, n, torch.int32), _dev(env, ps, torch.float64)
+    nat.check(L.av_track_obstacles(ctx.handle, None, C.byref(cfg), S, tcap, nat.ptr(snap), nat.ptr(n_t), nat.ptr(ps_t), ocap,
+                                   nat.ptr(out), nat.ptr(cnt)))
+    torch.cuda.synchronize()
+    got, got_n = out.cpu().numpy(), cnt.cpu().numpy()
+    assert np.isnan(got[S * ocap * 3:]).all() and (got_n[S:] == -7).all()
+    got = got[:S * ocap * 3].reshape(S, ocap, 3)
+    total = 0
+    for f in range(S):
+        want = track_obstacles(rows[f], n[f], ps[f], OBS_CFG)
+        assert got_n[f] == len(want), "state %d" % f
+        assert np.array_equal(got[f, :len(want), 2], want[:, 2]), "state %d" % f
+        np.testing.assert_allclose(got[f, :len(want), :2], want[:, :2], rtol=1e-12, atol=1e-11, err_msg="state %d" % f)
+        total += len(want)
+    assert got_n[2] == tcap and got_n[0] == 0 and got_n[1] == 0 and total > 5 * tcap
+    # ocap < tcap is refused
+    assert L.av_track_obstacles(ctx.handle, None, C.byref(cfg), S, tcap, nat.ptr(snap), nat.ptr(n_t), nat.ptr(ps_t), tcap - 1,
+                                nat.ptr(out), nat.ptr(cnt)) == -1
+
+
+@gpu
+def test_argument_checks(env):
+    torch, nat, L, ctx = env
+    configure(env, 51, 7)
+    st = _dev(env, POOL[:2], torch.float64)
+    w, cost, order = _outputs(env, 2, 21, 51, False)
+    obs, n_obs, ref, n_ref = (_dev(env, a, dt) for a, dt in zip(_packed(2, 1), (torch.float64, torch.int32) * 2))
+    call = lambda *a: L.av_planner_plan_each(ctx.handle, None, *a)
+    P = nat.ptr
+    assert call(2, P(st), P(ref), P(n_ref), RCAP, 1, P(obs), P(n_obs), OCAP, None, P(cost), P(order)) == 0
+    assert call(0, P(st), P(ref), P(n_ref), RCAP, 1, P(obs), P(n_obs), OCAP, None, P(cost), P(order)) == -1
+    assert call(2, P(st), P(ref), None, RCAP, 1, P(obs), P(n_obs), OCAP, None, P(cost), P(order)) == -1
+    assert call(2, P(st), None, P(n_ref), RCAP, 1, P(obs), P(n_obs), OCAP, None, P(cost), P(order)) == -1
+    assert call(2, P(st), P(ref), P(n_ref), RCAP, 1, P(obs), None, OCAP, None, P(cost), P(order)) == -1
+    assert call(2, P(st), P(ref), P(n_ref), RCAP, 0, P(obs), P(n_obs), OCAP, None, P(cost), P(order)) == -1
+    assert call(2, P(st), None, None, 0, 1, None, None, 0, None, None, P(order)) == -1
+    torch.cuda.synchronize()
+    fresh = nat.Context(0)                                  # planner not configured
+    assert L.av_planner_plan_each(fresh.handle, None, 2, P(st), None, None, 0, 1, None, None, 0, None, P(cost), P(order)) == -4
+    fresh.close()
+
+
+# ---- (d) the loop ------------------------------------------------------------------------------------------------------------------
+
+LOOP_RADIUS = [1.5, 2.0, 0.5, 0.75, 0.75, 2.5] + [0.0] * 10
+LOOP_CFG = dict(OBS_CFG, radius=LOOP_RADIUS)
+FRAMES, OFFSETS = 24, [0, 17, 34]
+_PLANS = {}
+
+
+def _oracle_plan(ps, obstacles):
+    from oracle.planner_ref import PlannerRef
+    key = (ps.tobytes(), obstacles.tobytes())
+    if key not in _PLANS:
+        _PLANS[key] = PlannerRef().plan(ps, [tuple(o) for o in obstacles])
+    return _PLANS[key]
+
+
+def _run_tracks(env, W, graph):
+    """24 frames of the "tracks" loop -> per-step host copies (results, snapshot rows, counts, plan_state)."""
+    from multimodal_autonomous_driving_perception_and_planning_amd.pipeline import HotLoop
+    from oracle.harness_ref import ego_motion
+    loop = HotLoop(n_streams=3, window=W, obstacles="tracks", obstacle_kw=dict(radius=LOOP_RADIUS))
+    assert loop.fused_step is False
+    loop.reset(frame_offsets=OFFSETS)
+    z = np.stack([ego_motion(FRAMES, seed=s) for s in range(3)])
+    steps = []
+    for k in range(FRAMES // W):
+        loop.load_measurements(z[:, k * W:(k + 1) * W])
+        loop.step(graph=graph, sync=True)
+        rows, n = loop.snapshots()
+        steps.append((loop.results(), rows.copy(), n.copy(), loop.plan_state.cpu().numpy()))
+    return loop, z, steps
+
+
+@gpu
+@pytest.mark.parametrize("W", [1, 4])
+def test_loop_plans_around_its_own_tracks(env, W):
+    torch = env[0]
+    loop, z, steps = _run_tracks(env, W, graph=False)
+    changed, skipped, counts, worst = [0, 0, 0], 0, [], np.inf
+    for k, (r, rows, n, ps) in enumerate(steps):
+        assert set(r) >= {"obstacles", "n_obs"}
+        for s in range(3):
+            for f in range(W):
+                where = "W=%d frame %d stream %d" % (W, k * W + f, s)
+                want_obs = track_obstacles(rows[s, f], n[s, f], ps[s, f], LOOP_CFG)
+                m = int(r["n_obs"][s, f])
+                assert m == len(want_obs), where
+                got_obs = r["obstacles"][s, f, :m]
+                assert np.array_equal(got_obs[:, 2], want_obs[:, 2]), where
+                np.testing.assert_allclose(got_obs[:, :2], want_obs[:, :2], rtol=1e-12, atol=1e-11, err_msg=where)
+                live = rows[s, f][:n[s, f]]
+                skipped += int((((live["flags"] & 1) == 1) & (live["cls"] >= 6)).sum())
+                counts.append(m)
+                want = _oracle_plan(ps[s, f], got_obs)
+                margin, allow = _margin_and_allowance(want["wp"], got_obs)
+                worst = min(worst, margin)
+                assert margin >= 1e-6, "%s: the oracle is %g m from a branch boundary" % (where, margin)
+                check_with_obstacles(r["cost"][s, f], r["order"][s, f], r["wp"][s, f], want, allow, where)
+                free = _oracle_plan(ps[s, f], np.zeros((0, 3)))
+                changed[s] += int(want["order"][0] != free["order"][0])
+    print("W=%d: best candidate changed in %r of %d frames, %d rows of classes 6 / 7 skipped, obstacles per frame %d .. %d, "
+          "boundary margin %.3g m" % (W, changed, FRAMES, skipped, min(counts), max(counts), worst))
+    assert all(c >= 1 for c in changed), changed
+    assert skipped >= 1 and min(counts) == 0 and max(counts) > 0
+
+    # the captured graph replays the same steps bit for bit
+    loop_g, _, steps_g = _run_tracks(env, W, graph=True)
+    for (r, _, _, ps), (rg, _, _, psg) in zip(steps, steps_g):
+        assert np.array_equal(ps.view(np.int64), psg.view(np.int64)) and np.array_equal(r["n_obs"], rg["n_obs"])
+        for key in ("cost", "order", "wp"):
+            assert np.array_equal(r[key].view(np.uint8), rg[key].view(np.uint8)), key
+        live = np.arange(loop.tcap)[None, None, :] < r["n_obs"][:, :, None]
+        assert np.array_equal(r["obstacles"][live].view(np.int64), rg["obstacles"][live].view(np.int64))
+
+    # caller-supplied obstacles: the finished run's tensors reproduce its last window's costs
+    from multimodal_autonomous_driving_perception_and_planning_amd.pipeline import HotLoop
+    plain = HotLoop(n_streams=3, window=W, fused_step=False)
+    plain.reset(frame_offsets=OFFSETS)
+    last = FRAMES // W - 1
+    for k in range(last + 1):
+        if k == last:
+            plain.set_obstacles(loop.obstacles, loop.n_obs)
+        plain.load_measurements(z[:, k * W:(k + 1) * W])
+        plain.step(sync=True)
+    rp = plain.results()
+    for key in ("cost", "order", "wp"):
+        assert np.array_equal(rp[key].view(np.uint8), steps[-1][0][key].view(np.uint8)), key
+    assert "obstacles" in rp
+    plain.set_obstacles(None, None)
+    assert "obstacles" not in plain.results()
+
+
+@gpu
+def test_loop_reference_path_per_stream(env):
+    """set_reference_paths: stream s plans every frame of its window against path s = av_planner_plan on that stream's start
+    states with path s shared, bit for bit."""
+    torch, nat, L, ctx = env
+    from multimodal_autonomous_driving_perception_and_planning_amd.pipeline import HotLoop
+    from oracle.harness_ref import ego_motion
+    S, W = 3, 4
+    loop = HotLoop(n_streams=S, window=W, fused_step=False)
+    paths = np.full((S, RCAP, 2), np.nan)
+    n_ref = np.array([len(REF2), len(ARC), 7], np.int32)
+    paths[0, :2], paths[1, :37], paths[2, :7] = REF2, ARC, ARC[::-1][:7] + [0.0, 2.0]
+    loop.set_reference_paths(_dev(env, paths, torch.float64), _dev(env, n_ref, torch.int32))
+    loop.load_measurements(np.stack([ego_motion(W, seed=s) for s in range(S)]))
+    loop.step(sync=True)
+    r = loop.results()
+    assert "obstacles" not in r
+    for s in range(S):
+        st = loop.plan_state[s].contiguous()
+        w, cost, order = _outputs(env, W, loop.n_cand, loop.n_points, True)
+        ref_t = _dev(env, paths[s, :n_ref[s]], torch.float64)
+        nat.check(L.av_planner_plan(loop.ctx.handle, None, W, nat.ptr(st), nat.ptr(ref_t), int(n_ref[s]), None, 0, nat.ptr(w),
+                                    nat.ptr(cost), nat.ptr(order)))
+        torch.cuda.synchronize()
+        assert np.array_equal(cost.cpu().numpy().view(np.int64), r["cost"][s].view(np.int64)), s
+        assert np.array_equal(order.cpu().numpy(), r["order"][s]), s
+        assert np.array_equal(w[:-8].cpu().numpy().view(np.int64), r["wp"][s].reshape(-1).view(np.int64)), s
+    assert len({r["cost"][s, 0].tobytes() for s in range(S)}) == S          # three paths, three different costs
+
+
+# ---- (e) refusals -------------------------------------------------------------------------------------------------------------------
+
+@gpu
+def test_loop_refusals(env):
+    torch = env[0]
+    from multimodal_autonomous_driving_perception_and_planning_amd.pipeline import HotLoop
+    for kw in (dict(fused_step=True), dict(overlap=2), dict(keep_snapshots=False)):
+        with pytest.raises(ValueError):
+            HotLoop(n_streams=2, window=1, obstacles="tracks", **kw)
+    with pytest.raises(ValueError):
+        HotLoop(n_streams=2, obstacles="boxes")
+    fused = HotLoop()
+    assert fused.fused_step is True
+    dev = torch.device("cuda", 0)
+    with pytest.raises(RuntimeError):
+        fused.set_obstacles(torch.zeros(1, 1, 4, 3, dtype=torch.float64, device=dev), torch.zeros(1, 1, dtype=torch.int32, device=dev))
+    with pytest.raises(RuntimeError):
+        fused.set_reference_paths(torch.zeros(1, 4, 2, dtype=torch.float64, device=dev), torch.zeros(1, dtype=torch.int32, device=dev))
+    tracks = HotLoop(n_streams=2, window=1, obstacles="tracks")
+    assert tracks.fused_step is False
+    with pytest.raises(RuntimeError):
+        tracks.set_obstacles(None, None)

@@ -1,0 +1,112 @@
+#!/usr/bin/env python3
+"""Planner with per-state inputs: what the lookup costs.
+
+  planner   av_planner_plan without extras | av_planner_plan_each with null lists | av_planner_plan with 16 shared obstacles |
+            av_planner_plan_each with the same 16 per state, at 64 and 16 384 start states, default planner
+  step      HotLoop(64 streams, fused_step=False) plain and with obstacles="tracks", window 1 and 256
+
+HIP events on the stream the work runs on, median of --reps launches after warm-up, the whole measurement --rounds times
+(the spread between rounds is the figure's own noise).  Runs on a tree without av_planner_plan_each too (those columns are
+left out): the same script gives the figures of an older commit.
+"""
+import argparse
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+from multimodal_autonomous_driving_perception_and_planning_amd import _native as nat  # noqa: E402
+from multimodal_autonomous_driving_perception_and_planning_amd.harness import generate_ego_motion  # noqa: E402
+from multimodal_autonomous_driving_perception_and_planning_amd.pipeline import HotLoop  # noqa: E402
+
+
+def timed(L, stream, fn, reps, warm=10):
+    """Median us of fn() (an enqueue on `stream`) between two events."""
+    e0, e1 = C.c_void_p(), C.c_void_p()
+    nat.check(L.av_event_create(C.byref(e0)))
+    nat.check(L.av_event_create(C.byref(e1)))
+    ms, out = C.c_float(), []
+    for k in range(warm + reps):
+        nat.check(L.av_event_record(e0, stream))
+        fn()
+        nat.check(L.av_event_record(e1, stream))
+        nat.check(L.av_event_elapsed_ms(e0, e1, C.byref(ms)))
+        if k >= warm:
+            out.append(ms.value * 1e3)
+    L.av_event_destroy(e0), L.av_event_destroy(e1)
+    return float(np.median(out))
+
+
+def planner_figures(reps):
+    L, ctx = nat.lib(), nat.Context(0)
+    cfg = nat.PlannerCfg(5.0, 0.1, 7, 0, 1.0, 0.5, 0.3, 0.4)
+    nat.check(L.av_planner_configure(ctx.handle, C.byref(cfg)))
+    dev, st = torch.device("cuda", 0), torch.cuda.Stream()
+    s = C.c_void_p(st.cuda_stream)
+    rng = np.random.default_rng(1)
+    has_each = hasattr(L, "av_planner_plan_each")
+    out = {}
+    for S in (64, 16384):
+        state = torch.as_tensor(np.stack([rng.uniform(-50, 50, S), rng.uniform(-50, 50, S), rng.uniform(-3, 3, S),
+                                          rng.uniform(5, 15, S)], axis=1), device=dev)
+        # 16 obstacles ahead of every state, in its own frame (so every list costs the same work)
+        ahead = np.stack([rng.uniform(5, 40, 16), rng.uniform(-4, 4, 16), rng.uniform(0.5, 1.5, 16)], axis=1)
+        sn = state.cpu().numpy()
+        each = np.zeros((S, 16, 3))
+        each[:, :, 0] = sn[:, None, 0] + ahead[None, :, 0] * np.cos(sn[:, None, 2]) - ahead[None, :, 1] * np.sin(sn[:, None, 2])
+        each[:, :, 1] = sn[:, None, 1] + ahead[None, :, 0] * np.sin(sn[:, None, 2]) + ahead[None, :, 1] * np.cos(sn[:, None, 2])
+        each[:, :, 2] = ahead[None, :, 2]
+        obs_each, n_each = torch.as_tensor(each, device=dev), torch.full((S,), 16, dtype=torch.int32, device=dev)
+        obs_shared = obs_each[0].contiguous()
+        wp = torch.empty(S * 21 * 51 * 6, dtype=torch.float64, device=dev)
+        cost = torch.empty(S, 21, dtype=torch.float64, device=dev)
+        order = torch.empty(S, 21, dtype=torch.int32, device=dev)
+        P = nat.ptr
+        runs = {"plan": lambda: nat.check(L.av_planner_plan(ctx.handle, s, S, P(state), None, 0, None, 0, P(wp), P(cost), P(order))),
+                "plan+16": lambda: nat.check(L.av_planner_plan(ctx.handle, s, S, P(state), None, 0, P(obs_shared), 16, P(wp), P(cost),
+                                                               P(order)))}
+        if has_each:
+            runs["each(null)"] = lambda: nat.check(L.av_planner_plan_each(ctx.handle, s, S, P(state), None, None, 0, 1, None, None, 0,
+                                                                          P(wp), P(cost), P(order)))
+            runs["each+16"] = lambda: nat.check(L.av_planner_plan_each(ctx.handle, s, S, P(state), None, None, 0, 1, P(obs_each),
+                                                                       P(n_each), 16, P(wp), P(cost), P(order)))
+        for name, fn in runs.items():
+            out["%s S=%d" % (name, S)] = round(timed(L, s, fn, reps), 2)
+        torch.cuda.synchronize()
+    ctx.close()
+    return out
+
+
+def step_figures(reps):
+    L, out = nat.lib(), {}
+    modes = [("plain", {})]
+    if hasattr(L, "av_track_obstacles"):
+        modes.append(("tracks", dict(obstacles="tracks")))
+    for W in (1, 256):
+        z = np.stack([np.asarray(generate_ego_motion(W, seed=k)) for k in range(64)])
+        for name, kw in modes:
+            loop = HotLoop(n_streams=64, window=W, fused_step=False, **kw)
+            loop.load_measurements(z)
+            for graph in (False, True):
+                us = timed(L, loop._s, lambda: loop.step(graph=graph), reps if W == 1 else max(5, reps // 4), warm=5)
+                out["%s W=%d%s" % (name, W, " graph" if graph else "")] = round(us, 1)
+            loop.synchronize()
+            del loop
+    return out
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--what", default="planner,step")
+    a = ap.parse_args()
+    for r in range(a.rounds):
+        if "planner" in a.what:
+            print("planner us:", planner_figures(a.reps), flush=True)
+        if "step" in a.what:
+            print("step us:", step_figures(a.reps), flush=True)
