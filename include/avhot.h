@@ -258,6 +258,18 @@ int av_planner_plan_each(av_ctx* ctx, av_stream_t stream, int n_states, const do
                          const double* obstacles, const int32_t* n_obs, int ocap,
                          double* waypoints, double* cost, int32_t* order);
 
+/* av_planner_plan_each around MOVING obstacles: rows of five doubles (x, y, radius, vx, vy), position and velocity in the
+ * planner's frame (m, m/s).  For the waypoint with timestamp t (waypoint field 4, the configuration's table value) the disc is at
+ *   px = x + vx * t,  py = y + vy * t           (float64, two roundings each: no FMA)
+ * and the rest of the cost is av_planner_plan's unchanged: dist = sqrt((wx - px)^2 + (wy - py)^2), the < 2r and < 4r branches
+ * (:253-259), per waypoint over the list in order.  vx = vy = 0 is av_planner_plan_each's term, bit for bit.
+ *   obstacles [n_states][ocap][5], n_obs [n_states] clamped to 0..ocap; both NULL = no obstacles
+ * Every other argument, the clamping, the NULL rules, the error codes and the dispatch are av_planner_plan_each's. */
+int av_planner_plan_moving(av_ctx* ctx, av_stream_t stream, int n_states, const double* state,
+                           const double* ref_path, const int32_t* n_ref, int rcap, int ref_stride,
+                           const double* obstacles, const int32_t* n_obs, int ocap,
+                           double* waypoints, double* cost, int32_t* order);
+
 /* The tracker's tables as the planner's obstacles: every confirmed track (flags bit0) of a frame, in table order, at the place
  * the BEV panel draws it (av_bev_build; bev_renderer.py:207-208), carried into the planner's frame by the frame's start state
  * (x0, y0, h, .) the way a candidate is placed (motion_planner.py:175-180):
@@ -275,6 +287,19 @@ typedef struct {
 int av_track_obstacles(av_ctx* ctx, av_stream_t stream, const av_obstacle_cfg* cfg, int n_states, int tcap,
                        const av_track_row* snap, const int32_t* snap_n, const double* plan_state,
                        int ocap, double* obstacles, int32_t* n_obs);
+/* av_track_obstacles with the tracks' velocities, for av_planner_plan_moving: the same rows in the same order at the same place
+ * with the same radius (columns 0..2 and n_obs are av_track_obstacles' output), and in columns 3..4 the constant velocity the
+ * track's last centre difference predicts (Track.velocity, what predict_next_position uses, multi_object_tracker.py:35-47), in
+ * the planner's frame.  With the frame's start state (x0, y0, h, v0) and frame_rate in frames per second (> 0, finite):
+ *   rvx, rvy = row.vx, row.vy if row.hist_len >= 2, else 0, 0        (px per frame)
+ *   vl = (rvx * x_scale) * frame_rate                                  lateral, m/s, relative to the ego
+ *   vf = v0 - (rvy * y_scale) * frame_rate                             forward, m/s: the image is ego-centric, so the ego's
+ *                                                                      own speed is added (a track at rest in it moves with the ego)
+ *   vx = vf cos h + vl cos(h + pi/2), vy = vf sin h + vl sin(h + pi/2)
+ *   obstacles [n_states][ocap][5] (x, y, radius, vx, vy); everything else as av_track_obstacles */
+int av_track_obstacles_moving(av_ctx* ctx, av_stream_t stream, const av_obstacle_cfg* cfg, double frame_rate, int n_states,
+                              int tcap, const av_track_row* snap, const int32_t* snap_n, const double* plan_state,
+                              int ocap, double* obstacles, int32_t* n_obs);
 
 /* generate_polynomial_trajectory for arbitrary (lateral offset, target speed) pairs (:126-204).
  *   state [n_traj][4], end_lateral_offset [n_traj], target_velocity [n_traj] -> waypoints [n_traj][n][6] */
@@ -286,6 +311,11 @@ int av_planner_generate(av_ctx* ctx, av_stream_t stream, int n_traj, const doubl
 int av_planner_evaluate(av_ctx* ctx, av_stream_t stream, int n_traj, int n_wp, const double* waypoints,
                         const double* ref_path, int n_ref, const double* obstacles, int n_obs,
                         double* cost);
+/* av_planner_evaluate around moving obstacles [n_obs][5] (x, y, radius, vx, vy): the same strict order (obstacle outer,
+ * waypoint inner), each disc at x + vx * t, y + vy * t for t = that waypoint's own field 4. */
+int av_planner_evaluate_moving(av_ctx* ctx, av_stream_t stream, int n_traj, int n_wp, const double* waypoints,
+                               const double* ref_path, int n_ref, const double* obstacles, int n_obs,
+                               double* cost);
 
 /* ---- L1-L7: lane detector ----------------------------------------------------------------------
  * Replaces LaneDetector.detect and its private stages (src/perception/lane_detector.py:47-218):

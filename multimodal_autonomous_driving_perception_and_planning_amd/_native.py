@@ -131,6 +131,9 @@ _SIGS = [
     ("av_planner_plan", C.c_int, [vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp]),
     ("av_planner_plan_each", C.c_int, [vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp]),
     ("av_track_obstacles", C.c_int, [vp, vp, C.POINTER(ObstacleCfg), C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp]),
+    ("av_planner_plan_moving", C.c_int, [vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp]),
+    ("av_track_obstacles_moving", C.c_int, [vp, vp, C.POINTER(ObstacleCfg), C.c_double, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp,
+                                            vp]),
     ("av_hot_step", C.c_int, [vp, vp, C.POINTER(TrackerCfg), C.POINTER(KfCfg)] + [C.c_int] * 5 + [vp] * 17 + [vp, C.c_int, C.c_int]),
     ("av_hot_step_fits", C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     ("av_hot_steps_seq", C.c_int, [vp, C.c_int, vp, C.POINTER(TrackerCfg), C.POINTER(KfCfg)] + [C.c_int] * 5 + [vp] * 7 +
@@ -139,6 +142,7 @@ _SIGS = [
      [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int]),
     ("av_planner_generate", C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp]),
     ("av_planner_evaluate", C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp]),
+    ("av_planner_evaluate_moving", C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp]),
     ("av_lane_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     ("av_lane_workspace_init", C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     ("av_lane_workspace_view", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t),

@@ -9,13 +9,19 @@
 // Mapping: one wave per start state (= one frame of one stream), lane = table row, 64 rows per round.  Confirmed rows whose class has
 // a positive radius are compacted in table order by ballot + prefix count; every lane writes its own 24-byte (x, y, radius) row.
 // float64 in the operation order include/avhot.h states (-ffp-contract=off: no FMA), the planner's own for a waypoint.
+//
+// The moving form (av_track_obstacles_moving) adds the track's velocity in the planner's frame to every row: the row's last centre
+// difference (px / frame, Track.velocity, multi_object_tracker.py:35-47) scaled like the position and by the frame rate, plus the
+// ego's own speed along its heading -- the image is ego-centric, so a track at rest in it moves with the ego.  Same wave per
+// state, same compaction; a kept lane writes 40 bytes (x, y, radius, vx, vy).
 #include "common.h"
 
 #include <cmath>
 
 namespace {
 
-__global__ void __launch_bounds__(256) track_obstacles_kernel(av_obstacle_cfg cfg, int n_states, int tcap,
+template <bool MOVING>      // MOVING: rows of 5 doubles, frame_rate in frames per second (unused otherwise)
+__global__ void __launch_bounds__(256) track_obstacles_kernel(av_obstacle_cfg cfg, double frame_rate, int n_states, int tcap,
                                                               const av_track_row* __restrict__ snap,
                                                               const int32_t* __restrict__ snap_n,
                                                               const double* __restrict__ plan_state, int ocap,
@@ -32,12 +38,14 @@ __global__ void __launch_bounds__(256) track_obstacles_kernel(av_obstacle_cfg cf
     sincos(h, &sn, &cs);
     sincos(h + 1.5707963267948966, &s2, &c2);                       // heading + np.pi/2  (motion_planner.py:179)
     const av_track_row* rows = snap + (size_t)f * tcap;
-    double* out = obstacles + (size_t)f * ocap * 3;
+    constexpr int OS = MOVING ? 5 : 3;
+    const double v0 = MOVING ? plan_state[(size_t)f * 4 + 3] : 0.0;
+    double* out = obstacles + (size_t)f * ocap * OS;
     int count = 0;                                                  // obstacles of the rows before this round
     for (int b = 0; b < n; b += 64) {
         const int i = b + lane;
         bool keep = false;
-        double ox = 0.0, oy = 0.0, rad = 0.0;
+        double ox = 0.0, oy = 0.0, rad = 0.0, ovx = 0.0, ovy = 0.0;
         if (i < n) {
             const av_track_row r = rows[i];
 #pragma unroll
@@ -47,11 +55,20 @@ __global__ void __launch_bounds__(256) track_obstacles_kernel(av_obstacle_cfg cf
             const double l = (cx - cfg.x_center) * cfg.x_scale, fw = cfg.y_far - cy * cfg.y_scale;
             ox = (x0 + fw * cs) + l * c2;
             oy = (y0 + fw * sn) + l * s2;
+            if constexpr (MOVING) {
+                const bool has_vel = r.hist_len >= 2;               // (vx, vy are valid from the second centre on)
+                const double rvx = has_vel ? (double)r.vx : 0.0, rvy = has_vel ? (double)r.vy : 0.0;
+                const double vl = (rvx * cfg.x_scale) * frame_rate;                  // lateral, m/s, relative to the ego
+                const double vf = v0 - (rvy * cfg.y_scale) * frame_rate;             // forward, m/s: the ego's own speed added
+                ovx = vf * cs + vl * c2;
+                ovy = vf * sn + vl * s2;
+            }
         }
         const unsigned long long m = __ballot(keep);
         if (keep) {
-            double* o = out + (size_t)(count + __popcll(m & ((1ull << lane) - 1ull))) * 3;      // < n <= tcap <= ocap
+            double* o = out + (size_t)(count + __popcll(m & ((1ull << lane) - 1ull))) * OS;     // < n <= tcap <= ocap
             o[0] = ox, o[1] = oy, o[2] = rad;
+            if constexpr (MOVING) o[3] = ovx, o[4] = ovy;
         }
         count += __popcll(m);
     }
@@ -60,14 +77,30 @@ __global__ void __launch_bounds__(256) track_obstacles_kernel(av_obstacle_cfg cf
 
 }  // namespace
 
+template <bool MOVING>
+static int track_obstacles_launch(av_ctx* ctx, av_stream_t stream, const av_obstacle_cfg* cfg, double frame_rate, int n_states, int tcap,
+                                  const av_track_row* snap, const int32_t* snap_n, const double* plan_state, int ocap,
+                                  double* obstacles, int32_t* n_obs, const char* who) {
+    AV_REQUIRE(ctx && cfg && snap && snap_n && plan_state && obstacles && n_obs, AV_EINVAL, "%s: null argument", who);
+    AV_REQUIRE(n_states > 0 && tcap > 0, AV_EINVAL, "%s: n_states and tcap must be > 0", who);
+    AV_REQUIRE(ocap >= tcap, AV_EINVAL, "%s: ocap %d < tcap %d (no obstacle is ever dropped)", who, ocap, tcap);
+    AV_REQUIRE(!MOVING || (frame_rate > 0.0 && std::isfinite(frame_rate)), AV_EINVAL, "%s: frame_rate must be > 0 and finite", who);
+    hipLaunchKernelGGL(track_obstacles_kernel<MOVING>, dim3((n_states + 3) / 4), dim3(256), 0, as_stream(stream), *cfg, frame_rate,
+                       n_states, tcap, snap, snap_n, plan_state, ocap, obstacles, n_obs);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
 extern "C" int av_track_obstacles(av_ctx* ctx, av_stream_t stream, const av_obstacle_cfg* cfg, int n_states, int tcap,
                                   const av_track_row* snap, const int32_t* snap_n, const double* plan_state, int ocap,
                                   double* obstacles, int32_t* n_obs) {
-    AV_REQUIRE(ctx && cfg && snap && snap_n && plan_state && obstacles && n_obs, AV_EINVAL, "av_track_obstacles: null argument");
-    AV_REQUIRE(n_states > 0 && tcap > 0, AV_EINVAL, "av_track_obstacles: n_states and tcap must be > 0");
-    AV_REQUIRE(ocap >= tcap, AV_EINVAL, "av_track_obstacles: ocap %d < tcap %d (no obstacle is ever dropped)", ocap, tcap);
-    hipLaunchKernelGGL(track_obstacles_kernel, dim3((n_states + 3) / 4), dim3(256), 0, as_stream(stream), *cfg, n_states, tcap, snap,
-                       snap_n, plan_state, ocap, obstacles, n_obs);
-    AV_LAUNCH_CHECK();
-    return AV_OK;
+    return track_obstacles_launch<false>(ctx, stream, cfg, 0.0, n_states, tcap, snap, snap_n, plan_state, ocap, obstacles, n_obs,
+                                         "av_track_obstacles");
+}
+
+extern "C" int av_track_obstacles_moving(av_ctx* ctx, av_stream_t stream, const av_obstacle_cfg* cfg, double frame_rate, int n_states,
+                                         int tcap, const av_track_row* snap, const int32_t* snap_n, const double* plan_state, int ocap,
+                                         double* obstacles, int32_t* n_obs) {
+    return track_obstacles_launch<true>(ctx, stream, cfg, frame_rate, n_states, tcap, snap, snap_n, plan_state, ocap, obstacles, n_obs,
+                                        "av_track_obstacles_moving");
 }

@@ -116,19 +116,26 @@ struct PlanNoHook {
 // f is, so those instantiations pay nothing for the lookup.
 struct PlanLists {
     const double* ref; int n_ref;      // [n_ref][2]
-    const double* obs; int n_obs;      // [n_obs][3]
+    const double* obs; int n_obs;      // [n_obs][OSTRIDE]
 };
 // one reference path and one obstacle list for every state of the launch (av_planner_plan)
 struct PlanShared {
+    static constexpr int OSTRIDE = 3;             // doubles per obstacle row: (x, y, radius)
+    static constexpr bool MOVING = false;
     const double* ref; int n_ref;
     const double* obs; int n_obs;
     __device__ __forceinline__ PlanLists at(int) const { return PlanLists{ref, n_ref, obs, n_obs}; }
     __device__ __forceinline__ bool has_ref(int) const { return n_ref > 0; }
 };
-// state f reads obstacle list f and reference path f / ref_stride (av_planner_plan_each); a null list pointer: none for any state
-struct PlanEach {
+// state f reads obstacle list f and reference path f / ref_stride (av_planner_plan_each); a null list pointer: none for any state.
+// OS = 5 (av_planner_plan_moving): rows (x, y, radius, vx, vy), the disc of the waypoint with timestamp t is at (x + vx t, y + vy t);
+// the row width and the motion are properties of the type, so the OS = 3 kernels are the ones they were
+template <int OS>
+struct PlanEachT {
+    static constexpr int OSTRIDE = OS;
+    static constexpr bool MOVING = OS == 5;
     const double* ref; const int32_t* n_ref;      // [n_paths][rcap][2], [n_paths]
-    const double* obs; const int32_t* n_obs;      // [n_states][ocap][3], [n_states]
+    const double* obs; const int32_t* n_obs;      // [n_states][ocap][OS], [n_states]
     int rcap, ref_stride, ocap;
     __device__ __forceinline__ int path_points(int pth) const {
         const int k = n_ref[pth] > rcap ? rcap : n_ref[pth];
@@ -146,11 +153,13 @@ struct PlanEach {
         if (obs) {
             const int k = n_obs[f];
             l.n_obs = k < 0 ? 0 : (k > ocap ? ocap : k);
-            l.obs = obs + (size_t)f * ocap * 3;
+            l.obs = obs + (size_t)f * ocap * OS;
         }
         return l;
     }
 };
+using PlanEach = PlanEachT<3>;
+using PlanEachMoving = PlanEachT<5>;
 
 template <int G, int NW, class Hook = PlanNoHook, class Lists = PlanShared>
 __device__ __forceinline__ void plan_block_lists(const PlanParams& p, int f0, int n_states, const double* __restrict__ state,
@@ -346,8 +355,14 @@ __device__ __forceinline__ void plan_block_lists(const PlanParams& p, int f0, in
                 }
                 lat_sum += p.w_lat * (md * md);
             }
+            constexpr int OS = Lists::OSTRIDE;
             for (int q = 0; q < n_obs; ++q) {                   // :253-259
-                const double ox = obs[3 * q], oy = obs[3 * q + 1], rad = obs[3 * q + 2];
+                double ox = obs[OS * q], oy = obs[OS * q + 1];
+                const double rad = obs[OS * q + 2];
+                if constexpr (Lists::MOVING) {                  // the disc where its velocity has carried it by this waypoint's time
+                    const double tw = w[4];
+                    ox = ox + obs[OS * q + 3] * tw, oy = oy + obs[OS * q + 4] * tw;
+                }
                 const double ex = x - ox, ey = y - oy;
                 const double dist = sqrt(ex * ex + ey * ey);
                 if (dist < rad * 2.0) obs_sum += 1000.0 * (rad * 2.0 - dist);
@@ -594,8 +609,11 @@ __global__ void __launch_bounds__(256) planner_wave_kernel(PlanParams p, int n_s
                     lat_sum = wave_sum_dpp(in ? p.w_lat * (md * md) : 0.0);
                 }
                 if (EXTRA && n_obs > 0) {
+                    constexpr int OS = Lists::OSTRIDE;
                     for (int q = 0; q < n_obs; ++q) {
-                        const double ox = obs[3 * q], oy = obs[3 * q + 1], rad = obs[3 * q + 2];
+                        double ox = obs[OS * q], oy = obs[OS * q + 1];
+                        const double rad = obs[OS * q + 2];
+                        if constexpr (Lists::MOVING) ox = ox + obs[OS * q + 3] * t_i, oy = oy + obs[OS * q + 4] * t_i;
                         const double ex = x - ox, ey = y - oy;
                         const double dist = sqrt(ex * ex + ey * ey);
                         if (dist < rad * 2.0) obs_sum += 1000.0 * (rad * 2.0 - dist);
@@ -705,6 +723,7 @@ __global__ void __launch_bounds__(64) planner_generate_kernel(PlanParams p, int 
 
 // evaluate_trajectory_cost for an arbitrary trajectory, strictly in the reference's accumulation order
 // (one thread per trajectory; this is a utility entry, the hot path is planner_kernel).
+template <bool MOVING>      // MOVING: obstacle rows (x, y, radius, vx, vy), each at its place for the waypoint's own timestamp (field 4)
 __global__ void planner_evaluate_kernel(PlanParams p, int n_traj, int n_wp, const double* __restrict__ wp,
                                         const double* __restrict__ ref, int n_ref, const double* __restrict__ obs,
                                         int n_obs, double* __restrict__ cost) {
@@ -738,10 +757,13 @@ __global__ void planner_evaluate_kernel(PlanParams p, int n_traj, int n_wp, cons
         }
     }
     for (int i = 0; i < n_wp; ++i) c = c + p.w_curv * (w[6 * i + 5] * w[6 * i + 5]);
+    constexpr int OS = MOVING ? 5 : 3;
     for (int q = 0; q < n_obs; ++q) {
-        const double ox = obs[3 * q], oy = obs[3 * q + 1], rad = obs[3 * q + 2];
+        const double ox = obs[OS * q], oy = obs[OS * q + 1], rad = obs[OS * q + 2];
         for (int i = 0; i < n_wp; ++i) {
-            const double ex = w[6 * i] - ox, ey = w[6 * i + 1] - oy;
+            double px = ox, py = oy;
+            if constexpr (MOVING) px = ox + obs[OS * q + 3] * w[6 * i + 4], py = oy + obs[OS * q + 4] * w[6 * i + 4];
+            const double ex = w[6 * i] - px, ey = w[6 * i + 1] - py;
             const double dist = sqrt(ex * ex + ey * ey);
             if (dist < rad * 2.0) c = c + 1000.0 * (rad * 2.0 - dist);
             else if (dist < rad * 4.0) c = c + 10.0 / (dist - rad + 0.1);
@@ -764,7 +786,7 @@ static void fill_params(const av_ctx* ctx, PlanParams& p) {
 
 #ifndef AVHOT_DEVICE_ONLY      // (step.hip includes this file for its device code only)
 
-// The one launch plan of av_planner_plan and av_planner_plan_each.  `extra`: a reference path and / or obstacles may take part in
+// The one launch plan of av_planner_plan, av_planner_plan_each and av_planner_plan_moving.  `extra`: a reference path and / or obstacles may take part in
 // the cost (the wave kernel's EXTRA form).
 template <class Lists>
 static int plan_dispatch(av_ctx* ctx, hipStream_t st, int n_states, const double* state, const Lists& lists, bool extra,
@@ -834,19 +856,51 @@ int av_planner_generate(av_ctx* ctx, av_stream_t stream, int n_traj, const doubl
     return AV_OK;
 }
 
-int av_planner_evaluate(av_ctx* ctx, av_stream_t stream, int n_traj, int n_wp, const double* waypoints,
-                        const double* ref_path, int n_ref, const double* obstacles, int n_obs, double* cost) {
-    AV_REQUIRE(ctx && cost && (waypoints || n_wp == 0), AV_EINVAL, "av_planner_evaluate: null argument");
-    AV_REQUIRE(ctx->planner_ready, AV_ESTATE, "av_planner_evaluate: call av_planner_configure first");
-    AV_REQUIRE(n_traj > 0 && n_wp >= 0, AV_EINVAL, "av_planner_evaluate: bad sizes");
+}  // extern "C"
+
+// av_planner_evaluate and av_planner_evaluate_moving: the same checks and launch, the obstacle rows 3 or 5 doubles wide
+template <bool MOVING>
+static int evaluate_launch(av_ctx* ctx, av_stream_t stream, int n_traj, int n_wp, const double* waypoints, const double* ref_path,
+                           int n_ref, const double* obstacles, int n_obs, double* cost, const char* who) {
+    AV_REQUIRE(ctx && cost && (waypoints || n_wp == 0), AV_EINVAL, "%s: null argument", who);
+    AV_REQUIRE(ctx->planner_ready, AV_ESTATE, "%s: call av_planner_configure first", who);
+    AV_REQUIRE(n_traj > 0 && n_wp >= 0, AV_EINVAL, "%s: bad sizes", who);
     AV_REQUIRE(n_ref >= 0 && n_obs >= 0 && (n_ref == 0 || ref_path) && (n_obs == 0 || obstacles), AV_EINVAL,
-               "av_planner_evaluate: ref_path/obstacles pointer missing");
+               "%s: ref_path/obstacles pointer missing", who);
     PlanParams p;
     fill_params(ctx, p);
-    hipLaunchKernelGGL(planner_evaluate_kernel, dim3((n_traj + 63) / 64), dim3(64), 0, as_stream(stream), p, n_traj,
+    hipLaunchKernelGGL(planner_evaluate_kernel<MOVING>, dim3((n_traj + 63) / 64), dim3(64), 0, as_stream(stream), p, n_traj,
                        n_wp, waypoints, ref_path, n_ref, obstacles, n_obs, cost);
     AV_LAUNCH_CHECK();
     return AV_OK;
+}
+
+// av_planner_plan_each and av_planner_plan_moving: the same checks and dispatch, the obstacle rows 3 or 5 doubles wide
+template <int OS>
+static int plan_each_launch(av_ctx* ctx, av_stream_t stream, int n_states, const double* state, const double* ref_path,
+                            const int32_t* n_ref, int rcap, int ref_stride, const double* obstacles, const int32_t* n_obs, int ocap,
+                            double* waypoints, double* cost, int32_t* order, const char* who) {
+    AV_REQUIRE(ctx && state && cost && order, AV_EINVAL, "%s: null argument", who);
+    AV_REQUIRE(ctx->planner_ready, AV_ESTATE, "%s: call av_planner_configure first", who);
+    AV_REQUIRE(n_states > 0, AV_EINVAL, "%s: n_states must be > 0", who);
+    AV_REQUIRE(!ref_path == !n_ref && !obstacles == !n_obs, AV_EINVAL, "%s: a list and its counts go together", who);
+    AV_REQUIRE(ref_stride >= 1, AV_EINVAL, "%s: ref_stride must be >= 1", who);
+    AV_REQUIRE((!ref_path || rcap >= 0) && (!obstacles || ocap >= 0), AV_EINVAL, "%s: negative capacity", who);
+    return plan_dispatch(ctx, as_stream(stream), n_states, state, PlanEachT<OS>{ref_path, n_ref, obstacles, n_obs, rcap, ref_stride, ocap},
+                         ref_path || obstacles, waypoints, cost, order, who);
+}
+
+extern "C" {
+
+int av_planner_evaluate(av_ctx* ctx, av_stream_t stream, int n_traj, int n_wp, const double* waypoints,
+                        const double* ref_path, int n_ref, const double* obstacles, int n_obs, double* cost) {
+    return evaluate_launch<false>(ctx, stream, n_traj, n_wp, waypoints, ref_path, n_ref, obstacles, n_obs, cost, "av_planner_evaluate");
+}
+
+int av_planner_evaluate_moving(av_ctx* ctx, av_stream_t stream, int n_traj, int n_wp, const double* waypoints,
+                               const double* ref_path, int n_ref, const double* obstacles, int n_obs, double* cost) {
+    return evaluate_launch<true>(ctx, stream, n_traj, n_wp, waypoints, ref_path, n_ref, obstacles, n_obs, cost,
+                                 "av_planner_evaluate_moving");
 }
 
 int av_planner_configure(av_ctx* ctx, const av_planner_cfg* cfg) {
@@ -917,14 +971,15 @@ int av_planner_plan(av_ctx* ctx, av_stream_t stream, int n_states, const double*
 int av_planner_plan_each(av_ctx* ctx, av_stream_t stream, int n_states, const double* state, const double* ref_path,
                          const int32_t* n_ref, int rcap, int ref_stride, const double* obstacles, const int32_t* n_obs, int ocap,
                          double* waypoints, double* cost, int32_t* order) {
-    AV_REQUIRE(ctx && state && cost && order, AV_EINVAL, "av_planner_plan_each: null argument");
-    AV_REQUIRE(ctx->planner_ready, AV_ESTATE, "av_planner_plan_each: call av_planner_configure first");
-    AV_REQUIRE(n_states > 0, AV_EINVAL, "av_planner_plan_each: n_states must be > 0");
-    AV_REQUIRE(!ref_path == !n_ref && !obstacles == !n_obs, AV_EINVAL, "av_planner_plan_each: a list and its counts go together");
-    AV_REQUIRE(ref_stride >= 1, AV_EINVAL, "av_planner_plan_each: ref_stride must be >= 1");
-    AV_REQUIRE((!ref_path || rcap >= 0) && (!obstacles || ocap >= 0), AV_EINVAL, "av_planner_plan_each: negative capacity");
-    return plan_dispatch(ctx, as_stream(stream), n_states, state, PlanEach{ref_path, n_ref, obstacles, n_obs, rcap, ref_stride, ocap},
-                         ref_path || obstacles, waypoints, cost, order, "av_planner_plan_each");
+    return plan_each_launch<3>(ctx, stream, n_states, state, ref_path, n_ref, rcap, ref_stride, obstacles, n_obs, ocap, waypoints, cost,
+                               order, "av_planner_plan_each");
+}
+
+int av_planner_plan_moving(av_ctx* ctx, av_stream_t stream, int n_states, const double* state, const double* ref_path,
+                           const int32_t* n_ref, int rcap, int ref_stride, const double* obstacles, const int32_t* n_obs, int ocap,
+                           double* waypoints, double* cost, int32_t* order) {
+    return plan_each_launch<5>(ctx, stream, n_states, state, ref_path, n_ref, rcap, ref_stride, obstacles, n_obs, ocap, waypoints, cost,
+                               order, "av_planner_plan_moving");
 }
 
 }  // extern "C"

@@ -12,7 +12,9 @@ the stream; every kernel is in libavhot.so.
 
 Opt-in (HotLoop(obstacles="tracks"), set_obstacles, set_reference_paths): every frame plans with its own obstacle
 list and every stream with its own reference path (av_planner_plan_each); with "tracks" the lists are the frame's
-confirmed tracks (av_track_obstacles), and the planner then runs behind the tracker.
+confirmed tracks (av_track_obstacles), and the planner then runs behind the tracker.  With "moving_tracks" every such
+obstacle also carries the velocity its track's last centre difference predicts (av_track_obstacles_moving), and each waypoint
+meets it where it is at that waypoint's time (av_planner_plan_moving).
 """
 import ctypes as C
 
@@ -39,7 +41,11 @@ class HotLoop:
         BEV panel draws them, in the planner's frame) and the planner runs per state (av_planner_plan_each) behind the tracker;
         self.obstacles [S, W, tcap, 3] / self.n_obs [S, W].  obstacle_kw overrides av_obstacle_cfg's fields (x_center, x_scale,
         y_far, y_scale, radius: up to 16 per-class radii, default 1.5 for ids 0..5 = car, truck, pedestrian, cyclist, motorcycle,
-        bus and 0 = no obstacle for the rest).  Needs keep_snapshots=True and the stage launches (no fused step, overlap 1)."""
+        bus and 0 = no obstacle for the rest).  Needs keep_snapshots=True and the stage launches (no fused step, overlap 1).
+        obstacles="moving_tracks": the same obstacles, each with the constant velocity of its track in the planner's frame
+        (av_track_obstacles_moving: the last centre difference at obstacle_kw's frame_rate, default 30 frames/s, plus the ego's
+        own speed), planned around where they are at each waypoint's time (av_planner_plan_moving); self.obstacles
+        [S, W, tcap, 5] (x, y, radius, vx, vy).  frame_rate is accepted only in this mode."""
         if not torch.cuda.is_available():
             raise RuntimeError("HotLoop needs a HIP device; this package has no CPU path")
         self.S, self.W, self.h, self.w, self.tcap, self.dcap = n_streams, window, h, w, tcap, dcap
@@ -87,21 +93,27 @@ class HotLoop:
         self.stream = torch.cuda.Stream(device=d)
         self.graph_id = None
         self._graphs = {}
-        if obstacles not in (None, "tracks"):
-            raise ValueError('obstacles is None or "tracks"')
-        if obstacles == "tracks" and (fused_step or overlap != 1 or not keep_snapshots):
-            raise ValueError('obstacles="tracks" needs keep_snapshots=True and the stage launches (fused_step=True and overlap > 1 '
-                             'plan without obstacles)')
-        self._obs_mode = obstacles                # None | "tracks" | "given" (set_obstacles)
+        if obstacles not in (None, "tracks", "moving_tracks"):
+            raise ValueError('obstacles is None, "tracks" or "moving_tracks"')
+        if obstacles is not None and (fused_step or overlap != 1 or not keep_snapshots):
+            raise ValueError('obstacles="%s" needs keep_snapshots=True and the stage launches (fused_step=True and overlap > 1 '
+                             'plan without obstacles)' % obstacles)
+        self._obs_mode = obstacles                # None | "tracks" | "moving_tracks" | "given" (set_obstacles)
         self.obstacles = self.n_obs = self.ref_paths = self.n_ref = None
-        if obstacles == "tracks":
+        if obstacles is not None:
             ok = dict(x_center=320.0, x_scale=0.03, y_far=50.0, y_scale=0.1, radius=[1.5] * 6 + [0.0] * 10)
             ok.update(obstacle_kw or {})
+            if obstacles == "moving_tracks":
+                self.frame_rate = float(ok.pop("frame_rate", 30.0))
+                if not (self.frame_rate > 0.0 and np.isfinite(self.frame_rate)):
+                    raise ValueError("obstacle_kw: frame_rate must be > 0 and finite")
+            elif "frame_rate" in ok:
+                raise ValueError('obstacle_kw: frame_rate belongs to obstacles="moving_tracks"')
             rad = [float(r) for r in ok.pop("radius")]
             if len(rad) > 16:
                 raise ValueError("obstacle_kw: at most 16 per-class radii")
             self.ocfg = nat.ObstacleCfg(radius=(C.c_double * 16)(*(rad + [0.0] * (16 - len(rad)))), **ok)
-            self.obstacles = torch.zeros(S, W, tcap, 3, dtype=f64, device=d)
+            self.obstacles = torch.zeros(S, W, tcap, 5 if obstacles == "moving_tracks" else 3, dtype=f64, device=d)
             self.n_obs = torch.zeros(S, W, dtype=i32, device=d)
             fused_step = False
         can_fuse = window == 1 and tcap == 64 and 7 <= dcap <= 8 and self.tcfg.iou_threshold > 0
@@ -295,17 +307,18 @@ class HotLoop:
         self._graphs, self.graph_id = {}, None
 
     def set_obstacles(self, obstacles, n_obs):
-        """Caller-supplied obstacles for every frame of the window: float64 device tensor [S, W, ocap, 3] (x, y, radius) and int32
-        [S, W] counts, read by every step from now on; None, None: none.  Not together with obstacles="tracks"."""
-        if self._obs_mode == "tracks":
-            raise RuntimeError('set_obstacles: this loop takes its obstacles from the tracker (obstacles="tracks")')
+        """Caller-supplied obstacles for every frame of the window: float64 device tensor [S, W, ocap, 3] (x, y, radius) or, moving,
+        [S, W, ocap, 5] (x, y, radius, vx, vy), and int32 [S, W] counts, read by every step from now on; None, None: none.  Not
+        together with obstacles="tracks" / "moving_tracks"."""
+        if self._obs_mode in ("tracks", "moving_tracks"):
+            raise RuntimeError('set_obstacles: this loop takes its obstacles from the tracker (obstacles="%s")' % self._obs_mode)
         if (obstacles is None) != (n_obs is None):
             raise ValueError("set_obstacles: the list and its counts go together")
         if obstacles is not None:
             self._need_stage_launches("set_obstacles")
             if not (obstacles.dtype == torch.float64 and obstacles.dim() == 4 and tuple(obstacles.shape[:2]) == (self.S, self.W)
-                    and obstacles.shape[3] == 3 and obstacles.is_contiguous() and obstacles.is_cuda):
-                raise ValueError("set_obstacles: obstacles is a contiguous float64 device tensor [S, W, ocap, 3]")
+                    and obstacles.shape[3] in (3, 5) and obstacles.is_contiguous() and obstacles.is_cuda):
+                raise ValueError("set_obstacles: obstacles is a contiguous float64 device tensor [S, W, ocap, 3] or [S, W, ocap, 5]")
             if not (n_obs.dtype == torch.int32 and tuple(n_obs.shape) == (self.S, self.W) and n_obs.is_contiguous() and n_obs.is_cuda):
                 raise ValueError("set_obstacles: n_obs is a contiguous int32 device tensor [S, W]")
         self.obstacles, self.n_obs = obstacles, n_obs
@@ -328,24 +341,30 @@ class HotLoop:
         self._drop_graphs()
 
     def enqueue_obstacles(self, stream=None):
-        """obstacles="tracks": the window's snapshot tables and start states -> self.obstacles / self.n_obs (av_track_obstacles);
-        call where the tracker's and the Kalman filter's outputs are complete (after the join)."""
-        if self._obs_mode != "tracks":
-            raise RuntimeError('enqueue_obstacles needs HotLoop(obstacles="tracks")')
-        nat.check(self.L.av_track_obstacles(self.ctx.handle, stream or self._s, C.byref(self.ocfg), self.S * self.W, self.tcap,
-                                            nat.ptr(self.snap), nat.ptr(self.snap_n), nat.ptr(self.plan_state), self.tcap,
-                                            nat.ptr(self.obstacles), nat.ptr(self.n_obs)))
+        """obstacles="tracks" / "moving_tracks": the window's snapshot tables and start states -> self.obstacles / self.n_obs
+        (av_track_obstacles / av_track_obstacles_moving); call where the tracker's and the Kalman filter's outputs are complete
+        (after the join)."""
+        if self._obs_mode not in ("tracks", "moving_tracks"):
+            raise RuntimeError('enqueue_obstacles needs HotLoop(obstacles="tracks") or "moving_tracks"')
+        tail = (self.S * self.W, self.tcap, nat.ptr(self.snap), nat.ptr(self.snap_n), nat.ptr(self.plan_state), self.tcap,
+                nat.ptr(self.obstacles), nat.ptr(self.n_obs))
+        if self._obs_mode == "moving_tracks":
+            nat.check(self.L.av_track_obstacles_moving(self.ctx.handle, stream or self._s, C.byref(self.ocfg), self.frame_rate, *tail))
+        else:
+            nat.check(self.L.av_track_obstacles(self.ctx.handle, stream or self._s, C.byref(self.ocfg), *tail))
 
     def enqueue_plan_each(self, stream=None):
-        """The planner with per-state inputs (av_planner_plan_each): frame (s, f) reads obstacle list (s, f) and stream s's
-        reference path."""
+        """The planner with per-state inputs (av_planner_plan_each; av_planner_plan_moving where the obstacle rows carry a
+        velocity): frame (s, f) reads obstacle list (s, f) and stream s's reference path."""
         self._serial_only("enqueue_plan_each")
         rcap = 0 if self.ref_paths is None else int(self.ref_paths.shape[1])
         ocap = 0 if self.obstacles is None else int(self.obstacles.shape[2])
-        nat.check(self.L.av_planner_plan_each(self.ctx.handle, stream or self._s, self.S * self.W, nat.ptr(self.plan_state),
-                                              nat.ptr(self.ref_paths), nat.ptr(self.n_ref), rcap, self.W,
-                                              nat.ptr(self.obstacles), nat.ptr(self.n_obs), ocap,
-                                              nat.ptr(self.wp), nat.ptr(self.cost), nat.ptr(self.order)))
+        moving = self.obstacles is not None and int(self.obstacles.shape[3]) == 5
+        plan = self.L.av_planner_plan_moving if moving else self.L.av_planner_plan_each
+        nat.check(plan(self.ctx.handle, stream or self._s, self.S * self.W, nat.ptr(self.plan_state),
+                       nat.ptr(self.ref_paths), nat.ptr(self.n_ref), rcap, self.W,
+                       nat.ptr(self.obstacles), nat.ptr(self.n_obs), ocap,
+                       nat.ptr(self.wp), nat.ptr(self.cost), nat.ptr(self.order)))
 
     def set_wire(self, wire, stream0=0, frame0=0):
         """Fused step only: `wire` (uint8 device tensor [S, av_wire_table_bytes(tcap)], or None) receives every stream's
@@ -469,7 +488,7 @@ class HotLoop:
             # per-state planner inputs: fork{detect; track} || {kf}; join; [tracks -> obstacles]; plan.  With obstacles from the
             # tracker the planner consumes the tables, so it moves behind the join
             nat.check(L.av_join(h, s))
-            if self._obs_mode == "tracks":
+            if self._obs_mode in ("tracks", "moving_tracks"):
                 self.enqueue_obstacles()
             self.enqueue_plan_each()
             return

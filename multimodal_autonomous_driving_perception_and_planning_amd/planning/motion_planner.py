@@ -146,10 +146,18 @@ class MotionPlanner:
 
     @staticmethod
     def _obs_arrays(dev, obstacles):
+        """-> (device list or None, count, moving).  An obstacle is (x, y, radius) or, moving, (x, y, radius, vx, vy) in the
+        planner's frame (m, m/s); one 5-tuple makes the whole list moving, the 3-tuples padded with zero velocities."""
         if not obstacles:
-            return None, 0
-        o = np.asarray([tuple(x) for x in obstacles], np.float64).reshape(-1, 3)
-        return dev.upload(o, np.float64), len(o)
+            return None, 0, False
+        rows = [tuple(x) for x in obstacles]
+        if any(len(r) not in (3, 5) for r in rows):
+            raise ValueError("an obstacle is (x, y, radius) or (x, y, radius, vx, vy)")
+        moving = any(len(r) == 5 for r in rows)
+        if moving:
+            rows = [r if len(r) == 5 else r + (0.0, 0.0) for r in rows]
+        o = np.asarray(rows, np.float64).reshape(-1, 5 if moving else 3)
+        return dev.upload(o, np.float64), len(o), moving
 
     # ---- reference surface ----------------------------------------------------------------------------
     def set_reference_path(self, waypoints: List[Tuple[float, float]]):
@@ -189,24 +197,32 @@ class MotionPlanner:
                            np.float64)
         wp = d.upload(arr.reshape(1, -1, 6), np.float64)
         ref, nr = self._ref_arrays()
-        obs, no = self._obs_arrays(d, obstacles)
+        obs, no, moving = self._obs_arrays(d, obstacles)
         out = d.empty(1, torch.float64)
-        nat.check(d.lib.av_planner_evaluate(d.ctx.handle, d.stream, 1, len(arr), nat.ptr(wp), nat.ptr(ref), nr,
-                                            nat.ptr(obs), no, nat.ptr(out)))
+        evaluate = d.lib.av_planner_evaluate_moving if moving else d.lib.av_planner_evaluate
+        nat.check(evaluate(d.ctx.handle, d.stream, 1, len(arr), nat.ptr(wp), nat.ptr(ref), nr, nat.ptr(obs), no, nat.ptr(out)))
         trajectory.cost = float(out.item())
         return trajectory.cost
 
     def plan(self, current_state: Tuple[float, float, float, float],
              obstacles: Optional[List[Tuple[float, float, float]]] = None) -> Tuple[Trajectory, List[Trajectory]]:
+        """obstacles: (x, y, radius) as in the reference, or (x, y, radius, vx, vy): a disc moving at a constant velocity, which
+        every waypoint meets where it is at that waypoint's timestamp."""
         self._configure()
         d = self._dev
         io = self._io
         io.h["st"][0] = np.asarray(current_state, np.float64).reshape(4)
         io.upload(upto="st")
         ref, nr = self._ref_arrays()
-        obs, no = self._obs_arrays(d, obstacles)
-        nat.check(d.lib.av_planner_plan(d.ctx.handle, d.stream, 1, io.ptr("st"), nat.ptr(ref), nr, nat.ptr(obs), no,
-                                        io.ptr("wp"), io.ptr("cost"), io.ptr("order")))
+        obs, no, moving = self._obs_arrays(d, obstacles)
+        if moving:
+            # moving obstacles are a per-state input (av_planner_plan_moving): one state, its list and the path with a count each
+            n_obs, n_ref = d.upload([no], np.int32), (d.upload([nr], np.int32) if ref is not None else None)
+            nat.check(d.lib.av_planner_plan_moving(d.ctx.handle, d.stream, 1, io.ptr("st"), nat.ptr(ref), nat.ptr(n_ref), nr, 1,
+                                                   nat.ptr(obs), nat.ptr(n_obs), no, io.ptr("wp"), io.ptr("cost"), io.ptr("order")))
+        else:
+            nat.check(d.lib.av_planner_plan(d.ctx.handle, d.stream, 1, io.ptr("st"), nat.ptr(ref), nr, nat.ptr(obs), no,
+                                            io.ptr("wp"), io.ptr("cost"), io.ptr("order")))
         io.download(first="wp")
         wph = io.h["wp"][0].copy()                 # the staging buffer is reused by the next call
         costh, orderh = io.h["cost"][0].tolist(), io.h["order"][0].tolist()

@@ -1,0 +1,415 @@
+"""Moving obstacles: av_planner_plan_moving, av_planner_evaluate_moving, av_track_obstacles_moving and
+HotLoop(obstacles="moving_tracks").
+
+(1) with zero velocities av_planner_plan_moving is av_planner_plan_each on the 3-column lists, bit for bit, on every kernel of
+    the dispatch, with and without waypoints;
+(2) and with velocities it is MovingPlannerRef (tests/moving_ref.py) at the project's tolerances (tests/test_gpu_plan_each.py:
+    cost rtol 1e-12 + atol 1e-12 + the obstacle term's Lipschitz allowance, waypoints rtol 1e-12 / atol 1e-11, ranking by
+    tests/_util.order_mismatch + the stable sort of the device's own costs).  The allowance is computed with every obstacle at
+    its place for the waypoint's time; the obstacle's own position is the same two roundings on both sides, so the formula is
+    the static one.  The oracle's margin to the jumps at dist = 2r, 4r is asserted first (tests/test_moving_host.py proves it
+    on the CPU for every input used here);
+(3) av_planner_evaluate_moving on the device's own waypoints; (4) av_track_obstacles_moving against the restatement and against
+    av_track_obstacles' own bytes; (5) the loop, stage by stage; (6) the classes and what they refuse; (7) argument checks.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from tests import moving_cases as M
+from tests import test_gpu_plan_each as E
+from tests.moving_ref import MovingPlannerRef, margin_and_allowance, track_obstacles_moving
+from tests.test_gpu_planner import POOL, U, configure
+
+gpu = pytest.mark.gpu
+OCAP, RCAP = E.OCAP, E.RCAP
+
+
+def test_shapes_reach_every_kernel_that_takes_a_list():
+    reached = {E.kernel_path(n, 3 * ns, S, True) for n, ns, S in M.SHAPES}
+    assert reached == E.REQUIRED - {"wave"}, reached
+    assert [E.kernel_path(n, 3 * ns, S, True) for n, ns, S in M.SHAPES] == [
+        "block<1,8>", "block<1,4>", "block<1,2>", "block<2,4>", "block<4,4>", "block<8,4>", "wave+extra", "wave+extra", "block<1,8>"]
+
+
+@pytest.fixture(scope="module")
+def env():
+    torch = pytest.importorskip("torch")
+    if not torch.cuda.is_available():
+        pytest.fail("GPU test selected but no HIP device is visible")
+    from multimodal_autonomous_driving_perception_and_planning_amd import _native as nat
+    return torch, nat, nat.lib(), nat.Context(0)
+
+
+def _packed5(S, shift=0, zero_velocity=False):
+    """Per-state obstacle tensors of the assignment list (f + shift) % 5; rows past each count are NaN."""
+    obs = np.full((S, OCAP, 5), np.nan)
+    n_obs = np.zeros(S, np.int32)
+    for f in range(S):
+        l = M.MLISTS[(f + shift) % 5]
+        obs[f, :len(l)], n_obs[f] = l, len(l)
+        if zero_velocity:
+            obs[f, :len(l), 3:] = 0.0
+    return obs, n_obs
+
+
+def run_moving(env, n, ns, states_t, ref_stride, wp=True, shift=0, zero_velocity=False):
+    torch, nat, L, ctx = env
+    S, C_ = states_t.shape[0], 3 * ns
+    _, _, ref, n_ref = E._packed(S, ref_stride)                   # the reference paths of the existing test: path (f // ref_stride) % 4
+    obs, n_obs = _packed5(S, shift, zero_velocity)
+    obs, n_obs, ref, n_ref = (E._dev(env, a, dt) for a, dt in zip((obs, n_obs, ref, n_ref), (torch.float64, torch.int32) * 2))
+    w, cost, order = E._outputs(env, S, C_, n, wp)
+    nat.check(L.av_planner_plan_moving(ctx.handle, None, S, nat.ptr(states_t), nat.ptr(ref), nat.ptr(n_ref), RCAP, ref_stride,
+                                       nat.ptr(obs), nat.ptr(n_obs), OCAP, nat.ptr(w), nat.ptr(cost), nat.ptr(order)))
+    torch.cuda.synchronize()
+    if wp:
+        assert torch.isnan(w[-8:]).all()                          # the eight guard doubles behind the waypoints
+        w = w[:-8].view(S, C_, n, 6)
+    return w, cost, order
+
+
+_IDS = ["n%d-ns%d-S%d" % c for c in M.SHAPES]
+
+
+@gpu
+@pytest.mark.parametrize("n,ns,S", M.SHAPES, ids=_IDS)
+def test_zero_velocity_is_the_static_planner_bit_for_bit(env, n, ns, S):
+    torch = env[0]
+    print("n=%d C=%d n_states=%d -> %s" % (n, 3 * ns, S, E.kernel_path(n, 3 * ns, S, True)))
+    configure(env, n, ns)
+    states_t = E._dev(env, POOL[np.arange(S) % U], torch.float64)
+    for rs in (1, 4):
+        sw, sc, so = E.run_each(env, n, ns, states_t, rs)
+        mw, mc, mo = run_moving(env, n, ns, states_t, rs, zero_velocity=True)
+        assert torch.equal(E._bits(mc), E._bits(sc)) and torch.equal(mo, so), "ref_stride %d" % rs
+        assert torch.equal(E._bits(mw), E._bits(sw)), "ref_stride %d" % rs
+        del sw, mw
+        _, mc2, mo2 = run_moving(env, n, ns, states_t, rs, wp=False, zero_velocity=True)
+        assert torch.equal(E._bits(mc2), E._bits(sc)) and torch.equal(mo2, so), "ref_stride %d, no waypoints" % rs
+
+
+# batches of fewer than five states never reach MFULL with the assignment f % 5: they are compared a second time with the
+# assignment (f + 3) % 5 (state 0: MFULL, state 1: the far mover, state 2: none)
+_ORACLE_RUNS = [(c, 0) for c in M.SHAPES] + [(c, 3) for c in M.SHAPES if c[2] < 5]
+
+
+@gpu
+@pytest.mark.parametrize("shape,shift", _ORACLE_RUNS, ids=["n%d-ns%d-S%d-shift%d" % (c + (s,)) for c, s in _ORACLE_RUNS])
+def test_moving_matches_oracle(env, shape, shift):
+    torch = env[0]
+    n, ns, S = shape
+    configure(env, n, ns)
+    states = POOL[np.arange(S) % U]
+    rs = 4
+    w, cost, order = run_moving(env, n, ns, E._dev(env, states, torch.float64), rs, shift=shift)
+    ok = [f for f in range(S) if (f + shift) % 5 in (0, 3, 4)]         # (the OBS lists sit exactly on 2r / 4r: test 1 covers them)
+    # at most 40 states, spread over the batch: up to 13 of every list (2 where a state has 192 candidates: the oracle's time)
+    per = max(2, min(13, 273 // (3 * ns)))
+    pick = {ok[-1]}
+    for li in (0, 3, 4):
+        c = [f for f in ok if (f + shift) % 5 == li]
+        pick.update(c[::max(1, -(-len(c) // per))][:per])
+    pick = sorted(pick)
+    assert len(pick) <= 40 and {(f + shift) % 5 for f in pick} == {(f + shift) % 5 for f in range(S)} & {0, 3, 4}
+    assert S < 5 or {f % 5 for f in pick} == {0, 3, 4}
+    idx = torch.as_tensor(pick, device=w.device)
+    cost, order, w = cost[idx].cpu().numpy(), order[idx].cpu().numpy(), w[idx].cpu().numpy()
+    worst = np.inf
+    for k, f in enumerate(pick):
+        li, pi = (f + shift) % 5, (f // rs) % 4
+        want = M.planner(n, ns, E.PATHS[pi]).plan(states[f], M.MLISTS[li])
+        margin, allow, _, _ = margin_and_allowance(want["wp"], M.MLISTS[li])
+        where = "state %d list %d path %d" % (f, li, pi)
+        if li == 3:
+            worst = min(worst, margin)
+            assert margin >= M.MARGIN, "%s: the oracle is %g m from a branch boundary" % (where, margin)
+        err = np.abs(cost[k] - want["cost"]).max()
+        print("%s: cost off by %.3g at most (allowance %.3g .. %.3g)" % (where, err, allow.min(), allow.max()))
+        E.check_with_obstacles(cost[k], order[k], w[k], want, allow, where)
+    print("%d states compared, boundary margin of the MFULL states %.3g m" % (len(pick), worst))
+
+
+@gpu
+def test_evaluate_moving(env):
+    torch, nat, L, ctx = env
+    n, ns, S = 51, 7, 5
+    configure(env, n, ns)
+    states = POOL[:S]
+    w, _, _ = run_moving(env, n, ns, E._dev(env, states, torch.float64), 1)
+    wps = w.reshape(S * 3 * ns, n, 6).contiguous()
+    n_traj = wps.shape[0]
+    mfull = E._dev(env, M.MFULL, torch.float64)
+    out = torch.full((n_traj + 8,), float("nan"), dtype=torch.float64, device=wps.device)
+    call = lambda fn, obs, n_wp=n: nat.check(fn(ctx.handle, None, n_traj, n_wp, nat.ptr(wps), None, 0, nat.ptr(obs), 64, nat.ptr(out)))
+    call(L.av_planner_evaluate_moving, mfull)
+    torch.cuda.synchronize()
+    got, wh = out.cpu().numpy(), wps.cpu().numpy()
+    assert np.isnan(got[n_traj:]).all()
+    p = MovingPlannerRef()
+    want = np.array([p.cost(wh[j], M.MFULL) for j in range(n_traj)])
+    margin, allow, hard, soft = margin_and_allowance(wh, M.MFULL)
+    assert margin >= M.MARGIN and hard >= 1 and soft >= 1, (margin, hard, soft)
+    tol = 1e-12 + 1e-12 * np.abs(want) + allow
+    print("evaluate_moving: off by %.3g at most (tolerance %.3g at least)" % (np.abs(got[:n_traj] - want).max(), tol.min()))
+    assert np.all(np.abs(got[:n_traj] - want) <= tol)
+    static = np.array([p.cost(wh[j], np.concatenate([M.FULL, np.zeros((64, 2))], axis=1)) for j in range(n_traj)])
+    assert (want != static).any()
+    # zero velocities: av_planner_evaluate on the 3-column list, byte for byte
+    zero = M.MFULL.copy()
+    zero[:, 3:] = 0.0
+    call(L.av_planner_evaluate_moving, E._dev(env, zero, torch.float64))
+    torch.cuda.synchronize()
+    got0 = out.clone()
+    out.fill_(float("nan"))
+    call(L.av_planner_evaluate, E._dev(env, M.FULL, torch.float64))
+    torch.cuda.synchronize()
+    assert torch.equal(E._bits(got0[:n_traj]), E._bits(out[:n_traj]))
+    # no waypoints: inf (motion_planner.py:218)
+    call(L.av_planner_evaluate_moving, mfull, 0)
+    torch.cuda.synchronize()
+    assert torch.isinf(out[:n_traj]).all() and (out[:n_traj] > 0).all() and torch.isnan(out[n_traj:]).all()
+
+
+# ---- (4) av_track_obstacles_moving ---------------------------------------------------------------------------------------------
+
+@gpu
+@pytest.mark.parametrize("tcap,extra", [(64, 0), (64, 3), (128, 0), (128, 3)])
+def test_track_obstacles_moving_matches_restatement(env, tcap, extra):
+    torch, nat, L, ctx = env
+    S, ocap = 37, tcap + extra
+    rows, n = E._tables(nat, S, tcap)
+    rng = np.random.default_rng(200 + tcap)
+    rows["vx"], rows["vy"] = rng.integers(-80, 81, rows.shape) / 2.0, rng.integers(-80, 81, rows.shape) / 2.0
+    rows["hist_len"] = rng.choice([0, 1, 2, 7], rows.shape)
+    rng = np.random.default_rng(5)
+    ps = np.stack([rng.uniform(-200, 200, S), rng.uniform(-200, 200, S), rng.uniform(-np.pi, np.pi, S), rng.uniform(0, 20, S)], axis=1)
+    ps[2:12, 2] = [0.0, np.pi / 2, -np.pi / 2, np.pi, 0.05, 0.0, 0.0, np.pi / 2, -np.pi / 2, np.pi]
+    ps[2:6, :2] = 0.0
+    cfg = nat.ObstacleCfg(E.OBS_CFG["x_center"], E.OBS_CFG["x_scale"], E.OBS_CFG["y_far"], E.OBS_CFG["y_scale"],
+                          (C.c_double * 16)(*E.RADIUS))
+    dev = torch.device("cuda", 0)
+    snap = torch.as_tensor(rows.view(np.uint8).reshape(S, tcap, 64)).to(dev)
+    out5 = torch.full((S * ocap * 5 + 16,), float("nan"), dtype=torch.float64, device=dev)
+    out3 = torch.full((S * ocap * 3 + 16,), float("nan"), dtype=torch.float64, device=dev)
+    cnt5, cnt3 = (torch.full((S + 8,), -7, dtype=torch.int32, device=dev) for _ in range(2))
+    n_t, ps_t = E._dev(env, n, torch.int32), E._dev(env, ps, torch.float64)
+    tail = lambda o, out, cnt: (S, tcap, nat.ptr(snap), nat.ptr(n_t), nat.ptr(ps_t), o, nat.ptr(out), nat.ptr(cnt))
+    nat.check(L.av_track_obstacles(ctx.handle, None, C.byref(cfg), *tail(ocap, out3, cnt3)))
+    nat.check(L.av_track_obstacles_moving(ctx.handle, None, C.byref(cfg), 30.0, *tail(ocap, out5, cnt5)))
+    torch.cuda.synchronize()
+    got, got_n, st, st_n = out5.cpu().numpy(), cnt5.cpu().numpy(), out3.cpu().numpy(), cnt3.cpu().numpy()
+    assert np.isnan(got[S * ocap * 5:]).all() and (got_n[S:] == -7).all()
+    assert np.array_equal(got_n, st_n)
+    got, st = got[:S * ocap * 5].reshape(S, ocap, 5), st[:S * ocap * 3].reshape(S, ocap, 3)
+    radius = np.asarray(E.RADIUS)
+    total = ego_only = 0
+    for f in range(S):
+        want = track_obstacles_moving(rows[f], n[f], ps[f], E.OBS_CFG, 30.0)
+        m = len(want)
+        assert got_n[f] == m, "state %d" % f
+        assert np.array_equal(got[f, :m, :3].view(np.int64), st[f, :m].view(np.int64)), "state %d" % f
+        assert np.isnan(got[f, m:]).all(), "state %d: a row past the count was written" % f
+        np.testing.assert_allclose(got[f, :m, 3:], want[:, 3:], rtol=1e-12, atol=1e-11, err_msg="state %d" % f)
+        live = rows[f][:n[f]]
+        cls = live["cls"]
+        kept = ((live["flags"] & 1) == 1) & (cls >= 0) & (cls < 16) & (radius[np.clip(cls, 0, 15)] > 0)
+        assert int(kept.sum()) == m
+        young = live["hist_len"][kept] < 2
+        h, v0 = ps[f, 2], ps[f, 3]
+        ego = np.array([v0 * np.cos(h) + 0.0 * np.cos(h + np.pi / 2), v0 * np.sin(h) + 0.0 * np.sin(h + np.pi / 2)])
+        assert np.array_equal(want[young, 3:], np.broadcast_to(ego, (int(young.sum()), 2)))
+        np.testing.assert_allclose(got[f, :m, 3:][young], want[young, 3:], rtol=1e-12, atol=1e-11, err_msg="state %d" % f)
+        total, ego_only = total + m, ego_only + int(young.sum())
+    assert got_n[2] == tcap and got_n[0] == 0 and got_n[1] == 0 and total > 5 * tcap and 0 < ego_only < total
+    # refusals: ocap < tcap, and a frame rate that is not a positive finite number
+    assert L.av_track_obstacles_moving(ctx.handle, None, C.byref(cfg), 30.0, *tail(tcap - 1, out5, cnt5)) == -1
+    for rate in (0.0, -30.0, float("nan"), float("inf")):
+        assert L.av_track_obstacles_moving(ctx.handle, None, C.byref(cfg), rate, *tail(ocap, out5, cnt5)) == -1
+    torch.cuda.synchronize()
+    assert np.array_equal(out5.cpu().numpy().view(np.int64), np.concatenate([got.reshape(-1), [np.nan] * 16]).view(np.int64))
+
+
+# ---- (5) the loop ----------------------------------------------------------------------------------------------------------------
+
+_PLANS = {}
+
+
+def _oracle_plan(ps, obstacles):
+    """MovingPlannerRef for [m, 5] obstacles, PlannerRef (the static discs) for [m, 3]; computed once per input."""
+    from oracle.planner_ref import PlannerRef
+    key = (ps.tobytes(), obstacles.shape[1], obstacles.tobytes())
+    if key not in _PLANS:
+        _PLANS[key] = (MovingPlannerRef().plan(ps, obstacles) if obstacles.shape[1] == 5
+                       else PlannerRef().plan(ps, [tuple(o) for o in obstacles]))
+    return _PLANS[key]
+
+
+def _run_moving_tracks(env, W, graph):
+    from multimodal_autonomous_driving_perception_and_planning_amd.pipeline import HotLoop
+    from oracle.harness_ref import ego_motion
+    loop = HotLoop(n_streams=3, window=W, obstacles="moving_tracks", obstacle_kw=dict(radius=E.LOOP_RADIUS, frame_rate=M.FRAME_RATE))
+    assert loop.fused_step is False and tuple(loop.obstacles.shape) == (3, W, loop.tcap, 5)
+    loop.reset(frame_offsets=M.OFFSETS)
+    z = np.stack([ego_motion(M.FRAMES, seed=s) for s in range(3)])
+    steps = []
+    for k in range(M.FRAMES // W):
+        loop.load_measurements(z[:, k * W:(k + 1) * W])
+        loop.step(graph=graph, sync=True)
+        rows, n = loop.snapshots()
+        steps.append((loop.results(), rows.copy(), n.copy(), loop.plan_state.cpu().numpy()))
+    return loop, z, steps
+
+
+@gpu
+@pytest.mark.parametrize("W", [1, 4])
+def test_loop_plans_around_its_own_moving_tracks(env, W):
+    torch = env[0]
+    loop, z, steps = _run_moving_tracks(env, W, graph=False)
+    changed, counts, worst, moving_rows = [0, 0, 0], [], np.inf, 0
+    for k, (r, rows, n, ps) in enumerate(steps):
+        assert r["obstacles"].shape == (3, W, loop.tcap, 5)
+        for s in range(3):
+            for f in range(W):
+                where = "W=%d frame %d stream %d" % (W, k * W + f, s)
+                want_obs = track_obstacles_moving(rows[s, f], n[s, f], ps[s, f], M.LOOP_CFG, M.FRAME_RATE)
+                m = int(r["n_obs"][s, f])
+                assert m == len(want_obs), where
+                got_obs = r["obstacles"][s, f, :m]
+                assert np.array_equal(got_obs[:, 2], want_obs[:, 2]), where
+                np.testing.assert_allclose(got_obs[:, [0, 1, 3, 4]], want_obs[:, [0, 1, 3, 4]], rtol=1e-12, atol=1e-11, err_msg=where)
+                counts.append(m)
+                live = rows[s, f][:n[s, f]]
+                moving_rows += int((((live["flags"] & 1) == 1) & (live["hist_len"] >= 2) & ((live["vx"] != 0) | (live["vy"] != 0))).sum())
+                want = _oracle_plan(ps[s, f], got_obs)
+                margin, allow, _, _ = margin_and_allowance(want["wp"], got_obs)
+                worst = min(worst, margin)
+                assert margin >= M.MARGIN, "%s: the oracle is %g m from a branch boundary" % (where, margin)
+                E.check_with_obstacles(r["cost"][s, f], r["order"][s, f], r["wp"][s, f], want, allow, where)
+                static = _oracle_plan(ps[s, f], np.ascontiguousarray(got_obs[:, :3]))
+                changed[s] += int(want["order"][0] != static["order"][0])
+    print("W=%d: best candidate differs from the static plan's in %r of %d frames, obstacles per frame %d .. %d, %d rows with a "
+          "velocity in the image, boundary margin %.3g m" % (W, changed, M.FRAMES, min(counts), max(counts), moving_rows, worst))
+    assert all(c >= 1 for c in changed), changed
+    assert min(counts) == 0 and max(counts) > 0 and moving_rows > 0
+
+    # the captured graph replays the same steps bit for bit
+    loop_g, _, steps_g = _run_moving_tracks(env, W, graph=True)
+    for (r, _, _, ps), (rg, _, _, psg) in zip(steps, steps_g):
+        assert np.array_equal(ps.view(np.int64), psg.view(np.int64)) and np.array_equal(r["n_obs"], rg["n_obs"])
+        for key in ("cost", "order", "wp"):
+            assert np.array_equal(r[key].view(np.uint8), rg[key].view(np.uint8)), key
+        live = np.arange(loop.tcap)[None, None, :] < r["n_obs"][:, :, None]
+        assert np.array_equal(r["obstacles"][live].view(np.int64), rg["obstacles"][live].view(np.int64))
+
+    # caller-supplied moving obstacles: the finished run's [S, W, tcap, 5] tensors reproduce its last window's costs
+    from multimodal_autonomous_driving_perception_and_planning_amd.pipeline import HotLoop
+    plain = HotLoop(n_streams=3, window=W, fused_step=False)
+    plain.reset(frame_offsets=M.OFFSETS)
+    last = M.FRAMES // W - 1
+    for k in range(last + 1):
+        if k == last:
+            plain.set_obstacles(loop.obstacles, loop.n_obs)
+        plain.load_measurements(z[:, k * W:(k + 1) * W])
+        plain.step(sync=True)
+    rp = plain.results()
+    for key in ("cost", "order", "wp"):
+        assert np.array_equal(rp[key].view(np.uint8), steps[-1][0][key].view(np.uint8)), key
+    assert rp["obstacles"].shape == (3, W, loop.tcap, 5)
+    plain.set_obstacles(None, None)
+    assert "obstacles" not in plain.results()
+
+
+# ---- (6) classes and refusals ----------------------------------------------------------------------------------------------------
+
+@gpu
+def test_motion_planner_takes_moving_obstacles(env):
+    torch, nat, L, ctx = env
+    from multimodal_autonomous_driving_perception_and_planning_amd.planning.motion_planner import MotionPlanner
+    state, mover = (0.0, 0.0, 0.0, 10.0), [(12.0, 0.0, 1.5, 10.0, 0.0)]
+    p = MotionPlanner()
+    best, cands = p.plan(state, mover)
+    configure(env, 51, 7)
+    st = E._dev(env, [state], torch.float64)
+    obs, n_obs = E._dev(env, [mover], torch.float64), E._dev(env, [1], torch.int32)
+    w, cost, order = E._outputs(env, 1, 21, 51, True)
+    nat.check(L.av_planner_plan_moving(ctx.handle, None, 1, nat.ptr(st), None, None, 0, 1, nat.ptr(obs), nat.ptr(n_obs), 1, nat.ptr(w),
+                                       nat.ptr(cost), nat.ptr(order)))
+    torch.cuda.synchronize()
+    cost, order, w = cost.cpu().numpy()[0], order.cpu().numpy()[0], w[:-8].view(21, 51, 6).cpu().numpy()
+    assert np.array_equal(np.array([t.cost for t in cands]).view(np.int64), cost[order].view(np.int64))
+    assert np.array_equal(np.stack([t._arr for t in cands]).view(np.int64), w[order].view(np.int64))
+    assert best is cands[0]
+    # the same disc frozen at its first place costs otherwise; a mixed list is padded with zero velocities
+    _, frozen = p.plan(state, [(12.0, 0.0, 1.5)])
+    assert sorted(t.cost for t in frozen) != sorted(t.cost for t in cands)
+    _, mixed = p.plan(state, [(12.0, 0.0, 1.5), (5000.0, 5000.0, 1.0, 1.0, 1.0)])
+    assert [t.cost for t in mixed] == [t.cost for t in frozen]
+    # evaluate_trajectory_cost: the same call through the C entry point
+    keep = [t for t in cands if t.trajectory_type == "lane_keep"][0]         # (drives through the frozen disc, behind the moving one)
+    got = p.evaluate_trajectory_cost(keep, mover)
+    out = torch.full((1,), float("nan"), dtype=torch.float64, device=st.device)
+    arr = E._dev(env, keep._arr, torch.float64)
+    nat.check(L.av_planner_evaluate_moving(ctx.handle, None, 1, 51, nat.ptr(arr), None, 0, nat.ptr(obs), 1, nat.ptr(out)))
+    torch.cuda.synchronize()
+    assert got == float(out.item()) and got != p.evaluate_trajectory_cost(keep, [(12.0, 0.0, 1.5)])
+    for bad in ([(12.0, 0.0, 1.5, 10.0)], [(12.0, 0.0)], [(12.0, 0.0, 1.5), (1.0, 2.0, 3.0, 4.0, 5.0, 6.0)]):
+        with pytest.raises(ValueError):
+            p.plan(state, bad)
+        with pytest.raises(ValueError):
+            p.evaluate_trajectory_cost(cands[0], bad)
+
+
+@gpu
+def test_loop_refusals(env):
+    torch = env[0]
+    from multimodal_autonomous_driving_perception_and_planning_amd.pipeline import HotLoop
+    for kw in (dict(fused_step=True), dict(overlap=2), dict(keep_snapshots=False)):
+        with pytest.raises(ValueError):
+            HotLoop(n_streams=2, window=1, obstacles="moving_tracks", **kw)
+    with pytest.raises(ValueError):
+        HotLoop(n_streams=2, window=1, obstacles="tracks", obstacle_kw=dict(frame_rate=30.0))
+    for rate in (0.0, -1.0, float("nan")):
+        with pytest.raises(ValueError):
+            HotLoop(n_streams=2, window=1, obstacles="moving_tracks", obstacle_kw=dict(frame_rate=rate))
+    with pytest.raises(ValueError):
+        HotLoop(n_streams=2, obstacles="boxes")
+    moving = HotLoop(n_streams=2, window=1, obstacles="moving_tracks")
+    assert moving.fused_step is False and moving.frame_rate == 30.0
+    with pytest.raises(RuntimeError):
+        moving.set_obstacles(None, None)
+    dev = torch.device("cuda", 0)
+    plain = HotLoop(n_streams=2, window=1, fused_step=False)
+    with pytest.raises(ValueError):
+        plain.set_obstacles(torch.zeros(2, 1, 4, 4, dtype=torch.float64, device=dev), torch.zeros(2, 1, dtype=torch.int32, device=dev))
+    with pytest.raises(RuntimeError):
+        HotLoop().set_obstacles(torch.zeros(1, 1, 4, 5, dtype=torch.float64, device=dev), torch.zeros(1, 1, dtype=torch.int32, device=dev))
+
+
+# ---- (7) argument checks -----------------------------------------------------------------------------------------------------------
+
+@gpu
+def test_argument_checks(env):
+    torch, nat, L, ctx = env
+    configure(env, 51, 7)
+    st = E._dev(env, POOL[:2], torch.float64)
+    w, cost, order = E._outputs(env, 2, 21, 51, False)
+    _, _, ref, n_ref = E._packed(2, 1)
+    obs, n_obs = _packed5(2)
+    obs, n_obs, ref, n_ref = (E._dev(env, a, dt) for a, dt in zip((obs, n_obs, ref, n_ref), (torch.float64, torch.int32) * 2))
+    call = lambda *a: L.av_planner_plan_moving(ctx.handle, None, *a)
+    P = nat.ptr
+    assert call(2, P(st), P(ref), P(n_ref), RCAP, 1, P(obs), P(n_obs), OCAP, None, P(cost), P(order)) == 0
+    assert call(0, P(st), P(ref), P(n_ref), RCAP, 1, P(obs), P(n_obs), OCAP, None, P(cost), P(order)) == -1
+    assert call(2, P(st), P(ref), None, RCAP, 1, P(obs), P(n_obs), OCAP, None, P(cost), P(order)) == -1
+    assert call(2, P(st), None, P(n_ref), RCAP, 1, P(obs), P(n_obs), OCAP, None, P(cost), P(order)) == -1
+    assert call(2, P(st), P(ref), P(n_ref), RCAP, 1, P(obs), None, OCAP, None, P(cost), P(order)) == -1
+    assert call(2, P(st), P(ref), P(n_ref), RCAP, 1, None, P(n_obs), OCAP, None, P(cost), P(order)) == -1
+    assert call(2, P(st), P(ref), P(n_ref), RCAP, 0, P(obs), P(n_obs), OCAP, None, P(cost), P(order)) == -1
+    assert call(2, P(st), None, None, 0, 1, None, None, 0, None, None, P(order)) == -1
+    torch.cuda.synchronize()
+    fresh = nat.Context(0)                                  # planner not configured
+    assert L.av_planner_plan_moving(fresh.handle, None, 2, P(st), None, None, 0, 1, None, None, 0, None, P(cost), P(order)) == -4
+    assert L.av_planner_evaluate_moving(fresh.handle, None, 1, 0, None, None, 0, None, 0, P(cost)) == -4
+    fresh.close()

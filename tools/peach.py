@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
-"""Planner with per-state inputs: what the lookup costs.
+"""Planner with per-state inputs: what the lookup costs and what motion costs (section 7e).
 
   planner   av_planner_plan without extras | av_planner_plan_each with null lists | av_planner_plan with 16 shared obstacles |
-            av_planner_plan_each with the same 16 per state, at 64 and 16 384 start states, default planner
-  step      HotLoop(64 streams, fused_step=False) plain and with obstacles="tracks", window 1 and 256
+            av_planner_plan_each with the same 16 per state | av_planner_plan_moving with the same 16 and a velocity each,
+            at 64 and 16 384 start states, default planner
+  step      HotLoop(64 streams, fused_step=False) plain, with obstacles="tracks" and with "moving_tracks", window 1 and 256
 
 HIP events on the stream the work runs on, median of --reps launches after warm-up, the whole measurement --rounds times
-(the spread between rounds is the figure's own noise).  Runs on a tree without av_planner_plan_each too (those columns are
-left out): the same script gives the figures of an older commit.
+(the spread between rounds is the figure's own noise).  Runs on a tree without av_planner_plan_each or av_planner_plan_moving
+too (those columns are left out): the same script gives the figures of an older commit.
 """
 import argparse
 import ctypes as C
@@ -48,7 +49,8 @@ def planner_figures(reps):
     dev, st = torch.device("cuda", 0), torch.cuda.Stream()
     s = C.c_void_p(st.cuda_stream)
     rng = np.random.default_rng(1)
-    has_each = hasattr(L, "av_planner_plan_each")
+    has_each, has_moving = hasattr(L, "av_planner_plan_each"), hasattr(L, "av_planner_plan_moving")
+    vrng = np.random.default_rng(2)          # (a generator of its own: the other inputs are those of a tree without the moving case)
     out = {}
     for S in (64, 16384):
         state = torch.as_tensor(np.stack([rng.uniform(-50, 50, S), rng.uniform(-50, 50, S), rng.uniform(-3, 3, S),
@@ -74,6 +76,16 @@ def planner_figures(reps):
                                                                           P(wp), P(cost), P(order)))
             runs["each+16"] = lambda: nat.check(L.av_planner_plan_each(ctx.handle, s, S, P(state), None, None, 0, 1, P(obs_each),
                                                                        P(n_each), 16, P(wp), P(cost), P(order)))
+        if has_moving:
+            # the same 16, each with the ego's speed along the state's heading and up to 2 m/s of its own
+            rel = vrng.uniform(-2.0, 2.0, (16, 2))
+            mov = np.zeros((S, 16, 5))
+            mov[:, :, :3] = each
+            mov[:, :, 3] = sn[:, None, 3] * np.cos(sn[:, None, 2]) + rel[None, :, 0]
+            mov[:, :, 4] = sn[:, None, 3] * np.sin(sn[:, None, 2]) + rel[None, :, 1]
+            obs_mov = torch.as_tensor(mov, device=dev)
+            runs["moving+16"] = lambda: nat.check(L.av_planner_plan_moving(ctx.handle, s, S, P(state), None, None, 0, 1, P(obs_mov),
+                                                                           P(n_each), 16, P(wp), P(cost), P(order)))
         for name, fn in runs.items():
             out["%s S=%d" % (name, S)] = round(timed(L, s, fn, reps), 2)
         torch.cuda.synchronize()
@@ -86,6 +98,8 @@ def step_figures(reps):
     modes = [("plain", {})]
     if hasattr(L, "av_track_obstacles"):
         modes.append(("tracks", dict(obstacles="tracks")))
+    if hasattr(L, "av_track_obstacles_moving"):
+        modes.append(("moving_tracks", dict(obstacles="moving_tracks")))
     for W in (1, 256):
         z = np.stack([np.asarray(generate_ego_motion(W, seed=k)) for k in range(64)])
         for name, kw in modes:
