@@ -301,6 +301,45 @@ int av_track_obstacles_moving(av_ctx* ctx, av_stream_t stream, const av_obstacle
                               int tcap, const av_track_row* snap, const int32_t* snap_n, const double* plan_state,
                               int ocap, double* obstacles, int32_t* n_obs);
 
+/* The YOLO-mode detector's output (av_yolo_forward: float32 boxes and confidences, the model's class ids, confidence-descending)
+ * as the tracker's input (av_tracker_update), on the device; what ObjectDetector._detect_yolo does per box on the host
+ * (detector.py:111-121: map(int, xyxy), float(conf), int(cls)), plus an optional class table.  Per frame f:
+ *   n = clamp(src_n[f], 0, max_det); entries 0 .. n-1 are visited in order
+ *   class_map given: entry i is kept when 0 <= src_cls[i] < n_map and class_map[src_cls[i]] >= 0; its class is class_map[src_cls[i]]
+ *   class_map NULL:  every entry is kept with its raw class id
+ *   the first dcap kept entries are written in order: det_n[f] = min(kept, dcap), dropped[f] = kept - det_n[f]
+ *   det_box = the four coordinates truncated toward zero (int(x)); saturated to the int32 range, NaN -> 0
+ *   det_conf = (double)src_conf
+ *   rows at or past det_n[f] are not written
+ *   src_n [F], src_box [F][max_det][4], src_conf [F][max_det], src_cls [F][max_det]; class_map [n_map] or NULL
+ *   det_n [F], det_box [F][dcap][4], det_cls [F][dcap], det_conf [F][dcap]; dropped [F] or NULL
+ * 1 <= dcap <= 64 (the tracker's limit), max_det >= 1, n_frames >= 1: AV_EINVAL otherwise. */
+int av_dets_to_tracker(av_ctx* ctx, av_stream_t stream, int n_frames, int max_det, const int32_t* src_n,
+                       const float* src_box, const float* src_conf, const int32_t* src_cls, const int32_t* class_map,
+                       int n_map, int dcap, int32_t* det_n, int32_t* det_box, int32_t* det_cls, double* det_conf,
+                       int32_t* dropped);
+
+/* The lane detector's fits (av_lane_detect) as the planner's reference path, one per stream (av_planner_plan_each with
+ * ref_stride = the window), and as the maneuver tagger's lane offset in metres (av_maneuver_detect).  cfg's four scale fields
+ * are av_track_obstacles' (the radii are ignored), so tracks and lanes land in one road plane.  Stream s uses start state
+ * s * ref_stride (x0, y0, h0, .), the first frame of its window.  Where info[s][0] and info[s][1] are both non-zero, for
+ * i = 0 .. n_points - 1 (float64, every operation rounded on its own: no FMA):
+ *   y  = (double)h - (double)i * ((0.4 * (double)h) / (double)(n_points - 1))     rows h .. 0.6 h, nearest first
+ *                                                                                  (lane_detector.py:164)
+ *   x_side = (c2 * y + c1) * y + c0 for side 0 (left) and 1 (right) of poly;  xc = (x_left + x_right) / 2
+ *   l = (xc - x_center) * x_scale,  f = y_far - y * y_scale
+ *   ref_path[s][i] = ((x0 + f cos h0) + l cos(h0 + pi/2), (y0 + f sin h0) + l sin(h0 + pi/2))
+ *   n_ref[s] = n_points
+ *   lane_offset[s] = ((double)w / 2 - (double)(pts[s][0][49][0] + pts[s][1][49][0]) / 2) * x_scale
+ *                                                                  (get_lane_center_offset, lane_detector.py:253-272, in metres)
+ * otherwise n_ref[s] = 0, lane_offset[s] = NaN and no path row is written.  Rows at or past n_ref[s] are never written.
+ *   poly [S][2][3], pts [S][2][50][2], info [S][8] (av_lane_detect); plan_state [S * ref_stride][4] (av_kf_step)
+ *   ref_path [S][rcap][2], n_ref [S]; lane_offset [S] or NULL
+ * 2 <= n_points <= rcap and n_points <= 64 (one wave per stream); n_streams, h, w, ref_stride >= 1: AV_EINVAL otherwise. */
+int av_lane_paths(av_ctx* ctx, av_stream_t stream, const av_obstacle_cfg* cfg, int n_streams, int h, int w, int n_points,
+                  const double* poly, const int32_t* pts, const int32_t* info, const double* plan_state, int ref_stride,
+                  int rcap, double* ref_path, int32_t* n_ref, double* lane_offset);
+
 /* generate_polynomial_trajectory for arbitrary (lateral offset, target speed) pairs (:126-204).
  *   state [n_traj][4], end_lateral_offset [n_traj], target_velocity [n_traj] -> waypoints [n_traj][n][6] */
 int av_planner_generate(av_ctx* ctx, av_stream_t stream, int n_traj, const double* state,

@@ -134,6 +134,9 @@ _SIGS = [
     ("av_planner_plan_moving", C.c_int, [vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp]),
     ("av_track_obstacles_moving", C.c_int, [vp, vp, C.POINTER(ObstacleCfg), C.c_double, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp,
                                             vp]),
+    ("av_dets_to_tracker", C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    ("av_lane_paths", C.c_int, [vp, vp, C.POINTER(ObstacleCfg), C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int,
+                                C.c_int, vp, vp, vp]),
     ("av_hot_step", C.c_int, [vp, vp, C.POINTER(TrackerCfg), C.POINTER(KfCfg)] + [C.c_int] * 5 + [vp] * 17 + [vp, C.c_int, C.c_int]),
     ("av_hot_step_fits", C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     ("av_hot_steps_seq", C.c_int, [vp, C.c_int, vp, C.POINTER(TrackerCfg), C.POINTER(KfCfg)] + [C.c_int] * 5 + [vp] * 7 +

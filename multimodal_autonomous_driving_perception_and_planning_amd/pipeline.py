@@ -15,6 +15,11 @@ list and every stream with its own reference path (av_planner_plan_each); with "
 confirmed tracks (av_track_obstacles), and the planner then runs behind the tracker.  With "moving_tracks" every such
 obstacle also carries the velocity its track's last centre difference predicts (av_track_obstacles_moving), and each waypoint
 meets it where it is at that waypoint's time (av_planner_plan_moving).
+
+Opt-in (set_detections, set_lane_inputs, CameraLoop): the tracker is fed by a real detector's output left in HBM
+(av_dets_to_tracker instead of the simulated detector) and every stream's reference path is its own lane fit
+(av_lane_paths); CameraLoop wires a PerceptionLoop to a HotLoop that way, S cameras from pixels to ranked trajectories
+with no host round trip.
 """
 import ctypes as C
 
@@ -100,19 +105,12 @@ class HotLoop:
                              'plan without obstacles)' % obstacles)
         self._obs_mode = obstacles                # None | "tracks" | "moving_tracks" | "given" (set_obstacles)
         self.obstacles = self.n_obs = self.ref_paths = self.n_ref = None
+        self._obstacle_kw = dict(obstacle_kw or {})
+        self._src = self._class_map = self.det_dropped = None       # set_detections
+        self._lanes = self.lane_offset = None                       # set_lane_inputs
+        self._ext_streams = {}
         if obstacles is not None:
-            ok = dict(x_center=320.0, x_scale=0.03, y_far=50.0, y_scale=0.1, radius=[1.5] * 6 + [0.0] * 10)
-            ok.update(obstacle_kw or {})
-            if obstacles == "moving_tracks":
-                self.frame_rate = float(ok.pop("frame_rate", 30.0))
-                if not (self.frame_rate > 0.0 and np.isfinite(self.frame_rate)):
-                    raise ValueError("obstacle_kw: frame_rate must be > 0 and finite")
-            elif "frame_rate" in ok:
-                raise ValueError('obstacle_kw: frame_rate belongs to obstacles="moving_tracks"')
-            rad = [float(r) for r in ok.pop("radius")]
-            if len(rad) > 16:
-                raise ValueError("obstacle_kw: at most 16 per-class radii")
-            self.ocfg = nat.ObstacleCfg(radius=(C.c_double * 16)(*(rad + [0.0] * (16 - len(rad)))), **ok)
+            self.ocfg = self._make_ocfg(obstacles)
             self.obstacles = torch.zeros(S, W, tcap, 5 if obstacles == "moving_tracks" else 3, dtype=f64, device=d)
             self.n_obs = torch.zeros(S, W, dtype=i32, device=d)
             fused_step = False
@@ -150,6 +148,22 @@ class HotLoop:
             except RuntimeError as e:
                 raise ValueError("overlap=%d: %s" % (self.overlap, e)) from None
         self.reset()
+
+    def _make_ocfg(self, mode):
+        """av_obstacle_cfg from the constructor's obstacle_kw over the BEV panel's defaults; frame_rate (-> self.frame_rate) is
+        accepted with mode "moving_tracks" only."""
+        ok = dict(x_center=320.0, x_scale=0.03, y_far=50.0, y_scale=0.1, radius=[1.5] * 6 + [0.0] * 10)
+        ok.update(self._obstacle_kw)
+        if mode == "moving_tracks":
+            self.frame_rate = float(ok.pop("frame_rate", 30.0))
+            if not (self.frame_rate > 0.0 and np.isfinite(self.frame_rate)):
+                raise ValueError("obstacle_kw: frame_rate must be > 0 and finite")
+        elif "frame_rate" in ok:
+            raise ValueError('obstacle_kw: frame_rate belongs to obstacles="moving_tracks"')
+        rad = [float(r) for r in ok.pop("radius")]
+        if len(rad) > 16:
+            raise ValueError("obstacle_kw: at most 16 per-class radii")
+        return nat.ObstacleCfg(radius=(C.c_double * 16)(*(rad + [0.0] * (16 - len(rad)))), **ok)
 
     _PER_STEP = ("det_n", "det_box", "det_cls", "det_conf", "snap", "snap_n", "det2trk", "z", "vstate", "plan_state", "wp",
                  "cost", "order")
@@ -204,6 +218,18 @@ class HotLoop:
     # ---- individual stages (enqueue only) --------------------------------------------------------
     def enqueue_detect(self, stream=None):
         self._serial_only("enqueue_detect")
+        if self._src is not None:
+            # set_detections: the caller's detector output -> det_* (av_dets_to_tracker); the frame counters advance as they do
+            # with the simulated detector, on the same stream
+            n, box, conf, cls = self._src
+            nat.check(self.L.av_dets_to_tracker(self.ctx.handle, stream or self._s, self.S * self.W, int(box.shape[2]), nat.ptr(n),
+                                                nat.ptr(box), nat.ptr(conf), nat.ptr(cls), nat.ptr(self._class_map),
+                                                0 if self._class_map is None else int(self._class_map.numel()), self.dcap,
+                                                nat.ptr(self.det_n), nat.ptr(self.det_box), nat.ptr(self.det_cls),
+                                                nat.ptr(self.det_conf), nat.ptr(self.det_dropped)))
+            with torch.cuda.stream(self._torch_stream(stream)):
+                self.frame_count.add_(self.W)
+            return
         nat.check(self.L.av_simdet_generate(self.ctx.handle, stream or self._s, self.S, self.W, self.h, self.w,
                                             self.dcap, nat.ptr(self.frame_count), nat.ptr(self.det_n),
                                             nat.ptr(self.det_box), nat.ptr(self.det_cls), nat.ptr(self.det_conf),
@@ -306,6 +332,102 @@ class HotLoop:
             nat.check(self.L.av_graph_destroy(self.ctx.handle, gid))
         self._graphs, self.graph_id = {}, None
 
+    def _torch_stream(self, stream):
+        """The torch stream object of a raw stream handle (None: the loop's own stream)."""
+        if stream is None:
+            return self.stream
+        h = stream.value if hasattr(stream, "value") else int(stream)
+        if h not in self._ext_streams:
+            self._ext_streams[h] = torch.cuda.ExternalStream(h, device=self.dev)
+        return self._ext_streams[h]
+
+    def set_detections(self, src_n, src_box=None, src_conf=None, src_cls=None, class_map=None):
+        """A real detector's output as the tracker's input, read in place by every step from now on: device tensors int32 [S, W]
+        counts, float32 [S, W, max_det, 4] boxes (x1, y1, x2, y2), float32 [S, W, max_det] confidences and int32 [S, W, max_det]
+        class ids, in the detector's (confidence-descending) order -- PerceptionLoop's det_* viewed as [S, 1, ...].
+        enqueue_detect then calls av_dets_to_tracker into the loop's own det_* instead of the simulated detector: coordinates
+        truncated like int(), at most dcap entries per frame, the surplus counted in self.det_dropped [S, W].  class_map: None
+        (raw class ids) or an int32 table detector id -> tracker id, negative = skip the entry (host array or device tensor).
+        set_detections(None): the simulated detector again."""
+        if src_n is None:
+            if not (src_box is None and src_conf is None and src_cls is None):
+                raise ValueError("set_detections: the four detector tensors go together")
+            self._src = self._class_map = self.det_dropped = None
+            self._drop_graphs()
+            return
+        self._need_stage_launches("set_detections")
+        if src_box is None or src_conf is None or src_cls is None:
+            raise ValueError("set_detections: the four detector tensors go together")
+        ok = lambda t, dt, shape: (t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.is_cuda
+                                   and t.device == self.dev)
+        if not (torch.is_tensor(src_box) and src_box.dim() == 4 and src_box.shape[2] >= 1
+                and ok(src_box, torch.float32, (self.S, self.W, src_box.shape[2], 4))):
+            raise ValueError("set_detections: src_box is a contiguous float32 device tensor [S, W, max_det, 4]")
+        md = int(src_box.shape[2])
+        if not (torch.is_tensor(src_n) and ok(src_n, torch.int32, (self.S, self.W))):
+            raise ValueError("set_detections: src_n is a contiguous int32 device tensor [S, W]")
+        if not (torch.is_tensor(src_conf) and ok(src_conf, torch.float32, (self.S, self.W, md))):
+            raise ValueError("set_detections: src_conf is a contiguous float32 device tensor [S, W, max_det]")
+        if not (torch.is_tensor(src_cls) and ok(src_cls, torch.int32, (self.S, self.W, md))):
+            raise ValueError("set_detections: src_cls is a contiguous int32 device tensor [S, W, max_det]")
+        if not 1 <= self.dcap <= 64:
+            raise ValueError("set_detections: dcap %d not in 1 .. 64 (the tracker's limit)" % self.dcap)
+        if class_map is not None:
+            if not torch.is_tensor(class_map):
+                class_map = torch.as_tensor(np.ascontiguousarray(class_map, np.int32))
+            if class_map.dtype != torch.int32 or class_map.dim() != 1 or class_map.numel() == 0:
+                raise ValueError("set_detections: class_map is a one-dimensional int32 table")
+            class_map = class_map.to(self.dev).contiguous()
+        self._src, self._class_map = (src_n, src_box, src_conf, src_cls), class_map
+        self.det_dropped = torch.zeros(self.S, self.W, dtype=torch.int32, device=self.dev)
+        self._drop_graphs()
+
+    def set_lane_inputs(self, poly, pts=None, info=None, n_points=50):
+        """The lane detector's fits as every stream's reference path, rebuilt every step: device tensors float64 [S, 2, 3],
+        int32 [S, 2, 50, 2] and int32 [S, 8] (av_lane_detect's poly / pts / info, PerceptionLoop's attributes), read in place.
+        enqueue_step then runs av_lane_paths behind the Kalman stage into self.ref_paths [S, n_points, 2] / self.n_ref [S] /
+        self.lane_offset [S] (metres, NaN without a lane pair: what enqueue_maneuver(lane_offset=...) takes when the window is
+        1) and plans per state (av_planner_plan_each).  The image -> road scales are the loop's av_obstacle_cfg (obstacle_kw).
+        Not together with set_reference_paths.  set_lane_inputs(None): no lane paths."""
+        if poly is None:
+            if not (pts is None and info is None):
+                raise ValueError("set_lane_inputs: poly, pts and info go together")
+            if self._lanes is not None:
+                self._lanes = self.ref_paths = self.n_ref = self.lane_offset = None
+                self._drop_graphs()
+            return
+        self._need_stage_launches("set_lane_inputs")
+        if self._lanes is None and self.ref_paths is not None:
+            raise RuntimeError("set_lane_inputs: this loop has caller-supplied reference paths (set_reference_paths)")
+        if not 2 <= int(n_points) <= 64:
+            raise ValueError("set_lane_inputs: n_points is 2 .. 64")
+        ok = lambda t, dt, shape: (torch.is_tensor(t) and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous()
+                                   and t.is_cuda and t.device == self.dev)
+        if not ok(poly, torch.float64, (self.S, 2, 3)):
+            raise ValueError("set_lane_inputs: poly is a contiguous float64 device tensor [S, 2, 3]")
+        if not ok(pts, torch.int32, (self.S, 2, 50, 2)):
+            raise ValueError("set_lane_inputs: pts is a contiguous int32 device tensor [S, 2, 50, 2]")
+        if not ok(info, torch.int32, (self.S, 8)):
+            raise ValueError("set_lane_inputs: info is a contiguous int32 device tensor [S, 8]")
+        if not hasattr(self, "ocfg"):
+            self.ocfg = self._make_ocfg(None)
+        self._lanes = (poly, pts, info, int(n_points))
+        self.ref_paths = torch.zeros(self.S, int(n_points), 2, dtype=torch.float64, device=self.dev)
+        self.n_ref = torch.zeros(self.S, dtype=torch.int32, device=self.dev)
+        self.lane_offset = torch.full((self.S,), float("nan"), dtype=torch.float64, device=self.dev)
+        self._drop_graphs()
+
+    def enqueue_lane_paths(self, stream=None):
+        """set_lane_inputs: the lane fits and the window's first start states -> self.ref_paths / self.n_ref / self.lane_offset
+        (av_lane_paths); call behind enqueue_kf on the same stream."""
+        if self._lanes is None:
+            raise RuntimeError("enqueue_lane_paths needs set_lane_inputs")
+        poly, pts, info, n_points = self._lanes
+        nat.check(self.L.av_lane_paths(self.ctx.handle, stream or self._s, C.byref(self.ocfg), self.S, self.h, self.w, n_points,
+                                       nat.ptr(poly), nat.ptr(pts), nat.ptr(info), nat.ptr(self.plan_state), self.W,
+                                       int(self.ref_paths.shape[1]), nat.ptr(self.ref_paths), nat.ptr(self.n_ref),
+                                       nat.ptr(self.lane_offset)))
+
     def set_obstacles(self, obstacles, n_obs):
         """Caller-supplied obstacles for every frame of the window: float64 device tensor [S, W, ocap, 3] (x, y, radius) or, moving,
         [S, W, ocap, 5] (x, y, radius, vx, vy), and int32 [S, W] counts, read by every step from now on; None, None: none.  Not
@@ -330,6 +452,8 @@ class HotLoop:
         device tensor [S, rcap, 2] and int32 [S] point counts (fewer than two points: no path for that stream); None, None: none."""
         if (paths is None) != (n_ref is None):
             raise ValueError("set_reference_paths: the paths and their counts go together")
+        if self._lanes is not None:
+            raise RuntimeError("set_reference_paths: this loop builds its reference paths from the lane fits (set_lane_inputs)")
         if paths is not None:
             self._need_stage_launches("set_reference_paths")
             if not (paths.dtype == torch.float64 and paths.dim() == 3 and paths.shape[0] == self.S and paths.shape[2] == 2
@@ -485,9 +609,11 @@ class HotLoop:
         self.enqueue_track(self.ctx.side_stream)
         self.enqueue_kf()
         if self._per_state():
-            # per-state planner inputs: fork{detect; track} || {kf}; join; [tracks -> obstacles]; plan.  With obstacles from the
+            # per-state planner inputs: fork{detect; track} || {kf}; join; [lanes -> paths]; [tracks -> obstacles]; plan.  With obstacles from the
             # tracker the planner consumes the tables, so it moves behind the join
             nat.check(L.av_join(h, s))
+            if self._lanes is not None:
+                self.enqueue_lane_paths()
             if self._obs_mode in ("tracks", "moving_tracks"):
                 self.enqueue_obstacles()
             self.enqueue_plan_each()
@@ -564,6 +690,11 @@ class HotLoop:
             out["wp"] = self.wp.cpu().numpy().reshape(self.S, self.W, self.n_cand, self.n_points, 6)
         if self._obs_mode is not None:
             out["obstacles"], out["n_obs"] = self.obstacles.cpu().numpy(), self.n_obs.cpu().numpy()
+        if self._src is not None:
+            out["det_dropped"] = self.det_dropped.cpu().numpy()
+        if self._lanes is not None:
+            out["ref_paths"], out["n_ref"] = self.ref_paths.cpu().numpy(), self.n_ref.cpu().numpy()
+            out["lane_offset"] = self.lane_offset.cpu().numpy()
         return out
 
     # algorithmic HBM bytes of one planner launch: per start state
@@ -787,3 +918,77 @@ def _yolo_flops(H, W):
     for (cin, cout, k, s, _), d in zip(specs, div):
         fl += 2 * cin * cout * k * k * (H // d) * (W // d)
     return fl
+
+
+# detector class name -> the reference's class id (ObjectDetector.CLASSES: the ids av_obstacle_cfg.radius and the interaction tagger
+# expect); "_" in a name reads as " "
+_REFERENCE_IDS = {"car": 0, "truck": 1, "person": 2, "pedestrian": 2, "bicycle": 3, "cyclist": 3, "motorcycle": 4, "bus": 5,
+                  "traffic light": 6, "stop sign": 7}
+
+
+def reference_class_map(names):
+    """names: the detector's {id: name} dict or name list -> int32 table detector id -> reference id, -1 where the reference has
+    no such class (av_dets_to_tracker's class_map)."""
+    items = names.items() if isinstance(names, dict) else enumerate(names)
+    items = [(int(k), str(v)) for k, v in items]
+    table = np.full(max(k for k, _ in items) + 1, -1, np.int32)
+    for k, v in items:
+        table[k] = _REFERENCE_IDS.get(v.strip().lower().replace("_", " "), -1)
+    return table
+
+
+class CameraLoop:
+    """S cameras from pixels to ranked trajectories with no host round trip: a PerceptionLoop (self.cam: frames -> YOLO-mode
+    detector + lane detector) feeding a HotLoop of window 1 on the stage launches (self.hot: tracker -> Kalman -> planner) through
+    av_dets_to_tracker and av_lane_paths.  The tracker sees the detector's boxes, the planner avoids the tracks
+    (obstacles="moving_tracks" / "tracks" / None) and follows each camera's own lane centre line."""
+
+    def __init__(self, n_streams, h=720, w=1280, model="random:0", precision="fp16", dcap=64, obstacles="moving_tracks",
+                 class_map="reference", device=0, tracker_kw=None, kf_kw=None, planner_kw=None, obstacle_kw=None):
+        """class_map: "reference" (the detector's class names -> the reference's eight ids, everything else skipped:
+        reference_class_map), None (raw ids) or an explicit int table.  obstacle_kw: HotLoop's; the defaults stretch the BEV
+        panel's 640 x 500 px convention to the frame (x_center = w / 2, x_scale = 0.03 * 640 / w, y_far = 50,
+        y_scale = 50 / h)."""
+        self.S, self.h, self.w = n_streams, h, w
+        self.cam = PerceptionLoop(n_streams=n_streams, h=h, w=w, device=device, model=model, precision=precision)
+        ok = dict(x_center=w / 2.0, x_scale=0.03 * 640.0 / w, y_far=50.0, y_scale=50.0 / h)
+        ok.update(obstacle_kw or {})
+        self.hot = HotLoop(n_streams=n_streams, window=1, h=h, w=w, dcap=dcap, device=device, tracker_kw=tracker_kw, kf_kw=kf_kw,
+                           planner_kw=planner_kw, ctx=self.cam.ctx, fused_step=False, obstacles=obstacles, obstacle_kw=ok)
+        if isinstance(class_map, str):
+            if class_map != "reference":
+                raise ValueError('class_map is "reference", None or an int table')
+            class_map = reference_class_map(self.cam.yolo.names)
+        self.class_map = class_map
+        c, S = self.cam, n_streams
+        self.hot.set_detections(c.det_n.view(S, 1), c.det_box.view(S, 1, c.max_det, 4), c.det_conf.view(S, 1, c.max_det),
+                                c.det_cls.view(S, 1, c.max_det), class_map=class_map)
+        self.hot.set_lane_inputs(c.poly, c.pts, c.info)
+        self._stepped = False
+
+    def load_measurements(self, z):
+        """z: float64 [S, 1, 4] (or [S, 4]) ego measurements of the next step (HotLoop.load_measurements)."""
+        self.hot.load_measurements(z)
+
+    def step(self, sync=False):
+        """cam.step(); hot.step() behind it.  The camera half of the next step overwrites what the hot half reads (det_*, poly,
+        pts, info), so it first waits for the hot half of this one."""
+        if self.cam._tail_deferred or self.cam._lanes_pending:
+            raise RuntimeError("CameraLoop steps the plain PerceptionLoop.step(): with a deferred detector tail or a pending lane "
+                               "half det_* / poly describe the previous frame")
+        if self._stepped:
+            self.cam.stream.wait_stream(self.hot.stream)
+        self.cam.step()
+        self.hot.stream.wait_stream(self.cam.stream)
+        self.hot.step()
+        self._stepped = True
+        if sync:
+            self.synchronize()
+
+    def synchronize(self):
+        self.cam.synchronize()
+        self.hot.synchronize()
+
+    def results(self):
+        """HotLoop.results() of the last step: with det_dropped [S, 1], ref_paths [S, 50, 2], n_ref [S] and lane_offset [S]."""
+        return self.hot.results()
