@@ -567,6 +567,76 @@ int av_interaction_detect(av_ctx* ctx, av_stream_t stream, const av_interaction_
                           const uint8_t* has_state, const double* vy, void* state, av_interaction_row* rows,
                           av_interaction_summary* summary);
 
+/* ---- tag log: per-frame tag masks, search, event segments, statistics -----------------------------------------
+ * Replaces AutoTagger's bookkeeping (src/tagging/auto_tagger.py:112-310: all_tags, tag_counts, search_by_tag(s),
+ * get_high_risk_frames, get_event_segments, get_tag_statistics) for S streams, on the device.  A logged frame is one 64-bit mask
+ * over the vocabulary below plus the frame's speed; the tags are laid out in the reference's Enum definition order (the indices
+ * the three taggers' rows carry), each group at its base bit.  A frame's tags are a set: the reference's first-seen order inside
+ * all_tags is not kept. */
+#define AV_TAG_ROAD_TYPE 0            /* 6: unknown intersection highway urban residential parking          */
+#define AV_TAG_ELEMENT 6              /* 5: traffic_light stop_sign crosswalk yield_sign speed_limit         */
+#define AV_TAG_CONDITION 11           /* 6: clear congested night day rain fog                               */
+#define AV_TAG_PEDESTRIAN_AREA 17
+#define AV_TAG_LATERAL 18             /* 4 */
+#define AV_TAG_LONGITUDINAL 22        /* 5 */
+#define AV_TAG_TURNING 27             /* 6 */
+#define AV_TAG_INTERACTION 33         /* 13; no_interaction is bit 33 */
+#define AV_TAG_RISK 46                /* 3: risk_medium risk_high risk_critical (RiskLevel index - 1) */
+#define AV_TAG_COUNT 49               /* bits 49..60 are zero */
+#define AV_TAG_HAS_SCENE 61           /* presence flags, not tags: the frame had a scene row / a maneuver row / an */
+#define AV_TAG_HAS_MANEUVER 62        /* interaction summary (get_tag_statistics' `if ft.maneuver`, `if ft.interaction`) */
+#define AV_TAG_HAS_INTERACTION 63
+/* The three taggers' rows of n_streams x n_frames frames as masks and speeds (the get_tags_list of scene_classifier.py:66,
+ * maneuver_detector.py:71, interaction_detector.py:95).  Each input group may be NULL; its presence flag is then clear.
+ *   maneuver       av_maneuver_row [S][W]: the three enum bits; out_speed = speed_kmh (NaN without maneuver rows)
+ *   inter_rows     av_interaction_row [S][W][tcap], inter_summary [S][W], snap_n [S][W] (given together), tcap == 64: the type bit
+ *                  of every row below clamp(snap_n, 0, tcap) with 0 <= type < 13 and confidence > 0.5 (exactly 0.5 is no tag);
+ *                  risk_<overall_risk> when overall_risk is 1..3
+ *   scene          av_scene_row [S][W]: road_type (after the vote), conditions[k] for k < clamp(n_conditions, 0, 3),
+ *                  pedestrian_area when has_pedestrian != 0
+ *   det_n [S][W], det_cls [S][W][max_det], elem_table u8 [n_elem] (given together, only with scene rows: traffic elements are scene
+ *                  tags): per class id 0 = none, else TrafficElement index + 1; one element bit per detection
+ *                  i < clamp(det_n, 0, max_det) whose class id lies inside the table and whose entry is 1..5
+ * An enum index outside its range sets no bit.   out_mask u64 [S][W], out_speed f64 [S][W] */
+int av_tags_pack(av_ctx* ctx, av_stream_t stream, int n_streams, int n_frames, const av_maneuver_row* maneuver,
+                 const av_interaction_row* inter_rows, const av_interaction_summary* inter_summary, const int32_t* snap_n, int tcap,
+                 const av_scene_row* scene, const int32_t* det_n, const int32_t* det_cls, int max_det, const uint8_t* elem_table,
+                 int n_elem, uint64_t* out_mask, double* out_speed);
+/* The log: log_mask u64 [S][cap], log_speed f64 [S][cap], log_n int32 [S], dropped int32 [S], the caller's, zeroed to start with.
+ * av_taglog_append copies mask / speed [S][W] behind log_n[s] and advances log_n on the device (no host synchronisation: it can
+ * sit in a step).  A frame that does not fit is not written and counted in dropped[s]; log_n never exceeds cap. */
+int av_taglog_append(av_ctx* ctx, av_stream_t stream, int n_streams, int n_frames, const uint64_t* mask, const double* speed,
+                     int cap, uint64_t* log_mask, double* log_speed, int32_t* log_n, int32_t* dropped);
+/* Queries cut a stream's log into chunks of AV_TAGLOG_CHUNK frames, one wave each, and hand what a chunk needs of the chunks before
+ * it from launch to launch through `workspace` (av_taglog_workspace_bytes(S, cap) bytes, 8-byte aligned, contents irrelevant
+ * between calls; one query at a time per workspace).
+ * Frame i of stream s matches when (m & all) == all, (any == 0 or (m & any) != 0) and (m & none) == 0, and first <= i < last;
+ * the range is clamped to [0, log_n[s]) (first = 0, last = cap: the whole log). */
+#define AV_TAGLOG_CHUNK 1024
+size_t av_taglog_workspace_bytes(int n_streams, int cap);
+/*   out_idx int32 [S][out_cap] the matching frame indices, increasing; out_n [S] the number of matches, which may exceed out_cap;
+ *   rows at or past min(out_n, out_cap) are not written */
+int av_taglog_search(av_ctx* ctx, av_stream_t stream, int n_streams, int cap, const uint64_t* log_mask, const int32_t* log_n,
+                     uint64_t all, uint64_t any, uint64_t none, int first, int last, void* workspace, int out_cap,
+                     int32_t* out_idx, int32_t* out_n);
+/* get_event_segments (auto_tagger.py:281-310): the maximal runs of matching frames with last - first + 1 >= min_duration, in
+ * order, as out_seg int32 [S][seg_cap][2] (first, last); a run that reaches the end of the range is closed there.  out_n [S] is
+ * the number of such runs, which may exceed seg_cap; rows at or past min(out_n, seg_cap) are not written. */
+int av_taglog_segments(av_ctx* ctx, av_stream_t stream, int n_streams, int cap, const uint64_t* log_mask, const int32_t* log_n,
+                       uint64_t all, uint64_t any, uint64_t none, int first, int last, int min_duration, void* workspace,
+                       int seg_cap, int32_t* out_seg, int32_t* out_n);
+/* get_tag_statistics (auto_tagger.py:210-250) of every stream's whole log.  Integer fields and min / max are exact; the partial
+ * sums of the chunks are folded in a fixed order, so speed_sum is the same on every call. */
+typedef struct av_taglog_stats_row {
+    int64_t tag_count[64];          /* frames carrying each bit (the presence flags included) */
+    int64_t n_frames, n_maneuver;   /* log_n; frames with AV_TAG_HAS_MANEUVER */
+    int64_t risk_count[4];          /* low (AV_TAG_HAS_INTERACTION and none of the risk bits), medium, high, critical */
+    double speed_min, speed_max;    /* over the frames with AV_TAG_HAS_MANEUVER; +inf / -inf without one */
+    double speed_sum;
+} av_taglog_stats_row;              /* 584 bytes */
+int av_taglog_stats(av_ctx* ctx, av_stream_t stream, int n_streams, int cap, const uint64_t* log_mask, const double* log_speed,
+                    const int32_t* log_n, void* workspace, av_taglog_stats_row* out);
+
 /* ---- rendering ----------------------------------------------------------------
  * Replaces the cv2 drawing behind BEVRenderer.render (src/visualization/bev_renderer.py:286-348 and its helpers
  * :92-284,350-364), OverlayRenderer (src/visualization/overlays.py:26-210) and the draw_* methods of the four hot-path

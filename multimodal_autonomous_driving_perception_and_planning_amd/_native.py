@@ -71,6 +71,10 @@ SCENE_ROW_FIELDS = [("gray_sum", "<u8"), ("green_count", "<u8"), ("lap_sum", "<i
                     ("history", "<i4", (5,)), ("reserved", "<i4")]
 SCENE_ROW_BYTES = 240
 SCENE_CAT_TRAFFIC, SCENE_CAT_VEHICLE, SCENE_CAT_PEDESTRIAN = 1, 2, 4
+TAGLOG_CHUNK = 1024
+TAGLOG_STATS_FIELDS = [("tag_count", "<i8", (64,)), ("n_frames", "<i8"), ("n_maneuver", "<i8"), ("risk_count", "<i8", (4,)),
+                       ("speed_min", "<f8"), ("speed_max", "<f8"), ("speed_sum", "<f8")]
+TAGLOG_STATS_BYTES = 584
 
 
 class BevCfg(C.Structure):
@@ -179,6 +183,14 @@ _SIGS = [
     ("av_scene_workspace_init", C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     ("av_scene_classify", C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp,
                                     vp, vp, vp, vp]),
+    ("av_tags_pack", C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp]),
+    ("av_taglog_append", C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]),
+    ("av_taglog_workspace_bytes", C.c_size_t, [C.c_int, C.c_int]),
+    ("av_taglog_search", C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int, vp,
+                                   C.c_int, vp, vp]),
+    ("av_taglog_segments", C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int,
+                                     C.c_int, vp, C.c_int, vp, vp]),
+    ("av_taglog_stats", C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
 ]
 
 # entry points added by later translation units; bound when present in the header list below

@@ -109,6 +109,7 @@ class HotLoop:
         self._src = self._class_map = self.det_dropped = None       # set_detections
         self._lanes = self.lane_offset = None                       # set_lane_inputs
         self._ext_streams = {}
+        self.tag_log = None                                         # enable_tag_log
         if obstacles is not None:
             self.ocfg = self._make_ocfg(obstacles)
             self.obstacles = torch.zeros(S, W, tcap, 5 if obstacles == "moving_tracks" else 3, dtype=f64, device=d)
@@ -279,6 +280,29 @@ class HotLoop:
         nat.check(self.L.av_interaction_detect(self.ctx.handle, stream or self._s, C.byref(cfg), self.S, self.W, self.tcap,
                                                nat.ptr(self.snap), nat.ptr(self.snap_n), nat.ptr(self.vstate), None, None,
                                                nat.ptr(self.inter_state), nat.ptr(self.inter_rows), nat.ptr(self.inter_summary)))
+
+    def enable_tag_log(self, capacity):
+        """A device-resident tag log of `capacity` frames per stream (tagging.tag_log.TagLog, self.tag_log) for enqueue_tags."""
+        self._serial_only("enable_tag_log")
+        from .tagging.tag_log import TagLog
+        self.tag_log = TagLog(self.S, capacity, device=self.dev.index, ctx=self.ctx, stream=self.stream)
+        return self.tag_log
+
+    def enqueue_tags(self, stream=None, scene_rows=None, det=None, elem_table=None):
+        """This window's tags into self.tag_log (av_tags_pack + av_taglog_append): the maneuver rows and the interaction rows /
+        summaries, whichever enqueue_maneuver / enqueue_interactions have produced -- call it after them on the same stream --
+        plus, when given, scene_rows (av_scene_row [S][W] as uint8) with det = (det_n [S][W], det_cls [S][W][max_det]) and
+        elem_table (tagging.tag_log.element_table) for the traffic elements."""
+        self._serial_only("enqueue_tags")
+        if self.tag_log is None:
+            raise RuntimeError("enqueue_tags needs enable_tag_log(capacity)")
+        inter = hasattr(self, "inter_rows")
+        det_n, det_cls = det if det is not None else (None, None)
+        self.tag_log.pack_and_append(self.W, maneuver=getattr(self, "maneuver", None),
+                                     inter_rows=self.inter_rows if inter else None,
+                                     inter_summary=self.inter_summary if inter else None, snap_n=self.snap_n if inter else None,
+                                     scene_rows=scene_rows, det_n=det_n, det_cls=det_cls, elem_table=elem_table,
+                                     stream=stream or self._s)
 
     def enqueue_bev(self, stream=None, frame=None, n_candidates=10):
         """BEV panels of every stream (BEVRenderer.render, bev_renderer.py:286-348) for one frame of the window, built and
@@ -864,7 +888,8 @@ class PerceptionLoop:
     def enqueue_scene(self, stream=None, speeds=None, max_segments=4096):
         """Opt-in scene stage (SceneClassifier.classify for every camera, av_scene_classify) on the frames, detections and
         lane outputs in HBM: call it after step() (after flush_lanes() in the deferred mode), so that det_* and info / poly
-        describe the current frames.  speeds: ego speed per camera (NaN = no vehicle state), or None for none.  The stage
+        describe the current frames.  speeds: ego speed per camera (NaN = no vehicle state; a host array, or a float64 device
+        tensor [S], which is read on the stream the stage runs on), or None for none.  The stage
         has its own workspace and 5-deep road-type history per camera; rows land in self.scene_rows."""
         from .tagging.scene_classifier import category_table
         S, d = self.S, self.dev
@@ -872,7 +897,7 @@ class PerceptionLoop:
             self.scene_cap = int(max_segments)
             self.scene_ws = torch.empty(int(self.L.av_scene_workspace_bytes(S, self.h, self.w, self.scene_cap)), dtype=torch.uint8,
                                         device=d)
-            nat.check(self.L.av_scene_workspace_init(self.ctx.handle, self._s, S, self.h, self.w, self.scene_cap,
+            nat.check(self.L.av_scene_workspace_init(self.ctx.handle, stream or self._s, S, self.h, self.w, self.scene_cap,
                                                      nat.ptr(self.scene_ws)))
             if getattr(self, "scene_state", None) is None:
                 self.scene_state = torch.zeros(int(self.L.av_scene_state_bytes(S)), dtype=torch.uint8, device=d)
@@ -881,7 +906,16 @@ class PerceptionLoop:
                 self.scene_cat = torch.as_tensor(cat).to(d)
                 self.scene_speed = torch.full((S,), float("nan"), dtype=torch.float64, device=d)
         sp = None
-        if speeds is not None:
+        if isinstance(speeds, torch.Tensor) and speeds.is_cuda:
+            # a device tensor (e.g. the Kalman output's speed column): copied on the stream the stage runs on, no host round trip
+            if speeds.dtype != torch.float64 or tuple(speeds.shape) != (S,):
+                raise ValueError("speeds on the device: a float64 tensor [n_streams]")
+            ts = self.stream if stream is None else torch.cuda.ExternalStream(stream.value if hasattr(stream, "value") else int(stream),
+                                                                              device=d)
+            with torch.cuda.stream(ts):
+                self.scene_speed.copy_(speeds)
+            sp = nat.ptr(self.scene_speed)
+        elif speeds is not None:
             with torch.cuda.stream(self.stream):
                 self.scene_speed.copy_(torch.as_tensor(np.asarray(speeds, np.float64).reshape(S)))
             sp = nat.ptr(self.scene_speed)
@@ -944,11 +978,19 @@ class CameraLoop:
     (obstacles="moving_tracks" / "tracks" / None) and follows each camera's own lane centre line."""
 
     def __init__(self, n_streams, h=720, w=1280, model="random:0", precision="fp16", dcap=64, obstacles="moving_tracks",
-                 class_map="reference", device=0, tracker_kw=None, kf_kw=None, planner_kw=None, obstacle_kw=None):
+                 class_map="reference", device=0, tracker_kw=None, kf_kw=None, planner_kw=None, obstacle_kw=None, tags=None,
+                 tag_capacity=4096):
         """class_map: "reference" (the detector's class names -> the reference's eight ids, everything else skipped:
         reference_class_map), None (raw ids) or an explicit int table.  obstacle_kw: HotLoop's; the defaults stretch the BEV
         panel's 640 x 500 px convention to the frame (x_center = w / 2, x_scale = 0.03 * 640 / w, y_far = 50,
-        y_scale = 50 / h)."""
+        y_scale = 50 / h).
+        tags: None, "motion" or "all" -- every step() also tags its frame behind hot.step() on the hot stream and appends it to
+        self.tag_log (a TagLog of tag_capacity frames per camera): "motion" runs the maneuver tagger (with the lanes' offset), the
+        interaction tagger (class_map="reference" only: it needs the reference's class ids) and enqueue_tags; "all" runs the scene
+        stage ahead of them (cam.enqueue_scene with the Kalman speed, read on the device) and adds its tags and the detector's
+        traffic elements.  The scene stage is the expensive one, hence not the default of `tags`."""
+        if tags not in (None, "motion", "all"):
+            raise ValueError('tags is None, "motion" or "all"')
         self.S, self.h, self.w = n_streams, h, w
         self.cam = PerceptionLoop(n_streams=n_streams, h=h, w=w, device=device, model=model, precision=precision)
         ok = dict(x_center=w / 2.0, x_scale=0.03 * 640.0 / w, y_far=50.0, y_scale=50.0 / h)
@@ -965,6 +1007,14 @@ class CameraLoop:
                                 c.det_cls.view(S, 1, c.max_det), class_map=class_map)
         self.hot.set_lane_inputs(c.poly, c.pts, c.info)
         self._stepped = False
+        self.tags, self.tag_log = tags, None
+        if tags is not None:
+            from .perception.detector import ObjectDetector
+            from .tagging.tag_log import element_table
+            self.tag_log = self.hot.enable_tag_log(tag_capacity)
+            self._tag_interactions = isinstance(class_map, np.ndarray) and np.array_equal(class_map, reference_class_map(c.yolo.names))
+            self._tag_classes = [ObjectDetector.CLASSES[k] for k in range(8)]
+            self._elem_table = torch.as_tensor(element_table(c.yolo.names)).to(self.hot.dev) if tags == "all" else None
 
     def load_measurements(self, z):
         """z: float64 [S, 1, 4] (or [S, 4]) ego measurements of the next step (HotLoop.load_measurements)."""
@@ -981,9 +1031,25 @@ class CameraLoop:
         self.cam.step()
         self.hot.stream.wait_stream(self.cam.stream)
         self.hot.step()
+        if self.tags is not None:
+            self._enqueue_tags()
         self._stepped = True
         if sync:
             self.synchronize()
+
+    def _enqueue_tags(self):
+        """The taggers and the log append behind hot.step(), all on the hot stream: it has waited for the camera half, and the next
+        cam.step() waits for it, so the scene stage may read the frames, detections and lane fits there."""
+        hot, cam, S = self.hot, self.cam, self.S
+        scene = det = None
+        with torch.cuda.stream(hot.stream):         # the stages' buffers, made at the first call, are zero-filled on that stream too
+            if self.tags == "all":
+                cam.enqueue_scene(stream=hot._s, speeds=hot.vstate[:, 0, 5])
+                scene, det = cam.scene_rows.view(S, 1, -1), (cam.det_n.view(S, 1), cam.det_cls.view(S, 1, cam.max_det))
+            hot.enqueue_maneuver(lane_offset=hot.lane_offset)
+            if self._tag_interactions:
+                hot.enqueue_interactions(frame_shape=(self.h, self.w), class_names=self._tag_classes)
+            hot.enqueue_tags(scene_rows=scene, det=det, elem_table=self._elem_table)
 
     def synchronize(self):
         self.cam.synchronize()

@@ -4,8 +4,9 @@ from .interaction_detector import (Interaction, InteractionDetector, Interaction
 from .maneuver_detector import (LateralManeuver, LongitudinalManeuver, ManeuverDetector, ManeuverTags,  # noqa: F401
                                 TurningManeuver)
 from .scene_classifier import Condition, RoadType, SceneClassifier, SceneTags, TrafficElement  # noqa: F401
+from .tag_log import TAGS, TagLog, tag_mask, tags_of  # noqa: F401
 
 __all__ = ["ManeuverDetector", "ManeuverTags", "LateralManeuver", "LongitudinalManeuver", "TurningManeuver",
            "InteractionDetector", "InteractionTags", "Interaction", "InteractionType", "RiskLevel",
            "SceneClassifier", "SceneTags", "RoadType", "TrafficElement", "Condition",
-           "AutoTagger", "FrameTags", "TaggingSession"]
+           "AutoTagger", "FrameTags", "TaggingSession", "TagLog", "TAGS", "tag_mask", "tags_of"]

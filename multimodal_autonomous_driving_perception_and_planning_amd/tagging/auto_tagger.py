@@ -3,7 +3,8 @@
 Joins the port's three taggers per frame (SceneClassifier, ManeuverDetector, InteractionDetector, each on the GPU)
 and keeps the reference's host-side bookkeeping (auto_tagger.py:74-372): the frame's tag list in first-seen order,
 per-tag confidences (later writers win), tag counts, searches, event segments and the dict / JSON / CSV exports.
-This part is aggregation over a few strings per frame and has no kernel.
+This part is aggregation over a few strings per frame and has no kernel.  Its batched counterpart, for S streams with the
+tags kept and searched on the device, is tagging/tag_log.py (TagLog).
 """
 import json
 from dataclasses import dataclass, field
