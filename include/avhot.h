@@ -234,6 +234,16 @@ typedef struct {
  * av_planner_plan plans every configuration this call accepts. */
 int av_planner_configure(av_ctx* ctx, const av_planner_cfg* cfg);
 int av_planner_dims(const av_ctx* ctx, int* n_points, int* n_candidates);   /* host out */
+/* The launch av_planner_plan / _plan_each / _plan_moving make for n_states start states of a configuration with n_points
+ * waypoints and n_candidates candidates; extra != 0: a reference path or obstacles are given (_plan_each / _plan_moving: a list
+ * pointer is).  Needs neither a context nor a device: it is the library's own launch plan, asked without launching.
+ *   out[0]  0: planner_kernel<G, NW> (a workgroup of NW waves plans G start states), 1: planner_wave_kernel (every wave on its own;
+ *           with `extra` its form that reads the lists)
+ *   out[1]  G; for the wave kernel the start states per wave        out[2]  NW, waves per workgroup
+ *   out[3]  dynamic LDS bytes of a workgroup (<= 65 536)
+ * AV_EINVAL outside what av_planner_configure accepts (n_points in [1,256], n_candidates = 3 * num_samples in [3,192]) and for
+ * n_states <= 0. */
+int av_planner_launch_shape(int n_points, int n_candidates, int n_states, int extra, int32_t out[4]);   /* host out */
 /* One plan() per start state.  n_states = S*W.
  *   state     [n_states][4]          x, y, heading, speed
  *   ref_path  [n_ref][2] or NULL     shared by all states of this call (set_reference_path, :93-124)

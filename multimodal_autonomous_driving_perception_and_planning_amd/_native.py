@@ -132,6 +132,7 @@ _SIGS = [
     ("av_kf_step", C.c_int, [vp, vp, C.POINTER(KfCfg), C.c_int, C.c_int, vp, vp, vp, vp, vp]),
     ("av_planner_configure", C.c_int, [vp, C.POINTER(PlannerCfg)]),
     ("av_planner_dims", C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("av_planner_launch_shape", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_i32p]),
     ("av_planner_plan", C.c_int, [vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp]),
     ("av_planner_plan_each", C.c_int, [vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp]),
     ("av_track_obstacles", C.c_int, [vp, vp, C.POINTER(ObstacleCfg), C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp]),

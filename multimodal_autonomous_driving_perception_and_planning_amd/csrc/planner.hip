@@ -71,12 +71,23 @@ __device__ __forceinline__ double atan2_fast(double y, double x, const double (&
     return __builtin_copysign(a, y);
 }
 
-__host__ __device__ inline int even_up(int v) { return (v + 1) & ~1; }
+__host__ __device__ constexpr int even_up(int v) { return (v + 1) & ~1; }
 
 // doubles of dynamic LDS for G start states per workgroup of NW waves
 __host__ __device__ inline size_t plan_lds_doubles(int G, int n, int C, int NW = 4) {
     return (size_t)G * 3 * n * 2 + even_up(G * 3 * 3) + (size_t)G * 8 + (size_t)3 * even_up(G * C) + (size_t)NW * n * 6;
 }
+
+// Output ring of planner_wave_kernel: 256 units of 16 B.  It holds at most 63 carried units + one tile of
+// 3n <= 192 units; FPW*3*n <= 384 doubles of phase-1 scratch also fit.
+constexpr int RING_UNITS = 256, RING_DOUBLES = RING_UNITS * 2;
+
+// doubles of dynamic LDS of ONE wave of planner_wave_kernel, FPW start states each: (v, s) | ring | costs | sums | heading terms
+__host__ __device__ constexpr size_t wave_lds_doubles(int FPW, int n, int C) {
+    return (size_t)FPW * 3 * n * 2 + RING_DOUBLES + even_up(FPW * C) + FPW * 3 * 4 + FPW * 8;
+}
+// the most its four waves ever need (n <= 64, C <= 192, two states per wave): (768 + 512 + 384 + 24 + 16) doubles each
+static_assert(wave_lds_doubles(2, 64, 192) * 4 * sizeof(double) == 54528, "the wave kernel fits 64 KB of LDS whatever the configuration");
 
 // Orders this wave's LDS accesses for the compiler.  The hardware executes one wave's DS operations
 // in issue order, so no s_waitcnt is needed (and none for outstanding global stores either).
@@ -84,6 +95,74 @@ __device__ __forceinline__ void wave_lds_fence() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+}
+
+// ---- the reference's arithmetic, one copy each; every kernel below calls these ----------------------------------------------
+__device__ __forceinline__ double target_speed(int k) { return 8.0 + 2.0 * (double)k; }                        // [8.0, 10.0, 12.0]  (:280)
+__device__ __forceinline__ double blend_velocity(double v0, double dv, double alpha) { return v0 + dv * alpha; }   // :153-154
+__device__ __forceinline__ double velocity_term(double w_vel, double v) {                                      // :236
+    const double e = v - 10.0;
+    return w_vel * (e * e);
+}
+// from two consecutive velocities and the time between them; the callers add it up only where that time is > 0 (:240-244)
+__device__ __forceinline__ double acceleration_term(double w_acc, double v, double vp, double dtd) {
+    const double a = (v - vp) / dtd;
+    return w_acc * (a * a);
+}
+// A start state as the waypoints are placed from it: the point at arc length s is `along` the heading (:175-176), its lateral
+// offset d `across` it (:179-180); a waypoint is the sum of the two.
+struct PlanFrame {
+    double x0, y0, cs, sn, c2, s2;      // position, cos / sin of the heading and of heading + pi/2
+    __device__ __forceinline__ void along(double s, double& bx, double& by) const { bx = x0 + s * cs, by = y0 + s * sn; }
+    __device__ __forceinline__ void across(double d, double& dx, double& dy) const { dx = d * c2, dy = d * s2; }
+    __device__ __forceinline__ void point(double s, double d, double& x, double& y) const {
+        double dx, dy;
+        along(s, x, y), across(d, dx, dy);
+        x = x + dx, y = y + dy;
+    }
+};
+// curvature of interior waypoint i of an AoS tile whose headings are in place (:196)
+__device__ __forceinline__ double tile_curvature(const double* tile, int i, double dt) {
+    const double* w = tile + (size_t)i * 6;
+    return (w[2] - tile[(size_t)(i - 1) * 6 + 2]) / (w[3] * dt + 1e-6);
+}
+// the last waypoint has no forward difference: it repeats the heading before it, a lone one the start state's (:190)
+__device__ __forceinline__ void tile_last_heading(double* tile, int n, double h0) {
+    tile[(size_t)(n - 1) * 6 + 2] = n > 1 ? tile[(size_t)(n - 2) * 6 + 2] : h0;
+}
+// reference-path term of a waypoint: the squared distance to the nearest of the n_ref > 0 path points (:229-231)
+__device__ __forceinline__ double ref_path_term(double w_lat, const double* ref, int n_ref, double x, double y) {
+    double md = INFINITY;
+    for (int r = 0; r < n_ref; ++r) {
+        const double dx = ref[2 * r] - x, dy = ref[2 * r + 1] - y;
+        const double dd = sqrt(dx * dx + dy * dy);
+        md = dd < md ? dd : md;
+    }
+    return w_lat * (md * md);
+}
+// adds to `sum` what obstacle row o (x, y, radius; MOVING: + vx, vy, the disc where its velocity has carried it by the waypoint's
+// time tw) costs the waypoint at (x, y) (:253-259).  The callers own the loops: their summation orders differ.
+template <bool MOVING>
+__device__ __forceinline__ void add_obstacle_penalty(double& sum, const double* o, double x, double y, double tw) {
+    double ox = o[0], oy = o[1];
+    const double rad = o[2];
+    if constexpr (MOVING) ox = ox + o[3] * tw, oy = oy + o[4] * tw;
+    const double ex = x - ox, ey = y - oy;
+    const double dist = sqrt(ex * ex + ey * ey);
+    if (dist < rad * 2.0) sum = sum + 1000.0 * (rad * 2.0 - dist);
+    else if (dist < rad * 4.0) sum = sum + 10.0 / (dist - rad + 0.1);
+}
+// candidate c of state f: its stable ascending rank among the state's C costs cc (== Python's stable sort, :300), stored with its cost
+__device__ __forceinline__ void rank_and_store(const double* cc, int C, int c, int f, double* __restrict__ cost,
+                                               int32_t* __restrict__ order) {
+    const double mine = cc[c];
+    int rank = 0;
+    for (int o2 = 0; o2 < C; ++o2) {
+        const double v = cc[o2];
+        rank += (v < mine || (v == mine && o2 < c)) ? 1 : 0;
+    }
+    cost[(size_t)f * C + c] = mine;
+    order[(size_t)f * C + rank] = c;
 }
 
 // The workgroup-cooperative planner for small batches (and n > 64): G consecutive start states f0 .. f0 + G - 1 by a workgroup of
@@ -187,16 +266,12 @@ __device__ __forceinline__ void plan_block_lists(const PlanParams& p, int f0, in
         return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
     };
     auto terms = [&](double v0, double dv, int i, double& v, double& vdt, double& velt, double& acct) {
-        v = v0 + dv * p.alpha[i];                             // :153-154
+        v = blend_velocity(v0, dv, p.alpha[i]);
         vdt = v * p.dt;
-        const double e = v - 10.0;
-        velt = p.w_vel * (e * e);                             // :236
+        velt = velocity_term(p.w_vel, v);
         acct = 0.0;
-        if (i > 0) {                                          // (added up only where dtd[i] > 0, like the reference's test)
-            const double vp = v0 + dv * p.alpha[i - 1];
-            const double a = (v - vp) / p.dtd[i];
-            acct = p.w_acc * (a * a);                         // :244
-        }
+        if (i > 0)                                            // (added up only where dtd[i] > 0, like the reference's test)
+            acct = acceleration_term(p.w_acc, v, blend_velocity(v0, dv, p.alpha[i - 1]), p.dtd[i]);
     };
     // the cost chains of one pair from its terms: S_v over all waypoints, then the acceleration terms on top (:235-244)
     auto cost_chains = [&](double velt, double acct, unsigned long long hasm, double* b) {
@@ -224,8 +299,7 @@ __device__ __forceinline__ void plan_block_lists(const PlanParams& p, int f0, in
             const int g = wid / 3, k = wid - g * 3, f = f0 + g;
             if (f < n_states) {
                 const double v0 = state[(size_t)(f + sd) * 4 + 3];
-                const double vt = 8.0 + 2.0 * (double)k;      // [8.0, 10.0, 12.0]  (:280)
-                const double dv = vt - v0;
+                const double dv = target_speed(k) - v0;
                 double* o = vs + ((size_t)(g * 3 + k) * n) * 2;
                 double v = 0.0, vdt = 0.0;
                 bool has = false;
@@ -246,8 +320,7 @@ __device__ __forceinline__ void plan_block_lists(const PlanParams& p, int f0, in
             const int g = pr / 3, k = pr - g * 3, f = f0 + g;
             if (f >= n_states) continue;
             const double v0 = state[(size_t)(f + sd) * 4 + 3];
-            const double vt = 8.0 + 2.0 * (double)k;
-            const double dv = vt - v0;
+            const double dv = target_speed(k) - v0;
             double* o = vs + ((size_t)(g * 3 + k) * n) * 2;
             double* b = base + (g * 3 + k) * 3;
             double* tv = stage;                               // [n] v_i dt | [n] velocity cost term | [n] acceleration cost term
@@ -315,20 +388,18 @@ __device__ __forceinline__ void plan_block_lists(const PlanParams& p, int f0, in
         const int li = c / 3, k = c - li * 3;
         const double df = p.lat[li];
         const double* tg = trig + g * 8;
-        const double x0 = tg[0], y0 = tg[1], cs = tg[2], sn = tg[3], c2 = tg[4], s2 = tg[5], h0 = tg[6];
+        const PlanFrame fr{tg[0], tg[1], tg[2], tg[3], tg[4], tg[5]};
+        const double h0 = tg[6];
         const double* o = vs + ((size_t)(g * 3 + k) * n) * 2;
 
         for (int i = lane; i < n; i += 64) {
             const double v = o[2 * i], s = o[2 * i + 1];
             const bool first = i == lane;
-            const double d = df * (first ? q_l : p.q[i]);
-            double x = x0 + s * cs, y = y0 + s * sn;            // :175-176
-            x = x + d * c2, y = y + d * s2;                     // :179-180
-            double hd = 0.0;
+            double x, y, hd = 0.0;
+            fr.point(s, df * (first ? q_l : p.q[i]), x, y);
             if (i < n - 1) {
-                const double s1 = o[2 * i + 3], d1 = df * (first ? q_l1 : p.q[i + 1]);
-                double x1 = x0 + s1 * cs, y1 = y0 + s1 * sn;
-                x1 = x1 + d1 * c2, y1 = y1 + d1 * s2;
+                double x1, y1;
+                fr.point(o[2 * i + 3], df * (first ? q_l1 : p.q[i + 1]), x1, y1);
                 hd = atan2_fast(y1 - y, x1 - x, p.atq);         // :188
             }
             double* w = stage + (size_t)i * 6;
@@ -339,38 +410,15 @@ __device__ __forceinline__ void plan_block_lists(const PlanParams& p, int f0, in
         for (int i = lane; i < n; i += 64) {
             double* w = stage + (size_t)i * 6;
             double curv = 0.0;
-            if (i > 0 && i < n - 1) {
-                const double hp = stage[(size_t)(i - 1) * 6 + 2];
-                curv = (w[2] - hp) / (w[3] * p.dt + 1e-6);      // :196
-                w[5] = curv;
-            }
+            if (i > 0 && i < n - 1) w[5] = curv = tile_curvature(stage, i, p.dt);
             curv_sum += p.w_curv * (curv * curv);               // :248
             const double x = w[0], y = w[1];
-            if (n_ref > 0) {                                    // :229-231
-                double md = INFINITY;
-                for (int r = 0; r < n_ref; ++r) {
-                    const double dx = ref[2 * r] - x, dy = ref[2 * r + 1] - y;
-                    const double dd = sqrt(dx * dx + dy * dy);
-                    md = dd < md ? dd : md;
-                }
-                lat_sum += p.w_lat * (md * md);
-            }
-            constexpr int OS = Lists::OSTRIDE;
-            for (int q = 0; q < n_obs; ++q) {                   // :253-259
-                double ox = obs[OS * q], oy = obs[OS * q + 1];
-                const double rad = obs[OS * q + 2];
-                if constexpr (Lists::MOVING) {                  // the disc where its velocity has carried it by this waypoint's time
-                    const double tw = w[4];
-                    ox = ox + obs[OS * q + 3] * tw, oy = oy + obs[OS * q + 4] * tw;
-                }
-                const double ex = x - ox, ey = y - oy;
-                const double dist = sqrt(ex * ex + ey * ey);
-                if (dist < rad * 2.0) obs_sum += 1000.0 * (rad * 2.0 - dist);
-                else if (dist < rad * 4.0) obs_sum += 10.0 / (dist - rad + 0.1);
-            }
+            if (n_ref > 0) lat_sum += ref_path_term(p.w_lat, ref, n_ref, x, y);
+            for (int q = 0; q < n_obs; ++q)
+                add_obstacle_penalty<Lists::MOVING>(obs_sum, obs + Lists::OSTRIDE * q, x, y, w[4]);
         }
         wave_lds_fence();
-        if (lane == 0) stage[(size_t)(n - 1) * 6 + 2] = n > 1 ? stage[(size_t)(n - 2) * 6 + 2] : h0;   // :190
+        if (lane == 0) tile_last_heading(stage, n, h0);
         curv_sum = wave_sum_dpp(curv_sum);
         if (extra) lat_sum = wave_sum_dpp(lat_sum), obs_sum = wave_sum_dpp(obs_sum);
         if (lane == 0) costs[g * C + c] = lat_sum, costs[CS + g * C + c] = curv_sum, costs[2 * CS + g * C + c] = obs_sum;
@@ -398,15 +446,7 @@ __device__ __forceinline__ void plan_block_lists(const PlanParams& p, int f0, in
     for (int idx = tid; idx < G * C; idx += NW * 64) {
         const int g = idx / C, c = idx - g * C, f = f0 + g;
         if (f >= n_states) continue;
-        const double* cc = costs + g * C;
-        const double mine = cc[c];
-        int rank = 0;
-        for (int o2 = 0; o2 < C; ++o2) {
-            const double v = cc[o2];
-            rank += (v < mine || (v == mine && o2 < c)) ? 1 : 0;
-        }
-        cost[(size_t)f * C + c] = mine;
-        order[(size_t)f * C + rank] = c;
+        rank_and_store(costs + g * C, C, c, f, cost, order);
     }
 }
 
@@ -427,10 +467,6 @@ __global__ void __launch_bounds__(NW * 64) planner_kernel(PlanParams p, int n_st
     plan_block_lists<G, NW, PlanNoHook, Lists>(p, blockIdx.x * G, n_states, state, lists, wp, cost, order, sm);
 }
 
-// Output ring of planner_wave_kernel: 256 units of 16 B.  It holds at most 63 carried units + one tile of
-// 3n <= 192 units; FPW*3*n <= 384 doubles of phase-1 scratch also fit.
-constexpr int RING_UNITS = 256, RING_DOUBLES = RING_UNITS * 2;
-
 // Throughput variant for large batches and n <= 64: every wave is autonomous (no workgroup barrier).
 // A wave owns FPW consecutive start states; lane = waypoint index, so the per-waypoint constants
 // (1-exp(-t_i), quintic blend, timestamp) sit in registers for the whole kernel.
@@ -446,8 +482,7 @@ __global__ void __launch_bounds__(256) planner_wave_kernel(PlanParams p, int n_s
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int n = p.n, C = p.C;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const size_t per_wave = (size_t)FPW * 3 * n * 2 + RING_DOUBLES + even_up(FPW * C) + FPW * 3 * 4 + FPW * 8;
-    double* vs = sm + wid * per_wave;                  // [FPW*3][n][2]  (v, s)
+    double* vs = sm + wid * wave_lds_doubles(FPW, n, C);                 // [FPW*3][n][2]  (v, s)
     double* stage = vs + (size_t)FPW * 3 * n * 2;      // output ring (256 x 16 B); phase 1: acc terms [FPW*3][n]
     double* costs = stage + RING_DOUBLES;              // [FPW][C]
     double* base = costs + even_up(FPW * C);           // [FPW*3][4]  S_v, S_a, running
@@ -483,11 +518,9 @@ __global__ void __launch_bounds__(256) planner_wave_kernel(PlanParams p, int n_s
             for (int k = 0; k < 3; ++k) {
                 const int pair = g * 3 + k;
                 const double v0 = st_v[g];
-                const double dv = (8.0 + 2.0 * (double)k) - v0;
-                const double v = v0 + dv * al_i;                       // :153-154
-                const double vp = v0 + dv * al_p;
-                const double a = (v - vp) / dtd_i;
-                const double acc = (lane > 0 && dtd_i > 0.0) ? p.w_acc * (a * a) : 0.0;   // :240-244
+                const double dv = target_speed(k) - v0;
+                const double v = blend_velocity(v0, dv, al_i);
+                const double acc = (lane > 0 && dtd_i > 0.0) ? acceleration_term(p.w_acc, v, blend_velocity(v0, dv, al_p), dtd_i) : 0.0;
                 if (in) {
                     vs[((size_t)pair * n + lane) * 2] = v;
                     stage[(size_t)pair * n + lane] = acc;
@@ -515,8 +548,7 @@ __global__ void __launch_bounds__(256) planner_wave_kernel(PlanParams p, int n_s
             const double v = o[2 * i];
             if (i > 0) s = s + v * p.dt;                               // :157
             o[2 * i + 1] = s;
-            const double e = v - 10.0;
-            sv = sv + p.w_vel * (e * e);                               // :236
+            sv = sv + velocity_term(p.w_vel, v);
         }
         double run = sv, sa = 0.0;
         for (int i = 1; i < n; ++i) {                                  // zero terms stand for skipped ones
@@ -547,7 +579,8 @@ __global__ void __launch_bounds__(256) planner_wave_kernel(PlanParams p, int n_s
     for (int g = 0; g < nf; ++g) {
         const int f = f0 + g;
         const double* tg = trig + g * 8;
-        const double x0 = tg[0], y0 = tg[1], cs = tg[2], sn = tg[3], c2 = tg[4], s2 = tg[5], h0 = tg[6];
+        const PlanFrame fr{tg[0], tg[1], tg[2], tg[3], tg[4], tg[5]};
+        const double h0 = tg[6];
         const PlanLists ls = lists.at(f);                            // this state's reference path and obstacles
         const double* ref = ls.ref;
         const double* obs = ls.obs;
@@ -561,8 +594,8 @@ __global__ void __launch_bounds__(256) planner_wave_kernel(PlanParams p, int n_s
             const double* o = vs + ((size_t)(g * 3 + k) * n) * 2;
             const double v = o[2 * li_c], s = o[2 * li_c + 1], s1 = o[2 * ln_c + 1];
             kv[k] = v;
-            kbx[k] = x0 + s * cs, kby[k] = y0 + s * sn;              // :175-176
-            kbx1[k] = x0 + s1 * cs, kby1[k] = y0 + s1 * sn;
+            fr.along(s, kbx[k], kby[k]);
+            fr.along(s1, kbx1[k], kby1[k]);
             kden[k] = v * p.dt + 1e-6;                               // :196 denominator
             krden[k] = 1.0 / kden[k];                                // shared by the n_lat trajectories of this speed
             const double* b = base + (g * 3 + k) * 4;
@@ -570,8 +603,9 @@ __global__ void __launch_bounds__(256) planner_wave_kernel(PlanParams p, int n_s
         }
         for (int li = 0; li < p.n_lat; ++li) {
             const double df = readlane_f64(lat_l, li);
-            const double d = df * q_i, d1 = df * q_n;
-            const double dxc = d * c2, dyc = d * s2, dxc1 = d1 * c2, dyc1 = d1 * s2;
+            double dxc, dyc, dxc1, dyc1;
+            fr.across(df * q_i, dxc, dyc);
+            fr.across(df * q_n, dxc1, dyc1);
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 const int c = li * 3 + k;
@@ -587,7 +621,7 @@ __global__ void __launch_bounds__(256) planner_wave_kernel(PlanParams p, int n_s
                     if (np > 2) r2 = ring[(u0 + 128) & (RING_UNITS - 1)];
                     wave_lds_fence();
                 }
-                const double x = bx + dxc, y = by + dyc;             // :179-180
+                const double x = bx + dxc, y = by + dyc;             // (PlanFrame::point, its two halves made above)
                 const double x1 = bx1 + dxc1, y1 = by1 + dyc1;
                 double hd = atan2_fast(y1 - y, x1 - x, p.atq);       // :188
                 const double hprev = dpp_mov_f64<0x138>(hd);         // lane i <- lane i-1
@@ -600,25 +634,12 @@ __global__ void __launch_bounds__(256) planner_wave_kernel(PlanParams p, int n_s
                 if (lane == n - 1) hd = n > 1 ? hprev : h0;          // :190
                 double lat_sum = 0.0, obs_sum = 0.0;
                 if (EXTRA && n_ref > 0) {
-                    double md = INFINITY;
-                    for (int r = 0; r < n_ref; ++r) {
-                        const double dx = ref[2 * r] - x, dy = ref[2 * r + 1] - y;
-                        const double dd = sqrt(dx * dx + dy * dy);
-                        md = dd < md ? dd : md;
-                    }
-                    lat_sum = wave_sum_dpp(in ? p.w_lat * (md * md) : 0.0);
+                    const double term = ref_path_term(p.w_lat, ref, n_ref, x, y);
+                    lat_sum = wave_sum_dpp(in ? term : 0.0);
                 }
                 if (EXTRA && n_obs > 0) {
-                    constexpr int OS = Lists::OSTRIDE;
-                    for (int q = 0; q < n_obs; ++q) {
-                        double ox = obs[OS * q], oy = obs[OS * q + 1];
-                        const double rad = obs[OS * q + 2];
-                        if constexpr (Lists::MOVING) ox = ox + obs[OS * q + 3] * t_i, oy = oy + obs[OS * q + 4] * t_i;
-                        const double ex = x - ox, ey = y - oy;
-                        const double dist = sqrt(ex * ex + ey * ey);
-                        if (dist < rad * 2.0) obs_sum += 1000.0 * (rad * 2.0 - dist);
-                        else if (dist < rad * 4.0) obs_sum += 10.0 / (dist - rad + 0.1);
-                    }
+                    for (int q = 0; q < n_obs; ++q)
+                        add_obstacle_penalty<Lists::MOVING>(obs_sum, obs + Lists::OSTRIDE * q, x, y, t_i);
                     obs_sum = wave_sum_dpp(in ? obs_sum : 0.0);
                 }
                 const double curv_sum = wave_sum_dpp(in ? p.w_curv * (curv * curv) : 0.0);
@@ -657,16 +678,8 @@ __global__ void __launch_bounds__(256) planner_wave_kernel(PlanParams p, int n_s
     wave_lds_fence();
     // ---- 3 -----------------------------------------------------------------------------------------
     for (int idx = lane; idx < nf * C; idx += 64) {
-        const int g = idx / C, c = idx - g * C, f = f0 + g;
-        const double* cc = costs + g * C;
-        const double mine = cc[c];
-        int rank = 0;
-        for (int o2 = 0; o2 < C; ++o2) {
-            const double vv = cc[o2];
-            rank += (vv < mine || (vv == mine && o2 < c)) ? 1 : 0;
-        }
-        cost[(size_t)f * C + c] = mine;
-        order[(size_t)f * C + rank] = c;
+        const int g = idx / C, c = idx - g * C;
+        rank_and_store(costs + g * C, C, c, f0 + g, cost, order);
     }
 }
 
@@ -685,37 +698,31 @@ __global__ void __launch_bounds__(64) planner_generate_kernel(PlanParams p, int 
         const double dv = vt - v0;
         double s = 0.0;
         for (int i = 0; i < n; ++i) {
-            const double v = v0 + dv * p.alpha[i];
+            const double v = blend_velocity(v0, dv, p.alpha[i]);
             if (i > 0) s = s + v * p.dt;
             vs[2 * i] = v, vs[2 * i + 1] = s;
         }
     }
     wave_lds_fence();
     const double hp2 = h0 + 1.5707963267948966;
-    const double cs = cos(h0), sn = sin(h0), c2 = cos(hp2), s2 = sin(hp2);
+    const PlanFrame fr{x0, y0, cos(h0), sin(h0), cos(hp2), sin(hp2)};
     for (int i = lane; i < n; i += 64) {
         const double v = vs[2 * i], s = vs[2 * i + 1];
-        const double d = df * p.q[i];
-        double x = x0 + s * cs, y = y0 + s * sn;
-        x = x + d * c2, y = y + d * s2;
-        double hd = 0.0;
+        double x, y, hd = 0.0;
+        fr.point(s, df * p.q[i], x, y);
         if (i < n - 1) {
-            const double s1 = vs[2 * i + 3], d1 = df * p.q[i + 1];
-            double x1 = x0 + s1 * cs, y1 = y0 + s1 * sn;
-            x1 = x1 + d1 * c2, y1 = y1 + d1 * s2;
-            hd = atan2(y1 - y, x1 - x);
+            double x1, y1;
+            fr.point(vs[2 * i + 3], df * p.q[i + 1], x1, y1);
+            hd = atan2(y1 - y, x1 - x);                         // (libm's here, atan2_fast in the plan kernels)
         }
         double* w = stage + (size_t)i * 6;
         w[0] = x, w[1] = y, w[2] = hd, w[3] = v, w[4] = p.t[i], w[5] = 0.0;
     }
     wave_lds_fence();
     for (int i = lane; i < n; i += 64)
-        if (i > 0 && i < n - 1) {
-            double* w = stage + (size_t)i * 6;
-            w[5] = (w[2] - stage[(size_t)(i - 1) * 6 + 2]) / (w[3] * p.dt + 1e-6);
-        }
+        if (i > 0 && i < n - 1) stage[(size_t)i * 6 + 5] = tile_curvature(stage, i, p.dt);
     wave_lds_fence();
-    if (lane == 0) stage[(size_t)(n - 1) * 6 + 2] = n > 1 ? stage[(size_t)(n - 2) * 6 + 2] : h0;
+    if (lane == 0) tile_last_heading(stage, n, h0);
     wave_lds_fence();
     double* dst = wp + (size_t)j * n * 6;
     for (int q = lane; q < n * 6; q += 64) dst[q] = stage[q];
@@ -736,39 +743,15 @@ __global__ void planner_evaluate_kernel(PlanParams p, int n_traj, int n_wp, cons
     const double* w = wp + (size_t)j * n_wp * 6;
     double c = 0.0;
     if (n_ref > 0)
-        for (int i = 0; i < n_wp; ++i) {
-            double md = INFINITY;
-            for (int r = 0; r < n_ref; ++r) {
-                const double dx = ref[2 * r] - w[6 * i], dy = ref[2 * r + 1] - w[6 * i + 1];
-                const double dd = sqrt(dx * dx + dy * dy);
-                md = dd < md ? dd : md;
-            }
-            c = c + p.w_lat * (md * md);
-        }
-    for (int i = 0; i < n_wp; ++i) {
-        const double e = w[6 * i + 3] - 10.0;
-        c = c + p.w_vel * (e * e);
-    }
+        for (int i = 0; i < n_wp; ++i) c = c + ref_path_term(p.w_lat, ref, n_ref, w[6 * i], w[6 * i + 1]);
+    for (int i = 0; i < n_wp; ++i) c = c + velocity_term(p.w_vel, w[6 * i + 3]);
     for (int i = 1; i < n_wp; ++i) {
         const double dtt = w[6 * i + 4] - w[6 * (i - 1) + 4];
-        if (dtt > 0.0) {
-            const double a = (w[6 * i + 3] - w[6 * (i - 1) + 3]) / dtt;
-            c = c + p.w_acc * (a * a);
-        }
+        if (dtt > 0.0) c = c + acceleration_term(p.w_acc, w[6 * i + 3], w[6 * (i - 1) + 3], dtt);
     }
     for (int i = 0; i < n_wp; ++i) c = c + p.w_curv * (w[6 * i + 5] * w[6 * i + 5]);
-    constexpr int OS = MOVING ? 5 : 3;
-    for (int q = 0; q < n_obs; ++q) {
-        const double ox = obs[OS * q], oy = obs[OS * q + 1], rad = obs[OS * q + 2];
-        for (int i = 0; i < n_wp; ++i) {
-            double px = ox, py = oy;
-            if constexpr (MOVING) px = ox + obs[OS * q + 3] * w[6 * i + 4], py = oy + obs[OS * q + 4] * w[6 * i + 4];
-            const double ex = w[6 * i] - px, ey = w[6 * i + 1] - py;
-            const double dist = sqrt(ex * ex + ey * ey);
-            if (dist < rad * 2.0) c = c + 1000.0 * (rad * 2.0 - dist);
-            else if (dist < rad * 4.0) c = c + 10.0 / (dist - rad + 0.1);
-        }
-    }
+    for (int q = 0; q < n_obs; ++q)                     // obstacle outer, every term straight into the running cost: the reference's order
+        for (int i = 0; i < n_wp; ++i) add_obstacle_penalty<MOVING>(c, obs + (MOVING ? 5 : 3) * q, w[6 * i], w[6 * i + 1], w[6 * i + 4]);
     cost[j] = c;
 }
 
@@ -786,55 +769,66 @@ static void fill_params(const av_ctx* ctx, PlanParams& p) {
 
 #ifndef AVHOT_DEVICE_ONLY      // (step.hip includes this file for its device code only)
 
-// The one launch plan of av_planner_plan, av_planner_plan_each and av_planner_plan_moving.  `extra`: a reference path and / or obstacles may take part in
-// the cost (the wave kernel's EXTRA form).
+// Every instantiation of the two plan kernels there is, per list type.  planner_plan finds its kernel here and nowhere else.
+// wave: planner_wave_kernel<G, extra> (G start states per wave, four waves); else planner_kernel<G, NW>.
+template <class Lists>
+struct PlanInst {
+    bool wave, extra;
+    int G, NW;
+    void (*fn)(PlanParams, int, const double*, Lists, double*, double*, int32_t*);
+};
+template <class Lists>
+const PlanInst<Lists> plan_insts[] = {
+    {false, false, 1, 8, planner_kernel<1, 8, Lists>}, {false, false, 1, 4, planner_kernel<1, 4, Lists>},
+    {false, false, 1, 2, planner_kernel<1, 2, Lists>}, {false, false, 2, 4, planner_kernel<2, 4, Lists>},
+    {false, false, 4, 4, planner_kernel<4, 4, Lists>}, {false, false, 8, 4, planner_kernel<8, 4, Lists>},
+    {true, false, 2, 4, planner_wave_kernel<2, false, Lists>}, {true, true, 2, 4, planner_wave_kernel<2, true, Lists>},
+};
+
+// Everything a launch of av_planner_plan, av_planner_plan_each and av_planner_plan_moving is decided by, decided in one place.
+template <class Lists>
+struct PlanLaunch {
+    const PlanInst<Lists>* inst;
+    unsigned grid, block;
+    size_t lds;                        // dynamic LDS bytes
+};
+// `extra`: a reference path and / or obstacles may take part in the cost (the wave kernel's EXTRA form).  The shape does not depend on
+// the list type.
+template <class Lists>
+static PlanLaunch<Lists> planner_plan(int n, int C, int n_states, bool extra) {
+    const bool wave = n <= 64 && n_states >= 1024;
+    int G, NW = 4;
+    size_t lds;
+    if (wave) {
+        // two states per wave (103-KB output regions); one per wave -- 51-KB regions, twice the waves -- measured the same
+        // (59.4-60.7 % of HBM peak at 16 384 states either way, alternating runs on one box)
+        G = 2;
+        lds = wave_lds_doubles(G, n, C) * NW * sizeof(double);
+    } else {
+        extra = false;                 // (the workgroup kernel has one form)
+        G = n_states >= 4096 ? 8 : (n_states >= 1024 ? 4 : (n_states >= 512 ? 2 : 1));
+        while (G > 1 && plan_lds_doubles(G, n, C, 4) * 8 > 48 * 1024) G >>= 1;
+        // one state per workgroup: its 3 C trajectories over eight waves, or four / two where eight per-wave tiles do not fit
+        // (two fit every configuration av_planner_configure accepts: n = 256, C = 192 needs 41.6 KB)
+        if (G == 1) NW = 8;
+        while (G == 1 && NW > 2 && plan_lds_doubles(1, n, C, NW) * 8 > 64 * 1024) NW >>= 1;
+        lds = plan_lds_doubles(G, n, C, NW) * 8;
+    }
+    const int per_group = wave ? G * NW : G;          // start states of a workgroup
+    PlanLaunch<Lists> p{nullptr, (unsigned)((n_states + per_group - 1) / per_group), (unsigned)NW * 64, lds};
+    for (const PlanInst<Lists>& k : plan_insts<Lists>)
+        if (k.wave == wave && k.extra == extra && k.G == G && k.NW == NW) p.inst = &k;
+    return p;
+}
+
 template <class Lists>
 static int plan_dispatch(av_ctx* ctx, hipStream_t st, int n_states, const double* state, const Lists& lists, bool extra,
                          double* waypoints, double* cost, int32_t* order, const char* who) {
-    const int n = ctx->n_points, C = ctx->n_cand;
+    const PlanLaunch<Lists> l = planner_plan<Lists>(ctx->n_points, ctx->n_cand, n_states, extra);
+    AV_REQUIRE(l.lds <= 64 * 1024, AV_EINVAL, "%s: configuration needs %zu B of LDS", who, l.lds);
     PlanParams p;
     fill_params(ctx, p);
-    if (n <= 64 && n_states >= 1024) {
-        // two states per wave (103-KB output regions); one per wave -- 51-KB regions, twice the waves -- measured the same
-        // (59.4-60.7 % of HBM peak at 16 384 states either way, alternating runs on one box)
-        constexpr int FPW = 2;
-        const size_t per_wave = (size_t)FPW * 3 * n * 2 + RING_DOUBLES + even_up(FPW * C) + FPW * 3 * 4 + FPW * 8;
-        const size_t lds_w = per_wave * 4 * sizeof(double);
-        if (lds_w <= 64 * 1024) {
-            const int grid_w = (n_states + 4 * FPW - 1) / (4 * FPW);
-            if (extra)
-                hipLaunchKernelGGL((planner_wave_kernel<FPW, true, Lists>), dim3(grid_w), dim3(256), lds_w, st, p, n_states, state,
-                                   lists, waypoints, cost, order);
-            else
-                hipLaunchKernelGGL((planner_wave_kernel<FPW, false, Lists>), dim3(grid_w), dim3(256), lds_w, st, p, n_states, state,
-                                   lists, waypoints, cost, order);
-            AV_LAUNCH_CHECK();
-            return AV_OK;
-        }
-    }
-    int G = n_states >= 4096 ? 8 : (n_states >= 1024 ? 4 : (n_states >= 512 ? 2 : 1));
-    while (G > 1 && plan_lds_doubles(G, n, C, 4) * 8 > 48 * 1024) G >>= 1;
-    // one state per workgroup: its 3 C trajectories over eight waves, or four / two where eight per-wave tiles do not fit
-    // (two fit every configuration av_planner_configure accepts: n = 256, C = 192 needs 41.6 KB)
-    int NW = G == 1 ? 8 : 4;
-    while (G == 1 && NW > 2 && plan_lds_doubles(1, n, C, NW) * 8 > 64 * 1024) NW >>= 1;
-    const size_t lds = plan_lds_doubles(G, n, C, NW) * 8;
-    AV_REQUIRE(lds <= 64 * 1024, AV_EINVAL, "%s: configuration needs %zu B of LDS", who, lds);
-    const int grid = (n_states + G - 1) / G;
-#define AV_PLAN_LAUNCH(GG, NWV)                                                                                          \
-    hipLaunchKernelGGL((planner_kernel<GG, NWV, Lists>), dim3(grid), dim3(NWV * 64), lds, st, p, n_states, state, lists, \
-                       waypoints, cost, order)
-    switch (G) {
-        case 8: AV_PLAN_LAUNCH(8, 4); break;
-        case 4: AV_PLAN_LAUNCH(4, 4); break;
-        case 2: AV_PLAN_LAUNCH(2, 4); break;
-        default:
-            if (NW == 8) AV_PLAN_LAUNCH(1, 8);
-            else if (NW == 4) AV_PLAN_LAUNCH(1, 4);
-            else AV_PLAN_LAUNCH(1, 2);
-            break;
-    }
-#undef AV_PLAN_LAUNCH
+    hipLaunchKernelGGL(l.inst->fn, dim3(l.grid), dim3(l.block), l.lds, st, p, n_states, state, lists, waypoints, cost, order);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }
@@ -953,6 +947,17 @@ int av_planner_dims(const av_ctx* ctx, int* n_points, int* n_candidates) {
     AV_REQUIRE(ctx && n_points && n_candidates, AV_EINVAL, "av_planner_dims: null argument");
     AV_REQUIRE(ctx->planner_ready, AV_ESTATE, "av_planner_dims: call av_planner_configure first");
     *n_points = ctx->n_points, *n_candidates = ctx->n_cand;
+    return AV_OK;
+}
+
+int av_planner_launch_shape(int n_points, int n_candidates, int n_states, int extra, int32_t out[4]) {
+    AV_REQUIRE(out, AV_EINVAL, "av_planner_launch_shape: null argument");
+    AV_REQUIRE(n_points >= 1 && n_points <= 256 && n_candidates >= 3 && n_candidates <= 192 && n_candidates % 3 == 0, AV_EINVAL,
+               "av_planner_launch_shape: %d waypoints, %d candidates: not a configuration av_planner_configure accepts", n_points,
+               n_candidates);
+    AV_REQUIRE(n_states > 0, AV_EINVAL, "av_planner_launch_shape: n_states must be > 0");
+    const PlanLaunch<PlanShared> l = planner_plan<PlanShared>(n_points, n_candidates, n_states, extra != 0);
+    out[0] = l.inst->wave, out[1] = l.inst->G, out[2] = l.inst->NW, out[3] = (int32_t)l.lds;
     return AV_OK;
 }
 

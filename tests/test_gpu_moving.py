@@ -19,6 +19,7 @@ import pytest
 
 from tests import moving_cases as M
 from tests import test_gpu_plan_each as E
+from tests._util import kernel_path
 from tests.moving_ref import MovingPlannerRef, margin_and_allowance, track_obstacles_moving
 from tests.test_gpu_planner import POOL, U, configure
 
@@ -27,9 +28,9 @@ OCAP, RCAP = E.OCAP, E.RCAP
 
 
 def test_shapes_reach_every_kernel_that_takes_a_list():
-    reached = {E.kernel_path(n, 3 * ns, S, True) for n, ns, S in M.SHAPES}
+    reached = {kernel_path(n, 3 * ns, S, True) for n, ns, S in M.SHAPES}
     assert reached == E.REQUIRED - {"wave"}, reached
-    assert [E.kernel_path(n, 3 * ns, S, True) for n, ns, S in M.SHAPES] == [
+    assert [kernel_path(n, 3 * ns, S, True) for n, ns, S in M.SHAPES] == [
         "block<1,8>", "block<1,4>", "block<1,2>", "block<2,4>", "block<4,4>", "block<8,4>", "wave+extra", "wave+extra", "block<1,8>"]
 
 
@@ -77,7 +78,7 @@ _IDS = ["n%d-ns%d-S%d" % c for c in M.SHAPES]
 @pytest.mark.parametrize("n,ns,S", M.SHAPES, ids=_IDS)
 def test_zero_velocity_is_the_static_planner_bit_for_bit(env, n, ns, S):
     torch = env[0]
-    print("n=%d C=%d n_states=%d -> %s" % (n, 3 * ns, S, E.kernel_path(n, 3 * ns, S, True)))
+    print("n=%d C=%d n_states=%d -> %s" % (n, 3 * ns, S, kernel_path(n, 3 * ns, S, True)))
     configure(env, n, ns)
     states_t = E._dev(env, POOL[np.arange(S) % U], torch.float64)
     for rs in (1, 4):

@@ -17,7 +17,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from tests._util import order_mismatch
+from tests._util import kernel_path, order_mismatch
 from tests.obstacles_ref import track_obstacles
 from tests.test_gpu_planner import CASES as PLAN_CASES, N_OF, OBS, POOL, REF2, U, check_state, configure
 
@@ -35,32 +35,6 @@ PATHS = [np.zeros((0, 2)), REF2, ARC, np.array([[3.0, 4.0]])]                   
 EACH_CASES = [(51, 7, 1), (51, 7, 5), (16, 2, 13), (65, 7, 3), (1, 7, 3), (151, 7, 3), (256, 64, 2), (51, 7, 513), (16, 2, 1023),
               (65, 2, 1025), (65, 1, 4097), (51, 7, 1025), (64, 7, 1027), (3, 2, 4099), (16, 64, 1024)]
 REQUIRED = {"block<1,8>", "block<1,4>", "block<1,2>", "block<2,4>", "block<4,4>", "block<8,4>", "wave", "wave+extra"}
-
-
-def _lds(G, n, C_, NW):
-    ev = lambda v: (v + 1) & ~1
-    return (G * 3 * n * 2 + ev(G * 9) + G * 8 + 3 * ev(G * C_) + NW * n * 6) * 8
-
-
-def kernel_path(n, C_, S, extra):
-    """The kernel plan_dispatch launches (planner.hip); extra: a list pointer is given (av_planner_plan: a list is)."""
-    if n <= 64 and S >= 1024:
-        return "wave+extra" if extra else "wave"
-    G = 8 if S >= 4096 else 4 if S >= 1024 else 2 if S >= 512 else 1
-    while G > 1 and _lds(G, n, C_, 4) > 48 * 1024:
-        G //= 2
-    NW = 8 if G == 1 else 4
-    while G == 1 and NW > 2 and _lds(1, n, C_, NW) > 64 * 1024:
-        NW //= 2
-    return "block<%d,%d>" % (G, NW)
-
-
-def test_cases_reach_every_kernel_path():
-    """The per-state call (list pointers given) and the shared calls it is compared with (with and without lists) reach all
-    eight kernels between them; the per-state call alone reaches every one that can take a list."""
-    each = {kernel_path(n, 3 * ns, S, True) for n, ns, S in EACH_CASES}
-    assert each == REQUIRED - {"wave"}, (each, REQUIRED)
-    assert REQUIRED <= each | {kernel_path(n, 3 * ns, S, False) for n, ns, S in EACH_CASES}
 
 
 @pytest.fixture(scope="module")

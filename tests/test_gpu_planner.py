@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from tests._util import order_mismatch
+from tests._util import kernel_path, order_mismatch
 
 pytestmark = pytest.mark.gpu
 
@@ -36,24 +36,6 @@ EXTRAS = {"none": (None, None), "ref2": (REF2, None), "reflong": (REFLONG, None)
 N_OF = {1: (0.5, 1.0), 2: (1.0, 1.0), 3: (2.0, 1.0), 16: (3.0, 0.2), 51: (5.0, 0.1), 63: (15.5, 0.25), 64: (15.75, 0.25),
         65: (16.0, 0.25), 66: (16.25, 0.25), 67: (16.5, 0.25), 101: (10.0, 0.1), 150: (14.9, 0.1), 151: (15.0, 0.1),
         256: (63.75, 0.25)}
-
-
-def _lds(G, n, C_, NW):
-    ev = lambda v: (v + 1) & ~1
-    return (G * 3 * n * 2 + ev(G * 9) + G * 8 + 3 * ev(G * C_) + NW * n * 6) * 8
-
-
-def kernel_path(n, C_, S, extra):
-    """The kernel av_planner_plan launches (planner.hip, av_planner_plan)."""
-    if n <= 64 and S >= 1024:
-        return "wave+extra" if extra else "wave"
-    G = 8 if S >= 4096 else 4 if S >= 1024 else 2 if S >= 512 else 1
-    while G > 1 and _lds(G, n, C_, 4) > 48 * 1024:
-        G //= 2
-    NW = 8 if G == 1 else 4
-    while G == 1 and NW > 2 and _lds(1, n, C_, NW) > 64 * 1024:
-        NW //= 2
-    return "block<%d,%d>" % (G, NW)
 
 
 # (n, num_samples, batch size, extras, compare waypoints of every k-th state)
@@ -167,14 +149,6 @@ def test_plan_matches_oracle(env, n, ns, S, ex, stride):
     # without waypoints: the same costs and order, bit for bit
     _, cost2, order2 = run_plan(env, n, ns, states, ex, wp=False)
     assert np.array_equal(cost2.cpu().numpy(), cost) and np.array_equal(order2.cpu().numpy(), order)
-
-
-def test_matrix_reaches_every_kernel_path():
-    reached = {kernel_path(n, 3 * ns, S, ex != "none") for n, ns, S, ex, _ in CASES}
-    assert REQUIRED <= reached, REQUIRED - reached
-    assert {"ref2", "reflong", "obs", "both"} <= {ex for n, ns, S, ex, _ in CASES if kernel_path(n, 3 * ns, S, True) == "wave+extra"}
-    for p in REQUIRED - {"wave", "wave+extra"}:
-        assert any(kernel_path(n, 3 * ns, S, True) == p and ex in ("obs", "both") for n, ns, S, ex, _ in CASES), p
 
 
 @pytest.mark.parametrize("n,ns,S,ex", [(51, 7, 1025, "none"), (51, 7, 1024, "both"), (64, 22, 1030, "none"), (16, 1, 3000, "obs")])
