@@ -384,10 +384,21 @@ typedef struct {
 size_t av_lane_workspace_bytes(int n_streams, int h, int w, int max_segments);
 int av_lane_workspace_init(av_ctx* ctx, av_stream_t stream, int n_streams, int h, int w, int max_segments,
                            void* workspace);
-/* Byte range of an intermediate inside the workspace (tests, visualisation):
- * 0 blurred u8[S][h][w], 1 NMS map, 2 Canny edges (only written when stages&1), 3 ROI-masked edges
- * (consumed by the Hough stage: lines it finds are erased), 4 thresholds double[S][4] (lo, hi, median),
- * 5 segments int32[S][max_segments][4], 6 segment counts int32[S], 7 Hough accumulator. */
+/* Byte range of an intermediate inside the workspace (tests, visualisation, the scene stage); `what` is one of: */
+#define AV_LANE_VIEW_BLUR 0         /* blurred u8[S][h][w]; widths that are multiples of 16 write it only with AV_LANE_KEEP_EDGES
+                                       (with AV_LANE_GIVEN_GRAY: the caller's gray image) */
+#define AV_LANE_VIEW_NMS 1          /* NMS map u8[S][h][w] */
+#define AV_LANE_VIEW_EDGES 2        /* Canny edges u8[S][h][w], only written with AV_LANE_KEEP_EDGES */
+#define AV_LANE_VIEW_MASKED 3       /* ROI-masked edges (consumed by the Hough stage: lines it finds are erased) */
+#define AV_LANE_VIEW_THRESHOLDS 4   /* double[S][4]: lo, hi, median, spare */
+#define AV_LANE_VIEW_SEGMENTS 5     /* int32[S][max_segments][4] */
+#define AV_LANE_VIEW_NSEG 6         /* segment counts int32[S] */
+#define AV_LANE_VIEW_ACCUM 7        /* Hough accumulator */
+#define AV_LANE_VIEW_HOUGH_PATH 8   /* int32[S], after the Hough stage: the kernel that made the frame's segments -- 1 the
+                                       theta-sharded kernel, 2 the single-workgroup kernel, 3 the generic kernel */
+#define AV_LANE_VIEW_POINTS 9       /* uint32[S][h*w], after the pixel stages: frame s's ROI edge points x | y << 16, row-major,
+                                       from [s][0] (the Hough stage reorders them) */
+#define AV_LANE_VIEW_NPOINTS 10     /* point counts int32[S] */
 int av_lane_workspace_view(int what, int n_streams, int h, int w, int max_segments, size_t* offset,
                            size_t* bytes);
 /*   bgr        u8 [S][h][w][3]
@@ -397,14 +408,20 @@ int av_lane_workspace_view(int what, int n_streams, int h, int w, int max_segmen
  *   pts        int32 [S][2][50][2]
  *   info       int32 [S][8]    valid_left valid_right n_left_segments n_right_segments n_segments n_points lo hi
  *   conf       double [S][2]   min(1, n_side_segments / 10)
- *   stages     bit0: also write the pre-ROI Canny edge map (view 2); bit1: stop after the pixel stages
- *              (no Hough, no fit); bit2: reserved, ignored; bit3: Hough by the generic PPHT kernel alone, then the
- *              fit (no theta-sharded or single-workgroup LDS kernel; the Hough kernels' test hook); bit4: skip the pixel stages and run Hough + fit on what the last bit1 call left
- *              in the workspace -- the two halves of a frame can then be enqueued apart, e.g. the Hough half beside
- *              the next frame's LDS-free kernels (it holds most of a CU's LDS); bit5 (with bit4): fit only, on the
- *              segment list already in the workspace (views 5 / 6) -- a test hook for the least-squares stage; bit6: Canny of
- *              the u8 image the caller left in view 0 (no gray / blur / median) with the thresholds it left in view 4
- *              (lo, hi as doubles), then the ROI and compaction as usual (the scene stage: full-frame roi_rows) */
+ *   stages     0 = the whole chain, or a sum of the AV_LANE_* bits below */
+#define AV_LANE_KEEP_EDGES 1        /* also write the pre-ROI Canny edge map (view 2) */
+#define AV_LANE_PIXELS_ONLY 2       /* stop after the pixel stages (no Hough, no fit): the point lists stay in the workspace */
+#define AV_LANE_RESERVED 4          /* ignored */
+#define AV_LANE_GENERIC_HOUGH 8     /* Hough by the generic PPHT kernel alone, then the fit (no theta-sharded or single-workgroup
+                                       LDS kernel): the Hough kernels' test hook */
+#define AV_LANE_HOUGH_ONLY 16       /* skip the pixel stages and run Hough + fit on what the last AV_LANE_PIXELS_ONLY call left in
+                                       the workspace -- the two halves of a frame can then be enqueued apart, e.g. the Hough half
+                                       beside the next frame's LDS-free kernels (it holds most of a CU's LDS) */
+#define AV_LANE_FIT_ONLY 32         /* (with AV_LANE_HOUGH_ONLY) fit only, on the segment list already in the workspace (views
+                                       5 / 6): a test hook for the least-squares stage */
+#define AV_LANE_GIVEN_GRAY 64       /* Canny of the u8 image the caller left in view 0 (no gray / blur / median) with the thresholds
+                                       it left in view 4 (lo, hi as doubles), then the ROI and compaction as usual (the scene
+                                       stage: full-frame roi_rows) */
 int av_lane_detect(av_ctx* ctx, av_stream_t stream, const av_lane_cfg* cfg, int n_streams, int h, int w,
                    const uint8_t* bgr, const int32_t* roi_rows, void* workspace, double* lane_state,
                    double* poly, int32_t* pts, int32_t* info, double* conf, int stages);

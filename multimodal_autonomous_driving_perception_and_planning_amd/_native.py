@@ -72,6 +72,11 @@ SCENE_ROW_FIELDS = [("gray_sum", "<u8"), ("green_count", "<u8"), ("lap_sum", "<i
 SCENE_ROW_BYTES = 240
 SCENE_CAT_TRAFFIC, SCENE_CAT_VEHICLE, SCENE_CAT_PEDESTRIAN = 1, 2, 4
 TAGLOG_CHUNK = 1024
+# av_lane_detect's `stages` bits and av_lane_workspace_view's view ids (AV_LANE_* of include/avhot.h)
+LANE_KEEP_EDGES, LANE_PIXELS_ONLY, LANE_RESERVED, LANE_GENERIC_HOUGH = 1, 2, 4, 8
+LANE_HOUGH_ONLY, LANE_FIT_ONLY, LANE_GIVEN_GRAY = 16, 32, 64
+(LANE_VIEW_BLUR, LANE_VIEW_NMS, LANE_VIEW_EDGES, LANE_VIEW_MASKED, LANE_VIEW_THRESHOLDS, LANE_VIEW_SEGMENTS, LANE_VIEW_NSEG,
+ LANE_VIEW_ACCUM, LANE_VIEW_HOUGH_PATH, LANE_VIEW_POINTS, LANE_VIEW_NPOINTS) = range(11)
 TAGLOG_STATS_FIELDS = [("tag_count", "<i8", (64,)), ("n_frames", "<i8"), ("n_maneuver", "<i8"), ("risk_count", "<i8", (4,)),
                        ("speed_min", "<f8"), ("speed_max", "<f8"), ("speed_sum", "<f8")]
 TAGLOG_STATS_BYTES = 584

@@ -155,7 +155,7 @@ __global__ void __launch_bounds__(256) thresholds_kernel(int h, int w, unsigned*
     }
 }
 
-// stages bit 6: the caller wrote the u8 image (view 0) and the thresholds (view 4); clears what thresholds_kernel would have
+// AV_LANE_GIVEN_GRAY: the caller wrote the u8 image (view 0) and the thresholds (view 4); clears what thresholds_kernel would have
 __global__ void __launch_bounds__(256) given_clear_kernel(int h, unsigned* __restrict__ hist, int* __restrict__ rowcnt,
                                                           int* __restrict__ npts, int* __restrict__ nseg) {
     const int s = blockIdx.x, tid = threadIdx.x;
@@ -277,7 +277,7 @@ __global__ void __launch_bounds__(256) ccl_merge_kernel(const uint8_t* __restric
 struct Roi {
     int x0, x1, x2, x3, yt;
 };
-__device__ __forceinline__ void roi_bounds(const Roi& r, int h, int y, const int* rows, int& xl, int& xr) {
+__host__ __device__ __forceinline__ void roi_bounds(const Roi& r, int h, int y, const int* rows, int& xl, int& xr) {
     if (rows) { xl = rows[2 * y], xr = rows[2 * y + 1]; return; }
     if (y < r.yt || y >= h) { xl = 1, xr = 0; return; }
     const long long den = h - r.yt, t = h - y;
@@ -1580,7 +1580,7 @@ __device__ __noinline__ void houghp_fast_body(int h, int w, int numrho, HoughCfg
                                                    const unsigned* __restrict__ nz_all, const int* __restrict__ npts,
                                                    int* __restrict__ accum_all, const float* __restrict__ trig,
                                                    int* __restrict__ segs, int* __restrict__ nseg,
-                                                   int* __restrict__ fallback, int check_flag, int* __restrict__ path) {
+                                                   int* __restrict__ fallback, int* __restrict__ path) {
     __shared__ unsigned nz[NZCAP];
     __shared__ unsigned bm[BMWORDS];
     __shared__ int fifo[FIFO];             // points drawn from the list but not voted yet (ring buffer)
@@ -1597,7 +1597,7 @@ __device__ __noinline__ void houghp_fast_body(int h, int w, int numrho, HoughCfg
     // the flag is both this kernel's input (1: houghp_shard gave the frame up) and its verdict for houghp_kernel, written
     // by thread 0 below: every thread must branch on the value read BEFORE that write, so it goes through LDS
     __shared__ int sh_skip;
-    if (tid == 0) sh_skip = (check_flag && fallback[s] == 0) ? 1 : 0;
+    if (tid == 0) sh_skip = fallback[s] == 0 ? 1 : 0;
     __syncthreads();
     if (sh_skip) return;                                        // already done by houghp_shard
     const int total = npts[s];
@@ -2520,19 +2520,18 @@ __device__ void lane_fit_one(int s, int side, int h, int w, int max_segments, do
     conf[(size_t)s * 2 + side] = fmin(1.0, (double)nl / 10.0);          // :172
 }
 
-// one wave per (stream, side): lane 0 does the fit, then lane k makes point k of the 50
-__global__ void __launch_bounds__(64) lane_fit_kernel(int S, int h, int w, int max_segments, double smoothing, const int* __restrict__ segs,
-                                const int* __restrict__ nseg, double* __restrict__ lane_state,
-                                double* __restrict__ poly, int* __restrict__ pts, int* __restrict__ info,
-                                double* __restrict__ conf, const double* __restrict__ thr, const int* __restrict__ npts) {
-    const int id = blockIdx.x, lane = threadIdx.x;
-    if (id >= S * 2) return;
-    const int s = id >> 1, side = id & 1;
-    __shared__ double coef[4];                                           // c2 c1 c0 valid
-    if (lane == 0) coef[3] = 0.0;
-    if (lane == 0) lane_fit_one(s, side, h, w, max_segments, smoothing, segs, nseg, lane_state, poly, info, conf, thr, npts, coef);
+// One wave per (stream, side), `on` for the waves that have a side: lane 0 fits it into the shared coef[4] (c2 c1 c0 valid),
+// workgroup barrier (every wave of the workgroup calls this), then lane k makes point k of the 50.
+__device__ __forceinline__ void lane_fit_tail(bool on, int s, int side, int lane, double* coef, int h, int w, int max_segments, double smoothing,
+                                              const int* __restrict__ segs, const int* __restrict__ nseg, double* __restrict__ lane_state,
+                                              double* __restrict__ poly, int* __restrict__ pts, int* __restrict__ info,
+                                              double* __restrict__ conf, const double* __restrict__ thr, const int* __restrict__ npts) {
+    if (on && lane == 0) {
+        coef[3] = 0.0;
+        lane_fit_one(s, side, h, w, max_segments, smoothing, segs, nseg, lane_state, poly, info, conf, thr, npts, coef);
+    }
     __syncthreads();
-    if (coef[3] == 0.0 || lane >= 50) return;
+    if (!on || coef[3] == 0.0 || lane >= 50) return;
     // np.linspace(h*0.6, h, 50); np.polyval (Horner); astype(int32) truncates toward zero
     const double c2 = coef[0], c1 = coef[1], c0 = coef[2];
     const double ya = (double)h * 0.6, yb = (double)h, step = (yb - ya) / 49.0;
@@ -2542,7 +2541,17 @@ __global__ void __launch_bounds__(64) lane_fit_kernel(int S, int h, int w, int m
     pp[2 * lane] = (int)x, pp[2 * lane + 1] = (int)y;
 }
 
-// the generic PPHT kernel alone (stage bit 3: tests of the fallback chain)
+__global__ void __launch_bounds__(64) lane_fit_kernel(int S, int h, int w, int max_segments, double smoothing, const int* __restrict__ segs,
+                                const int* __restrict__ nseg, double* __restrict__ lane_state,
+                                double* __restrict__ poly, int* __restrict__ pts, int* __restrict__ info,
+                                double* __restrict__ conf, const double* __restrict__ thr, const int* __restrict__ npts) {
+    const int id = blockIdx.x, lane = threadIdx.x;
+    if (id >= S * 2) return;
+    __shared__ double coef[4];
+    lane_fit_tail(true, id >> 1, id & 1, lane, coef, h, w, max_segments, smoothing, segs, nseg, lane_state, poly, pts, info, conf, thr, npts);
+}
+
+// the generic PPHT kernel alone (AV_LANE_GENERIC_HOUGH: tests of the fallback chain)
 __global__ void __launch_bounds__(192) houghp_kernel(uint8_t* __restrict__ masked, int h, int w, int numrho, HoughCfg cfg,
                                                      unsigned* __restrict__ nz_all, const int* __restrict__ npts, int* __restrict__ accum_all,
                                                      const float* __restrict__ trig, int* __restrict__ segs, int* __restrict__ nseg,
@@ -2556,77 +2565,243 @@ __global__ void __launch_bounds__(192) houghp_kernel(uint8_t* __restrict__ maske
 __global__ void __launch_bounds__(192) hough_tail_kernel(uint8_t* __restrict__ masked, int h, int w, int numrho, HoughCfg cfg,
                                                          unsigned* __restrict__ nz_all, const int* __restrict__ npts, int* __restrict__ accum_all,
                                                          const float* __restrict__ trig, int* __restrict__ segs, int* __restrict__ nseg,
-                                                         int* __restrict__ fallback, int* __restrict__ path, int check_flag, int rebuild_mask,
+                                                         int* __restrict__ fallback, int* __restrict__ path, int rebuild_mask,
                                                          int max_segments, double smoothing, double* __restrict__ lane_state,
                                                          double* __restrict__ poly, int* __restrict__ pts, int* __restrict__ info,
                                                          double* __restrict__ conf, const double* __restrict__ thr) {
-    houghp_fast_body(h, w, numrho, cfg, nz_all, npts, accum_all, trig, segs, nseg, fallback, check_flag, path);
+    houghp_fast_body(h, w, numrho, cfg, nz_all, npts, accum_all, trig, segs, nseg, fallback, path);
     __threadfence();
     __syncthreads();
     houghp_generic_body(masked, h, w, numrho, cfg, nz_all, npts, accum_all, trig, segs, nseg, fallback, path, rebuild_mask);
     __threadfence();
     __syncthreads();
-    const int s = blockIdx.x, side = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    __shared__ double coef2[2][4];                                       // c2 c1 c0 valid, per side
-    if (side < 2 && lane == 0) {
-        coef2[side][3] = 0.0;
-        lane_fit_one(s, side, h, w, max_segments, smoothing, segs, nseg, lane_state, poly, info, conf, thr, npts, coef2[side]);
-    }
-    __syncthreads();
-    if (side >= 2 || coef2[side][3] == 0.0 || lane >= 50) return;
-    const double c2 = coef2[side][0], c1 = coef2[side][1], c0 = coef2[side][2];
-    const double ya = (double)h * 0.6, yb = (double)h, step = (yb - ya) / 49.0;
-    int* pp = pts + ((size_t)s * 2 + side) * 100;
-    const double y = lane == 49 ? yb : (double)lane * step + ya;
-    const double x = (c2 * y + c1) * y + c0;
-    pp[2 * lane] = (int)x, pp[2 * lane + 1] = (int)y;
+    const int side = threadIdx.x >> 6;                                   // waves 0 and 1 take a side each, wave 2 only the barrier
+    __shared__ double coef2[2][4];
+    lane_fit_tail(side < 2, blockIdx.x, side, threadIdx.x & 63, coef2[side & 1], h, w, max_segments, smoothing, segs, nseg, lane_state, poly,
+                  pts, info, conf, thr, npts);
 }
 
-struct LaneCtx {
-    float* d_trig = nullptr;
-    int* d_roi = nullptr;           // default trapezoid's [xl, xr] per row for frames of roi_h x roi_w (the bit-map resolve path)
-    int roi_h = 0, roi_w = 0;
-};
-
-// ---- what one av_lane_detect call runs, decided from its shape and stage bits alone --------------------------------------------
+// ---- what one av_lane_detect call runs, decided from its shape, its stage bits and the two test hooks in the environment ----------
 enum class Front {
     Fused,              // front_pack: one pass BGR -> non-maximum-suppressed magnitudes (the hysteresis pass applies the thresholds)
     Stream,             // two passes, streaming kernels (w % 4 == 0): gray_blur_hist_stream, thresholds_kernel, sobel_nms_stream
     Generic,            // two passes, LDS tiles: gray_blur_hist_kernel, thresholds_kernel, sobel_nms_kernel
-    GivenStream,        // stage bit 6: u8 image and thresholds already in views 0 / 4, then sobel_nms_stream
-    GivenGeneric,       //              ... then sobel_nms_kernel
+    GivenStream,        // AV_LANE_GIVEN_GRAY: u8 image and thresholds already in views 0 / 4, then sobel_nms_stream
+    GivenGeneric,       //                     ... then sobel_nms_kernel
+};
+enum class Hough {
+    None,               // AV_LANE_PIXELS_ONLY
+    Sharded,            // houghp_shard, then hough_tail_kernel: the single-workgroup and the generic PPHT for the frames left over, and the fit
+    Generic,            // AV_LANE_GENERIC_HOUGH: houghp_kernel alone, then lane_fit_kernel
+    FitOnly,            // AV_LANE_FIT_ONLY: lane_fit_kernel on the segments in the workspace
 };
 struct LanePlan {
+    bool pixels;        // the pixel stages run (no AV_LANE_HOUGH_ONLY)
     Front front;
     int frows;          // band height of front_pack
+    bool keep_edges;    // AV_LANE_KEEP_EDGES: the pre-ROI edge map (view 2) and the blurred image (view 0) are written
     bool tiled;         // tiled hysteresis + chunk-box resolve / compaction (w % 16 == 0, 16-byte aligned buffers)
     bool bitpath;       // the ROI is resolved through the bit maps: no masked byte map (the generic Hough kernel rebuilds it)
     Roi roi;            // the default trapezoid, lane_detector.py:55-60
     int bx0, by0, bcw, bch;             // chunk box the resolve / compaction passes visit: first chunk column, first row, chunks, rows
+    Hough hough;
+    bool clear_exchange;                // the compaction pass also clears houghp_shard's exchange words and the fallback flags (else: hough_prep_kernel)
+    int spin, drop_frame;               // houghp_shard: bound of every exchange spin; frame whose last shard withholds a word (-1: none)
 };
 
 LanePlan lane_plan(int stages, int S, int h, int w, const void* bgr, const void* ws, const int32_t* roi_rows) {
     LanePlan p{};
+    p.pixels = !(stages & AV_LANE_HOUGH_ONLY), p.keep_edges = (stages & AV_LANE_KEEP_EDGES) != 0;
     const bool aligned = (((size_t)bgr | (size_t)ws) & 15) == 0;
     p.tiled = (w % 16 == 0) && w >= 32 && aligned && (long long)h * (w >> 4) < (1ll << 24);     // chunk_xy's exact range
     const bool streamp = (w % 4 == 0) && w >= 8 && aligned;
-    if (stages & 64) p.front = streamp ? Front::GivenStream : Front::GivenGeneric;
+    if (stages & AV_LANE_GIVEN_GRAY) p.front = streamp ? Front::GivenStream : Front::GivenGeneric;
     else p.front = p.tiled ? Front::Fused : (streamp ? Front::Stream : Front::Generic);
     // a few frames per launch (the per-frame class calls): short bands, so that a frame is hundreds of waves instead of 96
-    p.frows = (stages & 1) ? 72 : (S <= 8 ? 15 : 48);
+    p.frows = p.keep_edges ? 72 : (S <= 8 ? 15 : 48);
     p.roi.x0 = (int)(w * 0.1), p.roi.x1 = (int)(w * 0.4), p.roi.x2 = (int)(w * 0.6), p.roi.x3 = (int)(w * 0.9);
     p.roi.yt = (int)(h * 0.6);
-    // the debug edge map (bit 0) or a caller-defined ROI: every chunk, byte-map resolve; else the default trapezoid's bounding
-    // box (rows yt .. h-1, columns x0 .. x3).  Bit 0 concerns the pixel stages only: a Hough-only call (bit 4) follows a
+    // the debug edge map or a caller-defined ROI: every chunk, byte-map resolve; else the default trapezoid's bounding
+    // box (rows yt .. h-1, columns x0 .. x3).  AV_LANE_KEEP_EDGES concerns the pixel stages only: a Hough-only call follows a
     // production pixel call of the same shape and takes that call's decision.
     p.bx0 = 0, p.by0 = 0, p.bcw = w >> 4, p.bch = h;
-    const bool trapezoid = p.tiled && !roi_rows && (!(stages & 1) || (stages & 16));
+    const bool trapezoid = p.tiled && !roi_rows && (!p.keep_edges || !p.pixels);
     if (trapezoid) {
         p.by0 = p.roi.yt < h ? p.roi.yt : h - 1, p.bch = h - p.by0;
         p.bx0 = p.roi.x0 >> 4, p.bcw = (((p.roi.x3 < w ? p.roi.x3 : w - 1) >> 4) - p.bx0) + 1;
     }
     p.bitpath = trapezoid && p.roi.yt < h && (h - p.roi.yt) <= CB_ROWS;
+    p.hough = (stages & AV_LANE_PIXELS_ONLY) ? Hough::None : (stages & AV_LANE_FIT_ONLY) ? Hough::FitOnly
+              : (stages & AV_LANE_GENERIC_HOUGH) ? Hough::Generic : Hough::Sharded;
+    // The fallback flags overlay the first S row counters of frame 0: the compaction pass may clear them only when those lie above
+    // the box rows it reads.  (Decided from the stage bits as it always was: a fit-only call that runs the pixel stages clears too.)
+    p.clear_exchange = p.pixels && p.bitpath && !(stages & (AV_LANE_PIXELS_ONLY | AV_LANE_GENERIC_HOUGH)) && S <= p.by0;
+    // test hooks, read per call (tests/test_gpu_bench_sizes.py changes them between calls on one context)
+    const char *sp = getenv("AVHOT_HOUGH_SPIN"), *dr = getenv("AVHOT_HOUGH_DROP");
+    p.spin = sp && atoi(sp) > 0 ? atoi(sp) : HS_SPIN;
+    p.drop_frame = dr ? atoi(dr) : -1;
     return p;
+}
+
+struct LaneCtx {                    // per-context device tables
+    float* d_trig = nullptr;
+    int* d_roi = nullptr;           // default trapezoid's [xl, xr] per row for frames of roi_h x roi_w (the bit-map resolve path)
+    int roi_h = 0, roi_w = 0;
+
+    // trig table of cv::HoughLinesProbabilistic: theta is a float, angles n*theta in double
+    int trig_table() {
+        if (d_trig) return AV_OK;
+        float tt[2 * NUMANGLE];
+        const float theta = (float)(3.14159265358979323846 / 180.0);
+        for (int n = 0; n < NUMANGLE; ++n) {
+            tt[2 * n] = (float)(std::cos((double)n * theta) * 1.0f);
+            tt[2 * n + 1] = (float)(std::sin((double)n * theta) * 1.0f);
+        }
+        AV_HIP(hipMalloc(&d_trig, sizeof(tt)));
+        AV_HIP(hipMemcpy(d_trig, tt, sizeof(tt), hipMemcpyHostToDevice));
+        return AV_OK;
+    }
+    // the default trapezoid's inclusive column range per row (rows above it: empty)
+    int roi_table(const Roi& roi, int h, int w) {
+        if (d_roi && roi_h == h && roi_w == w) return AV_OK;
+        std::vector<int> tab(2 * (size_t)h);
+        for (int y = 0; y < h; ++y) roi_bounds(roi, h, y, nullptr, tab[2 * y], tab[2 * y + 1]);
+        if (d_roi) AV_HIP(hipFree(d_roi));
+        d_roi = nullptr;
+        AV_HIP(hipMalloc(&d_roi, tab.size() * sizeof(int)));
+        AV_HIP(hipMemcpy(d_roi, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
+        roi_h = h, roi_w = w;
+        return AV_OK;
+    }
+};
+
+struct LaneBufs {                   // the workspace's arrays (lane_layout)
+    uint8_t *blur, *map, *edges, *masked;
+    unsigned *labels, *hist, *nz, *tedge, *rbits, *kbits;
+    double* thr;
+    int *rowcnt, *npts, *accum, *segs, *nseg, numrho;
+    LaneBufs(const LaneWs& L, unsigned char* ws)
+        : blur(ws + L.blur), map(ws + L.map), edges(ws + L.edges), masked(ws + L.masked), labels((unsigned*)(ws + L.labels)),
+          hist((unsigned*)(ws + L.hist)), nz((unsigned*)(ws + L.nz)), tedge((unsigned*)(ws + L.tedge)), rbits((unsigned*)(ws + L.rbits)),
+          kbits((unsigned*)(ws + L.kbits)), thr((double*)(ws + L.thr)), rowcnt((int*)(ws + L.rowcnt)), npts((int*)(ws + L.npts)),
+          accum((int*)(ws + L.accum)), segs((int*)(ws + L.segs)), nseg((int*)(ws + L.nseg)), numrho(L.numrho) {}
+};
+
+// ---- the pixel stages: BGR (or the given gray image) -> row-major list of the ROI's edge points --------------------------------
+int launch_pixels(const LanePlan& P, const LaneCtx& lc, hipStream_t st, int S, int h, int w, const uint8_t* bgr,
+                  const int32_t* roi_rows, const LaneBufs& B) {
+    const bool fused = P.front == Front::Fused, given = P.front == Front::GivenStream || P.front == Front::GivenGeneric;
+    const bool streamk = P.front == Front::Stream || P.front == Front::GivenStream;
+    const dim3 sgrid((((w + SW - 1) / SW) * ((h + SROWS - 1) / SROWS) + 3) / 4, 1, S);      // streaming kernels: waves = strips x bands
+    const dim3 tiles((w + TW - 1) / TW, (h + TH - 1) / TH, S);
+    if (fused) {
+        // front_pack's per-lane offsets are 32-bit: a batch whose BGR spans 2^32 bytes or more runs in groups of frames
+        // (one frame always fits: h, w < 32768)
+        const size_t fpx = (size_t)h * w;
+        const int group = (int)(0xFFFFFFFFull / (fpx * 3));
+        for (int s0 = 0; s0 < S; s0 += group) {
+            const int n = S - s0 < group ? S - s0 : group;
+            // work geometry of front_pack: full strips of 62 chunks, the remainder chunks of G frames share one wave
+            FrontGeo g{};
+            const int C = w >> 2;
+            g.S = n, g.nb = (h + P.frows - 1) / P.frows, g.nfull = C / 62, g.rem = C - 62 * g.nfull;
+            g.G = g.rem ? 64 / (g.rem + 2) : 0;
+            if (g.G > 16) g.G = 16;
+            g.nc = g.G > 6 ? g.G : 6;                              // 6 KB of LDS per wave: 26 waves fit a CU
+            const int ngr = g.G ? (n + g.G - 1) / g.G : 0;
+            const dim3 pgrid((unsigned)(n * g.nb * g.nfull + ngr * g.nb));      // one wave per workgroup
+            const uint8_t* gb = bgr + s0 * fpx * 3;
+            uint8_t *gl = B.blur + s0 * fpx, *gm = B.map + s0 * fpx;
+            unsigned* gh = B.hist + (size_t)s0 * 256;
+            const auto front = P.keep_edges ? front_pack<true, 72> : (P.frows == 48 ? front_pack<false, 48> : front_pack<false, 15>);
+            hipLaunchKernelGGL(front, pgrid, dim3(64), (size_t)g.nc * 1024, st, gb, h, w, g, gl, gm, gh);
+            AV_LAUNCH_CHECK();
+        }
+    } else if (!given) {            // two passes with the blurred image in memory between them
+        if (streamk) hipLaunchKernelGGL(gray_blur_hist_stream, sgrid, dim3(256), 0, st, bgr, h, w, B.blur, B.hist);
+        else hipLaunchKernelGGL(gray_blur_hist_kernel, tiles, dim3(256), 0, st, bgr, h, w, B.blur, B.hist);
+        AV_LAUNCH_CHECK();
+    }
+    if (given) hipLaunchKernelGGL(given_clear_kernel, dim3(S), dim3(256), 0, st, h, B.hist, B.rowcnt, B.npts, B.nseg);
+    else hipLaunchKernelGGL(thresholds_kernel, dim3(S), dim3(256), 0, st, h, w, B.hist, B.thr, B.rowcnt, B.npts, B.nseg);
+    AV_LAUNCH_CHECK();
+    if (!fused) {
+        if (streamk) hipLaunchKernelGGL(sobel_nms_stream, sgrid, dim3(256), 0, st, B.blur, h, w, B.thr, B.map, B.labels);
+        else hipLaunchKernelGGL(sobel_nms_kernel, tiles, dim3(256), 0, st, B.blur, h, w, B.thr, B.map, B.labels);
+        AV_LAUNCH_CHECK();
+    }
+    uint8_t* edges = P.keep_edges ? B.edges : nullptr;
+    if (!P.tiled) {
+        hipLaunchKernelGGL(ccl_merge_kernel, dim3((w + 63) / 64, (h + 3) / 4, S), dim3(256), 0, st, B.map, h, w, B.labels);
+        AV_LAUNCH_CHECK();
+        hipLaunchKernelGGL(finalize_kernel, dim3((w + 1023) / 1024, h, S), dim3(256), 0, st, B.map, h, w, B.labels, P.roi, roi_rows, edges,
+                           B.masked, B.rowcnt);
+        AV_LAUNCH_CHECK();
+        hipLaunchKernelGGL(compact_kernel, dim3(h, S), dim3(256), 0, st, B.masked, h, w, B.rowcnt, B.nz, B.npts);
+        AV_LAUNCH_CHECK();
+        return AV_OK;
+    }
+    // default ROI, no debug edge map (bitpath): the tile pass leaves the ROI's candidates as one bit per pixel of the ROI's chunk box
+    // and the resolve / compaction passes work on bit maps
+    const BitBox bb = P.bitpath ? BitBox{P.bx0, P.by0, P.bcw, P.bch, (P.bcw + 1) / 2} : BitBox{0, 0, 0, 0, 0};
+    const int* rt = P.bitpath ? lc.d_roi : nullptr;
+    const dim3 tgrid((w + CT_C - 1) / CT_C, ((h + CT_R - 1) / CT_R + CT_STACK - 1) / CT_STACK, S);
+    hipLaunchKernelGGL(fused ? ccl_tile_kernel<true> : ccl_tile_kernel<false>, tgrid, dim3(256), 0, st, B.map, h, w, B.thr, B.labels, B.tedge,
+                       rt, (uint16_t*)B.rbits, bb);
+    const int nbh = (h - 1) / CT_R, nbv = (w - 1) / CT_C, span = (w > h ? w : h);
+    if (nbh + nbv > 0) {
+        const dim3 bgrid((span + 255) / 256, nbh + nbv, S);
+        hipLaunchKernelGGL(ccl_border_kernel, bgrid, dim3(256), 0, st, h, w, nbh, B.tedge, (int)tgrid.x, (int)tgrid.y, B.labels);
+    }
+    AV_LAUNCH_CHECK();
+    const dim3 ngrid(((unsigned)P.bch * (unsigned)P.bcw + 256 * FCK - 1) / (256 * FCK), S);
+    if (P.bitpath)
+        hipLaunchKernelGGL(resolve_bits_kernel, dim3(((unsigned)(bb.bch * bb.pw) + 255) / 256, S), dim3(256), 0, st, h, w, B.labels, B.rbits,
+                           B.kbits, B.rowcnt, bb);
+    else
+        hipLaunchKernelGGL(fused ? finalize_fast<true> : finalize_fast<false>, ngrid, dim3(256), 0, st, B.map, h, w, B.thr, B.labels, P.roi,
+                           roi_rows, edges, B.masked, B.rowcnt, P.bx0, P.by0, P.bcw, P.bch);
+    AV_LAUNCH_CHECK();
+    if (P.bch <= CB_ROWS)
+        hipLaunchKernelGGL(compact_box_kernel, dim3(S, 4), dim3(1024), (size_t)P.bch * sizeof(int), st, B.masked, h, w, B.rowcnt, B.nz, B.npts,
+                           P.bx0, P.by0, P.bcw, P.bch, P.bitpath ? B.kbits : nullptr, bb.pw, P.clear_exchange ? B.accum : nullptr,
+                           (size_t)NUMANGLE * B.numrho, 8 * HG, B.rowcnt);
+    else hipLaunchKernelGGL(compact_kernel, dim3(h, S), dim3(256), 0, st, B.masked, h, w, B.rowcnt, B.nz, B.npts);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
+// ---- the Hough stage: point lists -> segments -> fits --------------------------------------------------------------------------
+int launch_hough(const LanePlan& P, const LaneCtx& lc, hipStream_t st, const av_lane_cfg& cfg, int S, int h, int w, const LaneBufs& B,
+                 double* lane_state, double* poly, int32_t* pts, int32_t* info, double* conf) {
+    if (P.hough == Hough::None) return AV_OK;
+    const HoughCfg hc{cfg.hough_threshold, cfg.min_line_length, cfg.max_line_gap, cfg.max_segments};
+    const int rebuild = P.bitpath ? 1 : 0;      // no masked byte map: the generic Hough kernel rebuilds it from the point list
+    int* fb = B.rowcnt;             // the per-row counters are dead after compaction: their first S words are the fallback flags,
+    int* hpath = B.rowcnt + S;      // the next S say which kernel made a frame's segments (view 8)
+    if (P.hough == Hough::Sharded) {
+        if (!P.clear_exchange) {
+            hipLaunchKernelGGL(hough_prep_kernel, dim3((S * 8 * HG + 255) / 256), dim3(256), 0, st, S, B.numrho, B.accum, fb);
+            AV_LAUNCH_CHECK();
+        }
+        hipLaunchKernelGGL(houghp_shard, dim3(S * HG), dim3((HVW + 1) * 64), 0, st, h, w, B.numrho, hc, B.nz, B.npts, B.accum, lc.d_trig,
+                           B.segs, B.nseg, fb, P.spin, P.drop_frame, hpath);
+        AV_LAUNCH_CHECK();
+        hipLaunchKernelGGL(hough_tail_kernel, dim3(S), dim3(192), 0, st, B.masked, h, w, B.numrho, hc, B.nz, B.npts, B.accum, lc.d_trig,
+                           B.segs, B.nseg, fb, hpath, rebuild, cfg.max_segments, cfg.smoothing_factor, lane_state, poly, pts, info, conf,
+                           B.thr);
+        AV_LAUNCH_CHECK();
+        return AV_OK;
+    }
+    if (P.hough == Hough::Generic) {
+        hipLaunchKernelGGL(houghp_kernel, dim3(S), dim3(192), 0, st, B.masked, h, w, B.numrho, hc, B.nz, B.npts, B.accum, lc.d_trig, B.segs,
+                           B.nseg, (const int*)nullptr, hpath, rebuild);
+        AV_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(lane_fit_kernel, dim3(S * 2), dim3(64), 0, st, S, h, w, cfg.max_segments, cfg.smoothing_factor, B.segs, B.nseg,
+                       lane_state, poly, pts, info, conf, B.thr, B.npts);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
 }
 
 }  // namespace
@@ -2654,17 +2829,17 @@ int av_lane_workspace_view(int what, int n_streams, int h, int w, int max_segmen
     const LaneWs L = lane_layout(n_streams, h, w, max_segments);
     const size_t px = (size_t)n_streams * h * w;
     switch (what) {
-        case 0: *offset = L.blur, *bytes = px; break;
-        case 1: *offset = L.map, *bytes = px; break;
-        case 2: *offset = L.edges, *bytes = px; break;
-        case 3: *offset = L.masked, *bytes = px; break;
-        case 4: *offset = L.thr, *bytes = (size_t)n_streams * 32; break;
-        case 5: *offset = L.segs, *bytes = (size_t)n_streams * max_segments * 16; break;
-        case 6: *offset = L.nseg, *bytes = (size_t)n_streams * 4; break;
-        case 7: *offset = L.accum, *bytes = (size_t)n_streams * NUMANGLE * L.numrho * 4; break;
-        case 8: *offset = L.rowcnt + (size_t)n_streams * 4, *bytes = (size_t)n_streams * 4; break;     // Hough kernel taken per frame
-        case 9: *offset = L.nz, *bytes = px * 4; break;                      // point lists: frame s at [s * h * w], x | y << 16, row-major
-        case 10: *offset = L.npts, *bytes = (size_t)n_streams * 4; break;
+        case AV_LANE_VIEW_BLUR: *offset = L.blur, *bytes = px; break;
+        case AV_LANE_VIEW_NMS: *offset = L.map, *bytes = px; break;
+        case AV_LANE_VIEW_EDGES: *offset = L.edges, *bytes = px; break;
+        case AV_LANE_VIEW_MASKED: *offset = L.masked, *bytes = px; break;
+        case AV_LANE_VIEW_THRESHOLDS: *offset = L.thr, *bytes = (size_t)n_streams * 32; break;
+        case AV_LANE_VIEW_SEGMENTS: *offset = L.segs, *bytes = (size_t)n_streams * max_segments * 16; break;
+        case AV_LANE_VIEW_NSEG: *offset = L.nseg, *bytes = (size_t)n_streams * 4; break;
+        case AV_LANE_VIEW_ACCUM: *offset = L.accum, *bytes = (size_t)n_streams * NUMANGLE * L.numrho * 4; break;
+        case AV_LANE_VIEW_HOUGH_PATH: *offset = L.rowcnt + (size_t)n_streams * 4, *bytes = (size_t)n_streams * 4; break;
+        case AV_LANE_VIEW_POINTS: *offset = L.nz, *bytes = px * 4; break;
+        case AV_LANE_VIEW_NPOINTS: *offset = L.npts, *bytes = (size_t)n_streams * 4; break;
         default: av_set_error("av_lane_workspace_view: unknown view %d", what); return AV_EINVAL;
     }
     return AV_OK;
@@ -2680,201 +2855,23 @@ int av_lane_workspace_init(av_ctx* ctx, av_stream_t stream, int n_streams, int h
 int av_lane_detect(av_ctx* ctx, av_stream_t stream, const av_lane_cfg* cfg, int n_streams, int h, int w,
                    const uint8_t* bgr, const int32_t* roi_rows, void* workspace, double* lane_state, double* poly,
                    int32_t* pts, int32_t* info, double* conf, int stages) {
-    AV_REQUIRE(ctx && cfg && bgr && workspace && lane_state && poly && pts && info && conf, AV_EINVAL,
-               "av_lane_detect: null argument");
+    AV_REQUIRE(ctx && cfg && bgr && workspace && lane_state && poly && pts && info && conf, AV_EINVAL, "av_lane_detect: null argument");
     AV_REQUIRE(n_streams > 0 && h >= 8 && w >= 8 && h < 32768 && w < 32768, AV_EINVAL, "av_lane_detect: bad frame size %dx%d", w, h);
     AV_REQUIRE(cfg->max_segments > 0 && cfg->hough_threshold > 0, AV_EINVAL, "av_lane_detect: bad configuration");
     AV_REQUIRE((size_t)h * w < (1u << 31), AV_EINVAL, "av_lane_detect: frame too large for 31-bit labels");
-    hipStream_t st = as_stream(stream);
     if (!ctx->lane) {
-        // trig table of cv::HoughLinesProbabilistic: theta is a float, angles n*theta in double
-        LaneCtx* lc = new (std::nothrow) LaneCtx();
-        AV_REQUIRE(lc, AV_ENOMEM, "av_lane_detect: out of host memory");
-        float tt[2 * NUMANGLE];
-        const float theta = (float)(3.14159265358979323846 / 180.0);
-        for (int n = 0; n < NUMANGLE; ++n) {
-            tt[2 * n] = (float)(std::cos((double)n * theta) * 1.0f);
-            tt[2 * n + 1] = (float)(std::sin((double)n * theta) * 1.0f);
-        }
-        AV_HIP(hipMalloc(&lc->d_trig, sizeof(tt)));
-        AV_HIP(hipMemcpy(lc->d_trig, tt, sizeof(tt), hipMemcpyHostToDevice));
-        ctx->lane = lc;
+        ctx->lane = new (std::nothrow) LaneCtx();
+        AV_REQUIRE(ctx->lane, AV_ENOMEM, "av_lane_detect: out of host memory");
     }
     LaneCtx* lc = (LaneCtx*)ctx->lane;
-    const LaneWs L = lane_layout(n_streams, h, w, cfg->max_segments);
-    unsigned char* ws = (unsigned char*)workspace;
-    uint8_t* blur = ws + L.blur;
-    uint8_t* map = ws + L.map;
-    unsigned* labels = (unsigned*)(ws + L.labels);
-    uint8_t* edges = ws + L.edges;
-    uint8_t* masked = ws + L.masked;
-    unsigned* hist = (unsigned*)(ws + L.hist);
-    double* thr = (double*)(ws + L.thr);
-    int* rowcnt = (int*)(ws + L.rowcnt);
-    unsigned* nz = (unsigned*)(ws + L.nz);
-    int* npts = (int*)(ws + L.npts);
-    int* accum = (int*)(ws + L.accum);
-    int* segs = (int*)(ws + L.segs);
-    int* nseg = (int*)(ws + L.nseg);
-    unsigned* tedge = (unsigned*)(ws + L.tedge);
-    unsigned* rbits = (unsigned*)(ws + L.rbits);
-    unsigned* kbits = (unsigned*)(ws + L.kbits);
     const LanePlan P = lane_plan(stages, n_streams, h, w, bgr, workspace, roi_rows);
-    bool prepped = false;            // the compaction pass cleared the sharded Hough kernel's exchange words and fallback flags
-    const char* shard_env = getenv("AVHOT_HOUGH_SHARD");
-    const bool use_shard = !(stages & 8) && !(shard_env && atoi(shard_env) == 0);      // AVHOT_HOUGH_SHARD=0 skips the sharded kernel
-    if (!(stages & 16)) {                                          // bit 4: Hough + fit only, on the point lists already in the workspace
-        const bool fused = P.front == Front::Fused;
-        if (fused) {
-            // front_pack's per-lane offsets are 32-bit: a batch whose BGR spans 2^32 bytes or more runs in groups of frames
-            // (one frame always fits: h, w < 32768)
-            const size_t fpx = (size_t)h * w;
-            const int group = (int)(0xFFFFFFFFull / (fpx * 3));
-            for (int s0 = 0; s0 < n_streams; s0 += group) {
-                const int n = n_streams - s0 < group ? n_streams - s0 : group;
-                // work geometry of front_pack: full strips of 62 chunks, the remainder chunks of G frames share one wave
-                FrontGeo g{};
-                const int C = w >> 2;
-                g.S = n, g.nb = (h + P.frows - 1) / P.frows, g.nfull = C / 62, g.rem = C - 62 * g.nfull;
-                g.G = g.rem ? 64 / (g.rem + 2) : 0;
-                if (g.G > 16) g.G = 16;
-                g.nc = g.G > 6 ? g.G : 6;                              // 6 KB of LDS per wave: 26 waves fit a CU
-                const int ngr = g.G ? (n + g.G - 1) / g.G : 0;
-                const dim3 pgrid((unsigned)(n * g.nb * g.nfull + ngr * g.nb));      // one wave per workgroup
-                const size_t lds = (size_t)g.nc * 1024;
-                const uint8_t* gb = bgr + s0 * fpx * 3;
-                uint8_t *gl = blur + s0 * fpx, *gm = map + s0 * fpx;
-                unsigned* gh = hist + (size_t)s0 * 256;
-                if (stages & 1) hipLaunchKernelGGL((front_pack<true, 72>), pgrid, dim3(64), lds, st, gb, h, w, g, gl, gm, gh);
-                else if (P.frows == 48) hipLaunchKernelGGL((front_pack<false, 48>), pgrid, dim3(64), lds, st, gb, h, w, g, gl, gm, gh);
-                else hipLaunchKernelGGL((front_pack<false, 15>), pgrid, dim3(64), lds, st, gb, h, w, g, gl, gm, gh);
-                AV_LAUNCH_CHECK();
-            }
-            hipLaunchKernelGGL(thresholds_kernel, dim3(n_streams), dim3(256), 0, st, h, w, hist, thr, rowcnt, npts, nseg);
-            AV_LAUNCH_CHECK();
-        } else {
-            // two passes with the blurred image in memory between them
-            const bool streamk = P.front == Front::Stream || P.front == Front::GivenStream;
-            const dim3 sgrid((((w + SW - 1) / SW) * ((h + SROWS - 1) / SROWS) + 3) / 4, 1, n_streams);      // waves = strips x bands
-            const dim3 tiles((w + TW - 1) / TW, (h + TH - 1) / TH, n_streams);
-            if (P.front == Front::GivenStream || P.front == Front::GivenGeneric) {
-                hipLaunchKernelGGL(given_clear_kernel, dim3(n_streams), dim3(256), 0, st, h, hist, rowcnt, npts, nseg);
-            } else {
-                if (streamk) hipLaunchKernelGGL(gray_blur_hist_stream, sgrid, dim3(256), 0, st, bgr, h, w, blur, hist);
-                else hipLaunchKernelGGL(gray_blur_hist_kernel, tiles, dim3(256), 0, st, bgr, h, w, blur, hist);
-                AV_LAUNCH_CHECK();
-                hipLaunchKernelGGL(thresholds_kernel, dim3(n_streams), dim3(256), 0, st, h, w, hist, thr, rowcnt, npts, nseg);
-            }
-            AV_LAUNCH_CHECK();
-            if (streamk) hipLaunchKernelGGL(sobel_nms_stream, sgrid, dim3(256), 0, st, blur, h, w, thr, map, labels);
-            else hipLaunchKernelGGL(sobel_nms_kernel, tiles, dim3(256), 0, st, blur, h, w, thr, map, labels);
-            AV_LAUNCH_CHECK();
-        }
-        BitBox bb{0, 0, 0, 0, 0};
-        if (P.tiled) {
-            // default ROI, no debug edge map: the tile pass leaves the ROI's candidates as one bit per pixel of the ROI's chunk box and
-            // the resolve / compaction passes work on bit maps
-            if (P.bitpath) {
-                if (!lc->d_roi || lc->roi_h != h || lc->roi_w != w) {
-                    const Roi& roi = P.roi;
-                    std::vector<int> tab(2 * (size_t)h);
-                    for (int y = 0; y < h; ++y) {
-                        int xl = 1, xr = 0;
-                        if (y >= roi.yt) {                             // roi_bounds' arithmetic
-                            const long long den = h - roi.yt, t = h - y;
-                            xl = (int)((2 * (roi.x0 * den + (long long)(roi.x1 - roi.x0) * t) + den) / (2 * den));
-                            xr = (int)((2 * (roi.x3 * den + (long long)(roi.x2 - roi.x3) * t) + den) / (2 * den));
-                        }
-                        tab[2 * y] = xl, tab[2 * y + 1] = xr;
-                    }
-                    if (lc->d_roi) AV_HIP(hipFree(lc->d_roi));
-                    lc->d_roi = nullptr;
-                    AV_HIP(hipMalloc(&lc->d_roi, tab.size() * sizeof(int)));
-                    AV_HIP(hipMemcpy(lc->d_roi, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
-                    lc->roi_h = h, lc->roi_w = w;
-                }
-                bb = BitBox{P.bx0, P.by0, P.bcw, P.bch, (P.bcw + 1) / 2};
-            }
-            const dim3 tgrid((w + CT_C - 1) / CT_C, ((h + CT_R - 1) / CT_R + CT_STACK - 1) / CT_STACK, n_streams);
-            const int* rt = P.bitpath ? lc->d_roi : nullptr;
-            if (fused) hipLaunchKernelGGL(ccl_tile_kernel<true>, tgrid, dim3(256), 0, st, map, h, w, thr, labels, tedge, rt, (uint16_t*)rbits, bb);
-            else hipLaunchKernelGGL(ccl_tile_kernel<false>, tgrid, dim3(256), 0, st, map, h, w, thr, labels, tedge, rt, (uint16_t*)rbits, bb);
-            const int nbh = (h - 1) / CT_R, nbv = (w - 1) / CT_C, span = (w > h ? w : h);
-            if (nbh + nbv > 0) {
-                const dim3 bgrid((span + 255) / 256, nbh + nbv, n_streams);
-                hipLaunchKernelGGL(ccl_border_kernel, bgrid, dim3(256), 0, st, h, w, nbh, tedge, (int)tgrid.x, (int)tgrid.y, labels);
-            }
-            AV_LAUNCH_CHECK();
-            const unsigned fchunks = (unsigned)P.bch * (unsigned)P.bcw;
-            const dim3 ngrid((fchunks + 256 * FCK - 1) / (256 * FCK), n_streams);
-            if (P.bitpath)
-                hipLaunchKernelGGL(resolve_bits_kernel, dim3(((unsigned)(bb.bch * bb.pw) + 255) / 256, n_streams), dim3(256), 0, st, h, w,
-                                   labels, rbits, kbits, rowcnt, bb);
-            else if (fused)
-                hipLaunchKernelGGL(finalize_fast<true>, ngrid, dim3(256), 0, st, map, h, w, thr, labels, P.roi, roi_rows,
-                                   (stages & 1) ? edges : nullptr, masked, rowcnt, P.bx0, P.by0, P.bcw, P.bch);
-            else
-                hipLaunchKernelGGL(finalize_fast<false>, ngrid, dim3(256), 0, st, map, h, w, thr, labels, P.roi, roi_rows,
-                                   (stages & 1) ? edges : nullptr, masked, rowcnt, P.bx0, P.by0, P.bcw, P.bch);
-        } else {
-            hipLaunchKernelGGL(ccl_merge_kernel, dim3((w + 63) / 64, (h + 3) / 4, n_streams), dim3(256), 0, st, map, h, w, labels);
-            AV_LAUNCH_CHECK();
-            hipLaunchKernelGGL(finalize_kernel, dim3((w + 1023) / 1024, h, n_streams), dim3(256), 0, st, map, h, w, labels, P.roi,
-                               roi_rows, (stages & 1) ? edges : nullptr, masked, rowcnt);
-        }
-        AV_LAUNCH_CHECK();
-        // (the fallback flags overlay the first n_streams row counters of frame 0: cleared by this pass only when those lie above the
-        // box rows it reads, and only when the Hough stage follows in this call)
-        const bool prep_here = P.bitpath && use_shard && !(stages & 2) && n_streams <= P.by0;
-        if (P.tiled && P.bch <= CB_ROWS)
-            hipLaunchKernelGGL(compact_box_kernel, dim3(n_streams, 4), dim3(1024), (size_t)P.bch * sizeof(int), st, masked, h, w,
-                               rowcnt, nz, npts, P.bx0, P.by0, P.bcw, P.bch, P.bitpath ? kbits : nullptr, bb.pw,
-                               prep_here ? accum : nullptr, (size_t)NUMANGLE * L.numrho, 8 * HG, rowcnt);
-        else hipLaunchKernelGGL(compact_kernel, dim3(h, n_streams), dim3(256), 0, st, masked, h, w, rowcnt, nz, npts);
-        AV_LAUNCH_CHECK();
-        prepped = prep_here;
-    }
-    if (stages & 2) return AV_OK;                                  // pixel stages only (tests, profiling)
-    HoughCfg hc{cfg->hough_threshold, cfg->min_line_length, cfg->max_line_gap, cfg->max_segments};
-    if (stages & 32) {                                             // bit 5 (with bit 4): fit only, on the segments in the workspace
-        hipLaunchKernelGGL(lane_fit_kernel, dim3(n_streams * 2), dim3(64), 0, st, n_streams, h, w, cfg->max_segments,
-                           cfg->smoothing_factor, segs, nseg, lane_state, poly, pts, info, conf, thr, npts);
-        AV_LAUNCH_CHECK();
-        return AV_OK;
-    }
-    const bool rebuild = P.bitpath;     // no masked byte map: the generic Hough kernel rebuilds it from the point list
-    int* fb = rowcnt;       // the per-row counters are dead after compaction: their first n_streams words are the fallback flags,
-    int* hpath = rowcnt + n_streams;   // the next n_streams say which kernel made a frame's segments (1 shard, 2 fast, 3 generic)
-    const bool use_fast = !(stages & 8);
-    if (use_fast) {
-        // theta-sharded LDS variant first (4 workgroups per frame); frames it cannot hold, or where a partner did not
-        // show up in time, are flagged for houghp_fast, and what that cannot hold for houghp_kernel.
-        // AVHOT_HOUGH_SHARD=0 skips the first stage.
-        if (use_shard) {
-            if (!prepped) {
-                hipLaunchKernelGGL(hough_prep_kernel, dim3((n_streams * 8 * HG + 255) / 256), dim3(256), 0, st, n_streams, L.numrho, accum, fb);
-                AV_LAUNCH_CHECK();
-            }
-            const char* sp = getenv("AVHOT_HOUGH_SPIN");
-            const char* dr = getenv("AVHOT_HOUGH_DROP");
-            const int spin = sp && atoi(sp) > 0 ? atoi(sp) : HS_SPIN;
-            hipLaunchKernelGGL(houghp_shard, dim3(n_streams * HG), dim3((HVW + 1) * 64), 0, st, h, w, L.numrho, hc, nz, npts, accum,
-                               lc->d_trig, segs, nseg, fb, spin, dr ? atoi(dr) : -1, hpath);
-            AV_LAUNCH_CHECK();
-        }
-        hipLaunchKernelGGL(hough_tail_kernel, dim3(n_streams), dim3(192), 0, st, masked, h, w, L.numrho, hc, nz, npts, accum, lc->d_trig,
-                           segs, nseg, fb, hpath, use_shard ? 1 : 0, rebuild ? 1 : 0, cfg->max_segments, cfg->smoothing_factor, lane_state,
-                           poly, pts, info, conf, thr);
-        AV_LAUNCH_CHECK();
-        return AV_OK;
-    }
-    hipLaunchKernelGGL(houghp_kernel, dim3(n_streams), dim3(192), 0, st, masked, h, w, L.numrho, hc, nz, npts, accum,
-                       lc->d_trig, segs, nseg, use_fast ? fb : nullptr, hpath, rebuild ? 1 : 0);
-    AV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(lane_fit_kernel, dim3(n_streams * 2), dim3(64), 0, st, n_streams, h, w,
-                       cfg->max_segments, cfg->smoothing_factor, segs, nseg, lane_state, poly, pts, info, conf, thr, npts);
-    AV_LAUNCH_CHECK();
-    return AV_OK;
+    int rc = lc->trig_table();
+    if (!rc && P.pixels && P.bitpath) rc = lc->roi_table(P.roi, h, w);
+    if (rc) return rc;
+    const LaneBufs B(lane_layout(n_streams, h, w, cfg->max_segments), (unsigned char*)workspace);
+    hipStream_t st = as_stream(stream);
+    if (P.pixels && (rc = launch_pixels(P, *lc, st, n_streams, h, w, bgr, roi_rows, B))) return rc;
+    return launch_hough(P, *lc, st, *cfg, n_streams, h, w, B, lane_state, poly, pts, info, conf);
 }
 
 }  // extern "C"

@@ -12,10 +12,10 @@
 //   scene_front    ONE read of the BGR frame: gray into the lane workspace (view 0), gray sum, HSV green count
 //                  (OpenCV's RGB2HSV_b fixed-point arithmetic), sum and sum of squares of the 3x3 Laplacian
 //                  (BORDER_REFLECT_101) -- exact integers combined with atomics, so the order does not matter
-//   lane chain     av_lane_detect stages bit 6 | bit 1: Canny (Sobel, NMS, union-find hysteresis) of that gray image,
+//   lane chain     av_lane_detect, AV_LANE_GIVEN_GRAY | AV_LANE_PIXELS_ONLY: Canny (Sobel, NMS, union-find hysteresis) of that gray image,
 //                  full-frame ROI, row-major edge point list
 //   scene_center   edge points inside the centre third (read before the PPHT, which reorders the point list)
-//   lane chain     av_lane_detect stages bit 4: the PPHT with the scene's settings into the segment list
+//   lane chain     av_lane_detect, AV_LANE_HOUGH_ONLY: the PPHT with the scene's settings into the segment list
 //   scene_decide   one thread per stream: line statistics (np.mean in NumPy's pairwise order), scores and rules
 #include "common.h"
 
@@ -371,12 +371,12 @@ int av_scene_classify(av_ctx* ctx, av_stream_t stream, int n_streams, int h, int
     unsigned char* lws = ws + L.lane;
     size_t off_gray, off_thr, off_nz, off_npts, off_segs, off_nseg, nb;
     int rc;
-    if ((rc = av_lane_workspace_view(0, n_streams, h, w, max_segments, &off_gray, &nb)) ||
-        (rc = av_lane_workspace_view(4, n_streams, h, w, max_segments, &off_thr, &nb)) ||
-        (rc = av_lane_workspace_view(9, n_streams, h, w, max_segments, &off_nz, &nb)) ||
-        (rc = av_lane_workspace_view(10, n_streams, h, w, max_segments, &off_npts, &nb)) ||
-        (rc = av_lane_workspace_view(5, n_streams, h, w, max_segments, &off_segs, &nb)) ||
-        (rc = av_lane_workspace_view(6, n_streams, h, w, max_segments, &off_nseg, &nb)))
+    if ((rc = av_lane_workspace_view(AV_LANE_VIEW_BLUR, n_streams, h, w, max_segments, &off_gray, &nb)) ||
+        (rc = av_lane_workspace_view(AV_LANE_VIEW_THRESHOLDS, n_streams, h, w, max_segments, &off_thr, &nb)) ||
+        (rc = av_lane_workspace_view(AV_LANE_VIEW_POINTS, n_streams, h, w, max_segments, &off_nz, &nb)) ||
+        (rc = av_lane_workspace_view(AV_LANE_VIEW_NPOINTS, n_streams, h, w, max_segments, &off_npts, &nb)) ||
+        (rc = av_lane_workspace_view(AV_LANE_VIEW_SEGMENTS, n_streams, h, w, max_segments, &off_segs, &nb)) ||
+        (rc = av_lane_workspace_view(AV_LANE_VIEW_NSEG, n_streams, h, w, max_segments, &off_nseg, &nb)))
         return rc;
     unsigned long long* stats = (unsigned long long*)(ws + L.stats);
     int* roi = (int*)(ws + L.roi);
@@ -392,11 +392,14 @@ int av_scene_classify(av_ctx* ctx, av_stream_t stream, int n_streams, int h, int
     int32_t* pts = (int32_t*)(ws + L.pts);
     int32_t* info = (int32_t*)(ws + L.info);
     double* conf = (double*)(ws + L.conf);
-    if ((rc = av_lane_detect(ctx, stream, &lc, n_streams, h, w, bgr, roi, lws, lstate, poly, pts, info, conf, 64 | 2))) return rc;
+    if ((rc = av_lane_detect(ctx, stream, &lc, n_streams, h, w, bgr, roi, lws, lstate, poly, pts, info, conf,
+                             AV_LANE_GIVEN_GRAY | AV_LANE_PIXELS_ONLY)))
+        return rc;
     hipLaunchKernelGGL(scene_center_kernel, dim3(n_streams, 8), dim3(256), 0, st, h, w, (const unsigned*)(lws + off_nz),
                        (const int*)(lws + off_npts), stats);
     AV_LAUNCH_CHECK();
-    if ((rc = av_lane_detect(ctx, stream, &lc, n_streams, h, w, bgr, roi, lws, lstate, poly, pts, info, conf, 16))) return rc;
+    if ((rc = av_lane_detect(ctx, stream, &lc, n_streams, h, w, bgr, roi, lws, lstate, poly, pts, info, conf, AV_LANE_HOUGH_ONLY)))
+        return rc;
     hipLaunchKernelGGL(scene_decide_kernel, dim3((n_streams + 63) / 64), dim3(64), 0, st, n_streams, h, w, max_segments, stats,
                        (const int*)(lws + off_segs), (const int*)(lws + off_nseg), det_n, det_cls, max_det, cat, n_cat, speed, lanes,
                        lane_info, lane_poly, (int*)state, rows);

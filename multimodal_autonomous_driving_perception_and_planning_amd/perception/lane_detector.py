@@ -93,6 +93,7 @@ class LaneDetector:
         self._shape = (h, w)
 
     def _view(self, what, dtype, shape):
+        """Workspace view `what` (nat.LANE_VIEW_*) of the last frame as a host array."""
         h, w = self._shape
         off, nb = C.c_size_t(), C.c_size_t()
         nat.check(self._dev.lib.av_lane_workspace_view(what, 1, h, w, self.MAX_SEGMENTS, C.byref(off), C.byref(nb)))
@@ -100,6 +101,7 @@ class LaneDetector:
         return raw.view(dtype).reshape(shape)
 
     def _run(self, frame, stages=0):
+        """stages: 0 = the whole chain, or a sum of nat.LANE_* bits."""
         frame = np.ascontiguousarray(frame, np.uint8)
         if frame.ndim != 3 or frame.shape[2] != 3:
             raise ValueError("frame must be an HxWx3 uint8 BGR image, got shape %s" % (frame.shape,))

@@ -793,8 +793,8 @@ class PerceptionLoop:
                                          nat.ptr(self.det_cls)))
 
     def enqueue_lanes(self, stream=None, stages=0):
-        """stages 0: the whole chain; 2: pixel stages only (edge points left in the workspace); 16: Hough + fit of
-        what the last pixel-stage call left there."""
+        """stages 0: the whole chain; nat.LANE_PIXELS_ONLY: pixel stages only (edge points left in the workspace);
+        nat.LANE_HOUGH_ONLY: Hough + fit of what the last pixel-stage call left there."""
         nat.check(self.L.av_lane_detect(self.ctx.handle, stream or self._s, C.byref(self.lcfg), self.S, self.h, self.w,
                                         nat.ptr(self.frames), None, nat.ptr(self.ws), nat.ptr(self.lane_state),
                                         nat.ptr(self.poly), nat.ptr(self.pts), nat.ptr(self.info), nat.ptr(self.conf), stages))
@@ -869,8 +869,8 @@ class PerceptionLoop:
         self.enqueue_generate()
         nat.check(self.L.av_fork(h, self._s))
         if self._lanes_pending:
-            self.enqueue_lanes(self.ctx.side_stream, stages=16)
-        self.enqueue_lanes(self.ctx.side_stream, stages=2)
+            self.enqueue_lanes(self.ctx.side_stream, stages=nat.LANE_HOUGH_ONLY)
+        self.enqueue_lanes(self.ctx.side_stream, stages=nat.LANE_PIXELS_ONLY)
         self._lanes_pending = True
         self.enqueue_detect()
         nat.check(self.L.av_join(h, self._s))
@@ -878,7 +878,7 @@ class PerceptionLoop:
     def flush_lanes(self):
         """Hough + fit of the last frame step_deferred() left pending."""
         if self._lanes_pending:
-            self.enqueue_lanes(stages=16)
+            self.enqueue_lanes(stages=nat.LANE_HOUGH_ONLY)
             self._lanes_pending = False
         self.join_detector_tail()
 

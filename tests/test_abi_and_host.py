@@ -32,6 +32,17 @@ def test_struct_layouts_match_header(lib):
     assert lib.av_tracker_state_bytes(0, 50) == 0
 
 
+def test_lane_stage_bits_and_view_ids_match_header():
+    import re
+    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "avhot.h")).read()
+    defs = {k: int(v) for k, v in re.findall(r"#define\s+AV_(LANE_[A-Z_]+)\s+(\d+)", hdr)}
+    mine = {k: v for k, v in vars(nat).items() if k.startswith("LANE_")}
+    assert defs == mine and len(defs) == 18
+    assert [defs[k] for k in ("LANE_KEEP_EDGES", "LANE_PIXELS_ONLY", "LANE_RESERVED", "LANE_GENERIC_HOUGH", "LANE_HOUGH_ONLY",
+                              "LANE_FIT_ONLY", "LANE_GIVEN_GRAY")] == [1, 2, 4, 8, 16, 32, 64]
+    assert sorted(v for k, v in defs.items() if k.startswith("LANE_VIEW_")) == list(range(11))
+
+
 def test_no_device_fails_loudly(lib):
     import torch
     if torch.cuda.is_available():

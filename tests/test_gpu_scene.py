@@ -48,7 +48,7 @@ def check_stats(row, st, tag):
     np.testing.assert_allclose(row["lap_var"], st["lap_var"], rtol=1e-12, err_msg=str(tag))
 
 
-@pytest.mark.parametrize("S,h,w", [(64, 720, 1280), (5, 360, 600), (3, 48, 64)])
+@pytest.mark.parametrize("S,h,w", [(64, 720, 1280), (5, 360, 600), (3, 48, 64), (7, 250, 333)])
 def test_scene_stats_match_the_restatement(S, h, w):
     frames = np.stack([sr.scene_frame(h, w, s, 3 * s, s % 7) for s in range(S)])
     speeds = np.array([[np.nan, 1.0, 20.0, 9.0][s % 4] for s in range(S)])
