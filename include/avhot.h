@@ -755,6 +755,11 @@ int av_hot_step(av_ctx* ctx, av_stream_t stream, const av_tracker_cfg* tracker_c
  * av_hot_step, D for av_hot_step_seq); AV_EINVAL where it cannot (the planner's per-wave tiles do not fit the LDS even with eight
  * waves per workgroup, e.g. 126 waypoints at 21 candidates), and the caller keeps the four stage calls. */
 int av_hot_step_fits(av_ctx* ctx, int n_streams, int dcap, int tcap, int depth);
+/* The launch shape av_hot_step_fits decides on, under the same conditions and with the same return codes: waves per workgroup of
+ * the step kernel (16, 12 or 8: sixteen where `depth` launches of 2 S sixteen-wave workgroups are all resident, else twelve, else
+ * eight; AVHOT_STEP_PW=8|12|16 forces one), the workgroups per CU the occupancy query answered for that kernel (0 at depth 1, where
+ * it is not asked) and the dynamic LDS bytes of a launch.  Any of the three pointers may be NULL.  Launches nothing. */
+int av_hot_step_plan(av_ctx* ctx, int n_streams, int dcap, int tcap, int depth, int* waves, int* per_cu, size_t* lds_bytes);
 
 /* Consecutive time-steps OVERLAPPED (still one launch per step, same results bit for bit).  The reference's loop runs frame t + 1
  * after frame t (demo.py:97-120); what frame t + 1 needs of frame t is the stream's tracker table (tracker role) and its filter
@@ -768,13 +773,17 @@ int av_hot_step_fits(av_ctx* ctx, int n_streams, int dcap, int tcap, int depth);
  *              (AVHOT_STEP_SPIN polls, default 2^22: a predecessor that was never launched) and it left without running its step,
  *              bit 1: frame_count[s] was not base + seq; check it after synchronising; [64 S + 32 + s] = frame_count[s] at the
  *              reset (the detections of step seq are made for frame count base + seq + 1 without waiting for step seq - 1);
- *              the last 64 ints: phase clocks summed by the kernel when AVHOT_STEP_FENCE=8 (tools/steptime.py), otherwise unused.
+ *              the last 64 ints (at an even word -- one word of padding in front of them for odd S -- so that seq_flags has to be 8-byte
+ *              aligned): phase clocks summed by the kernel when AVHOT_STEP_FENCE=8 (tools/steptime.py), otherwise unused.  (For odd S
+ *              this is one word more than the earlier 65 S + 96: a caller that still allocates that is only overrun with
+ *              AVHOT_STEP_FENCE=8 set.)
  * Step numbers are 32-bit and wrap (a signed int carrying an unsigned count: 2^31 - 1 is followed by -2^31, -1 by 0); the stream and
  * buffer set of step seq are those of (uint32_t)seq % D.
  * `depth` = D: up to D launches may be in flight, each possibly waiting for the one before it, so all of them must be RESIDENT
- * together: the call picks sixteen or eight waves per workgroup accordingly and returns AV_EINVAL when D launches of 2 S workgroups
- * cannot fit (64 streams: D <= 2 with sixteen waves, <= 4 with eight).  HotLoop(window=1, overlap=D) drives it. */
-#define AV_STEP_FLAG_INTS(n_streams) (65 * (n_streams) + 32 + 64)
+ * together: the call picks sixteen, twelve or eight waves per workgroup accordingly (av_hot_step_plan says which) and returns
+ * AV_EINVAL when D launches of 2 S workgroups cannot fit (64 streams: D <= 2 with sixteen waves, <= 4 with twelve or eight).
+ * HotLoop(window=1, overlap=D) drives it. */
+#define AV_STEP_FLAG_INTS(n_streams) (65 * (n_streams) + ((n_streams) & 1) + 32 + 64)
 int av_hot_step_seq(av_ctx* ctx, av_stream_t stream, const av_tracker_cfg* tracker_cfg, const av_kf_cfg* kf_cfg, int n_streams, int h,
                     int w, int dcap, int tcap, int32_t* frame_count, int32_t* det_n, int32_t* det_box, int32_t* det_cls,
                     double* det_conf, int32_t* det_status, void* tracker_state, av_track_row* snap, int32_t* snap_n, int32_t* det2trk,

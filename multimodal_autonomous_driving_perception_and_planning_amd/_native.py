@@ -149,6 +149,8 @@ _SIGS = [
                                 C.c_int, vp, vp, vp]),
     ("av_hot_step", C.c_int, [vp, vp, C.POINTER(TrackerCfg), C.POINTER(KfCfg)] + [C.c_int] * 5 + [vp] * 17 + [vp, C.c_int, C.c_int]),
     ("av_hot_step_fits", C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("av_hot_step_plan", C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                   C.POINTER(C.c_size_t)]),
     ("av_hot_steps_seq", C.c_int, [vp, C.c_int, vp, C.POINTER(TrackerCfg), C.POINTER(KfCfg)] + [C.c_int] * 5 + [vp] * 7 +
      [C.c_int, C.c_int, vp, C.c_int, C.c_int]),
     ("av_hot_step_seq", C.c_int, [vp, vp, C.POINTER(TrackerCfg), C.POINTER(KfCfg)] + [C.c_int] * 5 + [vp] * 17 +
@@ -269,7 +271,15 @@ def register(sigs):
 
 def step_flag_ints(n_streams):
     """AV_STEP_FLAG_INTS(n_streams) of include/avhot.h: int32 words of the overlapped steps' sequence flags."""
-    return 65 * n_streams + 32 + 64
+    return 65 * n_streams + (n_streams & 1) + 32 + 64
+
+
+def step_plan(ctx_handle, n_streams, dcap, tcap, depth):
+    """av_hot_step_plan: (rc, waves per workgroup, workgroups per CU from the occupancy query -- 0 at depth 1 --, dynamic LDS bytes) of
+    the one-launch step with `depth` launches in flight; rc != 0 (see av_last_error_string) where no shape fits."""
+    w, p, b = C.c_int(), C.c_int(), C.c_size_t()
+    rc = lib().av_hot_step_plan(ctx_handle, n_streams, dcap, tcap, depth, C.byref(w), C.byref(p), C.byref(b))
+    return rc, w.value, p.value, b.value
 
 
 def step_i32(v):

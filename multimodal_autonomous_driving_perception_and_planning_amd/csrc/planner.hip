@@ -255,8 +255,11 @@ __device__ __forceinline__ void plan_block_lists(const PlanParams& p, int f0, in
     const int CS = even_up(G * C);
 
     const int tid = threadIdx.x, lane = tid & 63;
-    double* stage = stage_all + (size_t)(tid >> 6) * n * 6;
-    const int wid = ((tid >> 6) + NW - rot) % NW;      // the wave's place in the dealing of tasks
+    // (the wave's number by the scalar unit: its place in the dealing, the trajectories it takes, their indices, tile and output
+    // addresses are then scalar values, not one copy per lane in vector registers)
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    double* stage = stage_all + (size_t)wave * n * 6;
+    const int wid = (wave + NW - rot) % NW;            // the wave's place in the dealing of tasks
     constexpr int P = G * 3;                           // (state, speed) pairs
     static_assert(NW >= 2, "the heading terms take the last wave");   // (fast, P <= NW: one wave per pair keeps its terms in registers)
 
@@ -282,7 +285,7 @@ __device__ __forceinline__ void plan_block_lists(const PlanParams& p, int f0, in
         double run = sv, sa = 0.0;
 #pragma unroll
         for (int i = 1; i < 64; ++i)
-            if (i < n && ((hasm >> i) & 1ull)) {
+            if ((hasm >> i) & 1ull) {          // (hasm has no bit from n on: tested again here, the 63 `i < n` of the loop above stay live in scalar pairs)
                 const double term = bcast(acct, i);
                 run = run + term, sa = sa + term;
             }

@@ -13,10 +13,17 @@
 //   workgroups [S, 2 S)    stream s: Kalman step in the first wave (axis-separable filter in two parts -- kf_axis_chain1: the record
 //                          and the planner's start state, all the next step and the planner wait for; kf_axis_tail1: the rest of
 //                          the frame's output, later, on a planner wave with slack; the dense filter on one lane for a stream
-//                          flagged non-separable), then the 3 C candidate trajectories spread over the workgroup's sixteen (or
-//                          eight) waves (plan_block<1, PW>, start state read from LDS), cost ranking, outputs
+//                          flagged non-separable), then the 3 C candidate trajectories spread over the workgroup's sixteen, twelve
+//                          or eight waves (plan_block<1, PW>, start state read from LDS), cost ranking, outputs
 // The two roles of a stream never exchange data (the planner does not consume tracks).
 // av_hot_step launches one such step; av_hot_step_seq / av_hot_steps_seq keep up to four consecutive steps in flight (below).
+// Three workgroup shapes (hot_step_shape picks, av_hot_step_plan reports): sixteen waves (21 trajectories in two rounds, one
+// workgroup per CU: serial launches and depth 2 at 64 streams), TWELVE (two rounds as well, two workgroups per CU: depth 3 and 4, the
+// headline -- a launch's lifetime counts against the step rate there, and most of it is the planner's rounds) and eight (three rounds,
+// two per CU: the fallback).  Twelve waves x two workgroups are six waves per SIMD, i.e. at most 80 vector registers:
+// hot_step_kernel<12> is compiled for that and takes 78 with no scratch and no scalar spill (DESIGN.md section 4b has the figures and
+// what it took: each role loads its arguments inside its own branch, the debug clocks carry nothing in registers, the planner's wave
+// number is a scalar value).
 #define AVHOT_DEVICE_ONLY
 #include "simdet.hip"
 #include "tracker.hip"
@@ -66,34 +73,46 @@ constexpr int STEP_NW = 8;
 // The per-step outputs (detections, snapshot rows, det2trk, Kalman output, waypoints, costs, order, wire table) rotate through D
 // buffer sets on the host side, so steps in flight never write the same output and the Kalman counter moves on before the
 // planner has run.  All launches in flight must be RESIDENT together (each may be waiting for the one before it): hot_step_args picks
-// sixteen or eight waves per workgroup from the occupancy and refuses a depth that does not fit.  Every wait is bounded: after `spin`
+// sixteen, twelve or eight waves per workgroup from the occupancy and refuses a depth that does not fit.  Every wait is bounded: after `spin`
 // polls the workgroup sets the fault word (bit 0) and leaves without running its step, the launches behind it give up at once
 // (HotLoop.synchronize raises) -- no launch can hang on a lost predecessor.
 // seq_flags layout (AV_STEP_FLAG_INTS): one 128-byte line per counter -- 2 S pollers hammer them -- then the fault word's line, then
 // the streams' detector frame counts at reset (the count before step q is base + q: the detections do not have to wait)
 __device__ __host__ inline int flag_fault(int S) { return 64 * S; }
 __device__ __host__ inline int flag_base(int S) { return 64 * S + 32; }
-__device__ __host__ inline int flag_stats(int S) { return 65 * S + 32; }      // 32 u64 of phase clocks (AVHOT_STEP_FENCE=8, tools/steptime.py)
+// 32 u64 of phase clocks (AVHOT_STEP_FENCE=8, tools/steptime.py), at an even word: 64-bit atomics need their 8-byte alignment
+__device__ __host__ constexpr int flag_stats(int S) { return 65 * S + (S & 1) + 32; }
+static_assert(flag_stats(1) % 2 == 0 && flag_stats(3) % 2 == 0 && flag_stats(64) % 2 == 0 && flag_stats(1) + 64 == AV_STEP_FLAG_INTS(1) &&
+                  flag_stats(3) + 64 == AV_STEP_FLAG_INTS(3) && flag_stats(64) + 64 == AV_STEP_FLAG_INTS(64),
+              "the phase clocks are the last 64 words of AV_STEP_FLAG_INTS and start at an even word");
+// Nothing of it is carried in registers: the last stamp is kept in LDS, and whether the clocks are on and where they add up is worked
+// out again at every mark.  Carried, they were live from a role's first line to its last, switched on or not -- the stamp in two
+// vector registers of every wave, the switched-on lanes and the address in two scalar pairs -- which is what hot_step_kernel<12>
+// was short of.
 struct StepClock {                    // debug only: 100-MHz clock stamps of a role's thread 0, summed per phase over all launches
-    unsigned long long t;
-    bool on;
-    unsigned long long* acc;
-    __device__ void start(const StepArgs& a, int role);
-    __device__ void mark(int k) {
-        if (!on) return;
+    const StepArgs& a;
+    int role;
+    unsigned long long* t;            // in LDS
+    __device__ __forceinline__ bool on() const {
+        int fence = a.fence;
+        asm volatile("" : "+s"(fence));           // (a value of its own at every mark, or the compiler keeps the first one's lane mask)
+        return (fence & 8) && a.flags && threadIdx.x == 0;
+    }
+    __device__ __forceinline__ unsigned long long* acc() const {
+        return reinterpret_cast<unsigned long long*>(a.flags + flag_stats(a.S)) + role * 16;
+    }
+    __device__ __forceinline__ void start() {
+        if (!on()) return;
+        *t = __builtin_amdgcn_s_memrealtime();
+        atomicAdd(acc() + 15, 1ull);
+    }
+    __device__ __forceinline__ void mark(int k) {
+        if (!on()) return;
         const unsigned long long n = __builtin_amdgcn_s_memrealtime();
-        atomicAdd(acc + k, n - t);
-        t = n;
+        atomicAdd(acc() + k, n - *t);
+        *t = n;
     }
 };
-
-__device__ void StepClock::start(const StepArgs& a, int role) {
-    on = a.flags && (a.fence & 8) && threadIdx.x == 0;
-    if (!on) return;
-    acc = reinterpret_cast<unsigned long long*>(a.flags + flag_stats(a.S)) + role * 16;
-    t = __builtin_amdgcn_s_memrealtime();
-    atomicAdd(acc + 15, 1ull);
-}
 
 __device__ __forceinline__ bool seq_enter(const StepArgs& a, int slot, int* go) {
     if (threadIdx.x == 0) {
@@ -142,12 +161,24 @@ __device__ __forceinline__ void fetch_record(const void* src, void* dst_lds, int
         l[i] = coherent ? __hip_atomic_load(g + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : g[i];
 }
 
-// PW: waves of a planner workgroup (the tracker role always runs on STEP_NW = 8; with PW = 16 its workgroups' other eight waves leave
-// at once).  The 3 C = 21 trajectories of a start state are dealt to the waves whole: eight waves take three rounds, sixteen two.
+// The kernel's arguments as a ROLE reads them: from the kernel-argument segment (StepArgs is the kernel's only parameter, at its
+// offset 0), through a pointer the compiler cannot trace back to the parameter.  Read from the parameter, all ~130 scalar registers
+// of arguments -- both roles' -- are loaded at the kernel's entry and most of them spilled to vector-register lanes at once (148-152
+// of them, three vector registers); read through this, a role's loads are scalar loads placed inside its own branch, and only its own.
+__device__ __forceinline__ const StepArgs& role_args() {
+    auto p = __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return *(const StepArgs*)p;
+}
+
+// PW: waves of a planner workgroup (the tracker role always runs on STEP_NW = 8; with PW = 16 or 12 its workgroups' other waves leave
+// at once).  The 3 C = 21 trajectories of a start state are dealt to the waves whole: eight waves take three rounds, twelve and
+// sixteen two (twelve: the three phase-1 pair waves one trajectory each, the nine others two).
 template <int PW>
-__global__ void __launch_bounds__(PW * 64) hot_step_kernel(StepArgs a) {
+__device__ __forceinline__ void hot_step_body(const StepArgs& a0) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int go, fc_stage;
+    __shared__ unsigned long long ck_t;
     __shared__ __attribute__((aligned(16))) double kf_stage[AV_KF_STATE_DOUBLES + 2];
     // the Kalman wave's hand-off inside the workgroup: the planner's start state (px, py, heading, speed), what the tail of the
     // Kalman step needs beside the record, and whether there is a tail to run (the dense filter does everything at once)
@@ -160,14 +191,15 @@ __global__ void __launch_bounds__(PW * 64) hot_step_kernel(StepArgs a) {
     __shared__ __attribute__((aligned(16))) double d_conf[8], d_area[8], z_stage[4];
     __shared__ int d_cls[8], d_n[1];
     const int tid = threadIdx.x;
-    const bool seq = a.flags != nullptr;          // consecutive steps overlapped: wait for / publish to the neighbouring launches
+    const bool seq = a0.flags != nullptr;          // consecutive steps overlapped: wait for / publish to the neighbouring launches
     // Both roles run on an LDS copy of the stream's record (tracker: header + rows; Kalman: the filter's 46 doubles), fetched by the
     // whole workgroup at once -- with device-scope loads and stores when the neighbouring steps are separate launches in flight.
-    if ((int)blockIdx.x < a.S) {
+    if ((int)blockIdx.x < a0.S) {
+        const StepArgs& a = role_args();
         if (PW > STEP_NW && tid >= STEP_NW * 64) return;
         const int s = blockIdx.x;
-        StepClock ck;
-        ck.start(a, 0);
+        StepClock ck{a, 0, &ck_t};
+        ck.start();
         // the detections first: overlapped, the detector's count before step q is its count at reset + q -- no need to wait for step
         // q - 1 (tid 0 checks that against the counter the predecessor left: fault bit 1)
         int fc_before = 0;
@@ -222,9 +254,10 @@ __global__ void __launch_bounds__(PW * 64) hot_step_kernel(StepArgs a) {
                          a.snap + (size_t)s * a.tcap, a.stream0 + s, a.frame0 + fc_stage);
         }
     } else {
+        const StepArgs& a = role_args();
         const int s = blockIdx.x - a.S;
-        StepClock ck;
-        ck.start(a, 1);
+        StepClock ck{a, 1, &ck_t};
+        ck.start();
         if (tid < 4) z_stage[tid] = a.z[(size_t)s * 4 + tid];
         if (seq && !seq_enter(a, 2 * s + 1, &go)) return;
         ck.mark(1);
@@ -262,7 +295,7 @@ __global__ void __launch_bounds__(PW * 64) hot_step_kernel(StepArgs a) {
         ck.mark(4);                   // planner start
         // The Kalman wave publishes its counter itself, behind the acknowledgement of its record stores -- while the planner's phase 1
         // runs on other waves: plan_block deals its tasks from wave KF_ROT on, which leaves wave 0 without phase-1 work (it joins the
-        // phase-1 barrier when its counter is stored and takes three trajectories after it)
+        // phase-1 barrier when its counter is stored and takes its trajectories after it: three with eight waves, two with twelve)
         constexpr int KF_ROT = 4;
         static_assert(KF_ROT + 3 < PW, "wave 0 must not be a phase-1 pair wave nor the heading wave (task wave PW - 1)");
         if (seq && tid < 64) {
@@ -284,6 +317,18 @@ __global__ void __launch_bounds__(PW * 64) hot_step_kernel(StepArgs a) {
     }
 }
 
+// StepArgs is, and has to stay, the ONLY parameter of these kernels: role_args() reads it at offset 0 of the kernel-argument segment.
+// Anything a step needs beside it goes into StepArgs.
+template <int PW>
+__global__ void __launch_bounds__(PW * 64) hot_step_kernel(StepArgs a) {
+    hot_step_body<PW>(a);
+}
+// twelve waves, two workgroups per CU: six waves per SIMD, which the register allocator is told here (<= 80 vector registers)
+template <>
+__global__ void __launch_bounds__(12 * 64) __attribute__((amdgpu_waves_per_eu(6))) hot_step_kernel<12>(StepArgs a) {
+    hot_step_body<12>(a);
+}
+
 }  // namespace
 
 // dynamic LDS of the tracker role: the tracker's layout for one staged frame on eight replica waves (tracker_lds_bytes), then the copy
@@ -300,39 +345,48 @@ static size_t hot_step_static_lds(const void* kernel) {
     return hipFuncGetAttributes(&fa, kernel) == hipSuccess ? (size_t)fa.sharedSizeBytes : (size_t)16384;
 }
 
+// the kernel of a workgroup shape, for the attribute and occupancy queries (hot_step_go launches them by name)
+static const void* hot_step_fn(int pw) {
+    return pw == 16 ? reinterpret_cast<const void*>(hot_step_kernel<16>)
+           : pw == 12 ? reinterpret_cast<const void*>(hot_step_kernel<12>)
+                      : reinterpret_cast<const void*>(hot_step_kernel<8>);
+}
+
 // dynamic LDS (the larger of the tracker role's and the planner's) and waves per workgroup of the one-launch step; AV_EINVAL where
-// neither sixteen nor eight waves fit
-static int hot_step_shape(const av_ctx* ctx, int n_streams, size_t lds_t, int depth, size_t& lds_out, int& pw_out) {
-    // Waves per workgroup: sixteen (the planner's 21 trajectories in two rounds) unless the planner's sixteen per-wave tiles do not fit
-    // the LDS (n > 66 at 21 candidates) or that many launches in flight would not all be resident -- every one of them may be waiting
-    // for the one before it, so `depth` launches of 2 S workgroups must fit on the device together -- in which case eight (three
-    // rounds, twice the workgroups per CU).  AVHOT_STEP_PW=8|16 forces one.
+// no shape fits.  per_cu_out: the occupancy answer for the chosen shape (0 where it was not asked: depth 1)
+static int hot_step_shape(const av_ctx* ctx, int n_streams, size_t lds_t, int depth, size_t& lds_out, int& pw_out, int* per_cu_out = nullptr) {
+    // Waves per workgroup: sixteen (the planner's 21 trajectories in two rounds, one workgroup per CU), else twelve (two rounds as
+    // well -- the three phase-1 pair waves take one trajectory, the nine others two -- and two workgroups per CU: hot_step_kernel<12>
+    // is held to 80 registers), else eight (three rounds, two per CU).  A shape is passed over when the planner's per-wave tiles do
+    // not fit the LDS with it (n > 66 at 21 candidates and sixteen waves) or when `depth` launches in flight would not all be
+    // resident -- every one of them may be waiting for the one before it, so depth x 2 S workgroups must fit on the device together;
+    // residency is what the occupancy query answers for that instantiation, never assumed.  AVHOT_STEP_PW=8|12|16 forces one.
     // static __shared__ of the kernel (the Kalman bodies' arrays) counts against the same 64 KB
-    static const size_t lds_static16 = hot_step_static_lds(reinterpret_cast<const void*>(hot_step_kernel<16>));
-    static const size_t lds_static8 = hot_step_static_lds(reinterpret_cast<const void*>(hot_step_kernel<8>));
+    static const size_t lds_static16 = hot_step_static_lds(hot_step_fn(16));
+    static const size_t lds_static12 = hot_step_static_lds(hot_step_fn(12));
+    static const size_t lds_static8 = hot_step_static_lds(hot_step_fn(8));
     const char* pwe = getenv("AVHOT_STEP_PW");
-    int pw = pwe && atoi(pwe) == 8 ? 8 : 16;
+    const int forced = pwe ? atoi(pwe) : 0;
+    int pw = forced == 8 || forced == 12 ? forced : 16;
     size_t lds = 0;
-    for (;;) {
+    int per_cu = 0;
+    for (;; pw = pw == 16 ? 12 : 8) {                 // (left by break; a shape that does not fit falls to the next one unless it was forced)
         const size_t lds_p = plan_lds_doubles(1, ctx->n_points, ctx->n_cand, pw) * 8;
         lds = lds_t > lds_p ? lds_t : lds_p;
-        const size_t lds_static = pw == 16 ? lds_static16 : lds_static8;
+        const size_t lds_static = pw == 16 ? lds_static16 : pw == 12 ? lds_static12 : lds_static8;
         if (lds + lds_static > 64 * 1024) {
-            AV_REQUIRE(pw == 16 && !pwe, AV_EINVAL,
+            AV_REQUIRE(pw > 8 && !pwe, AV_EINVAL,
                        "av_hot_step: configuration needs %zu B of dynamic + %zu B of static LDS (limit 65536)", lds, lds_static);
-            pw = 8;
             continue;
         }
         if (depth <= 1) break;
-        int per_cu = 0;
-        if (pw == 16) AV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hot_step_kernel<16>, 16 * 64, lds));
-        else AV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hot_step_kernel<8>, 8 * 64, lds));
+        AV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hot_step_fn(pw), pw * 64, lds));
         if ((long long)depth * 2 * n_streams <= (long long)per_cu * ctx->n_cus) break;
-        AV_REQUIRE(pw == 16 && !pwe, AV_EINVAL, "av_hot_step: %d launches of %d workgroups in flight do not fit the device (%d per CU x %d CUs)",
+        AV_REQUIRE(pw > 8 && !pwe, AV_EINVAL, "av_hot_step: %d launches of %d workgroups in flight do not fit the device (%d per CU x %d CUs)",
                    depth, 2 * n_streams, per_cu, ctx->n_cus);
-        pw = 8;
     }
     lds_out = lds, pw_out = pw;
+    if (per_cu_out) *per_cu_out = per_cu;
     return AV_OK;
 }
 
@@ -364,6 +418,7 @@ static int hot_step_args(av_ctx* ctx, const av_tracker_cfg* tcfg, const av_kf_cf
     a.z = z, a.kf_state = kf_state, a.vstate = vstate, a.plan_state = plan_state;
     a.wp = waypoints, a.cost = cost, a.order = order;
     a.wire = (uint8_t*)wire, a.stream0 = stream0, a.frame0 = frame0;
+    AV_REQUIRE(((uintptr_t)seq_flags & 7) == 0, AV_EINVAL, "av_hot_step: the sequence flags must be 8-byte aligned (64-bit phase clocks in their last 64 words)");
     a.flags = seq_flags, a.seq = seq;
     const char* spe = seq_flags ? getenv("AVHOT_STEP_SPIN") : nullptr;
     a.spin = spe ? atoi(spe) : (1 << 22);
@@ -377,6 +432,7 @@ static int hot_step_args(av_ctx* ctx, const av_tracker_cfg* tcfg, const av_kf_cf
 
 static int hot_step_go(const StepArgs& a, size_t lds, int pw, av_stream_t stream) {
     if (pw == 16) hipLaunchKernelGGL(hot_step_kernel<16>, dim3(2 * a.S), dim3(16 * 64), lds, as_stream(stream), a);
+    else if (pw == 12) hipLaunchKernelGGL(hot_step_kernel<12>, dim3(2 * a.S), dim3(12 * 64), lds, as_stream(stream), a);
     else hipLaunchKernelGGL(hot_step_kernel<8>, dim3(2 * a.S), dim3(8 * 64), lds, as_stream(stream), a);
     AV_LAUNCH_CHECK();
     return AV_OK;
@@ -406,6 +462,21 @@ extern "C" int av_hot_step_fits(av_ctx* ctx, int n_streams, int dcap, int tcap, 
     size_t lds = 0;
     int pw = 0;
     return hot_step_shape(ctx, n_streams, hot_step_tracker_lds(dcap, tcap, stage_off), depth, lds, pw);
+}
+
+extern "C" int av_hot_step_plan(av_ctx* ctx, int n_streams, int dcap, int tcap, int depth, int* waves, int* per_cu, size_t* lds_bytes) {
+    AV_REQUIRE(ctx && n_streams > 0 && depth >= 1, AV_EINVAL, "av_hot_step_plan: bad argument");
+    AV_REQUIRE(ctx->planner_ready, AV_ESTATE, "av_hot_step_plan: call av_planner_configure first");
+    AV_REQUIRE(tcap == 64 && dcap >= 7 && dcap <= 8, AV_EINVAL, "av_hot_step_plan: needs tcap 64, dcap 7..8");
+    AV_HIP(hipSetDevice(ctx->device));
+    int stage_off = 0, pw = 0, pc = 0;
+    size_t lds = 0;
+    const int rc = hot_step_shape(ctx, n_streams, hot_step_tracker_lds(dcap, tcap, stage_off), depth, lds, pw, &pc);
+    if (rc != AV_OK) return rc;
+    if (waves) *waves = pw;
+    if (per_cu) *per_cu = pc;
+    if (lds_bytes) *lds_bytes = lds;
+    return AV_OK;
 }
 
 extern "C" int av_hot_step(av_ctx* ctx, av_stream_t stream, const av_tracker_cfg* tcfg, const av_kf_cfg* kcfg, int n_streams, int h,

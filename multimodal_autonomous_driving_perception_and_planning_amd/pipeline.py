@@ -176,6 +176,16 @@ class HotLoop:
 
     _i32 = staticmethod(nat.step_i32)
 
+    @property
+    def step_waves(self):
+        """Waves per workgroup of the one-launch step as the library launches it for this loop (av_hot_step_plan at the loop's
+        overlap depth: 16, 12 or 8; AVHOT_STEP_PW is read at every launch, and here); None without the fused step."""
+        if not self.fused_step:
+            return None
+        rc, waves, _, _ = nat.step_plan(self.ctx.handle, self.S, self.dcap, self.tcap, self.overlap)
+        nat.check(rc)
+        return waves
+
     def _serial_only(self, what):
         if self.overlap != 1:
             raise RuntimeError("%s is not available with overlap=2.. (only the one-launch step is ordered across the loop's streams)" % what)

@@ -135,7 +135,7 @@ for k in fe:
 # ---- the one-launch time-step (headline): HBM bytes per launch ------------------------------------------------------------------
 fe, wr = counters("step_fetch"), counters("step_write")
 _hs = [k for k in fe if "hot_step_kernel" in k and k in wr]
-for k in sorted(_hs, key=lambda k: fe[k]["launches"])[-1:]:           # the instance the headline launches (eight waves per workgroup at depth 4)
+for k in sorted(_hs, key=lambda k: fe[k]["launches"])[-1:]:           # the instance the headline launches (twelve waves per workgroup at depth 4)
     if True:
         f, w_ = 2.0 * fe[k]["FETCH_SIZE"] * 1024.0, wr[k]["WRITE_SIZE"] * 1024.0
         json.dump({"kernel": k, "source": "rocprofv3 --pmc WRITE_SIZE / --pmc FETCH_SIZE (separate passes, each with --kernel-trace only) -- "

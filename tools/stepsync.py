@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The headline's step kernel (HotLoop(64, window 1, overlap=4): eight waves per workgroup, sequence counters, device-scope hand-over)
+"""The headline's step kernel (HotLoop(64, window 1, overlap=4): twelve waves per workgroup, sequence counters, device-scope hand-over)
 launched ONE AT A TIME, the host waiting after every launch: the form a counter pass needs.  rocprofv3 --pmc runs kernels one after
 the other in an order of its own choosing, and a step whose predecessor has not run yet waits for it -- with the launches overlapped as
 bench.py runs them the pass ends in the loop's fault word instead of counters."""
