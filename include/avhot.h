@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define AV_VERSION 102
+#define AV_VERSION 103
 
 enum {
     AV_OK = 0,
@@ -737,7 +737,9 @@ int av_synth_frames(av_ctx* ctx, av_stream_t stream, int n_streams, int h, int w
 /* ---- one launch per time-step (BASELINE config 4, window 1; the reference's per-frame cadence, demo.py:97-120) -----------
  * av_hot_step = av_simdet_generate + av_tracker_update + av_kf_step + av_planner_plan (no reference path / obstacles) for ONE
  * frame of every stream, as a single kernel with role-split workgroups that run the stage kernels' own device code: the
- * results are those of the four calls bit for bit.  Buffers as in the stage calls with n_frames = 1:
+ * results are those of the four calls bit for bit.  A step's arguments are two structs -- av_step_loop: what all steps of a
+ * loop share (the configurations, the shapes, the persistent state); av_step_set: the buffers one step reads and writes -- plus
+ * the wire tables.  Buffers as in the stage calls with n_frames = 1:
  *   frame_count [S]; det_n [S], det_box [S][dcap][4], det_cls / det_conf [S][dcap], det_status [S] or NULL;
  *   tracker_state as av_tracker_update; snap [S][tcap] + snap_n [S] (or both NULL); det2trk [S][dcap];
  *   z [S][4]; kf_state [S][AV_KF_STATE_DOUBLES]; vstate [S][AV_VSTATE_DOUBLES]; plan_state [S][4];
@@ -746,11 +748,26 @@ int av_synth_frames(av_ctx* ctx, av_stream_t stream, int n_streams, int h, int w
  *   n_sel = 1), written by the same launch (needs snap); header.stream = stream0 + s, header.frame = frame0 + frame_count[s]
  *   after the step (the stream's own detector frame count, read on the device: a captured graph stamps every replay correctly).
  * Built for tcap 64, dcap 7..8, iou_threshold > 0 (AV_EINVAL otherwise: use the stage calls). */
-int av_hot_step(av_ctx* ctx, av_stream_t stream, const av_tracker_cfg* tracker_cfg, const av_kf_cfg* kf_cfg, int n_streams, int h,
-                int w, int dcap, int tcap, int32_t* frame_count, int32_t* det_n, int32_t* det_box, int32_t* det_cls,
-                double* det_conf, int32_t* det_status, void* tracker_state, av_track_row* snap, int32_t* snap_n, int32_t* det2trk,
-                const double* z, double* kf_state, double* vstate, double* plan_state, double* waypoints, double* cost,
-                int32_t* order, void* wire, int stream0, int frame0);
+typedef struct av_step_set {
+    int32_t *det_n, *det_box, *det_cls;
+    double* det_conf;
+    av_track_row* snap;
+    int32_t *snap_n, *det2trk;
+    const double* z;
+    double *vstate, *plan_state, *waypoints, *cost;
+    int32_t* order;
+} av_step_set;
+typedef struct av_step_loop {
+    av_tracker_cfg tracker_cfg;
+    av_kf_cfg kf_cfg;
+    int32_t n_streams, h, w, dcap, tcap, reserved;      /* (reserved: the pointers start 8-byte aligned) */
+    int32_t* frame_count;
+    int32_t* det_status;
+    void* tracker_state;
+    double* kf_state;
+} av_step_loop;
+int av_hot_step(av_ctx* ctx, av_stream_t stream, const av_step_loop* loop, const av_step_set* set, void* wire, int stream0,
+                int frame0);
 /* AV_OK when the one-launch step can run n_streams streams with the planner configured now and `depth` launches in flight (1 for
  * av_hot_step, D for av_hot_step_seq); AV_EINVAL where it cannot (the planner's per-wave tiles do not fit the LDS even with eight
  * waves per workgroup, e.g. 126 waypoints at 21 candidates), and the caller keeps the four stage calls. */
@@ -765,8 +782,8 @@ int av_hot_step_plan(av_ctx* ctx, int n_streams, int dcap, int tcap, int depth, 
  * after frame t (demo.py:97-120); what frame t + 1 needs of frame t is the stream's tracker table (tracker role) and its filter
  * state (Kalman role), not the planner's output.  The caller launches step `seq` (0, 1, 2, ... since the state was reset) on HIP
  * stream seq % D of D = 2 .. 4 streams -- so that step seq + D follows step seq in stream order -- and gives the D steps that may
- * be in flight DIFFERENT per-step buffers (det_*, snap, snap_n, det2trk, z, vstate, plan_state, waypoints, cost, order, wire); the persistent
- * buffers (frame_count, det_status, tracker_state, kf_state) and seq_flags are shared.  On the device a role of step `seq` waits
+ * be in flight DIFFERENT per-step buffers (an av_step_set each, and a wire buffer each); the av_step_loop -- the persistent
+ * buffers (frame_count, det_status, tracker_state, kf_state) -- and seq_flags are shared.  On the device a role of step `seq` waits
  * until seq_flags says its stream's role of step seq - 1 has finished and published its state:
  *   seq_flags  int32 [AV_STEP_FLAG_INTS(S)], set up when the state is reset: [32 (2 s + r)] = 0, the steps done by role r (0 tracker,
  *              1 Kalman) of stream s, a 128-byte line each; [64 S] = 0, the fault word -- bit 0: a workgroup's wait ran out
@@ -784,11 +801,9 @@ int av_hot_step_plan(av_ctx* ctx, int n_streams, int dcap, int tcap, int depth, 
  * AV_EINVAL when D launches of 2 S workgroups cannot fit (64 streams: D <= 2 with sixteen waves, <= 4 with twelve or eight).
  * HotLoop(window=1, overlap=D) drives it. */
 #define AV_STEP_FLAG_INTS(n_streams) (65 * (n_streams) + ((n_streams) & 1) + 32 + 64)
-int av_hot_step_seq(av_ctx* ctx, av_stream_t stream, const av_tracker_cfg* tracker_cfg, const av_kf_cfg* kf_cfg, int n_streams, int h,
-                    int w, int dcap, int tcap, int32_t* frame_count, int32_t* det_n, int32_t* det_box, int32_t* det_cls,
-                    double* det_conf, int32_t* det_status, void* tracker_state, av_track_row* snap, int32_t* snap_n, int32_t* det2trk,
-                    const double* z, double* kf_state, double* vstate, double* plan_state, double* waypoints, double* cost,
-                    int32_t* order, void* wire, int stream0, int frame0, int32_t* seq_flags, int seq, int depth);
+#define AV_STEP_MAX_DEPTH 4
+int av_hot_step_seq(av_ctx* ctx, av_stream_t stream, const av_step_loop* loop, const av_step_set* set, void* wire, int stream0,
+                    int frame0, int32_t* seq_flags, int seq, int depth);
 
 /* n_steps consecutive overlapped steps (seq0, seq0 + 1, ...) enqueued by ONE call: the launch loop of av_hot_step_seq in C (a Python
  * caller spends 8 us per launch, the device 6-7), with `depth` (2 .. AV_STEP_MAX_DEPTH) steps in flight: step q runs on
@@ -796,20 +811,8 @@ int av_hot_step_seq(av_ctx* ctx, av_stream_t stream, const av_tracker_cfg* track
  * in flight have to fit on the device together (depth * 2 S workgroups, two per CU): AV_EINVAL otherwise.
  *   z_steps     NULL (every step reads its set's z), or [n_steps][S][4]: the measurements of step seq0 + i at z_steps + i * S * 4
  *   wire_steps  NULL, or [n_steps][S][av_wire_table_bytes(tcap)]: every step's wire tables (the per-frame all-gather's payload) */
-#define AV_STEP_MAX_DEPTH 4
-typedef struct av_step_set {
-    int32_t *det_n, *det_box, *det_cls;
-    double* det_conf;
-    av_track_row* snap;
-    int32_t *snap_n, *det2trk;
-    const double* z;
-    double *vstate, *plan_state, *waypoints, *cost;
-    int32_t* order;
-} av_step_set;
-int av_hot_steps_seq(av_ctx* ctx, int depth, const av_stream_t* streams, const av_tracker_cfg* tracker_cfg, const av_kf_cfg* kf_cfg,
-                     int n_streams, int h, int w, int dcap, int tcap, int32_t* frame_count, int32_t* det_status, void* tracker_state,
-                     double* kf_state, const av_step_set* sets, const double* z_steps, void* wire_steps, int stream0, int frame0,
-                     int32_t* seq_flags, int seq0, int n_steps);
+int av_hot_steps_seq(av_ctx* ctx, int depth, const av_stream_t* streams, const av_step_loop* loop, const av_step_set* sets,
+                     const double* z_steps, void* wire_steps, int stream0, int frame0, int32_t* seq_flags, int seq0, int n_steps);
 
 #ifdef __cplusplus
 }

@@ -23,6 +23,19 @@ class KfCfg(C.Structure):
     _fields_ = [("dt", C.c_double), ("process_noise", C.c_double), ("measurement_noise", C.c_double)]
 
 
+class StepSet(C.Structure):
+    """av_step_set: the buffers one step of the one-launch step reads and writes."""
+    _fields_ = [(k, C.c_void_p) for k in ("det_n", "det_box", "det_cls", "det_conf", "snap", "snap_n", "det2trk", "z", "vstate",
+                                          "plan_state", "waypoints", "cost", "order")]
+
+
+class StepLoop(C.Structure):
+    """av_step_loop: what all steps of a loop share."""
+    _fields_ = ([("tracker_cfg", TrackerCfg), ("kf_cfg", KfCfg)] +
+                [(k, C.c_int32) for k in ("n_streams", "h", "w", "dcap", "tcap", "reserved")] +
+                [(k, C.c_void_p) for k in ("frame_count", "det_status", "tracker_state", "kf_state")])
+
+
 class PlannerCfg(C.Structure):
     _fields_ = [("planning_horizon", C.c_double), ("dt", C.c_double), ("num_samples", C.c_int32),
                 ("reserved", C.c_int32), ("w_lateral", C.c_double), ("w_velocity", C.c_double),
@@ -147,14 +160,13 @@ _SIGS = [
     ("av_dets_to_tracker", C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
     ("av_lane_paths", C.c_int, [vp, vp, C.POINTER(ObstacleCfg), C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int,
                                 C.c_int, vp, vp, vp]),
-    ("av_hot_step", C.c_int, [vp, vp, C.POINTER(TrackerCfg), C.POINTER(KfCfg)] + [C.c_int] * 5 + [vp] * 17 + [vp, C.c_int, C.c_int]),
+    ("av_hot_step", C.c_int, [vp, vp, C.POINTER(StepLoop), C.POINTER(StepSet), vp, C.c_int, C.c_int]),
     ("av_hot_step_fits", C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     ("av_hot_step_plan", C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                    C.POINTER(C.c_size_t)]),
-    ("av_hot_steps_seq", C.c_int, [vp, C.c_int, vp, C.POINTER(TrackerCfg), C.POINTER(KfCfg)] + [C.c_int] * 5 + [vp] * 7 +
-     [C.c_int, C.c_int, vp, C.c_int, C.c_int]),
-    ("av_hot_step_seq", C.c_int, [vp, vp, C.POINTER(TrackerCfg), C.POINTER(KfCfg)] + [C.c_int] * 5 + [vp] * 17 +
-     [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int]),
+    ("av_hot_step_seq", C.c_int, [vp, vp, C.POINTER(StepLoop), C.POINTER(StepSet), vp, C.c_int, C.c_int, vp, C.c_int, C.c_int]),
+    ("av_hot_steps_seq", C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(StepLoop), C.POINTER(StepSet), vp, vp, C.c_int, C.c_int, vp,
+                                   C.c_int, C.c_int]),
     ("av_planner_generate", C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp]),
     ("av_planner_evaluate", C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp]),
     ("av_planner_evaluate_moving", C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp]),
@@ -286,12 +298,6 @@ def step_i32(v):
     """A step number (kept modulo 2^32) as the signed int the C ABI takes."""
     v &= 0xFFFFFFFF
     return v - (1 << 32) if v & 0x80000000 else v
-
-
-class StepSet(C.Structure):
-    """av_step_set: the per-step buffers of one parity (av_hot_steps_seq)."""
-    _fields_ = [(k, C.c_void_p) for k in ("det_n", "det_box", "det_cls", "det_conf", "snap", "snap_n", "det2trk", "z", "vstate",
-                                          "plan_state", "waypoints", "cost", "order")]
 
 
 def check(rc):

@@ -72,7 +72,7 @@ constexpr int STEP_NW = 8;
 //     bit-identical to the serial loop; tools/soak.py: 10^6 steps.
 // The per-step outputs (detections, snapshot rows, det2trk, Kalman output, waypoints, costs, order, wire table) rotate through D
 // buffer sets on the host side, so steps in flight never write the same output and the Kalman counter moves on before the
-// planner has run.  All launches in flight must be RESIDENT together (each may be waiting for the one before it): hot_step_args picks
+// planner has run.  All launches in flight must be RESIDENT together (each may be waiting for the one before it): hot_step_shape picks
 // sixteen, twelve or eight waves per workgroup from the occupancy and refuses a depth that does not fit.  Every wait is bounded: after `spin`
 // polls the workgroup sets the fault word (bit 0) and leaves without running its step, the launches behind it give up at once
 // (HotLoop.synchronize raises) -- no launch can hang on a lost predecessor.
@@ -340,128 +340,117 @@ static size_t hot_step_tracker_lds(int dcap, int tcap, int& stage_off) {
     return lds_t + HDR_INTS * 4 + (size_t)tcap * sizeof(av_track_row);
 }
 
-static size_t hot_step_static_lds(const void* kernel) {
+// A workgroup shape of the step kernel: waves per workgroup, the kernel (for the launch and for the attribute and occupancy queries)
+// and its static __shared__ (the Kalman bodies' arrays), which counts against the same 64 KB as the dynamic LDS.
+struct StepShape {
+    int waves;
+    const void* fn;
+    size_t lds_static;
+};
+template <int PW>
+static StepShape hot_step_shape_of() {
+    const void* fn = reinterpret_cast<const void*>(hot_step_kernel<PW>);
     hipFuncAttributes fa{};
-    return hipFuncGetAttributes(&fa, kernel) == hipSuccess ? (size_t)fa.sharedSizeBytes : (size_t)16384;
+    return {PW, fn, hipFuncGetAttributes(&fa, fn) == hipSuccess ? (size_t)fa.sharedSizeBytes : (size_t)16384};
 }
+// a launch as hot_step_shape decided it: the shape, the dynamic LDS (the larger of the tracker role's and the planner's), where in
+// it the tracker role's copy of the stream's table starts, and the occupancy answer for that shape (0 where it was not asked: depth 1)
+struct StepPlan {
+    const StepShape* shape;
+    size_t lds;
+    int stage_off, per_cu;
+};
 
-// the kernel of a workgroup shape, for the attribute and occupancy queries (hot_step_go launches them by name)
-static const void* hot_step_fn(int pw) {
-    return pw == 16 ? reinterpret_cast<const void*>(hot_step_kernel<16>)
-           : pw == 12 ? reinterpret_cast<const void*>(hot_step_kernel<12>)
-                      : reinterpret_cast<const void*>(hot_step_kernel<8>);
-}
-
-// dynamic LDS (the larger of the tracker role's and the planner's) and waves per workgroup of the one-launch step; AV_EINVAL where
-// no shape fits.  per_cu_out: the occupancy answer for the chosen shape (0 where it was not asked: depth 1)
-static int hot_step_shape(const av_ctx* ctx, int n_streams, size_t lds_t, int depth, size_t& lds_out, int& pw_out, int* per_cu_out = nullptr) {
+// AV_EINVAL where no shape fits
+static int hot_step_shape(const av_ctx* ctx, int n_streams, int dcap, int tcap, int depth, StepPlan& plan) {
     // Waves per workgroup: sixteen (the planner's 21 trajectories in two rounds, one workgroup per CU), else twelve (two rounds as
     // well -- the three phase-1 pair waves take one trajectory, the nine others two -- and two workgroups per CU: hot_step_kernel<12>
     // is held to 80 registers), else eight (three rounds, two per CU).  A shape is passed over when the planner's per-wave tiles do
     // not fit the LDS with it (n > 66 at 21 candidates and sixteen waves) or when `depth` launches in flight would not all be
     // resident -- every one of them may be waiting for the one before it, so depth x 2 S workgroups must fit on the device together;
     // residency is what the occupancy query answers for that instantiation, never assumed.  AVHOT_STEP_PW=8|12|16 forces one.
-    // static __shared__ of the kernel (the Kalman bodies' arrays) counts against the same 64 KB
-    static const size_t lds_static16 = hot_step_static_lds(hot_step_fn(16));
-    static const size_t lds_static12 = hot_step_static_lds(hot_step_fn(12));
-    static const size_t lds_static8 = hot_step_static_lds(hot_step_fn(8));
+    static const StepShape shapes[3] = {hot_step_shape_of<16>(), hot_step_shape_of<12>(), hot_step_shape_of<8>()};      // (queried once)
+    int stage_off = 0;
+    const size_t lds_t = hot_step_tracker_lds(dcap, tcap, stage_off);
     const char* pwe = getenv("AVHOT_STEP_PW");
     const int forced = pwe ? atoi(pwe) : 0;
-    int pw = forced == 8 || forced == 12 ? forced : 16;
-    size_t lds = 0;
-    int per_cu = 0;
-    for (;; pw = pw == 16 ? 12 : 8) {                 // (left by break; a shape that does not fit falls to the next one unless it was forced)
-        const size_t lds_p = plan_lds_doubles(1, ctx->n_points, ctx->n_cand, pw) * 8;
-        lds = lds_t > lds_p ? lds_t : lds_p;
-        const size_t lds_static = pw == 16 ? lds_static16 : pw == 12 ? lds_static12 : lds_static8;
-        if (lds + lds_static > 64 * 1024) {
-            AV_REQUIRE(pw > 8 && !pwe, AV_EINVAL,
-                       "av_hot_step: configuration needs %zu B of dynamic + %zu B of static LDS (limit 65536)", lds, lds_static);
+    // (left by return; a shape that does not fit falls to the next one unless it was forced)
+    for (const StepShape* sh = shapes + (forced == 8 ? 2 : forced == 12 ? 1 : 0);; ++sh) {
+        const size_t lds_p = plan_lds_doubles(1, ctx->n_points, ctx->n_cand, sh->waves) * 8;
+        const size_t lds = lds_t > lds_p ? lds_t : lds_p;
+        int per_cu = 0;
+        if (lds + sh->lds_static > 64 * 1024) {
+            AV_REQUIRE(sh->waves > 8 && !pwe, AV_EINVAL,
+                       "av_hot_step: configuration needs %zu B of dynamic + %zu B of static LDS (limit 65536)", lds, sh->lds_static);
             continue;
         }
-        if (depth <= 1) break;
-        AV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hot_step_fn(pw), pw * 64, lds));
-        if ((long long)depth * 2 * n_streams <= (long long)per_cu * ctx->n_cus) break;
-        AV_REQUIRE(pw > 8 && !pwe, AV_EINVAL, "av_hot_step: %d launches of %d workgroups in flight do not fit the device (%d per CU x %d CUs)",
-                   depth, 2 * n_streams, per_cu, ctx->n_cus);
+        if (depth > 1) {
+            AV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sh->fn, sh->waves * 64, lds));
+            if ((long long)depth * 2 * n_streams > (long long)per_cu * ctx->n_cus) {
+                AV_REQUIRE(sh->waves > 8 && !pwe, AV_EINVAL,
+                           "av_hot_step: %d launches of %d workgroups in flight do not fit the device (%d per CU x %d CUs)", depth,
+                           2 * n_streams, per_cu, ctx->n_cus);
+                continue;
+            }
+        }
+        plan = StepPlan{sh, lds, stage_off, per_cu};
+        return AV_OK;
     }
-    lds_out = lds, pw_out = pw;
-    if (per_cu_out) *per_cu_out = per_cu;
-    return AV_OK;
 }
 
-// validates one step's arguments and fills its kernel arguments (lds: dynamic LDS bytes, pw: waves per workgroup)
-static int hot_step_args(av_ctx* ctx, const av_tracker_cfg* tcfg, const av_kf_cfg* kcfg, int n_streams, int h,
-                           int w, int dcap, int tcap, int32_t* frame_count, int32_t* det_n, int32_t* det_box, int32_t* det_cls,
-                           double* det_conf, int32_t* det_status, void* tracker_state, av_track_row* snap, int32_t* snap_n,
-                           int32_t* det2trk, const double* z, double* kf_state, double* vstate, double* plan_state,
-                           double* waypoints, double* cost, int32_t* order, void* wire, int stream0, int frame0, int32_t* seq_flags,
-                           int seq, StepArgs& a, size_t& lds_out, int& pw_out, int depth = 1) {
-    AV_REQUIRE(ctx && tcfg && kcfg && frame_count && det_n && det_box && det_cls && det_conf && tracker_state && z && kf_state &&
-                   vstate && plan_state && cost && order,
-               AV_EINVAL, "av_hot_step: null argument");
-    AV_REQUIRE(n_streams > 0, AV_EINVAL, "av_hot_step: n_streams must be > 0");
+// Validates the arguments of the steps of one call -- one per buffer set, n_sets of them, all with step number seq -- fills their
+// kernel arguments par[0 .. n_sets) and decides the launch they share.  z_steps: read instead of the sets' z where given.
+static int hot_step_prepare(av_ctx* ctx, const av_step_loop* loop, const av_step_set* sets, int n_sets, const double* z_steps, void* wire,
+                            int stream0, int frame0, int32_t* seq_flags, int seq, int depth, StepArgs* par, StepPlan& plan) {
+    AV_REQUIRE(ctx && loop && sets, AV_EINVAL, "av_hot_step: null argument");
+    const av_step_loop& l = *loop;
+    for (int k = 0; k < n_sets; ++k) {
+        const av_step_set& b = sets[k];
+        AV_REQUIRE(l.frame_count && b.det_n && b.det_box && b.det_cls && b.det_conf && l.tracker_state && (z_steps || b.z) && l.kf_state &&
+                       b.vstate && b.plan_state && b.cost && b.order,
+                   AV_EINVAL, "av_hot_step: null argument");
+    }
+    AV_REQUIRE(l.n_streams > 0, AV_EINVAL, "av_hot_step: n_streams must be > 0");
     AV_REQUIRE(ctx->planner_ready && ctx->d_simtab, AV_ESTATE, "av_hot_step: call av_planner_configure first");
-    AV_REQUIRE((snap == nullptr) == (snap_n == nullptr), AV_EINVAL, "av_hot_step: snap and snap_n go together");
-    AV_REQUIRE(!wire || snap, AV_EINVAL, "av_hot_step: the wire tables are made from the snapshot rows");
+    for (int k = 0; k < n_sets; ++k) {
+        AV_REQUIRE((sets[k].snap == nullptr) == (sets[k].snap_n == nullptr), AV_EINVAL, "av_hot_step: snap and snap_n go together");
+        AV_REQUIRE(!wire || sets[k].snap, AV_EINVAL, "av_hot_step: the wire tables are made from the snapshot rows");
+    }
     // the shapes the one-launch step is built for; anything else keeps the four stage calls
-    AV_REQUIRE(tcap == 64 && dcap >= 7 && dcap <= 8 && tcfg->iou_threshold > 0.0 && tcfg->trajectory_length >= 1, AV_EINVAL,
-               "av_hot_step: needs tcap 64, dcap 7..8 and iou_threshold > 0 (use the stage calls otherwise)");
-    AV_REQUIRE(h > 0 && w > 121, AV_EINVAL, "av_hot_step: frame %dx%d too small", w, h);
-    a = StepArgs{};
-    a.S = n_streams, a.h = h, a.w = w, a.dcap = dcap, a.tcap = tcap;
-    a.tcfg = *tcfg, a.kcfg = *kcfg;
-    fill_params(ctx, a.pp);
-    a.frame_count = frame_count, a.tab = (const SimRow*)ctx->d_simtab, a.cdf = ctx->d_cdf;
-    a.det_n = det_n, a.det_box = det_box, a.det_cls = det_cls, a.det_conf = det_conf, a.det_status = det_status;
-    a.trk_state = (unsigned char*)tracker_state, a.snap = snap, a.snap_n = snap_n, a.det2trk = det2trk;
-    a.z = z, a.kf_state = kf_state, a.vstate = vstate, a.plan_state = plan_state;
-    a.wp = waypoints, a.cost = cost, a.order = order;
-    a.wire = (uint8_t*)wire, a.stream0 = stream0, a.frame0 = frame0;
+    AV_REQUIRE(l.tcap == 64 && l.dcap >= 7 && l.dcap <= 8 && l.tracker_cfg.iou_threshold > 0.0 && l.tracker_cfg.trajectory_length >= 1,
+               AV_EINVAL, "av_hot_step: needs tcap 64, dcap 7..8 and iou_threshold > 0 (use the stage calls otherwise)");
+    AV_REQUIRE(l.h > 0 && l.w > 121, AV_EINVAL, "av_hot_step: frame %dx%d too small", l.w, l.h);
     AV_REQUIRE(((uintptr_t)seq_flags & 7) == 0, AV_EINVAL, "av_hot_step: the sequence flags must be 8-byte aligned (64-bit phase clocks in their last 64 words)");
+    const int rc = hot_step_shape(ctx, l.n_streams, l.dcap, l.tcap, depth, plan);
+    if (rc != AV_OK) return rc;
+    StepArgs a{};
+    a.S = l.n_streams, a.h = l.h, a.w = l.w, a.dcap = l.dcap, a.tcap = l.tcap;
+    a.tcfg = l.tracker_cfg, a.kcfg = l.kf_cfg;
+    fill_params(ctx, a.pp);
+    a.frame_count = l.frame_count, a.tab = (const SimRow*)ctx->d_simtab, a.cdf = ctx->d_cdf;
+    a.det_status = l.det_status, a.trk_state = (unsigned char*)l.tracker_state, a.kf_state = l.kf_state;
+    a.wire = (uint8_t*)wire, a.stream0 = stream0, a.frame0 = frame0;
     a.flags = seq_flags, a.seq = seq;
     const char* spe = seq_flags ? getenv("AVHOT_STEP_SPIN") : nullptr;
     a.spin = spe ? atoi(spe) : (1 << 22);
     const char* fe = seq_flags ? getenv("AVHOT_STEP_FENCE") : nullptr;
     a.fence = fe ? atoi(fe) : 0;     // (debug: 1 = full agent-scope acquire in every role, the form the comment above prices)
-    int stage_off = 0;
-    const size_t lds_t = hot_step_tracker_lds(dcap, tcap, stage_off);
-    a.stage_off = stage_off;
-    return hot_step_shape(ctx, n_streams, lds_t, depth, lds_out, pw_out);
-}
-
-static int hot_step_go(const StepArgs& a, size_t lds, int pw, av_stream_t stream) {
-    if (pw == 16) hipLaunchKernelGGL(hot_step_kernel<16>, dim3(2 * a.S), dim3(16 * 64), lds, as_stream(stream), a);
-    else if (pw == 12) hipLaunchKernelGGL(hot_step_kernel<12>, dim3(2 * a.S), dim3(12 * 64), lds, as_stream(stream), a);
-    else hipLaunchKernelGGL(hot_step_kernel<8>, dim3(2 * a.S), dim3(8 * 64), lds, as_stream(stream), a);
-    AV_LAUNCH_CHECK();
+    a.stage_off = plan.stage_off;
+    for (int k = 0; k < n_sets; ++k) {
+        const av_step_set& b = sets[k];
+        a.det_n = b.det_n, a.det_box = b.det_box, a.det_cls = b.det_cls, a.det_conf = b.det_conf;
+        a.snap = b.snap, a.snap_n = b.snap_n, a.det2trk = b.det2trk;
+        a.z = z_steps ? z_steps : b.z, a.vstate = b.vstate, a.plan_state = b.plan_state;
+        a.wp = b.waypoints, a.cost = b.cost, a.order = b.order;
+        par[k] = a;
+    }
     return AV_OK;
 }
 
-static int hot_step_launch(av_ctx* ctx, av_stream_t stream, const av_tracker_cfg* tcfg, const av_kf_cfg* kcfg, int n_streams, int h,
-                           int w, int dcap, int tcap, int32_t* frame_count, int32_t* det_n, int32_t* det_box, int32_t* det_cls,
-                           double* det_conf, int32_t* det_status, void* tracker_state, av_track_row* snap, int32_t* snap_n,
-                           int32_t* det2trk, const double* z, double* kf_state, double* vstate, double* plan_state,
-                           double* waypoints, double* cost, int32_t* order, void* wire, int stream0, int frame0, int32_t* seq_flags,
-                           int seq, int depth = 1) {
-    StepArgs a;
-    size_t lds;
-    int pw;
-    const int rc = hot_step_args(ctx, tcfg, kcfg, n_streams, h, w, dcap, tcap, frame_count, det_n, det_box, det_cls, det_conf, det_status,
-                                 tracker_state, snap, snap_n, det2trk, z, kf_state, vstate, plan_state, waypoints, cost, order, wire, stream0,
-                                 frame0, seq_flags, seq, a, lds, pw, depth);
-    return rc != AV_OK ? rc : hot_step_go(a, lds, pw, stream);
-}
-
-extern "C" int av_hot_step_fits(av_ctx* ctx, int n_streams, int dcap, int tcap, int depth) {
-    AV_REQUIRE(ctx && n_streams > 0 && depth >= 1, AV_EINVAL, "av_hot_step_fits: bad argument");
-    AV_REQUIRE(ctx->planner_ready, AV_ESTATE, "av_hot_step_fits: call av_planner_configure first");
-    AV_REQUIRE(tcap == 64 && dcap >= 7 && dcap <= 8, AV_EINVAL, "av_hot_step_fits: needs tcap 64, dcap 7..8");
-    AV_HIP(hipSetDevice(ctx->device));
-    int stage_off = 0;
-    size_t lds = 0;
-    int pw = 0;
-    return hot_step_shape(ctx, n_streams, hot_step_tracker_lds(dcap, tcap, stage_off), depth, lds, pw);
+static int hot_step_go(const StepArgs& a, const StepPlan& p, av_stream_t stream) {
+    void* args[] = {const_cast<StepArgs*>(&a)};
+    AV_HIP(hipLaunchKernel(p.shape->fn, dim3(2 * a.S), dim3(p.shape->waves * 64), args, p.lds, as_stream(stream)));
+    return AV_OK;
 }
 
 extern "C" int av_hot_step_plan(av_ctx* ctx, int n_streams, int dcap, int tcap, int depth, int* waves, int* per_cu, size_t* lds_bytes) {
@@ -469,67 +458,58 @@ extern "C" int av_hot_step_plan(av_ctx* ctx, int n_streams, int dcap, int tcap, 
     AV_REQUIRE(ctx->planner_ready, AV_ESTATE, "av_hot_step_plan: call av_planner_configure first");
     AV_REQUIRE(tcap == 64 && dcap >= 7 && dcap <= 8, AV_EINVAL, "av_hot_step_plan: needs tcap 64, dcap 7..8");
     AV_HIP(hipSetDevice(ctx->device));
-    int stage_off = 0, pw = 0, pc = 0;
-    size_t lds = 0;
-    const int rc = hot_step_shape(ctx, n_streams, hot_step_tracker_lds(dcap, tcap, stage_off), depth, lds, pw, &pc);
+    StepPlan p;
+    const int rc = hot_step_shape(ctx, n_streams, dcap, tcap, depth, p);
     if (rc != AV_OK) return rc;
-    if (waves) *waves = pw;
-    if (per_cu) *per_cu = pc;
-    if (lds_bytes) *lds_bytes = lds;
+    if (waves) *waves = p.shape->waves;
+    if (per_cu) *per_cu = p.per_cu;
+    if (lds_bytes) *lds_bytes = p.lds;
     return AV_OK;
 }
 
-extern "C" int av_hot_step(av_ctx* ctx, av_stream_t stream, const av_tracker_cfg* tcfg, const av_kf_cfg* kcfg, int n_streams, int h,
-                           int w, int dcap, int tcap, int32_t* frame_count, int32_t* det_n, int32_t* det_box, int32_t* det_cls,
-                           double* det_conf, int32_t* det_status, void* tracker_state, av_track_row* snap, int32_t* snap_n,
-                           int32_t* det2trk, const double* z, double* kf_state, double* vstate, double* plan_state,
-                           double* waypoints, double* cost, int32_t* order, void* wire, int stream0, int frame0) {
-    return hot_step_launch(ctx, stream, tcfg, kcfg, n_streams, h, w, dcap, tcap, frame_count, det_n, det_box, det_cls, det_conf, det_status,
-                           tracker_state, snap, snap_n, det2trk, z, kf_state, vstate, plan_state, waypoints, cost, order, wire, stream0,
-                           frame0, nullptr, 0);
+extern "C" int av_hot_step_fits(av_ctx* ctx, int n_streams, int dcap, int tcap, int depth) {
+    return av_hot_step_plan(ctx, n_streams, dcap, tcap, depth, nullptr, nullptr, nullptr);
 }
 
-extern "C" int av_hot_step_seq(av_ctx* ctx, av_stream_t stream, const av_tracker_cfg* tcfg, const av_kf_cfg* kcfg, int n_streams, int h,
-                               int w, int dcap, int tcap, int32_t* frame_count, int32_t* det_n, int32_t* det_box, int32_t* det_cls,
-                               double* det_conf, int32_t* det_status, void* tracker_state, av_track_row* snap, int32_t* snap_n,
-                               int32_t* det2trk, const double* z, double* kf_state, double* vstate, double* plan_state,
-                               double* waypoints, double* cost, int32_t* order, void* wire, int stream0, int frame0,
-                               int32_t* seq_flags, int seq, int depth) {
+static_assert(sizeof(av_step_set) == 104 && sizeof(av_step_loop) == 104, "av_step_set / av_step_loop: the layouts the bindings mirror");
+
+extern "C" int av_hot_step(av_ctx* ctx, av_stream_t stream, const av_step_loop* loop, const av_step_set* set, void* wire, int stream0,
+                           int frame0) {
+    StepArgs a;
+    StepPlan p;
+    const int rc = hot_step_prepare(ctx, loop, set, 1, nullptr, wire, stream0, frame0, nullptr, 0, 1, &a, p);
+    return rc != AV_OK ? rc : hot_step_go(a, p, stream);
+}
+
+extern "C" int av_hot_step_seq(av_ctx* ctx, av_stream_t stream, const av_step_loop* loop, const av_step_set* set, void* wire, int stream0,
+                               int frame0, int32_t* seq_flags, int seq, int depth) {
     AV_REQUIRE(seq_flags, AV_EINVAL, "av_hot_step_seq: needs the sequence flags (AV_STEP_FLAG_INTS(n_streams) int32)");
     AV_REQUIRE(depth >= 2 && depth <= AV_STEP_MAX_DEPTH, AV_EINVAL, "av_hot_step_seq: depth %d not in [2, %d]", depth, AV_STEP_MAX_DEPTH);
-    return hot_step_launch(ctx, stream, tcfg, kcfg, n_streams, h, w, dcap, tcap, frame_count, det_n, det_box, det_cls, det_conf, det_status,
-                           tracker_state, snap, snap_n, det2trk, z, kf_state, vstate, plan_state, waypoints, cost, order, wire, stream0,
-                           frame0, seq_flags, seq, depth);
+    StepArgs a;
+    StepPlan p;
+    const int rc = hot_step_prepare(ctx, loop, set, 1, nullptr, wire, stream0, frame0, seq_flags, seq, depth, &a, p);
+    return rc != AV_OK ? rc : hot_step_go(a, p, stream);
 }
 
-extern "C" int av_hot_steps_seq(av_ctx* ctx, int depth, const av_stream_t* streams, const av_tracker_cfg* tcfg, const av_kf_cfg* kcfg,
-                                int n_streams, int h, int w, int dcap, int tcap, int32_t* frame_count, int32_t* det_status,
-                                void* tracker_state, double* kf_state, const av_step_set* sets, const double* z_steps, void* wire_steps,
-                                int stream0, int frame0, int32_t* seq_flags, int seq0, int n_steps) {
+extern "C" int av_hot_steps_seq(av_ctx* ctx, int depth, const av_stream_t* streams, const av_step_loop* loop, const av_step_set* sets,
+                                const double* z_steps, void* wire_steps, int stream0, int frame0, int32_t* seq_flags, int seq0, int n_steps) {
     AV_REQUIRE(seq_flags && n_steps > 0 && sets && streams, AV_EINVAL, "av_hot_steps_seq: bad argument");
     AV_REQUIRE(depth >= 2 && depth <= AV_STEP_MAX_DEPTH, AV_EINVAL, "av_hot_steps_seq: depth %d not in [2, %d]", depth, AV_STEP_MAX_DEPTH);
     for (int k = 0; k < depth; ++k)
         for (int j = 0; j < k; ++j)
             AV_REQUIRE(streams[k] != streams[j], AV_EINVAL, "av_hot_steps_seq: the %d steps in flight need %d different HIP streams", depth, depth);
     StepArgs par[AV_STEP_MAX_DEPTH];
-    size_t lds = 0;
-    int pw = 16;
-    for (int k = 0; k < depth; ++k) {
-        const av_step_set& b = sets[k];
-        const int rc = hot_step_args(ctx, tcfg, kcfg, n_streams, h, w, dcap, tcap, frame_count, b.det_n, b.det_box, b.det_cls, b.det_conf, det_status,
-                                     tracker_state, b.snap, b.snap_n, b.det2trk, z_steps ? z_steps : b.z, kf_state, b.vstate, b.plan_state,
-                                     b.waypoints, b.cost, b.order, wire_steps, stream0, frame0, seq_flags, seq0, par[k], lds, pw, depth);
-        if (rc != AV_OK) return rc;
-    }
-    const size_t zb = (size_t)n_streams * 4, wb = (size_t)n_streams * (AV_WIRE_HDR_BYTES + (size_t)tcap * AV_WIRE_ROW_BYTES);
+    StepPlan p;
+    int rc = hot_step_prepare(ctx, loop, sets, depth, z_steps, wire_steps, stream0, frame0, seq_flags, seq0, depth, par, p);
+    if (rc != AV_OK) return rc;
+    const size_t zb = (size_t)par[0].S * 4, wb = (size_t)par[0].S * (AV_WIRE_HDR_BYTES + (size_t)par[0].tcap * AV_WIRE_ROW_BYTES);
     for (int i = 0; i < n_steps; ++i) {
         const int q = (int)((unsigned)seq0 + (unsigned)i), k = (int)((unsigned)q % (unsigned)depth);      // (32-bit step numbers wrap)
         StepArgs& a = par[k];
         a.seq = q;
         if (z_steps) a.z = z_steps + (size_t)i * zb;
         if (wire_steps) a.wire = (uint8_t*)wire_steps + (size_t)i * wb;
-        const int rc = hot_step_go(a, lds, pw, streams[k]);
-        if (rc != AV_OK) return rc;
+        if ((rc = hot_step_go(a, p, streams[k])) != AV_OK) return rc;
     }
     return AV_OK;
 }

@@ -39,9 +39,10 @@ class HotLoop:
         step's LDS: av_hot_step_fits); True where it does not raises ValueError.
         overlap=2 (fused step only): consecutive steps are launched alternately on two HIP streams and ordered per stream and
         role on the device (av_hot_step_seq), so step t + 1 starts while step t's planner is still writing.  The per-step
-        buffers (det_*, snap, snap_n, det2trk, z, vstate, plan_state, wp, cost, order) then exist twice; the attributes always
-        name the set of the step enqueued LAST (for `z`: the set the NEXT step will read), and that set is next written by
-        the step after the next one.  Same results as overlap=1 bit for bit.
+        buffers (det_*, snap, snap_n, det2trk, z, vstate, plan_state, wp, cost, order) are kept as `overlap` buffer sets (one
+        at overlap=1), each with its av_step_set made once; the attributes always name the set of the step enqueued LAST (for
+        `z`: the set the NEXT step will read), and that set is next written by the step `overlap` steps on.  Same results as
+        overlap=1 bit for bit.
         obstacles="tracks": every frame's confirmed tracks become that frame's planner obstacles (av_track_obstacles: where the
         BEV panel draws them, in the planner's frame) and the planner runs per state (av_planner_plan_each) behind the tracker;
         self.obstacles [S, W, tcap, 3] / self.n_obs [S, W].  obstacle_kw overrides av_obstacle_cfg's fields (x_center, x_scale,
@@ -54,15 +55,16 @@ class HotLoop:
         if not torch.cuda.is_available():
             raise RuntimeError("HotLoop needs a HIP device; this package has no CPU path")
         self.S, self.W, self.h, self.w, self.tcap, self.dcap = n_streams, window, h, w, tcap, dcap
+        self.overlap = int(overlap)
+        if self.overlap not in (1, 2, 3, 4):
+            raise ValueError("overlap is 1 .. 4")
         self.dev = torch.device("cuda", device)
         self.ctx = ctx or nat.Context(device)
         self.L = nat.lib()
         tk = dict(iou_threshold=0.3, max_age=30, min_hits=3, trajectory_length=50)
         tk.update(tracker_kw or {})
-        self.tcfg = nat.TrackerCfg(**tk)
         kk = dict(dt=0.033, process_noise=0.1, measurement_noise=1.0)
         kk.update(kf_kw or {})
-        self.kcfg = nat.KfCfg(**kk)
         pk = dict(planning_horizon=5.0, dt=0.1, num_samples=7, w_lateral=1.0, w_velocity=0.5,
                   w_acceleration=0.3, w_curvature=0.4)
         pk.update(planner_kw or {})
@@ -75,27 +77,21 @@ class HotLoop:
         S, W, d = n_streams, window, self.dev
         i32, f64 = torch.int32, torch.float64
         self.frame_count = torch.zeros(S, dtype=i32, device=d)
-        self.det_n = torch.zeros(S, W, dtype=i32, device=d)
-        self.det_box = torch.zeros(S, W, dcap, 4, dtype=i32, device=d)
-        self.det_cls = torch.zeros(S, W, dcap, dtype=i32, device=d)
-        self.det_conf = torch.zeros(S, W, dcap, dtype=f64, device=d)
         self.det_status = torch.zeros(S, dtype=i32, device=d)
-        self.trk_bytes = int(self.L.av_tracker_state_bytes(tcap, self.tcfg.trajectory_length))
+        self.trk_bytes = int(self.L.av_tracker_state_bytes(tcap, tk["trajectory_length"]))
         self.trk_state = torch.zeros(S, self.trk_bytes, dtype=torch.uint8, device=d)
-        self.keep_snapshots = keep_snapshots
-        self.snap = torch.zeros(S, W, tcap, nat.TRACK_ROW_BYTES, dtype=torch.uint8, device=d) if keep_snapshots else None
-        self.snap_n = torch.zeros(S, W, dtype=i32, device=d) if keep_snapshots else None
-        self.det2trk = torch.zeros(S, W, dcap, dtype=i32, device=d)
-        self.z = torch.zeros(S, W, 4, dtype=f64, device=d)
         self.kf_state = torch.zeros(S, nat.KF_STATE_DOUBLES, dtype=f64, device=d)
-        self.vstate = torch.zeros(S, W, nat.VSTATE_DOUBLES, dtype=f64, device=d)
-        self.plan_state = torch.zeros(S, W, 4, dtype=f64, device=d)
-        self.keep_waypoints = keep_waypoints
-        self.wp = (torch.zeros(S * W, self.n_cand, self.n_points, nat.WP_DOUBLES, dtype=f64, device=d)
-                   if keep_waypoints else None)
-        self.cost = torch.zeros(S * W, self.n_cand, dtype=f64, device=d)
-        self.order = torch.zeros(S * W, self.n_cand, dtype=i32, device=d)
-        self.stream = torch.cuda.Stream(device=d)
+        # what all steps share, as the one-launch step takes it (av_step_loop); tcfg / kcfg are its members, not copies
+        self._cloop = nat.StepLoop(nat.TrackerCfg(**tk), nat.KfCfg(**kk), S, h, w, dcap, tcap, 0, self.frame_count.data_ptr(),
+                                   self.det_status.data_ptr(), self.trk_state.data_ptr(), self.kf_state.data_ptr())
+        self.tcfg, self.kcfg = self._cloop.tracker_cfg, self._cloop.kf_cfg
+        self.keep_snapshots, self.keep_waypoints = keep_snapshots, keep_waypoints
+        # the per-step buffers: `overlap` sets, each with its av_step_set; the attributes name one of them (reset(): the first)
+        self._sets = [self._new_set() for _ in range(self.overlap)]
+        self._csets = (nat.StepSet * self.overlap)(*[nat.StepSet(*[t.data_ptr() if t is not None else None for t in b.values()])
+                                                     for b in self._sets])
+        self.__dict__.update(self._sets[0])
+        self._use_streams([torch.cuda.Stream(device=d) for _ in range(self.overlap)])
         self.graph_id = None
         self._graphs = {}
         if obstacles not in (None, "tracks", "moving_tracks"):
@@ -129,19 +125,11 @@ class HotLoop:
         self.fused_step = can_fuse if fused_step is None else bool(fused_step)
         self.wire = None                  # set_wire(): the fused step also writes every stream's table in wire format
         self._wire_ids = (0, 0)
-        self.overlap = int(overlap)
-        if self.overlap not in (1, 2, 3, 4):
-            raise ValueError("overlap is 1 .. 4")
+        self._seq, self._stepped = 0, False
         if self.overlap > 1:
             if not self.fused_step:
                 raise ValueError("overlap=2 needs the fused step (window 1, tcap 64, dcap 7..8, iou_threshold > 0)")
-            names = [k for k in self._PER_STEP if getattr(self, k) is not None]
-            self._sets = [{k: getattr(self, k) for k in names}] + [{k: torch.zeros_like(getattr(self, k)) for k in names}
-                                                                   for _ in range(self.overlap - 1)]
-            self._pstreams = [self.stream] + [torch.cuda.Stream(device=d) for _ in range(self.overlap - 1)]
             self.seq_flags = torch.zeros(nat.step_flag_ints(S), dtype=i32, device=d)
-            self._seq, self._stepped = 0, False
-            self._csets = None
             self.reset()
             try:                              # (one step now: the library refuses a depth whose launches would not all be resident)
                 self._enqueue_step_seq()
@@ -166,8 +154,23 @@ class HotLoop:
             raise ValueError("obstacle_kw: at most 16 per-class radii")
         return nat.ObstacleCfg(radius=(C.c_double * 16)(*(rad + [0.0] * (16 - len(rad)))), **ok)
 
-    _PER_STEP = ("det_n", "det_box", "det_cls", "det_conf", "snap", "snap_n", "det2trk", "z", "vstate", "plan_state", "wp",
-                 "cost", "order")
+    def _new_set(self):
+        """One set of the per-step buffers, attribute name -> tensor (None: not kept), in av_step_set's member order (wp is its
+        `waypoints`)."""
+        S, W, d, i32, f64 = self.S, self.W, self.dev, torch.int32, torch.float64
+        zeros = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=d)
+        return dict(det_n=zeros(S, W, dtype=i32), det_box=zeros(S, W, self.dcap, 4, dtype=i32), det_cls=zeros(S, W, self.dcap, dtype=i32),
+                    det_conf=zeros(S, W, self.dcap, dtype=f64),
+                    snap=zeros(S, W, self.tcap, nat.TRACK_ROW_BYTES, dtype=torch.uint8) if self.keep_snapshots else None,
+                    snap_n=zeros(S, W, dtype=i32) if self.keep_snapshots else None, det2trk=zeros(S, W, self.dcap, dtype=i32),
+                    z=zeros(S, W, 4, dtype=f64), vstate=zeros(S, W, nat.VSTATE_DOUBLES, dtype=f64), plan_state=zeros(S, W, 4, dtype=f64),
+                    wp=zeros(S * W, self.n_cand, self.n_points, nat.WP_DOUBLES, dtype=f64) if self.keep_waypoints else None,
+                    cost=zeros(S * W, self.n_cand, dtype=f64), order=zeros(S * W, self.n_cand, dtype=i32))
+
+    def _use_streams(self, streams):
+        """The HIP streams the steps run on: step q on streams[q % overlap]; `stream` is the first."""
+        self._pstreams, self.stream = list(streams), streams[0]
+        self._cstreams = (C.c_void_p * self.overlap)(*[st.cuda_stream for st in streams])
 
     # ------------------------------------------------------------------------------------------
     @property
@@ -193,9 +196,8 @@ class HotLoop:
     def reset(self, frame_offsets=None):
         """Resets every stream (tracker.reset(), state_estimator.reset(), detector.reset())."""
         h, L = self.ctx.handle, self.L
-        if self.overlap > 1:
-            for st in self._pstreams:
-                st.synchronize()
+        for st in self._pstreams:
+            st.synchronize()
         nat.check(L.av_tracker_reset(h, self._s, self.S, self.tcap, self.tcfg.trajectory_length, nat.ptr(self.trk_state)))
         nat.check(L.av_kf_reset(h, self._s, self.S, nat.ptr(self.kf_state)))
         with torch.cuda.stream(self.stream):
@@ -206,25 +208,20 @@ class HotLoop:
             if self.overlap > 1:
                 self.seq_flags.zero_()
                 self.seq_flags[64 * self.S + 32:65 * self.S + 32].copy_(self.frame_count)
-        if self.overlap > 1:
-            self._seq, self._stepped = 0, False
-            self.__dict__.update(self._sets[0])
+        self._seq, self._stepped = 0, False
+        self.__dict__.update(self._sets[0])
         self.stream.synchronize()
 
     def load_measurements(self, z, all_sets=False):
-        """z: float64 [S, W, 4] ego measurements for the next window (host array).  overlap=2: for the next STEP (its buffer
-        set); all_sets=True: for every step from now on (both sets)."""
-        if self.overlap > 1:                  # the next step's set, on the next step's stream
-            zt = torch.as_tensor(np.ascontiguousarray(z, np.float64)).view(self.S, self.W, 4)
-            for k in (range(self.overlap) if all_sets else (self._seq % self.overlap,)):
-                with torch.cuda.stream(self._pstreams[k]):
-                    self._sets[k]["z"].copy_(zt)
-                self._pstreams[k].synchronize()
-            self.z = self._sets[self._seq % self.overlap]["z"]
-            return
-        with torch.cuda.stream(self.stream):
-            self.z.copy_(torch.as_tensor(np.ascontiguousarray(z, np.float64)).view(self.S, self.W, 4))
-        self.stream.synchronize()
+        """z: float64 [S, W, 4] ego measurements for the next window (host array).  overlap=2..: for the next STEP (its buffer
+        set, on its stream); all_sets=True: for every step from now on (all sets)."""
+        zt = torch.as_tensor(np.ascontiguousarray(z, np.float64)).view(self.S, self.W, 4)
+        nxt = self._seq % self.overlap
+        for k in (range(self.overlap) if all_sets else (nxt,)):
+            with torch.cuda.stream(self._pstreams[k]):
+                self._sets[k]["z"].copy_(zt)
+            self._pstreams[k].synchronize()
+        self.z = self._sets[nxt]["z"]
 
     # ---- individual stages (enqueue only) --------------------------------------------------------
     def enqueue_detect(self, stream=None):
@@ -536,13 +533,7 @@ class HotLoop:
         """Window 1: detect + track + Kalman + plan of one frame of every stream as ONE launch."""
         if self.overlap > 1:
             return self._enqueue_step_seq(stream)
-        nat.check(self.L.av_hot_step(self.ctx.handle, stream or self._s, C.byref(self.tcfg), C.byref(self.kcfg), self.S, self.h,
-                                     self.w, self.dcap, self.tcap, nat.ptr(self.frame_count), nat.ptr(self.det_n),
-                                     nat.ptr(self.det_box), nat.ptr(self.det_cls), nat.ptr(self.det_conf),
-                                     nat.ptr(self.det_status), nat.ptr(self.trk_state), nat.ptr(self.snap), nat.ptr(self.snap_n),
-                                     nat.ptr(self.det2trk), nat.ptr(self.z), nat.ptr(self.kf_state), nat.ptr(self.vstate),
-                                     nat.ptr(self.plan_state), nat.ptr(self.wp), nat.ptr(self.cost), nat.ptr(self.order),
-                                     nat.ptr(self.wire), self._wire_ids[0], self._wire_ids[1]))
+        nat.check(self.L.av_hot_step(self.ctx.handle, stream or self._s, self._cloop, self._csets[0], nat.ptr(self.wire), *self._wire_ids))
 
     def _enqueue_step_seq(self, stream=None):
         """overlap=D: step number self._seq on stream seq % D with buffer set seq % D, ordered behind step seq - 1 per stream and
@@ -550,15 +541,9 @@ class HotLoop:
         if stream is not None:
             raise RuntimeError("overlap=2.. launches on the loop's own streams")
         k = self._seq % self.overlap         # (_seq is kept modulo 2^32: the library's step numbers are 32-bit and wrap)
-        b = self._sets[k]
-        self.__dict__.update(b)              # the attributes name the set of the step enqueued last
-        nat.check(self.L.av_hot_step_seq(self.ctx.handle, C.c_void_p(self._pstreams[k].cuda_stream), C.byref(self.tcfg), C.byref(self.kcfg),
-                                         self.S, self.h, self.w, self.dcap, self.tcap, nat.ptr(self.frame_count), nat.ptr(b["det_n"]),
-                                         nat.ptr(b["det_box"]), nat.ptr(b["det_cls"]), nat.ptr(b["det_conf"]),
-                                         nat.ptr(self.det_status), nat.ptr(self.trk_state), nat.ptr(b.get("snap")), nat.ptr(b.get("snap_n")),
-                                         nat.ptr(b["det2trk"]), nat.ptr(b["z"]), nat.ptr(self.kf_state), nat.ptr(b["vstate"]),
-                                         nat.ptr(b["plan_state"]), nat.ptr(b.get("wp")), nat.ptr(b["cost"]), nat.ptr(b["order"]),
-                                         nat.ptr(self.wire), self._wire_ids[0], self._wire_ids[1], nat.ptr(self.seq_flags), self._i32(self._seq), self.overlap))
+        self.__dict__.update(self._sets[k])  # the attributes name the set of the step enqueued last
+        nat.check(self.L.av_hot_step_seq(self.ctx.handle, C.c_void_p(self._pstreams[k].cuda_stream), self._cloop, self._csets[k],
+                                         nat.ptr(self.wire), *self._wire_ids, nat.ptr(self.seq_flags), self._i32(self._seq), self.overlap))
         self._seq = (self._seq + 1) & 0xFFFFFFFF
         self._stepped = True
 
@@ -571,23 +556,14 @@ class HotLoop:
             raise RuntimeError("enqueue_steps needs overlap=2..")
         if n_steps <= 0:
             return
-        if self._csets is None:
-            def cset(b):
-                m = {"wp": "waypoints"}
-                return nat.StepSet(**{m.get(k, k): (b[k].data_ptr() if b.get(k) is not None else None) for k in self._PER_STEP})
-            self._csets = (nat.StepSet * self.overlap)(*[cset(b) for b in self._sets])
-            self._cstreams = (C.c_void_p * self.overlap)(*[st.cuda_stream for st in self._pstreams])
         if z_steps is not None and (z_steps.dtype != torch.float64 or z_steps.numel() != n_steps * self.S * 4 or not z_steps.is_contiguous()):
             raise ValueError("z_steps: contiguous float64 [n_steps, S, 4]")
         if wire_steps is not None:
             wb = int(self.L.av_wire_table_bytes(self.tcap))
             if not (self.keep_snapshots and wire_steps.dtype == torch.uint8 and wire_steps.numel() == n_steps * self.S * wb and wire_steps.is_contiguous()):
                 raise ValueError("wire_steps: contiguous uint8 [n_steps, S, %d] (and keep_snapshots=True)" % wb)
-        nat.check(self.L.av_hot_steps_seq(self.ctx.handle, self.overlap, self._cstreams,
-                                          C.byref(self.tcfg), C.byref(self.kcfg), self.S, self.h, self.w, self.dcap, self.tcap,
-                                          nat.ptr(self.frame_count), nat.ptr(self.det_status), nat.ptr(self.trk_state), nat.ptr(self.kf_state),
-                                          self._csets, nat.ptr(z_steps), nat.ptr(wire_steps),
-                                          self._wire_ids[0], self._wire_ids[1], nat.ptr(self.seq_flags), self._i32(self._seq), int(n_steps)))
+        nat.check(self.L.av_hot_steps_seq(self.ctx.handle, self.overlap, self._cstreams, self._cloop, self._csets, nat.ptr(z_steps),
+                                          nat.ptr(wire_steps), *self._wire_ids, nat.ptr(self.seq_flags), self._i32(self._seq), int(n_steps)))
         self._seq = (self._seq + int(n_steps)) & 0xFFFFFFFF
         self._stepped = True
         self.__dict__.update(self._sets[((self._seq - 1) & 0xFFFFFFFF) % self.overlap])
@@ -611,8 +587,7 @@ class HotLoop:
             sets.append([fresh[i] for i in sorted(rs.choice(len(fresh), D, replace=False))])
         tried = []
         for cand in sets:
-            self._pstreams, self.stream = list(cand), cand[0]
-            self._csets = None
+            self._use_streams(cand)
             self.reset()
             self.enqueue_steps(64)
             self.synchronize()
@@ -621,8 +596,7 @@ class HotLoop:
             self.synchronize()
             tried.append(((time.perf_counter() - t0) / steps * 1e6, cand))
         best = min(tried, key=lambda x: x[0])
-        self._pstreams, self.stream = list(best[1]), best[1][0]
-        self._csets = None
+        self._use_streams(best[1])
         self.reset()
         return [round(t, 2) for t, _ in tried]
 
@@ -685,14 +659,11 @@ class HotLoop:
             self.synchronize()
 
     def synchronize(self, check=True):
-        if self.overlap > 1:
-            for st in self._pstreams:
-                st.synchronize()
-            if check and int(self.seq_flags[64 * self.S].item()) != 0:
-                raise RuntimeError("HotLoop(overlap=%d): a step waited in vain for its predecessor (sequence flags: fault word set); "
-                                   "the state is no longer that of a serial run -- reset()" % self.overlap)
-            return
-        self.stream.synchronize()
+        for st in self._pstreams:
+            st.synchronize()
+        if self.overlap > 1 and check and int(self.seq_flags[64 * self.S].item()) != 0:
+            raise RuntimeError("HotLoop(overlap=%d): a step waited in vain for its predecessor (sequence flags: fault word set); "
+                               "the state is no longer that of a serial run -- reset()" % self.overlap)
 
     # ---- host views of the last window -------------------------------------------------------------
     def snapshots(self):

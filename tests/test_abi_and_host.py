@@ -21,7 +21,7 @@ def test_library_exports_every_declared_symbol(lib):
     assert len(names) >= 29
     for n in names:
         assert hasattr(lib, n), "libavhot.so lacks %s declared in include/avhot.h" % n
-    assert lib.av_version() == 102
+    assert lib.av_version() == 103
     assert {s[0] for s in nat._SIGS + nat._OPTIONAL_SIGS} >= set(names), "ctypes binding missing for a declared symbol"
 
 
@@ -30,6 +30,21 @@ def test_struct_layouts_match_header(lib):
     assert C.sizeof(nat.TrackerCfg) == 24 and C.sizeof(nat.KfCfg) == 24 and C.sizeof(nat.PlannerCfg) == 56
     assert lib.av_tracker_state_bytes(64, 50) == 64 + 64 * 64 + 64 * 50 * 32
     assert lib.av_tracker_state_bytes(0, 50) == 0
+
+
+def test_step_structs_match_header():
+    """nat.StepSet / nat.StepLoop against av_step_set / av_step_loop: the sizes the library asserts, the members in the header's order."""
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(root, "include", "avhot.h")).read(), flags=re.S)
+    hip = open(os.path.join(os.path.dirname(nat.LIB_PATH), "csrc", "step.hip")).read()
+    for cls, name in ((nat.StepSet, "av_step_set"), (nat.StepLoop, "av_step_loop")):
+        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), hdr, flags=re.S).group(1)
+        members = [m for decl in body.split(";") for m in re.findall(r"(\w+)\s*(?:,|$)", decl.strip())]
+        assert members == [f[0] for f in cls._fields_], name
+        assert C.sizeof(cls) == int(re.search(r"static_assert\(.*?sizeof\(%s\) == (\d+)" % name, hip).group(1)), name
+    assert C.sizeof(nat.StepSet) == 104 and len(nat.StepSet._fields_) == 13
+    assert nat.StepLoop.frame_count.offset % 8 == 0 and nat.StepLoop.frame_count.offset == nat.StepLoop.reserved.offset + 4
 
 
 def test_lane_stage_bits_and_view_ids_match_header():
@@ -64,6 +79,15 @@ def test_argument_validation_without_gpu(lib):
     assert lib.av_planner_configure(None, None) == -1
     assert lib.av_ctx_destroy(None) == 0
     assert lib.av_graph_launch(None, 0, None) == -1
+    # the one-launch step: a NULL context, av_step_loop or av_step_set is refused before anything is read or any HIP call made
+    # (ctx: never read here, any non-NULL address will do)
+    ctx, loop, one, flags = C.create_string_buffer(8), nat.StepLoop(), nat.StepSet(), (C.c_int32 * nat.step_flag_ints(1))()
+    sets, streams = (nat.StepSet * 2)(), (C.c_void_p * 2)(1, 2)
+    for c, l, s in ((None, loop, one), (ctx, None, one), (ctx, loop, None)):
+        assert lib.av_hot_step(c, None, l, s, None, 0, 0) == -1
+        assert lib.av_hot_step_seq(c, None, l, s, None, 0, 0, flags, 0, 2) == -1
+        assert lib.av_hot_steps_seq(c, 2, streams, l, sets if s else None, None, None, 0, 0, flags, 0, 1) == -1
+        assert (b"null argument" in lib.av_last_error_string()) == (s is not None)        # (no set array: "bad argument")
 
 
 def test_dataclass_surfaces():

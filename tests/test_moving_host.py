@@ -33,7 +33,7 @@ def test_exports_and_obstacle_cfg_layout(lib):
     for name in NEW:
         assert name in nat.declared_symbols() and hasattr(lib, name)
         assert name in {s[0] for s in nat._SIGS}
-    assert lib.av_version() == 102
+    assert lib.av_version() == 103
 
 
 def test_argument_validation_without_gpu(lib):

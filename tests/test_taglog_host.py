@@ -65,7 +65,7 @@ def test_header_constants_agree_with_the_vocabulary():
     assert set(hdr) == set(first) | {"COUNT", "HAS_SCENE", "HAS_MANEUVER", "HAS_INTERACTION"}
     assert int(re.search(r"#define\s+AV_TAGLOG_CHUNK\s+(\d+)", txt).group(1)) == nat.TAGLOG_CHUNK
     assert np.dtype(nat.TAGLOG_STATS_FIELDS).itemsize == nat.TAGLOG_STATS_BYTES
-    assert int(re.search(r"#define\s+AV_VERSION\s+(\d+)", txt).group(1)) == 102
+    assert int(re.search(r"#define\s+AV_VERSION\s+(\d+)", txt).group(1)) == 103
 
 
 def test_tag_mask_and_tags_of():
