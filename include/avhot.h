@@ -436,7 +436,8 @@ int av_lane_detect(av_ctx* ctx, av_stream_t stream, const av_lane_cfg* cfg, int 
  * is allocated here, once, and the launches of a forward are planned here: a shape that no kernel serves fails at creation.
  * Test hooks, read from the environment once per forward (a change re-plans the launches; outputs stay bit-identical, which is what
  * tests/test_gpu_yolo.py asserts with them): AVHOT_YOLO_NO_FUSE (one launch per layer: no fused front end, no fused C2f blocks, no
- * virtual Upsample + Concat), AVHOT_CONV_GENERIC80 (the 80-channel layers of the class branch on the generic kernels),
+ * virtual Upsample + Concat), AVHOT_CONV_GENERIC80 (the 80-channel layers of the class branch on the generic kernels, which have no
+ * decode epilogue: the class candidates and with them the detections are not written, the logits of av_yolo_keep_logits are),
  * AVHOT_CONV_NO_GEMM (no GEMM-form convolution), AVHOT_CONV_NO_GEMM_1X1 (none for the 1x1 layers), AVHOT_YOLO_GENERIC_PRE (the
  * generic letterbox kernel for every frame shape).  The library reads no other variable for this stage. */
 typedef struct av_yolo av_yolo;
@@ -476,6 +477,40 @@ int av_yolo_keep_logits(av_yolo* h, int enable);
  * anchor as the head wrote them: box float32 [A][4], confidence float32 [A], class int32 [A]; 120-122 = the same from the
  * stand-alone decode of the kept logits). */
 int av_yolo_tensor(const av_yolo* h, int id, void** ptr, int* H, int* W, int* C, int* cstride, int* coff);
+/* Test hook: the ops of the network as av_yolo_create built them, one per layer in execution order (what a forward under
+ * AVHOT_YOLO_NO_FUSE launches one by one), so that a test can read one layer's operands and output back and evaluate that layer alone
+ * (tests/test_gpu_yolo_layers.py does, in float64).  The query reads host memory only: it launches nothing, copies nothing and does
+ * not touch the plan.  A slice is `c` channels from channel `coff` of an NHWC map of `cstride` elements per pixel, H x W per image,
+ * image b at ptr + b H W cstride elements; ptr = NULL: the op has no such operand.  Convolutions (AV_YOLO_OP_CONV): weights with
+ * BatchNorm folded, half [cout][kpad] with k = tap cin + ci (tap = ky ksz + kx) and zeros from kreal on -- or, with wgt_f32 (the
+ * AV_YOLO_FP32 mode), float32 [cout][tap][cin] --, a float32 bias [cout], zero padding ksz / 2, out = act ? silu(.) : (.), then
+ * + res.  `out` is float32 for the head's last convolutions (written only with keep_logits or in float32 mode).  in2: the
+ * half-resolution map from which the default plan reads input channels [0, in2.c) of this 1x1 layer itself (virtual Upsample + Concat),
+ * instead of their upsampled copy in `in`.  AV_YOLO_OP_STEM: `in` is the network input WITH its one-pixel frame of zeros
+ * (in_frame = 1: no further padding), 4 channels per pixel, weights half [16][64] with k = 16 ky + 4 kx + c.  AV_YOLO_OP_POOLS:
+ * out channels [i in.c, (i + 1) in.c) = the 5x5 stride-1 maximum applied i + 1 times; AV_YOLO_OP_MAXPOOL: applied once;
+ * AV_YOLO_OP_UPSAMPLE: nearest neighbour x2. */
+#define AV_YOLO_OP_CONV 0
+#define AV_YOLO_OP_STEM 1
+#define AV_YOLO_OP_POOLS 2
+#define AV_YOLO_OP_MAXPOOL 3
+#define AV_YOLO_OP_UPSAMPLE 4
+typedef struct av_yolo_slice {
+    const void* ptr;
+    int32_t H, W, cstride, coff, c;
+    int32_t f32;                    /* 1: float32 elements, 0: IEEE half */
+} av_yolo_slice;
+typedef struct av_yolo_op_info {
+    int32_t kind;                   /* AV_YOLO_OP_* */
+    int32_t ksz, stride, act, cin, cout;
+    int32_t kpad, kreal;            /* row length of the weight matrix, and how much of a row is used */
+    int32_t in_frame, wgt_f32;
+    av_yolo_slice in, in2, out, res;
+    const void* wgt;
+    const float* bias;
+} av_yolo_op_info;
+int av_yolo_op_count(const av_yolo* h, int* n_ops);                                /* host out */
+int av_yolo_op(const av_yolo* h, int k, av_yolo_op_info* info);                    /* host out */
 
 /* ---- T3: scene classifier (road type, conditions, lane count) -------------------------------------------
  * Replaces SceneClassifier.classify and its helpers (src/tagging/scene_classifier.py:76-303): BGR2GRAY, Canny(50, 150)

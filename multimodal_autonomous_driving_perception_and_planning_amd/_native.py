@@ -101,6 +101,20 @@ class BevCfg(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class YoloSlice(C.Structure):
+    """av_yolo_slice: `c` channels from channel `coff` of an NHWC map with `cstride` elements per pixel (test hook av_yolo_op)."""
+    _fields_ = [("ptr", C.c_void_p)] + [(k, C.c_int32) for k in ("H", "W", "cstride", "coff", "c", "f32")]
+
+
+class YoloOpInfo(C.Structure):
+    """av_yolo_op_info: one op of the YOLO network as av_yolo_create built it (test hook av_yolo_op)."""
+    _fields_ = ([(k, C.c_int32) for k in ("kind", "ksz", "stride", "act", "cin", "cout", "kpad", "kreal", "in_frame", "wgt_f32")]
+                + [(k, YoloSlice) for k in ("in_", "in2", "out", "res")] + [("wgt", C.c_void_p), ("bias", C.c_void_p)])
+
+
+YOLO_OP_CONV, YOLO_OP_STEM, YOLO_OP_POOLS, YOLO_OP_MAXPOOL, YOLO_OP_UPSAMPLE = range(5)
+
+
 class InteractionCfg(C.Structure):
     _fields_ = [("frame_h", C.c_int32), ("frame_w", C.c_int32), ("class_kind", C.c_int32 * 16)]
 PRIM_FIELDS = [("type", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("x2", "<i4"), ("y2", "<i4"),
@@ -195,6 +209,8 @@ _SIGS = [
     ("av_yolo_defer_tail", C.c_int, [vp, C.c_int]),
     ("av_yolo_join_tail", C.c_int, [vp, vp]),
     ("av_yolo_tensor", C.c_int, [vp, C.c_int, C.POINTER(vp)] + [C.POINTER(C.c_int)] * 5),
+    ("av_yolo_op_count", C.c_int, [vp, C.POINTER(C.c_int)]),
+    ("av_yolo_op", C.c_int, [vp, C.c_int, C.POINTER(YoloOpInfo)]),
     ("av_lane_detect", C.c_int, [vp, vp, C.POINTER(LaneCfg), C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp,
                                  vp, C.c_int]),
     ("av_scene_state_bytes", C.c_size_t, [C.c_int]),

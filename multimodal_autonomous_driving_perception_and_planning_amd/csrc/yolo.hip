@@ -1366,9 +1366,11 @@ __global__ void preprocess_kernel(const uint8_t* __restrict__ bgr, int B, int h,
     float c[3] = {114.f, 114.f, 114.f};
     const int yy = y - top, xx = x - left;
     if (yy >= 0 && yy < nh && xx >= 0 && xx < nw) {
-        const float sy = ((float)yy + 0.5f) * ((float)h / (float)nh) - 0.5f, sx = ((float)xx + 0.5f) * ((float)w / (float)nw) - 0.5f;
-        const float fy = floorf(sy), fx = floorf(sx);
-        const float wy = sy - fy, wx = sx - fx;
+        // source coordinates in double, as the oracle computes them (oracle/yolo_ref.py: preprocess): in float they are off by up to 4e-5 at a
+        // generic scale, which moved 1 value in 4 000 of a 90 x 333 frame to the neighbouring uint8 level
+        const double sy = ((double)yy + 0.5) * ((double)h / (double)nh) - 0.5, sx = ((double)xx + 0.5) * ((double)w / (double)nw) - 0.5;
+        const double fy = floor(sy), fx = floor(sx);
+        const float wy = (float)(sy - fy), wx = (float)(sx - fx);
         int y0 = (int)fy, x0 = (int)fx, y1 = y0 + 1, x1 = x0 + 1;
         y0 = y0 < 0 ? 0 : (y0 > h - 1 ? h - 1 : y0), y1 = y1 < 0 ? 0 : (y1 > h - 1 ? h - 1 : y1);
         x0 = x0 < 0 ? 0 : (x0 > w - 1 ? w - 1 : x0), x1 = x1 < 0 ? 0 : (x1 > w - 1 ? w - 1 : x1);
@@ -2123,9 +2125,11 @@ __global__ void preprocess_f32_kernel(const uint8_t* __restrict__ bgr, int B, in
     float c[3] = {114.f, 114.f, 114.f};
     const int yy = y - top, xx = x - left;
     if (yy >= 0 && yy < nh && xx >= 0 && xx < nw) {
-        const float sy = ((float)yy + 0.5f) * ((float)h / (float)nh) - 0.5f, sx = ((float)xx + 0.5f) * ((float)w / (float)nw) - 0.5f;
-        const float fy = floorf(sy), fx = floorf(sx);
-        const float wy = sy - fy, wx = sx - fx;
+        // source coordinates in double, as the oracle computes them (oracle/yolo_ref.py: preprocess): in float they are off by up to 4e-5 at a
+        // generic scale, which moved 1 value in 4 000 of a 90 x 333 frame to the neighbouring uint8 level
+        const double sy = ((double)yy + 0.5) * ((double)h / (double)nh) - 0.5, sx = ((double)xx + 0.5) * ((double)w / (double)nw) - 0.5;
+        const double fy = floor(sy), fx = floor(sx);
+        const float wy = (float)(sy - fy), wx = (float)(sx - fx);
         int y0 = (int)fy, x0 = (int)fx, y1 = y0 + 1, x1 = x0 + 1;
         y0 = y0 < 0 ? 0 : (y0 > h - 1 ? h - 1 : y0), y1 = y1 < 0 ? 0 : (y1 > h - 1 ? h - 1 : y1);
         x0 = x0 < 0 ? 0 : (x0 > w - 1 ? w - 1 : x0), x1 = x1 < 0 ? 0 : (x1 > w - 1 ? w - 1 : x1);
@@ -2465,11 +2469,16 @@ bool add_stem(Yolo& y, Slice in, Slice out) {
 bool add_c2f(Yolo& y, Slice in, Slice out, int n, bool shortcut) {
     const Buf& bi = y.bufs[in.buf];
     const int c = out.c / 2, H = bi.H, W = bi.W;
-    const int cat = new_buf(y, H, W, (2 + n) * c), tmp = new_buf(y, H, W, c);
-    if (cat < 0 || tmp < 0) return false;
+    const int cat = new_buf(y, H, W, (2 + n) * c);
+    if (cat < 0) return false;
     const size_t first = y.ops.size();
     if (!add_conv(y, in, Slice{cat, 0, 2 * c}, 1, 1, true, nullptr, 0, nullptr)) return false;
     for (int i = 0; i < n; ++i) {
+        // a temp buffer per bottleneck (not one per block): after a forward with one launch per layer every op's input is still in
+        // memory, which av_yolo_op's readers rely on.  Two blocks have n = 2 (layers 4 and 6): 2 c H W more bytes per image each,
+        // 360 KB per 384 x 640 image together; the fused kernels keep this map in LDS and never touch the buffers.
+        const int tmp = new_buf(y, H, W, c);
+        if (tmp < 0) return false;
         const Slice src{cat, (1 + i) * c, c}, dst{cat, (2 + i) * c, c};
         if (!add_conv(y, src, Slice{tmp, 0, c}, 3, 1, true, nullptr, 0, nullptr)) return false;
         if (!add_conv(y, Slice{tmp, 0, c}, dst, 3, 1, true, nullptr, 0, shortcut ? &src : nullptr)) return false;
@@ -2948,6 +2957,61 @@ int av_yolo_tensor(const av_yolo* h, int id, void** ptr, int* H, int* W, int* C,
         }
     av_set_error("av_yolo_tensor: unknown tensor id %d", id);
     return AV_EINVAL;
+}
+
+// test hook: the ops as build_graph made them (reads host memory only)
+static_assert(sizeof(av_yolo_slice) == 32 && sizeof(av_yolo_op_info) == 184 && offsetof(av_yolo_op_info, wgt) == 168, "what _native.py binds");
+int av_yolo_op_count(const av_yolo* h, int* n_ops) {
+    AV_REQUIRE(h && n_ops, AV_EINVAL, "av_yolo_op_count: null argument");
+    *n_ops = (int)h->y.ops.size();
+    return AV_OK;
+}
+
+int av_yolo_op(const av_yolo* h, int k, av_yolo_op_info* info) {
+    AV_REQUIRE(h && info, AV_EINVAL, "av_yolo_op: null argument");
+    const Yolo& y = h->y;
+    AV_REQUIRE(k >= 0 && k < (int)y.ops.size(), AV_EINVAL, "av_yolo_op: op %d of %d", k, (int)y.ops.size());
+    const Yolo::Op& op = y.ops[k];
+    const int f32 = y.f32 ? 1 : 0;
+    av_yolo_op_info o{};
+    auto of_slice = [&](Slice s, int H, int W) {
+        const Buf& b = y.bufs[s.buf];
+        return av_yolo_slice{b.p, H, W, b.C, s.coff, s.c, f32};
+    };
+    // the members ConvArgs and ConvArgsF share
+    auto of_conv = [&](const auto& a) {
+        o.kind = AV_YOLO_OP_CONV, o.ksz = a.ksz, o.stride = a.stride, o.act = a.act, o.cin = a.cin, o.cout = a.cout;
+        o.in = av_yolo_slice{a.in, a.H, a.W, a.in_cs, a.in_coff, a.cin, f32};
+        o.out = av_yolo_slice{a.out, a.Ho, a.Wo, a.out_cs, a.out_coff, a.cout, f32};
+        if (a.res) o.res = av_yolo_slice{a.res, a.Ho, a.Wo, a.res_cs, a.res_coff, a.cout, f32};
+        o.wgt = a.wgt, o.bias = a.bias;
+    };
+    switch (op.kind) {
+    case OP_CONV_F32:
+        of_conv(op.cf);
+        o.kpad = o.kreal = op.cf.ksz * op.cf.ksz * op.cf.cin, o.wgt_f32 = 1;
+        break;
+    case OP_CONV:
+    case OP_STEM:
+        of_conv(op.ca);
+        o.kpad = op.ca.kpad, o.kreal = op.ca.kreal;
+        if (op.ca.out32) o.out.ptr = op.ca.out32, o.out.f32 = 1;
+        if (op.kind == OP_STEM) o.kind = AV_YOLO_OP_STEM, o.in_frame = 1, o.in.H += 2, o.in.W += 2;
+        if (k > 0 && y.ops[k - 1].kind == OP_UPSAMPLE && y.ops[k - 1].vcat == k && reads_upsample(y, y.ops[k - 1], op))
+            o.in2 = of_slice(y.ops[k - 1].in, y.ops[k - 1].H, y.ops[k - 1].W);
+        break;
+    case OP_POOLS:
+    case OP_MAXPOOL:
+    case OP_UPSAMPLE: {
+        const int up = op.kind == OP_UPSAMPLE ? 2 : 1;
+        o.kind = op.kind == OP_POOLS ? AV_YOLO_OP_POOLS : (op.kind == OP_MAXPOOL ? AV_YOLO_OP_MAXPOOL : AV_YOLO_OP_UPSAMPLE);
+        o.ksz = op.kind == OP_UPSAMPLE ? 0 : 5, o.stride = 1, o.cin = op.in.c, o.cout = op.out.c;
+        o.in = of_slice(op.in, op.H, op.W), o.out = of_slice(op.out, up * op.H, up * op.W);
+        break;
+    }
+    }
+    *info = o;
+    return AV_OK;
 }
 
 int av_yolo_forward(av_yolo* h, av_stream_t stream, const uint8_t* bgr, float conf_thres, float iou_thres, int max_det,

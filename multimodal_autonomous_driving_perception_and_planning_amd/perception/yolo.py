@@ -325,6 +325,37 @@ class YoloV8n:
             return (arr.astype(np.uint16).astype(np.uint32) << 16).view(np.float32)
         return np.ascontiguousarray(arr).view(np.float16).astype(np.float32)
 
+    def ops(self):
+        """The ops of the network as the library built them, one per layer in execution order (test hook av_yolo_op): a list of
+        nat.YoloOpInfo.  Reads nothing from the device."""
+        n = C.c_int()
+        nat.check(self._dev.lib.av_yolo_op_count(self._h, C.byref(n)))
+        out = []
+        for k in range(n.value):
+            info = nat.YoloOpInfo()
+            nat.check(self._dev.lib.av_yolo_op(self._h, k, C.byref(info)))
+            out.append(info)
+        return out
+
+    def _read(self, ptr, count, dtype):
+        """Host copy of `count` elements of library-owned device memory."""
+        t = torch.empty(count, dtype=dtype, device=self._dev.device)
+        self._dev.sync()
+        rc = _memcpy_d2d(t.data_ptr(), ptr, t.numel() * t.element_size())
+        if rc != 0:
+            raise RuntimeError("hipMemcpy failed (%d)" % rc)
+        return t.cpu().numpy()
+
+    def read_slice(self, s):
+        """Host copy of a nat.YoloSlice of an op, all images: float32 or float16 [batch, H, W, c] (test hook)."""
+        a = self._read(s.ptr, self.batch * s.H * s.W * s.cstride, torch.float32 if s.f32 else torch.float16)
+        return np.ascontiguousarray(a.reshape(self.batch, s.H, s.W, s.cstride)[..., s.coff:s.coff + s.c])
+
+    def read_weights(self, op):
+        """Host copy of a convolution op's folded weights, float32 or float16 [cout, kpad], and of its float32 bias [cout] (test hook)."""
+        w = self._read(op.wgt, op.cout * op.kpad, torch.float32 if op.wgt_f32 else torch.float16).reshape(op.cout, op.kpad)
+        return w, self._read(op.bias, op.cout, torch.float32)
+
     def close(self):
         if self._h is not None:
             self._dev.sync()

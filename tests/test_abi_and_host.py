@@ -18,7 +18,7 @@ def lib():
 
 def test_library_exports_every_declared_symbol(lib):
     names = nat.declared_symbols()
-    assert len(names) >= 29
+    assert len(names) >= 29 and {"av_yolo_tensor", "av_yolo_op_count", "av_yolo_op"} <= set(names)
     for n in names:
         assert hasattr(lib, n), "libavhot.so lacks %s declared in include/avhot.h" % n
     assert lib.av_version() == 103
@@ -30,6 +30,8 @@ def test_struct_layouts_match_header(lib):
     assert C.sizeof(nat.TrackerCfg) == 24 and C.sizeof(nat.KfCfg) == 24 and C.sizeof(nat.PlannerCfg) == 56
     assert lib.av_tracker_state_bytes(64, 50) == 64 + 64 * 64 + 64 * 50 * 32
     assert lib.av_tracker_state_bytes(0, 50) == 0
+    # av_yolo_slice / av_yolo_op_info (test hook av_yolo_op): 8-byte pointers first or last, int32 between, no padding
+    assert C.sizeof(nat.YoloSlice) == 32 and C.sizeof(nat.YoloOpInfo) == 40 + 4 * 32 + 16 and nat.YoloOpInfo.wgt.offset == 168
 
 
 def test_step_structs_match_header():
