@@ -1,3 +1,3 @@
-from .video_loader import VideoDataLoader  # noqa: F401
+from .video_loader import VideoDataLoader, Y4MWriter  # noqa: F401
 
-__all__ = ["VideoDataLoader"]
+__all__ = ["VideoDataLoader", "Y4MWriter"]

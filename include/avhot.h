@@ -755,6 +755,88 @@ int av_bev_build(av_ctx* ctx, av_stream_t stream, const av_bev_cfg* cfg, int n_s
 int av_resize_into(av_ctx* ctx, av_stream_t stream, const uint8_t* src, int sh, int sw, uint8_t* dst, int dh, int dw, int dst_pitch_px,
                    int dst_x0);
 
+/* The source / destination form of av_raster_draw: the h x w pictures src [n_images][h][src_pitch_px][3] are painted into the h x w
+ * window at column dst_x0 of dst [n_images][h][dst_pitch_px][3]; every pixel is read once and written once, the source stays as it
+ * is.  src == dst with equal pitches and dst_x0 = 0 is av_raster_draw; any other overlap of the two is refused (AV_EINVAL). */
+int av_raster_draw_to(av_ctx* ctx, av_stream_t stream, int n_images, int h, int w, const uint8_t* src, int src_pitch_px, uint8_t* dst,
+                      int dst_pitch_px, int dst_x0, const av_prim* prims, int prim_cap, const int32_t* n_prims, const int32_t* verts,
+                      int vert_cap);
+
+/* ---- the demo's annotated view (demo.py:122-150), composed on the device ---------------------------------------------------------
+ * av_camview_build writes, one workgroup per camera, the primitive list of the camera view from what a camera loop's step left in
+ * HBM, in the order and with the arithmetic of the class methods demo.py calls; `flags` selects the layers:
+ *   AV_VIEW_DETECTIONS  ObjectDetector.draw_detections: every box of det_* in order (float32 coordinates truncated toward zero),
+ *                       colour det_colors[cls] (white outside the table), outline 2, label box, "name 0.87" ("unknown" outside
+ *                       the name table; the confidence is "%.2f" of the float32 widened to double)
+ *   AV_VIEW_LANES       LaneDetector.draw_lanes: the blended area left + reversed right when both sides exist (lane_info[s][0],
+ *                       [1]), then the left and the right polyline, thickness 3
+ *   AV_VIEW_TRACKS      MultiObjectTracker.draw_tracks (defaults): confirmed rows of the snapshot in table order, palette[id % 8],
+ *                       "ID:n name" (the class id in decimal outside trk_names), the trail from the history ring
+ *   AV_VIEW_INFO        OverlayRenderer.draw_info_panel: "Frame: n" (the tracker's frame counter - 1), "FPS: %.1f" (fps), and from
+ *                       vstate speed * 3.6, heading * (180 / pi), acceleration, position (vstate NULL: the first two lines only)
+ *   AV_VIEW_SUMMARY     draw_detection_summary, top right: a count per class name in order of first appearance (names are told
+ *                       apart by their id: two ids with one name would be listed twice; ids outside the table are one "unknown")
+ *   AV_VIEW_GAUGE       draw_lane_offset_indicator of get_lane_center_offset (the empty gauge without a lane pair)
+ * The list is compacted: n_prims[s] primitives, no empty slots.  Number text is that of Python's % operator (csrc/fmtnum.h).
+ * Name tables: char [n][AV_NAME_BYTES] plus int32 lengths [n] (negative: no such id), at most max_name (< AV_NAME_BYTES) characters
+ * are drawn; det_colors u8 [n_det_colors][3] in B, G, R order. */
+#define AV_NAME_BYTES 24
+enum {
+    AV_VIEW_DETECTIONS = 1, AV_VIEW_LANES = 2, AV_VIEW_TRACKS = 4, AV_VIEW_INFO = 8, AV_VIEW_SUMMARY = 16, AV_VIEW_GAUGE = 32,
+    AV_VIEW_DEMO = 31,       /* the layers demo.py draws */
+    AV_VIEW_ALL = 63
+};
+typedef struct {
+    int32_t n_streams, h, w;                /* cameras, frame size */
+    int32_t flags;                          /* AV_VIEW_* */
+    int32_t n_frames, frame;                /* snap / snap_n / vstate are [S][n_frames][..]; the frame of the window to draw */
+    int32_t max_det, tcap, trajectory_length, max_name;
+    int32_t n_det_names, n_det_colors, n_trk_names, reserved;
+    double fps;
+    const int32_t* det_n;                   /* [S] */
+    const float* det_box;                   /* [S][max_det][4] x1 y1 x2 y2 */
+    const float* det_conf;                  /* [S][max_det] */
+    const int32_t* det_cls;                 /* [S][max_det] */
+    const char* det_names;                  /* [n_det_names][AV_NAME_BYTES] */
+    const int32_t* det_name_len;            /* [n_det_names] */
+    const uint8_t* det_colors;              /* [n_det_colors][3] */
+    const int32_t* lane_pts;                /* [S][2][50][2] of av_lane_detect */
+    const int32_t* lane_info;               /* [S][8] of av_lane_detect */
+    const av_track_row* snap;               /* [S][n_frames][tcap] */
+    const int32_t* snap_n;                  /* [S][n_frames] */
+    const void* tracker_state;              /* the tracker's persistent state: frame counter and history rings */
+    const char* trk_names;                  /* [n_trk_names][AV_NAME_BYTES] */
+    const int32_t* trk_name_len;            /* [n_trk_names] */
+    const double* vstate;                   /* [S][n_frames][AV_VSTATE_DOUBLES] or NULL */
+} av_camview_args;
+/* slots a camera's list can need; 0 for arguments out of range (max_det, tcap <= 1024, max_name < AV_NAME_BYTES) */
+int av_camview_prim_cap(int max_det, int tcap, int trajectory_length, int max_name);
+/*   prims  av_prim [S][prim_cap], n_prims int32 [S]; verts int32 [S][vert_cap][2], vert_cap >= 100 with AV_VIEW_LANES
+ * AV_EINVAL when av_camview_prim_cap() exceeds the rasteriser's 65535 or prim_cap is below it. */
+int av_camview_build(av_ctx* ctx, av_stream_t stream, const av_camview_args* args, av_prim* prims, int prim_cap, int32_t* n_prims,
+                     int32_t* verts, int vert_cap);
+
+/* OverlayRenderer.create_side_by_side for n_images pairs in one launch: both pictures at the taller one's height th, the one that
+ * keeps its height copied, the other resized by av_resize_into's rule to int(w * (th / h)) columns (overlays.py:88-90), the labels
+ * at (10, 25) and (nw1 + 10, 25) in the doubled font.   cam u8 [n][h1][w1][3], bev u8 [n][h2][w2][3], out u8 [n][th][nw1 + nw2][3].
+ * cam (or bev) may be NULL when that half keeps its size and is already in place in `out` (painted there by av_raster_draw_to):
+ * the call then writes the other half and the labels only.  Labels: at most AV_VIEW_LABEL_BYTES - 1 characters. */
+#define AV_VIEW_LABEL_BYTES 32
+int av_view_compose_size(int h1, int w1, int h2, int w2, int* th, int* nw1, int* nw2);
+int av_view_compose(av_ctx* ctx, av_stream_t stream, int n_images, const uint8_t* cam, int h1, int w1, const uint8_t* bev, int h2, int w2,
+                    uint8_t* out, const char* label1, const char* label2);
+
+/* "%.{decimals}f" % v as Python writes it, decimals 0 .. 2 (csrc/fmtnum.h, the formatter the view builder runs on the device): exact
+ * for |v| < 1e9, "nan" / "inf" / "-inf", and "inf" / "-inf" for a finite |v| >= 1e9.  `cap` characters fit in out, no terminator is
+ * written.  -> the length, or AV_EINVAL (bad argument, or the text does not fit: nothing is written).  Needs no context. */
+int av_format_fixed(double v, int decimals, char* out, int cap);
+
+/* Interleaved BGR -> planar YUV 4:2:0 (I420), the inverse direction of av_i420_to_bgr, for writing uncompressed video: BT.601 limited
+ * range in OpenCV's 20-bit constants (Y = (269484 R + 528482 G + 102760 B + 2^19 >> 20) + 16; U, V from -155188 / -305135 / 460324
+ * and 460324 / -385875 / -74448, + 128), chroma from the rounded mean colour of each 2 x 2 block.  Parity unpinned (OpenCV absent).
+ *   bgr u8 [n_frames][h][w][3];  yuv u8 [n_frames][h*w*3/2];  h and w even (AV_EINVAL otherwise) */
+int av_bgr_to_i420(av_ctx* ctx, av_stream_t stream, int n_frames, int h, int w, const uint8_t* bgr, uint8_t* yuv);
+
 /* ---- video ingest ----------------------------------------------------------------
  * The pixel half of VideoDataLoader.read_frame / read_frame_at (data/loaders/video_loader.py:88-131): what a decoder hands over
  * as planar YUV 4:2:0 becomes the BGR frame cv2.VideoCapture.read returns, then av_resize_into scales it to target_size

@@ -122,6 +122,38 @@ PRIM_FIELDS = [("type", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y
 PRIM_BYTES = 48
 PRIM_RECT, PRIM_SEG, PRIM_QUAD, PRIM_DISC, PRIM_RING, PRIM_GLYPH, PRIM_BLEND_RECT, PRIM_POLY_BLEND = 1, 2, 3, 4, 5, 6, 7, 8
 VSTATE_DOUBLES = 12
+NAME_BYTES = 24
+VIEW_DETECTIONS, VIEW_LANES, VIEW_TRACKS, VIEW_INFO, VIEW_SUMMARY, VIEW_GAUGE, VIEW_DEMO, VIEW_ALL = 1, 2, 4, 8, 16, 32, 31, 63
+
+
+class CamviewArgs(C.Structure):
+    """av_camview_args (include/avhot.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("n_streams", "h", "w", "flags", "n_frames", "frame", "max_det", "tcap", "trajectory_length",
+                                         "max_name", "n_det_names", "n_det_colors", "n_trk_names", "reserved")] + [("fps", C.c_double)] + [
+        (n, C.c_void_p) for n in ("det_n", "det_box", "det_conf", "det_cls", "det_names", "det_name_len", "det_colors", "lane_pts",
+                                  "lane_info", "snap", "snap_n", "tracker_state", "trk_names", "trk_name_len", "vstate")]
+
+
+def name_table(names, what="class names"):
+    """{id: name} or a name list -> (uint8 [n][NAME_BYTES], int32 lengths [n], -1 where there is no such id): the device tables of
+    av_camview_build.  A name of more than NAME_BYTES - 1 characters, or one outside Latin-1, raises ValueError."""
+    import numpy as np
+    items = names.items() if isinstance(names, dict) else enumerate(names)
+    items = [(int(k), str(v)) for k, v in items]
+    n = max([k for k, _ in items if k >= 0], default=-1) + 1
+    tab, lens = np.zeros((max(n, 1), NAME_BYTES), np.uint8), np.full(max(n, 1), -1, np.int32)
+    for k, v in items:
+        if k < 0:
+            continue
+        try:
+            raw = v.encode("latin-1")
+        except UnicodeEncodeError:
+            raise ValueError("%s: %r has characters outside Latin-1" % (what, v)) from None
+        if len(raw) > NAME_BYTES - 1:
+            raise ValueError("%s: %r is longer than %d characters" % (what, v, NAME_BYTES - 1))
+        tab[k, :len(raw)] = np.frombuffer(raw, np.uint8)
+        lens[k] = len(raw)
+    return tab, lens
 WP_DOUBLES = 6
 
 # (name, restype, argtypes); everything returns int status except the three noted
@@ -193,6 +225,13 @@ _SIGS = [
     ("av_bev_build", C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp]),
     ("av_i420_to_bgr", C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     ("av_resize_into", C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("av_raster_draw_to", C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int]),
+    ("av_camview_prim_cap", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("av_camview_build", C.c_int, [vp, vp, vp, vp, C.c_int, vp, vp, C.c_int]),
+    ("av_view_compose_size", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    ("av_view_compose", C.c_int, [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_char_p, C.c_char_p]),
+    ("av_format_fixed", C.c_int, [C.c_double, C.c_int, vp, C.c_int]),
+    ("av_bgr_to_i420", C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     ("av_synth_frames", C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     ("av_maneuver_reset", C.c_int, [vp, vp, C.c_int, vp]),
     ("av_interaction_state_bytes", C.c_size_t, [C.c_int]),

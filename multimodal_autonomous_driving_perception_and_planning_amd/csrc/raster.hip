@@ -13,39 +13,17 @@
 // Workgroup = one 32x32 tile of one image: it filters the list down to the primitives whose bounding box touches the
 // tile (order kept, LDS), then every thread walks that short list for its 4 pixels, which live in registers from the
 // first read to the only write.  HBM traffic = the image once in, once out.
+// The picture read and the picture written may be different ones (av_raster_draw_to): paint a frame into a window of a wider picture
+// without touching the frame.  Font, primitive constructor and the resize rule live in raster_dev.h, shared with camview.hip.
 #include "common.h"
+#include "raster_dev.h"
 
 namespace {
 
+using namespace rasterdev;
+
 constexpr int RT = 32;                     // tile edge
 constexpr int RLIST = 1024;                // tile-local primitive indices held in LDS at a time
-
-// 5x7 glyphs, ASCII 32..126, five column bytes each (bit 0 = top row): the classic public-domain LCD font
-__constant__ unsigned char FONT5X7[95][5] = {
-    {0x00, 0x00, 0x00, 0x00, 0x00}, {0x00, 0x00, 0x5F, 0x00, 0x00}, {0x00, 0x07, 0x00, 0x07, 0x00}, {0x14, 0x7F, 0x14, 0x7F, 0x14},
-    {0x24, 0x2A, 0x7F, 0x2A, 0x12}, {0x23, 0x13, 0x08, 0x64, 0x62}, {0x36, 0x49, 0x55, 0x22, 0x50}, {0x00, 0x05, 0x03, 0x00, 0x00},
-    {0x00, 0x1C, 0x22, 0x41, 0x00}, {0x00, 0x41, 0x22, 0x1C, 0x00}, {0x14, 0x08, 0x3E, 0x08, 0x14}, {0x08, 0x08, 0x3E, 0x08, 0x08},
-    {0x00, 0x50, 0x30, 0x00, 0x00}, {0x08, 0x08, 0x08, 0x08, 0x08}, {0x00, 0x60, 0x60, 0x00, 0x00}, {0x20, 0x10, 0x08, 0x04, 0x02},
-    {0x3E, 0x51, 0x49, 0x45, 0x3E}, {0x00, 0x42, 0x7F, 0x40, 0x00}, {0x42, 0x61, 0x51, 0x49, 0x46}, {0x21, 0x41, 0x45, 0x4B, 0x31},
-    {0x18, 0x14, 0x12, 0x7F, 0x10}, {0x27, 0x45, 0x45, 0x45, 0x39}, {0x3C, 0x4A, 0x49, 0x49, 0x30}, {0x01, 0x71, 0x09, 0x05, 0x03},
-    {0x36, 0x49, 0x49, 0x49, 0x36}, {0x06, 0x49, 0x49, 0x29, 0x1E}, {0x00, 0x36, 0x36, 0x00, 0x00}, {0x00, 0x56, 0x36, 0x00, 0x00},
-    {0x08, 0x14, 0x22, 0x41, 0x00}, {0x14, 0x14, 0x14, 0x14, 0x14}, {0x00, 0x41, 0x22, 0x14, 0x08}, {0x02, 0x01, 0x51, 0x09, 0x06},
-    {0x32, 0x49, 0x79, 0x41, 0x3E}, {0x7E, 0x11, 0x11, 0x11, 0x7E}, {0x7F, 0x49, 0x49, 0x49, 0x36}, {0x3E, 0x41, 0x41, 0x41, 0x22},
-    {0x7F, 0x41, 0x41, 0x22, 0x1C}, {0x7F, 0x49, 0x49, 0x49, 0x41}, {0x7F, 0x09, 0x09, 0x09, 0x01}, {0x3E, 0x41, 0x49, 0x49, 0x7A},
-    {0x7F, 0x08, 0x08, 0x08, 0x7F}, {0x00, 0x41, 0x7F, 0x41, 0x00}, {0x20, 0x40, 0x41, 0x3F, 0x01}, {0x7F, 0x08, 0x14, 0x22, 0x41},
-    {0x7F, 0x40, 0x40, 0x40, 0x40}, {0x7F, 0x02, 0x0C, 0x02, 0x7F}, {0x7F, 0x04, 0x08, 0x10, 0x7F}, {0x3E, 0x41, 0x41, 0x41, 0x3E},
-    {0x7F, 0x09, 0x09, 0x09, 0x06}, {0x3E, 0x41, 0x51, 0x21, 0x5E}, {0x7F, 0x09, 0x19, 0x29, 0x46}, {0x46, 0x49, 0x49, 0x49, 0x31},
-    {0x01, 0x01, 0x7F, 0x01, 0x01}, {0x3F, 0x40, 0x40, 0x40, 0x3F}, {0x1F, 0x20, 0x40, 0x20, 0x1F}, {0x3F, 0x40, 0x38, 0x40, 0x3F},
-    {0x63, 0x14, 0x08, 0x14, 0x63}, {0x07, 0x08, 0x70, 0x08, 0x07}, {0x61, 0x51, 0x49, 0x45, 0x43}, {0x00, 0x7F, 0x41, 0x41, 0x00},
-    {0x02, 0x04, 0x08, 0x10, 0x20}, {0x00, 0x41, 0x41, 0x7F, 0x00}, {0x04, 0x02, 0x01, 0x02, 0x04}, {0x40, 0x40, 0x40, 0x40, 0x40},
-    {0x00, 0x01, 0x02, 0x04, 0x00}, {0x20, 0x54, 0x54, 0x54, 0x78}, {0x7F, 0x48, 0x44, 0x44, 0x38}, {0x38, 0x44, 0x44, 0x44, 0x20},
-    {0x38, 0x44, 0x44, 0x48, 0x7F}, {0x38, 0x54, 0x54, 0x54, 0x18}, {0x08, 0x7E, 0x09, 0x01, 0x02}, {0x0C, 0x52, 0x52, 0x52, 0x3E},
-    {0x7F, 0x08, 0x04, 0x04, 0x78}, {0x00, 0x44, 0x7D, 0x40, 0x00}, {0x20, 0x40, 0x44, 0x3D, 0x00}, {0x7F, 0x10, 0x28, 0x44, 0x00},
-    {0x00, 0x41, 0x7F, 0x40, 0x00}, {0x7C, 0x04, 0x18, 0x04, 0x78}, {0x7C, 0x08, 0x04, 0x04, 0x78}, {0x38, 0x44, 0x44, 0x44, 0x38},
-    {0x7C, 0x14, 0x14, 0x14, 0x08}, {0x08, 0x14, 0x14, 0x18, 0x7C}, {0x7C, 0x08, 0x04, 0x04, 0x08}, {0x48, 0x54, 0x54, 0x54, 0x20},
-    {0x04, 0x3F, 0x44, 0x40, 0x20}, {0x3C, 0x40, 0x40, 0x20, 0x7C}, {0x1C, 0x20, 0x40, 0x20, 0x1C}, {0x3C, 0x40, 0x30, 0x40, 0x3C},
-    {0x44, 0x28, 0x10, 0x28, 0x44}, {0x0C, 0x50, 0x50, 0x50, 0x3C}, {0x44, 0x64, 0x54, 0x4C, 0x44}, {0x00, 0x08, 0x36, 0x41, 0x00},
-    {0x00, 0x00, 0x7F, 0x00, 0x00}, {0x00, 0x41, 0x36, 0x08, 0x00}, {0x10, 0x08, 0x08, 0x10, 0x08}};
 
 __device__ __forceinline__ void prim_bbox(const av_prim& q, int& bx0, int& by0, int& bx1, int& by1) {
     switch (q.type) {
@@ -117,10 +95,7 @@ __device__ __forceinline__ bool prim_covers(const av_prim& q, int x, int y, cons
             return d4 >= (2 * r - 1) * (2 * r - 1) && d4 <= (2 * r + 1) * (2 * r + 1);
         }
         case AV_PRIM_GLYPH: {
-            const int sc = q.x1 > 0 ? q.x1 : 1;
-            const int gx = x - q.x0, gy = y - q.y0;
-            if (gx < 0 || gy < 0 || gx >= 5 * sc || gy >= 7 * sc || q.p < 32 || q.p > 126) return false;
-            return (FONT5X7[q.p - 32][gx / sc] >> (gy / sc)) & 1;
+            return glyph_bit(q.p, x - q.x0, y - q.y0, q.x1 > 0 ? q.x1 : 1);
         }
         case AV_PRIM_POLY_BLEND: {
             // even-odd rule on the vertex list verts[2 * (x0 + k)], k < y0; the pixel centre against half-open edges
@@ -156,16 +131,19 @@ __device__ __forceinline__ unsigned prim_apply(const av_prim& q, unsigned px) {
     return c;
 }
 
-__global__ void __launch_bounds__(256) raster_kernel(int n_images, int H, int W, uint8_t* __restrict__ img, const av_prim* __restrict__ prims,
-                                                     int prim_cap, const int32_t* __restrict__ n_prims, const int32_t* __restrict__ verts,
-                                                     int vert_cap) {
+// src [n][H][spitch][3] -> the H x W window at column dx0 of dst [n][H][dpitch][3]; src == dst (same pitch, dx0 0) paints in place:
+// a pixel is read and written by the same thread, and by no other
+__global__ void __launch_bounds__(256) raster_kernel(int n_images, int H, int W, const uint8_t* src, int spitch, uint8_t* dst, int dpitch,
+                                                     int dx0, const av_prim* __restrict__ prims, int prim_cap,
+                                                     const int32_t* __restrict__ n_prims, const int32_t* __restrict__ verts, int vert_cap) {
     __shared__ unsigned short list[RLIST];
     __shared__ int s_cnt, s_wbase[4];
     const int im = blockIdx.z, tx0 = blockIdx.x * RT, ty0 = blockIdx.y * RT, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const av_prim* pr = prims + (size_t)im * prim_cap;
     const int32_t* vt = verts ? verts + (size_t)im * vert_cap * 2 : nullptr;
     const int np = min(n_prims[im], prim_cap);
-    uint8_t* base = img + (size_t)im * H * W * 3;
+    const uint8_t* sbase = src + (size_t)im * H * spitch * 3;
+    uint8_t* base = dst + ((size_t)im * H * dpitch + dx0) * 3;
     // this thread's 4 pixels: row ty0 + tid / 8, columns tx0 + 4 (tid % 8) ..
     const int y = ty0 + (tid >> 3), xb = tx0 + 4 * (tid & 7);
     unsigned px[4];
@@ -173,7 +151,7 @@ __global__ void __launch_bounds__(256) raster_kernel(int n_images, int H, int W,
     for (int k = 0; k < 4; ++k) {
         px[k] = 0;
         if (y < H && xb + k < W) {
-            const uint8_t* p = base + ((size_t)y * W + xb + k) * 3;
+            const uint8_t* p = sbase + ((size_t)y * spitch + xb + k) * 3;
             px[k] = (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16);
         }
     }
@@ -217,7 +195,7 @@ __global__ void __launch_bounds__(256) raster_kernel(int n_images, int H, int W,
 #pragma unroll
     for (int k = 0; k < 4; ++k)
         if (y < H && xb + k < W) {
-            uint8_t* p = base + ((size_t)y * W + xb + k) * 3;
+            uint8_t* p = base + ((size_t)y * dpitch + xb + k) * 3;
             p[0] = (uint8_t)(px[k] & 255u), p[1] = (uint8_t)((px[k] >> 8) & 255u), p[2] = (uint8_t)((px[k] >> 16) & 255u);
         }
 }
@@ -228,21 +206,10 @@ __global__ void resize_kernel(const uint8_t* __restrict__ src, int sh, int sw, u
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= dh * dw) return;
     const int y = i / dw, x = i - y * dw;
-    // source position in 1/65536 pixels: (x + 0.5) * sw / dw - 0.5
-    const long long fx = ((2LL * x + 1) * sw * 32768LL) / dw - 32768LL, fy = ((2LL * y + 1) * sh * 32768LL) / dh - 32768LL;
-    const long long cx = fx < 0 ? 0 : fx, cy = fy < 0 ? 0 : fy;
-    int x0 = (int)(cx >> 16), y0 = (int)(cy >> 16);
-    const int wx = (int)(cx & 65535), wy = (int)(cy & 65535);
-    const int x1 = min(x0 + 1, sw - 1), y1 = min(y0 + 1, sh - 1);
-    x0 = min(x0, sw - 1), y0 = min(y0, sh - 1);
+    const ResizeTap t = resize_tap(sh, sw, dh, dw, x, y);
     uint8_t* o = dst + ((size_t)y * dpitch + dx0 + x) * 3;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const long long p00 = src[((size_t)y0 * sw + x0) * 3 + k], p01 = src[((size_t)y0 * sw + x1) * 3 + k];
-        const long long p10 = src[((size_t)y1 * sw + x0) * 3 + k], p11 = src[((size_t)y1 * sw + x1) * 3 + k];
-        const long long top = p00 * (65536 - wx) + p01 * wx, bot = p10 * (65536 - wx) + p11 * wx;
-        o[k] = (uint8_t)((top * (65536 - wy) + bot * wy + (1LL << 31)) >> 32);
-    }
+    for (int k = 0; k < 3; ++k) o[k] = resize_channel(src, sw, t, k);
 }
 
 
@@ -257,12 +224,6 @@ struct BevGeom {
 };
 __device__ __forceinline__ void w2p(const BevGeom& g, double x, double y, int& px, int& py) {
     px = (int)((x - g.x_lo) * g.xs), py = (int)((double)g.H - (y - g.y_lo) * g.ys);          // bev_renderer.py:70-83 (int() truncates)
-}
-__device__ __forceinline__ av_prim mk(int type, int x0, int y0, int x1, int y1, int p, unsigned bgr) {
-    av_prim q{};
-    q.type = type, q.x0 = x0, q.y0 = y0, q.x1 = x1, q.y1 = y1, q.p = p;
-    q.b = (uint8_t)(bgr & 255u), q.g = (uint8_t)((bgr >> 8) & 255u), q.r = (uint8_t)(bgr >> 16);
-    return q;
 }
 __device__ __forceinline__ int cv_round_d(double v) { return (int)rint(v); }
 // footprint + outline + arrow of one vehicle: 8 primitives at out[0..8)
@@ -444,7 +405,30 @@ int av_raster_draw(av_ctx* ctx, av_stream_t stream, int n_images, int h, int w, 
     AV_REQUIRE(prim_cap > 0 && prim_cap <= 65535 && vert_cap >= 0, AV_EINVAL, "av_raster_draw: prim_cap must be in [1, 65535]");
     static_assert(sizeof(av_prim) == 48, "av_prim layout");
     const dim3 grid((w + RT - 1) / RT, (h + RT - 1) / RT, n_images);
-    hipLaunchKernelGGL(raster_kernel, grid, dim3(256), 0, as_stream(stream), n_images, h, w, img, prims, prim_cap, n_prims, verts, vert_cap);
+    hipLaunchKernelGGL(raster_kernel, grid, dim3(256), 0, as_stream(stream), n_images, h, w, img, w, img, w, 0, prims, prim_cap, n_prims, verts,
+                       vert_cap);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
+int av_raster_draw_to(av_ctx* ctx, av_stream_t stream, int n_images, int h, int w, const uint8_t* src, int src_pitch_px, uint8_t* dst,
+                      int dst_pitch_px, int dst_x0, const av_prim* prims, int prim_cap, const int32_t* n_prims, const int32_t* verts,
+                      int vert_cap) {
+    AV_REQUIRE(ctx && src && dst && prims && n_prims, AV_EINVAL, "av_raster_draw_to: null argument");
+    AV_REQUIRE(n_images > 0 && h > 0 && w > 0 && h < 8192 && w < 8192, AV_EINVAL, "av_raster_draw_to: bad image size %dx%d", w, h);
+    AV_REQUIRE(src_pitch_px >= w && dst_x0 >= 0 && dst_pitch_px >= w && dst_x0 <= dst_pitch_px - w, AV_EINVAL,
+               "av_raster_draw_to: the %d-pixel window does not fit (source rows %d, destination rows %d from column %d)", w, src_pitch_px,
+               dst_pitch_px, dst_x0);
+    AV_REQUIRE(prim_cap > 0 && prim_cap <= 65535 && vert_cap >= 0, AV_EINVAL, "av_raster_draw_to: prim_cap must be in [1, 65535]");
+    {
+        // overlapping but unequal pictures would be read after they were written by another workgroup
+        const size_t sb = (size_t)n_images * h * src_pitch_px * 3, db = (size_t)n_images * h * dst_pitch_px * 3;
+        const bool same = src == dst && src_pitch_px == dst_pitch_px && dst_x0 == 0;
+        AV_REQUIRE(same || src + sb <= dst || dst + db <= src, AV_EINVAL, "av_raster_draw_to: source and destination overlap");
+    }
+    const dim3 grid((w + RT - 1) / RT, (h + RT - 1) / RT, n_images);
+    hipLaunchKernelGGL(raster_kernel, grid, dim3(256), 0, as_stream(stream), n_images, h, w, src, src_pitch_px, dst, dst_pitch_px, dst_x0,
+                       prims, prim_cap, n_prims, verts, vert_cap);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }

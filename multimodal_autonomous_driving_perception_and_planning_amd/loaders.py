@@ -8,6 +8,9 @@ two formats that need none and does the pixel work on the device:
   * `.npy`  uint8 array [frames, height, width, 3] (BGR), memory-mapped; resize on the GPU.
 Compressed containers (mp4 / avi / mov / mkv) raise ValueError naming the missing decoder.  Same properties and methods
 as the reference class, plus read_frames_device() which leaves a batch of frames in HBM for the batched pipeline.
+
+Y4MWriter is the way out: where the reference hands its annotated frames to cv2.VideoWriter (demo.py:84-90, :170), this writes them
+as a 4:2:0 `.y4m` file the loader above (or ffmpeg) reads, converting on the device (av_bgr_to_i420).
 """
 from pathlib import Path
 from typing import Generator, Optional, Tuple
@@ -169,3 +172,52 @@ class VideoDataLoader:
     def __repr__(self) -> str:
         return "VideoDataLoader(path='%s', frames=%d, fps=%.1f, size=%dx%d)" % (self.video_path.name, self._total_frames, self._fps,
                                                                              self._width, self._height)
+
+
+class Y4MWriter:
+    """Uncompressed YUV4MPEG2 4:2:0 video file.  Y4MWriter(path, fps, (width, height)); write(frame) takes one BGR frame on the host
+    like cv2.VideoWriter.write, write_device(batch) a uint8 device tensor [n, height, width, 3] (one conversion launch, one
+    download); release() closes the file.  4:2:0 needs even sizes (ValueError otherwise)."""
+
+    def __init__(self, path: str, fps: float, size: Tuple[int, int], device: int = 0):
+        w, h = int(size[0]), int(size[1])
+        if w <= 0 or h <= 0 or w % 2 or h % 2:
+            raise ValueError("Y4MWriter: 4:2:0 needs even sizes, got %dx%d" % (w, h))
+        from fractions import Fraction
+        fr = Fraction(float(fps)).limit_denominator(1001)
+        if fr <= 0:
+            raise ValueError("Y4MWriter: fps must be positive")
+        self.path, self.fps, self.width, self.height = Path(path), float(fps), w, h
+        self._dev = Dev(device)
+        self._f = open(self.path, "wb")
+        self._f.write(b"YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420jpeg\n" % (w, h, fr.numerator, fr.denominator))
+
+    def write_device(self, batch: torch.Tensor):
+        if self._f is None:
+            raise ValueError("Y4MWriter: the file is closed")
+        if (not torch.is_tensor(batch) or not batch.is_cuda or batch.dtype != torch.uint8 or batch.dim() != 4
+                or tuple(batch.shape[1:]) != (self.height, self.width, 3)):
+            raise ValueError("Y4MWriter.write_device: expected a uint8 device tensor [n, %d, %d, 3]" % (self.height, self.width))
+        n = int(batch.shape[0])
+        if n == 0:
+            return
+        d = self._dev
+        batch = batch.contiguous()
+        fsz = self.width * self.height * 3 // 2
+        yuv = d.empty((n, fsz), torch.uint8)
+        nat.check(d.lib.av_bgr_to_i420(d.ctx.handle, d.stream, n, self.height, self.width, nat.ptr(batch), nat.ptr(yuv)))
+        host = yuv.cpu().numpy()
+        for k in range(n):
+            self._f.write(b"FRAME\n")
+            self._f.write(host[k].tobytes())
+
+    def write(self, frame: np.ndarray):
+        frame = np.ascontiguousarray(frame, np.uint8)
+        if frame.shape != (self.height, self.width, 3):
+            raise ValueError("Y4MWriter.write: expected a %dx%dx3 uint8 frame, got shape %s" % (self.height, self.width, frame.shape))
+        self.write_device(self._dev.upload(frame[None], np.uint8))
+
+    def release(self):
+        if self._f is not None:
+            self._f.close()
+            self._f = None

@@ -960,7 +960,7 @@ class CameraLoop:
 
     def __init__(self, n_streams, h=720, w=1280, model="random:0", precision="fp16", dcap=64, obstacles="moving_tracks",
                  class_map="reference", device=0, tracker_kw=None, kf_kw=None, planner_kw=None, obstacle_kw=None, tags=None,
-                 tag_capacity=4096):
+                 tag_capacity=4096, view=None):
         """class_map: "reference" (the detector's class names -> the reference's eight ids, everything else skipped:
         reference_class_map), None (raw ids) or an explicit int table.  obstacle_kw: HotLoop's; the defaults stretch the BEV
         panel's 640 x 500 px convention to the frame (x_center = w / 2, x_scale = 0.03 * 640 / w, y_far = 50,
@@ -969,15 +969,23 @@ class CameraLoop:
         self.tag_log (a TagLog of tag_capacity frames per camera): "motion" runs the maneuver tagger (with the lanes' offset), the
         interaction tagger (class_map="reference" only: it needs the reference's class ids) and enqueue_tags; "all" runs the scene
         stage ahead of them (cam.enqueue_scene with the Kalman speed, read on the device) and adds its tags and the detector's
-        traffic elements.  The scene stage is the expensive one, hence not the default of `tags`."""
+        traffic elements.  The scene stage is the expensive one, hence not the default of `tags`.
+        view: None, "camera" or "demo" -- every step() also renders the frame it processed, behind the hot half on the hot stream
+        (enqueue_view): "camera" leaves self.view_cam (uint8 [S, h, w, 3]: the frames with detections, lane area, tracks,
+        info panel and detection summary as demo.py:124-136 draws them), "demo" leaves self.view (uint8 [S, th, tw, 3]: that picture
+        beside the BEV panel, labelled, as create_side_by_side joins them).  The frames themselves are not touched.  The info
+        panel's "FPS" line shows self.view_fps (0.0 until set)."""
         if tags not in (None, "motion", "all"):
             raise ValueError('tags is None, "motion" or "all"')
+        if view not in (None, "camera", "demo"):
+            raise ValueError('view is None, "camera" or "demo"')
         self.S, self.h, self.w = n_streams, h, w
         self.cam = PerceptionLoop(n_streams=n_streams, h=h, w=w, device=device, model=model, precision=precision)
         ok = dict(x_center=w / 2.0, x_scale=0.03 * 640.0 / w, y_far=50.0, y_scale=50.0 / h)
         ok.update(obstacle_kw or {})
         self.hot = HotLoop(n_streams=n_streams, window=1, h=h, w=w, dcap=dcap, device=device, tracker_kw=tracker_kw, kf_kw=kf_kw,
-                           planner_kw=planner_kw, ctx=self.cam.ctx, fused_step=False, obstacles=obstacles, obstacle_kw=ok)
+                           planner_kw=planner_kw, ctx=self.cam.ctx, fused_step=False, obstacles=obstacles, obstacle_kw=ok,
+                           keep_waypoints=True, keep_snapshots=True)          # what enqueue_bev / enqueue_view read
         if isinstance(class_map, str):
             if class_map != "reference":
                 raise ValueError('class_map is "reference", None or an int table')
@@ -996,6 +1004,79 @@ class CameraLoop:
             self._tag_interactions = isinstance(class_map, np.ndarray) and np.array_equal(class_map, reference_class_map(c.yolo.names))
             self._tag_classes = [ObjectDetector.CLASSES[k] for k in range(8)]
             self._elem_table = torch.as_tensor(element_table(c.yolo.names)).to(self.hot.dev) if tags == "all" else None
+        self.view_mode, self.view_fps = view, 0.0
+        self.view = self.view_cam = None
+        if view is not None:
+            self._setup_view()
+
+    VIEW_LABELS = ("Camera View", "Bird's Eye View")         # demo.py:149
+
+    def _setup_view(self):
+        """Device tables and buffers of enqueue_view: the name and colour tables go up once, the argument block is made once."""
+        from .perception.detector import ObjectDetector
+        cam, hot, S, d = self.cam, self.hot, self.S, self.hot.dev
+        is_ref = isinstance(self.class_map, np.ndarray) and np.array_equal(self.class_map, reference_class_map(cam.yolo.names))
+        det_tab, det_len = nat.name_table(cam.yolo.names, "detector class names")
+        trk_tab, trk_len = nat.name_table(ObjectDetector.CLASSES if is_ref else cam.yolo.names, "track class names")
+        colors = np.array([ObjectDetector.CLASS_COLORS[k] for k in range(len(ObjectDetector.CLASS_COLORS))], np.uint8)
+        max_name = int(max(det_len.max(), trk_len.max(), 0))
+        L = hot.tcfg.trajectory_length
+        cap = int(self.hot.L.av_camview_prim_cap(cam.max_det, hot.tcap, L, max_name))
+        if cap <= 0 or cap > 65535:
+            raise ValueError("view: a camera's list may need %d primitives (max_det %d, tcap %d, trajectory_length %d), the rasteriser "
+                             "takes 65535" % (cap, cam.max_det, hot.tcap, L))
+        up = lambda a: torch.as_tensor(np.ascontiguousarray(a)).to(d)       # noqa: E731
+        self._view_tabs = [up(a) for a in (det_tab, det_len, colors, trk_tab, trk_len)]
+        self._view_cap, self._view_vcap = cap, 128
+        self._view_prims = torch.zeros(S, cap, nat.PRIM_BYTES, dtype=torch.uint8, device=d)
+        self._view_n = torch.zeros(S, dtype=torch.int32, device=d)
+        self._view_verts = torch.zeros(S, self._view_vcap, 2, dtype=torch.int32, device=d)
+        tabs = self._view_tabs
+        self._view_args = nat.CamviewArgs(
+            n_streams=S, h=self.h, w=self.w, flags=nat.VIEW_DEMO, n_frames=1, frame=0, max_det=cam.max_det, tcap=hot.tcap,
+            trajectory_length=L, max_name=max_name, n_det_names=len(det_len), n_det_colors=len(colors), n_trk_names=len(trk_len),
+            fps=0.0, det_n=cam.det_n.data_ptr(), det_box=cam.det_box.data_ptr(), det_conf=cam.det_conf.data_ptr(),
+            det_cls=cam.det_cls.data_ptr(), det_names=tabs[0].data_ptr(), det_name_len=tabs[1].data_ptr(), det_colors=tabs[2].data_ptr(),
+            lane_pts=cam.pts.data_ptr(), lane_info=cam.info.data_ptr(), snap=hot.snap.data_ptr(), snap_n=hot.snap_n.data_ptr(),
+            tracker_state=hot.trk_state.data_ptr(), trk_names=tabs[3].data_ptr(), trk_name_len=tabs[4].data_ptr(),
+            vstate=hot.vstate.data_ptr())
+        self._view_geom = None
+        if self.view_mode == "demo":
+            from .visualization.bev_renderer import BEVRenderer
+            r = BEVRenderer(device=d.index)
+            th, nw1, nw2 = C.c_int(), C.c_int(), C.c_int()
+            nat.check(hot.L.av_view_compose_size(self.h, self.w, r.height, r.width, C.byref(th), C.byref(nw1), C.byref(nw2)))
+            self._view_geom = (th.value, nw1.value, nw2.value, r.height, r.width)
+            self.view = torch.zeros(S, th.value, nw1.value + nw2.value, 3, dtype=torch.uint8, device=d)
+        if self.view_mode == "camera" or self._view_geom[0] != self.h:
+            # "demo" with a camera picture shorter than the panel: the painted frames are resized, so they are staged here
+            self.view_cam = torch.zeros(S, self.h, self.w, 3, dtype=torch.uint8, device=d)
+        torch.cuda.current_stream(d).synchronize()          # the buffers are zero-filled before the hot stream writes them
+
+    def enqueue_view(self, fps=0.0, layers=None):
+        """Render what the last step() left in HBM, on the hot stream (call it behind hot.step(); step() does when `view` is
+        set): av_camview_build writes every camera's primitive list, the rasteriser paints it from cam.frames into self.view_cam
+        or straight into the camera half of self.view (av_raster_draw_to: the frames are read, never written), and for "demo"
+        HotLoop.enqueue_bev and av_view_compose add the panel and the labels.  layers: a sum of nat.VIEW_* bits, None = the
+        layers demo.py draws (nat.VIEW_DEMO: no lane-offset gauge)."""
+        if self.view_mode is None:
+            raise RuntimeError('enqueue_view needs CameraLoop(view="camera") or view="demo"')
+        hot, cam, L, a = self.hot, self.cam, self.hot.L, self._view_args
+        a.fps, a.flags = float(fps), nat.VIEW_DEMO if layers is None else int(layers)
+        h, st, S = hot.ctx.handle, hot._s, self.S
+        nat.check(L.av_camview_build(h, st, C.byref(a), nat.ptr(self._view_prims), self._view_cap, nat.ptr(self._view_n),
+                                     nat.ptr(self._view_verts), self._view_vcap))
+        staged = self.view_cam is not None
+        dst, pitch = (self.view_cam, self.w) if staged else (self.view, self.view.shape[2])
+        nat.check(L.av_raster_draw_to(h, st, S, self.h, self.w, nat.ptr(cam.frames), self.w, nat.ptr(dst), pitch, 0,
+                                      nat.ptr(self._view_prims), self._view_cap, nat.ptr(self._view_n), nat.ptr(self._view_verts),
+                                      self._view_vcap))
+        if self.view_mode == "demo":
+            _, _, _, bh, bw = self._view_geom
+            with torch.cuda.stream(hot.stream):             # the panel's buffers, made at the first call, are filled on that stream too
+                hot.enqueue_bev()
+            nat.check(L.av_view_compose(h, st, S, nat.ptr(self.view_cam) if staged else None, self.h, self.w, nat.ptr(hot.bev), bh, bw,
+                                        nat.ptr(self.view), self.VIEW_LABELS[0].encode(), self.VIEW_LABELS[1].encode()))
 
     def load_measurements(self, z):
         """z: float64 [S, 1, 4] (or [S, 4]) ego measurements of the next step (HotLoop.load_measurements)."""
@@ -1014,6 +1095,8 @@ class CameraLoop:
         self.hot.step()
         if self.tags is not None:
             self._enqueue_tags()
+        if self.view_mode is not None:
+            self.enqueue_view(fps=self.view_fps)
         self._stepped = True
         if sync:
             self.synchronize()
