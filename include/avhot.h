@@ -840,9 +840,95 @@ int av_bgr_to_i420(av_ctx* ctx, av_stream_t stream, int n_frames, int h, int w, 
 /* ---- video ingest ----------------------------------------------------------------
  * The pixel half of VideoDataLoader.read_frame / read_frame_at (data/loaders/video_loader.py:88-131): what a decoder hands over
  * as planar YUV 4:2:0 becomes the BGR frame cv2.VideoCapture.read returns, then av_resize_into scales it to target_size
- * (:103-104).  Bitstream decoding is NOT here (no decoder in this image): the loader reads uncompressed containers.
+ * (:103-104).  Baseline JPEG (Motion-JPEG) is decoded by av_jpeg_decode below; no other bitstream decoder is here.
  *   yuv  u8 [n_frames][h*w*3/2]  I420: Y plane, then U, then V (each (h/2) x (w/2));   bgr  u8 [n_frames][h][w][3] */
 int av_i420_to_bgr(av_ctx* ctx, av_stream_t stream, int n_frames, int h, int w, const uint8_t* yuv, uint8_t* bgr);
+
+/* Baseline JPEG (Motion-JPEG in AVI, or a raw .mjpeg stream) decoded on the device: the one compressed format this library opens.
+ * Supported: one SOF0 frame (8-bit, Huffman), one interleaved scan (Ss 0, Se 63, Ah = Al = 0), 1 component (gray) or 3 (YCbCr) with
+ * luma sampling 1x1, 2x1 or 2x2 and 1x1 chroma (4:4:4 / 4:2:2 / 4:2:0), 8-bit DQT, DHT in the frame or absent (then the four "typical"
+ * tables of ITU-T T.81 Annex K, as AVI MJPEG frames expect), optional DRI with RST0-7; APPn / COM are skipped by their length.
+ *
+ * The pixels are those of libjpeg's default path (what Pillow / libjpeg-turbo produce; tests/golden/mjpeg.npz pins them bit for bit):
+ *   entropy   EXTEND(v, s) = v if v >= 2^(s-1) else v - 2^s + 1; the DC predictors are 0 at the start of every restart segment.
+ *   IDCT      jidctint "islow": CONST_BITS 13, PASS1_BITS 2, columns first, on coefficient * quantiser, with the constants
+ *             2446 3196 4433 6270 7373 9633 12299 15137 16069 16819 20995 25172.  Even part: z1 = (in2 + in6) * 4433;
+ *             tmp2 = z1 - in6 * 15137; tmp3 = z1 + in2 * 6270; tmp0 = (in0 + in4) << 13; tmp1 = (in0 - in4) << 13.  Odd part from
+ *             in7, in5, in3, in1 with z5 = (z3 + z4) * 9633 and the multipliers 2446, 16819, 25172, 12299, -7373, -20995, -16069,
+ *             -3196.  Descale with rounding by 11 after the columns and by 18 after the rows, + 128, clamp to 0..255.  (32-bit
+ *             two's-complement arithmetic throughout: what a damaged stream's coefficients overflow wraps.)
+ *   chroma    libjpeg's "fancy" triangle filters over the real chroma extent ceil(w/2) x ceil(h/2) (x h for 4:2:2); edge samples
+ *             stand in for neighbours outside it.  2x1: out[2i] = (3 s[i] + s[i-1] + 1) >> 2, out[2i+1] = (3 s[i] + s[i+1] + 2) >> 2.
+ *             2x2: t[i] = 3 near[i] + far[i] (far: the chroma row above for the upper output row, below for the lower one), then
+ *             out[2i] = (3 t[i] + t[i-1] + 8) >> 4, out[2i+1] = (3 t[i] + t[i+1] + 7) >> 4.
+ *   colour    cb, cr centred by -128: R = Y + ((91881 cr + 32768) >> 16), B = Y + ((116130 cb + 32768) >> 16),
+ *             G = Y + ((-22554 cb - 46802 cr + 32768) >> 16), arithmetic shifts, clamped.  Gray goes to all three channels.
+ * Parity with OpenCV's FFmpeg-based MJPEG decoder is unpinned (neither is in this image).
+ *
+ * av_jpeg_desc: what av_jpeg_parse reads from one frame's headers (928 bytes; quantisers in natural order, Huffman tables as BITS /
+ * HUFFVAL, selectors per component).  seg_base and byte_base are the caller's: where this frame's segments start in the batch's
+ * segment table and where its bytes start in the batch's byte buffer.  av_jpeg_seg: the byte range [begin, end) of one restart
+ * interval's entropy data, relative to the frame's first byte; segment i holds the MCUs [i * restart_interval, ...) (without DRI:
+ * one segment, the whole scan). */
+typedef struct av_jpeg_desc {
+    int32_t width, height, ncomp;       /* ncomp 1 or 3 */
+    int32_t hs, vs;                     /* luma sampling factors: 1x1, 2x1 or 2x2 (1x1 for gray) */
+    int32_t restart_interval;           /* MCUs per segment; 0: no DRI */
+    int32_t n_segments;                 /* ceil(MCUs / restart_interval), or 1 */
+    int32_t flags;                      /* AV_JPEG_ESEGS when the scan held another number of restart intervals; goes into status */
+    int32_t scan_offset;                /* first byte of entropy data */
+    int32_t seg_base;                   /* caller: index of this frame's first av_jpeg_seg in the batch's table */
+    uint32_t byte_base;                 /* caller: offset of this frame's first byte in the batch's byte buffer */
+    int32_t reserved;
+    uint8_t tq[4], td[4], ta[4], pad[4];/* per component: quantiser, DC table, AC table */
+    uint8_t qt[4][64];                  /* natural (row-major) order */
+    uint8_t dc_bits[2][16], dc_val[2][16], ac_bits[2][16], ac_val[2][256];
+} av_jpeg_desc;
+typedef struct av_jpeg_seg {
+    uint32_t begin, end;
+} av_jpeg_seg;
+#define AV_JPEG_DESC_BYTES 928
+
+/* status bits of a decoded frame (0: every segment decoded cleanly).  A segment that hits one of the first four stops there: its
+ * block in progress and all its later blocks decode as all-zero coefficients (mid-gray); other segments and frames are unaffected. */
+#define AV_JPEG_ECODE 1   /* a bit pattern that is no Huffman code */
+#define AV_JPEG_ERUN 2    /* a zero run past coefficient 63 */
+#define AV_JPEG_EBYTES 4  /* the segment's bytes ran out (also: a 0xFF not followed by 0x00 inside it) */
+#define AV_JPEG_ELEFT 8   /* whole bytes left over after the segment's last block */
+#define AV_JPEG_ESEGS 16  /* the scan held fewer or more restart intervals than the frame size asks for (set by av_jpeg_parse) */
+#define AV_JPEG_EDESC 32  /* the descriptor is not one av_jpeg_parse makes for this h x w: nothing decoded, the frame is mid-gray */
+
+/* av_jpeg_parse refuses what is not supported, each kind with its own code (and av_last_error_string): */
+#define AV_EJPEG_TRUNCATED (-101)  /* the bytes end inside the headers */
+#define AV_EJPEG_FORMAT (-102)     /* no SOI, a malformed segment, no frame header before the scan */
+#define AV_EJPEG_SOF (-103)        /* SOF1/2/3/5/6/7: extended, progressive, lossless, hierarchical */
+#define AV_EJPEG_ARITH (-104)      /* SOF9..15 or DAC: arithmetic coding */
+#define AV_EJPEG_PRECISION (-105)  /* sample precision other than 8 */
+#define AV_EJPEG_COMPONENTS (-106) /* neither 1 nor 3 components */
+#define AV_EJPEG_SAMPLING (-107)   /* sampling factors other than 4:4:4, 4:2:2, 4:2:0 */
+#define AV_EJPEG_DQT16 (-108)      /* a 16-bit quantiser table */
+#define AV_EJPEG_MULTISCAN (-109)  /* a scan that does not hold every component, or a second scan */
+#define AV_EJPEG_SIZE (-110)       /* the frame is not h x w */
+#define AV_EJPEG_TABLE (-111)      /* a table that is missing, out of range or no prefix code */
+#define AV_EJPEG_SCAN (-112)       /* scan parameters other than Ss 0, Se 63, Ah 0, Al 0 */
+#define AV_EJPEG_SEGCAP (-113)     /* more restart intervals than seg_cap */
+
+/* Host half, needs no context and no device.  Reads one frame (`len` bytes from SOI) that has to be h x w, fills *desc (seg_base and
+ * byte_base left 0) and segs[0 .. desc->n_segments), found by walking the scan for FF D0-D7 / FF D9 (FF 00 is stuffing; a scan that
+ * ends without EOI ends at `len`).  Every offset is <= len.  -> AV_OK, AV_EINVAL (null / non-positive argument) or AV_EJPEG_*. */
+int av_jpeg_parse(const uint8_t* data, size_t len, int h, int w, av_jpeg_desc* desc, av_jpeg_seg* segs, int seg_cap, int* n_segs);
+
+/* Device half.  Decodes n_frames frames of one h x w in one call into bgr u8 [n_frames][h][w][3] and status i32 [n_frames] (AV_JPEG_E*
+ * bits).  desc [n_frames], segs [n_segs_total] and bytes [n_bytes] are DEVICE copies; bytes is 4-byte aligned and n_bytes includes at
+ * least 8 bytes of padding behind the last frame.  A batch may mix frames of different files, tables, subsampling and restart
+ * intervals.  max_segs sizes the entropy launch (one lane per frame and restart segment): a frame whose n_segments exceeds it is not
+ * decoded (AV_JPEG_EDESC, mid-gray).  The kernels
+ * bound every descriptor field, segment index and byte offset themselves (AV_JPEG_EDESC / clamped to n_bytes), so a wrong table
+ * cannot make them read or write outside the buffers given here.  workspace: av_jpeg_workspace_bytes(n_frames, h, w) bytes, 16-byte
+ * aligned, contents irrelevant before and after.  Enqueues four kernels on `stream`; no host synchronisation, no allocation. */
+size_t av_jpeg_workspace_bytes(int n_frames, int h, int w);
+int av_jpeg_decode(av_ctx* ctx, av_stream_t stream, int n_frames, int h, int w, const av_jpeg_desc* desc, const av_jpeg_seg* segs,
+                   int n_segs_total, int max_segs, const uint8_t* bytes, size_t n_bytes, void* workspace, uint8_t* bgr, int32_t* status);
 
 /* ---- synthetic input ---------------------------------------------------
  * Deterministic 8-bit BGR road scenes generated on the device, standing in for the reference's lost

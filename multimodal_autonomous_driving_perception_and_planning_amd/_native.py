@@ -115,6 +115,21 @@ class YoloOpInfo(C.Structure):
 YOLO_OP_CONV, YOLO_OP_STEM, YOLO_OP_POOLS, YOLO_OP_MAXPOOL, YOLO_OP_UPSAMPLE = range(5)
 
 
+class JpegDesc(C.Structure):
+    """av_jpeg_desc (include/avhot.h): one frame's headers as av_jpeg_parse reads them; 928 bytes."""
+    _fields_ = ([(k, C.c_int32) for k in ("width", "height", "ncomp", "hs", "vs", "restart_interval", "n_segments", "flags", "scan_offset",
+                                          "seg_base")] + [("byte_base", C.c_uint32), ("reserved", C.c_int32)] +
+                [(k, C.c_uint8 * 4) for k in ("tq", "td", "ta", "pad")] + [("qt", C.c_uint8 * 64 * 4)] +
+                [("dc_bits", C.c_uint8 * 16 * 2), ("dc_val", C.c_uint8 * 16 * 2), ("ac_bits", C.c_uint8 * 16 * 2), ("ac_val", C.c_uint8 * 256 * 2)])
+
+
+JPEG_DESC_BYTES = 928
+JPEG_SEG_FIELDS = [("begin", "<u4"), ("end", "<u4")]
+JPEG_ECODE, JPEG_ERUN, JPEG_EBYTES, JPEG_ELEFT, JPEG_ESEGS, JPEG_EDESC = 1, 2, 4, 8, 16, 32
+(EJPEG_TRUNCATED, EJPEG_FORMAT, EJPEG_SOF, EJPEG_ARITH, EJPEG_PRECISION, EJPEG_COMPONENTS, EJPEG_SAMPLING, EJPEG_DQT16, EJPEG_MULTISCAN,
+ EJPEG_SIZE, EJPEG_TABLE, EJPEG_SCAN, EJPEG_SEGCAP) = range(-101, -114, -1)
+
+
 class InteractionCfg(C.Structure):
     _fields_ = [("frame_h", C.c_int32), ("frame_w", C.c_int32), ("class_kind", C.c_int32 * 16)]
 PRIM_FIELDS = [("type", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("x2", "<i4"), ("y2", "<i4"),
@@ -232,6 +247,9 @@ _SIGS = [
     ("av_view_compose", C.c_int, [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_char_p, C.c_char_p]),
     ("av_format_fixed", C.c_int, [C.c_double, C.c_int, vp, C.c_int]),
     ("av_bgr_to_i420", C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
+    ("av_jpeg_parse", C.c_int, [vp, C.c_size_t, C.c_int, C.c_int, vp, vp, C.c_int, C.POINTER(C.c_int)]),
+    ("av_jpeg_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    ("av_jpeg_decode", C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_size_t, vp, vp, vp]),
     ("av_synth_frames", C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     ("av_maneuver_reset", C.c_int, [vp, vp, C.c_int, vp]),
     ("av_interaction_state_bytes", C.c_size_t, [C.c_int]),

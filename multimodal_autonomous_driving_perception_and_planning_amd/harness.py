@@ -53,7 +53,8 @@ def synthetic_frame(h=720, w=1280, stream=0, frame=0):
     return img.astype(np.uint8)
 
 
-def run_loop(num_frames=300, h=720, w=1280, lanes=True, verbose=True):
+def run_loop(num_frames=300, h=720, w=1280, lanes=True, verbose=True, video=None):
+    """video: a file VideoDataLoader opens (.y4m, .npy, Motion-JPEG .avi / .mjpeg) instead of synthetic frames."""
     from .perception import LaneDetector, ObjectDetector
     from .planning import MotionPlanner
     from .state_estimation import VehicleStateEstimator
@@ -61,11 +62,19 @@ def run_loop(num_frames=300, h=720, w=1280, lanes=True, verbose=True):
 
     detector, lane_detector = ObjectDetector(mode="simulated"), LaneDetector()
     tracker, estimator, planner = MultiObjectTracker(), VehicleStateEstimator(), MotionPlanner()
+    loader = None
+    if video is not None:
+        from .loaders import VideoDataLoader
+        loader = VideoDataLoader(video)
+        num_frames = min(num_frames, len(loader))
     ego = generate_ego_motion(num_frames)
-    frames = [synthetic_frame(h, w, 0, f) for f in range(min(num_frames, 8))]
+    frames = [synthetic_frame(h, w, 0, f) for f in range(min(num_frames, 8))] if loader is None else []
     t0 = time.perf_counter()
     for i in range(num_frames):
-        frame = frames[i % len(frames)]
+        frame = frames[i % len(frames)] if loader is None else loader.read_frame()
+        if frame is None:                                # a frame that does not decode ends the run, like a failed cap.read()
+            num_frames = i
+            break
         detections = detector.detect(frame)
         left, right = lane_detector.detect(frame) if lanes else (None, None)
         tracks = tracker.update(detections)
@@ -117,11 +126,12 @@ def main(argv=None):
     ap.add_argument("--test", action="store_true")
     ap.add_argument("--frames", type=int, default=300)
     ap.add_argument("--no-lanes", action="store_true")
+    ap.add_argument("--video", default=None, help="run the loop on this file (.y4m, .npy, Motion-JPEG .avi / .mjpeg)")
     a = ap.parse_args(argv)
     if a.test:
         self_test()
     else:
-        print("Average FPS: %.1f" % run_loop(a.frames, lanes=not a.no_lanes))
+        print("Average FPS: %.1f" % run_loop(a.frames, lanes=not a.no_lanes, video=a.video))
 
 
 if __name__ == "__main__":

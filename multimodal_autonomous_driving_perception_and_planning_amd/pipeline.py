@@ -768,6 +768,24 @@ class PerceptionLoop:
                                          nat.ptr(self.frames)))
         self.frame_idx += 1
 
+    def enqueue_frames(self, frames=None):
+        """The step's input on the loop's stream.  None: generate (enqueue_generate).  A uint8 device tensor [S, h, w, 3]: copied into
+        self.frames (nothing is enqueued when it IS self.frames); the caller orders whatever produced it before the loop's stream.
+        An object with read_into(dst, stream) -- a loaders.VideoFeed -- decodes straight into self.frames.  frame_idx advances."""
+        if frames is None:
+            return self.enqueue_generate()
+        if hasattr(frames, "read_into"):
+            frames.read_into(self.frames, self.stream)
+        else:
+            if (not torch.is_tensor(frames) or frames.device != self.frames.device or frames.dtype != torch.uint8
+                    or tuple(frames.shape) != tuple(self.frames.shape)):
+                raise ValueError("frames must be a uint8 tensor %s on %s, or an object with read_into()" % (
+                    tuple(self.frames.shape), self.frames.device))
+            if frames.data_ptr() != self.frames.data_ptr() or not frames.is_contiguous():
+                with torch.cuda.stream(self.stream):
+                    self.frames.copy_(frames, non_blocking=True)
+        self.frame_idx += 1
+
     def enqueue_detect(self):
         nat.check(self.L.av_yolo_forward(self.yolo._h, self._s, nat.ptr(self.frames), 0.25, 0.7, self.max_det,
                                          nat.ptr(self.det_n), nat.ptr(self.det_box), nat.ptr(self.det_conf),
@@ -780,11 +798,11 @@ class PerceptionLoop:
                                         nat.ptr(self.frames), None, nat.ptr(self.ws), nat.ptr(self.lane_state),
                                         nat.ptr(self.poly), nat.ptr(self.pts), nat.ptr(self.info), nat.ptr(self.conf), stages))
 
-    def step(self, sync=False):
-        """generate; fork{lanes} || {detect}; join.  The detector and the lane chain only share the frames: the
-        lane chain (mostly the sequential per-frame PPHT, one CU per frame) runs beside the convolutions."""
+    def step(self, sync=False, frames=None):
+        """generate (or take `frames`: see enqueue_frames); fork{lanes} || {detect}; join.  The detector and the lane chain only
+        share the frames: the lane chain (mostly the sequential per-frame PPHT, one CU per frame) runs beside the convolutions."""
         h = self.ctx.handle
-        self.enqueue_generate()
+        self.enqueue_frames(frames)
         nat.check(self.L.av_fork(h, self._s))
         self.enqueue_lanes(self.ctx.side_stream)
         self.enqueue_detect()
@@ -840,14 +858,14 @@ class PerceptionLoop:
     def join_detector_tail(self):
         nat.check(self.L.av_yolo_join_tail(self.yolo._h, self._s))
 
-    def step_deferred(self):
+    def step_deferred(self, frames=None):
         """Throughput variant of step(): the Hough + fit half of a frame's lane chain is enqueued one step late, ahead
         of the next frame's pixel stages on the side stream.  The sharded PPHT holds 158 KB of LDS on every CU it
         runs on, which keeps the LDS-tiled convolutions off those CUs; one step late it runs beside the detector's
         preprocess + stem + first stride-2 convolution, which use no LDS.  Same kernels, same per-stream order, same
         results; the lane outputs (poly / pts / info / conf) describe the PREVIOUS frame until flush_lanes()."""
         h = self.ctx.handle
-        self.enqueue_generate()
+        self.enqueue_frames(frames)
         nat.check(self.L.av_fork(h, self._s))
         if self._lanes_pending:
             self.enqueue_lanes(self.ctx.side_stream, stages=nat.LANE_HOUGH_ONLY)
@@ -1082,15 +1100,16 @@ class CameraLoop:
         """z: float64 [S, 1, 4] (or [S, 4]) ego measurements of the next step (HotLoop.load_measurements)."""
         self.hot.load_measurements(z)
 
-    def step(self, sync=False):
-        """cam.step(); hot.step() behind it.  The camera half of the next step overwrites what the hot half reads (det_*, poly,
-        pts, info), so it first waits for the hot half of this one."""
+    def step(self, sync=False, frames=None):
+        """cam.step(frames=frames); hot.step() behind it.  The camera half of the next step overwrites what the hot half reads (det_*,
+        poly, pts, info -- and cam.frames, which the view and the scene stage read there), so it first waits for the hot half of this
+        one; the decode or copy of given `frames` (PerceptionLoop.enqueue_frames) is enqueued behind that wait like the generator."""
         if self.cam._tail_deferred or self.cam._lanes_pending:
             raise RuntimeError("CameraLoop steps the plain PerceptionLoop.step(): with a deferred detector tail or a pending lane "
                                "half det_* / poly describe the previous frame")
         if self._stepped:
             self.cam.stream.wait_stream(self.hot.stream)
-        self.cam.step()
+        self.cam.step(frames=frames)
         self.hot.stream.wait_stream(self.cam.stream)
         self.hot.step()
         if self.tags is not None:
