@@ -1,3 +1,3 @@
-from .video_loader import VideoDataLoader, VideoFeed, Y4MWriter  # noqa: F401
+from .video_loader import VideoDataLoader, MJPEGWriter, VideoFeed, Y4MWriter  # noqa: F401
 
-__all__ = ["VideoDataLoader", "VideoFeed", "Y4MWriter"]
+__all__ = ["VideoDataLoader", "VideoFeed", "Y4MWriter", "MJPEGWriter"]

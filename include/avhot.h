@@ -930,6 +930,51 @@ size_t av_jpeg_workspace_bytes(int n_frames, int h, int w);
 int av_jpeg_decode(av_ctx* ctx, av_stream_t stream, int n_frames, int h, int w, const av_jpeg_desc* desc, const av_jpeg_seg* segs,
                    int n_segs_total, int max_segs, const uint8_t* bytes, size_t n_bytes, void* workspace, uint8_t* bgr, int32_t* status);
 
+/* ---- video output: baseline JPEG (Motion-JPEG) encoded on the device ------------------------------------
+ * Frames of BGR u8 become baseline JPEG frames that equal, byte for byte, what libjpeg's default compress path writes (Pillow /
+ * libjpeg-turbo; tests/golden/mjpeg_encode.npz pins them): three components (Y, Cb, Cr), 4:2:0, 4:2:2 or 4:4:4, any h, w >= 1, the
+ * Annex K Huffman tables, quantisers from `quality`, optional restart intervals.  Grayscale, progressive, optimised Huffman tables
+ * and 16-bit quantisers are out of scope.  All arithmetic is 32-bit integer:
+ *   colour    FIX(x) = int(x * 65536 + 0.5): Y = (FIX(.299) R + FIX(.587) G + FIX(.114) B + 32768) >> 16,
+ *             Cb = (-FIX(.168735892) R - FIX(.331264108) G + FIX(.5) B + (128 << 16) + 32767) >> 16,
+ *             Cr = (FIX(.5) R - FIX(.418687589) G - FIX(.081312411) B + (128 << 16) + 32767) >> 16.
+ *   edges     luma is edge-replicated to whole MCUs.  Full-resolution chroma is replicated to the right to whole MCUs and at the
+ *             bottom only to a multiple of the vertical sampling factor, then downsampled (4:2:2: (a + b + bias) >> 1, bias 0, 1, 0,
+ *             1 .. along the output row; 4:2:0: (a + b + c + d + bias) >> 2, bias 1, 2, 1, 2 ..); the downsampled plane is then
+ *             replicated down to whole MCUs.
+ *   DCT       jfdctint "islow" on samples - 128: CONST_BITS 13, PASS1_BITS 2, the constants of the decoder's IDCT; rows first
+ *             (outputs scaled up by 4, the odd part descaled by 11), then columns (even terms descaled by 2, the rest by 15).
+ *   quantise  sign(c) * ((|c| + (8 q >> 1)) / (8 q)).  Tables: scale = 5000 / quality below 50, else 200 - 2 quality;
+ *             (base * scale + 50) / 100 clamped to 1..255 over the Annex K luminance and chrominance tables.
+ *   dummies   blocks of an MCU wholly outside ceil(w/8) x ceil(h/8) luma blocks take no pixels: AC 0, DC of the block coded before
+ *             them in the MCU.
+ *   entropy   differential DC per component (0 at every restart), run/size symbols with ZRL and EOB, bits MSB first, the last byte
+ *             of every restart interval and of the scan padded with 1-bits, FF followed by 00, RST(k mod 8) between intervals.
+ *   layout    SOI, APP0 JFIF 1.01 (units 0, density 1 x 1), DQT luma, DQT chroma, SOF0, DHT DC0, AC0, DC1, AC1, DRI when a restart
+ *             interval is set, SOS, data, EOI. */
+#define AV_JPEG_444 0
+#define AV_JPEG_422 1
+#define AV_JPEG_420 2
+#define AV_JPEG_EFULL 64  /* status bit of an encoded frame: it needs more than out_cap bytes (len tells how many) */
+
+/* Host half, needs no context and no device.  Writes SOI .. the SOS header of an h x w frame into out (cap bytes; 640 always
+ * suffice) and the two quantiser tables, natural order, into qt (what av_jpeg_encode takes).  restart_mcus: -1 one MCU row per
+ * restart interval, 0 no restart markers, else MCUs per interval, 1..65535.  -> the header's length, or AV_EINVAL (null pointer,
+ * h or w outside 1..65535 or more than 2^21 blocks, quality outside 1..100, unknown subsampling, bad restart_mcus, cap too small). */
+int av_jpeg_encode_header(int h, int w, int quality, int subsampling, int restart_mcus, uint8_t* out, int cap, uint8_t qt[2][64]);
+
+/* Device half.  Encodes n_frames frames bgr u8 [n_frames][h][w][3] in one call.  qt (u8 [2][64]) and header (header_len bytes, as
+ * av_jpeg_encode_header made them for the same h, w, subsampling and restart_mcus) are DEVICE copies.  Frame k is written
+ * contiguously at out + k * out_cap: header, scan, EOI.  len[k] (i32, device) is the length the frame needs whether or not it
+ * fitted; status[k] is 0, or AV_JPEG_EFULL when len[k] > out_cap: then nothing is written at or beyond out + (k + 1) * out_cap and
+ * the content of that slot is unspecified.  workspace: av_jpeg_encode_workspace_bytes(n_frames, h, w, subsampling) bytes, 16-byte
+ * aligned, contents irrelevant before and after (0: bad arguments).  The kernels index the caller's buffers by the geometry of the
+ * arguments checked here only.  Enqueues nine kernels on `stream`; no host synchronisation, no allocation. */
+size_t av_jpeg_encode_workspace_bytes(int n_frames, int h, int w, int subsampling);
+int av_jpeg_encode(av_ctx* ctx, av_stream_t stream, int n_frames, int h, int w, const uint8_t* bgr, const uint8_t* qt, int subsampling,
+                   int restart_mcus, const uint8_t* header, int header_len, void* workspace, uint8_t* out, int out_cap, int32_t* len,
+                   int32_t* status);
+
 /* ---- synthetic input ---------------------------------------------------
  * Deterministic 8-bit BGR road scenes generated on the device, standing in for the reference's lost
  * SyntheticDataGenerator (data/generators, source absent).  Frame (stream0+s, frame) is bit-identical to

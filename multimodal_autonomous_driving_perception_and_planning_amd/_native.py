@@ -126,6 +126,8 @@ class JpegDesc(C.Structure):
 JPEG_DESC_BYTES = 928
 JPEG_SEG_FIELDS = [("begin", "<u4"), ("end", "<u4")]
 JPEG_ECODE, JPEG_ERUN, JPEG_EBYTES, JPEG_ELEFT, JPEG_ESEGS, JPEG_EDESC = 1, 2, 4, 8, 16, 32
+JPEG_EFULL, JPEG_HEADER_MAX = 64, 640              # av_jpeg_encode
+JPEG_SUBSAMPLING = {"444": 0, "422": 1, "420": 2}
 (EJPEG_TRUNCATED, EJPEG_FORMAT, EJPEG_SOF, EJPEG_ARITH, EJPEG_PRECISION, EJPEG_COMPONENTS, EJPEG_SAMPLING, EJPEG_DQT16, EJPEG_MULTISCAN,
  EJPEG_SIZE, EJPEG_TABLE, EJPEG_SCAN, EJPEG_SEGCAP) = range(-101, -114, -1)
 
@@ -250,6 +252,9 @@ _SIGS = [
     ("av_jpeg_parse", C.c_int, [vp, C.c_size_t, C.c_int, C.c_int, vp, vp, C.c_int, C.POINTER(C.c_int)]),
     ("av_jpeg_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     ("av_jpeg_decode", C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_size_t, vp, vp, vp]),
+    ("av_jpeg_encode_header", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
+    ("av_jpeg_encode_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("av_jpeg_encode", C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, vp]),
     ("av_synth_frames", C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     ("av_maneuver_reset", C.c_int, [vp, vp, C.c_int, vp]),
     ("av_interaction_state_bytes", C.c_size_t, [C.c_int]),

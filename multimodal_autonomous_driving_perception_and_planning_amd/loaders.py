@@ -15,8 +15,12 @@ Inter-frame codecs (mp4 / mov / mkv, non-MJPG avi) raise ValueError naming the m
 as the reference class, plus read_frames_device() / read_frames_into(), which leave a batch of frames in HBM for the batched
 pipeline, and VideoFeed, which reads frame k of S files in one decode call (what PerceptionLoop / CameraLoop step on).
 
-Y4MWriter is the way out: where the reference hands its annotated frames to cv2.VideoWriter (demo.py:84-90, :170), this writes them
-as a 4:2:0 `.y4m` file the loader above (or ffmpeg) reads, converting on the device (av_bgr_to_i420).
+The way out, where the reference hands its annotated frames to cv2.VideoWriter (demo.py:84-90, :170):
+  * MJPEGWriter  Motion-JPEG, `.avi` (video_index.AviWriter) or a raw `.mjpeg` / `.mjpg` stream: a batch is encoded on the device in one
+                 av_jpeg_encode call (baseline JPEG, byte for byte libjpeg's / Pillow's frames), and only the compressed bytes come down,
+                 about 0.1 byte per pixel.  Any player and browser opens the file, and so does the loader above;
+  * Y4MWriter    uncompressed 4:2:0 `.y4m` (av_bgr_to_i420, 1.5 bytes per pixel), which the loader above (or ffmpeg) reads.
+Grayscale, progressive and optimised-Huffman JPEG are not written.
 """
 import ctypes as C
 import mmap
@@ -428,3 +432,109 @@ class Y4MWriter:
         if self._f is not None:
             self._f.close()
             self._f = None
+
+
+class MJPEGWriter:
+    """Motion-JPEG video file, encoded on the device.  MJPEGWriter(path, fps, (width, height), quality=85, subsampling="420" | "422" |
+    "444", restart_mcus=-1 (one restart interval per MCU row; 0: none; else MCUs per interval)); write(frame) takes one BGR frame on
+    the host like cv2.VideoWriter.write, write_device(batch) a uint8 device tensor [n, height, width, 3]: one av_jpeg_encode call, a
+    download of the lengths, then of the used bytes only.  `.avi` gives an AVI with an MJPG stream, `.mjpeg` / `.mjpg` the frames one
+    behind the other.  release() (or leaving the `with` block) finishes the file.  Every frame is what libjpeg writes for the same
+    pixels and parameters; odd sizes are fine."""
+
+    def __init__(self, path: str, fps: float, size: Tuple[int, int], quality: int = 85, subsampling: str = "420", restart_mcus: int = -1,
+                 device: int = 0):
+        w, h = int(size[0]), int(size[1])
+        self.path = Path(path)
+        suf = self.path.suffix.lower()
+        if suf not in (".avi", ".mjpeg", ".mjpg"):
+            raise ValueError("MJPEGWriter: %s is neither .avi nor .mjpeg / .mjpg" % self.path.name)
+        if subsampling not in nat.JPEG_SUBSAMPLING:
+            raise ValueError("MJPEGWriter: subsampling must be one of '420', '422', '444', got %r" % (subsampling,))
+        if not float(fps) > 0:
+            raise ValueError("MJPEGWriter: fps must be positive")
+        self.fps, self.width, self.height, self.quality, self.subsampling = float(fps), w, h, int(quality), subsampling
+        self.restart_mcus, self._sub = int(restart_mcus), nat.JPEG_SUBSAMPLING[subsampling]
+        head, qt = (C.c_uint8 * nat.JPEG_HEADER_MAX)(), (C.c_uint8 * 128)()
+        n = nat.lib().av_jpeg_encode_header(h, w, self.quality, self._sub, self.restart_mcus, head, nat.JPEG_HEADER_MAX, qt)
+        if n < 0:
+            raise ValueError("MJPEGWriter: %s" % nat.lib().av_last_error_string().decode())
+        self._dev = Dev(device)
+        self._header_len = int(n)
+        const = np.zeros(128 + nat.JPEG_HEADER_MAX, np.uint8)                  # quantisers, then the header: one upload
+        const[:128], const[128:128 + n] = np.frombuffer(qt, np.uint8), np.frombuffer(head, np.uint8)[:n]
+        self._const = self._dev.upload(const, np.uint8)
+        self._ws = None
+        self._cap = h * w                                                      # bytes per frame slot; grows when a frame needs more
+        self._frames = self._bytes = 0
+        self.last_call = None                                                  # (n, out_cap, retried) of the last write_device
+        self._avi = video_index.AviWriter(str(self.path), self.fps, w, h) if suf == ".avi" else None
+        self._f = None if self._avi else open(self.path, "wb")
+        self._open = True
+
+    frames_written = property(lambda self: self._frames)
+    bytes_written = property(lambda self: self._avi.bytes_written if self._avi else self._bytes)
+
+    def _encode(self, batch, n, cap):
+        d, L = self._dev, self._dev.lib
+        out = d.empty((n, cap), torch.uint8)
+        info = d.empty((2, n), torch.int32)
+        c = self._const.data_ptr()
+        nat.check(L.av_jpeg_encode(d.ctx.handle, d.stream, n, self.height, self.width, nat.ptr(batch), c, self._sub, self.restart_mcus, c + 128,
+                                   self._header_len, nat.ptr(self._ws), nat.ptr(out), cap, nat.ptr(info[0]), nat.ptr(info[1])))
+        return out, info.cpu().numpy()
+
+    def write_device(self, batch: torch.Tensor):
+        if not self._open:
+            raise ValueError("MJPEGWriter: the file is closed")
+        if (not torch.is_tensor(batch) or not batch.is_cuda or batch.dtype != torch.uint8 or batch.dim() != 4
+                or tuple(batch.shape[1:]) != (self.height, self.width, 3)):
+            raise ValueError("MJPEGWriter.write_device: expected a uint8 device tensor [n, %d, %d, 3]" % (self.height, self.width))
+        n = int(batch.shape[0])
+        if n == 0:
+            return
+        d = self._dev
+        batch = batch.contiguous()
+        ws = int(d.lib.av_jpeg_encode_workspace_bytes(n, self.height, self.width, self._sub))
+        if self._ws is None or self._ws.numel() < ws:
+            self._ws = d.empty((ws,), torch.uint8)
+        out, (lens, status) = self._encode(batch, n, self._cap)
+        retried = bool((status & nat.JPEG_EFULL).any())
+        if retried:                                                            # once more, sized by what the frames need
+            self._cap = (int(lens.max()) + 4095) & ~4095
+            out, (lens, status) = self._encode(batch, n, self._cap)
+        if status.any():
+            raise RuntimeError("MJPEGWriter: av_jpeg_encode status %s" % status.tolist())
+        self.last_call = (n, self._cap, retried)
+        used = int(lens.max())
+        host = out[:, :used].cpu().numpy()                                     # only the bytes the longest frame uses
+        for k in range(n):
+            data = host[k, :int(lens[k])].tobytes()
+            if self._avi:
+                self._avi.add(data)
+            else:
+                self._f.write(data)
+                self._bytes += len(data)
+            self._frames += 1
+
+    def write(self, frame: np.ndarray):
+        if not self._open:
+            raise ValueError("MJPEGWriter: the file is closed")
+        if not isinstance(frame, np.ndarray) or frame.dtype != np.uint8 or frame.shape != (self.height, self.width, 3):
+            raise ValueError("MJPEGWriter.write: expected a %dx%dx3 uint8 frame, got %s %s" % (
+                self.height, self.width, getattr(frame, "dtype", type(frame).__name__), getattr(frame, "shape", "")))
+        self.write_device(self._dev.upload(np.ascontiguousarray(frame)[None], np.uint8))
+
+    def release(self):
+        if self._open:
+            self._open = False
+            if self._avi:
+                self._avi.close()
+            else:
+                self._f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.release()

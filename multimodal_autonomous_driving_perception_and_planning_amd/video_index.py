@@ -3,6 +3,7 @@
 index_avi(buf)    RIFF AVI 1.0 with an MJPG video stream -> {"width", "height", "fps", "frames": [(offset, length)], "indexed"}
 index_mjpeg(buf)  a raw concatenation of JPEG frames      -> [(offset, length)]
 jpeg_size(buf, offset, length)  -> (width, height) of the frame header, or None
+AviWriter(path, fps, width, height)  writes such an AVI: add(jpeg_bytes) per frame, close() patches the counts and appends idx1
 
 `buf` is anything with len(), slicing to bytes and find(): bytes, or an mmap of the file.  Every (offset, length) lies inside buf.
 """
@@ -162,3 +163,67 @@ def jpeg_size(buf, offset, length):
             break
         p += 2 + L
     return None
+
+
+class AviWriter:
+    """RIFF AVI 1.0 with one MJPG video stream, what index_avi reads: hdrl (avih, one strl: strh `vids` / `MJPG` + strf), a `movi` list
+    of `00dc` chunks padded to even length, and idx1 (offsets relative to the `movi` tag).  add(data) appends one JPEG frame;
+    close() writes idx1 and patches the frame count, the largest frame and the list sizes.  The file stays below 2 GB (AVI 1.0 without
+    OpenDML): the add() that would cross it raises ValueError and writes nothing."""
+    LIMIT = (1 << 31) - 1
+
+    def __init__(self, path, fps, width, height):
+        w, h, fps = int(width), int(height), float(fps)
+        if w <= 0 or h <= 0 or not fps > 0:
+            raise ValueError("AviWriter: bad size %dx%d or fps %r" % (w, h, fps))
+        self.width, self.height, self.fps = w, h, fps
+        self._rate, self._scale = int(round(fps * 1000)), 1000
+        self._index, self._largest = [], 0
+        self._f = open(path, "wb")
+        self._f.write(self._head())
+        self._movi = self._f.tell() - 4                 # offset of the 'movi' tag
+        self._pos = self._f.tell()
+
+    frames = property(lambda self: len(self._index))
+    bytes_written = property(lambda self: self._pos)
+
+    def _head(self, movi_bytes=4, riff_bytes=0):
+        n, w, h = len(self._index), self.width, self.height
+        avih = struct.pack("<14I", int(round(1e6 / self.fps)), 0, 0, 0x10, n, 0, 1, self._largest, w, h, 0, 0, 0, 0)
+        strh = b"vids" + b"MJPG" + struct.pack("<IHHIIIIIIII4h", 0, 0, 0, 0, self._scale, self._rate, 0, n, self._largest, 0xFFFFFFFF, 0, 0, 0, w, h)
+        strf = struct.pack("<IiiHH4sIiiII", 40, w, h, 1, 24, b"MJPG", w * h * 3, 0, 0, 0, 0)
+        strl = b"strl" + b"strh" + struct.pack("<I", len(strh)) + strh + b"strf" + struct.pack("<I", len(strf)) + strf
+        hdrl = b"hdrl" + b"avih" + struct.pack("<I", len(avih)) + avih + b"LIST" + struct.pack("<I", len(strl)) + strl
+        return (b"RIFF" + struct.pack("<I", riff_bytes) + b"AVI " + b"LIST" + struct.pack("<I", len(hdrl)) + hdrl +
+                b"LIST" + struct.pack("<I", movi_bytes) + b"movi")
+
+    def _closing_bytes(self, frames):
+        return 8 + 16 * frames                          # the idx1 chunk
+
+    def add(self, data):
+        if self._f is None:
+            raise ValueError("AviWriter: the file is closed")
+        n = len(data)
+        if self._pos + 8 + n + (n & 1) + self._closing_bytes(len(self._index) + 1) > self.LIMIT:
+            raise ValueError("AviWriter: the file would pass 2 GB, which needs OpenDML (not written here); start another file")
+        self._f.write(b"00dc" + struct.pack("<I", n))
+        self._f.write(data)
+        if n & 1:
+            self._f.write(b"\0")
+        self._index.append((self._pos - self._movi, n))
+        self._largest = max(self._largest, n)
+        self._pos += 8 + n + (n & 1)
+
+    def close(self):
+        if self._f is None:
+            return
+        f, self._f = self._f, None
+        try:
+            f.write(b"idx1" + struct.pack("<I", 16 * len(self._index)))
+            f.write(b"".join(b"00dc" + struct.pack("<III", 0x10, o, n) for o, n in self._index))
+            end = self._pos + self._closing_bytes(len(self._index))
+            f.seek(0)
+            f.write(self._head(self._pos - self._movi, end - 8))
+        finally:
+            f.close()
+        self._pos = end
