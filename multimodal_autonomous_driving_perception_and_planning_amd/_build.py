@@ -28,8 +28,8 @@ def sources():
 
 
 def _deps_mtime(src, seen=None):
-    """Newest modification time of `src` and of everything it includes from csrc/ or include/ (step.hip includes the stage
-    files themselves, not only headers)."""
+    """Newest modification time of `src` and of everything it includes, directly or not, from csrc/ or include/ (a stage's
+    *_dev.h is included by the stage's own .hip and by step.hip: touching it rebuilds both)."""
     import re
     seen = set() if seen is None else seen
     if src in seen or not os.path.exists(src):

@@ -5,8 +5,8 @@
 // their launches: four graph nodes, ~60 us per step of 64 frames, of which ~16 us graph replay and 23 us a planner kernel for 64
 // start states.  Here the step is one kernel with role-split workgroups, every role running the stage kernels' OWN device code
 // (simdet_frame, tracker_body, kf_axis_chain1 + kf_axis_tail1 -- kf_axis_body's one-frame step, same expressions -- / kf_dense_stream,
-// plan_block: this file includes the stage files for their device parts), so the results are those of the separate launches bit for
-// bit (tests/test_gpu_step.py, tests/test_gpu_step_roles.py):
+// plan_block: the stages' *_dev.h headers, which this file and the stage files both include), so the results are those of the separate
+// launches bit for bit (tests/test_gpu_step.py, tests/test_gpu_step_roles.py):
 //   workgroups [0, S)      stream s: simulated detections of its next frame (one thread: a 232-byte table row + box arithmetic),
 //                          then the tracker frame on eight replica waves, then -- optionally -- the stream's 32-byte-per-row
 //                          wire table for the all-gather (exchange.hip's format), all from the same workgroup
@@ -24,12 +24,10 @@
 // hot_step_kernel<12> is compiled for that and takes 78 with no scratch and no scalar spill (DESIGN.md section 4b has the figures and
 // what it took: each role loads its arguments inside its own branch, the debug clocks carry nothing in registers, the planner's wave
 // number is a scalar value).
-#define AVHOT_DEVICE_ONLY
-#include "simdet.hip"
-#include "tracker.hip"
-#include "kf.hip"
-#include "planner.hip"
-#undef AVHOT_DEVICE_ONLY
+#include "simdet_dev.h"
+#include "tracker_dev.h"
+#include "kf_dev.h"
+#include "planner_dev.h"
 
 namespace {
 

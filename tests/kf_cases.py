@@ -19,7 +19,7 @@ D = (0.5, 2.0, 0.25)
 Z = (0.0, 0.1, 1.0)            # dt = 0: acceleration and yaw rate are exactly 0
 SETTINGS = {"A": A, "B": B, "C": C, "D": D, "Z": Z}
 
-KF_BATCH = 64                  # frames per batch of the kernel's lane = frame extract (csrc/kf.hip)
+KF_BATCH = 64                  # frames per batch of the kernel's lane = frame extract (csrc/kf_dev.h)
 MARGIN = 1e-6
 
 _SPEEDS = (0.0, 0.0, 0.03, 3.0, 8.0)

@@ -49,6 +49,20 @@ def test_step_structs_match_header():
     assert nat.StepLoop.frame_count.offset % 8 == 0 and nat.StepLoop.frame_count.offset == nat.StepLoop.reserved.offset + 4
 
 
+def test_no_hip_file_includes_a_hip_file():
+    """Device code shared between translation units lives in headers (csrc/*_dev.h): no csrc/*.hip includes a .hip file, and the
+    AVHOT_DEVICE_ONLY fence that such an inclusion once needed appears nowhere under csrc/."""
+    import re
+    csrc = os.path.join(os.path.dirname(nat.LIB_PATH), "csrc")
+    names = sorted(n for n in os.listdir(csrc) if os.path.isfile(os.path.join(csrc, n)))
+    assert "step.hip" in names and "planner_dev.h" in names
+    for n in names:
+        text = open(os.path.join(csrc, n), errors="replace").read()
+        assert "AVHOT_DEVICE_ONLY" not in text, n
+        if n.endswith(".hip"):
+            assert not re.findall(r'^\s*#\s*include\s*["<][^">]*\.hip[">]', text, flags=re.M), n
+
+
 def test_lane_stage_bits_and_view_ids_match_header():
     import re
     hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "avhot.h")).read()

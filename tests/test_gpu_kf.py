@@ -1,4 +1,4 @@
-"""The Kalman stage (csrc/kf.hip, csrc/kf_dense.inc) through av_kf_step against oracle/kf_ref.py on the paths the other
+"""The Kalman stage (csrc/kf.hip, csrc/kf_dev.h, csrc/kf_dense.inc) through av_kf_step against oracle/kf_ref.py on the paths the other
 tests never feed: mode arrays in a window, standstill (the heading hold and its carries across 64-frame batches), the +-pi wrap,
 non-default settings, dt = 0, the steady loop left and re-entered, the register-form dense kernel over windows -- and the bit
 identities the kernel claims: every partition of a sequence into launches gives the same bytes, and the dense filter's register

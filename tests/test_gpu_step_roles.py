@@ -1,4 +1,4 @@
-"""The Kalman role of the one-launch time-step in two parts (csrc/kf.hip: kf_axis_chain1 before the counter store, kf_axis_tail1 on
+"""The Kalman role of the one-launch time-step in two parts (csrc/kf_dev.h: kf_axis_chain1 before the counter store, kf_axis_tail1 on
 a planner wave) and the planner's start state handed over in LDS: every output byte for byte against the stage launches
 (kf_axis_kernel + planner_kernel run kf_axis_body / plan_block unchanged), against the serial one-launch loop at depth 2, 3, 4, on the
 smallest grids and with eight waves launched serially.

@@ -60,7 +60,7 @@ def _shape(lib, n, C_, S, extra):
 def test_launch_shape_query(lib):
     """The thresholds of the plan (512 / 1024 / 4096 states; 48 KB for G > 1, 64 KB for G = 1), on both sides of each; the
     dynamic LDS of every shape the GPU tests use; what the query refuses."""
-    # LDS bytes worked out by hand from the layouts in planner.hip (plan_block_lists: [G][3][n][2] + even(9 G) + 8 G + 3 even(G C)
+    # LDS bytes worked out by hand from the layouts in planner_dev.h (plan_block_lists: [G][3][n][2] + even(9 G) + 8 G + 3 even(G C)
     # + [NW][6 n] doubles; the wave kernel: four waves of [2][3][n][2] + 512 + even(2 C) + 24 + 16 doubles)
     for extra in (0, 1):
         # n = 51 (<= 64: the wave kernel from 1024 states on), C = 21

@@ -21,8 +21,6 @@ FIELDS = (("VGPRs", "vgpr"), ("AGPRs", "agpr"), ("ScratchSize \\[bytes/lane\\]",
           ("LDS Size \\[bytes/block\\]", "lds"), ("VGPRs Spill", "spill"))
 print("%-12s %-78s %5s %5s %7s %5s %8s" % ("file", "kernel", "vgpr", "spill", "scratch", "w/SIMD", "staticLDS"))
 for f in files:
-    if os.path.basename(f) == "step.hip":           # includes the stage files: same device code, one extra kernel
-        pass
     r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"),
                         "-I", CSRC, "-c", f, "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
     cur, rows = None, {}

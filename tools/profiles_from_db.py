@@ -16,7 +16,8 @@ CSRC = os.path.join(REPO, "multimodal_autonomous_driving_perception_and_planning
 
 def stamp(kernel_file):
     """What bench.py needs to decide whether a counter value still describes the kernel it is printed next to: the commit the
-    profile was taken at and a hash of the kernel's source file (bench.py drops `traffic` to null when the file has changed)."""
+    profile was taken at and a hash of the file that holds the measured kernel's body -- the stage's *_dev.h where the kernel is a
+    thin wrapper of a device function, the .hip file otherwise (bench.py drops `traffic` to null when the file has changed)."""
     import hashlib
     import subprocess
     try:
@@ -116,7 +117,7 @@ for k in fe:
                                           "python3 tools/kbench.py --streams 64 --window 256 --stages plan --reps 2, MI355X, " + tag,
                    "states_per_launch": states, "WRITE_SIZE_KiB": wr[k]["WRITE_SIZE"], "FETCH_SIZE_KiB_raw": fe[k]["FETCH_SIZE"],
                    "fetch_correction": "x2 on gfx950 (MI355X_MICROARCH.md, HBM section)", "hbm_bytes_per_launch": int(f + w_),
-                   "hbm_bytes_per_state": round((f + w_) / states), "algorithmic_bytes_per_state": 51660, **stamp("planner.hip")},
+                   "hbm_bytes_per_state": round((f + w_) / states), "algorithmic_bytes_per_state": 51660, **stamp("planner_dev.h")},
                   open(os.path.join(dst, "planner_pmc.json"), "w"), indent=2)
 
 # ---- tracker (the headline step's longest kernel: latency-bound, its HBM traffic is reported for completeness) --------------------
@@ -129,7 +130,7 @@ for k in fe:
                                           "python3 tools/kbench.py --streams 64 --window 256 --stages detect,track --reps 2, MI355X, " + tag,
                    "frames_per_launch": frames, "WRITE_SIZE_KiB": wr[k]["WRITE_SIZE"], "FETCH_SIZE_KiB_raw": fe[k]["FETCH_SIZE"],
                    "fetch_correction": "x2 on gfx950 (MI355X_MICROARCH.md, HBM section)", "hbm_bytes_per_launch": int(f + w_),
-                   "hbm_bytes_per_frame": round((f + w_) / frames, 1), "algorithmic_bytes_per_frame": 4776, **stamp("tracker.hip")},
+                   "hbm_bytes_per_frame": round((f + w_) / frames, 1), "algorithmic_bytes_per_frame": 4776, **stamp("tracker_dev.h")},
                   open(os.path.join(dst, "tracker_pmc.json"), "w"), indent=2)
 
 # ---- the one-launch time-step (headline): HBM bytes per launch ------------------------------------------------------------------
