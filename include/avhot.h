@@ -698,6 +698,52 @@ typedef struct av_taglog_stats_row {
 } av_taglog_stats_row;              /* 584 bytes */
 int av_taglog_stats(av_ctx* ctx, av_stream_t stream, int n_streams, int cap, const uint64_t* log_mask, const double* log_speed,
                     const int32_t* log_n, void* workspace, av_taglog_stats_row* out);
+/* Per-frame records: the numbers of the taggers' rows that a mask cannot hold, kept beside mask and speed as a third log array
+ * log_cols av_taglog_cols [S][cap] (array of structs).  They fill the reference's `frames` table (src/database/tag_database.py)
+ * and answer numeric queries.  Every value is copied bit for bit from its row; nothing is computed. */
+typedef struct av_taglog_cols {
+    double road_type_confidence;                       /* av_scene_row.confidence; 0 without a scene row     */
+    double lateral_confidence, longitudinal_confidence, turning_confidence;   /* maneuver row; 0 without     */
+    double acceleration, yaw_rate_deg;                 /* maneuver row; 0 without                             */
+    double min_ttc, closest_distance;                  /* summary, bit for bit (NaN = None); NaN without one  */
+    int32_t agent_count, pedestrian_count, cyclist_count, vehicle_count;      /* summary; 0 without          */
+} av_taglog_cols;                                      /* 80 bytes */
+/* The records of n_streams x n_frames frames from the same three row arrays as av_tags_pack (each may be NULL).
+ *   out_cols  av_taglog_cols [S][W] */
+int av_tags_cols(av_ctx* ctx, av_stream_t stream, int n_streams, int n_frames, const av_maneuver_row* maneuver,
+                 const av_interaction_summary* inter_summary, const av_scene_row* scene, av_taglog_cols* out_cols);
+/* av_taglog_append with the records moved in the same launch to the same positions.  cols [S][W] and log_cols [S][cap] are both
+ * NULL (then it leaves exactly what av_taglog_append leaves) or both given. */
+int av_taglog_append_ex(av_ctx* ctx, av_stream_t stream, int n_streams, int n_frames, const uint64_t* mask, const double* speed,
+                        const av_taglog_cols* cols, int cap, uint64_t* log_mask, double* log_speed, av_taglog_cols* log_cols,
+                        int32_t* log_n, int32_t* dropped);
+/* A query over masks, speeds and records.  The mask part is that of av_taglog_search.  A NaN bound is unset and imposes nothing; a
+ * set bound is an inclusive comparison with the stored value, hence false where the stored value is NaN (a frame whose min_ttc is
+ * None never matches a ttc_max).  A count bound <= 0 imposes nothing. */
+typedef struct av_taglog_where {
+    uint64_t all, any, none;
+    double speed_min, speed_max;        /* log_speed                          */
+    double accel_min, accel_max;        /* av_taglog_cols.acceleration        */
+    double ttc_max, distance_max;       /* min_ttc, closest_distance          */
+    int32_t agents_min, pedestrians_min, cyclists_min, vehicles_min;
+} av_taglog_where;                      /* 88 bytes */
+/* av_taglog_search / av_taglog_segments with an av_taglog_where in place of the three masks: the same workspace, outputs and
+ * out_n contract.  log_speed is loaded only when a speed bound is set, a record's fields only when a bound on them is set;
+ * log_cols (or log_speed) may be NULL when no bound needs it, and is refused when one does. */
+int av_taglog_search_where(av_ctx* ctx, av_stream_t stream, int n_streams, int cap, const uint64_t* log_mask, const double* log_speed,
+                           const av_taglog_cols* log_cols, const int32_t* log_n, const av_taglog_where* where, int first, int last,
+                           void* workspace, int out_cap, int32_t* out_idx, int32_t* out_n);
+int av_taglog_segments_where(av_ctx* ctx, av_stream_t stream, int n_streams, int cap, const uint64_t* log_mask,
+                             const double* log_speed, const av_taglog_cols* log_cols, const int32_t* log_n,
+                             const av_taglog_where* where, int first, int last, int min_duration, void* workspace, int seg_cap,
+                             int32_t* out_seg, int32_t* out_n);
+/* The logged frames idx[s][i], i < min(idx_n[s], idx_cap), as out_mask u64 / out_speed f64 / out_cols av_taglog_cols [S][idx_cap];
+ * idx int32 [S][idx_cap] and idx_n [S] are what a search left (its out_n may exceed its out_cap, hence the clamp).  An index
+ * outside [0, log_n[s]) gives an all-zero record and is never read; rows at or past min(idx_n, idx_cap) are not written;
+ * out_cols is written only when log_cols is given. */
+int av_taglog_gather(av_ctx* ctx, av_stream_t stream, int n_streams, int cap, const uint64_t* log_mask, const double* log_speed,
+                     const av_taglog_cols* log_cols, const int32_t* log_n, const int32_t* idx, const int32_t* idx_n, int idx_cap,
+                     uint64_t* out_mask, double* out_speed, av_taglog_cols* out_cols);
 
 /* ---- rendering ----------------------------------------------------------------
  * Replaces the cv2 drawing behind BEVRenderer.render (src/visualization/bev_renderer.py:286-348 and its helpers

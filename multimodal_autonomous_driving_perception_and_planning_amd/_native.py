@@ -93,6 +93,18 @@ LANE_HOUGH_ONLY, LANE_FIT_ONLY, LANE_GIVEN_GRAY = 16, 32, 64
 TAGLOG_STATS_FIELDS = [("tag_count", "<i8", (64,)), ("n_frames", "<i8"), ("n_maneuver", "<i8"), ("risk_count", "<i8", (4,)),
                        ("speed_min", "<f8"), ("speed_max", "<f8"), ("speed_sum", "<f8")]
 TAGLOG_STATS_BYTES = 584
+TAGLOG_COLS_FIELDS = [("road_type_confidence", "<f8"), ("lateral_confidence", "<f8"), ("longitudinal_confidence", "<f8"),
+                      ("turning_confidence", "<f8"), ("acceleration", "<f8"), ("yaw_rate_deg", "<f8"), ("min_ttc", "<f8"),
+                      ("closest_distance", "<f8"), ("agent_count", "<i4"), ("pedestrian_count", "<i4"), ("cyclist_count", "<i4"),
+                      ("vehicle_count", "<i4")]
+TAGLOG_COLS_BYTES = 80
+
+
+class TaglogWhere(C.Structure):
+    """av_taglog_where (include/avhot.h): NaN = bound unset, a count bound <= 0 = none; 88 bytes."""
+    _fields_ = ([(k, C.c_uint64) for k in ("all", "any", "none")] +
+                [(k, C.c_double) for k in ("speed_min", "speed_max", "accel_min", "accel_max", "ttc_max", "distance_max")] +
+                [(k, C.c_int32) for k in ("agents_min", "pedestrians_min", "cyclists_min", "vehicles_min")])
 
 
 class BevCfg(C.Structure):
@@ -289,6 +301,13 @@ _SIGS = [
     ("av_taglog_segments", C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int,
                                      C.c_int, vp, C.c_int, vp, vp]),
     ("av_taglog_stats", C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    ("av_tags_cols", C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]),
+    ("av_taglog_append_ex", C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]),
+    ("av_taglog_search_where", C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, C.POINTER(TaglogWhere), C.c_int, C.c_int, vp,
+                                         C.c_int, vp, vp]),
+    ("av_taglog_segments_where", C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, C.POINTER(TaglogWhere), C.c_int, C.c_int,
+                                           C.c_int, vp, C.c_int, vp, vp]),
+    ("av_taglog_gather", C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp]),
 ]
 
 # entry points added by later translation units; bound when present in the header list below

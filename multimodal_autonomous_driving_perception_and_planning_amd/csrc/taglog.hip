@@ -22,9 +22,17 @@
 // The exclusive sums re-read the per-chunk words of all earlier chunks: (cap / 1024)^2 / 2 int32 loads per stream and query, 2 MB
 // out of L2 at 2^20 frames -- less than the masks; a log of 2^24 frames would want a scan launch instead.
 // No LDS except the stats fold, no atomics, every store a plain vector store.
+//
+// Records.  A log may carry a third array, av_taglog_cols [S][cap] (80 B, array of structs): the numbers of the taggers' rows that a
+// mask cannot hold.  av_tags_cols builds them (one lane per 8-byte word of a record, so the stores are contiguous; copies only),
+// av_taglog_append_ex moves them with the masks (a stream's window of records is one contiguous run of words), the *_where queries
+// replace pass 1 by a match over masks, speeds and records -- a bounded field costs one 8-byte load out of the frame's 80 B record,
+// under a wave-uniform branch, so an unbounded query still reads 8 B per frame -- and av_taglog_gather turns a search's indices
+// into records (one lane per output word).
 #include "common.h"
 
 #include <cmath>
+#include <cstddef>
 
 namespace {
 
@@ -172,6 +180,100 @@ __global__ void __launch_bounds__(256) taglog_append_kernel(int n_frames, const 
     }
 }
 
+// ---- records ---------------------------------------------------------------------------------------------------------------
+constexpr int COLS_WORDS = 10;              // av_taglog_cols in 8-byte words
+static_assert(sizeof(av_taglog_cols) == COLS_WORDS * 8, "av_taglog_cols layout");
+static_assert(sizeof(av_taglog_where) == 88, "av_taglog_where layout");
+static_assert(offsetof(av_taglog_cols, acceleration) == 32 && offsetof(av_taglog_cols, min_ttc) == 48 &&
+              offsetof(av_taglog_cols, closest_distance) == 56 && offsetof(av_taglog_cols, agent_count) == 64 &&
+              offsetof(av_taglog_cols, cyclist_count) == 72, "av_taglog_cols words");
+static_assert(offsetof(av_maneuver_row, lateral_confidence) == 16 && offsetof(av_maneuver_row, turning_confidence) == 32 &&
+              offsetof(av_maneuver_row, acceleration) == 48 && offsetof(av_maneuver_row, yaw_rate_deg) == 56 &&
+              sizeof(av_maneuver_row) == 72, "av_maneuver_row words");
+static_assert(offsetof(av_interaction_summary, agent_count) == 0 && offsetof(av_interaction_summary, cyclist_count) == 8 &&
+              offsetof(av_interaction_summary, closest_distance) == 32 && offsetof(av_interaction_summary, min_ttc) == 40 &&
+              sizeof(av_interaction_summary) == 56, "av_interaction_summary words");
+static_assert(offsetof(av_scene_row, confidence) % 8 == 0 && sizeof(av_scene_row) % 8 == 0, "av_scene_row words");
+constexpr unsigned long long NAN_BITS = 0x7ff8000000000000ull;
+constexpr int W_ACCEL = 4, W_TTC = 6, W_DIST = 7, W_AGENT_PED = 8, W_CYC_VEH = 9;      // words of a record the queries read
+
+// word -> word of the source row, in 8-byte words (the two count words are two int32 each, in the summary's order)
+__global__ void __launch_bounds__(256) tags_cols_kernel(long long n_words, const unsigned long long* __restrict__ maneuver,
+                                                        const unsigned long long* __restrict__ isum,
+                                                        const unsigned long long* __restrict__ scene,
+                                                        unsigned long long* __restrict__ out) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n_words) return;
+    const size_t f = (size_t)(t / COLS_WORDS);
+    const int w = (int)(t % COLS_WORDS);
+    unsigned long long v = 0ull;
+    if (w == 0) {
+        if (scene) v = scene[f * (sizeof(av_scene_row) / 8) + offsetof(av_scene_row, confidence) / 8];
+    } else if (w < 6) {                     // 1..3 the confidences (row words 2..4), 4..5 acceleration, yaw_rate_deg (6..7)
+        if (maneuver) v = maneuver[f * (sizeof(av_maneuver_row) / 8) + (w < 4 ? w + 1 : w + 2)];
+    } else if (w < 8) {                     // min_ttc (summary word 5), closest_distance (4)
+        v = isum ? isum[f * (sizeof(av_interaction_summary) / 8) + (w == W_TTC ? 5 : 4)] : NAN_BITS;
+    } else {                                // agent | pedestrian (word 0), cyclist | vehicle (word 1)
+        if (isum) v = isum[f * (sizeof(av_interaction_summary) / 8) + (w - 8)];
+    }
+    out[t] = v;
+}
+
+// av_taglog_append's kernel with the records: a stream's `fit` records are fit * 10 consecutive words on both sides.
+__global__ void __launch_bounds__(256) taglog_append_ex_kernel(int n_frames, const unsigned long long* __restrict__ mask,
+                                                               const double* __restrict__ speed,
+                                                               const unsigned long long* __restrict__ cols, int cap,
+                                                               unsigned long long* __restrict__ log_mask,
+                                                               double* __restrict__ log_speed, unsigned long long* __restrict__ log_cols,
+                                                               int32_t* __restrict__ log_n, int32_t* __restrict__ dropped) {
+    const size_t s = blockIdx.x;
+    int n0 = log_n[s];
+    n0 = n0 < 0 ? 0 : (n0 > cap ? cap : n0);
+    __syncthreads();                            // every thread has read log_n[s] before thread 0 advances it
+    const int fit = n_frames < cap - n0 ? n_frames : cap - n0;
+    for (int w = threadIdx.x; w < fit; w += blockDim.x) {                          // n0 + w < n0 + fit <= cap
+        log_mask[s * (size_t)cap + n0 + w] = mask[s * (size_t)n_frames + w];
+        log_speed[s * (size_t)cap + n0 + w] = speed[s * (size_t)n_frames + w];
+    }
+    if (cols) {
+        const unsigned long long* src = cols + s * (size_t)n_frames * COLS_WORDS;
+        unsigned long long* dst = log_cols + (s * (size_t)cap + (size_t)n0) * COLS_WORDS;
+        const long long words = (long long)fit * COLS_WORDS;                       // (n0 + fit) * 10 <= cap * 10 words of the row
+        for (long long j = threadIdx.x; j < words; j += blockDim.x) dst[j] = src[j];
+    }
+    if (threadIdx.x == 0) {
+        log_n[s] = n0 + fit;
+        dropped[s] += n_frames - fit;
+    }
+}
+
+// One lane per output word of a gathered row: word 0 the mask, 1 the speed, 2..11 the record.
+constexpr int GATHER_WORDS = 2 + COLS_WORDS;
+__global__ void __launch_bounds__(256) taglog_gather_kernel(int cap, const unsigned long long* __restrict__ log_mask,
+                                                            const unsigned long long* __restrict__ log_speed,
+                                                            const unsigned long long* __restrict__ log_cols,
+                                                            const int32_t* __restrict__ log_n, const int32_t* __restrict__ idx,
+                                                            const int32_t* __restrict__ idx_n, int idx_cap,
+                                                            unsigned long long* __restrict__ out_mask,
+                                                            unsigned long long* __restrict__ out_speed,
+                                                            unsigned long long* __restrict__ out_cols) {
+    const size_t s = blockIdx.y;
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long row = t / GATHER_WORDS;
+    const int w = (int)(t % GATHER_WORDS);
+    int rows = idx_n[s];
+    rows = rows < 0 ? 0 : (rows > idx_cap ? idx_cap : rows);
+    if (row >= rows || (w >= 2 && !log_cols)) return;                              // row < rows <= idx_cap
+    int n = log_n[s];
+    n = n < 0 ? 0 : (n > cap ? cap : n);
+    const int f = idx[s * (size_t)idx_cap + (size_t)row];
+    const bool in = f >= 0 && f < n;                                               // f < n <= cap: inside the stream's row
+    const size_t src = s * (size_t)cap + (size_t)(in ? f : 0), dst = s * (size_t)idx_cap + (size_t)row;
+    if (w == 0) out_mask[dst] = in ? log_mask[src] : 0ull;
+    else if (w == 1) out_speed[dst] = in ? log_speed[src] : 0ull;
+    else out_cols[dst * COLS_WORDS + (w - 2)] = in ? log_cols[src * COLS_WORDS + (w - 2)] : 0ull;
+}
+
 // ---- queries: the wave's chunk ---------------------------------------------------------------------------------------------
 struct ChunkId {
     int lane, c, nc;
@@ -212,6 +314,88 @@ __global__ void __launch_bounds__(256) taglog_match_kernel(int cap, const unsign
         for (int r = 0; r < ROUNDS; ++r) {
             const int i = base + r * 64 + k.lane;
             const unsigned long long on = __ballot(i >= lo && i < hi && matches(m[r], p));
+            if (k.lane == r) mine = on;
+            count += __popcll(on);
+            if (~on != 0ull) lastoff = base + r * 64 + 63 - __clzll(~on);
+        }
+    } else {
+        lastoff = base + CHUNK - 1;
+    }
+    if (k.lane < ROUNDS) ws.bits[k.sc * ROUNDS + k.lane] = mine;
+    if (k.lane == 0) ws.cnt[k.sc] = count, ws.lastoff[k.sc] = lastoff;
+}
+
+// Pass 1 of the *_where queries: taglog_match_kernel's bits / cnt / lastoff from masks, speeds and records.  Which arrays are read is
+// decided by the bounds that are set -- kernel arguments, so every such branch is wave-uniform.
+struct WhereUse {
+    bool speed, accel, ttc, dist, agent_ped, cyc_veh;
+};
+__host__ __device__ inline bool is_set(double bound) { return bound == bound; }
+__host__ __device__ inline WhereUse where_use(const av_taglog_where& q) {
+    WhereUse u;
+    u.speed = is_set(q.speed_min) || is_set(q.speed_max);
+    u.accel = is_set(q.accel_min) || is_set(q.accel_max);
+    u.ttc = is_set(q.ttc_max);
+    u.dist = is_set(q.distance_max);
+    u.agent_ped = q.agents_min > 0 || q.pedestrians_min > 0;
+    u.cyc_veh = q.cyclists_min > 0 || q.vehicles_min > 0;
+    return u;
+}
+// an unset (NaN) bound imposes nothing; a set one is false against a stored NaN
+__device__ __forceinline__ bool at_least(double v, double bound) { return !is_set(bound) || v >= bound; }
+__device__ __forceinline__ bool at_most(double v, double bound) { return !is_set(bound) || v <= bound; }
+__device__ __forceinline__ bool count_at_least(int v, int bound) { return bound <= 0 || v >= bound; }
+
+__global__ void __launch_bounds__(256) taglog_match_where_kernel(int cap, const unsigned long long* __restrict__ log_mask,
+                                                                 const double* __restrict__ log_speed,
+                                                                 const unsigned long long* __restrict__ log_cols,
+                                                                 const int32_t* __restrict__ log_n, av_taglog_where q, int first,
+                                                                 int last, Workspace ws) {
+    const ChunkId k = my_chunk(cap);
+    if (!k.live) return;
+    int n = log_n[k.s];
+    n = n < 0 ? 0 : (n > cap ? cap : n);
+    const int lo = first < 0 ? 0 : first, hi = last < n ? last : n;
+    const int base = k.c * CHUNK;
+    const Predicate p{q.all, q.any, q.none};
+    const WhereUse use = where_use(q);
+    const unsigned long long* row = log_mask + k.s * (size_t)cap;
+    const double* vrow = log_speed + k.s * (size_t)cap;
+    const unsigned long long* crow = log_cols + k.s * (size_t)cap * COLS_WORDS;
+    unsigned long long mine = 0;                // lane r keeps round r's ballot
+    int count = 0, lastoff = -1;
+    if (base < hi && base + CHUNK > lo) {       // otherwise nothing of this chunk is in range: all bits off, no load
+        unsigned long long m[ROUNDS];           // the masks first, as taglog_match_kernel reads them: 16 loads in flight
+#pragma unroll
+        for (int r = 0; r < ROUNDS; ++r) {
+            const int i = base + r * 64 + k.lane;
+            m[r] = (i >= lo && i < hi) ? row[i] : 0ull;                            // i < hi <= n <= cap
+        }
+#pragma unroll
+        for (int r = 0; r < ROUNDS; ++r) {
+            const int i = base + r * 64 + k.lane;
+            const bool in = i >= lo && i < hi;                                     // every load below: i < hi <= n <= cap
+            bool ok = in && matches(m[r], p);
+            const unsigned long long* rec = crow + (size_t)(in ? i : 0) * COLS_WORDS;      // read under `in` only
+            if (use.speed) {
+                const double v = in ? vrow[i] : 0.0;
+                ok = ok && at_least(v, q.speed_min) && at_most(v, q.speed_max);
+            }
+            if (use.accel) {
+                const double v = __longlong_as_double((long long)(in ? rec[W_ACCEL] : 0ull));
+                ok = ok && at_least(v, q.accel_min) && at_most(v, q.accel_max);
+            }
+            if (use.ttc) ok = ok && at_most(__longlong_as_double((long long)(in ? rec[W_TTC] : 0ull)), q.ttc_max);
+            if (use.dist) ok = ok && at_most(__longlong_as_double((long long)(in ? rec[W_DIST] : 0ull)), q.distance_max);
+            if (use.agent_ped) {
+                const unsigned long long v = in ? rec[W_AGENT_PED] : 0ull;
+                ok = ok && count_at_least((int)(unsigned)v, q.agents_min) && count_at_least((int)(unsigned)(v >> 32), q.pedestrians_min);
+            }
+            if (use.cyc_veh) {
+                const unsigned long long v = in ? rec[W_CYC_VEH] : 0ull;
+                ok = ok && count_at_least((int)(unsigned)v, q.cyclists_min) && count_at_least((int)(unsigned)(v >> 32), q.vehicles_min);
+            }
+            const unsigned long long on = __ballot(ok);
             if (k.lane == r) mine = on;
             count += __popcll(on);
             if (~on != 0ull) lastoff = base + r * 64 + 63 - __clzll(~on);
@@ -478,6 +662,105 @@ extern "C" int av_taglog_stats(av_ctx* ctx, av_stream_t stream, int n_streams, i
                        reinterpret_cast<const unsigned long long*>(log_mask), log_speed, log_n, ws);
     AV_LAUNCH_CHECK();
     hipLaunchKernelGGL(taglog_stats_fold_kernel, dim3((unsigned)n_streams), dim3(FOLD_WAVES * 64), 0, as_stream(stream), cap, ws, out);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
+// ---- records: host ---------------------------------------------------------------------------------------------------------
+namespace {
+inline const unsigned long long* words(const void* p) { return reinterpret_cast<const unsigned long long*>(p); }
+inline unsigned long long* words(void* p) { return reinterpret_cast<unsigned long long*>(p); }
+}  // namespace
+
+extern "C" int av_tags_cols(av_ctx* ctx, av_stream_t stream, int n_streams, int n_frames, const av_maneuver_row* maneuver,
+                            const av_interaction_summary* inter_summary, const av_scene_row* scene, av_taglog_cols* out_cols) {
+    AV_REQUIRE(ctx && out_cols, AV_EINVAL, "av_tags_cols: null argument");
+    AV_REQUIRE(n_streams > 0 && n_frames > 0, AV_EINVAL, "av_tags_cols: n_streams and n_frames must be > 0");
+    const long long frames = (long long)n_streams * n_frames;
+    AV_REQUIRE(frames <= 0x7fffffffll / COLS_WORDS, AV_EINVAL, "av_tags_cols: n_streams * n_frames * 10 does not fit an int");
+    const long long n_words = frames * COLS_WORDS;
+    hipLaunchKernelGGL(tags_cols_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, as_stream(stream), n_words,
+                       words(maneuver), words(inter_summary), words(scene), words(out_cols));
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
+extern "C" int av_taglog_append_ex(av_ctx* ctx, av_stream_t stream, int n_streams, int n_frames, const uint64_t* mask,
+                                   const double* speed, const av_taglog_cols* cols, int cap, uint64_t* log_mask, double* log_speed,
+                                   av_taglog_cols* log_cols, int32_t* log_n, int32_t* dropped) {
+    AV_REQUIRE(ctx && mask && speed && log_mask && log_speed && log_n && dropped, AV_EINVAL, "av_taglog_append_ex: null argument");
+    AV_REQUIRE((cols == nullptr) == (log_cols == nullptr), AV_EINVAL,
+               "av_taglog_append_ex: cols and log_cols are given together or not at all");
+    AV_REQUIRE(n_streams > 0 && n_frames > 0 && cap > 0, AV_EINVAL, "av_taglog_append_ex: n_streams, n_frames and cap must be > 0");
+    hipLaunchKernelGGL(taglog_append_ex_kernel, dim3((unsigned)n_streams), dim3(256), 0, as_stream(stream), n_frames, words(mask),
+                       speed, words(cols), cap, words(log_mask), log_speed, words(log_cols), log_n, dropped);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
+namespace {
+// what both *_where queries check and launch first; 0 or the error code
+int launch_match_where(const char* who, av_ctx* ctx, av_stream_t stream, int n_streams, int cap, const uint64_t* log_mask,
+                       const double* log_speed, const av_taglog_cols* log_cols, const int32_t* log_n, const av_taglog_where* where,
+                       int first, int last, void* workspace, int out_cap, const void* out, const int32_t* out_n) {
+    AV_REQUIRE(ctx && log_mask && log_n && where && workspace && out_n && (out || out_cap == 0), AV_EINVAL, "%s: null argument", who);
+    AV_REQUIRE(n_streams > 0 && cap > 0, AV_EINVAL, "%s: n_streams and cap must be > 0", who);
+    AV_REQUIRE(out_cap >= 0, AV_EINVAL, "%s: the output capacity %d is negative", who, out_cap);
+    const WhereUse use = where_use(*where);
+    AV_REQUIRE(log_speed || !use.speed, AV_EINVAL, "%s: a speed bound without log_speed", who);
+    AV_REQUIRE(log_cols || !(use.accel || use.ttc || use.dist || use.agent_ped || use.cyc_veh), AV_EINVAL,
+               "%s: a bound on a record's field without log_cols", who);
+    hipLaunchKernelGGL(taglog_match_where_kernel, chunk_grid(n_streams, cap), dim3(256), 0, as_stream(stream), cap, words(log_mask),
+                       log_speed, words(log_cols), log_n, *where, first, last, carve(workspace, n_streams, cap));
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+}  // namespace
+
+extern "C" int av_taglog_search_where(av_ctx* ctx, av_stream_t stream, int n_streams, int cap, const uint64_t* log_mask,
+                                      const double* log_speed, const av_taglog_cols* log_cols, const int32_t* log_n,
+                                      const av_taglog_where* where, int first, int last, void* workspace, int out_cap,
+                                      int32_t* out_idx, int32_t* out_n) {
+    const int rc = launch_match_where("av_taglog_search_where", ctx, stream, n_streams, cap, log_mask, log_speed, log_cols, log_n, where,
+                                      first, last, workspace, out_cap, out_idx, out_n);
+    if (rc != AV_OK) return rc;
+    hipLaunchKernelGGL(taglog_search_write_kernel, chunk_grid(n_streams, cap), dim3(256), 0, as_stream(stream), cap,
+                       carve(workspace, n_streams, cap), out_cap, out_idx, out_n);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
+extern "C" int av_taglog_segments_where(av_ctx* ctx, av_stream_t stream, int n_streams, int cap, const uint64_t* log_mask,
+                                        const double* log_speed, const av_taglog_cols* log_cols, const int32_t* log_n,
+                                        const av_taglog_where* where, int first, int last, int min_duration, void* workspace,
+                                        int seg_cap, int32_t* out_seg, int32_t* out_n) {
+    const int rc = launch_match_where("av_taglog_segments_where", ctx, stream, n_streams, cap, log_mask, log_speed, log_cols, log_n,
+                                      where, first, last, workspace, seg_cap, out_seg, out_n);
+    if (rc != AV_OK) return rc;
+    const Workspace ws = carve(workspace, n_streams, cap);
+    const dim3 grid = chunk_grid(n_streams, cap);
+    hipLaunchKernelGGL(taglog_segments_kernel<false>, grid, dim3(256), 0, as_stream(stream), cap, ws, min_duration, seg_cap, out_seg,
+                       out_n);
+    AV_LAUNCH_CHECK();
+    hipLaunchKernelGGL(taglog_segments_kernel<true>, grid, dim3(256), 0, as_stream(stream), cap, ws, min_duration, seg_cap, out_seg,
+                       out_n);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
+extern "C" int av_taglog_gather(av_ctx* ctx, av_stream_t stream, int n_streams, int cap, const uint64_t* log_mask,
+                                const double* log_speed, const av_taglog_cols* log_cols, const int32_t* log_n, const int32_t* idx,
+                                const int32_t* idx_n, int idx_cap, uint64_t* out_mask, double* out_speed, av_taglog_cols* out_cols) {
+    AV_REQUIRE(ctx && log_mask && log_speed && log_n && idx_n && out_mask && out_speed, AV_EINVAL, "av_taglog_gather: null argument");
+    AV_REQUIRE(!log_cols || out_cols, AV_EINVAL, "av_taglog_gather: log_cols without out_cols");
+    AV_REQUIRE(n_streams > 0 && cap > 0, AV_EINVAL, "av_taglog_gather: n_streams and cap must be > 0");
+    AV_REQUIRE(idx_cap >= 0 && idx_cap <= 0x7fffffff / GATHER_WORDS, AV_EINVAL, "av_taglog_gather: idx_cap %d out of range", idx_cap);
+    AV_REQUIRE(idx || idx_cap == 0, AV_EINVAL, "av_taglog_gather: null argument");
+    if (idx_cap == 0) return AV_OK;
+    const long long threads = (long long)idx_cap * GATHER_WORDS;
+    hipLaunchKernelGGL(taglog_gather_kernel, dim3((unsigned)((threads + 255) / 256), (unsigned)n_streams), dim3(256), 0,
+                       as_stream(stream), cap, words(log_mask), words(log_speed), words(log_cols), log_n, idx, idx_n, idx_cap,
+                       words(out_mask), words(out_speed), words(out_cols));
     AV_LAUNCH_CHECK();
     return AV_OK;
 }

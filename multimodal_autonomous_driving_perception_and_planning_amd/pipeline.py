@@ -288,11 +288,12 @@ class HotLoop:
                                                nat.ptr(self.snap), nat.ptr(self.snap_n), nat.ptr(self.vstate), None, None,
                                                nat.ptr(self.inter_state), nat.ptr(self.inter_rows), nat.ptr(self.inter_summary)))
 
-    def enable_tag_log(self, capacity):
-        """A device-resident tag log of `capacity` frames per stream (tagging.tag_log.TagLog, self.tag_log) for enqueue_tags."""
+    def enable_tag_log(self, capacity, columns=False):
+        """A device-resident tag log of `capacity` frames per stream (tagging.tag_log.TagLog, self.tag_log) for enqueue_tags;
+        columns=True: with the per-frame records (TagLog(columns=True))."""
         self._serial_only("enable_tag_log")
         from .tagging.tag_log import TagLog
-        self.tag_log = TagLog(self.S, capacity, device=self.dev.index, ctx=self.ctx, stream=self.stream)
+        self.tag_log = TagLog(self.S, capacity, device=self.dev.index, ctx=self.ctx, stream=self.stream, columns=columns)
         return self.tag_log
 
     def enqueue_tags(self, stream=None, scene_rows=None, det=None, elem_table=None):
@@ -978,7 +979,7 @@ class CameraLoop:
 
     def __init__(self, n_streams, h=720, w=1280, model="random:0", precision="fp16", dcap=64, obstacles="moving_tracks",
                  class_map="reference", device=0, tracker_kw=None, kf_kw=None, planner_kw=None, obstacle_kw=None, tags=None,
-                 tag_capacity=4096, view=None):
+                 tag_capacity=4096, view=None, tag_columns=False):
         """class_map: "reference" (the detector's class names -> the reference's eight ids, everything else skipped:
         reference_class_map), None (raw ids) or an explicit int table.  obstacle_kw: HotLoop's; the defaults stretch the BEV
         panel's 640 x 500 px convention to the frame (x_center = w / 2, x_scale = 0.03 * 640 / w, y_far = 50,
@@ -988,6 +989,7 @@ class CameraLoop:
         interaction tagger (class_map="reference" only: it needs the reference's class ids) and enqueue_tags; "all" runs the scene
         stage ahead of them (cam.enqueue_scene with the Kalman speed, read on the device) and adds its tags and the detector's
         traffic elements.  The scene stage is the expensive one, hence not the default of `tags`.
+        tag_columns: the tag log also keeps the per-frame records (TagLog(columns=True)).
         view: None, "camera" or "demo" -- every step() also renders the frame it processed, behind the hot half on the hot stream
         (enqueue_view): "camera" leaves self.view_cam (uint8 [S, h, w, 3]: the frames with detections, lane area, tracks,
         info panel and detection summary as demo.py:124-136 draws them), "demo" leaves self.view (uint8 [S, th, tw, 3]: that picture
@@ -1018,7 +1020,7 @@ class CameraLoop:
         if tags is not None:
             from .perception.detector import ObjectDetector
             from .tagging.tag_log import element_table
-            self.tag_log = self.hot.enable_tag_log(tag_capacity)
+            self.tag_log = self.hot.enable_tag_log(tag_capacity, columns=tag_columns)
             self._tag_interactions = isinstance(class_map, np.ndarray) and np.array_equal(class_map, reference_class_map(c.yolo.names))
             self._tag_classes = [ObjectDetector.CLASSES[k] for k in range(8)]
             self._elem_table = torch.as_tensor(element_table(c.yolo.names)).to(self.hot.dev) if tags == "all" else None
