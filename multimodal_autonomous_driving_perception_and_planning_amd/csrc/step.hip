@@ -112,30 +112,35 @@ struct StepClock {                    // debug only: 100-MHz clock stamps of a r
     }
 };
 
-__device__ __forceinline__ bool seq_enter(const StepArgs& a, int slot, int* go) {
-    if (threadIdx.x == 0) {
-        int ok = 0;
-        // (locals: with the arguments read through `a` inside the loop the compiler reloads them from the kernel-argument segment on
-        // every poll, a scalar-cache round trip in front of each device-scope load)
-        int* const counter = a.flags + 32 * slot;
-        int* const fault = a.flags + flag_fault(a.S);
-        const int want = a.seq, spin = a.spin;
-        for (int n = 0; n <= spin; ++n) {
-            // (step numbers are 32-bit and wrap -- three hours of stepping at this rate -- so "has reached" is a signed distance)
-            if ((int)((unsigned)__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - (unsigned)want) >= 0) { ok = 1; break; }
-            // (once any wait has run out the chain is broken for good: the launches behind it give up at once instead of one timeout each)
-            if ((n & 255) == 255 && __hip_atomic_load(fault, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;
-        }
-        if (!ok) atomicOr(a.flags + flag_fault(a.S), 1);
-        if (ok && (a.fence & 8) && a.seq != 0) {      // debug: publisher's clock at its counter store -> this poll's return
-            const unsigned long long tp = __hip_atomic_load(reinterpret_cast<unsigned long long*>(a.flags + 32 * slot + 2), __ATOMIC_RELAXED,
-                                                            __HIP_MEMORY_SCOPE_AGENT);
-            const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-            unsigned long long* acc = reinterpret_cast<unsigned long long*>(a.flags + flag_stats(a.S)) + (slot & 1) * 16;
-            if (now > tp) atomicAdd(acc + 8, now - tp), atomicAdd(acc + 9, 1ull);
-        }
-        *go = ok;
+// The poll of one role of one stream, by ONE thread: true when the predecessor's counter has reached this step's number, false
+// (fault word set) when the wait ran out or another wait had.
+__device__ __forceinline__ int seq_poll(const StepArgs& a, int slot) {
+    int ok = 0;
+    // (locals: with the arguments read through `a` inside the loop the compiler reloads them from the kernel-argument segment on
+    // every poll, a scalar-cache round trip in front of each device-scope load)
+    int* const counter = a.flags + 32 * slot;
+    int* const fault = a.flags + flag_fault(a.S);
+    const int want = a.seq, spin = a.spin;
+    for (int n = 0; n <= spin; ++n) {
+        // (step numbers are 32-bit and wrap -- three hours of stepping at this rate -- so "has reached" is a signed distance)
+        if ((int)((unsigned)__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - (unsigned)want) >= 0) { ok = 1; break; }
+        // (once any wait has run out the chain is broken for good: the launches behind it give up at once instead of one timeout each)
+        if ((n & 255) == 255 && __hip_atomic_load(fault, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;
     }
+    if (!ok) atomicOr(a.flags + flag_fault(a.S), 1);
+    if (ok && (a.fence & 8) && a.seq != 0) {      // debug: publisher's clock at its counter store -> this poll's return
+        const unsigned long long tp = __hip_atomic_load(reinterpret_cast<unsigned long long*>(a.flags + 32 * slot + 2), __ATOMIC_RELAXED,
+                                                        __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+        unsigned long long* acc = reinterpret_cast<unsigned long long*>(a.flags + flag_stats(a.S)) + (slot & 1) * 16;
+        if (now > tp) atomicAdd(acc + 8, now - tp), atomicAdd(acc + 9, 1ull);
+    }
+    return ok;
+}
+// The tracker role's wait: thread 0 polls, the waves that fetch the record are others, so all of them meet at a workgroup barrier
+// between the poll and their loads.
+__device__ __forceinline__ bool seq_enter(const StepArgs& a, int slot, int* go) {
+    if (threadIdx.x == 0) *go = seq_poll(a, slot);
     __syncthreads();                  // (also keeps the compiler from moving any load of the role above the poll)
     if (!*go) return false;
     if (a.fence & 1) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // debug: the form the comment above prices
@@ -149,15 +154,30 @@ __device__ __forceinline__ void seq_leave(const StepArgs& a, int slot) {
                            __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(a.flags + 32 * slot, (int)((unsigned)a.seq + 1u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// n8 8-byte words of a stream's record into LDS, by the first `nthreads` threads of the workgroup.  coherent: device-scope loads (the
-// record was written by the previous step, possibly on another XCD).
-__device__ __forceinline__ void fetch_record(const void* src, void* dst_lds, int n8, int first, int end, bool coherent) {
-    unsigned long long* g = const_cast<unsigned long long*>(reinterpret_cast<const unsigned long long*>(src));
+// The persistent records as the roles address them: explicitly in the global address space.  A pointer that has been pinned in
+// registers (below) no longer tells the compiler where it points, and a load or store through it would be a flat_ instruction; the
+// hand-over's loads and stores are global_ ones.
+typedef __attribute__((address_space(1))) unsigned long long gu64;
+typedef __attribute__((address_space(1))) int32_t gi32;
+
+// n8 8-byte words of a stream's record into LDS, by the `nthreads` threads of the workgroup from thread `first` on, at most two words
+// per thread (n8 <= 2 nthreads: hot_step_prepare admits tcap 64 only).  Both loads of a thread are issued before its first wait --
+// one round trip to memory, not two -- hence straight-line code, no loop, and the kind of load a template argument, not a branch
+// beside each load.  COHERENT: device-scope loads (the record was written by the previous step, possibly on another XCD).
+template <bool COHERENT>
+__device__ __forceinline__ void fetch_record(gu64* g, void* dst_lds, int n8, int first, int nthreads) {
     unsigned long long* l = reinterpret_cast<unsigned long long*>(dst_lds);
-    if ((int)threadIdx.x < first || (int)threadIdx.x >= end) return;
-    for (int i = (int)threadIdx.x - first; i < n8; i += end - first)
-        l[i] = coherent ? __hip_atomic_load(g + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : g[i];
+    const int i = (int)threadIdx.x - first, j = i + nthreads;
+    if (i < 0 || i >= nthreads) return;
+    const bool p0 = i < n8, p1 = j < n8;
+    unsigned long long v0 = 0, v1 = 0;
+    if (p0) v0 = COHERENT ? __hip_atomic_load(g + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : g[i];
+    if (p1) v1 = COHERENT ? __hip_atomic_load(g + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : g[j];
+    if (p0) l[i] = v0;
+    if (p1) l[j] = v1;
 }
+static_assert((HDR_INTS * 4 + 64 * (int)sizeof(av_track_row)) / 8 <= 2 * (STEP_NW * 64 - 64) && AV_KF_STATE_DOUBLES <= 64,
+              "fetch_record: two words per thread cover the tracker's record (tcap 64), one the filter's");
 
 // The kernel's arguments as a ROLE reads them: from the kernel-argument segment (StepArgs is the kernel's only parameter, at its
 // offset 0), through a pointer the compiler cannot trace back to the parameter.  Read from the parameter, all ~130 scalar registers
@@ -210,20 +230,29 @@ __device__ __forceinline__ void hot_step_body(const StepArgs& a0) {
                 d_area[i] = (double)(d_box[4 * i + 2] - d_box[4 * i]) * (double)(d_box[4 * i + 3] - d_box[4 * i + 1]);
         }
         ck.mark(0);                   // detections made
+        // What the role needs right behind its wait is worked out in front of it, and pinned there: none of it depends on the
+        // predecessor, and left to the compiler the kernel-argument loads and the address arithmetic sit between the poll's barrier
+        // and the first record load, on the stream's chain.
+        int stage_off = a.stage_off, n8 = (HDR_INTS * 4 + a.tcap * (int)sizeof(av_track_row)) / 8;
+        gu64* rec = (gu64*)(a.trk_state + (size_t)s * state_bytes(a.tcap, a.tcfg.trajectory_length));
+        gi32* fcp = (gi32*)(a.frame_count + s);
+        asm volatile("" : "+s"(stage_off), "+s"(n8), "+s"(rec), "+s"(fcp));
         if (seq && !seq_enter(a, 2 * s, &go)) return;
         ck.mark(1);                   // waited for the predecessor
-        unsigned char* stage = smem + a.stage_off;
+        unsigned char* stage = smem + stage_off;
         int fc0 = 0;
-        if (seq && tid == 0) fc0 = __hip_atomic_load(a.frame_count + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // (in flight with the table)
+        if (seq && tid == 0) fc0 = __hip_atomic_load(fcp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // (in flight with the table)
         // (by the waves thread 0 is not in: launched serially, the record comes in while thread 0 still makes the detections)
-        fetch_record(a.trk_state + (size_t)s * state_bytes(a.tcap, a.tcfg.trajectory_length), stage,
-                     (HDR_INTS * 4 + a.tcap * (int)sizeof(av_track_row)) / 8, 64, STEP_NW * 64, seq);
+        if (seq)
+            fetch_record<true>(rec, stage, n8, 64, STEP_NW * 64 - 64);
+        else
+            fetch_record<false>(rec, stage, n8, 64, STEP_NW * 64 - 64);
         if (tid == 0) {
             if (seq) {
                 if (fc0 != fc_before) atomicOr(a.flags + flag_fault(a.S), 2);
-                __hip_atomic_store(a.frame_count + s, fc_stage, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(fcp, fc_stage, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             } else {
-                a.frame_count[s] = fc_stage;
+                *fcp = fc_stage;
             }
         }
         if (seq) __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): thread 0's frame-counter store is acknowledged before any wave passes the barrier
@@ -254,42 +283,72 @@ __device__ __forceinline__ void hot_step_body(const StepArgs& a0) {
     } else {
         const StepArgs& a = role_args();
         const int s = blockIdx.x - a.S;
+        size_t s64 = (size_t)s;       // (pinned as a scalar value: the compiler otherwise widens s inside the branch below, per lane)
+        asm volatile("" : "+s"(s64));
         StepClock ck{a, 1, &ck_t};
         ck.start();
-        if (tid < 4) z_stage[tid] = a.z[(size_t)s * 4 + tid];
-        if (seq && !seq_enter(a, 2 * s + 1, &go)) return;
-        ck.mark(1);
+        if (tid < 4) z_stage[tid] = a.z[s64 * 4 + tid];
         // The Kalman wave does only what the NEXT STEP waits for before it publishes (kf_axis_chain1: the record and the planner's
         // start state, left in LDS); the rest of the frame's Kalman output (kf_axis_tail1) is made later by a planner wave with slack.
-        double *vs = a.vstate + (size_t)s * AV_VSTATE_DOUBLES, *ps = a.plan_state + (size_t)s * 4;
+        // What it needs behind its wait -- addresses and filter settings, none of which the predecessor writes -- is in registers
+        // before it (pinned: the compiler otherwise loads them from the kernel-argument segment behind the poll, on the chain).
+        // (the arrays' bases, not the stream's addresses: the compiler adds a shifted index on the vector unit, which does not pin)
+        gu64* rec = (gu64*)a.kf_state;
+        long long kbits[3];           // (the settings as bit patterns: a double does not pin to scalar registers either)
+        static_assert(sizeof(kbits) == sizeof(av_kf_cfg), "av_kf_cfg is three doubles");
+        __builtin_memcpy(kbits, &a.kcfg, sizeof(kbits));
+        asm volatile("" : "+s"(rec), "+s"(kbits[0]), "+s"(kbits[1]), "+s"(kbits[2]));
+        rec += s64 * AV_KF_STATE_DOUBLES;
+        // (the output addresses are worked out where they are used, on the rare dense path and in the tail: kept from here they are
+        // four more registers through the chain, which has none to spare)
+        auto vs = [&] { return a.vstate + s64 * AV_VSTATE_DOUBLES; };
+        auto ps = [&] { return a.plan_state + s64 * 4; };
+        av_kf_cfg kc;
+        __builtin_memcpy(&kc, kbits, sizeof(kc));
+        // The wave that polls is the wave that fetches the record: it goes from its matched poll straight to its loads, without a
+        // workgroup barrier in between (the wavefront-scope fence is no instruction; it keeps the compiler from moving the loads up).
+        // The other waves learn `go` at the barrier that releases the planner.
         if (tid < 64) {
-            double* rec = a.kf_state + (size_t)s * AV_KF_STATE_DOUBLES;
-            fetch_record(rec, kf_stage, AV_KF_STATE_DOUBLES, 0, 64, seq);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-            ck.mark(2);
-            const bool separable = kf_axis_chain1(a.kcfg, z_stage, kf_stage, kf_start, kf_carry, tid);
-            if (tid == 0) {
-                kf_tail = separable;
-                if (!separable) {     // (LDS form: kf_dense.inc; its plan_state goes to LDS for the planner and from there to its output)
-                    kf_dense_stream_lds(a.kcfg, 0, 1, z_stage, nullptr, kf_stage, vs, kf_start);
-                    *reinterpret_cast<double4*>(ps) = *reinterpret_cast<const double4*>(kf_start);
-                }
+            int ok = 1;
+            if (seq) {
+                if (tid == 0) go = ok = seq_poll(a, 2 * s + 1);
+                ok = __builtin_amdgcn_readfirstlane(ok);
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                if (ok && (a.fence & 1)) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // debug, as in seq_enter
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-            if (tid < AV_KF_STATE_DOUBLES) {
+            if (ok) {
+                ck.mark(1);
                 if (seq)
-                    __hip_atomic_store(reinterpret_cast<unsigned long long*>(rec) + tid, (unsigned long long)__double_as_longlong(kf_stage[tid]),
-                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    fetch_record<true>(rec, kf_stage, AV_KF_STATE_DOUBLES, 0, 64);
                 else
-                    rec[tid] = kf_stage[tid];
+                    fetch_record<false>(rec, kf_stage, AV_KF_STATE_DOUBLES, 0, 64);
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+                ck.mark(2);
+                const bool separable = kf_axis_chain1(kc, z_stage, kf_stage, kf_start, kf_carry, tid);
+                if (tid == 0) {
+                    kf_tail = separable;
+                    if (!separable) {     // (LDS form: kf_dense.inc; its plan_state goes to LDS for the planner and from there to its output)
+                        kf_dense_stream_lds(kc, 0, 1, z_stage, nullptr, kf_stage, vs(), kf_start);
+                        *reinterpret_cast<double4*>(ps()) = *reinterpret_cast<const double4*>(kf_start);
+                    }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+                if (tid < AV_KF_STATE_DOUBLES) {
+                    if (seq)
+                        __hip_atomic_store(rec + tid, (unsigned long long)__double_as_longlong(kf_stage[tid]), __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT);
+                    else
+                        rec[tid] = (unsigned long long)__double_as_longlong(kf_stage[tid]);
+                }
             }
         }
         ck.mark(3);                   // Kalman chain + record stores issued
         __syncthreads();              // releases the planner: its start state is in LDS (no wait for any global store)
+        if (seq && !go) return;       // the wait ran out: the whole workgroup leaves without its step (the Kalman wave ran none of it)
         ck.mark(4);                   // planner start
         // The Kalman wave publishes its counter itself, behind the acknowledgement of its record stores -- while the planner's phase 1
         // runs on other waves: plan_block deals its tasks from wave KF_ROT on, which leaves wave 0 without phase-1 work (it joins the
@@ -305,7 +364,7 @@ __device__ __forceinline__ void hot_step_body(const StepArgs& a0) {
         auto tail = [&](int task_wave) {          // by the first pair wave, behind its cost chain
             if (task_wave != 0 || !kf_tail) return;
             const unsigned long long t0 = clocks ? __builtin_amdgcn_s_memrealtime() : 0ull;
-            kf_axis_tail1(a.kcfg, kf_stage, kf_carry, vs, ps, tid & 63);
+            kf_axis_tail1(a.kcfg, kf_stage, kf_carry, vs(), ps(), tid & 63);
             if (clocks && (tid & 63) == 0)
                 atomicAdd(reinterpret_cast<unsigned long long*>(a.flags + flag_stats(a.S)) + 16 + 7, __builtin_amdgcn_s_memrealtime() - t0);
         };
