@@ -453,6 +453,29 @@ int av_yolo_create(av_ctx* ctx, int batch, int in_h, int in_w, const float* weig
 #define AV_YOLO_FP32 1
 int av_yolo_create_ex(av_ctx* ctx, int batch, int in_h, int in_w, const float* weights, size_t n_weights, int precision,
                       av_yolo** out);
+/* The model family: YOLOv8 Detect models of yolov8.yaml.  av_yolo_model is everything the graph builder reads -- no table per scale
+ * exists anywhere else: ch = the widths of the five stages (layers 0/1/3/5/7), rep = the bottleneck pairs of the backbone's C2f blocks
+ * (layers 2/4/6/8), neck_rep = those of the neck's (12/15/18/21), nc = classes.  Derived: SPPF ch[4] -> ch[4]/2, 4 ch[4]/2 -> ch[4];
+ * Detect box branch ch -> hb -> hb -> 64 with hb = max(16, ch[2]/4, 64), class branch ch -> hc -> hc -> nc with
+ * hc = max(ch[2], min(nc, 100)).  Channel counts of the class branch that are no multiple of 16 are padded with zero filters and zero
+ * biases up to one (a padded hidden channel is silu(0) = 0 and meets zero weight columns; a padded logit is exactly 0.0f, lies at
+ * channels [nc, cstride) of the class logits and is never read by a decode).  av_yolo_model_preset fills a model for scale 'n', 's'
+ * or 'm' and 1 <= nc <= 256 (anything else: AV_EINVAL naming it; scales 'l' and 'x' are refused by name).  av_yolo_create_model and
+ * av_yolo_model_param_count take exactly what the preset gives for one of those three scales (reserved words zero): any other struct --
+ * an l- or x-shaped one, other widths or repeats -- is AV_EINVAL / 0, because only the presets' layer shapes have kernels.  av_yolo_create /
+ * av_yolo_create_ex / av_yolo_param_count are the ('n', 80) preset. */
+typedef struct av_yolo_model {
+    int32_t ch[5];
+    int32_t rep[4];
+    int32_t neck_rep;
+    int32_t nc;
+    int32_t reserved[5];            /* zero */
+} av_yolo_model;
+int av_yolo_model_preset(int scale_char, int nc, av_yolo_model* model);
+size_t av_yolo_model_param_count(const av_yolo_model* model);                      /* 0: not a preset of n, s or m */
+int av_yolo_create_model(av_ctx* ctx, int batch, int in_h, int in_w, const av_yolo_model* model, const float* weights,
+                         size_t n_weights, int precision, av_yolo** out);
+int av_yolo_model_of(const av_yolo* h, av_yolo_model* model);                      /* host out */
 int av_yolo_destroy(av_yolo* h);
 int av_yolo_dims(const av_yolo* h, int* net_h, int* net_w, int* n_anchors);        /* host out */
 /*   bgr      u8 [batch][in_h][in_w][3] (device)
@@ -487,7 +510,7 @@ int av_yolo_tensor(const av_yolo* h, int id, void** ptr, int* H, int* W, int* C,
  * + res.  `out` is float32 for the head's last convolutions (written only with keep_logits or in float32 mode).  in2: the
  * half-resolution map from which the default plan reads input channels [0, in2.c) of this 1x1 layer itself (virtual Upsample + Concat),
  * instead of their upsampled copy in `in`.  AV_YOLO_OP_STEM: `in` is the network input WITH its one-pixel frame of zeros
- * (in_frame = 1: no further padding), 4 channels per pixel, weights half [16][64] with k = 16 ky + 4 kx + c.  AV_YOLO_OP_POOLS:
+ * (in_frame = 1: no further padding), 4 channels per pixel, weights half [cout][64] with k = 16 ky + 4 kx + c.  AV_YOLO_OP_POOLS:
  * out channels [i in.c, (i + 1) in.c) = the 5x5 stride-1 maximum applied i + 1 times; AV_YOLO_OP_MAXPOOL: applied once;
  * AV_YOLO_OP_UPSAMPLE: nearest neighbour x2. */
 #define AV_YOLO_OP_CONV 0
@@ -511,6 +534,33 @@ typedef struct av_yolo_op_info {
 } av_yolo_op_info;
 int av_yolo_op_count(const av_yolo* h, int* n_ops);                                /* host out */
 int av_yolo_op(const av_yolo* h, int k, av_yolo_op_info* info);                    /* host out */
+/* With a padded class branch (av_yolo_model) an op's cout / out.c and a tensor's C are the REAL channel counts and cstride the padded
+ * one; cin / in.c of a convolution that reads a padded map count the operand's channels, zero padding included (the weights' K layout
+ * is tap cin + ci with that cin; the padding channels hold zeros on both sides).
+ *
+ * Test hook: the launches of a forward as they are planned now (for the hooks and keep_logits in force), in order.  family: which
+ * kernel family runs the launch; first_op / n_ops: the ops of av_yolo_op it covers (a fused block covers several; an upsample whose
+ * reader fetches the source itself is covered by that reader's launch; n_ops = 0: the letterbox); when: AV_YOLO_WHEN_*, the frame
+ * pointer alignment the launch is for (both forms of the front end are planned; a forward runs one).  Reads host memory only. */
+#define AV_YOLO_K_MFMA 0            /* conv_mfma_kernel: no LDS, one weight stream per wave -- the fallback for any shape */
+#define AV_YOLO_K_GEMM128 1
+#define AV_YOLO_K_LDS 2
+#define AV_YOLO_K_WS3 3
+#define AV_YOLO_K_WS1 4
+#define AV_YOLO_K_GEMM_F32 5
+#define AV_YOLO_K_STEM_F32 6        /* conv_f32_kernel: the float32 chain's no-LDS kernel (its 3-channel stem) */
+#define AV_YOLO_K_FIXED 7           /* a fused block, the half-precision stem, pools, upsample, letterbox */
+#define AV_YOLO_WHEN_ALWAYS 0
+#define AV_YOLO_WHEN_BGR_ALIGNED 1
+#define AV_YOLO_WHEN_BGR_UNALIGNED 2
+typedef struct av_yolo_step_info {
+    int32_t family, first_op, n_ops, when;
+    int32_t grid[3], block[3];
+    int32_t lds_bytes, lane;
+    int32_t variant[6];             /* the family's template parameters */
+} av_yolo_step_info;
+int av_yolo_plan_count(const av_yolo* h, int* n_steps);                            /* host out */
+int av_yolo_plan_step(const av_yolo* h, int k, av_yolo_step_info* info);           /* host out */
 
 /* ---- T3: scene classifier (road type, conditions, lane count) -------------------------------------------
  * Replaces SceneClassifier.classify and its helpers (src/tagging/scene_classifier.py:76-303): BGR2GRAY, Canny(50, 150)

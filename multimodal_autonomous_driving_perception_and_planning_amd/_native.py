@@ -127,6 +127,21 @@ class YoloOpInfo(C.Structure):
 YOLO_OP_CONV, YOLO_OP_STEM, YOLO_OP_POOLS, YOLO_OP_MAXPOOL, YOLO_OP_UPSAMPLE = range(5)
 
 
+class YoloModel(C.Structure):
+    """av_yolo_model: everything the YOLO graph builder reads (stage widths, C2f repeats, class count)."""
+    _fields_ = [("ch", C.c_int32 * 5), ("rep", C.c_int32 * 4), ("neck_rep", C.c_int32), ("nc", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+class YoloStepInfo(C.Structure):
+    """av_yolo_step_info: one launch of the YOLO forward's plan (test hook av_yolo_plan_step)."""
+    _fields_ = ([(k, C.c_int32) for k in ("family", "first_op", "n_ops", "when")] + [("grid", C.c_int32 * 3), ("block", C.c_int32 * 3)]
+                + [("lds_bytes", C.c_int32), ("lane", C.c_int32), ("variant", C.c_int32 * 6)])
+
+
+(YOLO_K_MFMA, YOLO_K_GEMM128, YOLO_K_LDS, YOLO_K_WS3, YOLO_K_WS1, YOLO_K_GEMM_F32, YOLO_K_STEM_F32, YOLO_K_FIXED) = range(8)
+YOLO_WHEN_ALWAYS, YOLO_WHEN_BGR_ALIGNED, YOLO_WHEN_BGR_UNALIGNED = range(3)
+
+
 class JpegDesc(C.Structure):
     """av_jpeg_desc (include/avhot.h): one frame's headers as av_jpeg_parse reads them; 928 bytes."""
     _fields_ = ([(k, C.c_int32) for k in ("width", "height", "ncomp", "hs", "vs", "restart_interval", "n_segments", "flags", "scan_offset",
@@ -276,6 +291,10 @@ _SIGS = [
     ("av_yolo_param_count", C.c_size_t, []),
     ("av_yolo_create", C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(vp)]),
     ("av_yolo_create_ex", C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.c_int, C.POINTER(vp)]),
+    ("av_yolo_model_preset", C.c_int, [C.c_int, C.c_int, C.POINTER(YoloModel)]),
+    ("av_yolo_model_param_count", C.c_size_t, [C.POINTER(YoloModel)]),
+    ("av_yolo_create_model", C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(YoloModel), vp, C.c_size_t, C.c_int, C.POINTER(vp)]),
+    ("av_yolo_model_of", C.c_int, [vp, C.POINTER(YoloModel)]),
     ("av_yolo_destroy", C.c_int, [vp]),
     ("av_yolo_dims", C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("av_yolo_forward", C.c_int, [vp, vp, vp, C.c_float, C.c_float, C.c_int, vp, vp, vp, vp]),
@@ -285,6 +304,8 @@ _SIGS = [
     ("av_yolo_tensor", C.c_int, [vp, C.c_int, C.POINTER(vp)] + [C.POINTER(C.c_int)] * 5),
     ("av_yolo_op_count", C.c_int, [vp, C.POINTER(C.c_int)]),
     ("av_yolo_op", C.c_int, [vp, C.c_int, C.POINTER(YoloOpInfo)]),
+    ("av_yolo_plan_count", C.c_int, [vp, C.POINTER(C.c_int)]),
+    ("av_yolo_plan_step", C.c_int, [vp, C.c_int, C.POINTER(YoloStepInfo)]),
     ("av_lane_detect", C.c_int, [vp, vp, C.POINTER(LaneCfg), C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp,
                                  vp, C.c_int]),
     ("av_scene_state_bytes", C.c_size_t, [C.c_int]),

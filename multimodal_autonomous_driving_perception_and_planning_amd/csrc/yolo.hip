@@ -1,8 +1,9 @@
-// D2: YOLOv8n-topology detector, MFMA convolution path.
+// D2: YOLOv8 detector (yolov8.yaml's Detect models of scales n, s and m with 1 - 256 classes; default n, 80), MFMA convolution path.
 //
 // Reference call site: ObjectDetector._detect_yolo (src/perception/detector.py:103-123) ->
-// ultralytics YOLO("yolov8n.pt")(frame) (third party, not vendored; topology restated in
-// oracle/yolo_ref.py, which also defines the parameter order this file consumes).
+// ultralytics YOLO(model_path)(frame), "yolov8n.pt" by default (third party, not vendored; topology restated in
+// oracle/yolo_ref.py at scale n, which also defines the parameter order this file consumes; av_yolo_model and
+// build_graph state it for every scale).
 //
 // Layout: activations are NHWC half with an explicit channel stride, so a producer can write straight
 // into a channel slice of a concat buffer (every Concat / chunk of the graph is free) and a consumer can
@@ -296,13 +297,17 @@ __global__ void __launch_bounds__(256) conv_gemm128_kernel(ConvArgs a) {
 // once per wave.  Wave w computes output rows 2w, 2w+1 of the tile (16 columns each).
 constexpr int LT_H = 8, LT_W = 16, LT_CK = 32, LT_PIXB = LT_CK * 2 + 32;   // row strides = 32 mod 64 bytes: ds_read_b128's four 16-lane groups
 // ({0-3,12-15,20-27}, ...: MI355X_MICROARCH.md LDS) then touch every bank once; with 16 bytes of padding 7 of 8 slots collided 2-way
+constexpr int lt_pixb(int stride) { return stride == 1 ? LT_PIXB : LT_CK * 2 + 16; }   // stride 2: neighbouring lanes read pixels two apart, so the
+// pixel stride is = 16 mod 32 bytes (twice that = 32 mod 64), as in conv3x3_ws_kernel
 
-template <int MT, int KS>     // KS: kernel size (1 or 3), stride 1.  (A stride-2 instance for the two cin = 128 stride-2 layers -- 17 x 33
-// patch per chunk -- was measured in round 3: 62.6 / 34.3 us against conv_mfma_kernel's 53.8 / 29.3 us; not kept.)
+template <int MT, int KS, int S = 1>     // KS: kernel size (1 or 3); S: stride.  (A stride-2 instance for the two cin = 128 stride-2 layers -- 17 x 33
+// patch per chunk -- was measured in round 3: 62.6 / 34.3 us against conv_mfma_kernel's 53.8 / 29.3 us; not kept for them.  S = 2 serves the
+// stride-2 layers of the wider scales that neither conv3x3_ws_kernel (weights past the LDS) nor conv_gemm128_kernel (cin % 64, cout % 128)
+// takes: scale m's 96 -> 192, 384 -> 576 and 192 -> 192.)
 __global__ void __launch_bounds__(256) conv_lds_kernel(ConvArgs a, int tiles_x, int tiles_y) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lsm[];
-    constexpr int taps = KS * KS, pad = KS >> 1, s = 1, PIXB = LT_PIXB;
-    constexpr int PH = LT_H - 1 + KS, PW = LT_W - 1 + KS;
+    constexpr int taps = KS * KS, pad = KS >> 1, s = S, PIXB = lt_pixb(S);
+    constexpr int PH = (LT_H - 1) * S + KS, PW = (LT_W - 1) * S + KS;
     constexpr int wrowb = taps * LT_CK * 2 + 32;
     unsigned char* patch = lsm;
     unsigned char* wts = lsm + (((size_t)PH * PW * PIXB + 15) & ~size_t(15));
@@ -687,8 +692,10 @@ __global__ void __launch_bounds__(NW * 64) conv3x3_ws_kernel(ConvArgs a, int til
 // so that lane group h holds all 16 bins of side h of its pixel, then decode_kernel's arithmetic to the letter (sequential
 // max / exp / sums over the bins, IEEE divide) and one box coordinate per lane.  2: class branch (80 classes): first maximum
 // (lowest class among equals, as decode_kernel's scan) over the lane's 20 values and across the four lane groups, sigmoid.
-// Candidates equal decode_kernel's bit for bit (test_fused_decode_equals_decode_kernel).
-struct DecArgs { float* cbox; float* cconf; int* ccls; int A, aoff, stride, keep_logits; };
+// Candidates equal decode_kernel's bit for bit (test_fused_decode_equals_decode_kernel).  3: the class branch of any other model --
+// dec.nc classes at run time in 16 MT >= nc output channels (the rest are zero filters: logits of exactly 0.0f, stored with the kept
+// logits but never a candidate for the maximum); the 80-class instantiation (2) keeps its compile-time count.
+struct DecArgs { float* cbox; float* cconf; int* ccls; int A, aoff, stride, keep_logits, nc; };      // nc: read by DEC = 3 only
 constexpr int DEC_ROW = 68;                        // floats per pixel row of the box detour (64 + 4: conflict-free b128 rows)
 
 template <int MT, int KS, bool TAIL16 = false, int DEC = 0>      // TAIL16: 16 more input channels after the KS whole steps (cin = 80), as a zero-padded K = 32 step
@@ -698,7 +705,7 @@ __global__ void __launch_bounds__(DEC == 1 ? 128 : 256) conv1x1_ws_kernel(ConvAr
     // waves per workgroup: two for the box decode, whose per-wave LDS detour would otherwise push the workgroup past the 19 KB
     // that stay free on a CU beside the other head lane's 144-KB 3x3 kernel
     constexpr int NWV = DEC == 1 ? 2 : 4, NTH = NWV * 64;
-    static_assert(DEC == 0 || (DEC == 1 && MT == 4) || (DEC == 2 && MT == 5), "decode epilogues belong to the 64- and 80-channel head outputs");
+    static_assert(DEC == 0 || (DEC == 1 && MT == 4) || (DEC == 2 && MT == 5) || DEC == 3, "decode epilogues belong to the 64- and 80-channel head outputs, or take nc at run time");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, h = lane >> 4;
     const int ch_base = blockIdx.y * 16 * MT;
     {
@@ -822,7 +829,7 @@ __global__ void __launch_bounds__(DEC == 1 ? 128 : 256) conv1x1_ws_kernel(ConvAr
                     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
                         for (int q = 0; q < 4; ++q)
-                            if (vv[mt][q] > best) best = vv[mt][q], bj = mt * 16 + 4 * h + q;
+                            if (vv[mt][q] > best && (DEC == 2 || mt * 16 + 4 * h + q < dec.nc)) best = vv[mt][q], bj = mt * 16 + 4 * h + q;
 #pragma unroll
                     for (int off = 16; off < 64; off <<= 1) {
                         const float ob = __shfl_xor(best, off, 64);
@@ -1329,11 +1336,14 @@ __global__ void __launch_bounds__(F32_NTH) c2f32_tail_kernel(C2f32Args a) {
 // (kx = 3 and c = 3 carry zero weights; 48 -> 64): an 8-element B operand is then two horizontally adjacent input
 // pixels = one aligned 16-byte load (the frame makes column 2*ox + kx even and every load in bounds), and the whole
 // receptive field is two MFMA steps.  Half the bytes of the 8-channel layout on both sides of the kernel.
+// TILED: more than 16 output channels (scales s and m: 32, 48), blockIdx.y = the 16-channel tile; false: the 16-channel stem as it was.
+template <bool TILED>
 __global__ void __launch_bounds__(256) stem_conv_kernel(ConvArgs a, int npix) {
     const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, h = lane >> 4;
-    const half8 A0 = *reinterpret_cast<const half8*>(a.wgt + l15 * 64 + 8 * h);
-    const half8 A1 = *reinterpret_cast<const half8*>(a.wgt + l15 * 64 + 32 + 8 * h);
-    const float4 bs = *reinterpret_cast<const float4*>(a.bias + 4 * h);
+    const int ch_base = TILED ? blockIdx.y * 16 : 0;
+    const half8 A0 = *reinterpret_cast<const half8*>(a.wgt + (ch_base + l15) * 64 + 8 * h);
+    const half8 A1 = *reinterpret_cast<const half8*>(a.wgt + (ch_base + l15) * 64 + 32 + 8 * h);
+    const float4 bs = *reinterpret_cast<const float4*>(a.bias + ch_base + 4 * h);
     const int pitch = (a.W + 2) * 4, hw = a.Ho * a.Wo;                           // elements per framed input row
     // k-step 0: group h = (ky, kx) = (h >> 1, 2 (h & 1)); k-step 1: ky = 2, groups 2 and 3 have zero weights
     const int off0 = (h >> 1) * pitch + (h & 1) * 8, off1 = 2 * pitch + (h & 1) * 8;
@@ -1351,7 +1361,7 @@ __global__ void __launch_bounds__(256) stem_conv_kernel(ConvArgs a, int npix) {
         acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(A0, B0, acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(A1, B1, acc, 0, 0, 0);
         if (p < npix)
-            *reinterpret_cast<half4*>(a.out + (size_t)p * a.out_cs + a.out_coff + 4 * h) =
+            *reinterpret_cast<half4*>(a.out + (size_t)p * a.out_cs + a.out_coff + ch_base + 4 * h) =
                 make_half4(silu(acc[0] + bs.x), silu(acc[1] + bs.y), silu(acc[2] + bs.z), silu(acc[3] + bs.w));
     }
 }
@@ -1636,9 +1646,12 @@ __global__ void upsample2_kernel(const half_t* in, int cs_in, int coff_in, half_
 
 struct Level { const float* box; const float* cls; int H, W, stride, aoff; };
 
-// DFL expectation + best class; writes candidates of every anchor
+// DFL expectation + best class; writes candidates of every anchor.  NCT: the class count at compile time (80, the default model:
+// the kernel as it was) or 0: `nc` classes in pixels of `ccs` floats (the padded stride), both at run time.
+template <int NCT>
 __global__ void decode_kernel(Level l0, Level l1, Level l2, int A, int B, float* __restrict__ cbox, float* __restrict__ cconf,
-                              int* __restrict__ ccls) {
+                              int* __restrict__ ccls, int nc, int ccs) {
+    const int ncl = NCT ? NCT : nc, cstr = NCT ? NCT : ccs;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B * A) return;
     const int n = i / A, a = i - n * A;
@@ -1657,10 +1670,10 @@ __global__ void decode_kernel(Level l0, Level l1, Level l2, int A, int B, float*
         d[s] = ex / sum;
     }
     const float ax = (float)x + 0.5f, ay = (float)y + 0.5f, st = (float)L.stride;
-    const float* cl = L.cls + ((size_t)(n * L.H + y) * L.W + x) * NC;
+    const float* cl = L.cls + ((size_t)(n * L.H + y) * L.W + x) * cstr;
     float best = -INFINITY;
     int bj = 0;
-    for (int j = 0; j < NC; ++j)
+    for (int j = 0; j < ncl; ++j)
         if (cl[j] > best) best = cl[j], bj = j;
     float* o = cbox + (size_t)i * 4;
     o[0] = (ax - d[0]) * st, o[1] = (ay - d[1]) * st, o[2] = (ax + d[2]) * st, o[3] = (ay + d[3]) * st;
@@ -2170,7 +2183,8 @@ __global__ void upsample2_f32_kernel(const float* in, int cs_in, int coff_in, fl
 // ---- host side: graph of layers --------------------------------------------------------------------------------
 
 struct Buf { half_t* p = nullptr; int C = 0, H = 0, W = 0; };     // (reference-precision mode: the same pointer holds float elements)
-struct Slice { int buf, coff, c; };
+struct Slice { int buf, coff, c, real = 0; };     // c channels as allocated / as the kernels see them; real (0: = c): how many of them the model has,
+// the rest being the zero padding of a class branch whose width is no multiple of 16
 
 enum OpKind { OP_CONV, OP_STEM, OP_POOLS, OP_MAXPOOL, OP_UPSAMPLE, OP_CONV_F32 };     // OP_POOLS: SPPF's three pools in one launch (half); OP_MAXPOOL: one of them (float32)
 
@@ -2200,9 +2214,14 @@ struct Variant { Family fam; int p[6]; const void* fn; int lds_limit; };
 const Variant kVariants[] = {
     // generic fallback, any shape
     AV_KT(K_MFMA, 0, conv_mfma_kernel, 2, 2), AV_KT(K_MFMA, 0, conv_mfma_kernel, 4, 2), AV_KT(K_MFMA, 0, conv_mfma_kernel, 5, 2),
+    AV_KT(K_MFMA, 0, conv_mfma_kernel, 1, 2), AV_KT(K_MFMA, 0, conv_mfma_kernel, 3, 2),
     {K_GEMM128, {}, reinterpret_cast<const void*>(&conv_gemm128_kernel), 160 * 1024},
     // <MT, KS>
     AV_KT(K_LDS, 100 * 1024, conv_lds_kernel, 4, 1), AV_KT(K_LDS, 100 * 1024, conv_lds_kernel, 4, 3), AV_KT(K_LDS, 100 * 1024, conv_lds_kernel, 5, 3),
+    // the widths of scales s and m and of padded class branches: 16-, 32-, 48- and 80-channel tiles; <MT, KS, S>: stride 2
+    AV_KT(K_LDS, 100 * 1024, conv_lds_kernel, 1, 1), AV_KT(K_LDS, 100 * 1024, conv_lds_kernel, 2, 1), AV_KT(K_LDS, 100 * 1024, conv_lds_kernel, 3, 1),
+    AV_KT(K_LDS, 100 * 1024, conv_lds_kernel, 5, 1), AV_KT(K_LDS, 100 * 1024, conv_lds_kernel, 1, 3), AV_KT(K_LDS, 100 * 1024, conv_lds_kernel, 2, 3),
+    AV_KT(K_LDS, 100 * 1024, conv_lds_kernel, 3, 3), AV_KT(K_LDS, 100 * 1024, conv_lds_kernel, 4, 3, 2),
     // <MT, NT, NW, CINP, RES, S>: stride 1 with 8 or 16 tile rows, with and without residual; stride 2
     AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 1, 1, 8, 32, false, 1), AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 1, 1, 8, 32, true, 1),
     AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 1, 2, 8, 32, false, 1), AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 1, 2, 8, 32, true, 1),
@@ -2214,8 +2233,17 @@ const Variant kVariants[] = {
     AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 5, 1, 8, 80, false, 1),
     AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 2, 1, 8, 32, false, 2), AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 4, 1, 8, 32, false, 2),
     AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 4, 1, 8, 64, false, 2),
+    // 48-channel tiles (scale m): the 48 -> 48 bottlenecks of layer 2, layer 1 (48 -> 96, stride 2)
+    AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 3, 1, 8, 64, false, 1), AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 3, 1, 8, 64, true, 1),
+    AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 3, 2, 8, 64, false, 1), AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 3, 2, 8, 64, true, 1),
+    AV_KT(K_WS3, 160 * 1024, conv3x3_ws_kernel, 3, 1, 8, 64, false, 2),
     // <MT, KS, TAIL16, DEC>: the head's last box / class convolutions with the decode in their epilogue, then the plain ones
     AV_KT(K_WS1, 0, conv1x1_ws_kernel, 4, 2, false, 1), AV_KT(K_WS1, 0, conv1x1_ws_kernel, 5, 2, true, 2),
+    AV_KT(K_WS1, 0, conv1x1_ws_kernel, 5, 2, true, 0),      // 80 -> 80 without an epilogue: scale n with nc = 65 .. 79 (hc = nc, both padded to 80)
+    // DEC = 3, the class decode with nc at run time: hc = 64 (scale n, nc <= 32), 128 (s) and 192 (m) with nc <= 16 or 65 .. 80
+    AV_KT(K_WS1, 0, conv1x1_ws_kernel, 1, 2, false, 3), AV_KT(K_WS1, 0, conv1x1_ws_kernel, 2, 2, false, 3),
+    AV_KT(K_WS1, 0, conv1x1_ws_kernel, 1, 4, false, 3), AV_KT(K_WS1, 0, conv1x1_ws_kernel, 5, 4, false, 3),
+    AV_KT(K_WS1, 100 * 1024, conv1x1_ws_kernel, 1, 6, false, 3), AV_KT(K_WS1, 100 * 1024, conv1x1_ws_kernel, 5, 6, false, 3),
     AV_KT(K_WS1, 100 * 1024, conv1x1_ws_kernel, 2, 1, false, 0), AV_KT(K_WS1, 100 * 1024, conv1x1_ws_kernel, 4, 2, false, 0),
     AV_KT(K_WS1, 100 * 1024, conv1x1_ws_kernel, 4, 3, false, 0), AV_KT(K_WS1, 100 * 1024, conv1x1_ws_kernel, 4, 4, false, 0),
     AV_KT(K_WS1, 100 * 1024, conv1x1_ws_kernel, 4, 6, false, 0), AV_KT(K_WS1, 100 * 1024, conv1x1_ws_kernel, 4, 8, false, 0),
@@ -2224,8 +2252,12 @@ const Variant kVariants[] = {
     AV_KT(K_GEMM_F32, 100 * 1024, conv_gemm_f32_kernel, 128, 64, 32), AV_KT(K_GEMM_F32, 100 * 1024, conv_gemm_f32_kernel, 64, 128, 32),
     AV_KT(K_GEMM_F32, 100 * 1024, conv_gemm_f32_kernel, 80, 128, 32), AV_KT(K_GEMM_F32, 100 * 1024, conv_gemm_f32_kernel, 80, 128, 16),
     AV_KT(K_GEMM_F32, 0, conv_gemm_f32_kernel, 32, 128, 32), AV_KT(K_GEMM_F32, 0, conv_gemm_f32_kernel, 32, 128, 16),
-    AV_KT(K_GEMM_F32, 0, conv_gemm_f32_kernel, 16, 128, 16),
+    AV_KT(K_GEMM_F32, 0, conv_gemm_f32_kernel, 16, 128, 16), AV_KT(K_GEMM_F32, 0, conv_gemm_f32_kernel, 16, 128, 32),
+    AV_KT(K_GEMM_F32, 100 * 1024, conv_gemm_f32_kernel, 48, 128, 32), AV_KT(K_GEMM_F32, 100 * 1024, conv_gemm_f32_kernel, 48, 128, 16),
+    // cin = 112 (scale n with nc > 96: hc padded to 112) into 128- / 256- and 192-wide padded class counts
+    AV_KT(K_GEMM_F32, 100 * 1024, conv_gemm_f32_kernel, 128, 64, 16), AV_KT(K_GEMM_F32, 100 * 1024, conv_gemm_f32_kernel, 64, 128, 16),
     AV_KT(K_STEM_F32, 0, conv_f32_kernel, 1, 1, 4, 2), AV_KT(K_STEM_F32, 0, conv_f32_kernel, 1, 2, 4, 2), AV_KT(K_STEM_F32, 0, conv_f32_kernel, 1, 4, 4, 2),
+    AV_K(0, stem_conv_kernel<false>), AV_K(0, stem_conv_kernel<true>), AV_K(0, decode_kernel<NC>), AV_K(0, decode_kernel<0>),
     AV_K(C2F_LDS, c2f16_fused_kernel), AV_K(FR_LDS, front_fused_kernel), AV_K(F32H_LDS, c2f32_head_kernel),
     AV_K(f32t_lds(96), (c2f32_tail_kernel<96, true>)), AV_K(f32t_lds(64), (c2f32_tail_kernel<64, false>)),
     AV_K((int)rs_lds(7, 8), nms_sort_kernel<8>), AV_K((int)rs_lds(8, 7), nms_sort_kernel<7>),
@@ -2251,6 +2283,7 @@ struct Step {
     int lane = 0;                        // 1: the side stream
     bool head = false;                   // the Detect head begins here: everything before it is one dependency chain
     bool takes_bgr = false;              // the kernel's first parameter begins with the frame pointer, which every call brings
+    int fam = K_FIXED, var[6] = {0, 0, 0, 0, 0, 0}, first_op = 0, n_ops = 0;       // what av_yolo_plan_step reports
     alignas(16) unsigned char params[384];
     int off[12], nargs = 0;
     template <typename... A>
@@ -2276,12 +2309,14 @@ struct Step {
 
 struct Yolo {
     av_ctx* ctx = nullptr;
+    av_yolo_model model{};
+    int ncp = 0;                         // floats per pixel of the class logits: nc rounded up to a multiple of 16
     int B = 0, inH = 0, inW = 0, H = 0, W = 0, nh = 0, nw = 0, top = 0, left = 0, A = 0, words = 0;
     float gain = 1.f;
     std::vector<Buf> bufs;
     float* f32_zeros = nullptr;
     bool f32 = false;                    // reference-precision mode: float32 tensors and weights, conv_gemm_f32_kernel, no fusion
-    struct Op { OpKind kind; ConvArgs ca; ConvArgsF cf; int mt; Slice in, out; int H, W, C; int lane = 0; int fuse = 0; int dec = 0, dec_level = 0; int vcat = -1; };   // lane 1: internal side stream;
+    struct Op { OpKind kind; ConvArgs ca; ConvArgsF cf; int mt; int cout_real = 0; Slice in, out; int H, W, C; int lane = 0; int fuse = 0; int dec = 0, dec_level = 0; int vcat = -1; };   // lane 1: internal side stream;
     // vcat >= 0 (an upsample op): op index of the 1x1 convolution that can read this upsample's source directly (virtual Upsample + Concat);
     // fuse 1: this op and the next three are a C2f block c2f16_fused_kernel can run in one launch; 2 / 3: 32-channel blocks (c2f32_*); dec 1 / 2: the head's last box /
     // class convolution of level dec_level (its epilogue can do the decode)
@@ -2301,6 +2336,7 @@ struct Yolo {
     std::vector<Step> plan;
     Hooks plan_hooks{};
     bool plan_keep_logits = false;
+    bool decode_alone = false;           // the plan has no decode epilogue: decode_kernel makes the candidates (plan_forward)
     std::vector<void*> allocs;
     float* head_box[3] = {nullptr, nullptr, nullptr};
     float* head_cls[3] = {nullptr, nullptr, nullptr};
@@ -2356,7 +2392,10 @@ void fold_bn(const float* bp, int cout, bool bn_act, int co, float& scale, float
     }
 }
 
-int mt_of(int cout) { return (cout % 64 == 0) ? 4 : ((cout % 80 == 0) ? 5 : ((cout % 32 == 0) ? 2 : 1)); }
+// 16-channel tiles per workgroup for `cout` output channels (a multiple of 16): 64-, 80-, 48-, 32-, then 16-wide
+int mt_of(int cout) { return (cout % 64 == 0) ? 4 : ((cout % 80 == 0) ? 5 : ((cout % 48 == 0) ? 3 : ((cout % 32 == 0) ? 2 : 1))); }
+int pad16(int c) { return (c + 15) & ~15; }
+int real_of(Slice s) { return s.real ? s.real : s.c; }
 
 // what ConvArgs and ConvArgsF share: input, output and residual slices (an `out` without a buffer: the caller sets the output), sizes
 template <typename Args>
@@ -2374,18 +2413,18 @@ void conv_geometry(const Yolo& y, Args& a, Slice in, Slice out, int k, int s, bo
 
 // consumes one conv's parameters, folds BN, uploads half [cout][kpad] + f32 bias, appends the op
 bool add_conv_half(Yolo& y, Slice in, Slice out, int k, int s, bool bn_act, float* out32, int out32_cs, const Slice* res) {
-    const int cin = in.c, cout = out.c, taps = k * k;
+    const int cin = in.c, cout = out.c, taps = k * k, cin_r = real_of(in), cout_r = real_of(out);      // (padding: zero filters, zero biases, zero columns)
     const int kreal = taps * cin, kpad = (kreal + 31) & ~31;
     const float *w, *bp;
-    if (!take_params(y, (size_t)cout * cin * taps, cout, bn_act, w, bp)) return false;
+    if (!take_params(y, (size_t)cout_r * cin_r * taps, cout_r, bn_act, w, bp)) return false;
     std::vector<half_t> wb((size_t)cout * kpad, (half_t)0);
-    std::vector<float> bias(cout);
-    for (int co = 0; co < cout; ++co) {
+    std::vector<float> bias(cout, 0.f);
+    for (int co = 0; co < cout_r; ++co) {
         float scale;
-        fold_bn(bp, cout, bn_act, co, scale, bias[co]);
-        for (int ci = 0; ci < cin; ++ci)
+        fold_bn(bp, cout_r, bn_act, co, scale, bias[co]);
+        for (int ci = 0; ci < cin_r; ++ci)
             for (int t = 0; t < taps; ++t)
-                wb[(size_t)co * kpad + t * cin + ci] = f2h(w[((size_t)co * cin + ci) * taps + t] * scale);
+                wb[(size_t)co * kpad + t * cin + ci] = f2h(w[((size_t)co * cin_r + ci) * taps + t] * scale);
     }
     const half_t* dw = upload(y, wb);
     const float* db = upload(y, bias);
@@ -2396,7 +2435,7 @@ bool add_conv_half(Yolo& y, Slice in, Slice out, int k, int s, bool bn_act, floa
     conv_geometry(y, a, in, out, k, s, bn_act, res);
     a.wgt = dw, a.bias = db, a.kpad = kpad, a.kreal = kreal;
     if (out32) a.out = nullptr, a.out32 = out32, a.out_cs = out32_cs, a.out_coff = 0;
-    op.mt = mt_of(cout);
+    op.mt = mt_of(cout), op.cout_real = cout_r;
     y.ops.push_back(op);
     return true;
 }
@@ -2404,14 +2443,14 @@ bool add_conv_half(Yolo& y, Slice in, Slice out, int k, int s, bool bn_act, floa
 // the same for the reference-precision chain: float32 weights [cout][tap][cin]; an input of 4 channels whose parameters have 3 (the
 // stem) gets a zero fourth channel
 bool add_conv_f32(Yolo& y, Slice in, Slice out, int k, int s, bool bn_act, float* out32, int out32_cs, const Slice* res) {
-    const int cin = in.c, cout = out.c, taps = k * k;
-    const int cin_w = (cin == 4 && k == 3 && s == 2 && y.ops.empty()) ? 3 : cin;
+    const int cin = in.c, cout = out.c, taps = k * k, cout_r = real_of(out);
+    const int cin_w = (cin == 4 && k == 3 && s == 2 && y.ops.empty()) ? 3 : real_of(in);
     const float *w, *bp;
-    if (!take_params(y, (size_t)cout * cin_w * taps, cout, bn_act, w, bp)) return false;
-    std::vector<float> wf((size_t)cout * taps * cin, 0.f), bias(cout);
-    for (int co = 0; co < cout; ++co) {
+    if (!take_params(y, (size_t)cout_r * cin_w * taps, cout_r, bn_act, w, bp)) return false;
+    std::vector<float> wf((size_t)cout * taps * cin, 0.f), bias(cout, 0.f);
+    for (int co = 0; co < cout_r; ++co) {
         float scale;
-        fold_bn(bp, cout, bn_act, co, scale, bias[co]);
+        fold_bn(bp, cout_r, bn_act, co, scale, bias[co]);
         for (int ci = 0; ci < cin_w; ++ci)
             for (int t = 0; t < taps; ++t) wf[((size_t)co * taps + t) * cin + ci] = w[((size_t)co * cin_w + ci) * taps + t] * scale;
     }
@@ -2426,7 +2465,7 @@ bool add_conv_f32(Yolo& y, Slice in, Slice out, int k, int s, bool bn_act, float
     if (out32) a.out = out32, a.out_cs = out32_cs, a.out_coff = 0;
     if (!y.f32_zeros && !dev_alloc(y, (void**)&y.f32_zeros, 64)) return false;      // (dev_alloc clears)
     a.zeros = y.f32_zeros;
-    op.mt = mt_of(cout);
+    op.mt = mt_of(cout), op.cout_real = cout_r;
     y.ops.push_back(op);
     return true;
 }
@@ -2435,11 +2474,11 @@ bool add_conv(Yolo& y, Slice in, Slice out, int k, int s, bool bn_act, float* ou
     return y.f32 ? add_conv_f32(y, in, out, k, s, bn_act, out32, out32_cs, res) : add_conv_half(y, in, out, k, s, bn_act, out32, out32_cs, res);
 }
 
-// the stem's parameters (Conv 3 -> 16, k3 s2, BN, SiLU) packed for stem_conv_kernel: half [16][64], k = ky*16 + kx*4 + c
+// the stem's parameters (Conv 3 -> ch[0], k3 s2, BN, SiLU) packed for stem_conv_kernel: half [cout][64], k = ky*16 + kx*4 + c
 bool add_stem(Yolo& y, Slice in, Slice out) {
-    const int cout = 16, cin_real = 3, taps = 9;
+    const int cout = out.c, cin_real = 3, taps = 9;
     const float *w, *bp;
-    if (out.c != cout || !take_params(y, (size_t)cout * cin_real * taps, cout, true, w, bp)) return false;
+    if (cout % 16 || !take_params(y, (size_t)cout * cin_real * taps, cout, true, w, bp)) return false;
     std::vector<half_t> wb((size_t)cout * 64, (half_t)0);
     std::vector<float> bias(cout);
     for (int co = 0; co < cout; ++co) {
@@ -2460,7 +2499,7 @@ bool add_stem(Yolo& y, Slice in, Slice out) {
     a.Ho = (y.H - 1) / 2 + 1, a.Wo = (y.W - 1) / 2 + 1;
     a.out = y.bufs[out.buf].p, a.out32 = nullptr, a.out_cs = y.bufs[out.buf].C, a.out_coff = out.coff;
     a.cout = cout, a.res = nullptr, a.res_cs = 0, a.res_coff = 0, a.act = 1, a.npix = y.B * a.Ho * a.Wo;
-    op.mt = 1;
+    op.mt = 1, op.cout_real = cout;
     y.ops.push_back(op);
     return true;
 }
@@ -2506,64 +2545,72 @@ void letterbox(int h, int w, float& r, int& nh, int& nw, int& top, int& left, in
     H = nh + top + bottom, W = nw + left + right;
 }
 
-// buffers, parameters and ops of the whole network (yolov8.yaml layer numbers in the margin)
+// buffers, parameters and ops of the whole network, from the model alone (yolov8.yaml layer numbers in the margin): c1..c5 the stage
+// widths, a concat buffer per Concat with its producers writing their slices in place
 int build_graph(Yolo& y) {
     bool ok = true;
+    const av_yolo_model& m = y.model;
     const int H = y.H, W = y.W, batch = y.B;
+    const int c1 = m.ch[0], c2 = m.ch[1], c3 = m.ch[2], c4 = m.ch[3], c5 = m.ch[4], nr = m.neck_rep, nc = m.nc, cs = c5 / 2;
+    const int hb = std::max(16, std::max(c3 / 4, 4 * REG_MAX)), hc = std::max(c3, std::min(nc, 100));      // Detect's hidden widths
+    const int hcp = pad16(hc), ncp = pad16(nc);
+    y.ncp = ncp;
     auto nb = [&](int hh, int ww, int c) { const int b = new_buf(y, hh, ww, c); ok = ok && b >= 0; return b; };
-    const int x0 = y.f32 ? nb(H, W, 4) : nb(H + 2, W + 2, 4), b0 = nb(H / 2, W / 2, 16), b1 = nb(H / 4, W / 4, 32), b2 = nb(H / 4, W / 4, 32);
-    const int cat14 = nb(H / 8, W / 8, 192), cat11 = nb(H / 16, W / 16, 384), cat20 = nb(H / 32, W / 32, 384);
-    const int cat17 = nb(H / 16, W / 16, 192);
-    const int b3 = nb(H / 8, W / 8, 64), b5 = nb(H / 16, W / 16, 128), b7 = nb(H / 32, W / 32, 256), b8 = nb(H / 32, W / 32, 256);
-    const int spp = nb(H / 32, W / 32, 512), p3 = nb(H / 8, W / 8, 64), p4 = nb(H / 16, W / 16, 128), p5 = nb(H / 32, W / 32, 256);
+    const int x0 = y.f32 ? nb(H, W, 4) : nb(H + 2, W + 2, 4), b0 = nb(H / 2, W / 2, c1), b1 = nb(H / 4, W / 4, c2), b2 = nb(H / 4, W / 4, c2);
+    const int cat14 = nb(H / 8, W / 8, c4 + c3), cat11 = nb(H / 16, W / 16, c5 + c4), cat20 = nb(H / 32, W / 32, c4 + c5);
+    const int cat17 = nb(H / 16, W / 16, c3 + c4);
+    const int b3 = nb(H / 8, W / 8, c3), b5 = nb(H / 16, W / 16, c4), b7 = nb(H / 32, W / 32, c5), b8 = nb(H / 32, W / 32, c5);
+    const int spp = nb(H / 32, W / 32, 4 * cs), p3 = nb(H / 8, W / 8, c3), p4 = nb(H / 16, W / 16, c4), p5 = nb(H / 32, W / 32, c5);
     AV_REQUIRE(ok, AV_ENOMEM, "av_yolo_create: device allocation failed");
 #define CV(...) ok = ok && add_conv(y, __VA_ARGS__)
-    if (y.f32) CV(Slice{x0, 0, 4}, Slice{b0, 0, 16}, 3, 2, true, nullptr, 0, nullptr);           // 0 (4-channel input, fourth channel zero)
-    else ok = ok && add_stem(y, Slice{x0, 0, 4}, Slice{b0, 0, 16});                               // 0
-    CV(Slice{b0, 0, 16}, Slice{b1, 0, 32}, 3, 2, true, nullptr, 0, nullptr);                      // 1
-    ok = ok && add_c2f(y, Slice{b1, 0, 32}, Slice{b2, 0, 32}, 1, true);                            // 2
-    CV(Slice{b2, 0, 32}, Slice{b3, 0, 64}, 3, 2, true, nullptr, 0, nullptr);                      // 3
-    ok = ok && add_c2f(y, Slice{b3, 0, 64}, Slice{cat14, 128, 64}, 2, true);                       // 4 -> cat14[128:192]
-    CV(Slice{cat14, 128, 64}, Slice{b5, 0, 128}, 3, 2, true, nullptr, 0, nullptr);                // 5
-    ok = ok && add_c2f(y, Slice{b5, 0, 128}, Slice{cat11, 256, 128}, 2, true);                     // 6 -> cat11[256:384]
-    CV(Slice{cat11, 256, 128}, Slice{b7, 0, 256}, 3, 2, true, nullptr, 0, nullptr);               // 7
-    ok = ok && add_c2f(y, Slice{b7, 0, 256}, Slice{b8, 0, 256}, 1, true);                          // 8
-    CV(Slice{b8, 0, 256}, Slice{spp, 0, 128}, 1, 1, true, nullptr, 0, nullptr);                   // 9 SPPF cv1
+    if (y.f32) CV(Slice{x0, 0, 4}, Slice{b0, 0, c1}, 3, 2, true, nullptr, 0, nullptr);           // 0 (4-channel input, fourth channel zero)
+    else ok = ok && add_stem(y, Slice{x0, 0, 4}, Slice{b0, 0, c1});                               // 0
+    CV(Slice{b0, 0, c1}, Slice{b1, 0, c2}, 3, 2, true, nullptr, 0, nullptr);                      // 1
+    ok = ok && add_c2f(y, Slice{b1, 0, c2}, Slice{b2, 0, c2}, m.rep[0], true);                     // 2
+    CV(Slice{b2, 0, c2}, Slice{b3, 0, c3}, 3, 2, true, nullptr, 0, nullptr);                      // 3
+    ok = ok && add_c2f(y, Slice{b3, 0, c3}, Slice{cat14, c4, c3}, m.rep[1], true);                 // 4 -> cat14[c4:]
+    CV(Slice{cat14, c4, c3}, Slice{b5, 0, c4}, 3, 2, true, nullptr, 0, nullptr);                  // 5
+    ok = ok && add_c2f(y, Slice{b5, 0, c4}, Slice{cat11, c5, c4}, m.rep[2], true);                 // 6 -> cat11[c5:]
+    CV(Slice{cat11, c5, c4}, Slice{b7, 0, c5}, 3, 2, true, nullptr, 0, nullptr);                  // 7
+    ok = ok && add_c2f(y, Slice{b7, 0, c5}, Slice{b8, 0, c5}, m.rep[3], true);                     // 8
+    CV(Slice{b8, 0, c5}, Slice{spp, 0, cs}, 1, 1, true, nullptr, 0, nullptr);                     // 9 SPPF cv1
     if (y.f32) {
-        for (int i = 0; i < 3; ++i) add_simple(y, OP_MAXPOOL, Slice{spp, 128 * i, 128}, Slice{spp, 128 * (i + 1), 128}, H / 32, W / 32, 128);
+        for (int i = 0; i < 3; ++i) add_simple(y, OP_MAXPOOL, Slice{spp, cs * i, cs}, Slice{spp, cs * (i + 1), cs}, H / 32, W / 32, cs);
     } else {                                               // all three pools from one LDS copy of the map (at most 20 x 20 pixels: letterbox())
         ok = ok && (H / 32) * (W / 32) <= 1024;
-        add_simple(y, OP_POOLS, Slice{spp, 0, 128}, Slice{spp, 128, 384}, H / 32, W / 32, 128);
+        add_simple(y, OP_POOLS, Slice{spp, 0, cs}, Slice{spp, cs, 3 * cs}, H / 32, W / 32, cs);
     }
-    CV(Slice{spp, 0, 512}, Slice{cat20, 128, 256}, 1, 1, true, nullptr, 0, nullptr);              // 9 SPPF cv2 -> cat20[128:384]
-    add_simple(y, OP_UPSAMPLE, Slice{cat20, 128, 256}, Slice{cat11, 0, 256}, H / 32, W / 32, 256); // 10 upsample -> cat11[0:256]
+    CV(Slice{spp, 0, 4 * cs}, Slice{cat20, c4, c5}, 1, 1, true, nullptr, 0, nullptr);             // 9 SPPF cv2 -> cat20[c4:]
+    add_simple(y, OP_UPSAMPLE, Slice{cat20, c4, c5}, Slice{cat11, 0, c5}, H / 32, W / 32, c5);     // 10 upsample -> cat11[:c5]
     y.ops.back().vcat = (int)y.ops.size();                                                          // (its only reader: layer 12's cv1, the next op)
-    ok = ok && add_c2f(y, Slice{cat11, 0, 384}, Slice{cat17, 64, 128}, 1, false);                  // 12 -> cat17[64:192]
-    add_simple(y, OP_UPSAMPLE, Slice{cat17, 64, 128}, Slice{cat14, 0, 128}, H / 16, W / 16, 128);  // 13 upsample -> cat14[0:128]
+    ok = ok && add_c2f(y, Slice{cat11, 0, c5 + c4}, Slice{cat17, c3, c4}, nr, false);              // 12 -> cat17[c3:]
+    add_simple(y, OP_UPSAMPLE, Slice{cat17, c3, c4}, Slice{cat14, 0, c4}, H / 16, W / 16, c4);     // 13 upsample -> cat14[:c4]
     y.ops.back().vcat = (int)y.ops.size();                                                          // (layer 15's cv1)
-    ok = ok && add_c2f(y, Slice{cat14, 0, 192}, Slice{p3, 0, 64}, 1, false);                       // 15
-    CV(Slice{p3, 0, 64}, Slice{cat17, 0, 64}, 3, 2, true, nullptr, 0, nullptr);                   // 16 -> cat17[0:64]
-    ok = ok && add_c2f(y, Slice{cat17, 0, 192}, Slice{p4, 0, 128}, 1, false);                      // 18
-    CV(Slice{p4, 0, 128}, Slice{cat20, 0, 128}, 3, 2, true, nullptr, 0, nullptr);                 // 19 -> cat20[0:128]
-    ok = ok && add_c2f(y, Slice{cat20, 0, 384}, Slice{p5, 0, 256}, 1, false);                      // 21
-    const int pl[3] = {p3, p4, p5}, pc[3] = {64, 128, 256}, dv[3] = {8, 16, 32};
+    ok = ok && add_c2f(y, Slice{cat14, 0, c4 + c3}, Slice{p3, 0, c3}, nr, false);                  // 15
+    CV(Slice{p3, 0, c3}, Slice{cat17, 0, c3}, 3, 2, true, nullptr, 0, nullptr);                   // 16 -> cat17[:c3]
+    ok = ok && add_c2f(y, Slice{cat17, 0, c3 + c4}, Slice{p4, 0, c4}, nr, false);                  // 18
+    CV(Slice{p4, 0, c4}, Slice{cat20, 0, c4}, 3, 2, true, nullptr, 0, nullptr);                   // 19 -> cat20[:c4]
+    ok = ok && add_c2f(y, Slice{cat20, 0, c4 + c5}, Slice{p5, 0, c5}, nr, false);                  // 21
+    const int pl[3] = {p3, p4, p5}, pc[3] = {c3, c4, c5}, dv[3] = {8, 16, 32};
     y.A = 0;
-    for (int i = 0; i < 3 && ok; ++i) {
+    for (int i = 0; i < 3 && ok; ++i) {                                                            // 22 Detect
         const int hh = H / dv[i], ww = W / dv[i];
         y.lvH[i] = hh, y.lvW[i] = ww;
-        const int ba = nb(hh, ww, 64), bb = nb(hh, ww, 64), ca = nb(hh, ww, NC), cb = nb(hh, ww, NC);
-        ok = ok && dev_alloc(y, (void**)&y.head_box[i], (size_t)batch * hh * ww * 64 * 4);
-        ok = ok && dev_alloc(y, (void**)&y.head_cls[i], (size_t)batch * hh * ww * NC * 4);
+        // the class branch at its padded widths: zero filters and biases behind the real ones (Slice::real), so a padded hidden
+        // channel is silu(0) = 0 and a padded logit 0.0f
+        const int ba = nb(hh, ww, hb), bb = nb(hh, ww, hb), ca = nb(hh, ww, hcp), cb = nb(hh, ww, hcp);
+        ok = ok && dev_alloc(y, (void**)&y.head_box[i], (size_t)batch * hh * ww * 4 * REG_MAX * 4);
+        ok = ok && dev_alloc(y, (void**)&y.head_cls[i], (size_t)batch * hh * ww * ncp * 4);
         if (!ok) break;
         if (i == 0) y.head_begin = (int)y.ops.size();
-        CV(Slice{pl[i], 0, pc[i]}, Slice{ba, 0, 64}, 3, 1, true, nullptr, 0, nullptr);
-        CV(Slice{ba, 0, 64}, Slice{bb, 0, 64}, 3, 1, true, nullptr, 0, nullptr);
-        CV(Slice{bb, 0, 64}, Slice{-1, 0, 64}, 1, 1, false, y.head_box[i], 64, nullptr);
+        CV(Slice{pl[i], 0, pc[i]}, Slice{ba, 0, hb}, 3, 1, true, nullptr, 0, nullptr);
+        CV(Slice{ba, 0, hb}, Slice{bb, 0, hb}, 3, 1, true, nullptr, 0, nullptr);
+        CV(Slice{bb, 0, hb}, Slice{-1, 0, 4 * REG_MAX}, 1, 1, false, y.head_box[i], 4 * REG_MAX, nullptr);
         if (ok) y.ops.back().dec = 1, y.ops.back().dec_level = i;
         const size_t cls_first = y.ops.size();
-        CV(Slice{pl[i], 0, pc[i]}, Slice{ca, 0, NC}, 3, 1, true, nullptr, 0, nullptr);
-        CV(Slice{ca, 0, NC}, Slice{cb, 0, NC}, 3, 1, true, nullptr, 0, nullptr);
-        CV(Slice{cb, 0, NC}, Slice{-1, 0, NC}, 1, 1, false, y.head_cls[i], NC, nullptr);
+        CV(Slice{pl[i], 0, pc[i]}, Slice{ca, 0, hcp, hc}, 3, 1, true, nullptr, 0, nullptr);
+        CV(Slice{ca, 0, hcp, hc}, Slice{cb, 0, hcp, hc}, 3, 1, true, nullptr, 0, nullptr);
+        CV(Slice{cb, 0, hcp, hc}, Slice{-1, 0, ncp, nc}, 1, 1, false, y.head_cls[i], ncp, nullptr);
         if (ok) y.ops.back().dec = 2, y.ops.back().dec_level = i;
         for (size_t q = cls_first; q < y.ops.size(); ++q) y.ops[q].lane = 1;       // own buffers, independent of the box branch
         y.A += hh * ww;
@@ -2574,9 +2621,9 @@ int build_graph(Yolo& y) {
     ok = ok && dev_alloc(y, (void**)&y.cbox, (size_t)batch * y.A * 16) && dev_alloc(y, (void**)&y.cconf, (size_t)batch * y.A * 4) &&
          dev_alloc(y, (void**)&y.ccls, (size_t)batch * y.A * 4) && dev_alloc(y, (void**)&y.sbox, (size_t)batch * y.A * 16) &&
          dev_alloc(y, (void**)&y.sidx, (size_t)batch * y.A * 4) && dev_alloc(y, (void**)&y.scount, (size_t)batch * 4);
-    y.named = {{0, Slice{x0, 0, 3}}, {1, Slice{b1, 0, 32}}, {2, Slice{b2, 0, 32}}, {4, Slice{cat14, 128, 64}},
-               {6, Slice{cat11, 256, 128}}, {8, Slice{b8, 0, 256}}, {9, Slice{cat20, 128, 256}}, {12, Slice{cat17, 64, 128}},
-               {15, Slice{p3, 0, 64}}, {18, Slice{p4, 0, 128}}, {21, Slice{p5, 0, 256}}, {7, Slice{b7, 0, 256}}, {19, Slice{cat20, 0, 128}}};
+    y.named = {{0, Slice{x0, 0, 3}}, {1, Slice{b1, 0, c2}}, {2, Slice{b2, 0, c2}}, {4, Slice{cat14, c4, c3}},
+               {6, Slice{cat11, c5, c4}}, {8, Slice{b8, 0, c5}}, {9, Slice{cat20, c4, c5}}, {12, Slice{cat17, c3, c4}},
+               {15, Slice{p3, 0, c3}}, {18, Slice{p4, 0, c4}}, {21, Slice{p5, 0, c5}}, {7, Slice{b7, 0, c5}}, {19, Slice{cat20, 0, c4}}};
     if (y.dbg_cat >= 0) y.named.push_back({40, Slice{y.dbg_cat, 0, y.bufs[y.dbg_cat].C}});
     y.wsrc = nullptr;
     AV_REQUIRE(ok, AV_EINVAL, "av_yolo_create: graph construction failed (parameter blob / capacity mismatch)");
@@ -2591,6 +2638,7 @@ int use_variant(Step& s, Family fam, const int (&p)[6], dim3 grid, dim3 block, s
     AV_REQUIRE(v, AV_EINVAL, "av_yolo: no kernel of family %d for <%d,%d,%d,%d,%d,%d>", (int)fam, p[0], p[1], p[2], p[3], p[4], p[5]);
     AV_REQUIRE(lds <= (size_t)std::max(v->lds_limit, 64 * 1024), AV_EINVAL, "av_yolo: %zu bytes of LDS for a kernel limited to %d", lds, v->lds_limit);
     s.fn = v->fn, s.grid = grid, s.block = block, s.lds = lds;
+    s.fam = fam, std::copy(p, p + 6, s.var);
     return AV_OK;
 }
 
@@ -2606,8 +2654,8 @@ int choose_conv(const ConvArgs& a, int mt, int dec, const DecArgs& dec_args, int
         const int tiles_x = (a.Wo + LT_W - 1) / LT_W, tiles_y = (a.Ho + LT_H - 1) / LT_H, taps = a.ksz * a.ksz;
         const int PH = (LT_H - 1) * a.stride + a.ksz, PW = (LT_W - 1) * a.stride + a.ksz;
         s.args(a, tiles_x, tiles_y);
-        return use_variant(s, K_LDS, {mt, a.ksz}, dim3(tiles_x * tiles_y * B, gy), dim3(256),
-                           (((size_t)PH * PW * LT_PIXB + 15) & ~size_t(15)) + (size_t)16 * mt * (taps * LT_CK * 2 + 32));
+        return use_variant(s, K_LDS, {mt, a.ksz, a.stride == 1 ? 0 : a.stride}, dim3(tiles_x * tiles_y * B, gy), dim3(256),
+                           (((size_t)PH * PW * lt_pixb(a.stride) + 15) & ~size_t(15)) + (size_t)16 * mt * (taps * LT_CK * 2 + 32));
     };
     // 1x1 with cin a multiple of 64 and cout of 128 (the cv1 / cv2 of the P4 and P5 blocks, SPPF; layer 12's cv1 with both its sources): a
     // GEMM over flattened pixels.  Measured against conv1x1_ws_kernel / conv_lds_kernel on all eleven such layers at 64 frames: 7.0-15.6
@@ -2623,16 +2671,23 @@ int choose_conv(const ConvArgs& a, int mt, int dec, const DecArgs& dec_args, int
                            (((size_t)64 * ws_stride(128) + 15) & ~size_t(15)) + (size_t)2 * 16 * DEC_ROW * sizeof(float));
     }
     const bool generic80 = a.cin == 80 && hk.generic80;
-    if (one && a.cin == 80 && a.cout == 80 && mt == 5 && !a.res && !generic80) {
+    if (one && a.cin == 80 && a.cout == 80 && mt == 5 && !a.res && !generic80) {      // (dec: 2 or 0 here -- 3 needs whole 32-channel steps)
         s.args(a, n32, dec_args);
         return use_variant(s, K_WS1, {5, 2, true, dec == 2 ? 2 : 0}, dim3((unsigned)std::max(1, std::min((n32 + 3) / 4, 1024))), dim3(256),
                            (size_t)80 * ws_stride(160));
+    }
+    // the class branch's last convolution of any other model, nc at run time: all 16 mt >= nc output channels in one workgroup
+    if (dec == 3) {
+        s.args(a, n32, dec_args);
+        return use_variant(s, K_WS1, {mt, a.cin / 32, false, 3}, dim3((unsigned)std::max(1, std::min((n32 + 3) / 4, 1024))), dim3(256),
+                           (size_t)16 * mt * ws_stride(a.cin * 2));
     }
     if (gemm1x1) return gemm128();
     // 1x1 with whole 32-channel steps: weights resident in LDS, pixel fragments straight from global memory
     if (one && a.cin % 32 == 0 && !a.res && (mt == 2 || mt == 4)) {
         const int ks = a.cin / 32;
-        const bool ks_ok = ks == 1 || ks == 2 || ks == 3 || ks == 4 || ks == 6 || ks == 8 || ks == 12 || ks == 16;
+        const int want[6] = {mt, ks, 0, 0, 0, 0};
+        const bool ks_ok = find_variant(K_WS1, want) != nullptr;       // (listed: mt 2 with ks 1; mt 4 with ks 2, 3, 4, 6, 8, 12, 16)
         // measured per layer at 64 frames (profiles/README.md): wins on the small maps (P5 any cin, P4 up to 192 channels) and for
         // cin <= 64 anywhere; the big maps with long K stay with conv_lds_kernel, which is within 20 % of their HBM floor
         const bool pays = a.npix <= 20000 || (a.npix <= 70000 && ks <= 6) || ks <= 2;
@@ -2646,7 +2701,7 @@ int choose_conv(const ConvArgs& a, int mt, int dec, const DecArgs& dec_args, int
     // weight-stationary persistent kernel for the stride-2 layers whose weights fit (cin <= 64): 8 x 16 output tiles, 17 x 33 patches
     if (a.stride == 2 && a.ksz == 3 && a.cin % 8 == 0 && !a.res) {
         const int cp = (a.cin + 31) & ~31;
-        if ((cp == 32 && (mt == 2 || mt == 4)) || (cp == 64 && mt == 4)) {
+        if ((cp == 32 && (mt == 2 || mt == 4)) || (cp == 64 && (mt == 4 || mt == 3))) {
             const size_t lds = (((size_t)16 * mt * ws_stride(9 * cp * 2) + 15) & ~size_t(15)) + (size_t)17 * 33 * (cp * 2 + 16);
             const int tiles_x = (a.Wo + LT_W - 1) / LT_W, tiles_y = (a.Ho + 7) / 8, n_tiles = tiles_x * tiles_y * B;
             const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, (160 * 1024) / lds));
@@ -2657,7 +2712,7 @@ int choose_conv(const ConvArgs& a, int mt, int dec, const DecArgs& dec_args, int
     // the same for 3x3 stride 1: the whole weight matrix + one all-channel patch in LDS
     const int cinp = a.cin == 80 ? 80 : (a.cin + 31) & ~31;       // channels per pixel in the LDS image
     const bool ws_shape = a.stride == 1 && a.ksz == 3 && a.cin % 8 == 0 && a.cout == 16 * mt &&
-                          ((cinp == 32 && mt <= 2) || (cinp == 64 && (mt == 4 || mt == 5)) || (cinp == 80 && mt == 5));
+                          ((cinp == 32 && mt <= 2) || (cinp == 64 && (mt == 4 || mt == 5 || mt == 3)) || (cinp == 80 && mt == 5));
     if (ws_shape && !generic80) {
         const long tiles16 = (long)((a.Wo + LT_W - 1) / LT_W) * ((a.Ho + 15) / 16) * B;
         auto lds_of = [&](int tr) {
@@ -2674,24 +2729,35 @@ int choose_conv(const ConvArgs& a, int mt, int dec, const DecArgs& dec_args, int
     }
     // measured per layer (profiles/r01_yolo_b64_*): the LDS kernel wins for stride-1 3x3 (any cin >= 16, the tail of
     // a partial 32-channel chunk is zero-filled) and for 1x1 with whole chunks
-    if (a.stride == 1 && ((a.ksz == 3 && a.cin >= 16 && a.cin % 8 == 0) || (a.ksz == 1 && a.cin % LT_CK == 0))) return lds_tiled();
-    // the two cin = 128 stride-2 layers
-    if (a.ksz == 3 && a.stride == 2 && a.cin == 128 && a.cout % 128 == 0 && !a.res && a.kreal == 9 * a.cin && !hk.no_gemm) return gemm128();
+    // (1x1 with a partial last chunk: the kernel zero-fills it like the 3x3 form's; taken for the widths a padded class branch brings,
+    // 112 and up -- cin = 48 and 80, scale n's, stay on the kernels they are pinned to bit for bit)
+    const bool whole_or_wide = a.cin % LT_CK == 0 || (a.cin % 16 == 0 && a.cin > 96 && !split);
+    if (a.stride == 1 && ((a.ksz == 3 && a.cin >= 16 && a.cin % 8 == 0) || (a.ksz == 1 && whole_or_wide))) return lds_tiled();
+    // the long-K stride-2 layers (scale n: the two with cin = 128; s: 256 -> 512 / 256; m: 192 -> 384, 384 -> 384): the GEMM form where its
+    // tile fits (cin in whole 64-channel steps, cout in 128-channel tiles) ...
+    const bool gemm_s2 = a.ksz == 3 && a.stride == 2 && a.cin % CG_SC == 0 && a.cout % 128 == 0 && !a.res && a.kreal == 9 * a.cin;
+    if (gemm_s2 && !hk.no_gemm) return gemm128();
+    // ... and conv_lds_kernel's stride-2 form for the other 64-channel-tiled ones (m: 96 -> 192, 384 -> 576, 192 -> 192)
+    if (a.ksz == 3 && a.stride == 2 && a.cin % 8 == 0 && mt == 4 && !a.res && !gemm_s2) return lds_tiled();
     s.args(a);
     return use_variant(s, K_MFMA, {mt, 2}, dim3((a.npix + 16 * 2 * 4 - 1) / (16 * 2 * 4), gy), dim3(256), 0);
 }
 
 // the same for the float32 chain: the LDS-tiled GEMM form for every layer but the stem (cin = 4)
-int choose_conv_f32(const ConvArgsF& a, int mt, Step& s) {
+int choose_conv_f32(const ConvArgsF& a, Step& s) {
     s.args(a);
-    if ((a.cout % 128 == 0 || a.cout == 64 || a.cout == 80 || a.cout == 32 || a.cout == 16) && a.cin % 16 == 0) {
-        const int AR = a.cout % 128 == 0 ? 128 : a.cout, BR = AR == 128 ? 64 : 128, KC = a.cin % 32 == 0 ? 32 : 16;
+    if (a.cin % 16 == 0) {
+        // channel tile: the widest of 128, 80, 64, 48, 32, 16 that divides cout (48: scale m's 48 / 96 / 288; 16: a padded class count)
+        int AR = 16;
+        for (int t : {32, 48, 64, 80, 128})
+            if (a.cout % t == 0) AR = t;
+        const int BR = AR == 128 ? 64 : 128, KC = a.cin % 32 == 0 ? 32 : 16;
         return use_variant(s, K_GEMM_F32, {AR, BR, KC}, dim3((a.npix + BR - 1) / BR, a.cout / AR), dim3(256), (size_t)2 * (AR + BR) * (KC * 4 + 32));
     }
-    AV_REQUIRE(a.cin == 4 && a.cout == 16 * mt, AV_EINVAL, "av_yolo: no float32 kernel for a convolution %d -> %d", a.cin, a.cout);
-    // pixels per wave (16 NT): small maps need small tiles to fill the chip
+    AV_REQUIRE(a.cin == 4 && a.cout % 16 == 0, AV_EINVAL, "av_yolo: no float32 kernel for a convolution %d -> %d", a.cin, a.cout);
+    // the stem (K = 27), in 16-channel tiles at every scale; pixels per wave (16 NT): small maps need small tiles to fill the chip
     const int nt = a.npix >= 200000 ? 4 : (a.npix >= 50000 ? 2 : 1);
-    return use_variant(s, K_STEM_F32, {mt, nt, 4, 2}, dim3((a.npix + 64 * nt - 1) / (64 * nt), 1), dim3(256), 0);
+    return use_variant(s, K_STEM_F32, {1, nt, 4, 2}, dim3((a.npix + 64 * nt - 1) / (64 * nt), a.cout / 16), dim3(256), 0);
 }
 
 // the 1x1 convolution cv can fetch its first channels from upsample op's half-resolution source itself
@@ -2720,9 +2786,13 @@ C2f32Args c2f32_args(const ConvArgs& c1, const ConvArgs& b1, const ConvArgs& b2,
 // Every launch of a forward from the frame to the head's candidates (float32: to its logits), in order.  Which kernel runs a layer
 // depends on the layer shapes and the batch (fixed at create), the hooks and keep_logits -- and on the frame pointer's alignment,
 // for which the plan holds both forms of the front (Step::when).
-int plan_forward(const Yolo& y, Hooks hk, bool keep_logits, std::vector<Step>& plan) {
+// decode_alone: the head has no decode epilogue for this model's shapes -- its last convolutions write float32 logits and the stand-alone
+// decode_kernel makes the candidates (always so in the float32 chain).  Epilogues exist for a 64 -> 64 box convolution together with a class
+// convolution of 80 -> 80 with nc = 80 (compile-time count) or hc -> 16 mt >= nc with a conv1x1_ws_kernel<mt, hc / 32, false, 3> in kVariants.
+int plan_forward(const Yolo& y, Hooks hk, bool keep_logits, std::vector<Step>& plan, bool& decode_alone) {
     const int B = y.B, n = B * y.H * y.W;
     plan.clear();
+    decode_alone = true;
     auto add = [&](When when = ALWAYS) -> Step& {
         plan.emplace_back();
         plan.back().when = when;
@@ -2737,9 +2807,11 @@ int plan_forward(const Yolo& y, Hooks hk, bool keep_logits, std::vector<Step>& p
         // reference-precision chain: one lane, one launch per layer, float32 logits, stand-alone decode
         preprocess(preprocess_f32_kernel, n, ALWAYS, reinterpret_cast<float*>(y.bufs[0].p));
         for (const Yolo::Op& op : y.ops) {
+            const int k = (int)(&op - y.ops.data());
             if (op.kind == OP_CONV_F32) {
-                const int rc = choose_conv_f32(op.cf, op.mt, add());
+                const int rc = choose_conv_f32(op.cf, add());
                 if (rc != AV_OK) return rc;
+                plan.back().first_op = k, plan.back().n_ops = 1;
                 continue;
             }
             AV_REQUIRE(op.kind == OP_MAXPOOL || op.kind == OP_UPSAMPLE, AV_EINVAL, "av_yolo: op kind %d has no float32 form", (int)op.kind);
@@ -2747,9 +2819,23 @@ int plan_forward(const Yolo& y, Hooks hk, bool keep_logits, std::vector<Step>& p
             const int threads = op.kind == OP_MAXPOOL ? B * op.H * op.W * op.C : B * 4 * op.H * op.W * (op.C / 4);
             add().kernel(op.kind == OP_MAXPOOL ? maxpool5_f32_kernel : upsample2_f32_kernel, dim3((threads + 255) / 256), dim3(256), 0,
                          reinterpret_cast<const float*>(bi.p), bi.C, op.in.coff, reinterpret_cast<float*>(bo.p), bo.C, op.out.coff, B, op.H, op.W, op.C);
+            plan.back().first_op = k, plan.back().n_ops = 1;
         }
         return AV_OK;
     }
+    // which decode epilogue the head's last convolutions have (the three levels share their shapes)
+    auto cls_epilogue = [&](const Yolo::Op& o) {
+        const ConvArgs& a = o.ca;
+        if (a.cin == 80 && a.cout == 80 && o.mt == 5 && y.model.nc == NC) return 2;
+        const int p[6] = {o.mt, a.cin / 32, 0, 3, 0, 0};
+        return a.cin % 32 == 0 && a.cout == 16 * o.mt && find_variant(K_WS1, p) ? 3 : 0;
+    };
+    int epilogue = 0;
+    for (const Yolo::Op& o : y.ops) {
+        if (o.dec == 1 && !(o.ca.cin == 64 && o.ca.cout == 64 && o.mt == 4)) break;
+        if (o.dec == 2) { epilogue = cls_epilogue(o); break; }
+    }
+    decode_alone = epilogue == 0;
     // the 2:1 letterbox kernels read dwords: they need a 4-byte aligned frame pointer
     const bool twice = y.inH == 2 * y.nh && y.inW == 2 * y.nw && y.inW % 4 == 0 && y.left % 2 == 0 && y.nw % 2 == 0 && y.W % 2 == 0 && !hk.generic_pre;
     // letterbox + stem + layer 1 in one launch (front_fused_kernel); with keep_logits (test hook) the three launches run, so that
@@ -2766,7 +2852,7 @@ int plan_forward(const Yolo& y, Hooks hk, bool keep_logits, std::vector<Step>& p
         static_assert(offsetof(FrontArgs, bgr) == 0, "Step::takes_bgr");
         Step& s = add(BGR_ALIGNED);
         s.kernel(front_fused_kernel, dim3((unsigned)std::min(fa.n_tiles, 512)), dim3(FR_NTH), FR_LDS, fa);
-        s.takes_bgr = true;
+        s.takes_bgr = true, s.first_op = 0, s.n_ops = 2;
     } else if (twice) {
         preprocess(preprocess2_kernel, n / 2, BGR_ALIGNED, y.bufs[0].p);
     }
@@ -2779,15 +2865,19 @@ int plan_forward(const Yolo& y, Hooks hk, bool keep_logits, std::vector<Step>& p
         const size_t at = oi, first = plan.size();
         auto conv = [&](const Yolo::Op& o, const ConvArgs& a) {
             DecArgs dec{};
-            if (o.dec) {
+            const int epi = !o.dec || !epilogue ? 0 : (o.dec == 1 ? 1 : epilogue);
+            if (epi) {
                 int aoff = 0;
                 for (int i = 0; i < o.dec_level; ++i) aoff += y.lvH[i] * y.lvW[i];
-                dec = DecArgs{y.cbox, y.cconf, y.ccls, y.A, aoff, 8 << o.dec_level, keep_logits ? 1 : 0};
+                dec = DecArgs{y.cbox, y.cconf, y.ccls, y.A, aoff, 8 << o.dec_level, keep_logits ? 1 : 0, y.model.nc};
             }
-            return choose_conv(a, o.mt, o.dec, dec, B, hk, add());
+            const int rc = choose_conv(a, o.mt, epi, dec, B, hk, add());
+            plan.back().first_op = (int)(&o - y.ops.data()), plan.back().n_ops = 1;
+            return rc;
         };
         auto c2f32 = [&](auto kernel, size_t lds, const C2f32Args& fa) {
             add().kernel(kernel, dim3((unsigned)std::min(fa.n_tiles, 256)), dim3(F32_NTH), lds, fa);
+            plan.back().n_ops = 3;                         // a bottleneck pair + the 1x1 convolution on one of its sides
         };
         int rc = AV_OK;
         if (op.fuse == 1 && !hk.no_fuse) {                 // cv1, 3x3, 3x3 + shortcut, cv2 in one launch
@@ -2801,6 +2891,7 @@ int plan_forward(const Yolo& y, Hooks hk, bool keep_logits, std::vector<Step>& p
             fa.bs_cv1 = c1.bias, fa.bs_b1 = b1.bias, fa.bs_b2 = b2.bias, fa.bs_cv2 = c2.bias;
             fa.kb = b1.kpad, fa.kc = c2.kpad;
             add().kernel(c2f16_fused_kernel, dim3((unsigned)std::min(fa.n_tiles, 512)), dim3(C2F_NTH), C2F_LDS, fa);
+            plan.back().first_op = (int)at, plan.back().n_ops = 4;
             oi += 3;
         } else if (op.kind == OP_UPSAMPLE && op.vcat == (int)oi + 1 && !hk.no_fuse && reads_upsample(y, op, y.ops[oi + 1])) {
             // virtual Upsample + Concat: the upsample launch is skipped and its only reader, a 1x1 convolution, fetches the first k1 input
@@ -2812,6 +2903,7 @@ int plan_forward(const Yolo& y, Hooks hk, bool keep_logits, std::vector<Step>& p
             v.in = bi.p, v.in_cs = bi.C, v.in_coff = op.in.coff;                            // channels [0, k1): the upsample's source, half resolution
             v.in2 = c1.in, v.in2_cs = c1.in_cs, v.in2_coff = c1.in_coff + op.C, v.k1 = op.C;   // channels [k1, cin): the concat buffer's own part
             rc = conv(cv, v);
+            plan.back().first_op = (int)at, plan.back().n_ops = 2;       // the upsample and its reader
             oi += 1;
             const ConvArgs* c2 = cv.fuse == 3 ? &y.ops[oi + 3].ca : nullptr;
             if (rc == AV_OK && c2 && c2f32_shapes(c1, y.ops[oi + 1].ca, *c2, 1)) {
@@ -2820,6 +2912,7 @@ int plan_forward(const Yolo& y, Hooks hk, bool keep_logits, std::vector<Step>& p
                 fa.w_cv2 = c2->wgt, fa.bs_cv2 = c2->bias, fa.kc = c2->kpad;
                 fa.out = c2->out, fa.out_cs = c2->out_cs, fa.out_coff = c2->out_coff;
                 c2f32(c2f32_tail_kernel<64, false>, f32t_lds(64), fa);
+                plan.back().first_op = (int)oi + 1;
                 oi += 3;
             }
         } else if (op.fuse == 2 && !hk.no_fuse && op.ca.kpad == 64 && c2f32_shapes(op.ca, y.ops[oi + 1].ca, y.ops[oi + 5].ca, 2)) {
@@ -2829,15 +2922,19 @@ int plan_forward(const Yolo& y, Hooks hk, bool keep_logits, std::vector<Step>& p
             fh.in = c1.in, fh.in_cs = c1.in_cs, fh.in_coff = c1.in_coff;
             fh.w_cv1 = c1.wgt, fh.bs_cv1 = c1.bias, fh.k1 = c1.kpad;
             c2f32(c2f32_head_kernel, F32H_LDS, fh);
+            plan.back().first_op = (int)at;
             C2f32Args ft = c2f32_args(c1, y.ops[oi + 3].ca, y.ops[oi + 4].ca, 2, B);
             ft.w_cv2 = c2.wgt, ft.bs_cv2 = c2.bias, ft.kc = c2.kpad;
             ft.out = c2.out, ft.out_cs = c2.out_cs, ft.out_coff = c2.out_coff;
             c2f32(c2f32_tail_kernel<96, true>, f32t_lds(96), ft);
+            plan.back().first_op = (int)at + 3;
             oi += 5;
         } else if (op.kind == OP_CONV) {
             rc = conv(op, op.ca);
         } else if (op.kind == OP_STEM) {
-            add().kernel(stem_conv_kernel, dim3((op.ca.npix + 255) / 256), dim3(256), 0, op.ca, op.ca.npix);
+            if (op.ca.cout == 16) add().kernel(stem_conv_kernel<false>, dim3((op.ca.npix + 255) / 256), dim3(256), 0, op.ca, op.ca.npix);
+            else add().kernel(stem_conv_kernel<true>, dim3((op.ca.npix + 255) / 256, op.ca.cout / 16), dim3(256), 0, op.ca, op.ca.npix);
+            plan.back().first_op = (int)at, plan.back().n_ops = 1;
         } else {
             AV_REQUIRE(op.kind == OP_POOLS || op.kind == OP_UPSAMPLE, AV_EINVAL, "av_yolo: op kind %d has no half-precision form", (int)op.kind);
             const Buf &bi = y.bufs[op.in.buf], &bo = y.bufs[op.out.buf];
@@ -2848,6 +2945,7 @@ int plan_forward(const Yolo& y, Hooks hk, bool keep_logits, std::vector<Step>& p
             else
                 add().kernel(upsample2_kernel, dim3((B * 4 * hw * (op.C / 8) + 255) / 256), dim3(256), 0, bi.p, bi.C, op.in.coff, bo.p, bo.C,
                              op.out.coff, B, op.H, op.W, op.C);
+            plan.back().first_op = (int)at, plan.back().n_ops = 1;
         }
         if (rc != AV_OK) return rc;
         for (size_t q = first; q < plan.size(); ++q) {
@@ -2867,9 +2965,76 @@ extern "C" {
 
 int av_yolo_ctx_free(av_ctx*) { return AV_OK; }
 
+int av_yolo_model_preset(int scale_char, int nc, av_yolo_model* model) {
+    AV_REQUIRE(model, AV_EINVAL, "av_yolo_model_preset: null argument");
+    // yolov8.yaml: depth, width, max_channels per scale; channels = make_divisible(min(c, max_channels) width, 8), repeats = max(round(n depth), 1)
+    double depth, width;
+    int max_ch;
+    switch (scale_char) {
+    case 'n': depth = 0.33, width = 0.25, max_ch = 1024; break;
+    case 's': depth = 0.33, width = 0.50, max_ch = 1024; break;
+    case 'm': depth = 0.67, width = 0.75, max_ch = 768; break;
+    case 'l':
+    case 'x':
+        av_set_error("av_yolo_model_preset: scale '%c' is not built (n, s and m are)", scale_char);
+        return AV_EINVAL;
+    default:
+        av_set_error("av_yolo_model_preset: unknown scale character %d (n, s and m are built)", scale_char);
+        return AV_EINVAL;
+    }
+    AV_REQUIRE(nc >= 1 && nc <= 256, AV_EINVAL, "av_yolo_model_preset: nc = %d, 1 .. 256 are built", nc);
+    av_yolo_model m{};
+    const int base[5] = {64, 128, 256, 512, 1024}, reps[4] = {3, 6, 6, 3};
+    for (int i = 0; i < 5; ++i) m.ch[i] = (int)std::ceil(std::min(base[i], max_ch) * width / 8.0) * 8;
+    for (int i = 0; i < 4; ++i) m.rep[i] = std::max((int)std::nearbyint(reps[i] * depth), 1);
+    m.neck_rep = std::max((int)std::nearbyint(3 * depth), 1);
+    m.nc = nc;
+    *model = m;
+    return AV_OK;
+}
+
+namespace {
+// a model this library builds and tests: what av_yolo_model_preset gives for scale n, s or m with the model's nc, reserved words zero
+// (the struct is how the graph builder is told the model, not an invitation to other widths: their kernels are not listed)
+bool model_ok(const av_yolo_model& m) {
+    if (m.nc < 1 || m.nc > 256) return false;
+    for (char scale : {'n', 's', 'm'}) {
+        av_yolo_model p;
+        if (av_yolo_model_preset(scale, m.nc, &p) == AV_OK && memcmp(&p, &m, sizeof p) == 0) return true;
+    }
+    return false;
+}
+}  // namespace
+
+size_t av_yolo_model_param_count(const av_yolo_model* model) {
+    if (!model || !model_ok(*model)) return 0;
+    const av_yolo_model& m = *model;
+    size_t n = 0;
+    auto conv = [&](int cin, int cout, int k, bool bn) { n += (size_t)cout * cin * k * k + (bn ? 4 : 1) * (size_t)cout; };
+    auto c2f = [&](int cin, int cout, int r) {
+        const int c = cout / 2;
+        conv(cin, 2 * c, 1, true);
+        for (int i = 0; i < 2 * r; ++i) conv(c, c, 3, true);
+        conv((2 + r) * c, cout, 1, true);
+    };
+    const int c1 = m.ch[0], c2 = m.ch[1], c3 = m.ch[2], c4 = m.ch[3], c5 = m.ch[4];
+    conv(3, c1, 3, true), conv(c1, c2, 3, true), c2f(c2, c2, m.rep[0]), conv(c2, c3, 3, true), c2f(c3, c3, m.rep[1]);
+    conv(c3, c4, 3, true), c2f(c4, c4, m.rep[2]), conv(c4, c5, 3, true), c2f(c5, c5, m.rep[3]);
+    conv(c5, c5 / 2, 1, true), conv(2 * c5, c5, 1, true);
+    c2f(c5 + c4, c4, m.neck_rep), c2f(c4 + c3, c3, m.neck_rep), conv(c3, c3, 3, true), c2f(c3 + c4, c4, m.neck_rep);
+    conv(c4, c4, 3, true), c2f(c4 + c5, c5, m.neck_rep);
+    const int hb = std::max(16, std::max(c3 / 4, 4 * REG_MAX)), hc = std::max(c3, std::min(m.nc, 100));
+    for (int ch : {c3, c4, c5}) {
+        conv(ch, hb, 3, true), conv(hb, hb, 3, true), conv(hb, 4 * REG_MAX, 1, false);
+        conv(ch, hc, 3, true), conv(hc, hc, 3, true), conv(hc, m.nc, 1, false);
+    }
+    return n;
+}
+
 size_t av_yolo_param_count(void) {
-    // must equal oracle/yolo_ref.py: param_count()
-    return 3167776;
+    // the (n, 80) preset; must equal oracle/yolo_ref.py: param_count() = 3167776
+    av_yolo_model m;
+    return av_yolo_model_preset('n', NC, &m) == AV_OK ? av_yolo_model_param_count(&m) : 0;
 }
 
 int av_yolo_destroy(av_yolo* h) {
@@ -2890,15 +3055,26 @@ int av_yolo_create(av_ctx* ctx, int batch, int in_h, int in_w, const float* weig
 }
 
 int av_yolo_create_ex(av_ctx* ctx, int batch, int in_h, int in_w, const float* weights, size_t n_weights, int precision, av_yolo** out) {
-    AV_REQUIRE(ctx && weights && out, AV_EINVAL, "av_yolo_create: null argument");
+    av_yolo_model m;
+    const int rc = av_yolo_model_preset('n', NC, &m);
+    return rc != AV_OK ? rc : av_yolo_create_model(ctx, batch, in_h, in_w, &m, weights, n_weights, precision, out);
+}
+
+int av_yolo_create_model(av_ctx* ctx, int batch, int in_h, int in_w, const av_yolo_model* model, const float* weights, size_t n_weights,
+                         int precision, av_yolo** out) {
+    AV_REQUIRE(ctx && weights && out && model, AV_EINVAL, "av_yolo_create: null argument");
     AV_REQUIRE(precision == AV_YOLO_FP16 || precision == AV_YOLO_FP32, AV_EINVAL, "av_yolo_create_ex: unknown precision %d", precision);
     AV_REQUIRE(batch > 0 && in_h >= 32 && in_w >= 32, AV_EINVAL, "av_yolo_create: bad shape");
-    AV_REQUIRE(n_weights == av_yolo_param_count(), AV_EINVAL, "av_yolo_create: expected %zu parameters, got %zu",
-               av_yolo_param_count(), n_weights);
+    AV_REQUIRE(model_ok(*model), AV_EINVAL, "av_yolo_create_model: widths %d %d %d %d %d, repeats %d %d %d %d / %d, nc %d is not a preset of scale n, s or m with 1 .. 256 classes",
+               model->ch[0], model->ch[1], model->ch[2], model->ch[3], model->ch[4], model->rep[0], model->rep[1], model->rep[2], model->rep[3],
+               model->neck_rep, model->nc);
+    AV_REQUIRE(n_weights == av_yolo_model_param_count(model), AV_EINVAL, "av_yolo_create: expected %zu parameters, got %zu",
+               av_yolo_model_param_count(model), n_weights);
     AV_HIP(hipSetDevice(ctx->device));
     av_yolo* h = new (std::nothrow) av_yolo();
     AV_REQUIRE(h, AV_ENOMEM, "av_yolo_create: out of host memory");
     Yolo& y = h->y;
+    y.model = *model;
     y.ctx = ctx, y.B = batch, y.inH = in_h, y.inW = in_w, y.wsrc = weights, y.wtotal = n_weights;
     y.f32 = precision == AV_YOLO_FP32;
     letterbox(in_h, in_w, y.gain, y.nh, y.nw, y.top, y.left, y.H, y.W);
@@ -2912,7 +3088,7 @@ int av_yolo_create_ex(av_ctx* ctx, int batch, int in_h, int in_w, const float* w
             if (v.lds_limit) AV_HIP(hipFuncSetAttribute(v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds_limit));
         // the first plan: a shape that no kernel serves fails here, not at the first forward
         y.plan_hooks = read_hooks(), y.plan_keep_logits = y.keep_logits;
-        return plan_forward(y, y.plan_hooks, y.plan_keep_logits, y.plan);
+        return plan_forward(y, y.plan_hooks, y.plan_keep_logits, y.plan, y.decode_alone);
     }();
     if (rc != AV_OK) {
         av_yolo_destroy(h);
@@ -2920,6 +3096,12 @@ int av_yolo_create_ex(av_ctx* ctx, int batch, int in_h, int in_w, const float* w
     }
     (void)hipDeviceSynchronize();
     *out = h;
+    return AV_OK;
+}
+
+int av_yolo_model_of(const av_yolo* h, av_yolo_model* model) {
+    AV_REQUIRE(h && model, AV_EINVAL, "av_yolo_model_of: null argument");
+    *model = h->y.model;
     return AV_OK;
 }
 
@@ -2935,7 +3117,7 @@ int av_yolo_tensor(const av_yolo* h, int id, void** ptr, int* H, int* W, int* C,
     if (id >= 100 && id < 106) {            // head outputs (float32): 100+2i box, 101+2i cls
         const int i = (id - 100) / 2;
         *ptr = (id & 1) ? (void*)h->y.head_cls[i] : (void*)h->y.head_box[i];
-        *H = h->y.lvH[i], *W = h->y.lvW[i], *C = (id & 1) ? NC : 64, *cstride = *C, *coff = 0;
+        *H = h->y.lvH[i], *W = h->y.lvW[i], *C = (id & 1) ? h->y.model.nc : 4 * REG_MAX, *cstride = (id & 1) ? h->y.ncp : *C, *coff = 0;      // (channels [nc, cstride): 0.0f)
         return AV_OK;
     }
     if (id >= 110 && id < 113) {            // candidates written by the head's decode epilogues: box [A][4], confidence [A], class [A] (int32)
@@ -2982,8 +3164,9 @@ int av_yolo_op(const av_yolo* h, int k, av_yolo_op_info* info) {
     auto of_conv = [&](const auto& a) {
         o.kind = AV_YOLO_OP_CONV, o.ksz = a.ksz, o.stride = a.stride, o.act = a.act, o.cin = a.cin, o.cout = a.cout;
         o.in = av_yolo_slice{a.in, a.H, a.W, a.in_cs, a.in_coff, a.cin, f32};
-        o.out = av_yolo_slice{a.out, a.Ho, a.Wo, a.out_cs, a.out_coff, a.cout, f32};
-        if (a.res) o.res = av_yolo_slice{a.res, a.Ho, a.Wo, a.res_cs, a.res_coff, a.cout, f32};
+        o.cout = op.cout_real;                               // (a.cout counts the zero filters of a padded class branch too)
+        o.out = av_yolo_slice{a.out, a.Ho, a.Wo, a.out_cs, a.out_coff, o.cout, f32};
+        if (a.res) o.res = av_yolo_slice{a.res, a.Ho, a.Wo, a.res_cs, a.res_coff, o.cout, f32};
         o.wgt = a.wgt, o.bias = a.bias;
     };
     switch (op.kind) {
@@ -3014,6 +3197,31 @@ int av_yolo_op(const av_yolo* h, int k, av_yolo_op_info* info) {
     return AV_OK;
 }
 
+static_assert(sizeof(av_yolo_step_info) == 72 && sizeof(av_yolo_model) == 64, "what _native.py binds");
+static_assert(AV_YOLO_K_MFMA == K_MFMA && AV_YOLO_K_GEMM128 == K_GEMM128 && AV_YOLO_K_LDS == K_LDS && AV_YOLO_K_WS3 == K_WS3 && AV_YOLO_K_WS1 == K_WS1 &&
+              AV_YOLO_K_GEMM_F32 == K_GEMM_F32 && AV_YOLO_K_STEM_F32 == K_STEM_F32 && AV_YOLO_K_FIXED == K_FIXED, "family ids of avhot.h");
+static_assert(AV_YOLO_WHEN_ALWAYS == ALWAYS && AV_YOLO_WHEN_BGR_ALIGNED == BGR_ALIGNED && AV_YOLO_WHEN_BGR_UNALIGNED == BGR_UNALIGNED, "avhot.h");
+int av_yolo_plan_count(const av_yolo* h, int* n_steps) {
+    AV_REQUIRE(h && n_steps, AV_EINVAL, "av_yolo_plan_count: null argument");
+    *n_steps = (int)h->y.plan.size();
+    return AV_OK;
+}
+
+int av_yolo_plan_step(const av_yolo* h, int k, av_yolo_step_info* info) {
+    AV_REQUIRE(h && info, AV_EINVAL, "av_yolo_plan_step: null argument");
+    const std::vector<Step>& plan = h->y.plan;
+    AV_REQUIRE(k >= 0 && k < (int)plan.size(), AV_EINVAL, "av_yolo_plan_step: step %d of %d", k, (int)plan.size());
+    const Step& s = plan[k];
+    av_yolo_step_info o{};
+    o.family = s.fam, o.first_op = s.first_op, o.n_ops = s.n_ops, o.when = (int)s.when;
+    o.grid[0] = (int)s.grid.x, o.grid[1] = (int)s.grid.y, o.grid[2] = (int)s.grid.z;
+    o.block[0] = (int)s.block.x, o.block[1] = (int)s.block.y, o.block[2] = (int)s.block.z;
+    o.lds_bytes = (int)s.lds, o.lane = s.lane;
+    std::copy(s.var, s.var + 6, o.variant);
+    *info = o;
+    return AV_OK;
+}
+
 int av_yolo_forward(av_yolo* h, av_stream_t stream, const uint8_t* bgr, float conf_thres, float iou_thres, int max_det,
                     int32_t* det_n, float* det_box, float* det_conf, int32_t* det_cls) {
     AV_REQUIRE(h && bgr && det_n && det_box && det_conf && det_cls, AV_EINVAL, "av_yolo_forward: null argument");
@@ -3026,7 +3234,7 @@ int av_yolo_forward(av_yolo* h, av_stream_t stream, const uint8_t* bgr, float co
     const Hooks hk = read_hooks();
     if (y.plan.empty() || !(hk == y.plan_hooks) || y.keep_logits != y.plan_keep_logits) {
         y.plan_hooks = hk, y.plan_keep_logits = y.keep_logits;
-        const int rc = plan_forward(y, hk, y.keep_logits, y.plan);
+        const int rc = plan_forward(y, hk, y.keep_logits, y.plan, y.decode_alone);
         if (rc != AV_OK) {
             y.plan.clear();
             return rc;
@@ -3067,13 +3275,17 @@ int av_yolo_forward(av_yolo* h, av_stream_t stream, const uint8_t* bgr, float co
     }
     // The candidates (cbox / cconf / ccls) were written by the head's last convolutions.  With keep_logits the stand-alone
     // decode runs as well, from the float32 logits into buffers of its own: the test hook that shows the two are equal.
-    if (y.f32) {                                           // the float32 chain keeps its logits: the stand-alone decode IS its decode
-        hipLaunchKernelGGL(decode_kernel, dim3((B * y.A + 127) / 128), dim3(128), 0, st, lv[0], lv[1], lv[2], y.A, B, y.cbox, y.cconf, y.ccls);
+    // the 80-class model keeps its compile-time count; any other takes nc and the padded stride at run time
+    auto decode = [&](float* cbox, float* cconf, int* ccls) {
+        const auto kernel = y.model.nc == NC ? decode_kernel<NC> : decode_kernel<0>;
+        hipLaunchKernelGGL(kernel, dim3((B * y.A + 127) / 128), dim3(128), 0, st, lv[0], lv[1], lv[2], y.A, B, cbox, cconf, ccls, y.model.nc, y.ncp);
+    };
+    if (y.f32 || y.decode_alone) {                         // no decode epilogue (the float32 chain; head shapes without one): the stand-alone decode IS the decode
+        decode(y.cbox, y.cconf, y.ccls);
         AV_LAUNCH_CHECK();
-    } else
-    if (y.keep_logits) {
-        hipLaunchKernelGGL(decode_kernel, dim3((B * y.A + 127) / 128), dim3(128), 0, st, lv[0], lv[1], lv[2], y.A, B, y.dbg_cbox,
-                           y.dbg_cconf, y.dbg_ccls);
+    }
+    if (!y.f32 && y.keep_logits) {
+        decode(y.dbg_cbox, y.dbg_cconf, y.dbg_ccls);
         AV_LAUNCH_CHECK();
     }
     {

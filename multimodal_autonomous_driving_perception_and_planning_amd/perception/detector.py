@@ -40,8 +40,11 @@ class ObjectDetector:
                     5: (0, 255, 255), 6: (128, 0, 128), 7: (0, 128, 255)}
     DCAP = 8
 
-    def __init__(self, mode: str = "simulated", model_path: Optional[str] = None, device: int = 0):
+    def __init__(self, mode: str = "simulated", model_path: Optional[str] = None, device: int = 0, names=None):
+        """names: the YOLO model's class names (a list, or a dict by class id), for a checkpoint that carries none -- a fine-tuned
+        model with its own classes; default: the checkpoint's, COCO's for 80 classes, else "class<i>"."""
         self.mode = mode
+        self._names = names
         self.model = None
         self.frame_count = 0
         self._dev = Dev(device)
@@ -56,8 +59,8 @@ class ObjectDetector:
 
     def _load_yolo_model(self, model_path: str):
         try:
-            from .yolo import YoloV8n
-            self.model = YoloV8n(model_path, device=self._dev.index)
+            from .yolo import YoloV8
+            self.model = YoloV8(model_path, device=self._dev.index, names=self._names)
         except (ImportError, FileNotFoundError) as e:
             print("YOLO path unavailable (%s). Falling back to simulated mode." % e)
             self.mode = "simulated"

@@ -1,13 +1,14 @@
-"""YOLO-mode model for ObjectDetector (mode="yolo"): YOLOv8n topology on the library's MFMA conv path.
+"""YOLO-mode model for ObjectDetector (mode="yolo"): YOLOv8 Detect models of scales n, s and m with 1 .. 256 classes on the library's
+MFMA conv path (default: scale n, 80 classes).
 
-The reference calls ultralytics `YOLO("yolov8n.pt")(frame)` (detector.py:77-84,103-123); neither the
-package nor the weight file can be shipped, so this model takes its parameters from
-  * a YOLOv8n `state_dict` file with ultralytics' key names (`model.0.conv.weight`, `model.0.bn.running_mean`, ...,
-    `model.22.cv3.2.2.bias`): `.pt` / `.pth` / `.bin` read with `torch.load(weights_only=True)`, `.safetensors`, or an
+The reference calls ultralytics `YOLO(model_path)(frame)` on whatever checkpoint it is given, "yolov8n.pt" by default
+(detector.py:77-84,103-123); neither the package nor the weight file can be shipped, so this model takes its parameters from
+  * a YOLOv8 `state_dict` file with ultralytics' key names (`model.0.conv.weight`, `model.0.bn.running_mean`, ...,
+    `model.22.cv3.2.2.bias`), which decides scale and class count itself (infer_model): `.pt` / `.pth` / `.bin` read with `torch.load(weights_only=True)`, `.safetensors`, or an
     `.npz` of such arrays -- `torch.save(YOLO("yolov8n.pt").model.state_dict(), "yolov8n_sd.pt")` on a machine with
     ultralytics produces one (the pickled `DetectionModel` inside `yolov8n.pt` itself needs that package to load),
-  * a `.npy` / `.npz` file holding the flat float32 vector in the order of `conv_specs()`, or
-  * the pseudo path "random" / "random:<seed>" -> seeded He-normal weights with non-trivial BatchNorm
+  * a `.npy` / `.npz` file holding the flat float32 vector in the order of `conv_specs(scale, nc)`, or
+  * the pseudo path "random[:<seed>[:<scale>[:<nc>]]]" -> seeded He-normal weights with non-trivial BatchNorm
     statistics (BASELINE config 3: "random-init nano backbone").
 Any other path that does not exist raises FileNotFoundError, which ObjectDetector turns into the
 reference's graceful fallback to simulated mode.
@@ -41,23 +42,67 @@ def _c2f(c1, c2, n):
     return [(c1, 2 * c, 1, 1, True)] + [(c, c, 3, 1, True)] * (2 * n) + [((2 + n) * c, c2, 1, 1, True)]
 
 
-def conv_specs():
-    """[(cin, cout, k, stride, has_bn_act)] in execution order (yolov8.yaml, scale n)."""
-    s = [(3, 16, 3, 2, True), (16, 32, 3, 2, True)] + _c2f(32, 32, 1)
-    s += [(32, 64, 3, 2, True)] + _c2f(64, 64, 2) + [(64, 128, 3, 2, True)] + _c2f(128, 128, 2)
-    s += [(128, 256, 3, 2, True)] + _c2f(256, 256, 1) + [(256, 128, 1, 1, True), (512, 256, 1, 1, True)]
-    s += _c2f(384, 128, 1) + _c2f(192, 64, 1) + [(64, 64, 3, 2, True)] + _c2f(192, 128, 1)
-    s += [(128, 128, 3, 2, True)] + _c2f(384, 256, 1)
-    for ch in (64, 128, 256):
-        s += [(ch, 64, 3, 1, True), (64, 64, 3, 1, True), (64, 4 * REG_MAX, 1, 1, False)]
-        s += [(ch, NC, 3, 1, True), (NC, NC, 3, 1, True), (NC, NC, 1, 1, False)]
+# yolov8.yaml `scales`: depth, width, max_channels.  n, s and m are built; l and x are known so that they can be refused by name.
+SCALES = {"n": (0.33, 0.25, 1024), "s": (0.33, 0.50, 1024), "m": (0.67, 0.75, 768), "l": (1.00, 1.00, 512), "x": (1.00, 1.25, 512)}
+BUILT_SCALES = ("n", "s", "m")
+MAX_NC = 256
+
+
+def _check_model(scale, nc):
+    if scale not in SCALES:
+        raise ValueError("unknown YOLOv8 scale %r (n, s and m are built)" % (scale,))
+    if scale not in BUILT_SCALES:
+        raise ValueError("YOLOv8 scale %r is not built (n, s and m are)" % (scale,))
+    if not (isinstance(nc, (int, np.integer)) and 1 <= nc <= MAX_NC):
+        raise ValueError("nc = %r: 1 .. %d classes are built" % (nc, MAX_NC))
+
+
+def model_dims(scale="n", nc=NC):
+    """yolov8.yaml's rules for one scale: -> (stage widths c1..c5, C2f repeats of layers 2/4/6/8, repeats of the neck's C2f blocks,
+    hidden width of Detect's box branch, hidden width of its class branch).  Channels are make_divisible(min(c, max_channels) width,
+    8), repeats max(round(n depth), 1).  Any scale of SCALES (infer_model recognises l and x by these numbers)."""
+    depth, width, max_ch = SCALES[scale]
+    ch = tuple(int(-(-min(c, max_ch) * width // 8)) * 8 for c in (64, 128, 256, 512, 1024))
+    rep = tuple(max(round(n * depth), 1) for n in (3, 6, 6, 3))
+    return ch, rep, max(round(3 * depth), 1), max(16, ch[2] // 4, 4 * REG_MAX), max(ch[2], min(nc, 100))
+
+
+def native_model(scale="n", nc=NC):
+    """The library's av_yolo_model for (scale, nc) (av_yolo_model_preset)."""
+    m = nat.YoloModel()
+    nat.check(nat.lib().av_yolo_model_preset(ord(scale) if len(scale) == 1 else 0, int(nc), C.byref(m)))
+    return m
+
+
+def conv_specs(scale="n", nc=NC):
+    """[(cin, cout, k, stride, has_bn_act)] in execution order (yolov8.yaml)."""
+    _check_model(scale, nc)
+    (c1, c2, c3, c4, c5), rep, nr, hb, hc = model_dims(scale, nc)
+    s = [(3, c1, 3, 2, True), (c1, c2, 3, 2, True)] + _c2f(c2, c2, rep[0])
+    s += [(c2, c3, 3, 2, True)] + _c2f(c3, c3, rep[1]) + [(c3, c4, 3, 2, True)] + _c2f(c4, c4, rep[2])
+    s += [(c4, c5, 3, 2, True)] + _c2f(c5, c5, rep[3]) + [(c5, c5 // 2, 1, 1, True), (2 * c5, c5, 1, 1, True)]
+    s += _c2f(c5 + c4, c4, nr) + _c2f(c4 + c3, c3, nr) + [(c3, c3, 3, 2, True)] + _c2f(c3 + c4, c4, nr)
+    s += [(c4, c4, 3, 2, True)] + _c2f(c4 + c5, c5, nr)
+    for ch in (c3, c4, c5):
+        s += [(ch, hb, 3, 1, True), (hb, hb, 3, 1, True), (hb, 4 * REG_MAX, 1, 1, False)]
+        s += [(ch, hc, 3, 1, True), (hc, hc, 3, 1, True), (hc, nc, 1, 1, False)]
     return s
 
 
-def random_params(seed=0):
+def param_count(scale="n", nc=NC):
+    """Floats in the flat vector of conv_specs(scale, nc)."""
+    return sum(cout * cin * k * k + (4 if bn else 1) * cout for cin, cout, k, _, bn in conv_specs(scale, nc))
+
+
+def trainable_count(scale="n", nc=NC):
+    """The figure ultralytics prints: weights + two per BatchNorm channel + biases + the 16 constant DFL weights."""
+    return sum(cout * cin * k * k + (2 if bn else 1) * cout for cin, cout, k, _, bn in conv_specs(scale, nc)) + REG_MAX
+
+
+def random_params(seed=0, scale="n", nc=NC):
     rs = np.random.RandomState(seed)
     parts = []
-    for cin, cout, k, _, bn in conv_specs():
+    for cin, cout, k, _, bn in conv_specs(scale, nc):
         parts.append((rs.standard_normal((cout, cin, k, k)) * np.sqrt(2.0 / (cin * k * k))).astype(np.float32).ravel())
         if bn:
             parts += [rs.uniform(0.8, 1.2, cout).astype(np.float32), rs.uniform(-0.1, 0.1, cout).astype(np.float32),
@@ -67,41 +112,79 @@ def random_params(seed=0):
     return np.concatenate(parts)
 
 
-def ultralytics_layer_names():
-    """The module path of every convolution of conv_specs(), in that order, in ultralytics' YOLOv8n `state_dict`
+def ultralytics_layer_names(scale="n"):
+    """The module path of every convolution of conv_specs(scale), in that order, in ultralytics' YOLOv8 `state_dict`
     (`model.<layer>.…`; a Conv block holds `.conv.weight` + `.bn.{weight,bias,running_mean,running_var}`, the two plain
     Conv2d that end a Detect branch hold `.weight` + `.bias`) -- yolov8.yaml layer numbers, nn/modules/{conv,block,head}.py:
     C2f = cv1, m.<i>.cv1, m.<i>.cv2, cv2; SPPF = cv1, cv2; Detect = cv2.<level>.<0..2> (box), cv3.<level>.<0..2> (class)."""
+    _check_model(scale, NC)
+    _, rep, nr, _, _ = model_dims(scale)
+
     def c2f(layer, n):
         return (["%d.cv1" % layer] + [q for i in range(n) for q in ("%d.m.%d.cv1" % (layer, i), "%d.m.%d.cv2" % (layer, i))]
                 + ["%d.cv2" % layer])
-    names = ["0", "1"] + c2f(2, 1) + ["3"] + c2f(4, 2) + ["5"] + c2f(6, 2) + ["7"] + c2f(8, 1) + ["9.cv1", "9.cv2"]
-    names += c2f(12, 1) + c2f(15, 1) + ["16"] + c2f(18, 1) + ["19"] + c2f(21, 1)
+    names = ["0", "1"] + c2f(2, rep[0]) + ["3"] + c2f(4, rep[1]) + ["5"] + c2f(6, rep[2]) + ["7"] + c2f(8, rep[3]) + ["9.cv1", "9.cv2"]
+    names += c2f(12, nr) + c2f(15, nr) + ["16"] + c2f(18, nr) + ["19"] + c2f(21, nr)
     for lvl in range(3):
         names += ["22.cv2.%d.%d" % (lvl, j) for j in range(3)] + ["22.cv3.%d.%d" % (lvl, j) for j in range(3)]
     return names
 
 
-def params_from_state_dict(sd):
-    """Flat parameter vector (the order of conv_specs()) from a YOLOv8n `state_dict` with ultralytics' key names
-    (detector.py:77-84 loads such a model through `YOLO(model_path)`).  Keys may carry any number of leading `model.` /
-    `module.` prefixes; `num_batches_tracked` and the constant DFL convolution (`22.dfl.conv.weight`, arange(16)) are
-    ignored; every shape is checked.  BatchNorm is folded later by the library (eps 1e-3, ultralytics' Conv default)."""
+def _strip_prefixes(sd):
     import re
-    flat = {}
-    for k, v in sd.items():
-        k = re.sub(r"^(?:(?:model|module)\.)+", "", k)
-        flat[k] = v
-    specs, names = conv_specs(), ultralytics_layer_names()
+    return {re.sub(r"^(?:(?:model|module)\.)+", "", k): v for k, v in sd.items()}
+
+
+def infer_model(sd):
+    """(scale, nc) of a YOLOv8 Detect `state_dict`, read from its shapes: the rows of `0.conv.weight` (16 / 32 / 48 / 64 / 80 for n / s /
+    m / l / x), the `m.<i>` bottlenecks of layer 2 (they must be the scale's repeat count) and the rows of `22.cv3.0.2.weight` (nc).
+    ValueError naming the scale for l and x, which are not built; ValueError naming the key for anything that is not such a model."""
+    flat = _strip_prefixes(sd)
+
+    def rows(key):
+        if key not in flat:
+            raise ValueError("state_dict has no %r: not a YOLOv8 Detect model's state_dict" % ("model." + key))
+        shape = tuple(flat[key].shape)
+        if len(shape) != 4:
+            raise ValueError("%s has shape %s: not a YOLOv8 Detect model's state_dict" % ("model." + key, shape))
+        return shape[0]
+    c1 = rows("0.conv.weight")
+    by_width = {model_dims(s)[0][0]: s for s in SCALES}
+    if c1 not in by_width:
+        raise ValueError("model.0.conv.weight has %d rows: no YOLOv8 scale starts with that width (%s)" % (
+            c1, ", ".join("%s: %d" % (s, w) for w, s in sorted(by_width.items()))))
+    scale = by_width[c1]
+    reps = len({k.split(".")[2] for k in flat if k.startswith("2.m.") and k.endswith(".cv1.conv.weight")})
+    if reps != model_dims(scale)[1][0]:
+        raise ValueError("layer 2 has %d bottlenecks under model.2.m.<i>, YOLOv8%s has %d" % (reps, scale, model_dims(scale)[1][0]))
+    nc = rows("22.cv3.0.2.weight")
+    if scale not in BUILT_SCALES:
+        raise ValueError("a YOLOv8%s state_dict (scale %r, %d classes): scales n, s and m are built, l and x are not" % (scale, scale, nc))
+    _check_model(scale, nc)
+    return scale, nc
+
+
+def params_from_state_dict(sd, scale=None, nc=None):
+    """Flat parameter vector (the order of conv_specs()) from a YOLOv8 `state_dict` with ultralytics' key names
+    (detector.py:77-84 loads such a model through `YOLO(model_path)`).  The dict decides scale and nc itself (infer_model); given
+    arguments must agree with it.  Keys may carry any number of leading `model.` / `module.` prefixes; `num_batches_tracked` and the
+    constant DFL convolution (`22.dfl.conv.weight`, arange(16)) are ignored; every shape is checked.  BatchNorm is folded later by the
+    library (eps 1e-3, ultralytics' Conv default)."""
+    flat = _strip_prefixes(sd)
+    found = infer_model(flat)
+    if (scale is not None and scale != found[0]) or (nc is not None and nc != found[1]):
+        raise ValueError("the state_dict is a YOLOv8%s with %d classes, scale=%r nc=%r was asked for" % (found + (scale, nc)))
+    scale, nc = found
+    specs, names = conv_specs(scale, nc), ultralytics_layer_names(scale)
     assert len(specs) == len(names)
 
     def get(key, shape):
         if key not in flat:
-            raise KeyError("state_dict has no %r (a YOLOv8n checkpoint's state_dict is expected)" % ("model." + key))
+            raise KeyError("state_dict has no %r (a YOLOv8%s checkpoint's state_dict is expected)" % ("model." + key, scale))
         a = flat[key]
         a = a.detach().cpu().float().numpy() if hasattr(a, "detach") else np.asarray(a, np.float32)
         if tuple(a.shape) != tuple(shape):
-            raise ValueError("%s has shape %s, YOLOv8n (scale n) needs %s" % (key, tuple(a.shape), tuple(shape)))
+            raise ValueError("%s has shape %s, YOLOv8%s (scale %s, %d classes) needs %s" % (key, tuple(a.shape), scale, scale, nc, tuple(shape)))
         return np.ascontiguousarray(a, np.float32).ravel()
     parts = []
     for (cin, cout, k, _, bn), name in zip(specs, names):
@@ -113,12 +196,22 @@ def params_from_state_dict(sd):
     return np.concatenate(parts)
 
 
-def state_dict_from_params(params, prefix="model."):
+def model_of_params(params, scale=None, nc=None):
+    """(scale, nc) for a flat vector: the arguments (defaults n, 80), checked against the vector's length."""
+    scale, nc = scale or "n", NC if nc is None else nc
+    n = param_count(scale, nc)
+    if np.size(params) != n:
+        raise ValueError("parameter vector has %d floats, the YOLOv8%s graph with %d classes needs %d" % (np.size(params), scale, nc, n))
+    return scale, nc
+
+
+def state_dict_from_params(params, prefix="model.", scale=None, nc=None):
     """Inverse of params_from_state_dict (NumPy arrays under ultralytics' key names): lets a parameter vector of this
-    project be handed to code that expects a YOLOv8n state_dict, and is what the round-trip test uses."""
+    project be handed to code that expects a YOLOv8 state_dict, and is what the round-trip test uses."""
     params = np.asarray(params, np.float32).ravel()
+    scale, nc = model_of_params(params, scale, nc)
     sd, pos = {}, 0
-    for (cin, cout, k, _, bn), name in zip(conv_specs(), ultralytics_layer_names()):
+    for (cin, cout, k, _, bn), name in zip(conv_specs(scale, nc), ultralytics_layer_names(scale)):
         nw = cout * cin * k * k
         w = params[pos:pos + nw].reshape(cout, cin, k, k)
         pos += nw
@@ -148,29 +241,68 @@ def _load_checkpoint(model_path):
     except Exception as e:                                  # pickled module classes (ultralytics.nn.tasks.DetectionModel, ...)
         raise FileNotFoundError("%r is not a plain state_dict file (%s: %s); export one with "
                                 "torch.save(YOLO(path).model.state_dict(), out)" % (model_path, type(e).__name__, str(e)[:120]))
+    names = obj.get("names") if isinstance(obj, dict) else None
     for key in ("state_dict", "model_state_dict", "model"):
         if isinstance(obj, dict) and isinstance(obj.get(key), dict):
             obj = obj[key]
+            names = obj.get("names", names)
     if not isinstance(obj, dict):
         raise FileNotFoundError("%r holds a %s, not a state_dict" % (model_path, type(obj).__name__))
+    if isinstance(names, (list, tuple, dict)):              # a checkpoint's class names ride along under a key no layer has
+        obj = dict(obj, names=names)
     return obj
 
 
-def load_params(model_path):
+def _names_dict(names, nc, what):
+    """{class id: name} from a list or a dict with the ids 0 .. nc-1."""
+    d = {int(k): str(v) for k, v in names.items()} if isinstance(names, dict) else dict(enumerate(str(v) for v in names))
+    if sorted(d) != list(range(nc)):
+        raise ValueError("%s name %d classes, the model has %d" % (what, len(d), nc))
+    return d
+
+
+def load_model(model_path, scale=None, nc=None):
+    """-> (flat parameter vector, scale, nc, names or None).  A state_dict decides scale and nc itself and given arguments must agree
+    with it; "random[:seed[:scale[:nc]]]" and flat vectors take the arguments (the path's fields first; defaults n, 80) and the
+    vector's length is checked; a NumPy array in place of the path is taken as the flat vector.  names: the `names` entry of a checkpoint dict (list or dict, which weights_only=True loads) or of an
+    .npz state_dict (an array of strings), else None."""
+    def from_sd(sd):
+        sd = dict(sd)
+        names = sd.pop("names", None)
+        p = params_from_state_dict(sd, scale, nc)
+        return (p,) + infer_model(sd) + (names,)
+
+    def from_vector(p, scale, nc):
+        p = np.ascontiguousarray(p, np.float32).ravel()
+        return (p,) + model_of_params(p, scale, nc) + (None,)
+    if isinstance(model_path, np.ndarray):                  # the flat vector itself
+        return from_vector(model_path, scale, nc)
     if model_path.startswith("random"):
-        seed = int(model_path.split(":")[1]) if ":" in model_path else 0
-        return random_params(seed)
+        f = model_path.split(":")
+        seed = int(f[1]) if len(f) > 1 and f[1] else 0
+        p_scale, p_nc = (f[2] if len(f) > 2 else None), (int(f[3]) if len(f) > 3 else None)
+        if (scale is not None and p_scale is not None and scale != p_scale) or (nc is not None and p_nc is not None and nc != p_nc):
+            raise ValueError("%r and scale=%r, nc=%r disagree" % (model_path, scale, nc))
+        scale, nc = p_scale or scale or "n", p_nc if p_nc is not None else (NC if nc is None else nc)
+        return random_params(seed, scale, nc), scale, nc, None
     if not os.path.exists(model_path):
-        raise FileNotFoundError("model file %r not found (pass a YOLOv8n state_dict file (.pt/.pth/.safetensors), a "
-                                ".npy/.npz parameter vector or 'random[:seed]')" % model_path)
+        raise FileNotFoundError("model file %r not found (pass a YOLOv8 n/s/m state_dict file (.pt/.pth/.safetensors), a "
+                                ".npy/.npz parameter vector or 'random[:seed[:scale[:nc]]]')" % model_path)
     if model_path.endswith(".npz"):
         z = np.load(model_path)
         if len(z.files) > 1:                                # a state_dict saved with np.savez
-            return params_from_state_dict({k: z[k] for k in z.files})
-        return np.ascontiguousarray(z[z.files[0]], np.float32).ravel()
+            sd = {k: z[k] for k in z.files}
+            if "names" in sd:
+                sd["names"] = [str(v) for v in sd["names"]]
+            return from_sd(sd)
+        return from_vector(z[z.files[0]], scale, nc)
     if model_path.endswith(".npy"):
-        return np.ascontiguousarray(np.load(model_path), np.float32).ravel()
-    return params_from_state_dict(_load_checkpoint(model_path))
+        return from_vector(np.load(model_path), scale, nc)
+    return from_sd(_load_checkpoint(model_path))
+
+
+def load_params(model_path, scale=None, nc=None):
+    return load_model(model_path, scale, nc)[0]
 
 
 class _OwnStream:
@@ -189,9 +321,12 @@ class _OwnStream:
         self._stream.synchronize()
 
 
-class YoloV8n:
-    def __init__(self, model_path="random", device=0, batch=1, keep_logits=False, precision="fp16"):
-        """keep_logits: test hook -- the head also writes its float32 logits (tensor ids 100-105) and the stand-alone decode
+class YoloV8:
+    def __init__(self, model_path="random", device=0, batch=1, keep_logits=False, precision="fp16", scale=None, nc=None, names=None):
+        """scale ("n", "s", "m"), nc (1 .. 256): the model, for "random[:seed[:scale[:nc]]]" and flat vectors (defaults n, 80); a
+        state_dict decides both itself and the arguments, if given, must agree.  names: class names (a list, or a dict by class id);
+        default: the checkpoint's `names` entry, else COCO's for 80 classes, else {i: "class<i>"}.
+        keep_logits: test hook -- the head also writes its float32 logits (tensor ids 100-105) and the stand-alone decode
         runs on them (ids 120-122); normally the decode happens in the head's last convolutions and no logits exist.
         precision: "fp16" -- IEEE-half tensors / weights / MFMA operands with float32 accumulation, the fused production path;
         "fp32" -- the reference's own arithmetic (ultralytics on torch float32, detector.py:103-123): float32 everywhere on
@@ -200,11 +335,17 @@ class YoloV8n:
             raise ValueError("precision must be 'fp16' or 'fp32', got %r" % (precision,))
         self._dev = Dev(device)
         self.keep_logits = keep_logits
-        self.params = load_params(model_path)
-        n = int(self._dev.lib.av_yolo_param_count())
+        self.params, self.scale, self.nc, file_names = load_model(model_path, scale, nc)
+        self._model = native_model(self.scale, self.nc)
+        n = int(self._dev.lib.av_yolo_model_param_count(C.byref(self._model)))
         if self.params.size != n:
-            raise ValueError("parameter vector has %d floats, the YOLOv8n graph needs %d" % (self.params.size, n))
-        self.names = dict(enumerate(COCO_NAMES))
+            raise ValueError("parameter vector has %d floats, the YOLOv8%s graph with %d classes needs %d" % (self.params.size, self.scale, self.nc, n))
+        if names is not None:
+            self.names = _names_dict(names, self.nc, "names")
+        elif file_names is not None:
+            self.names = _names_dict(file_names, self.nc, "the checkpoint's names")
+        else:
+            self.names = dict(enumerate(COCO_NAMES)) if self.nc == NC else {i: "class%d" % i for i in range(self.nc)}
         self.batch = batch
         self.precision = precision
         self._h = None
@@ -225,8 +366,8 @@ class YoloV8n:
         d = self._dev
         self.close()
         hd = C.c_void_p()
-        nat.check(d.lib.av_yolo_create_ex(d.ctx.handle, self.batch, h, w, self.params.ctypes.data_as(C.c_void_p),
-                                          self.params.size, 1 if self.precision == "fp32" else 0, C.byref(hd)))
+        nat.check(d.lib.av_yolo_create_model(d.ctx.handle, self.batch, h, w, C.byref(self._model), self.params.ctypes.data_as(C.c_void_p),
+                                             self.params.size, 1 if self.precision == "fp32" else 0, C.byref(hd)))
         self._h = hd
         self._shape = (h, w)
         if self.keep_logits:
@@ -337,6 +478,18 @@ class YoloV8n:
             out.append(info)
         return out
 
+    def plan(self):
+        """The launches of a forward as they are planned now, in order (test hook av_yolo_plan_step): a list of nat.YoloStepInfo.
+        Reads nothing from the device."""
+        n = C.c_int()
+        nat.check(self._dev.lib.av_yolo_plan_count(self._h, C.byref(n)))
+        out = []
+        for k in range(n.value):
+            info = nat.YoloStepInfo()
+            nat.check(self._dev.lib.av_yolo_plan_step(self._h, k, C.byref(info)))
+            out.append(info)
+        return out
+
     def _read(self, ptr, count, dtype):
         """Host copy of `count` elements of library-owned device memory."""
         t = torch.empty(count, dtype=dtype, device=self._dev.device)
@@ -377,6 +530,9 @@ class YoloV8n:
             self.close()
         except Exception:
             pass
+
+
+YoloV8n = YoloV8          # the name of the default model (scale n, 80 classes)
 
 
 def _memcpy_d2d(dst, src, nbytes):

@@ -714,14 +714,16 @@ class PerceptionLoop:
     """BASELINE config 3: S camera streams, frames generated on the device, YOLO-mode detector (MFMA conv
     path) + lane detector per frame.  Everything stays in HBM; one enqueue per stage per step."""
 
-    def __init__(self, n_streams=16, h=720, w=1280, device=0, model="random:0", max_segments=512, ctx=None, precision="fp16"):
+    def __init__(self, n_streams=16, h=720, w=1280, device=0, model="random:0", max_segments=512, ctx=None, precision="fp16", names=None):
+        """model: a YOLOv8 n / s / m state_dict file, a flat parameter vector or "random[:seed[:scale[:nc]]]" (perception/yolo.py);
+        names: its class names, if the file carries none."""
         if not torch.cuda.is_available():
             raise RuntimeError("PerceptionLoop needs a HIP device; this package has no CPU path")
-        from .perception.yolo import MAX_DET, YoloV8n, conv_specs
+        from .perception.yolo import MAX_DET, YoloV8
         self.S, self.h, self.w, self.ms = n_streams, h, w, max_segments
         self.dev = torch.device("cuda", device)
         self.L = nat.lib()
-        self.yolo = YoloV8n(model, device=device, batch=n_streams, precision=precision)
+        self.yolo = YoloV8(model, device=device, batch=n_streams, precision=precision, names=names)
         self.ctx = self.yolo._dev.ctx
         self.yolo._prepare(h, w)
         # the detector chain is the critical path when the lane chain runs beside it: higher queue priority
@@ -743,11 +745,7 @@ class PerceptionLoop:
         self.max_det = MAX_DET
         net_h, net_w, _ = self.yolo.dims()
         # 2*MACs of every convolution at the letterboxed resolution (the figure the MFMA roofline is priced on)
-        fl, hh, ww = 0, net_h, net_w
-        sizes = []
-        for cin, cout, k, s, _ in conv_specs():
-            sizes.append((cin, cout, k, s))
-        self.flops_per_frame = _yolo_flops(net_h, net_w)
+        self.flops_per_frame = _yolo_flops(net_h, net_w, self.yolo.scale, self.yolo.nc)
         # HBM bytes per pixel the lane pixel stages have to move (bench.py): read BGR 3, write the non-maximum-suppressed
         # magnitudes 1, read them for the hysteresis pass 1 (the resolve / compaction passes only touch the ROI box: +0.3).
         # SURVEY 8d's 7*W*H per frame assumed the blurred image goes out to memory and back; the fused front end keeps it
@@ -935,16 +933,16 @@ class PerceptionLoop:
             nat.check(self.L.av_scene_reset(self.ctx.handle, self._s, self.S, nat.ptr(self.scene_state)))
 
 
-def _yolo_flops(H, W):
-    """2*MACs of the YOLOv8n graph at input H x W (per frame), walking the same layer list as the library."""
-    from .perception.yolo import conv_specs
-    specs = conv_specs()
-    # spatial size of every conv's OUTPUT, in execution order
-    def c2f(n):
-        return [0] * (2 + 2 * n)
-    div = []
-    div += [2, 4] + [4] * 4 + [8] + [8] * 6 + [16] + [16] * 6 + [32] + [32] * 4 + [32, 32]     # backbone + SPPF
-    div += [16] * 4 + [8] * 4 + [16] + [16] * 4 + [32] + [32] * 4                                # head
+def _yolo_flops(H, W, scale="n", nc=80):
+    """2*MACs of the YOLOv8 graph (scale, nc) at input H x W (per frame), walking the same layer list as the library."""
+    from .perception.yolo import conv_specs, model_dims
+    specs = conv_specs(scale, nc)
+    _, rep, nr, _, _ = model_dims(scale, nc)
+    # downscale of every conv's OUTPUT, in execution order (a C2f block with n bottleneck pairs has 2 + 2 n convolutions)
+    def c2f(n, d):
+        return [d] * (2 + 2 * n)
+    div = [2, 4] + c2f(rep[0], 4) + [8] + c2f(rep[1], 8) + [16] + c2f(rep[2], 16) + [32] + c2f(rep[3], 32) + [32, 32]     # backbone + SPPF
+    div += c2f(nr, 16) + c2f(nr, 8) + [16] + c2f(nr, 16) + [32] + c2f(nr, 32)                                              # neck
     for d in (8, 16, 32):
         div += [d] * 6
     assert len(div) == len(specs)
@@ -979,9 +977,12 @@ class CameraLoop:
 
     def __init__(self, n_streams, h=720, w=1280, model="random:0", precision="fp16", dcap=64, obstacles="moving_tracks",
                  class_map="reference", device=0, tracker_kw=None, kf_kw=None, planner_kw=None, obstacle_kw=None, tags=None,
-                 tag_capacity=4096, view=None, tag_columns=False):
-        """class_map: "reference" (the detector's class names -> the reference's eight ids, everything else skipped:
-        reference_class_map), None (raw ids) or an explicit int table.  obstacle_kw: HotLoop's; the defaults stretch the BEV
+                 tag_capacity=4096, view=None, tag_columns=False, names=None):
+        """model, names: PerceptionLoop's (any YOLOv8 n / s / m model, e.g. "random:0:s"; names for a checkpoint without them).
+        class_map: "reference" (the detector's class names -> the reference's eight ids, everything else skipped:
+        reference_class_map), None (raw ids) or an explicit int table.  With names that match none of the reference's eight (a
+        fine-tuned model's own classes, or the "class<i>" defaults) "reference" therefore skips EVERY detection: the tracker sees
+        nothing -- pass class_map=None or a table for such a model.  obstacle_kw: HotLoop's; the defaults stretch the BEV
         panel's 640 x 500 px convention to the frame (x_center = w / 2, x_scale = 0.03 * 640 / w, y_far = 50,
         y_scale = 50 / h).
         tags: None, "motion" or "all" -- every step() also tags its frame behind hot.step() on the hot stream and appends it to
@@ -1000,7 +1001,7 @@ class CameraLoop:
         if view not in (None, "camera", "demo"):
             raise ValueError('view is None, "camera" or "demo"')
         self.S, self.h, self.w = n_streams, h, w
-        self.cam = PerceptionLoop(n_streams=n_streams, h=h, w=w, device=device, model=model, precision=precision)
+        self.cam = PerceptionLoop(n_streams=n_streams, h=h, w=w, device=device, model=model, precision=precision, names=names)
         ok = dict(x_center=w / 2.0, x_scale=0.03 * 640.0 / w, y_far=50.0, y_scale=50.0 / h)
         ok.update(obstacle_kw or {})
         self.hot = HotLoop(n_streams=n_streams, window=1, h=h, w=w, dcap=dcap, device=device, tracker_kw=tracker_kw, kf_kw=kf_kw,
