@@ -311,6 +311,52 @@ int av_track_obstacles_moving(av_ctx* ctx, av_stream_t stream, const av_obstacle
                               int tcap, const av_track_row* snap, const int32_t* snap_n, const double* plan_state,
                               int ocap, double* obstacles, int32_t* n_obs);
 
+/* ---- Per-track Kalman filter over the snapshot tables (the SORT filter; the reference has none: Track.velocity is the last
+ * centre difference, multi_object_tracker.py:35-47) -------------------------------------------------------------------------
+ * A constant-velocity filter per track, fed the matched centres, predicting through misses.  State x = (cx, cy, vx, vy) in
+ * pixels and pixels per frame, one frame as the time step:
+ *   F = [[1,0,1,0],[0,1,0,1],[0,0,1,0],[0,0,0,1]],  Q = q_accel G G^T with G = [[1/2,0],[0,1/2],[1,0],[0,1]]
+ *   (per axis [[q/4, q/2], [q/2, q]]),  H = [I2 0],  R = r_meas I2
+ * One frame after the other per stream; for every live row i < clamp(snap_n, 0, tcap) of the frame, with
+ * z = ((x1 + x2) / 2, (y1 + y2) / 2) and k = row.slot (unique among live rows, inside [0, tcap), stable for a track's life):
+ *   birth   (state[k].id != row.id): x = (z, 0, 0), P = diag(p0_pos, p0_pos, p0_vel, p0_vel), state[k].id = row.id; no prediction
+ *   else    x <- F x, P <- F P F^T + Q
+ *   then    if row.misses == 0: the Kalman update with measurement z
+ *   filt row = (x, sqrt(P00 + P11), sqrt(P22 + P33))        the two uncertainties VehicleState carries
+ * Slots that no live row of a frame names keep their state.  A row whose slot lies outside [0, tcap) (a hand-made table) is
+ * skipped: its filt row is zeros and status bit 0 is set; no index leaves the state buffer.  float64 throughout. */
+typedef struct {
+    double q_accel;   /* 1.0   white-noise acceleration, px^2 / frame^4; finite, >= 0 */
+    double r_meas;    /* 4.0   measurement variance of a centre coordinate, px^2; finite, > 0 */
+    double p0_pos;    /* 4.0   initial variance of cx, cy; finite, >= 0 */
+    double p0_vel;    /* 100.0 initial variance of vx, vy; finite, >= 0 */
+} av_track_filter_cfg;           /* 32 bytes */
+/* Persistent per-stream filter state (device).  Layout, for stream s with capacity tcap, 16-byte aligned:
+ *   int32 hdr[16]                  hdr[0]=status; the rest 0
+ *   slot[tcap], 64 bytes each:     int32 id (-1: free), int32 reserved (0), double x[4] (cx, cy, vx, vy),
+ *                                  double p[3] (P00 = P11, P02 = P13, P22 = P33)
+ * x and y never mix and share F, Q, H, R and the initial variances, so P is two equal 2 x 2 blocks, one per axis, that depend
+ * only on the track's hit / miss pattern; every other entry of P is 0.  The three numbers ARE the covariance.
+ * status bit0: a row named a slot outside [0, tcap) and was skipped.
+ * av_track_filter_reset sets every id to -1 and every other byte, the status word included, to 0. */
+size_t av_track_filter_state_bytes(int tcap);          /* 0 for tcap <= 0 */
+int av_track_filter_reset(av_ctx* ctx, av_stream_t stream, int n_streams, int tcap, void* state);
+/*   snap [S][W][tcap], snap_n [S][W]   av_tracker_update's outputs
+ *   filt [S][W][tcap][6]               (cx, cy, vx, vy, pos_sigma, vel_sigma) aligned with the snapshot rows; rows at index
+ *                                      clamp(snap_n) and beyond are not written
+ * tcap as av_tracker_update's; n_streams, n_frames >= 1; cfg inside the ranges above: AV_EINVAL otherwise, before any launch. */
+int av_track_filter_update(av_ctx* ctx, av_stream_t stream, const av_track_filter_cfg* cfg, int n_streams, int n_frames, int tcap,
+                           const av_track_row* snap, const int32_t* snap_n, void* state, double* filt);
+/* av_track_obstacles_moving on the filtered tracks: row selection, order, count and radius are av_track_obstacles', position and
+ * velocity av_track_obstacles_moving's formulas in its operation order, with
+ *   cx, cy   = filt[f][i][0..1]     instead of the box centre
+ *   rvx, rvy = filt[f][i][2..3]     instead of row.vx, row.vy; no hist_len test (a newborn's filtered velocity is 0)
+ * so a coasting track's disc sits where the filter predicts it, not where it was last seen.
+ *   filt [n_states][tcap][6] (av_track_filter_update); everything else as av_track_obstacles_moving */
+int av_track_obstacles_filtered(av_ctx* ctx, av_stream_t stream, const av_obstacle_cfg* cfg, double frame_rate, int n_states, int tcap,
+                                const av_track_row* snap, const int32_t* snap_n, const double* filt, const double* plan_state,
+                                int ocap, double* obstacles, int32_t* n_obs);
+
 /* The YOLO-mode detector's output (av_yolo_forward: float32 boxes and confidences, the model's class ids, confidence-descending)
  * as the tracker's input (av_tracker_update), on the device; what ObjectDetector._detect_yolo does per box on the host
  * (detector.py:111-121: map(int, xyxy), float(conf), int(cls)), plus an optional class table.  Per frame f:

@@ -48,6 +48,15 @@ class ObstacleCfg(C.Structure):
                 ("radius", C.c_double * 16)]
 
 
+class TrackFilterCfg(C.Structure):
+    """av_track_filter_cfg: the per-track constant-velocity Kalman filter's noise and initial variances (px, frames)."""
+    _fields_ = [("q_accel", C.c_double), ("r_meas", C.c_double), ("p0_pos", C.c_double), ("p0_vel", C.c_double)]
+
+
+TRACK_FILTER_HDR_BYTES = 64
+TRACK_FILTER_SLOT_FIELDS = [("id", "<i4"), ("reserved", "<i4"), ("x", "<f8", (4,)), ("p", "<f8", (3,))]     # 64 bytes
+
+
 class LaneCfg(C.Structure):
     _fields_ = [("hough_threshold", C.c_int32), ("min_line_length", C.c_int32), ("max_line_gap", C.c_int32),
                 ("max_segments", C.c_int32), ("smoothing_factor", C.c_double)]
@@ -247,6 +256,11 @@ _SIGS = [
     ("av_planner_plan_moving", C.c_int, [vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp]),
     ("av_track_obstacles_moving", C.c_int, [vp, vp, C.POINTER(ObstacleCfg), C.c_double, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp,
                                             vp]),
+    ("av_track_filter_state_bytes", C.c_size_t, [C.c_int]),
+    ("av_track_filter_reset", C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
+    ("av_track_filter_update", C.c_int, [vp, vp, C.POINTER(TrackFilterCfg), C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+    ("av_track_obstacles_filtered", C.c_int, [vp, vp, C.POINTER(ObstacleCfg), C.c_double, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int,
+                                              vp, vp]),
     ("av_dets_to_tracker", C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
     ("av_lane_paths", C.c_int, [vp, vp, C.POINTER(ObstacleCfg), C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int,
                                 C.c_int, vp, vp, vp]),

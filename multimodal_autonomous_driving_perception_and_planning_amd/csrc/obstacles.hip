@@ -14,18 +14,28 @@
 // difference (px / frame, Track.velocity, multi_object_tracker.py:35-47) scaled like the position and by the frame rate, plus the
 // ego's own speed along its heading -- the image is ego-centric, so a track at rest in it moves with the ego.  Same wave per
 // state, same compaction; a kept lane writes 40 bytes (x, y, radius, vx, vy).
+//
+// The filtered form (av_track_obstacles_filtered) is the moving form with the track's centre and velocity taken from the per-track
+// Kalman filter's output row (av_track_filter_update, trackfilter.hip) in place of the box and of the last centre difference: a
+// coasting track's disc sits where the filter predicts it.  Same selection, order, count and radius.
 #include "common.h"
 
 #include <cmath>
 
 namespace {
 
-template <bool MOVING>      // MOVING: rows of 5 doubles, frame_rate in frames per second (unused otherwise)
+enum { STATIC = 0, MOVING_ROWS = 1, FILTERED = 2 };
+
+// MODE != STATIC: rows of 5 doubles, frame_rate in frames per second (unused otherwise); FILTERED: centre and velocity of row i
+// from filt [n_states][tcap][6] (cx, cy, vx, vy, ., .), NULL otherwise
+template <int MODE>
 __global__ void __launch_bounds__(256) track_obstacles_kernel(av_obstacle_cfg cfg, double frame_rate, int n_states, int tcap,
                                                               const av_track_row* __restrict__ snap,
                                                               const int32_t* __restrict__ snap_n,
                                                               const double* __restrict__ plan_state, int ocap,
-                                                              double* __restrict__ obstacles, int32_t* __restrict__ n_obs) {
+                                                              double* __restrict__ obstacles, int32_t* __restrict__ n_obs,
+                                                              const double* __restrict__ filt) {
+    constexpr bool MOVING = MODE != STATIC;
     const int lane = threadIdx.x & 63;
     const long long fl = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (fl >= n_states) return;
@@ -51,13 +61,21 @@ __global__ void __launch_bounds__(256) track_obstacles_kernel(av_obstacle_cfg cf
 #pragma unroll
             for (int k = 0; k < 16; ++k) rad = r.cls == k ? cfg.radius[k] : rad;      // (ids outside 0..15 keep 0: no obstacle)
             keep = (r.flags & 1) && rad > 0.0;
-            const double cx = (double)(r.x1 + r.x2) / 2.0, cy = (double)(r.y1 + r.y2) / 2.0;
+            double cx, cy, fvx = 0.0, fvy = 0.0;
+            if constexpr (MODE == FILTERED) {
+                const double2* fr = reinterpret_cast<const double2*>(filt + ((size_t)f * tcap + i) * 6);
+                const double2 c = fr[0], v = fr[1];
+                cx = c.x, cy = c.y, fvx = v.x, fvy = v.y;
+            } else {
+                cx = (double)(r.x1 + r.x2) / 2.0, cy = (double)(r.y1 + r.y2) / 2.0;
+            }
             const double l = (cx - cfg.x_center) * cfg.x_scale, fw = cfg.y_far - cy * cfg.y_scale;
             ox = (x0 + fw * cs) + l * c2;
             oy = (y0 + fw * sn) + l * s2;
             if constexpr (MOVING) {
                 const bool has_vel = r.hist_len >= 2;               // (vx, vy are valid from the second centre on)
-                const double rvx = has_vel ? (double)r.vx : 0.0, rvy = has_vel ? (double)r.vy : 0.0;
+                const double rvx = MODE == FILTERED ? fvx : (has_vel ? (double)r.vx : 0.0);   // (a newborn's filtered velocity is 0)
+                const double rvy = MODE == FILTERED ? fvy : (has_vel ? (double)r.vy : 0.0);
                 const double vl = (rvx * cfg.x_scale) * frame_rate;                  // lateral, m/s, relative to the ego
                 const double vf = v0 - (rvy * cfg.y_scale) * frame_rate;             // forward, m/s: the ego's own speed added
                 ovx = vf * cs + vl * c2;
@@ -77,16 +95,18 @@ __global__ void __launch_bounds__(256) track_obstacles_kernel(av_obstacle_cfg cf
 
 }  // namespace
 
-template <bool MOVING>
+template <int MODE>
 static int track_obstacles_launch(av_ctx* ctx, av_stream_t stream, const av_obstacle_cfg* cfg, double frame_rate, int n_states, int tcap,
                                   const av_track_row* snap, const int32_t* snap_n, const double* plan_state, int ocap,
-                                  double* obstacles, int32_t* n_obs, const char* who) {
+                                  double* obstacles, int32_t* n_obs, const double* filt, const char* who) {
+    constexpr bool MOVING = MODE != STATIC;
     AV_REQUIRE(ctx && cfg && snap && snap_n && plan_state && obstacles && n_obs, AV_EINVAL, "%s: null argument", who);
+    AV_REQUIRE(MODE != FILTERED || filt, AV_EINVAL, "%s: null argument", who);
     AV_REQUIRE(n_states > 0 && tcap > 0, AV_EINVAL, "%s: n_states and tcap must be > 0", who);
     AV_REQUIRE(ocap >= tcap, AV_EINVAL, "%s: ocap %d < tcap %d (no obstacle is ever dropped)", who, ocap, tcap);
     AV_REQUIRE(!MOVING || (frame_rate > 0.0 && std::isfinite(frame_rate)), AV_EINVAL, "%s: frame_rate must be > 0 and finite", who);
-    hipLaunchKernelGGL(track_obstacles_kernel<MOVING>, dim3((n_states + 3) / 4), dim3(256), 0, as_stream(stream), *cfg, frame_rate,
-                       n_states, tcap, snap, snap_n, plan_state, ocap, obstacles, n_obs);
+    hipLaunchKernelGGL(track_obstacles_kernel<MODE>, dim3((n_states + 3) / 4), dim3(256), 0, as_stream(stream), *cfg, frame_rate,
+                       n_states, tcap, snap, snap_n, plan_state, ocap, obstacles, n_obs, filt);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }
@@ -94,13 +114,20 @@ static int track_obstacles_launch(av_ctx* ctx, av_stream_t stream, const av_obst
 extern "C" int av_track_obstacles(av_ctx* ctx, av_stream_t stream, const av_obstacle_cfg* cfg, int n_states, int tcap,
                                   const av_track_row* snap, const int32_t* snap_n, const double* plan_state, int ocap,
                                   double* obstacles, int32_t* n_obs) {
-    return track_obstacles_launch<false>(ctx, stream, cfg, 0.0, n_states, tcap, snap, snap_n, plan_state, ocap, obstacles, n_obs,
-                                         "av_track_obstacles");
+    return track_obstacles_launch<STATIC>(ctx, stream, cfg, 0.0, n_states, tcap, snap, snap_n, plan_state, ocap, obstacles, n_obs,
+                                          nullptr, "av_track_obstacles");
 }
 
 extern "C" int av_track_obstacles_moving(av_ctx* ctx, av_stream_t stream, const av_obstacle_cfg* cfg, double frame_rate, int n_states,
                                          int tcap, const av_track_row* snap, const int32_t* snap_n, const double* plan_state, int ocap,
                                          double* obstacles, int32_t* n_obs) {
-    return track_obstacles_launch<true>(ctx, stream, cfg, frame_rate, n_states, tcap, snap, snap_n, plan_state, ocap, obstacles, n_obs,
-                                        "av_track_obstacles_moving");
+    return track_obstacles_launch<MOVING_ROWS>(ctx, stream, cfg, frame_rate, n_states, tcap, snap, snap_n, plan_state, ocap, obstacles,
+                                               n_obs, nullptr, "av_track_obstacles_moving");
+}
+
+extern "C" int av_track_obstacles_filtered(av_ctx* ctx, av_stream_t stream, const av_obstacle_cfg* cfg, double frame_rate, int n_states,
+                                           int tcap, const av_track_row* snap, const int32_t* snap_n, const double* filt,
+                                           const double* plan_state, int ocap, double* obstacles, int32_t* n_obs) {
+    return track_obstacles_launch<FILTERED>(ctx, stream, cfg, frame_rate, n_states, tcap, snap, snap_n, plan_state, ocap, obstacles, n_obs,
+                                            filt, "av_track_obstacles_filtered");
 }

@@ -14,7 +14,9 @@ Opt-in (HotLoop(obstacles="tracks"), set_obstacles, set_reference_paths): every 
 list and every stream with its own reference path (av_planner_plan_each); with "tracks" the lists are the frame's
 confirmed tracks (av_track_obstacles), and the planner then runs behind the tracker.  With "moving_tracks" every such
 obstacle also carries the velocity its track's last centre difference predicts (av_track_obstacles_moving), and each waypoint
-meets it where it is at that waypoint's time (av_planner_plan_moving).
+meets it where it is at that waypoint's time (av_planner_plan_moving).  With "filtered_tracks" the tables first pass through a
+per-track Kalman filter (av_track_filter_update, behind the tracker on the side stream) and the obstacles take the filter's
+centre and velocity (av_track_obstacles_filtered): smoothed, right after a gap, and predicted forward while a track coasts.
 
 Opt-in (set_detections, set_lane_inputs, CameraLoop): the tracker is fed by a real detector's output left in HBM
 (av_dets_to_tracker instead of the simulated detector) and every stream's reference path is its own lane fit
@@ -32,7 +34,7 @@ from . import _native as nat
 class HotLoop:
     def __init__(self, n_streams=1, window=1, h=720, w=1280, tcap=64, dcap=8, device=0,
                  tracker_kw=None, kf_kw=None, planner_kw=None, keep_waypoints=True, keep_snapshots=True,
-                 ctx=None, fused_step=None, overlap=1, obstacles=None, obstacle_kw=None):
+                 ctx=None, fused_step=None, overlap=1, obstacles=None, obstacle_kw=None, track_filter_kw=None):
         """fused_step: with window 1, run a time-step as ONE launch (av_hot_step: role-split workgroups running the stage
         kernels' own device code, same results bit for bit) instead of the four stage launches.  None = whenever the
         configuration allows it (window 1, tcap 64, dcap 7..8, iou_threshold > 0, and planner settings whose tiles fit the
@@ -51,7 +53,12 @@ class HotLoop:
         obstacles="moving_tracks": the same obstacles, each with the constant velocity of its track in the planner's frame
         (av_track_obstacles_moving: the last centre difference at obstacle_kw's frame_rate, default 30 frames/s, plus the ego's
         own speed), planned around where they are at each waypoint's time (av_planner_plan_moving); self.obstacles
-        [S, W, tcap, 5] (x, y, radius, vx, vy).  frame_rate is accepted only in this mode."""
+        [S, W, tcap, 5] (x, y, radius, vx, vy).  frame_rate is accepted only in this mode and the next.
+        obstacles="filtered_tracks": "moving_tracks" with every track's centre and velocity taken from a per-track constant-velocity
+        Kalman filter over the snapshot tables (av_track_filter_update, then av_track_obstacles_filtered): self.track_filt
+        [S, W, tcap, 6] (cx, cy, vx, vy, pos_sigma, vel_sigma; px and px / frame) aligned with the snapshot rows.  The filter's state
+        (self.track_filter, a tracking.TrackFilter) persists across windows and is cleared by reset().  track_filter_kw: its settings
+        (q_accel, r_meas, p0_pos, p0_vel), accepted only in this mode."""
         if not torch.cuda.is_available():
             raise RuntimeError("HotLoop needs a HIP device; this package has no CPU path")
         self.S, self.W, self.h, self.w, self.tcap, self.dcap = n_streams, window, h, w, tcap, dcap
@@ -94,12 +101,15 @@ class HotLoop:
         self._use_streams([torch.cuda.Stream(device=d) for _ in range(self.overlap)])
         self.graph_id = None
         self._graphs = {}
-        if obstacles not in (None, "tracks", "moving_tracks"):
-            raise ValueError('obstacles is None, "tracks" or "moving_tracks"')
+        if obstacles not in (None, "tracks", "moving_tracks", "filtered_tracks"):
+            raise ValueError('obstacles is None, "tracks", "moving_tracks" or "filtered_tracks"')
+        if track_filter_kw is not None and obstacles != "filtered_tracks":
+            raise ValueError('track_filter_kw belongs to obstacles="filtered_tracks"')
         if obstacles is not None and (fused_step or overlap != 1 or not keep_snapshots):
             raise ValueError('obstacles="%s" needs keep_snapshots=True and the stage launches (fused_step=True and overlap > 1 '
                              'plan without obstacles)' % obstacles)
-        self._obs_mode = obstacles                # None | "tracks" | "moving_tracks" | "given" (set_obstacles)
+        self._obs_mode = obstacles                # None | "tracks" | "moving_tracks" | "filtered_tracks" | "given" (set_obstacles)
+        self.track_filter = self.track_filt = None
         self.obstacles = self.n_obs = self.ref_paths = self.n_ref = None
         self._obstacle_kw = dict(obstacle_kw or {})
         self._src = self._class_map = self.det_dropped = None       # set_detections
@@ -108,8 +118,12 @@ class HotLoop:
         self.tag_log = None                                         # enable_tag_log
         if obstacles is not None:
             self.ocfg = self._make_ocfg(obstacles)
-            self.obstacles = torch.zeros(S, W, tcap, 5 if obstacles == "moving_tracks" else 3, dtype=f64, device=d)
+            self.obstacles = torch.zeros(S, W, tcap, 3 if obstacles == "tracks" else 5, dtype=f64, device=d)
             self.n_obs = torch.zeros(S, W, dtype=i32, device=d)
+            if obstacles == "filtered_tracks":
+                from .tracking.track_filter import TrackFilter
+                self.track_filter = TrackFilter(S, tcap, ctx=self.ctx, **(track_filter_kw or {}))
+                self.track_filt = torch.zeros(S, W, tcap, 6, dtype=f64, device=d)
             fused_step = False
         can_fuse = window == 1 and tcap == 64 and 7 <= dcap <= 8 and self.tcfg.iou_threshold > 0
         if fused_step and not can_fuse:
@@ -140,15 +154,15 @@ class HotLoop:
 
     def _make_ocfg(self, mode):
         """av_obstacle_cfg from the constructor's obstacle_kw over the BEV panel's defaults; frame_rate (-> self.frame_rate) is
-        accepted with mode "moving_tracks" only."""
+        accepted with modes "moving_tracks" and "filtered_tracks" only."""
         ok = dict(x_center=320.0, x_scale=0.03, y_far=50.0, y_scale=0.1, radius=[1.5] * 6 + [0.0] * 10)
         ok.update(self._obstacle_kw)
-        if mode == "moving_tracks":
+        if mode in ("moving_tracks", "filtered_tracks"):
             self.frame_rate = float(ok.pop("frame_rate", 30.0))
             if not (self.frame_rate > 0.0 and np.isfinite(self.frame_rate)):
                 raise ValueError("obstacle_kw: frame_rate must be > 0 and finite")
         elif "frame_rate" in ok:
-            raise ValueError('obstacle_kw: frame_rate belongs to obstacles="moving_tracks"')
+            raise ValueError('obstacle_kw: frame_rate belongs to obstacles="moving_tracks" / "filtered_tracks"')
         rad = [float(r) for r in ok.pop("radius")]
         if len(rad) > 16:
             raise ValueError("obstacle_kw: at most 16 per-class radii")
@@ -200,6 +214,8 @@ class HotLoop:
             st.synchronize()
         nat.check(L.av_tracker_reset(h, self._s, self.S, self.tcap, self.tcfg.trajectory_length, nat.ptr(self.trk_state)))
         nat.check(L.av_kf_reset(h, self._s, self.S, nat.ptr(self.kf_state)))
+        if self.track_filter is not None:
+            self.track_filter.reset(self._s)
         with torch.cuda.stream(self.stream):
             if frame_offsets is None:
                 self.frame_count.zero_()
@@ -463,8 +479,8 @@ class HotLoop:
     def set_obstacles(self, obstacles, n_obs):
         """Caller-supplied obstacles for every frame of the window: float64 device tensor [S, W, ocap, 3] (x, y, radius) or, moving,
         [S, W, ocap, 5] (x, y, radius, vx, vy), and int32 [S, W] counts, read by every step from now on; None, None: none.  Not
-        together with obstacles="tracks" / "moving_tracks"."""
-        if self._obs_mode in ("tracks", "moving_tracks"):
+        together with obstacles="tracks" / "moving_tracks" / "filtered_tracks"."""
+        if self._obs_mode in ("tracks", "moving_tracks", "filtered_tracks"):
             raise RuntimeError('set_obstacles: this loop takes its obstacles from the tracker (obstacles="%s")' % self._obs_mode)
         if (obstacles is None) != (n_obs is None):
             raise ValueError("set_obstacles: the list and its counts go together")
@@ -497,17 +513,30 @@ class HotLoop:
         self._drop_graphs()
 
     def enqueue_obstacles(self, stream=None):
-        """obstacles="tracks" / "moving_tracks": the window's snapshot tables and start states -> self.obstacles / self.n_obs
-        (av_track_obstacles / av_track_obstacles_moving); call where the tracker's and the Kalman filter's outputs are complete
-        (after the join)."""
-        if self._obs_mode not in ("tracks", "moving_tracks"):
-            raise RuntimeError('enqueue_obstacles needs HotLoop(obstacles="tracks") or "moving_tracks"')
+        """obstacles="tracks" / "moving_tracks" / "filtered_tracks": the window's snapshot tables and start states (and, filtered,
+        self.track_filt) -> self.obstacles / self.n_obs (av_track_obstacles / _moving / _filtered); call where the tracker's, the
+        track filter's and the Kalman filter's outputs are complete (after the join)."""
+        if self._obs_mode not in ("tracks", "moving_tracks", "filtered_tracks"):
+            raise RuntimeError('enqueue_obstacles needs HotLoop(obstacles="tracks"), "moving_tracks" or "filtered_tracks"')
+        if self._obs_mode == "filtered_tracks":
+            nat.check(self.L.av_track_obstacles_filtered(self.ctx.handle, stream or self._s, C.byref(self.ocfg), self.frame_rate,
+                                                         self.S * self.W, self.tcap, nat.ptr(self.snap), nat.ptr(self.snap_n),
+                                                         nat.ptr(self.track_filt), nat.ptr(self.plan_state), self.tcap,
+                                                         nat.ptr(self.obstacles), nat.ptr(self.n_obs)))
+            return
         tail = (self.S * self.W, self.tcap, nat.ptr(self.snap), nat.ptr(self.snap_n), nat.ptr(self.plan_state), self.tcap,
                 nat.ptr(self.obstacles), nat.ptr(self.n_obs))
         if self._obs_mode == "moving_tracks":
             nat.check(self.L.av_track_obstacles_moving(self.ctx.handle, stream or self._s, C.byref(self.ocfg), self.frame_rate, *tail))
         else:
             nat.check(self.L.av_track_obstacles(self.ctx.handle, stream or self._s, C.byref(self.ocfg), *tail))
+
+    def enqueue_track_filter(self, stream=None):
+        """obstacles="filtered_tracks": the window's snapshot tables -> self.track_filt, advancing the per-track filters' state
+        (av_track_filter_update); call behind the tracker, on its stream."""
+        if self.track_filter is None:
+            raise RuntimeError('enqueue_track_filter needs HotLoop(obstacles="filtered_tracks")')
+        self.track_filter.update(self.snap, self.snap_n, out=self.track_filt, stream=stream or self._s)
 
     def enqueue_plan_each(self, stream=None):
         """The planner with per-state inputs (av_planner_plan_each; av_planner_plan_moving where the obstacle rows carry a
@@ -616,6 +645,8 @@ class HotLoop:
         nat.check(L.av_fork(h, s))
         self.enqueue_detect(self.ctx.side_stream)
         self.enqueue_track(self.ctx.side_stream)
+        if self._obs_mode == "filtered_tracks":
+            self.enqueue_track_filter(self.ctx.side_stream)
         self.enqueue_kf()
         if self._per_state():
             # per-state planner inputs: fork{detect; track} || {kf}; join; [lanes -> paths]; [tracks -> obstacles]; plan.  With obstacles from the
@@ -623,7 +654,7 @@ class HotLoop:
             nat.check(L.av_join(h, s))
             if self._lanes is not None:
                 self.enqueue_lane_paths()
-            if self._obs_mode in ("tracks", "moving_tracks"):
+            if self._obs_mode in ("tracks", "moving_tracks", "filtered_tracks"):
                 self.enqueue_obstacles()
             self.enqueue_plan_each()
             return
@@ -696,6 +727,8 @@ class HotLoop:
             out["wp"] = self.wp.cpu().numpy().reshape(self.S, self.W, self.n_cand, self.n_points, 6)
         if self._obs_mode is not None:
             out["obstacles"], out["n_obs"] = self.obstacles.cpu().numpy(), self.n_obs.cpu().numpy()
+        if self.track_filt is not None:
+            out["track_filt"] = self.track_filt.cpu().numpy()
         if self._src is not None:
             out["det_dropped"] = self.det_dropped.cpu().numpy()
         if self._lanes is not None:
@@ -973,18 +1006,18 @@ class CameraLoop:
     """S cameras from pixels to ranked trajectories with no host round trip: a PerceptionLoop (self.cam: frames -> YOLO-mode
     detector + lane detector) feeding a HotLoop of window 1 on the stage launches (self.hot: tracker -> Kalman -> planner) through
     av_dets_to_tracker and av_lane_paths.  The tracker sees the detector's boxes, the planner avoids the tracks
-    (obstacles="moving_tracks" / "tracks" / None) and follows each camera's own lane centre line."""
+    (obstacles="moving_tracks" / "filtered_tracks" / "tracks" / None) and follows each camera's own lane centre line."""
 
     def __init__(self, n_streams, h=720, w=1280, model="random:0", precision="fp16", dcap=64, obstacles="moving_tracks",
                  class_map="reference", device=0, tracker_kw=None, kf_kw=None, planner_kw=None, obstacle_kw=None, tags=None,
-                 tag_capacity=4096, view=None, tag_columns=False, names=None):
+                 tag_capacity=4096, view=None, tag_columns=False, names=None, track_filter_kw=None):
         """model, names: PerceptionLoop's (any YOLOv8 n / s / m model, e.g. "random:0:s"; names for a checkpoint without them).
         class_map: "reference" (the detector's class names -> the reference's eight ids, everything else skipped:
         reference_class_map), None (raw ids) or an explicit int table.  With names that match none of the reference's eight (a
         fine-tuned model's own classes, or the "class<i>" defaults) "reference" therefore skips EVERY detection: the tracker sees
         nothing -- pass class_map=None or a table for such a model.  obstacle_kw: HotLoop's; the defaults stretch the BEV
         panel's 640 x 500 px convention to the frame (x_center = w / 2, x_scale = 0.03 * 640 / w, y_far = 50,
-        y_scale = 50 / h).
+        y_scale = 50 / h).  obstacles="filtered_tracks" and track_filter_kw: HotLoop's (the per-track Kalman filter; self.hot.track_filt).
         tags: None, "motion" or "all" -- every step() also tags its frame behind hot.step() on the hot stream and appends it to
         self.tag_log (a TagLog of tag_capacity frames per camera): "motion" runs the maneuver tagger (with the lanes' offset), the
         interaction tagger (class_map="reference" only: it needs the reference's class ids) and enqueue_tags; "all" runs the scene
@@ -1006,7 +1039,7 @@ class CameraLoop:
         ok.update(obstacle_kw or {})
         self.hot = HotLoop(n_streams=n_streams, window=1, h=h, w=w, dcap=dcap, device=device, tracker_kw=tracker_kw, kf_kw=kf_kw,
                            planner_kw=planner_kw, ctx=self.cam.ctx, fused_step=False, obstacles=obstacles, obstacle_kw=ok,
-                           keep_waypoints=True, keep_snapshots=True)          # what enqueue_bev / enqueue_view read
+                           keep_waypoints=True, keep_snapshots=True, track_filter_kw=track_filter_kw)          # what enqueue_bev / enqueue_view read
         if isinstance(class_map, str):
             if class_map != "reference":
                 raise ValueError('class_map is "reference", None or an int table')

@@ -1,3 +1,4 @@
 from .multi_object_tracker import MultiObjectTracker, Track
+from .track_filter import TrackFilter
 
-__all__ = ["MultiObjectTracker", "Track"]
+__all__ = ["MultiObjectTracker", "Track", "TrackFilter"]

@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
-"""Planner with per-state inputs: what the lookup costs and what motion costs (section 7e).
+"""Planner with per-state inputs: what the lookup costs, what motion costs (section 7e) and what the
+per-track Kalman filter costs (section 7l).
 
   planner   av_planner_plan without extras | av_planner_plan_each with null lists | av_planner_plan with 16 shared obstacles |
             av_planner_plan_each with the same 16 per state | av_planner_plan_moving with the same 16 and a velocity each,
             at 64 and 16 384 start states, default planner
   step      HotLoop(64 streams, fused_step=False) plain, with obstacles="tracks" and with "moving_tracks", window 1 and 256
+  filter    av_track_filter_update beside av_tracker_update on the same inputs (64 streams, tcap 64, window 1 and 256), and the
+            "filtered_tracks" step beside the "moving_tracks" step; not part of the default --what
 
 HIP events on the stream the work runs on, median of --reps launches after warm-up, the whole measurement --rounds times
 (the spread between rounds is the figure's own noise).  Runs on a tree without av_planner_plan_each or av_planner_plan_moving
@@ -113,6 +116,28 @@ def step_figures(reps):
     return out
 
 
+def filter_figures(reps):
+    """Section 7l: the filter's launch beside the tracker's on the same detections and tables, and the two steps, eager."""
+    L, out = nat.lib(), {}
+    for W in (1, 256):
+        z = np.stack([np.asarray(generate_ego_motion(W, seed=k)) for k in range(64)])
+        loop = HotLoop(n_streams=64, window=W, fused_step=False, obstacles="filtered_tracks")
+        loop.load_measurements(z)
+        loop.step(sync=True)                                      # detections and tables of a window
+        out["tracker W=%d" % W] = round(timed(L, loop._s, lambda: loop.enqueue_track(), reps), 2)
+        out["filter W=%d" % W] = round(timed(L, loop._s, lambda: loop.enqueue_track_filter(), reps), 2)
+        out["filter/tracker W=%d" % W] = round(out["filter W=%d" % W] / out["tracker W=%d" % W], 3)
+        loop.synchronize()
+        del loop
+        for name in ("moving_tracks", "filtered_tracks"):
+            loop = HotLoop(n_streams=64, window=W, fused_step=False, obstacles=name)
+            loop.load_measurements(z)
+            out["%s step W=%d" % (name, W)] = round(timed(L, loop._s, lambda: loop.step(), reps), 1)
+            loop.synchronize()
+            del loop
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
@@ -124,3 +149,5 @@ if __name__ == "__main__":
             print("planner us:", planner_figures(a.reps), flush=True)
         if "step" in a.what:
             print("step us:", step_figures(a.reps), flush=True)
+        if "filter" in a.what:
+            print("filter us:", filter_figures(a.reps), flush=True)
