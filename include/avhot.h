@@ -396,6 +396,68 @@ int av_lane_paths(av_ctx* ctx, av_stream_t stream, const av_obstacle_cfg* cfg, i
                   const double* poly, const int32_t* pts, const int32_t* info, const double* plan_state, int ref_stride,
                   int rcap, double* ref_path, int32_t* n_ref, double* lane_offset);
 
+/* ---- The camera model: a ground-plane homography per camera (opt-in; the reference has no camera, and av_obstacle_cfg's four
+ * numbers are the BEV panel's drawing convention) ----------------------------------------------------------------------------
+ * A flat road seen by a pinhole camera is a plane-to-plane projection: image (u, v, 1) -> g (u, v, 1)^T = (F, L, D),
+ * forward = F / D, lateral = L / D in metres.  Frames are taken as rectified (no lens distortion).
+ * Projection of an image point (float64, every operation rounded on its own: no FMA):
+ *   F = (g0*u + g1*v) + g2;  L = (g3*u + g4*v) + g5;  D = (g6*u + g7*v) + g8
+ *   f = F / D;  l = L / D
+ *   on_road = D > 0 && f >= 0 && f <= max_range        (a NaN fails)
+ *   dfu = (g0 - f*g6) / D;  dfv = (g1 - f*g7) / D;  dlu = (g3 - l*g6) / D;  dlv = (g4 - l*g7) / D      (the Jacobian, m / px) */
+typedef struct {
+    double g[9];       /* row-major; image (u, v, 1) -> (F, L, D): forward = F / D, lateral = L / D, metres, lateral > 0 towards image right */
+    double ginv[9];    /* the inverse: road (f, l, 1) -> (U, V, D'): u = U / D', v = V / D' */
+    double max_range;  /* metres, > 0, finite */
+    int32_t anchor;    /* 0: box centre ((x1+x2)/2, (y1+y2)/2); 1: bottom centre ((x1+x2)/2, y2) -- the default */
+    int32_t reserved;  /* 0 */
+} av_ground_cfg;       /* 160 bytes */
+/* Fills *out from g: ginv = adj(g) / det(g), the TRUE inverse (D' = 1 / D), so one sign convention holds in both directions:
+ * D > 0 = below the horizon and in front of the camera.  AV_EINVAL, *out untouched: an entry of g not finite; det == 0 or an
+ * entry of ginv not finite; max_range not > 0 and finite; anchor not 0 or 1.  Host only: no context, no GPU. */
+int av_ground_make(const double g[9], double max_range, int anchor, av_ground_cfg* out);
+
+/* av_track_obstacles / _moving / _filtered (mode 0 / 1 / 2) through a camera.  ground is a DEVICE table; state f uses entry
+ * f / cam_stride (ref_stride's convention).  cfg gives radius[] only.  Row selection, order, compaction and radius are
+ * av_track_obstacles'; in addition the row's foot point (u, v) must be on_road:
+ *   anchor 0: (cx, cy);  anchor 1: (cx, (double)y2), in mode 2 (filt cx, filt cy + (double)(y2 - y1) / 2.0)
+ *   with (cx, cy) the box centre (modes 0, 1) or filt[f][i][0..1] (mode 2)
+ * A confirmed row of a class with positive radius whose foot is not on_road is counted in n_off[f] and not written.
+ *   position: ox = (x0 + f cos h) + l cos(h + pi/2), oy likewise, with (f, l) the foot's projection
+ *   velocity (modes 1, 2; rvx, rvy as av_track_obstacles_moving / _filtered take them):
+ *     vl = (dlu*rvx + dlv*rvy) * frame_rate;  vf = v0 + (dfu*rvx + dfv*rvy) * frame_rate;  then the rotation by h as there
+ *   obstacles [n_states][ocap][3] (mode 0) or [5]; n_off [n_states] or NULL; filt non-NULL exactly in mode 2
+ * cam_stride >= 1, mode in 0..2, and the checks of the linear forms: AV_EINVAL otherwise, before any launch. */
+int av_track_obstacles_ground(av_ctx* ctx, av_stream_t stream, const av_obstacle_cfg* cfg, const av_ground_cfg* ground,
+                              int cam_stride, int mode, double frame_rate, int n_states, int tcap, const av_track_row* snap,
+                              const int32_t* snap_n, const double* filt, const double* plan_state, int ocap, double* obstacles,
+                              int32_t* n_obs, int32_t* n_off);
+
+/* av_lane_paths through a camera: ground is a DEVICE table, stream s uses ground[s].  Rows y_i and centre abscissa xc_i as in
+ * av_lane_paths; (f_i, l_i) = the projection of (xc_i, y_i); the path is the longest prefix i = 0 .. m-1 whose points are all
+ * on_road: n_ref[s] = m if m >= 2, else 0 (the planner takes fewer than two points as no path); rows at or past n_ref[s] are
+ * not written.
+ *   lane_offset[s] = l((double)w / 2, (double)h) - l(xm, (double)h),  xm = (double)(pts[s][0][49][0] + pts[s][1][49][0]) / 2
+ *   NaN if either point is not on_road or the lane pair is missing (info[s][0] or info[s][1] zero; then n_ref[s] = 0 too).
+ * Every other argument and check as av_lane_paths. */
+int av_lane_paths_ground(av_ctx* ctx, av_stream_t stream, const av_ground_cfg* ground, int n_streams, int h, int w, int n_points,
+                         const double* poly, const int32_t* pts, const int32_t* info, const double* plan_state, int ref_stride,
+                         int rcap, double* ref_path, int32_t* n_ref, double* lane_offset);
+
+/* The bird's-eye view of the frames: panel pixel (r, c) of camera k shows the road point
+ *   f = f_far - ((double)r + 0.5) * m_per_px;   l = (((double)c + 0.5) - (double)gw / 2.0) * m_per_px
+ * seen through ground[k].ginv = q (float64, no FMA):
+ *   U = (q0*f + q1*l) + q2;  V = (q3*f + q4*l) + q5;  D = (q6*f + q7*l) + q8;   !(D > 0): fill
+ *   u = U / D; v = V / D;   tu = floor(u * 65536.0 + 0.5), tv = floor(v * 65536.0 + 0.5)   (doubles)
+ *   !(0 <= tu <= (w-1) * 65536 && 0 <= tv <= (h-1) * 65536): fill
+ *   x0 = tu >> 16, wx = tu & 65535, x1 = min(x0 + 1, w - 1); y likewise; each channel by the bilinear rule of the side-by-side
+ *   view's resize: ((p00 (65536-wx) + p01 wx) (65536-wy) + (p10 (65536-wx) + p11 wx) wy + 2^31) >> 32
+ *   ground DEVICE [n_cams], bgr [n_cams][h][w][3], fill: three HOST bytes (b, g, r), out [n_cams][gh][gw][3]
+ * n_cams, h, w, gh, gw >= 1 (any width: no multiple-of-four rule); m_per_px > 0 and finite, f_far finite; n_cams and
+ * ceil(gh / 16) <= 65535: AV_EINVAL otherwise. */
+int av_ground_warp(av_ctx* ctx, av_stream_t stream, const av_ground_cfg* ground, int n_cams, int h, int w, const uint8_t* bgr,
+                   int gh, int gw, double f_far, double m_per_px, const uint8_t fill[3], uint8_t* out);
+
 /* generate_polynomial_trajectory for arbitrary (lateral offset, target speed) pairs (:126-204).
  *   state [n_traj][4], end_lateral_offset [n_traj], target_velocity [n_traj] -> waypoints [n_traj][n][6] */
 int av_planner_generate(av_ctx* ctx, av_stream_t stream, int n_traj, const double* state,

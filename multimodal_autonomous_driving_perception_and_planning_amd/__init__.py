@@ -7,3 +7,13 @@ hand-written HIP kernels in libavhot.so (include/avhot.h).  No CPU fallback exis
 __version__ = "0.1.0"
 
 from . import _native  # noqa: F401  (does not load the library until first use)
+
+__all__ = ["CameraCalibration"]
+
+
+def __getattr__(name):
+    # (on first use: the perception package imports torch)
+    if name == "CameraCalibration":
+        from .perception.calibration import CameraCalibration
+        return CameraCalibration
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -48,6 +48,12 @@ class ObstacleCfg(C.Structure):
                 ("radius", C.c_double * 16)]
 
 
+class GroundCfg(C.Structure):
+    """av_ground_cfg: one camera's ground-plane homography (image -> road), its inverse, the range limit and the box anchor."""
+    _fields_ = [("g", C.c_double * 9), ("ginv", C.c_double * 9), ("max_range", C.c_double), ("anchor", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class TrackFilterCfg(C.Structure):
     """av_track_filter_cfg: the per-track constant-velocity Kalman filter's noise and initial variances (px, frames)."""
     _fields_ = [("q_accel", C.c_double), ("r_meas", C.c_double), ("p0_pos", C.c_double), ("p0_vel", C.c_double)]
@@ -264,6 +270,13 @@ _SIGS = [
     ("av_dets_to_tracker", C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
     ("av_lane_paths", C.c_int, [vp, vp, C.POINTER(ObstacleCfg), C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int,
                                 C.c_int, vp, vp, vp]),
+    ("av_ground_make", C.c_int, [c_f64p, C.c_double, C.c_int, C.POINTER(GroundCfg)]),
+    ("av_track_obstacles_ground", C.c_int, [vp, vp, C.POINTER(ObstacleCfg), vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, vp,
+                                            vp, vp, vp, C.c_int, vp, vp, vp]),
+    ("av_lane_paths_ground", C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp,
+                                       vp]),
+    ("av_ground_warp", C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double,
+                                 C.POINTER(C.c_uint8), vp]),
     ("av_hot_step", C.c_int, [vp, vp, C.POINTER(StepLoop), C.POINTER(StepSet), vp, C.c_int, C.c_int]),
     ("av_hot_step_fits", C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     ("av_hot_step_plan", C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),

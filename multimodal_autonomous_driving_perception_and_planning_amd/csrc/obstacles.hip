@@ -18,7 +18,13 @@
 // The filtered form (av_track_obstacles_filtered) is the moving form with the track's centre and velocity taken from the per-track
 // Kalman filter's output row (av_track_filter_update, trackfilter.hip) in place of the box and of the last centre difference: a
 // coasting track's disc sits where the filter predicts it.  Same selection, order, count and radius.
+//
+// The ground forms (av_track_obstacles_ground, modes 0..2) are the same kernel with a camera in place of the four linear
+// scales: the row's foot point (av_ground_cfg.anchor) goes through the ground-plane homography of the state's camera (entry
+// f / cam_stride of a device table), a row whose foot is not on the road is dropped and counted in n_off, and the pixel velocity
+// is carried to metres per second by the projection's Jacobian at the foot.  The table entry is the same for a whole wave.
 #include "common.h"
+#include "ground_dev.h"
 
 #include <cmath>
 
@@ -26,16 +32,26 @@ namespace {
 
 enum { STATIC = 0, MOVING_ROWS = 1, FILTERED = 2 };
 
+// what the ground forms take on top of the linear ones; the linear forms carry the empty struct
+struct Linear {};
+struct Ground {
+    const av_ground_cfg* table;     // device [n_cams]
+    int cam_stride;                 // state f uses table[f / cam_stride]
+    int32_t* n_off;                 // [n_states] or NULL
+};
+
 // MODE != STATIC: rows of 5 doubles, frame_rate in frames per second (unused otherwise); FILTERED: centre and velocity of row i
 // from filt [n_states][tcap][6] (cx, cy, vx, vy, ., .), NULL otherwise
-template <int MODE>
+// VIA = Ground: cfg's radius[] only, the place and the velocity through the camera VIA names
+template <int MODE, typename VIA>
 __global__ void __launch_bounds__(256) track_obstacles_kernel(av_obstacle_cfg cfg, double frame_rate, int n_states, int tcap,
                                                               const av_track_row* __restrict__ snap,
                                                               const int32_t* __restrict__ snap_n,
                                                               const double* __restrict__ plan_state, int ocap,
                                                               double* __restrict__ obstacles, int32_t* __restrict__ n_obs,
-                                                              const double* __restrict__ filt) {
+                                                              const double* __restrict__ filt, VIA via) {
     constexpr bool MOVING = MODE != STATIC;
+    constexpr bool GROUND = sizeof(VIA) > 1;
     const int lane = threadIdx.x & 63;
     const long long fl = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (fl >= n_states) return;
@@ -52,9 +68,12 @@ __global__ void __launch_bounds__(256) track_obstacles_kernel(av_obstacle_cfg cf
     const double v0 = MOVING ? plan_state[(size_t)f * 4 + 3] : 0.0;
     double* out = obstacles + (size_t)f * ocap * OS;
     int count = 0;                                                  // obstacles of the rows before this round
+    int off = 0;                                                    // GROUND: rows dropped because their foot is not on the road
+    const av_ground_cfg* cam = nullptr;
+    if constexpr (GROUND) cam = via.table + f / via.cam_stride;
     for (int b = 0; b < n; b += 64) {
         const int i = b + lane;
-        bool keep = false;
+        bool keep = false, off_road = false;
         double ox = 0.0, oy = 0.0, rad = 0.0, ovx = 0.0, ovy = 0.0;
         if (i < n) {
             const av_track_row r = rows[i];
@@ -69,19 +88,42 @@ __global__ void __launch_bounds__(256) track_obstacles_kernel(av_obstacle_cfg cf
             } else {
                 cx = (double)(r.x1 + r.x2) / 2.0, cy = (double)(r.y1 + r.y2) / 2.0;
             }
-            const double l = (cx - cfg.x_center) * cfg.x_scale, fw = cfg.y_far - cy * cfg.y_scale;
+            double l, fw;
+            grounddev::RoadPoint p;
+            if constexpr (GROUND) {
+                // the foot point: anchor 1 = bottom centre (filtered: the filter's centre lowered by half the box height)
+                double u = cx, v = cy;
+                if (cam->anchor != 0) {
+                    if constexpr (MODE == FILTERED) v = cy + (double)(r.y2 - r.y1) / 2.0;
+                    else v = (double)r.y2;
+                }
+                p = grounddev::project(cam->g, cam->max_range, u, v);
+                l = p.l, fw = p.f;
+                off_road = keep && !p.on_road;
+                keep = keep && p.on_road;
+            } else {
+                l = (cx - cfg.x_center) * cfg.x_scale, fw = cfg.y_far - cy * cfg.y_scale;
+            }
             ox = (x0 + fw * cs) + l * c2;
             oy = (y0 + fw * sn) + l * s2;
             if constexpr (MOVING) {
                 const bool has_vel = r.hist_len >= 2;               // (vx, vy are valid from the second centre on)
                 const double rvx = MODE == FILTERED ? fvx : (has_vel ? (double)r.vx : 0.0);   // (a newborn's filtered velocity is 0)
                 const double rvy = MODE == FILTERED ? fvy : (has_vel ? (double)r.vy : 0.0);
-                const double vl = (rvx * cfg.x_scale) * frame_rate;                  // lateral, m/s, relative to the ego
-                const double vf = v0 - (rvy * cfg.y_scale) * frame_rate;             // forward, m/s: the ego's own speed added
+                double vl, vf;
+                if constexpr (GROUND) {
+                    const grounddev::RoadJac j = grounddev::jacobian(cam->g, p);     // metres per pixel at the foot
+                    vl = (j.dlu * rvx + j.dlv * rvy) * frame_rate;
+                    vf = v0 + (j.dfu * rvx + j.dfv * rvy) * frame_rate;
+                } else {
+                    vl = (rvx * cfg.x_scale) * frame_rate;                           // lateral, m/s, relative to the ego
+                    vf = v0 - (rvy * cfg.y_scale) * frame_rate;                      // forward, m/s: the ego's own speed added
+                }
                 ovx = vf * cs + vl * c2;
                 ovy = vf * sn + vl * s2;
             }
         }
+        if constexpr (GROUND) off += __popcll(__ballot(off_road));
         const unsigned long long m = __ballot(keep);
         if (keep) {
             double* o = out + (size_t)(count + __popcll(m & ((1ull << lane) - 1ull))) * OS;     // < n <= tcap <= ocap
@@ -91,22 +133,25 @@ __global__ void __launch_bounds__(256) track_obstacles_kernel(av_obstacle_cfg cf
         count += __popcll(m);
     }
     if (lane == 0) n_obs[f] = count;
+    if constexpr (GROUND) {
+        if (lane == 0 && via.n_off) via.n_off[f] = off;
+    }
 }
 
 }  // namespace
 
-template <int MODE>
+template <int MODE, typename VIA = Linear>
 static int track_obstacles_launch(av_ctx* ctx, av_stream_t stream, const av_obstacle_cfg* cfg, double frame_rate, int n_states, int tcap,
                                   const av_track_row* snap, const int32_t* snap_n, const double* plan_state, int ocap,
-                                  double* obstacles, int32_t* n_obs, const double* filt, const char* who) {
+                                  double* obstacles, int32_t* n_obs, const double* filt, const char* who, VIA via = VIA()) {
     constexpr bool MOVING = MODE != STATIC;
     AV_REQUIRE(ctx && cfg && snap && snap_n && plan_state && obstacles && n_obs, AV_EINVAL, "%s: null argument", who);
     AV_REQUIRE(MODE != FILTERED || filt, AV_EINVAL, "%s: null argument", who);
     AV_REQUIRE(n_states > 0 && tcap > 0, AV_EINVAL, "%s: n_states and tcap must be > 0", who);
     AV_REQUIRE(ocap >= tcap, AV_EINVAL, "%s: ocap %d < tcap %d (no obstacle is ever dropped)", who, ocap, tcap);
     AV_REQUIRE(!MOVING || (frame_rate > 0.0 && std::isfinite(frame_rate)), AV_EINVAL, "%s: frame_rate must be > 0 and finite", who);
-    hipLaunchKernelGGL(track_obstacles_kernel<MODE>, dim3((n_states + 3) / 4), dim3(256), 0, as_stream(stream), *cfg, frame_rate,
-                       n_states, tcap, snap, snap_n, plan_state, ocap, obstacles, n_obs, filt);
+    hipLaunchKernelGGL((track_obstacles_kernel<MODE, VIA>), dim3((n_states + 3) / 4), dim3(256), 0, as_stream(stream), *cfg,
+                       frame_rate, n_states, tcap, snap, snap_n, plan_state, ocap, obstacles, n_obs, filt, via);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }
@@ -130,4 +175,24 @@ extern "C" int av_track_obstacles_filtered(av_ctx* ctx, av_stream_t stream, cons
                                            const double* plan_state, int ocap, double* obstacles, int32_t* n_obs) {
     return track_obstacles_launch<FILTERED>(ctx, stream, cfg, frame_rate, n_states, tcap, snap, snap_n, plan_state, ocap, obstacles, n_obs,
                                             filt, "av_track_obstacles_filtered");
+}
+
+extern "C" int av_track_obstacles_ground(av_ctx* ctx, av_stream_t stream, const av_obstacle_cfg* cfg, const av_ground_cfg* ground,
+                                         int cam_stride, int mode, double frame_rate, int n_states, int tcap, const av_track_row* snap,
+                                         const int32_t* snap_n, const double* filt, const double* plan_state, int ocap,
+                                         double* obstacles, int32_t* n_obs, int32_t* n_off) {
+    const char* who = "av_track_obstacles_ground";
+    AV_REQUIRE(ground, AV_EINVAL, "%s: null argument", who);
+    AV_REQUIRE(cam_stride >= 1, AV_EINVAL, "%s: cam_stride must be >= 1", who);
+    AV_REQUIRE(mode >= STATIC && mode <= FILTERED, AV_EINVAL, "%s: mode %d not in 0..2", who, mode);
+    AV_REQUIRE((mode == FILTERED) == (filt != nullptr), AV_EINVAL, "%s: filt goes with mode 2 and with no other", who);
+    const Ground via{ground, cam_stride, n_off};
+    if (mode == FILTERED)
+        return track_obstacles_launch<FILTERED>(ctx, stream, cfg, frame_rate, n_states, tcap, snap, snap_n, plan_state, ocap, obstacles,
+                                                n_obs, filt, who, via);
+    if (mode == MOVING_ROWS)
+        return track_obstacles_launch<MOVING_ROWS>(ctx, stream, cfg, frame_rate, n_states, tcap, snap, snap_n, plan_state, ocap,
+                                                   obstacles, n_obs, nullptr, who, via);
+    return track_obstacles_launch<STATIC>(ctx, stream, cfg, 0.0, n_states, tcap, snap, snap_n, plan_state, ocap, obstacles, n_obs,
+                                          nullptr, who, via);
 }

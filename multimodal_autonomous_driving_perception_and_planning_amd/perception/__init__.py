@@ -1,4 +1,5 @@
+from .calibration import CameraCalibration
 from .detector import Detection, ObjectDetector
 from .lane_detector import LaneDetector, LaneLine
 
-__all__ = ["ObjectDetector", "LaneDetector", "Detection", "LaneLine"]
+__all__ = ["ObjectDetector", "LaneDetector", "Detection", "LaneLine", "CameraCalibration"]

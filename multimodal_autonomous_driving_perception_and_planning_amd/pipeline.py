@@ -22,6 +22,11 @@ Opt-in (set_detections, set_lane_inputs, CameraLoop): the tracker is fed by a re
 (av_dets_to_tracker instead of the simulated detector) and every stream's reference path is its own lane fit
 (av_lane_paths); CameraLoop wires a PerceptionLoop to a HotLoop that way, S cameras from pixels to ranked trajectories
 with no host round trip.
+
+Opt-in (calibration=, HotLoop and CameraLoop): a camera model per stream (perception.CameraCalibration, a ground-plane
+homography) in place of the linear pixel-to-metre scales: tracks stand where their boxes' feet meet the road
+(av_track_obstacles_ground), lane paths end at the horizon (av_lane_paths_ground), and CameraLoop.enqueue_ground_view warps the
+frames to a bird's-eye view (av_ground_warp).
 """
 import ctypes as C
 
@@ -34,7 +39,7 @@ from . import _native as nat
 class HotLoop:
     def __init__(self, n_streams=1, window=1, h=720, w=1280, tcap=64, dcap=8, device=0,
                  tracker_kw=None, kf_kw=None, planner_kw=None, keep_waypoints=True, keep_snapshots=True,
-                 ctx=None, fused_step=None, overlap=1, obstacles=None, obstacle_kw=None, track_filter_kw=None):
+                 ctx=None, fused_step=None, overlap=1, obstacles=None, obstacle_kw=None, track_filter_kw=None, calibration=None):
         """fused_step: with window 1, run a time-step as ONE launch (av_hot_step: role-split workgroups running the stage
         kernels' own device code, same results bit for bit) instead of the four stage launches.  None = whenever the
         configuration allows it (window 1, tcap 64, dcap 7..8, iou_threshold > 0, and planner settings whose tiles fit the
@@ -58,7 +63,12 @@ class HotLoop:
         Kalman filter over the snapshot tables (av_track_filter_update, then av_track_obstacles_filtered): self.track_filt
         [S, W, tcap, 6] (cx, cy, vx, vy, pos_sigma, vel_sigma; px and px / frame) aligned with the snapshot rows.  The filter's state
         (self.track_filter, a tracking.TrackFilter) persists across windows and is cleared by reset().  track_filter_kw: its settings
-        (q_accel, r_meas, p0_pos, p0_vel), accepted only in this mode."""
+        (q_accel, r_meas, p0_pos, p0_vel), accepted only in this mode.
+        calibration: one perception.CameraCalibration, or one per stream -- the camera model (a ground-plane homography,
+        av_ground_cfg) in place of av_obstacle_cfg's four linear scales: the obstacle stage becomes av_track_obstacles_ground in the
+        mode `obstacles` names (a track stands where its box's foot meets the road, a foot off the road is no obstacle and is
+        counted in self.n_off [S, W], pixel velocities go through the projection's Jacobian), set_lane_inputs' paths go through
+        av_lane_paths_ground.  obstacle_kw may then carry radius and frame_rate only.  Needs the stage launches like obstacles=."""
         if not torch.cuda.is_available():
             raise RuntimeError("HotLoop needs a HIP device; this package has no CPU path")
         self.S, self.W, self.h, self.w, self.tcap, self.dcap = n_streams, window, h, w, tcap, dcap
@@ -108,6 +118,9 @@ class HotLoop:
         if obstacles is not None and (fused_step or overlap != 1 or not keep_snapshots):
             raise ValueError('obstacles="%s" needs keep_snapshots=True and the stage launches (fused_step=True and overlap > 1 '
                              'plan without obstacles)' % obstacles)
+        if calibration is not None and (fused_step or overlap != 1):
+            raise ValueError("calibration= needs the stage launches (fused_step=True and overlap > 1 plan without obstacles and "
+                             "lane paths)")
         self._obs_mode = obstacles                # None | "tracks" | "moving_tracks" | "filtered_tracks" | "given" (set_obstacles)
         self.track_filter = self.track_filt = None
         self.obstacles = self.n_obs = self.ref_paths = self.n_ref = None
@@ -116,10 +129,21 @@ class HotLoop:
         self._lanes = self.lane_offset = None                       # set_lane_inputs
         self._ext_streams = {}
         self.tag_log = None                                         # enable_tag_log
+        self.calibration = self.ground = self.n_off = None
+        if calibration is not None:
+            from .perception.calibration import ground_table
+            scales = sorted(k for k in ("x_center", "x_scale", "y_far", "y_scale") if k in self._obstacle_kw)
+            if scales:
+                raise ValueError("obstacle_kw: %s belong to the linear map; with calibration= only radius and frame_rate are taken"
+                                 % ", ".join(scales))
+            self.ground, self.calibration = ground_table(calibration, S, d)         # uint8 [S, 160]: av_ground_cfg per stream
+            fused_step = False
         if obstacles is not None:
             self.ocfg = self._make_ocfg(obstacles)
             self.obstacles = torch.zeros(S, W, tcap, 3 if obstacles == "tracks" else 5, dtype=f64, device=d)
             self.n_obs = torch.zeros(S, W, dtype=i32, device=d)
+            if self.ground is not None:
+                self.n_off = torch.zeros(S, W, dtype=i32, device=d)
             if obstacles == "filtered_tracks":
                 from .tracking.track_filter import TrackFilter
                 self.track_filter = TrackFilter(S, tcap, ctx=self.ctx, **(track_filter_kw or {}))
@@ -471,6 +495,12 @@ class HotLoop:
         if self._lanes is None:
             raise RuntimeError("enqueue_lane_paths needs set_lane_inputs")
         poly, pts, info, n_points = self._lanes
+        if self.ground is not None:
+            nat.check(self.L.av_lane_paths_ground(self.ctx.handle, stream or self._s, nat.ptr(self.ground), self.S, self.h, self.w,
+                                                  n_points, nat.ptr(poly), nat.ptr(pts), nat.ptr(info), nat.ptr(self.plan_state),
+                                                  self.W, int(self.ref_paths.shape[1]), nat.ptr(self.ref_paths), nat.ptr(self.n_ref),
+                                                  nat.ptr(self.lane_offset)))
+            return
         nat.check(self.L.av_lane_paths(self.ctx.handle, stream or self._s, C.byref(self.ocfg), self.S, self.h, self.w, n_points,
                                        nat.ptr(poly), nat.ptr(pts), nat.ptr(info), nat.ptr(self.plan_state), self.W,
                                        int(self.ref_paths.shape[1]), nat.ptr(self.ref_paths), nat.ptr(self.n_ref),
@@ -518,6 +548,14 @@ class HotLoop:
         track filter's and the Kalman filter's outputs are complete (after the join)."""
         if self._obs_mode not in ("tracks", "moving_tracks", "filtered_tracks"):
             raise RuntimeError('enqueue_obstacles needs HotLoop(obstacles="tracks"), "moving_tracks" or "filtered_tracks"')
+        if self.ground is not None:
+            mode = ("tracks", "moving_tracks", "filtered_tracks").index(self._obs_mode)
+            nat.check(self.L.av_track_obstacles_ground(
+                self.ctx.handle, stream or self._s, C.byref(self.ocfg), nat.ptr(self.ground), self.W, mode,
+                self.frame_rate if mode else 0.0, self.S * self.W, self.tcap, nat.ptr(self.snap), nat.ptr(self.snap_n),
+                nat.ptr(self.track_filt) if mode == 2 else None, nat.ptr(self.plan_state), self.tcap, nat.ptr(self.obstacles),
+                nat.ptr(self.n_obs), nat.ptr(self.n_off)))
+            return
         if self._obs_mode == "filtered_tracks":
             nat.check(self.L.av_track_obstacles_filtered(self.ctx.handle, stream or self._s, C.byref(self.ocfg), self.frame_rate,
                                                          self.S * self.W, self.tcap, nat.ptr(self.snap), nat.ptr(self.snap_n),
@@ -727,6 +765,8 @@ class HotLoop:
             out["wp"] = self.wp.cpu().numpy().reshape(self.S, self.W, self.n_cand, self.n_points, 6)
         if self._obs_mode is not None:
             out["obstacles"], out["n_obs"] = self.obstacles.cpu().numpy(), self.n_obs.cpu().numpy()
+        if self.n_off is not None:
+            out["n_off"] = self.n_off.cpu().numpy()
         if self.track_filt is not None:
             out["track_filt"] = self.track_filt.cpu().numpy()
         if self._src is not None:
@@ -1010,14 +1050,16 @@ class CameraLoop:
 
     def __init__(self, n_streams, h=720, w=1280, model="random:0", precision="fp16", dcap=64, obstacles="moving_tracks",
                  class_map="reference", device=0, tracker_kw=None, kf_kw=None, planner_kw=None, obstacle_kw=None, tags=None,
-                 tag_capacity=4096, view=None, tag_columns=False, names=None, track_filter_kw=None):
+                 tag_capacity=4096, view=None, tag_columns=False, names=None, track_filter_kw=None, calibration=None):
         """model, names: PerceptionLoop's (any YOLOv8 n / s / m model, e.g. "random:0:s"; names for a checkpoint without them).
         class_map: "reference" (the detector's class names -> the reference's eight ids, everything else skipped:
         reference_class_map), None (raw ids) or an explicit int table.  With names that match none of the reference's eight (a
         fine-tuned model's own classes, or the "class<i>" defaults) "reference" therefore skips EVERY detection: the tracker sees
         nothing -- pass class_map=None or a table for such a model.  obstacle_kw: HotLoop's; the defaults stretch the BEV
         panel's 640 x 500 px convention to the frame (x_center = w / 2, x_scale = 0.03 * 640 / w, y_far = 50,
-        y_scale = 50 / h).  obstacles="filtered_tracks" and track_filter_kw: HotLoop's (the per-track Kalman filter; self.hot.track_filt).
+        y_scale = 50 / h).  calibration: HotLoop's (one CameraCalibration or one per camera); the stretched defaults are then not
+        built and obstacle_kw takes radius and frame_rate only.  enqueue_ground_view warps the frames to a bird's-eye view through
+        it.  obstacles="filtered_tracks" and track_filter_kw: HotLoop's (the per-track Kalman filter; self.hot.track_filt).
         tags: None, "motion" or "all" -- every step() also tags its frame behind hot.step() on the hot stream and appends it to
         self.tag_log (a TagLog of tag_capacity frames per camera): "motion" runs the maneuver tagger (with the lanes' offset), the
         interaction tagger (class_map="reference" only: it needs the reference's class ids) and enqueue_tags; "all" runs the scene
@@ -1035,11 +1077,12 @@ class CameraLoop:
             raise ValueError('view is None, "camera" or "demo"')
         self.S, self.h, self.w = n_streams, h, w
         self.cam = PerceptionLoop(n_streams=n_streams, h=h, w=w, device=device, model=model, precision=precision, names=names)
-        ok = dict(x_center=w / 2.0, x_scale=0.03 * 640.0 / w, y_far=50.0, y_scale=50.0 / h)
+        ok = {} if calibration is not None else dict(x_center=w / 2.0, x_scale=0.03 * 640.0 / w, y_far=50.0, y_scale=50.0 / h)
         ok.update(obstacle_kw or {})
         self.hot = HotLoop(n_streams=n_streams, window=1, h=h, w=w, dcap=dcap, device=device, tracker_kw=tracker_kw, kf_kw=kf_kw,
                            planner_kw=planner_kw, ctx=self.cam.ctx, fused_step=False, obstacles=obstacles, obstacle_kw=ok,
-                           keep_waypoints=True, keep_snapshots=True, track_filter_kw=track_filter_kw)          # what enqueue_bev / enqueue_view read
+                           keep_waypoints=True, keep_snapshots=True, track_filter_kw=track_filter_kw,
+                           calibration=calibration)          # what enqueue_bev / enqueue_view read
         if isinstance(class_map, str):
             if class_map != "reference":
                 raise ValueError('class_map is "reference", None or an int table')
@@ -1060,6 +1103,7 @@ class CameraLoop:
             self._elem_table = torch.as_tensor(element_table(c.yolo.names)).to(self.hot.dev) if tags == "all" else None
         self.view_mode, self.view_fps = view, 0.0
         self.view = self.view_cam = None
+        self.ground_view = None                 # enqueue_ground_view
         if view is not None:
             self._setup_view()
 
@@ -1131,6 +1175,22 @@ class CameraLoop:
                 hot.enqueue_bev()
             nat.check(L.av_view_compose(h, st, S, nat.ptr(self.view_cam) if staged else None, self.h, self.w, nat.ptr(hot.bev), bh, bw,
                                         nat.ptr(self.view), self.VIEW_LABELS[0].encode(), self.VIEW_LABELS[1].encode()))
+
+    def enqueue_ground_view(self, gh=500, gw=640, f_far=50.0, m_per_px=0.1, fill=(0, 0, 0)):
+        """The frames of the last step() seen from above, on the hot stream (call it behind step(); the next cam.step() waits for
+        that stream): self.ground_view uint8 [S, gh, gw, 3], row 0 at f_far metres ahead, m_per_px metres per pixel, the camera's
+        axis down the middle column (av_ground_warp through every camera's own calibration; `fill` where the road point is above
+        the horizon or outside the frame).  cam.frames is read, never written."""
+        hot = self.hot
+        if hot.ground is None:
+            raise RuntimeError("enqueue_ground_view needs CameraLoop(calibration=...)")
+        gh, gw = int(gh), int(gw)
+        if self.ground_view is None or tuple(self.ground_view.shape[1:3]) != (gh, gw):
+            with torch.cuda.stream(hot.stream):         # zero-filled on the stream that writes it
+                self.ground_view = torch.zeros(self.S, gh, gw, 3, dtype=torch.uint8, device=hot.dev)
+        nat.check(hot.L.av_ground_warp(hot.ctx.handle, hot._s, nat.ptr(hot.ground), self.S, self.h, self.w, nat.ptr(self.cam.frames),
+                                       gh, gw, float(f_far), float(m_per_px), (C.c_uint8 * 3)(*[int(c) for c in fill]),
+                                       nat.ptr(self.ground_view)))
 
     def load_measurements(self, z):
         """z: float64 [S, 1, 4] (or [S, 4]) ego measurements of the next step (HotLoop.load_measurements)."""

@@ -1,4 +1,4 @@
 from multimodal_autonomous_driving_perception_and_planning_amd.perception import (  # noqa: F401
-    Detection, LaneDetector, LaneLine, ObjectDetector)
+    CameraCalibration, Detection, LaneDetector, LaneLine, ObjectDetector)
 
-__all__ = ["ObjectDetector", "LaneDetector"]
+__all__ = ["ObjectDetector", "LaneDetector", "CameraCalibration"]
