@@ -399,7 +399,7 @@ int av_lane_paths(av_ctx* ctx, av_stream_t stream, const av_obstacle_cfg* cfg, i
 /* ---- The camera model: a ground-plane homography per camera (opt-in; the reference has no camera, and av_obstacle_cfg's four
  * numbers are the BEV panel's drawing convention) ----------------------------------------------------------------------------
  * A flat road seen by a pinhole camera is a plane-to-plane projection: image (u, v, 1) -> g (u, v, 1)^T = (F, L, D),
- * forward = F / D, lateral = L / D in metres.  Frames are taken as rectified (no lens distortion).
+ * forward = F / D, lateral = L / D in metres.  (u, v) is a RECTIFIED pixel; for raw frames see av_lens_cfg below.
  * Projection of an image point (float64, every operation rounded on its own: no FMA):
  *   F = (g0*u + g1*v) + g2;  L = (g3*u + g4*v) + g5;  D = (g6*u + g7*v) + g8
  *   f = F / D;  l = L / D
@@ -457,6 +457,71 @@ int av_lane_paths_ground(av_ctx* ctx, av_stream_t stream, const av_ground_cfg* g
  * ceil(gh / 16) <= 65535: AV_EINVAL otherwise. */
 int av_ground_warp(av_ctx* ctx, av_stream_t stream, const av_ground_cfg* ground, int n_cams, int h, int w, const uint8_t* bgr,
                    int gh, int gw, double f_far, double m_per_px, const uint8_t fill[3], uint8_t* out);
+
+/* ---- Lens distortion (opt-in): OpenCV's five-coefficient Brown-Conrady model in front of the ground-plane homography ---------
+ * A raw pixel (u, v) has normalised coordinates (xd, yd) = ((u - cx) / fx, (v - cy) / fy); the undistorted point (x, y) is shown
+ * at the rectified pixel (nfx*x + ncx, nfy*y + ncy).  Pixel c sits at u = c, as av_ground_warp indexes.  float64, every operation
+ * rounded on its own (no FMA), in exactly this order:
+ *   r2   = x*x + y*y
+ *   rad  = 1 + r2*(k1 + r2*(k2 + r2*k3))
+ *   xd   = x*rad + (2*p1*x*y + p2*(r2 + 2*x*x))          2*p1*x*y = ((2*p1)*x)*y, 2*x*x = (2*x)*x, and so on, left to right
+ *   yd   = y*rad + (p1*(r2 + 2*y*y) + 2*p2*x*y)
+ *   drad = k1 + r2*(2*k2 + r2*(3*k3))                    d rad / d r2
+ *   a = rad + 2*x*x*drad + (2*p1*y + 6*p2*x)             d xd / dx      (a = (rad + ((2*x)*x)*drad) + (..))
+ *   b = 2*x*y*drad + (2*p1*x + 2*p2*y)                   d xd / dy = d yd / dx
+ *   d = rad + 2*y*y*drad + (6*p1*y + 2*p2*x)             d yd / dy
+ * Undistorting a raw pixel: Newton's method from (x, y) = (xd, yd), exactly six iterations of
+ *   ex = xd(x, y) - xd;  ey = yd(x, y) - yd;  det = a*d - b*b
+ *   x' = x - (d*ex - b*ey) / det;  y' = y - (a*ey - b*ex) / det
+ * then the model once more at the result: valid = det > 0 at all seven points && ex*ex + ey*ey <= 1e-20   (a NaN fails).
+ * The Jacobian raw pixel -> rectified pixel at the result is the inverse of [[a, b], [b, d]], scaled:
+ *   juu = (d / det) * (nfx / fx);  juv = (-b / det) * (nfx / fy);  jvu = (-b / det) * (nfy / fx);  jvv = (a / det) * (nfy / fy) */
+typedef struct {
+    double fx, fy, cx, cy;          /* the raw frame's intrinsics */
+    double k1, k2, p1, p2, k3;      /* OpenCV's order */
+    double nfx, nfy, ncx, ncy;      /* the rectified picture's intrinsics */
+    int32_t w, h;                   /* frame size, raw and rectified */
+} av_lens_cfg;                      /* 112 bytes */
+/* Fills *out.  K = (fx, fy, cx, cy); dist = (k1, k2, p1, p2, k3); new_K = the rectified picture's four, or NULL for K.
+ * AV_EINVAL, *out untouched: an entry not finite; a focal length not > 0; w or h not in 1 .. 32768; a model that folds over inside
+ * the rectified frame: q = 1 + r2*(3*k1 + r2*(5*k2 + r2*(7*k3))) <= 0 (the radial map's derivative) at r = rmax * i / 1024 for any
+ * i = 1 .. 1024, rmax the largest normalised radius of the rectified frame's four corner pixels.  Host only: no context, no GPU. */
+int av_lens_make(const double K[4], const double dist[5], const double new_K[4], int w, int h, av_lens_cfg* out);
+
+/* The table that rectifies a frame (cold path, once per lens): map int32 [n_maps][h][w][2], lens DEVICE [n_maps].  Rectified
+ * pixel (r, c) of map k, through lens[k]:
+ *   x = ((double)c - ncx) / nfx;  y = ((double)r - ncy) / nfy;  (xd, yd) as above;  u = fx*xd + cx;  v = fy*yd + cy
+ *   tu = floor(u * 65536.0 + 0.5);  tv likewise
+ *   entry = (tu, tv) if 0 <= tu <= (w-1) * 65536 && 0 <= tv <= (h-1) * 65536, else (-1, -1)
+ * A table entry whose own w, h are not the arguments' gives a map of (-1, -1) throughout.
+ * n_maps >= 1, 1 <= h, w <= 32768, n_maps and ceil(h / 16) <= 65535: AV_EINVAL otherwise. */
+int av_lens_map_rectify(av_ctx* ctx, av_stream_t stream, const av_lens_cfg* lens, int n_maps, int h, int w, int32_t* map);
+
+/* The table of the bird's-eye view taken straight from RAW frames (cold path): map [n_maps][gh][gw][2].  Panel pixel (r, c) of
+ * map k: the road point and ground[k].ginv exactly as av_ground_warp, !(D > 0): (-1, -1); the rectified (u, v) = (U / D, V / D);
+ * then x = (u - ncx) / nfx, y = (v - ncy) / nfy through lens[k] to the raw frame as av_lens_map_rectify, within lens[k]'s w, h.
+ * gh, gw >= 1, m_per_px > 0 and finite, f_far finite, n_maps and ceil(gh / 16) <= 65535: AV_EINVAL otherwise. */
+int av_lens_map_ground(av_ctx* ctx, av_stream_t stream, const av_lens_cfg* lens, const av_ground_cfg* ground, int n_maps, int gh,
+                       int gw, double f_far, double m_per_px, int32_t* map);
+
+/* The hot path: out pixel (r, c) of camera k is the source picture at map[k / cam_stride][r][c] = (tu, tv), 1/65536 pixels:
+ *   x0 = tu >> 16, wx = tu & 65535, x1 = min(x0 + 1, sw - 1); y likewise; each channel by av_ground_warp's bilinear rule
+ *   an entry outside [0, (sw-1) * 65536] x [0, (sh-1) * 65536] (a builder's (-1, -1), or anything else): fill
+ *   map DEVICE [ceil(n_cams / cam_stride)][dh][dw][2], bgr [n_cams][sh][sw][3], fill: three HOST bytes, out [n_cams][dh][dw][3]
+ * Integer arithmetic only.  n_cams, dh, dw >= 1 (any width), 1 <= sh, sw <= 32768, cam_stride >= 1, n_cams and ceil(dh / 16)
+ * <= 65535, out overlapping neither bgr nor map: AV_EINVAL otherwise, before any launch. */
+int av_remap(av_ctx* ctx, av_stream_t stream, const int32_t* map, int n_cams, int cam_stride, int sh, int sw, const uint8_t* bgr,
+             int dh, int dw, const uint8_t fill[3], uint8_t* out);
+
+/* av_track_obstacles_ground for tracks given in RAW pixels: lens is a DEVICE table beside ground, under the same cam_stride.
+ * The foot point (u, v) of av_track_obstacles_ground is undistorted as above and the rectified pixel is projected; a foot that is
+ * not valid counts as not on_road (n_off).  The pixel velocity goes through the undistortion's Jacobian first,
+ *   qvx = juu*rvx + juv*rvy;  qvy = jvu*rvx + jvv*rvy
+ * and (qvx, qvy) through the ground Jacobian at the rectified foot.  Everything else, and every check, as there. */
+int av_track_obstacles_ground_lens(av_ctx* ctx, av_stream_t stream, const av_obstacle_cfg* cfg, const av_ground_cfg* ground,
+                                   const av_lens_cfg* lens, int cam_stride, int mode, double frame_rate, int n_states, int tcap,
+                                   const av_track_row* snap, const int32_t* snap_n, const double* filt, const double* plan_state,
+                                   int ocap, double* obstacles, int32_t* n_obs, int32_t* n_off);
 
 /* generate_polynomial_trajectory for arbitrary (lateral offset, target speed) pairs (:126-204).
  *   state [n_traj][4], end_lateral_offset [n_traj], target_velocity [n_traj] -> waypoints [n_traj][n][6] */

@@ -8,7 +8,7 @@ __version__ = "0.1.0"
 
 from . import _native  # noqa: F401  (does not load the library until first use)
 
-__all__ = ["CameraCalibration"]
+__all__ = ["CameraCalibration", "LensModel"]
 
 
 def __getattr__(name):
@@ -16,4 +16,7 @@ def __getattr__(name):
     if name == "CameraCalibration":
         from .perception.calibration import CameraCalibration
         return CameraCalibration
+    if name == "LensModel":
+        from .perception.calibration import LensModel
+        return LensModel
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

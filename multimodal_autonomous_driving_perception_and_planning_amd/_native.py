@@ -54,6 +54,12 @@ class GroundCfg(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class LensCfg(C.Structure):
+    """av_lens_cfg: one camera's Brown-Conrady lens (raw intrinsics, k1 k2 p1 p2 k3, the rectified picture's intrinsics, size)."""
+    _fields_ = [(n, C.c_double) for n in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3", "nfx", "nfy", "ncx", "ncy")] + [
+        ("w", C.c_int32), ("h", C.c_int32)]
+
+
 class TrackFilterCfg(C.Structure):
     """av_track_filter_cfg: the per-track constant-velocity Kalman filter's noise and initial variances (px, frames)."""
     _fields_ = [("q_accel", C.c_double), ("r_meas", C.c_double), ("p0_pos", C.c_double), ("p0_vel", C.c_double)]
@@ -277,6 +283,12 @@ _SIGS = [
                                        vp]),
     ("av_ground_warp", C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double,
                                  C.POINTER(C.c_uint8), vp]),
+    ("av_lens_make", C.c_int, [c_f64p, c_f64p, c_f64p, C.c_int, C.c_int, C.POINTER(LensCfg)]),
+    ("av_lens_map_rectify", C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    ("av_lens_map_ground", C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, vp]),
+    ("av_remap", C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.POINTER(C.c_uint8), vp]),
+    ("av_track_obstacles_ground_lens", C.c_int, [vp, vp, C.POINTER(ObstacleCfg), vp, vp, C.c_int, C.c_int, C.c_double, C.c_int,
+                                                 C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp]),
     ("av_hot_step", C.c_int, [vp, vp, C.POINTER(StepLoop), C.POINTER(StepSet), vp, C.c_int, C.c_int]),
     ("av_hot_step_fits", C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     ("av_hot_step_plan", C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),

@@ -23,10 +23,16 @@
 // scales: the row's foot point (av_ground_cfg.anchor) goes through the ground-plane homography of the state's camera (entry
 // f / cam_stride of a device table), a row whose foot is not on the road is dropped and counted in n_off, and the pixel velocity
 // is carried to metres per second by the projection's Jacobian at the foot.  The table entry is the same for a whole wave.
+//
+// The lens form (av_track_obstacles_ground_lens) takes the rows in RAW pixels: the foot is undistorted first (lens_dev.h: six
+// Newton iterations on the Brown-Conrady model of the state's camera), a foot with no valid preimage is off the road, and the
+// pixel velocity goes through the undistortion's Jacobian before the projection's.
 #include "common.h"
 #include "ground_dev.h"
+#include "lens_dev.h"
 
 #include <cmath>
+#include <type_traits>
 
 namespace {
 
@@ -39,10 +45,16 @@ struct Ground {
     int cam_stride;                 // state f uses table[f / cam_stride]
     int32_t* n_off;                 // [n_states] or NULL
 };
+struct GroundLens {
+    const av_ground_cfg* table;     // as Ground
+    int cam_stride;
+    int32_t* n_off;
+    const av_lens_cfg* lens;        // device [n_cams], beside table: the rows are raw pixels
+};
 
 // MODE != STATIC: rows of 5 doubles, frame_rate in frames per second (unused otherwise); FILTERED: centre and velocity of row i
 // from filt [n_states][tcap][6] (cx, cy, vx, vy, ., .), NULL otherwise
-// VIA = Ground: cfg's radius[] only, the place and the velocity through the camera VIA names
+// VIA = Ground / GroundLens: cfg's radius[] only, the place and the velocity through the camera VIA names
 template <int MODE, typename VIA>
 __global__ void __launch_bounds__(256) track_obstacles_kernel(av_obstacle_cfg cfg, double frame_rate, int n_states, int tcap,
                                                               const av_track_row* __restrict__ snap,
@@ -52,6 +64,7 @@ __global__ void __launch_bounds__(256) track_obstacles_kernel(av_obstacle_cfg cf
                                                               const double* __restrict__ filt, VIA via) {
     constexpr bool MOVING = MODE != STATIC;
     constexpr bool GROUND = sizeof(VIA) > 1;
+    constexpr bool LENS = std::is_same<VIA, GroundLens>::value;
     const int lane = threadIdx.x & 63;
     const long long fl = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (fl >= n_states) return;
@@ -70,7 +83,9 @@ __global__ void __launch_bounds__(256) track_obstacles_kernel(av_obstacle_cfg cf
     int count = 0;                                                  // obstacles of the rows before this round
     int off = 0;                                                    // GROUND: rows dropped because their foot is not on the road
     const av_ground_cfg* cam = nullptr;
+    const av_lens_cfg* lens = nullptr;
     if constexpr (GROUND) cam = via.table + f / via.cam_stride;
+    if constexpr (LENS) lens = via.lens + f / via.cam_stride;
     for (int b = 0; b < n; b += 64) {
         const int i = b + lane;
         bool keep = false, off_road = false;
@@ -90,6 +105,7 @@ __global__ void __launch_bounds__(256) track_obstacles_kernel(av_obstacle_cfg cf
             }
             double l, fw;
             grounddev::RoadPoint p;
+            lensdev::Undistorted rect;
             if constexpr (GROUND) {
                 // the foot point: anchor 1 = bottom centre (filtered: the filter's centre lowered by half the box height)
                 double u = cx, v = cy;
@@ -97,7 +113,13 @@ __global__ void __launch_bounds__(256) track_obstacles_kernel(av_obstacle_cfg cf
                     if constexpr (MODE == FILTERED) v = cy + (double)(r.y2 - r.y1) / 2.0;
                     else v = (double)r.y2;
                 }
+                if constexpr (LENS) {
+                    // (u, v) is a raw pixel: the rectified one stands on the road, if the lens has it at all
+                    rect = lensdev::undistort(lens, u, v);
+                    u = rect.u, v = rect.v;
+                }
                 p = grounddev::project(cam->g, cam->max_range, u, v);
+                if constexpr (LENS) p.on_road = p.on_road && rect.valid;
                 l = p.l, fw = p.f;
                 off_road = keep && !p.on_road;
                 keep = keep && p.on_road;
@@ -108,8 +130,13 @@ __global__ void __launch_bounds__(256) track_obstacles_kernel(av_obstacle_cfg cf
             oy = (y0 + fw * sn) + l * s2;
             if constexpr (MOVING) {
                 const bool has_vel = r.hist_len >= 2;               // (vx, vy are valid from the second centre on)
-                const double rvx = MODE == FILTERED ? fvx : (has_vel ? (double)r.vx : 0.0);   // (a newborn's filtered velocity is 0)
-                const double rvy = MODE == FILTERED ? fvy : (has_vel ? (double)r.vy : 0.0);
+                double rvx = MODE == FILTERED ? fvx : (has_vel ? (double)r.vx : 0.0);   // (a newborn's filtered velocity is 0)
+                double rvy = MODE == FILTERED ? fvy : (has_vel ? (double)r.vy : 0.0);
+                if constexpr (LENS) {
+                    const lensdev::LensJac j = lensdev::jacobian(lens, rect);       // rectified px per raw px at the foot
+                    const double qvx = j.juu * rvx + j.juv * rvy, qvy = j.jvu * rvx + j.jvv * rvy;
+                    rvx = qvx, rvy = qvy;
+                }
                 double vl, vf;
                 if constexpr (GROUND) {
                     const grounddev::RoadJac j = grounddev::jacobian(cam->g, p);     // metres per pixel at the foot
@@ -187,6 +214,26 @@ extern "C" int av_track_obstacles_ground(av_ctx* ctx, av_stream_t stream, const 
     AV_REQUIRE(mode >= STATIC && mode <= FILTERED, AV_EINVAL, "%s: mode %d not in 0..2", who, mode);
     AV_REQUIRE((mode == FILTERED) == (filt != nullptr), AV_EINVAL, "%s: filt goes with mode 2 and with no other", who);
     const Ground via{ground, cam_stride, n_off};
+    if (mode == FILTERED)
+        return track_obstacles_launch<FILTERED>(ctx, stream, cfg, frame_rate, n_states, tcap, snap, snap_n, plan_state, ocap, obstacles,
+                                                n_obs, filt, who, via);
+    if (mode == MOVING_ROWS)
+        return track_obstacles_launch<MOVING_ROWS>(ctx, stream, cfg, frame_rate, n_states, tcap, snap, snap_n, plan_state, ocap,
+                                                   obstacles, n_obs, nullptr, who, via);
+    return track_obstacles_launch<STATIC>(ctx, stream, cfg, 0.0, n_states, tcap, snap, snap_n, plan_state, ocap, obstacles, n_obs,
+                                          nullptr, who, via);
+}
+
+extern "C" int av_track_obstacles_ground_lens(av_ctx* ctx, av_stream_t stream, const av_obstacle_cfg* cfg, const av_ground_cfg* ground,
+                                              const av_lens_cfg* lens, int cam_stride, int mode, double frame_rate, int n_states,
+                                              int tcap, const av_track_row* snap, const int32_t* snap_n, const double* filt,
+                                              const double* plan_state, int ocap, double* obstacles, int32_t* n_obs, int32_t* n_off) {
+    const char* who = "av_track_obstacles_ground_lens";
+    AV_REQUIRE(ground && lens, AV_EINVAL, "%s: null argument", who);
+    AV_REQUIRE(cam_stride >= 1, AV_EINVAL, "%s: cam_stride must be >= 1", who);
+    AV_REQUIRE(mode >= STATIC && mode <= FILTERED, AV_EINVAL, "%s: mode %d not in 0..2", who, mode);
+    AV_REQUIRE((mode == FILTERED) == (filt != nullptr), AV_EINVAL, "%s: filt goes with mode 2 and with no other", who);
+    const GroundLens via{ground, cam_stride, n_off, lens};
     if (mode == FILTERED)
         return track_obstacles_launch<FILTERED>(ctx, stream, cfg, frame_rate, n_states, tcap, snap, snap_n, plan_state, ocap, obstacles,
                                                 n_obs, filt, who, via);

@@ -1,5 +1,5 @@
-from .calibration import CameraCalibration
+from .calibration import CameraCalibration, LensModel
 from .detector import Detection, ObjectDetector
 from .lane_detector import LaneDetector, LaneLine
 
-__all__ = ["ObjectDetector", "LaneDetector", "Detection", "LaneLine", "CameraCalibration"]
+__all__ = ["ObjectDetector", "LaneDetector", "Detection", "LaneLine", "CameraCalibration", "LensModel"]

@@ -2,7 +2,9 @@
 
 A flat road seen by a pinhole camera is a plane-to-plane projection, so image (u, v) and road (forward, lateral) in metres are
 related by a 3 x 3 matrix g up to scale: g (u, v, 1)^T = (F, L, D), forward = F / D, lateral = L / D, lateral > 0 towards the
-image's right.  D > 0 means below the horizon and in front of the camera.  Frames are taken as rectified (no lens distortion).
+image's right.  D > 0 means below the horizon and in front of the camera.  g is defined on RECTIFIED pixels; a LensModel
+(OpenCV's five-coefficient Brown-Conrady distortion, include/avhot.h: av_lens_cfg) beside it says how the raw frame's pixels
+relate to them.
 
 The reference has no camera model; its BEVRenderer places a track by forward = 50 - cy * 0.1, lateral = (cx - 320) * 0.03
 (bev_renderer.py:207-208), which from_linear restates as a (degenerate) homography.
@@ -17,10 +19,123 @@ _ANCHORS = {"centre": 0, "center": 0, "bottom": 1}
 LINEAR_MAX_RANGE = 1.0e9        # from_linear: the linear map has no horizon and no range limit; av_ground_cfg wants a finite one
 
 
+_OTHER_MODELS = {8: "rational (k4..k6)", 12: "thin-prism (s1..s4)", 14: "tilted-sensor (tau)"}
+
+
+class LensModel:
+    """OpenCV's five-coefficient Brown-Conrady lens: raw pixel <-> rectified pixel (av_lens_cfg; the operation order is the
+    header's, every operation rounded on its own)."""
+
+    def __init__(self, fx, fy, cx, cy, dist=(0.0, 0.0, 0.0, 0.0, 0.0), size=None, new_K=None, model="brown"):
+        """fx, fy, cx, cy: the raw frame's intrinsics (pixel c sits at u = c).  dist: (k1, k2, p1, p2, k3), OpenCV's order.
+        size: (w, h) of the frames.  new_K: (fx, fy, cx, cy) of the rectified picture, None for the raw ones."""
+        if model != "brown":
+            raise ValueError('LensModel: the %s model is not supported (the five-coefficient "brown" model only: no rational, '
+                             "thin-prism or fisheye terms)" % (model,))
+        dist = np.asarray(dist, dtype=np.float64).reshape(-1)
+        if dist.size != 5:
+            raise ValueError("LensModel: dist is (k1, k2, p1, p2, k3); %d coefficients%s" % (
+                dist.size, " are OpenCV's %s model, which is not supported" % _OTHER_MODELS[dist.size]
+                if dist.size in _OTHER_MODELS else (" could be OpenCV's fisheye model, which is not supported" if dist.size == 4 else "")))
+        if size is None or len(size) != 2:
+            raise ValueError("LensModel: size=(w, h) of the frames is needed")
+        self.K = tuple(float(v) for v in (fx, fy, cx, cy))
+        self.dist = tuple(float(v) for v in dist)
+        self.size = (int(size[0]), int(size[1]))
+        if new_K is not None and len(new_K) != 4:
+            raise ValueError("LensModel: new_K is (fx, fy, cx, cy)")
+        self.new_K = self.K if new_K is None else tuple(float(v) for v in new_K)
+        self._cfg = self._make()            # (validates: av_lens_make's refusals, with its messages)
+
+    def _make(self):
+        out = nat.LensCfg()
+        rc = nat.lib().av_lens_make((C.c_double * 4)(*self.K), (C.c_double * 5)(*self.dist), (C.c_double * 4)(*self.new_K),
+                                    self.size[0], self.size[1], C.byref(out))
+        if rc != 0:
+            raise ValueError(nat.lib().av_last_error_string().decode())
+        return out
+
+    def cfg(self):
+        """A fresh nat.LensCfg (av_lens_make's output)."""
+        return self._make()
+
+    def key(self):
+        return (self.K, self.dist, self.new_K, self.size)
+
+    def __eq__(self, other):
+        return isinstance(other, LensModel) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    # ---- the model in NumPy (vectorised) ----------------------------------------------------------------------------------
+    def _model(self, x, y):
+        k1, k2, p1, p2, k3 = (np.float64(v) for v in self.dist)
+        r2 = x * x + y * y
+        rad = 1 + r2 * (k1 + r2 * (k2 + r2 * k3))
+        xd = x * rad + (2 * p1 * x * y + p2 * (r2 + 2 * x * x))
+        yd = y * rad + (p1 * (r2 + 2 * y * y) + 2 * p2 * x * y)
+        drad = k1 + r2 * (2 * k2 + r2 * (3 * k3))
+        a = rad + 2 * x * x * drad + (2 * p1 * y + 6 * p2 * x)
+        b = 2 * x * y * drad + (2 * p1 * x + 2 * p2 * y)
+        d = rad + 2 * y * y * drad + (6 * p1 * y + 2 * p2 * x)
+        return xd, yd, a, b, d
+
+    def distort(self, uv):
+        """[..., 2] rectified pixels -> [..., 2] raw pixels (the forward model)."""
+        uv = np.asarray(uv, dtype=np.float64)
+        fx, fy, cx, cy = (np.float64(v) for v in self.K)
+        nfx, nfy, ncx, ncy = (np.float64(v) for v in self.new_K)
+        xd, yd = self._model((uv[..., 0] - ncx) / nfx, (uv[..., 1] - ncy) / nfy)[:2]
+        return np.stack([fx * xd + cx, fy * yd + cy], axis=-1)
+
+    def _newton(self, uv):
+        uv = np.asarray(uv, dtype=np.float64)
+        fx, fy, cx, cy = (np.float64(v) for v in self.K)
+        xd, yd = (uv[..., 0] - cx) / fx, (uv[..., 1] - cy) / fy
+        x, y = xd.copy(), yd.copy()
+        ok = np.ones(x.shape, dtype=bool)
+        with np.errstate(all="ignore"):
+            for _ in range(6):
+                mx, my, a, b, d = self._model(x, y)
+                ex, ey = mx - xd, my - yd
+                det = a * d - b * b
+                ok &= det > 0.0
+                x, y = x - (d * ex - b * ey) / det, y - (a * ey - b * ex) / det
+            mx, my, a, b, d = self._model(x, y)
+            ex, ey = mx - xd, my - yd
+            det = a * d - b * b
+            ok &= (det > 0.0) & (ex * ex + ey * ey <= 1e-20)
+        return x, y, a, b, d, det, ok
+
+    def undistort(self, uv):
+        """[..., 2] raw pixels -> ([..., 2] rectified pixels, [...] valid): six Newton iterations, as the device does."""
+        nfx, nfy, ncx, ncy = (np.float64(v) for v in self.new_K)
+        x, y, _, _, _, _, ok = self._newton(uv)
+        return np.stack([nfx * x + ncx, nfy * y + ncy], axis=-1), ok
+
+    def jacobian(self, uv):
+        """[..., 2] raw pixels -> [..., 2, 2]: d(rectified pixel) / d(raw pixel) at each."""
+        fx, fy = (np.float64(v) for v in self.K[:2])
+        nfx, nfy = (np.float64(v) for v in self.new_K[:2])
+        _, _, a, b, d, det, _ = self._newton(uv)
+        with np.errstate(all="ignore"):
+            J = np.stack([np.stack([(d / det) * (nfx / fx), (-b / det) * (nfx / fy)], axis=-1),
+                          np.stack([(-b / det) * (nfy / fx), (a / det) * (nfy / fy)], axis=-1)], axis=-2)
+        return J
+
+    def __repr__(self):
+        return "LensModel(K=%r, dist=%r, size=%r, new_K=%r)" % (self.K, self.dist, self.size, self.new_K)
+
+
 class CameraCalibration:
-    def __init__(self, g, max_range=80.0, anchor="bottom"):
-        """g: 3 x 3, image (u, v, 1) -> (F, L, D).  max_range: metres, > 0 and finite; a foot point farther ahead is off the
-        road.  anchor: which point of a box touches the road, "bottom" (bottom centre) or "centre"."""
+    def __init__(self, g, max_range=80.0, anchor="bottom", lens=None):
+        """g: 3 x 3, RECTIFIED image (u, v, 1) -> (F, L, D).  max_range: metres, > 0 and finite; a foot point farther ahead is off
+        the road.  anchor: which point of a box touches the road, "bottom" (bottom centre) or "centre".  lens: a LensModel, if the
+        camera's frames (and the boxes found in them) are raw, None if they are rectified."""
+        if lens is not None and not isinstance(lens, LensModel):
+            raise ValueError("lens is a LensModel or None")
+        self.lens = lens
         g = np.asarray(g, dtype=np.float64)
         if g.shape != (3, 3):
             raise ValueError("g is a 3 x 3 matrix")
@@ -46,16 +161,23 @@ class CameraCalibration:
 
     # ---- constructors ------------------------------------------------------------------------------------------------------
     @classmethod
-    def from_pose(cls, fx, fy, cx, cy, height, pitch=0.0, max_range=80.0, anchor="bottom"):
+    def from_pose(cls, fx, fy, cx, cy, height, pitch=0.0, max_range=80.0, anchor="bottom", dist=None, size=None):
         """A pinhole camera (focal lengths fx, fy and principal point cx, cy in pixels) `height` metres above a flat road,
         pitched down by `pitch` radians (positive = down); no roll, no yaw.  g = inv(P), P the road -> image matrix
-          [[cx cos t, fx, cx H sin t], [cy cos t - fy sin t, 0, (fy cos t + cy sin t) H], [cos t, 0, H sin t]]."""
+          [[cx cos t, fx, cx H sin t], [cy cos t - fy sin t, 0, (fy cos t + cy sin t) H], [cos t, 0, H sin t]].
+        dist = (k1, k2, p1, p2, k3) with size = (w, h): the frames are raw, lens = LensModel(fx, fy, cx, cy, dist, size), and g
+        is defined on the pixels rectified to the same intrinsics."""
         fx, fy, cx, cy, H, t = (float(x) for x in (fx, fy, cx, cy, height, pitch))
         if not (H > 0.0 and fx > 0.0 and fy > 0.0):
             raise ValueError("from_pose: height, fx and fy must be > 0")
         c, s = np.cos(t), np.sin(t)
         P = np.array([[cx * c, fx, cx * H * s], [cy * c - fy * s, 0.0, (fy * c + cy * s) * H], [c, 0.0, H * s]])
-        return cls(np.linalg.inv(P), max_range=max_range, anchor=anchor)
+        lens = None if dist is None else LensModel(fx, fy, cx, cy, dist=dist, size=size)
+        return cls(np.linalg.inv(P), max_range=max_range, anchor=anchor, lens=lens)
+
+    def rectified(self):
+        """The same camera on rectified pixels: this calibration without its lens."""
+        return self if self.lens is None else CameraCalibration(self.g, max_range=self.max_range, anchor=self.anchor)
 
     @classmethod
     def from_points(cls, image_pts, ground_pts, max_range=80.0, anchor="bottom"):
@@ -109,15 +231,21 @@ class CameraCalibration:
         return cls([[0.0, -ys, yf], [xs, 0.0, -xc * xs], [0.0, 0.0, 1.0]], max_range=max_range, anchor="centre")
 
     # ---- the projection in NumPy (vectorised; the operation order is the header's) --------------------------------------------
-    def image_to_ground(self, uv):
-        """[..., 2] image points -> ([..., 2] (forward, lateral), [...] on_road)."""
+    def image_to_ground(self, uv, raw=False):
+        """[..., 2] image points -> ([..., 2] (forward, lateral), [...] on_road).  raw: the points are raw pixels, undistorted
+        through self.lens first (a point with no valid preimage is not on the road)."""
         uv = np.asarray(uv, dtype=np.float64)
+        valid = True
+        if raw:
+            if self.lens is None:
+                raise ValueError("image_to_ground(raw=True) needs a calibration with a lens")
+            uv, valid = self.lens.undistort(uv)
         g = self.g.reshape(9)
         u, v = uv[..., 0], uv[..., 1]
         with np.errstate(divide="ignore", invalid="ignore"):
             F, L, D = (g[0] * u + g[1] * v) + g[2], (g[3] * u + g[4] * v) + g[5], (g[6] * u + g[7] * v) + g[8]
             f, l = F / D, L / D
-            on = (D > 0.0) & (f >= 0.0) & (f <= self.max_range)
+            on = (D > 0.0) & (f >= 0.0) & (f <= self.max_range) & valid
         return np.stack([f, l], axis=-1), on
 
     def ground_to_image(self, fl):
@@ -131,7 +259,8 @@ class CameraCalibration:
         return uv, D > 0.0
 
     def __repr__(self):
-        return "CameraCalibration(g=%r, max_range=%r, anchor=%r)" % (self.g.tolist(), self.max_range, self.anchor)
+        return "CameraCalibration(g=%r, max_range=%r, anchor=%r%s)" % (self.g.tolist(), self.max_range, self.anchor,
+                                                                       "" if self.lens is None else ", lens=%r" % (self.lens,))
 
 
 def ground_table(calibrations, n, device):
@@ -144,3 +273,27 @@ def ground_table(calibrations, n, device):
     raw = b"".join(bytes(c.cfg()) for c in cals)
     host = torch.frombuffer(bytearray(raw), dtype=torch.uint8).reshape(n, C.sizeof(nat.GroundCfg))
     return host.to(device), cals
+
+
+def lens_table(lenses, n, device):
+    """One LensModel, or a sequence of n of them -> (a device uint8 tensor [n, 112] of av_lens_cfg entries, the list)."""
+    import torch
+
+    ls = [lenses] * n if isinstance(lenses, LensModel) else list(lenses)
+    if len(ls) != n or not all(isinstance(l, LensModel) for l in ls):
+        raise ValueError("lens is one LensModel or one per stream (%d)" % n)
+    raw = b"".join(bytes(l.cfg()) for l in ls)
+    host = torch.frombuffer(bytearray(raw), dtype=torch.uint8).reshape(n, C.sizeof(nat.LensCfg))
+    return host.to(device), ls
+
+
+def lenses_of(calibrations, n):
+    """The lenses of one calibration or of n of them: None if none has one, a list of n if all have; mixed is refused."""
+    cals = [calibrations] * n if isinstance(calibrations, CameraCalibration) else list(calibrations)
+    have = [getattr(c, "lens", None) is not None for c in cals]
+    if not any(have):
+        return None
+    if not all(have):
+        raise ValueError("calibration: every stream has a lens or none has (streams %s have none)"
+                         % ", ".join(str(i) for i, h in enumerate(have) if not h))
+    return [c.lens for c in cals]

@@ -26,7 +26,9 @@ with no host round trip.
 Opt-in (calibration=, HotLoop and CameraLoop): a camera model per stream (perception.CameraCalibration, a ground-plane
 homography) in place of the linear pixel-to-metre scales: tracks stand where their boxes' feet meet the road
 (av_track_obstacles_ground), lane paths end at the horizon (av_lane_paths_ground), and CameraLoop.enqueue_ground_view warps the
-frames to a bird's-eye view (av_ground_warp).
+frames to a bird's-eye view (av_ground_warp).  Calibrations with a lens (perception.LensModel, Brown-Conrady): a HotLoop takes its
+tracker's boxes as raw pixels (av_track_obstacles_ground_lens); a CameraLoop rectifies every fed frame through a table built
+once (av_lens_map_rectify, av_remap: cam.raw -> cam.frames) and everything behind it sees rectified pixels.
 """
 import ctypes as C
 
@@ -68,7 +70,10 @@ class HotLoop:
         av_ground_cfg) in place of av_obstacle_cfg's four linear scales: the obstacle stage becomes av_track_obstacles_ground in the
         mode `obstacles` names (a track stands where its box's foot meets the road, a foot off the road is no obstacle and is
         counted in self.n_off [S, W], pixel velocities go through the projection's Jacobian), set_lane_inputs' paths go through
-        av_lane_paths_ground.  obstacle_kw may then carry radius and frame_rate only.  Needs the stage launches like obstacles=."""
+        av_lane_paths_ground.  obstacle_kw may then carry radius and frame_rate only.  Needs the stage launches like obstacles=.
+        Calibrations with a lens (all streams, or none): the tracker's boxes are RAW pixels, the obstacle stage is
+        av_track_obstacles_ground_lens (self.lens: the device table beside self.ground), and set_lane_inputs is refused -- lane
+        fits come from rectified frames, which CameraLoop provides."""
         if not torch.cuda.is_available():
             raise RuntimeError("HotLoop needs a HIP device; this package has no CPU path")
         self.S, self.W, self.h, self.w, self.tcap, self.dcap = n_streams, window, h, w, tcap, dcap
@@ -129,14 +134,17 @@ class HotLoop:
         self._lanes = self.lane_offset = None                       # set_lane_inputs
         self._ext_streams = {}
         self.tag_log = None                                         # enable_tag_log
-        self.calibration = self.ground = self.n_off = None
+        self.calibration = self.ground = self.n_off = self.lens = self.lenses = None
         if calibration is not None:
-            from .perception.calibration import ground_table
+            from .perception.calibration import ground_table, lens_table, lenses_of
             scales = sorted(k for k in ("x_center", "x_scale", "y_far", "y_scale") if k in self._obstacle_kw)
             if scales:
                 raise ValueError("obstacle_kw: %s belong to the linear map; with calibration= only radius and frame_rate are taken"
                                  % ", ".join(scales))
             self.ground, self.calibration = ground_table(calibration, S, d)         # uint8 [S, 160]: av_ground_cfg per stream
+            self.lenses = lenses_of(self.calibration, S)
+            if self.lenses is not None:
+                self.lens = lens_table(self.lenses, S, d)[0]                        # uint8 [S, 112]: av_lens_cfg per stream
             fused_step = False
         if obstacles is not None:
             self.ocfg = self._make_ocfg(obstacles)
@@ -468,6 +476,9 @@ class HotLoop:
                 self._lanes = self.ref_paths = self.n_ref = self.lane_offset = None
                 self._drop_graphs()
             return
+        if self.lens is not None:
+            raise ValueError("set_lane_inputs: this loop's calibration has a lens, so its pixels are raw, and lane fits come from "
+                             "rectified frames -- CameraLoop rectifies the frames and feeds both")
         self._need_stage_launches("set_lane_inputs")
         if self._lanes is None and self.ref_paths is not None:
             raise RuntimeError("set_lane_inputs: this loop has caller-supplied reference paths (set_reference_paths)")
@@ -550,11 +561,14 @@ class HotLoop:
             raise RuntimeError('enqueue_obstacles needs HotLoop(obstacles="tracks"), "moving_tracks" or "filtered_tracks"')
         if self.ground is not None:
             mode = ("tracks", "moving_tracks", "filtered_tracks").index(self._obs_mode)
-            nat.check(self.L.av_track_obstacles_ground(
-                self.ctx.handle, stream or self._s, C.byref(self.ocfg), nat.ptr(self.ground), self.W, mode,
-                self.frame_rate if mode else 0.0, self.S * self.W, self.tcap, nat.ptr(self.snap), nat.ptr(self.snap_n),
-                nat.ptr(self.track_filt) if mode == 2 else None, nat.ptr(self.plan_state), self.tcap, nat.ptr(self.obstacles),
-                nat.ptr(self.n_obs), nat.ptr(self.n_off)))
+            tail = (self.W, mode, self.frame_rate if mode else 0.0, self.S * self.W, self.tcap, nat.ptr(self.snap), nat.ptr(self.snap_n),
+                    nat.ptr(self.track_filt) if mode == 2 else None, nat.ptr(self.plan_state), self.tcap, nat.ptr(self.obstacles),
+                    nat.ptr(self.n_obs), nat.ptr(self.n_off))
+            head = (self.ctx.handle, stream or self._s, C.byref(self.ocfg), nat.ptr(self.ground))
+            if self.lens is not None:
+                nat.check(self.L.av_track_obstacles_ground_lens(*head, nat.ptr(self.lens), *tail))
+            else:
+                nat.check(self.L.av_track_obstacles_ground(*head, *tail))
             return
         if self._obs_mode == "filtered_tracks":
             nat.check(self.L.av_track_obstacles_filtered(self.ctx.handle, stream or self._s, C.byref(self.ocfg), self.frame_rate,
@@ -787,9 +801,13 @@ class PerceptionLoop:
     """BASELINE config 3: S camera streams, frames generated on the device, YOLO-mode detector (MFMA conv
     path) + lane detector per frame.  Everything stays in HBM; one enqueue per stage per step."""
 
-    def __init__(self, n_streams=16, h=720, w=1280, device=0, model="random:0", max_segments=512, ctx=None, precision="fp16", names=None):
+    def __init__(self, n_streams=16, h=720, w=1280, device=0, model="random:0", max_segments=512, ctx=None, precision="fp16", names=None,
+                 lens=None):
         """model: a YOLOv8 n / s / m state_dict file, a flat parameter vector or "random[:seed[:scale[:nc]]]" (perception/yolo.py);
-        names: its class names, if the file carries none."""
+        names: its class names, if the file carries none.  lens: one perception.LensModel or one per stream (size = (w, h)) -- the
+        step's input (generated, copied or decoded) then lands in self.raw and av_remap writes its rectified picture into
+        self.frames on the loop's stream before the detector, through a table built here (av_lens_map_rectify: self.lens_map
+        int32 [n_maps, h, w, 2], one map if every stream has the same lens); everything behind sees rectified pixels."""
         if not torch.cuda.is_available():
             raise RuntimeError("PerceptionLoop needs a HIP device; this package has no CPU path")
         from .perception.yolo import MAX_DET, YoloV8
@@ -803,6 +821,10 @@ class PerceptionLoop:
         self.stream = torch.cuda.Stream(device=self.dev, priority=-1)
         S, d = n_streams, self.dev
         self.frames = torch.empty(S, h, w, 3, dtype=torch.uint8, device=d)
+        self.raw = self.lens = self.lenses = self.lens_map = None
+        self.lens_fill = (0, 0, 0)              # rectified pixels that show nothing of the raw frame
+        if lens is not None:
+            self._setup_lens(lens)
         self.ws = torch.empty(int(self.L.av_lane_workspace_bytes(S, h, w, max_segments)), dtype=torch.uint8, device=d)
         nat.check(self.L.av_lane_workspace_init(self.ctx.handle, self._s, S, h, w, max_segments, nat.ptr(self.ws)))
         self.lane_state = torch.zeros(S, 8, dtype=torch.float64, device=d)
@@ -835,27 +857,56 @@ class PerceptionLoop:
     def _s(self):
         return C.c_void_p(self.stream.cuda_stream)
 
+    def _setup_lens(self, lens):
+        from .perception.calibration import lens_table
+        S, h, w, d = self.S, self.h, self.w, self.dev
+        table, self.lenses = lens_table(lens, S, d)
+        for l in self.lenses:
+            if l.size != (w, h):
+                raise ValueError("lens: size %r is not the loop's frame size %r" % (l.size, (w, h)))
+        self.lens = table                                                           # uint8 [S, 112]: av_lens_cfg per stream
+        shared = all(l == self.lenses[0] for l in self.lenses)
+        self.lens_stride = S if shared else 1                                       # camera k reads map k // lens_stride
+        n_maps = 1 if shared else S
+        with torch.cuda.stream(self.stream):
+            self.raw = torch.zeros(S, h, w, 3, dtype=torch.uint8, device=d)
+            self.lens_map = torch.empty(n_maps, h, w, 2, dtype=torch.int32, device=d)
+            nat.check(self.L.av_lens_map_rectify(self.ctx.handle, self._s, nat.ptr(table), n_maps, h, w, nat.ptr(self.lens_map)))
+
+    def enqueue_rectify(self):
+        """self.raw -> self.frames through self.lens_map on the loop's stream (av_remap)."""
+        nat.check(self.L.av_remap(self.ctx.handle, self._s, nat.ptr(self.lens_map), self.S, self.lens_stride, self.h, self.w,
+                                  nat.ptr(self.raw), self.h, self.w, (C.c_uint8 * 3)(*self.lens_fill), nat.ptr(self.frames)))
+
     def enqueue_generate(self, stream0=0):
         nat.check(self.L.av_synth_frames(self.ctx.handle, self._s, self.S, self.h, self.w, stream0, self.frame_idx,
-                                         nat.ptr(self.frames)))
+                                         nat.ptr(self.raw if self.lens is not None else self.frames)))
+        if self.lens is not None:
+            self.enqueue_rectify()
         self.frame_idx += 1
 
     def enqueue_frames(self, frames=None):
         """The step's input on the loop's stream.  None: generate (enqueue_generate).  A uint8 device tensor [S, h, w, 3]: copied into
         self.frames (nothing is enqueued when it IS self.frames); the caller orders whatever produced it before the loop's stream.
-        An object with read_into(dst, stream) -- a loaders.VideoFeed -- decodes straight into self.frames.  frame_idx advances."""
+        An object with read_into(dst, stream) -- a loaders.VideoFeed -- decodes straight into self.frames.  frame_idx advances.
+        With a lens all of that lands in self.raw (the camera's raw frames), and self.frames is its rectified picture."""
         if frames is None:
             return self.enqueue_generate()
+        dst = self.raw if self.lens is not None else self.frames
         if hasattr(frames, "read_into"):
-            frames.read_into(self.frames, self.stream)
+            frames.read_into(dst, self.stream)
         else:
-            if (not torch.is_tensor(frames) or frames.device != self.frames.device or frames.dtype != torch.uint8
-                    or tuple(frames.shape) != tuple(self.frames.shape)):
+            if (not torch.is_tensor(frames) or frames.device != dst.device or frames.dtype != torch.uint8
+                    or tuple(frames.shape) != tuple(dst.shape)):
                 raise ValueError("frames must be a uint8 tensor %s on %s, or an object with read_into()" % (
-                    tuple(self.frames.shape), self.frames.device))
-            if frames.data_ptr() != self.frames.data_ptr() or not frames.is_contiguous():
+                    tuple(dst.shape), dst.device))
+            if self.lens is not None and frames.data_ptr() == self.frames.data_ptr():
+                raise ValueError("frames is the loop's rectified buffer; give raw frames (cam.raw, or a tensor of your own)")
+            if frames.data_ptr() != dst.data_ptr() or not frames.is_contiguous():
                 with torch.cuda.stream(self.stream):
-                    self.frames.copy_(frames, non_blocking=True)
+                    dst.copy_(frames, non_blocking=True)
+        if self.lens is not None:
+            self.enqueue_rectify()
         self.frame_idx += 1
 
     def enqueue_detect(self):
@@ -1059,7 +1110,10 @@ class CameraLoop:
         panel's 640 x 500 px convention to the frame (x_center = w / 2, x_scale = 0.03 * 640 / w, y_far = 50,
         y_scale = 50 / h).  calibration: HotLoop's (one CameraCalibration or one per camera); the stretched defaults are then not
         built and obstacle_kw takes radius and frame_rate only.  enqueue_ground_view warps the frames to a bird's-eye view through
-        it.  obstacles="filtered_tracks" and track_filter_kw: HotLoop's (the per-track Kalman filter; self.hot.track_filt).
+        it.  Calibrations with a lens (all cameras, or none): the step's input is the cameras' RAW frames (cam.raw), cam.frames is
+        their rectified picture (av_remap through a table built once), and the detector, lanes, scene, views, tracker and the
+        ground kernels see rectified pixels as without a lens.
+        obstacles="filtered_tracks" and track_filter_kw: HotLoop's (the per-track Kalman filter; self.hot.track_filt).
         tags: None, "motion" or "all" -- every step() also tags its frame behind hot.step() on the hot stream and appends it to
         self.tag_log (a TagLog of tag_capacity frames per camera): "motion" runs the maneuver tagger (with the lanes' offset), the
         interaction tagger (class_map="reference" only: it needs the reference's class ids) and enqueue_tags; "all" runs the scene
@@ -1076,7 +1130,15 @@ class CameraLoop:
         if view not in (None, "camera", "demo"):
             raise ValueError('view is None, "camera" or "demo"')
         self.S, self.h, self.w = n_streams, h, w
-        self.cam = PerceptionLoop(n_streams=n_streams, h=h, w=w, device=device, model=model, precision=precision, names=names)
+        lenses = None
+        if calibration is not None:
+            from .perception.calibration import CameraCalibration, lenses_of
+            lenses = lenses_of(calibration, n_streams)
+            if lenses is not None:      # behind the rectification the hot half works on rectified pixels: the cameras without their lenses
+                calibration = (calibration.rectified() if isinstance(calibration, CameraCalibration)
+                               else [c.rectified() for c in calibration])
+        self.cam = PerceptionLoop(n_streams=n_streams, h=h, w=w, device=device, model=model, precision=precision, names=names,
+                                  lens=lenses)
         ok = {} if calibration is not None else dict(x_center=w / 2.0, x_scale=0.03 * 640.0 / w, y_far=50.0, y_scale=50.0 / h)
         ok.update(obstacle_kw or {})
         self.hot = HotLoop(n_streams=n_streams, window=1, h=h, w=w, dcap=dcap, device=device, tracker_kw=tracker_kw, kf_kw=kf_kw,
@@ -1104,6 +1166,7 @@ class CameraLoop:
         self.view_mode, self.view_fps = view, 0.0
         self.view = self.view_cam = None
         self.ground_view = None                 # enqueue_ground_view
+        self._ground_map = None                 # (geometry, av_lens_map_ground's table): enqueue_ground_view(source="raw")
         if view is not None:
             self._setup_view()
 
@@ -1176,18 +1239,37 @@ class CameraLoop:
             nat.check(L.av_view_compose(h, st, S, nat.ptr(self.view_cam) if staged else None, self.h, self.w, nat.ptr(hot.bev), bh, bw,
                                         nat.ptr(self.view), self.VIEW_LABELS[0].encode(), self.VIEW_LABELS[1].encode()))
 
-    def enqueue_ground_view(self, gh=500, gw=640, f_far=50.0, m_per_px=0.1, fill=(0, 0, 0)):
+    def enqueue_ground_view(self, gh=500, gw=640, f_far=50.0, m_per_px=0.1, fill=(0, 0, 0), source="frames"):
         """The frames of the last step() seen from above, on the hot stream (call it behind step(); the next cam.step() waits for
         that stream): self.ground_view uint8 [S, gh, gw, 3], row 0 at f_far metres ahead, m_per_px metres per pixel, the camera's
         axis down the middle column (av_ground_warp through every camera's own calibration; `fill` where the road point is above
-        the horizon or outside the frame).  cam.frames is read, never written."""
+        the horizon or outside the frame).  cam.frames is read, never written.
+        source="raw" (a loop with lenses only): the view is taken straight from cam.raw through the composed table road point ->
+        rectified pixel -> raw position (av_lens_map_ground, built at the first call with a geometry, then av_remap): one
+        interpolation instead of two."""
         hot = self.hot
         if hot.ground is None:
             raise RuntimeError("enqueue_ground_view needs CameraLoop(calibration=...)")
+        if source not in ("frames", "raw"):
+            raise ValueError('source is "frames" or "raw"')
+        if source == "raw" and self.cam.lens is None:
+            raise ValueError('enqueue_ground_view(source="raw") needs calibrations with a lens; without one cam.frames IS the raw frame')
         gh, gw = int(gh), int(gw)
         if self.ground_view is None or tuple(self.ground_view.shape[1:3]) != (gh, gw):
             with torch.cuda.stream(hot.stream):         # zero-filled on the stream that writes it
                 self.ground_view = torch.zeros(self.S, gh, gw, 3, dtype=torch.uint8, device=hot.dev)
+        if source == "raw":
+            geom = (gh, gw, float(f_far), float(m_per_px))
+            if self._ground_map is None or self._ground_map[0] != geom:
+                with torch.cuda.stream(hot.stream):
+                    table = torch.empty(self.S, gh, gw, 2, dtype=torch.int32, device=hot.dev)
+                nat.check(hot.L.av_lens_map_ground(hot.ctx.handle, hot._s, nat.ptr(self.cam.lens), nat.ptr(hot.ground), self.S, gh, gw,
+                                                   geom[2], geom[3], nat.ptr(table)))
+                self._ground_map = (geom, table)
+            nat.check(hot.L.av_remap(hot.ctx.handle, hot._s, nat.ptr(self._ground_map[1]), self.S, 1, self.h, self.w,
+                                     nat.ptr(self.cam.raw), gh, gw, (C.c_uint8 * 3)(*[int(c) for c in fill]),
+                                     nat.ptr(self.ground_view)))
+            return
         nat.check(hot.L.av_ground_warp(hot.ctx.handle, hot._s, nat.ptr(hot.ground), self.S, self.h, self.w, nat.ptr(self.cam.frames),
                                        gh, gw, float(f_far), float(m_per_px), (C.c_uint8 * 3)(*[int(c) for c in fill]),
                                        nat.ptr(self.ground_view)))
