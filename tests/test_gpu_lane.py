@@ -296,12 +296,7 @@ def test_fit_rank_cutoff_deviation_is_confined_to_degenerate_inputs(LaneDetector
     lb = LaneBatch(S, h, w, MS, torch.zeros(S, h, w, 3, dtype=torch.uint8, device="cuda"))
 
     def device_fit(segs):
-        o5, n5 = lb.span(5)
-        o6, _ = lb.span(6)
-        buf = np.zeros((MS, 4), np.int32)
-        buf[:len(segs)] = segs
-        lb.ws[o5:o5 + n5].copy_(torch.as_tensor(buf.view(np.uint8).reshape(-1)))
-        lb.ws[o6:o6 + 4].copy_(torch.as_tensor(np.array([len(segs)], np.int32).view(np.uint8)))
+        lb.load_segments(0, segs)
         lb.state.zero_()
         lb.run(16 | 32)
         return lb.poly.cpu().numpy()[0, 0].copy(), int(lb.info.cpu().numpy()[0, 0])
