@@ -523,6 +523,51 @@ int av_track_obstacles_ground_lens(av_ctx* ctx, av_stream_t stream, const av_obs
                                    const av_track_row* snap, const int32_t* snap_n, const double* filt, const double* plan_state,
                                    int ocap, double* obstacles, int32_t* n_obs, int32_t* n_off);
 
+/* ---- Camera rigs (opt-in): K cameras per vehicle, their obstacle lists fused on the road ------------------------------------------
+ * A mount places a camera's road frame (x forward, y lateral from the camera's ground point) in the vehicle's: a rotation by the
+ * mount's yaw (from the vehicle's forward axis towards +lateral) and a shift.  The table holds cos and sin, not the angle, so a
+ * quarter turn can be written exactly. */
+typedef struct {
+    double c, s;           /* cos(yaw), sin(yaw) */
+    double x, y;           /* the camera's ground point in the vehicle frame, metres */
+} av_rig_mount;            /* 32 bytes */
+typedef struct {
+    double merge_scale;    /* 1.0: the gate in units of the larger of the two radii */
+    double merge_min;      /* 1.0: the smallest gate, metres */
+} av_rig_cfg;              /* 16 bytes; both finite and >= 0 */
+/* The obstacle lists of every vehicle's K cameras -> one list per vehicle, in the planner's frame, objects seen by several cameras
+ * merged.  cam_obs holds each camera's obstacles in that camera's own road frame, columns (x, y, r) or (x, y, r, vx, vy) with the
+ * velocity relative to the vehicle: what av_track_obstacles_ground / _ground_lens write when their plan_state rows are
+ * (0, 0, 0, 0).  Camera k of vehicle v is list v * n_cams + k.  float64, every operation rounded on its own (no FMA), in the
+ * order written.  Per vehicle, cameras in the order k = 0 .. n_cams - 1 (a round), clusters kept in creation order:
+ *   candidates of camera k: rows 0 .. clamp(cam_n, 0, ocap_in) - 1 in order; a row with x, y or r not finite, r <= 0 or (ncol 5)
+ *     vx or vy not finite is skipped and counted in n_skip[v].  For a kept row, with the mount (c, s, mx, my):
+ *       m = max(x*x + y*y, 1.0);  w = 1.0 / (m*m)          (a pixel's footprint grows with the squared distance from the camera,
+ *                                                            so the variance of a ground position with its fourth power)
+ *       X = (mx + c*x) - s*y;  Y = (my + s*x) + c*y;  VX = c*vx - s*vy;  VY = s*vx + c*vy
+ *   association, against the clusters that existed when the round began (two rows of one camera never merge): for cluster i and
+ *     candidate j
+ *       dx = X_i - X_j;  dy = Y_i - Y_j;  d2 = dx*dx + dy*dy;  gate = max(merge_min, merge_scale * max(r_i, r_j))
+ *     the pair is admissible when d2 <= gate*gate (and d2 is finite).  Repeatedly the admissible pair with the smallest d2 among
+ *     the clusters and candidates not yet taken in this round is taken -- equal d2: the smallest i, then the smallest j -- until
+ *     none remains (multi_object_tracker.py:136-159, with the distance in place of the IoU).
+ *   absorption: sw += w; sx += w*X; sy += w*Y; svx += w*VX; svy += w*VY; r = max(r, r_j); views |= 1 << k; then
+ *     X = sx / sw, and Y, VX, VY likewise: the next round measures from the fused position.
+ *   new clusters: the candidates left over, in candidate order, behind the existing ones: sw = w, sx = w*X, ..., views = 1 << k;
+ *     a cluster with one member stands at that member's X, Y, VX, VY themselves.
+ *   output, cluster i = row i, placed as av_track_obstacles places a track, (x0, y0, h, v0) = plan_state[v]:
+ *       ox = (x0 + X cos h) + Y cos(h + pi/2);  oy = (y0 + X sin h) + Y sin(h + pi/2);  r
+ *       VF = VX + v0;  vx = VF cos h + VY cos(h + pi/2);  vy = VF sin h + VY sin(h + pi/2)                       (ncol 5)
+ *     n_obs[v] = the number of clusters, views[v][i] = the mask of the cameras that saw cluster i; rows at or past n_obs[v] are
+ *     not written.
+ *   mounts DEVICE [V][K]; cam_obs [V*K][ocap_in][ncol], cam_n [V*K]; plan_state [V][4] (av_kf_step's)
+ *   obstacles [V][ocap][ncol], n_obs [V]; views [V][ocap] or NULL; n_skip [V] or NULL
+ * AV_EINVAL before any launch: a null pointer other than views and n_skip; n_vehicles < 1; n_cams not in 1..8; ocap_in not in
+ * 1..64; ncol not 3 or 5; ocap < n_cams * ocap_in (nothing is ever dropped); cfg outside its ranges. */
+int av_rig_fuse(av_ctx* ctx, av_stream_t stream, const av_rig_cfg* cfg, int n_vehicles, int n_cams, const av_rig_mount* mounts,
+                int ncol, int ocap_in, const double* cam_obs, const int32_t* cam_n, const double* plan_state, int ocap,
+                double* obstacles, int32_t* n_obs, int32_t* views, int32_t* n_skip);
+
 /* generate_polynomial_trajectory for arbitrary (lateral offset, target speed) pairs (:126-204).
  *   state [n_traj][4], end_lateral_offset [n_traj], target_velocity [n_traj] -> waypoints [n_traj][n][6] */
 int av_planner_generate(av_ctx* ctx, av_stream_t stream, int n_traj, const double* state,

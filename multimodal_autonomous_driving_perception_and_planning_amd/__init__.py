@@ -8,7 +8,7 @@ __version__ = "0.1.0"
 
 from . import _native  # noqa: F401  (does not load the library until first use)
 
-__all__ = ["CameraCalibration", "LensModel"]
+__all__ = ["CameraCalibration", "LensModel", "CameraRig"]
 
 
 def __getattr__(name):
@@ -19,4 +19,7 @@ def __getattr__(name):
     if name == "LensModel":
         from .perception.calibration import LensModel
         return LensModel
+    if name == "CameraRig":
+        from .perception.calibration import CameraRig
+        return CameraRig
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

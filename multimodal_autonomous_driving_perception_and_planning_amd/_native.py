@@ -60,6 +60,16 @@ class LensCfg(C.Structure):
         ("w", C.c_int32), ("h", C.c_int32)]
 
 
+class RigMount(C.Structure):
+    """av_rig_mount: a camera's road frame in the vehicle's (cos and sin of the mount's yaw, the camera's ground point); 32 bytes."""
+    _fields_ = [("c", C.c_double), ("s", C.c_double), ("x", C.c_double), ("y", C.c_double)]
+
+
+class RigCfg(C.Structure):
+    """av_rig_cfg: av_rig_fuse's gate, max(merge_min, merge_scale * the larger radius); 16 bytes."""
+    _fields_ = [("merge_scale", C.c_double), ("merge_min", C.c_double)]
+
+
 class TrackFilterCfg(C.Structure):
     """av_track_filter_cfg: the per-track constant-velocity Kalman filter's noise and initial variances (px, frames)."""
     _fields_ = [("q_accel", C.c_double), ("r_meas", C.c_double), ("p0_pos", C.c_double), ("p0_vel", C.c_double)]
@@ -289,6 +299,8 @@ _SIGS = [
     ("av_remap", C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.POINTER(C.c_uint8), vp]),
     ("av_track_obstacles_ground_lens", C.c_int, [vp, vp, C.POINTER(ObstacleCfg), vp, vp, C.c_int, C.c_int, C.c_double, C.c_int,
                                                  C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp]),
+    ("av_rig_fuse", C.c_int, [vp, vp, C.POINTER(RigCfg), C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp,
+                              vp]),
     ("av_hot_step", C.c_int, [vp, vp, C.POINTER(StepLoop), C.POINTER(StepSet), vp, C.c_int, C.c_int]),
     ("av_hot_step_fits", C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     ("av_hot_step_plan", C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),

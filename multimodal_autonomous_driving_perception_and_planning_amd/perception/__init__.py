@@ -1,5 +1,5 @@
-from .calibration import CameraCalibration, LensModel
+from .calibration import CameraCalibration, CameraRig, LensModel
 from .detector import Detection, ObjectDetector
 from .lane_detector import LaneDetector, LaneLine
 
-__all__ = ["ObjectDetector", "LaneDetector", "Detection", "LaneLine", "CameraCalibration", "LensModel"]
+__all__ = ["ObjectDetector", "LaneDetector", "Detection", "LaneLine", "CameraCalibration", "LensModel", "CameraRig"]

@@ -263,6 +263,98 @@ class CameraCalibration:
                                                                        "" if self.lens is None else ", lens=%r" % (self.lens,))
 
 
+MAX_RIG_CAMERAS = 8             # av_rig_fuse's n_cams
+
+
+class CameraRig:
+    """K calibrated cameras on one vehicle: each camera's road frame (forward, lateral from its own ground point) placed in the
+    vehicle's by a mount (x, y, yaw) -- a rotation by yaw, measured from the vehicle's forward axis towards +lateral, and a shift
+    (include/avhot.h: av_rig_mount).  pipeline.RigLoop fuses the cameras' obstacle lists through it (av_rig_fuse)."""
+
+    def __init__(self, cameras, mounts):
+        """cameras: K CameraCalibrations, each in its own road frame; all of them carry a lens, or none does.
+        mounts: K triples (x, y, yaw): metres in the vehicle frame (x forward, y lateral, the library's sense) and radians."""
+        cams = list(cameras)
+        if not 1 <= len(cams) <= MAX_RIG_CAMERAS or not all(isinstance(c, CameraCalibration) for c in cams):
+            raise ValueError("CameraRig: cameras is a list of 1 .. %d CameraCalibrations" % MAX_RIG_CAMERAS)
+        try:
+            m = np.asarray(mounts, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("CameraRig: mounts is one (x, y, yaw) triple per camera") from None
+        if m.shape != (len(cams), 3):
+            raise ValueError("CameraRig: mounts is one (x, y, yaw) triple per camera (%d), not an array of shape %r"
+                             % (len(cams), m.shape))
+        if not np.isfinite(m).all():
+            raise ValueError("CameraRig: a mount is not finite")
+        lenses_of(cams, len(cams))              # (refuses a rig where some cameras have a lens and some have none)
+        self.cameras, self.mounts = cams, m.copy()
+        # (cos, sin, x, y) per camera: what the device table holds
+        self._csxy = np.array([[np.cos(yaw), np.sin(yaw), x, y] for x, y, yaw in m], dtype=np.float64).reshape(len(cams), 4)
+
+    @classmethod
+    def from_poses(cls, poses):
+        """One dict per camera: fx, fy, cx, cy, height, and optionally pitch=0.0, yaw=0.0, x=0.0, y=0.0, max_range=80.0,
+        anchor="bottom", dist=None, size=None -- CameraCalibration.from_pose's arguments plus the mount."""
+        cams, mounts = [], []
+        for i, p in enumerate(poses):
+            p = dict(p)
+            try:
+                mounts.append((float(p.pop("x", 0.0)), float(p.pop("y", 0.0)), float(p.pop("yaw", 0.0))))
+                cams.append(CameraCalibration.from_pose(**p))
+            except TypeError as e:
+                raise ValueError("CameraRig.from_poses: camera %d: %s" % (i, e)) from None
+        return cls(cams, mounts)
+
+    @property
+    def K(self):
+        return len(self.cameras)
+
+    def calibrations(self, n_vehicles):
+        """The per-camera list of n_vehicles rigs: camera k of vehicle v is entry v * K + k."""
+        return list(self.cameras) * int(n_vehicles)
+
+    def mounts_table(self, n_vehicles, device=None):
+        """float64 [V, K, 4] of (cos, sin, x, y): av_rig_fuse's `mounts` (device None: a host tensor)."""
+        import torch
+
+        t = torch.as_tensor(np.ascontiguousarray(np.broadcast_to(self._csxy, (int(n_vehicles),) + self._csxy.shape)))
+        return t if device is None else t.to(device)
+
+    def to_vehicle(self, k, fl):
+        """[..., 2] (forward, lateral) in camera k's road frame -> [..., 2] in the vehicle frame (av_rig_fuse's operation order)."""
+        fl = np.asarray(fl, dtype=np.float64)
+        c, s, mx, my = self._csxy[k]
+        f, l = fl[..., 0], fl[..., 1]
+        return np.stack([(mx + c * f) - s * l, (my + s * f) + c * l], axis=-1)
+
+    def from_vehicle(self, k, FL):
+        """[..., 2] vehicle-frame road points -> [..., 2] in camera k's road frame."""
+        FL = np.asarray(FL, dtype=np.float64)
+        c, s, mx, my = self._csxy[k]
+        dx, dy = FL[..., 0] - mx, FL[..., 1] - my
+        return np.stack([c * dx + s * dy, c * dy - s * dx], axis=-1)
+
+    def image_to_vehicle(self, k, uv, raw=False):
+        """[..., 2] pixels of camera k -> ([..., 2] vehicle-frame road points, [...] on that camera's road)."""
+        fl, on = self.cameras[k].image_to_ground(uv, raw=raw)
+        return self.to_vehicle(k, fl), on
+
+    def mount_matrix(self, k):
+        """The mount as a homography of the road plane: (F, L, D) in camera k's frame -> the vehicle's."""
+        c, s, mx, my = self._csxy[k]
+        return np.array([[c, -s, mx], [s, c, my], [0.0, 0.0, 1.0]])
+
+    def vehicle_calibration(self, k):
+        """Camera k with the mount folded into its homography, g = M_k g_k: image -> the VEHICLE's (forward, lateral).  Meaningful
+        only for a camera whose view lies ahead of the vehicle: on_road wants forward >= 0, which is why av_rig_fuse takes the
+        mounts beside the cameras instead of folded into every g."""
+        cam = self.cameras[k]
+        return CameraCalibration(self.mount_matrix(k) @ cam.g, max_range=cam.max_range, anchor=cam.anchor, lens=cam.lens)
+
+    def __repr__(self):
+        return "CameraRig(K=%d, mounts=%r)" % (self.K, self.mounts.tolist())
+
+
 def ground_table(calibrations, n, device):
     """One CameraCalibration, or a sequence of n of them -> a device uint8 tensor [n, 160] of av_ground_cfg entries."""
     import torch

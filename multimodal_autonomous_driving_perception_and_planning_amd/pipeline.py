@@ -29,6 +29,10 @@ homography) in place of the linear pixel-to-metre scales: tracks stand where the
 frames to a bird's-eye view (av_ground_warp).  Calibrations with a lens (perception.LensModel, Brown-Conrady): a HotLoop takes its
 tracker's boxes as raw pixels (av_track_obstacles_ground_lens); a CameraLoop rectifies every fed frame through a table built
 once (av_lens_map_rectify, av_remap: cam.raw -> cam.frames) and everything behind it sees rectified pixels.
+
+Opt-in (RigLoop): V vehicles with K cameras each (perception.CameraRig).  A CameraLoop of V * K cameras runs up to the per-camera
+obstacle lists, av_rig_fuse carries them through the mounts into the vehicle frame and merges what several cameras see, and a
+HotLoop of V ego states plans around the fused lists -- one plan per vehicle, no host round trip.
 """
 import ctypes as C
 
@@ -1319,3 +1323,164 @@ class CameraLoop:
     def results(self):
         """HotLoop.results() of the last step: with det_dropped [S, 1], ref_paths [S, 50, 2], n_ref [S] and lane_offset [S]."""
         return self.hot.results()
+
+
+class RigLoop:
+    """V vehicles with K cameras each (perception.CameraRig), one plan per vehicle around everything any of its cameras sees, with
+    no host round trip: a CameraLoop of V * K cameras driven stage by stage up to the per-camera obstacle lists (self.cams: camera
+    v * K + k is camera k of vehicle v; its start states are held at zero, so the lists stand in each camera's own road frame, and
+    its Kalman and planner stages are never enqueued), av_rig_fuse carrying them through the mounts into the vehicle frame and
+    merging the objects seen by several cameras, and a HotLoop of V ego states (self.ego) that plans around the fused lists."""
+
+    _OUT_OF_SCOPE = {"fused_step": "the one-launch step plans without obstacles", "overlap": "the overlapped loop plans without obstacles",
+                     "graph": "graph capture of a RigLoop is not supported", "graphs": "graph capture of a RigLoop is not supported",
+                     "tags": "the taggers describe one camera, not a rig", "tag_capacity": "the taggers describe one camera, not a rig",
+                     "tag_columns": "the taggers describe one camera, not a rig", "view": "the annotated views describe one camera, not a rig",
+                     "views": "the annotated views describe one camera, not a rig"}
+
+    def __init__(self, n_vehicles, rig, h=720, w=1280, model="random:0", precision="fp16", dcap=64, obstacles="moving_tracks",
+                 class_map="reference", lane_camera=0, fuse_kw=None, tracker_kw=None, kf_kw=None, planner_kw=None, obstacle_kw=None,
+                 track_filter_kw=None, names=None, device=0, **other):
+        """rig: a perception.CameraRig.  obstacles: "moving_tracks", "filtered_tracks" or "tracks", CameraLoop's modes (a rig
+        without obstacles has nothing to fuse).  lane_camera: the index of the camera whose lane fit is the vehicle's reference path
+        (av_lane_paths_ground through rig.vehicle_calibration(lane_camera)), None for no path; its mount may not be yawed beyond
+        +-pi/2, since a path behind the vehicle is none.  fuse_kw: av_rig_cfg's merge_scale and merge_min (1.0, 1.0 m).  Everything
+        else is CameraLoop's; kf_kw and planner_kw go to the ego loop.  The one-launch step, the overlapped loop, graph capture, tags
+        and views are refused by name."""
+        from .perception.calibration import CameraRig, ground_table
+        for k in other:
+            if k in self._OUT_OF_SCOPE:
+                raise ValueError("RigLoop: %s is out of scope (%s)" % (k, self._OUT_OF_SCOPE[k]))
+            raise TypeError("RigLoop() got an unexpected keyword argument %r" % k)
+        if not isinstance(rig, CameraRig):
+            raise ValueError("RigLoop: rig is a perception.CameraRig")
+        if obstacles not in ("moving_tracks", "filtered_tracks", "tracks"):
+            raise ValueError('RigLoop: obstacles is "moving_tracks", "filtered_tracks" or "tracks"')
+        V, K = int(n_vehicles), rig.K
+        if V < 1:
+            raise ValueError("RigLoop: n_vehicles must be >= 1")
+        if lane_camera is not None:
+            if not (isinstance(lane_camera, (int, np.integer)) and 0 <= lane_camera < K):
+                raise ValueError("RigLoop: lane_camera is None or a camera index 0 .. %d" % (K - 1))
+            yaw = float(np.arctan2(np.sin(rig.mounts[lane_camera, 2]), np.cos(rig.mounts[lane_camera, 2])))
+            if abs(yaw) > np.pi / 2:
+                raise ValueError("RigLoop: lane_camera %d is yawed %.1f degrees from the vehicle's forward axis, beyond +-90: its lane "
+                                 "lies behind the vehicle, and a reference path there is no path (on_road wants forward >= 0)"
+                                 % (lane_camera, np.degrees(yaw)))
+        fk = dict(merge_scale=1.0, merge_min=1.0)
+        fk.update(fuse_kw or {})
+        if sorted(fk) != ["merge_min", "merge_scale"]:
+            raise ValueError("RigLoop: fuse_kw takes merge_scale and merge_min")
+        if not all(np.isfinite(float(v)) and float(v) >= 0.0 for v in fk.values()):
+            raise ValueError("RigLoop: merge_scale and merge_min must be >= 0 and finite")
+        self.fcfg = nat.RigCfg(float(fk["merge_scale"]), float(fk["merge_min"]))
+        self.V, self.K, self.rig, self.h, self.w, self.lane_camera = V, K, rig, h, w, lane_camera
+        self.cams = CameraLoop(V * K, h=h, w=w, model=model, precision=precision, dcap=dcap, obstacles=obstacles, class_map=class_map,
+                               device=device, tracker_kw=tracker_kw, planner_kw=planner_kw, obstacle_kw=obstacle_kw, names=names,
+                               track_filter_kw=track_filter_kw, calibration=rig.calibrations(V))
+        hot = self.cams.hot
+        self.ego = HotLoop(V, window=1, h=h, w=w, device=device, kf_kw=kf_kw, planner_kw=planner_kw, ctx=self.cams.cam.ctx,
+                           fused_step=False, keep_waypoints=True)
+        self.L, self.dev, self.tcap = self.ego.L, self.ego.dev, hot.tcap
+        self.cols = int(hot.obstacles.shape[3])
+        d, i32, f64 = self.dev, torch.int32, torch.float64
+        if K * self.tcap > 512:
+            raise ValueError("RigLoop: %d cameras x %d tracks exceed av_rig_fuse's 512 clusters" % (K, self.tcap))
+        self.mounts = rig.mounts_table(V, d)                                        # float64 [V, K, 4]
+        self.obstacles = torch.zeros(V, 1, K * self.tcap, self.cols, dtype=f64, device=d)
+        self.n_obs = torch.zeros(V, 1, dtype=i32, device=d)
+        self.views = torch.zeros(V, K * self.tcap, dtype=i32, device=d)
+        self.n_skip = torch.zeros(V, dtype=i32, device=d)
+        self.ego.set_obstacles(self.obstacles, self.n_obs)
+        self.ref_paths = self.n_ref = self.lane_offset = self.lane_ground = None
+        if lane_camera is not None:
+            # the frames behind a lens are rectified before the lane detector sees them: the vehicle calibration without its lens
+            self.lane_ground = ground_table(rig.vehicle_calibration(lane_camera).rectified(), V, d)[0]
+            self._lane_idx = torch.arange(V, dtype=torch.int64, device=d) * K + int(lane_camera)
+            self._poly = torch.zeros(V, 2, 3, dtype=f64, device=d)
+            self._pts = torch.zeros(V, 2, 50, 2, dtype=i32, device=d)
+            self._info = torch.zeros(V, 8, dtype=i32, device=d)
+            self.ref_paths = torch.zeros(V, 50, 2, dtype=f64, device=d)
+            self.n_ref = torch.zeros(V, dtype=i32, device=d)
+            self.lane_offset = torch.full((V,), float("nan"), dtype=f64, device=d)
+            self.ego.set_reference_paths(self.ref_paths, self.n_ref)
+        self._stepped = False
+        torch.cuda.current_stream(d).synchronize()          # the buffers are filled before the loops' streams touch them
+
+    def load_measurements(self, z):
+        """z: float64 [V, 1, 4] (or [V, 4]) ego measurements of the next step (HotLoop.load_measurements)."""
+        self.ego.load_measurements(z)
+
+    def enqueue_fuse(self, stream=None):
+        """The cameras' lists (self.cams.hot.obstacles / n_obs) and the ego start states -> self.obstacles / n_obs / views / n_skip
+        (av_rig_fuse); call behind the cameras' enqueue_obstacles and the ego's enqueue_kf."""
+        hot, ego = self.cams.hot, self.ego
+        nat.check(self.L.av_rig_fuse(ego.ctx.handle, stream or ego._s, C.byref(self.fcfg), self.V, self.K, nat.ptr(self.mounts), self.cols,
+                                     self.tcap, nat.ptr(hot.obstacles), nat.ptr(hot.n_obs), nat.ptr(ego.plan_state), self.K * self.tcap,
+                                     nat.ptr(self.obstacles), nat.ptr(self.n_obs), nat.ptr(self.views), nat.ptr(self.n_skip)))
+
+    def enqueue_lane_paths(self, stream=None):
+        """The lane camera's fits, gathered on the device, and the ego start states -> self.ref_paths / n_ref / lane_offset
+        (av_lane_paths_ground through the lane camera's vehicle calibration); call behind the camera half and the ego's enqueue_kf."""
+        if self.lane_camera is None:
+            raise RuntimeError("enqueue_lane_paths needs RigLoop(lane_camera=...)")
+        cam, ego = self.cams.cam, self.ego
+        with torch.cuda.stream(ego._torch_stream(stream)):
+            torch.index_select(cam.poly, 0, self._lane_idx, out=self._poly)
+            torch.index_select(cam.pts, 0, self._lane_idx, out=self._pts)
+            torch.index_select(cam.info, 0, self._lane_idx, out=self._info)
+        nat.check(self.L.av_lane_paths_ground(ego.ctx.handle, stream or ego._s, nat.ptr(self.lane_ground), self.V, self.h, self.w, 50,
+                                              nat.ptr(self._poly), nat.ptr(self._pts), nat.ptr(self._info), nat.ptr(ego.plan_state), 1,
+                                              50, nat.ptr(self.ref_paths), nat.ptr(self.n_ref), nat.ptr(self.lane_offset)))
+
+    def step(self, frames=None, sync=False):
+        """The camera half for V * K frames (frames: PerceptionLoop.enqueue_frames', [V * K, h, w, 3]); then on the ego loop's
+        stream the cameras' detections -> tracker [-> track filter] -> camera-frame obstacle lists, the ego Kalman stage, av_rig_fuse,
+        the lane camera's reference path and the per-state planner.  The camera half of the next step overwrites what this one
+        reads, so it first waits for the ego stream, as CameraLoop.step does."""
+        cams, ego = self.cams, self.ego
+        cam, hot = cams.cam, cams.hot
+        if cam._tail_deferred or cam._lanes_pending:
+            raise RuntimeError("RigLoop steps the plain PerceptionLoop.step(): with a deferred detector tail or a pending lane half "
+                               "det_* / poly describe the previous frame")
+        if self._stepped:
+            cam.stream.wait_stream(ego.stream)
+        cam.step(frames=frames)
+        ego.stream.wait_stream(cam.stream)
+        s = ego._s
+        hot.enqueue_detect(s)
+        hot.enqueue_track(s)
+        if hot.track_filter is not None:
+            hot.enqueue_track_filter(s)
+        hot.enqueue_obstacles(s)                # hot.plan_state is zero: every list in its camera's own road frame
+        ego.enqueue_kf()
+        self.enqueue_fuse()
+        if self.lane_camera is not None:
+            self.enqueue_lane_paths()
+        ego.enqueue_plan_each()
+        self._stepped = True
+        if sync:
+            self.synchronize()
+
+    def capture(self):
+        raise RuntimeError("RigLoop: graph capture is out of scope")
+
+    def synchronize(self):
+        self.cams.synchronize()
+        self.ego.synchronize()
+
+    def results(self):
+        """The ego loop's results() of the last step (obstacles [V, 1, K * tcap, cols] and n_obs [V, 1] are the fused lists) plus
+        cam_obstacles [V, K, tcap, cols], cam_n_obs [V, K], n_off [V, K] (the cameras' own lists), views [V, K * tcap] (the mask of the
+        cameras that saw each fused obstacle), n_skip [V] and, with a lane camera, ref_paths [V, 50, 2], n_ref [V], lane_offset [V]."""
+        self.synchronize()
+        hot, V, K = self.cams.hot, self.V, self.K
+        out = self.ego.results()
+        out["cam_obstacles"] = hot.obstacles.cpu().numpy().reshape(V, K, self.tcap, self.cols)
+        out["cam_n_obs"] = hot.n_obs.cpu().numpy().reshape(V, K)
+        out["n_off"] = hot.n_off.cpu().numpy().reshape(V, K)
+        out["views"], out["n_skip"] = self.views.cpu().numpy(), self.n_skip.cpu().numpy()
+        if self.lane_camera is not None:
+            out["ref_paths"], out["n_ref"] = self.ref_paths.cpu().numpy(), self.n_ref.cpu().numpy()
+            out["lane_offset"] = self.lane_offset.cpu().numpy()
+        return out
