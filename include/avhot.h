@@ -568,6 +568,72 @@ int av_rig_fuse(av_ctx* ctx, av_stream_t stream, const av_rig_cfg* cfg, int n_ve
                 int ncol, int ocap_in, const double* cam_obs, const int32_t* cam_n, const double* plan_state, int ocap,
                 double* obstacles, int32_t* n_obs, int32_t* views, int32_t* n_skip);
 
+/* ---- Vehicle-frame tracks (opt-in): av_rig_fuse's lists followed over time -------------------------------------------------------
+ * A multi-object tracker in the planner's frame, one frame per call, with a state of its own per vehicle and a constant-velocity
+ * Kalman filter per track: a fused obstacle keeps its id from frame to frame and from camera to camera, and a track that no row
+ * matches coasts at its predicted place until max_age misses have passed.  The planner's frame is the ego filter's world frame:
+ * the ego's own motion is already out of the positions (and, with five columns, out of the velocities), so constant velocity is
+ * the right model there.  The greedy association is the reference tracker's (multi_object_tracker.py:136-159) with av_rig_fuse's
+ * distance and gate in place of the IoU; max_age and min_hits are that tracker's.  float64, every operation rounded on its own (no
+ * FMA), in the order written. */
+typedef struct {
+    double dt;            /* 1/30   seconds per frame; finite, > 0 */
+    double q_accel;       /* 4.0    white-noise acceleration, m^2 / s^4; finite, >= 0 */
+    double r_meas;        /* 0.25   measurement variance of a coordinate, m^2; finite, > 0 */
+    double r_range;       /* 1e-6   the range term of the measurement variance (below); finite, >= 0; 0: the plain SORT filter */
+    double p0_pos;        /* 1.0    initial variance of x, y; finite, >= 0 */
+    double p0_vel;        /* 25.0   initial variance of vx, vy; finite, >= 0 */
+    double gate_scale;    /* 2.0    the gate in units of the larger of the two radii; finite, >= 0 */
+    double gate_min;      /* 2.0    the smallest gate, metres; finite, >= 0 */
+    int32_t max_age;      /* 30     a track with more consecutive misses than this is freed; >= 0 */
+    int32_t min_hits;     /* 3      a track is confirmed (written to the output) from this many hits on; >= 1 */
+} av_rig_track_cfg;       /* 72 bytes */
+/* Persistent per-vehicle state (device).  Layout, for vehicle v with capacity tcap (1 .. 512), 16-byte aligned:
+ *   int32 hdr[16]                  hdr[0] = status, hdr[1] = the next id (1 after a reset), hdr[2] = frames seen,
+ *                                  hdr[3] = live tracks; the rest 0
+ *   slot[tcap], 96 bytes each:     int32 id (-1: free), hits, misses, age, views, views_ever, reserved[2] (0);
+ *                                  double x[4] (x, y, vx, vy); double p[3] (P_pos, P_pos,vel, P_vel); double r (the radius)
+ * x and y never mix and share F, Q, R and the initial variances, so the covariance is two equal 2 x 2 blocks, one per axis, as in
+ * av_track_filter_update.  status bit0: a row found no free slot and was dropped (sticky until the next reset).
+ * av_rig_track_reset sets every id to -1, hdr[1] to 1 and every other byte to 0. */
+size_t av_rig_track_state_bytes(int tcap);             /* 64 + 96 * tcap; 0 for tcap outside 1 .. 512 */
+int av_rig_track_reset(av_ctx* ctx, av_stream_t stream, int n_vehicles, int tcap, void* state);
+/* One frame per vehicle, (x0, y0, ., .) = plan_state[v], (a, b, c) = p, in this order:
+ *   1 predict, every live slot:   x = x + vx*dt;  y = y + vy*dt;  age += 1
+ *       bc = b + dt*c;  a' = ((a + dt*b) + dt*bc) + q11;  b' = bc + q12;  c' = c + q22            (P <- F P F^T + Q)
+ *       q11 = q_accel * (((dt*dt)*(dt*dt)) / 4.0);  q12 = q_accel * (((dt*dt)*dt) / 2.0);  q22 = q_accel * (dt*dt)
+ *   2 candidates: rows 0 .. clamp(n_in[v], 0, ocap_in) - 1 of obs_in[v]; a row with x, y or r not finite, r <= 0 or (ncol 5) vx
+ *       or vy not finite is skipped: counted in n_skip[v], match = -1.
+ *   3 association, live slot i (predicted) against candidate row j, stated as av_rig_fuse states it:
+ *       dx = x_i - x_j;  dy = y_i - y_j;  d2 = dx*dx + dy*dy;  gate = max(gate_min, gate_scale * max(r_i, r_j))
+ *     the pair is admissible when d2 <= gate*gate (and d2 is finite).  Repeatedly the admissible pair with the smallest d2 among
+ *     the slots and rows not yet taken is taken -- equal d2: the smallest slot, then the smallest row -- until none remains.
+ *   4 update of a matched slot with its row (zx, zy, r_j, views_j; views_j = 0 without views_in):
+ *       ex = zx - x0;  ey = zy - y0;  m = max(ex*ex + ey*ey, 1.0);  R = r_meas + r_range * (m*m)   (av_rig_fuse's fourth power
+ *                                                                                                   of the range from the vehicle)
+ *       S = a + R;  k0 = a / S;  k1 = b / S
+ *       per axis: y = z - x;  x = x + k0*y;  v = v + k1*y
+ *       a' = a - k0*a;  b' = b - k0*b;  c' = c - k1*b
+ *       r = r_j;  hits += 1;  misses = 0;  views = views_j;  views_ever |= views_j;  match[j] = id
+ *   5 live slots left unmatched: misses += 1; views = 0; with misses > max_age the slot is freed (id = -1, everything else 0).
+ *   6 births: the kept rows left unmatched, in row order, into the free slots in ascending order (those freed in step 5 among
+ *       them): id = hdr[1]++;  x = (zx, zy, vx_j, vy_j) (velocities 0 with ncol 3);  p = (p0_pos, 0, p0_vel);  r = r_j;  hits = 1;
+ *       misses = 0;  age = 0;  views = views_ever = views_j;  match[j] = id.  Without a free slot the row is dropped:
+ *       match[j] = -2, counted in n_drop[v], status bit0 set.
+ *   7 output: every live slot with hits >= min_hits, in slot order, compacted: (x, y, r) or (x, y, r, vx, vy) into obstacles[v],
+ *       its slot into obs_slot[v]; n_obs[v] = their number.  A coasting slot is written at its predicted place.
+ *   then hdr[2] += 1 and hdr[3] = the live slots.
+ *   obs_in [V][ocap_in][ncol], n_in [V], views_in [V][ocap_in] or NULL (av_rig_fuse's obstacles, n_obs, views); plan_state [V][4]
+ *   state  [V] x av_rig_track_state_bytes(tcap)
+ *   obstacles [V][ocap_out][ncol], n_obs [V]; obs_slot [V][ocap_out], match [V][ocap_in], n_skip [V], n_drop [V]: each or NULL
+ *   Rows of obstacles and obs_slot at or past n_obs[v], and entries of match at or past clamp(n_in[v]), are not written.
+ * AV_EINVAL before any launch and before the context is looked at: n_vehicles < 1; tcap or ocap_in not in 1..512; ncol not 3 or 5;
+ * ocap_out < tcap; cfg outside its ranges; a null pointer other than views_in, obs_slot, match, n_skip, n_drop and stream. */
+int av_rig_track(av_ctx* ctx, av_stream_t stream, const av_rig_track_cfg* cfg, int n_vehicles, int tcap, int ncol, int ocap_in,
+                 const double* obs_in, const int32_t* n_in, const int32_t* views_in, const double* plan_state, void* state,
+                 int ocap_out, double* obstacles, int32_t* n_obs, int32_t* obs_slot, int32_t* match, int32_t* n_skip,
+                 int32_t* n_drop);
+
 /* generate_polynomial_trajectory for arbitrary (lateral offset, target speed) pairs (:126-204).
  *   state [n_traj][4], end_lateral_offset [n_traj], target_velocity [n_traj] -> waypoints [n_traj][n][6] */
 int av_planner_generate(av_ctx* ctx, av_stream_t stream, int n_traj, const double* state,

@@ -70,6 +70,20 @@ class RigCfg(C.Structure):
     _fields_ = [("merge_scale", C.c_double), ("merge_min", C.c_double)]
 
 
+class RigTrackCfg(C.Structure):
+    """av_rig_track_cfg: the vehicle-frame tracker's filter, gate and life cycle (seconds, metres); 72 bytes."""
+    _fields_ = [("dt", C.c_double), ("q_accel", C.c_double), ("r_meas", C.c_double), ("r_range", C.c_double), ("p0_pos", C.c_double),
+                ("p0_vel", C.c_double), ("gate_scale", C.c_double), ("gate_min", C.c_double), ("max_age", C.c_int32),
+                ("min_hits", C.c_int32)]
+
+
+RIG_TRACK_HDR_BYTES = 64
+RIG_TRACK_SLOT_BYTES = 96
+RIG_TRACK_MAX = 512            # the largest tcap and ocap_in
+RIG_TRACK_SLOT_FIELDS = [("id", "<i4"), ("hits", "<i4"), ("misses", "<i4"), ("age", "<i4"), ("views", "<i4"), ("views_ever", "<i4"),
+                         ("reserved", "<i4", (2,)), ("x", "<f8", (4,)), ("p", "<f8", (3,)), ("r", "<f8")]           # 96 bytes
+
+
 class TrackFilterCfg(C.Structure):
     """av_track_filter_cfg: the per-track constant-velocity Kalman filter's noise and initial variances (px, frames)."""
     _fields_ = [("q_accel", C.c_double), ("r_meas", C.c_double), ("p0_pos", C.c_double), ("p0_vel", C.c_double)]
@@ -301,6 +315,10 @@ _SIGS = [
                                                  C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp]),
     ("av_rig_fuse", C.c_int, [vp, vp, C.POINTER(RigCfg), C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp,
                               vp]),
+    ("av_rig_track_state_bytes", C.c_size_t, [C.c_int]),
+    ("av_rig_track_reset", C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
+    ("av_rig_track", C.c_int, [vp, vp, C.POINTER(RigTrackCfg), C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp,
+                               vp, vp, vp, vp]),
     ("av_hot_step", C.c_int, [vp, vp, C.POINTER(StepLoop), C.POINTER(StepSet), vp, C.c_int, C.c_int]),
     ("av_hot_step_fits", C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     ("av_hot_step_plan", C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),

@@ -14,7 +14,7 @@
 // wave reduction on (d2, i, j), and only the threads whose posted cluster was the one just taken scan their slice again -- at most
 // 64 clusters each.  A round is bounded by its candidate count (<= 64 iterations), whatever the distances are.
 // float64, -ffp-contract=off: every operation rounded on its own.
-#include "common.h"
+#include "rig_dev.h"
 
 #include <cmath>
 
@@ -44,10 +44,8 @@ __device__ __forceinline__ void scan_slice(const Shared& sh, const av_rig_cfg& c
     bd = INFINITY, bi = -1;
     for (int i = s; i < m0; i += SLICES) {
         if (sh.taken[i]) continue;
-        const double dx = sh.X[i] - x, dy = sh.Y[i] - y;
-        const double d2 = dx * dx + dy * dy;
-        const double gate = fmax(cfg.merge_min, cfg.merge_scale * fmax(sh.r[i], r));
-        if (d2 <= gate * gate && d2 < bd) bd = d2, bi = i;
+        double d2;
+        if (rig_pair(sh.X[i], sh.Y[i], sh.r[i], x, y, r, cfg.merge_min, cfg.merge_scale, d2) && d2 < bd) bd = d2, bi = i;
     }
 }
 

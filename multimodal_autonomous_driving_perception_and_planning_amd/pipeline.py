@@ -1340,14 +1340,19 @@ class RigLoop:
 
     def __init__(self, n_vehicles, rig, h=720, w=1280, model="random:0", precision="fp16", dcap=64, obstacles="moving_tracks",
                  class_map="reference", lane_camera=0, fuse_kw=None, tracker_kw=None, kf_kw=None, planner_kw=None, obstacle_kw=None,
-                 track_filter_kw=None, names=None, device=0, **other):
+                 track_filter_kw=None, names=None, device=0, track=False, rig_track_kw=None, **other):
         """rig: a perception.CameraRig.  obstacles: "moving_tracks", "filtered_tracks" or "tracks", CameraLoop's modes (a rig
         without obstacles has nothing to fuse).  lane_camera: the index of the camera whose lane fit is the vehicle's reference path
         (av_lane_paths_ground through rig.vehicle_calibration(lane_camera)), None for no path; its mount may not be yawed beyond
         +-pi/2, since a path behind the vehicle is none.  fuse_kw: av_rig_cfg's merge_scale and merge_min (1.0, 1.0 m).  Everything
         else is CameraLoop's; kf_kw and planner_kw go to the ego loop.  The one-launch step, the overlapped loop, graph capture, tags
-        and views are refused by name."""
+        and views are refused by name.
+        track=True: a tracking.RigTracker follows the fused lists (av_rig_track behind av_rig_fuse, on the ego stream) and the
+        ego loop plans around its confirmed tracks -- ids that persist across frames and cameras, coasting through the frames in
+        which no camera sees an object.  rig_track_kw: RigTracker's settings (av_rig_track_cfg's fields; dt defaults to the ego
+        Kalman filter's) and tcap (default min(512, K * the cameras' tcap))."""
         from .perception.calibration import CameraRig, ground_table
+        from .tracking.rig_tracker import RigTracker, check_shape, rig_track_cfg
         for k in other:
             if k in self._OUT_OF_SCOPE:
                 raise ValueError("RigLoop: %s is out of scope (%s)" % (k, self._OUT_OF_SCOPE[k]))
@@ -1374,6 +1379,18 @@ class RigLoop:
         if not all(np.isfinite(float(v)) and float(v) >= 0.0 for v in fk.values()):
             raise ValueError("RigLoop: merge_scale and merge_min must be >= 0 and finite")
         self.fcfg = nat.RigCfg(float(fk["merge_scale"]), float(fk["merge_min"]))
+        if not isinstance(track, (bool, np.bool_)):
+            raise ValueError("RigLoop: track is True or False")
+        if rig_track_kw is not None and not track:
+            raise ValueError("RigLoop: rig_track_kw needs track=True")
+        tkw = dict(rig_track_kw or {})
+        track_tcap = tkw.pop("tcap", None)
+        if track:
+            rig_track_cfg(**tkw)                                                    # (ValueError for a setting outside its range)
+            if track_tcap is not None:
+                if isinstance(track_tcap, bool) or not isinstance(track_tcap, (int, np.integer)):
+                    raise ValueError("RigLoop: rig_track_kw's tcap is an integer")
+                check_shape(V, track_tcap, 3)
         self.V, self.K, self.rig, self.h, self.w, self.lane_camera = V, K, rig, h, w, lane_camera
         self.cams = CameraLoop(V * K, h=h, w=w, model=model, precision=precision, dcap=dcap, obstacles=obstacles, class_map=class_map,
                                device=device, tracker_kw=tracker_kw, planner_kw=planner_kw, obstacle_kw=obstacle_kw, names=names,
@@ -1391,7 +1408,15 @@ class RigLoop:
         self.n_obs = torch.zeros(V, 1, dtype=i32, device=d)
         self.views = torch.zeros(V, K * self.tcap, dtype=i32, device=d)
         self.n_skip = torch.zeros(V, dtype=i32, device=d)
-        self.ego.set_obstacles(self.obstacles, self.n_obs)
+        self.tracker = None
+        if track:
+            tkw.setdefault("dt", float(self.ego.kcfg.dt))
+            self.tracker = RigTracker(V, tcap=min(512, K * self.tcap) if track_tcap is None else int(track_tcap), ncol=self.cols,
+                                      ctx=self.ego.ctx, **tkw)
+            self.tracker.match = torch.full((V, K * self.tcap), -1, dtype=i32, device=d)      # (results() may come before a step)
+            self.ego.set_obstacles(self.tracker.obstacles.view(V, 1, self.tracker.tcap, self.cols), self.tracker.n_obs.view(V, 1))
+        else:
+            self.ego.set_obstacles(self.obstacles, self.n_obs)
         self.ref_paths = self.n_ref = self.lane_offset = self.lane_ground = None
         if lane_camera is not None:
             # the frames behind a lens are rectified before the lane detector sees them: the vehicle calibration without its lens
@@ -1418,6 +1443,13 @@ class RigLoop:
         nat.check(self.L.av_rig_fuse(ego.ctx.handle, stream or ego._s, C.byref(self.fcfg), self.V, self.K, nat.ptr(self.mounts), self.cols,
                                      self.tcap, nat.ptr(hot.obstacles), nat.ptr(hot.n_obs), nat.ptr(ego.plan_state), self.K * self.tcap,
                                      nat.ptr(self.obstacles), nat.ptr(self.n_obs), nat.ptr(self.views), nat.ptr(self.n_skip)))
+
+    def enqueue_rig_track(self, stream=None):
+        """track=True: the fused lists, their views and the ego start states -> self.tracker's obstacles / n_obs / obs_slot / match /
+        n_skip / n_drop (av_rig_track); call behind enqueue_fuse on the same stream."""
+        if self.tracker is None:
+            raise RuntimeError("enqueue_rig_track needs RigLoop(track=True)")
+        self.tracker.update(self.obstacles, self.n_obs, self.ego.plan_state, views=self.views, stream=stream or self.ego._s)
 
     def enqueue_lane_paths(self, stream=None):
         """The lane camera's fits, gathered on the device, and the ego start states -> self.ref_paths / n_ref / lane_offset
@@ -1455,6 +1487,8 @@ class RigLoop:
         hot.enqueue_obstacles(s)                # hot.plan_state is zero: every list in its camera's own road frame
         ego.enqueue_kf()
         self.enqueue_fuse()
+        if self.tracker is not None:
+            self.enqueue_rig_track()
         if self.lane_camera is not None:
             self.enqueue_lane_paths()
         ego.enqueue_plan_each()
@@ -1470,7 +1504,10 @@ class RigLoop:
         self.ego.synchronize()
 
     def results(self):
-        """The ego loop's results() of the last step (obstacles [V, 1, K * tcap, cols] and n_obs [V, 1] are the fused lists) plus
+        """The ego loop's results() of the last step (obstacles [V, 1, K * tcap, cols] and n_obs [V, 1] are the fused lists -- with track=True
+        the tracked lists [V, 1, tcap, cols], beside fused_obstacles / fused_n_obs (the fused lists), track_ids [V, tcap] (the id behind
+        each obstacle row, -1 past n_obs), match [V, K * tcap] (the id each fused row went to), n_drop [V] and rig_tracks
+        (RigTracker.tracks())) plus
         cam_obstacles [V, K, tcap, cols], cam_n_obs [V, K], n_off [V, K] (the cameras' own lists), views [V, K * tcap] (the mask of the
         cameras that saw each fused obstacle), n_skip [V] and, with a lane camera, ref_paths [V, 50, 2], n_ref [V], lane_offset [V]."""
         self.synchronize()
@@ -1480,6 +1517,15 @@ class RigLoop:
         out["cam_n_obs"] = hot.n_obs.cpu().numpy().reshape(V, K)
         out["n_off"] = hot.n_off.cpu().numpy().reshape(V, K)
         out["views"], out["n_skip"] = self.views.cpu().numpy(), self.n_skip.cpu().numpy()
+        if self.tracker is not None:
+            # obstacles / n_obs above are the tracked lists the ego loop planned around
+            t = self.tracker
+            out["fused_obstacles"], out["fused_n_obs"] = self.obstacles.cpu().numpy(), self.n_obs.cpu().numpy()
+            out["rig_tracks"] = t.tracks()
+            slot, n = t.obs_slot.cpu().numpy(), t.n_obs.cpu().numpy()
+            written = np.arange(t.tcap)[None, :] < n[:, None]
+            out["track_ids"] = np.where(written, np.take_along_axis(out["rig_tracks"]["id"], np.where(written, slot, 0), axis=1), -1)
+            out["match"], out["n_drop"] = t.match.cpu().numpy(), t.n_drop.cpu().numpy()
         if self.lane_camera is not None:
             out["ref_paths"], out["n_ref"] = self.ref_paths.cpu().numpy(), self.n_ref.cpu().numpy()
             out["lane_offset"] = self.lane_offset.cpu().numpy()

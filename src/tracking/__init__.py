@@ -1,3 +1,3 @@
-from multimodal_autonomous_driving_perception_and_planning_amd.tracking import MultiObjectTracker, Track, TrackFilter  # noqa: F401
+from multimodal_autonomous_driving_perception_and_planning_amd.tracking import MultiObjectTracker, RigTracker, Track, TrackFilter  # noqa: F401
 
-__all__ = ["MultiObjectTracker", "Track", "TrackFilter"]
+__all__ = ["MultiObjectTracker", "Track", "TrackFilter", "RigTracker"]
