@@ -7,8 +7,10 @@
 // (simdet_frame, tracker_body, kf_axis_chain1 + kf_axis_tail1 -- kf_axis_body's one-frame step, same expressions -- / kf_dense_stream,
 // plan_block: the stages' *_dev.h headers, which this file and the stage files both include), so the results are those of the separate
 // launches bit for bit (tests/test_gpu_step.py, tests/test_gpu_step_roles.py):
-//   workgroups [0, S)      stream s: simulated detections of its next frame (one thread: a 232-byte table row + box arithmetic),
-//                          then the tracker frame on eight replica waves, then -- optionally -- the stream's 32-byte-per-row
+//   workgroups [0, S)      stream s: simulated detections of its next frame (one thread: a 232-byte table row + box arithmetic;
+//                          its wave stores their output arrays at once, in front of the role's wait for the previous step), then
+//                          the tracker frame on eight replica waves, started from an LDS copy of the stream's record that
+//                          tracker_body reads with LDS loads (INIT_LDS), then -- optionally -- the stream's 32-byte-per-row
 //                          wire table for the all-gather (exchange.hip's format), all from the same workgroup
 //   workgroups [S, 2 S)    stream s: Kalman step in the first wave (axis-separable filter in two parts -- kf_axis_chain1: the record
 //                          and the planner's start state, all the next step and the planner wait for; kf_axis_tail1: the rest of
@@ -204,7 +206,7 @@ __device__ __forceinline__ void hot_step_body(const StepArgs& a0) {
     __shared__ __attribute__((aligned(16))) double kf_carry[KF_CARRY_DOUBLES];
     __shared__ int kf_tail;
     // the step's inputs that do not come from the previous step, in LDS before the wait: the frame's detections (made here, copied
-    // to their output arrays by the other threads) and the ego measurement
+    // to their output arrays by thread 0's wave, also in front of the wait) and the ego measurement
     __shared__ __attribute__((aligned(16))) int d_box[8 * 4];
     __shared__ __attribute__((aligned(16))) double d_conf[8], d_area[8], z_stage[4];
     __shared__ int d_cls[8], d_n[1];
@@ -229,7 +231,22 @@ __device__ __forceinline__ void hot_step_body(const StepArgs& a0) {
             for (int i = 0; i < a.dcap; ++i)      // the boxes' areas, as the tracker's chunk hand-over makes them (exact in float64)
                 d_area[i] = (double)(d_box[4 * i + 2] - d_box[4 * i]) * (double)(d_box[4 * i + 3] - d_box[4 * i + 1]);
         }
-        ck.mark(0);                   // detections made
+        // The detections' output arrays, by thread 0's own wave (dcap <= 8 lanes of it) and IN FRONT of the wait: the tracker reads
+        // the LDS copy, the arrays serve only the caller, and this step's output set is free (sets rotate per step; the previous
+        // user of the set has finished in stream order).  Stored behind the record fetch they were four unacknowledged stores of
+        // column wave 0 in the middle of the chain; here their acknowledgements arrive while the role waits for its predecessor.
+        if (tid < 64) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+            if (tid < a.dcap) {
+                reinterpret_cast<int4*>(a.det_box)[(size_t)s * a.dcap + tid] = reinterpret_cast<const int4*>(d_box)[tid];
+                a.det_cls[(size_t)s * a.dcap + tid] = d_cls[tid];
+                a.det_conf[(size_t)s * a.dcap + tid] = d_conf[tid];
+                if (tid == 0) a.det_n[s] = d_n[0];
+            }
+        }
+        ck.mark(0);                   // detections made, their output arrays stored
         // What the role needs right behind its wait is worked out in front of it, and pinned there: none of it depends on the
         // predecessor, and left to the compiler the kernel-argument loads and the address arithmetic sit between the poll's barrier
         // and the first record load, on the stream's chain.
@@ -258,15 +275,11 @@ __device__ __forceinline__ void hot_step_body(const StepArgs& a0) {
         if (seq) __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): thread 0's frame-counter store is acknowledged before any wave passes the barrier
         __syncthreads();              // the detections and the table copy are in LDS
         ck.mark(2);                   // record in LDS
-        if (tid < a.dcap) {           // the detections' output arrays (the tracker reads the LDS copy)
-            reinterpret_cast<int4*>(a.det_box)[(size_t)s * a.dcap + tid] = reinterpret_cast<const int4*>(d_box)[tid];
-            a.det_cls[(size_t)s * a.dcap + tid] = d_cls[tid];
-            a.det_conf[(size_t)s * a.dcap + tid] = d_conf[tid];
-            if (tid == 0) a.det_n[s] = d_n[0];
-        }
-        tracker_body<false, 8, STEP_NW>(a.tcfg, 1, a.dcap, d_n, d_box, d_cls, d_conf, a.tcap, a.trk_state, a.snap, a.snap_n,
-                                        a.det2trk, 1, s, smem, 0xFEDCBA9876543210ull, stage, seq, 0,
-                                        seq ? a.flags + 32 * (2 * s) : nullptr, (int)((unsigned)a.seq + 1u), (a.fence & 8) != 0, d_area);
+        // (INIT_LDS: the staged record is read with LDS loads -- no flat load, no vmcnt wait between this barrier and the first exchange)
+        tracker_body<false, 8, STEP_NW, 0, true>(a.tcfg, 1, a.dcap, d_n, d_box, d_cls, d_conf, a.tcap, a.trk_state, a.snap, a.snap_n,
+                                                 a.det2trk, 1, s, smem, 0xFEDCBA9876543210ull, stage, seq, 0,
+                                                 seq ? a.flags + 32 * (2 * s) : nullptr, (int)((unsigned)a.seq + 1u), (a.fence & 8) != 0,
+                                                 d_area);
         // (overlapped: the wave that keeps the complete rows has published the step counter itself, behind an s_waitcnt vmcnt(0) on its
         // record stores -- __syncthreads() compiles to s_waitcnt lgkmcnt(0) + s_barrier on this target and waits for no global store --
         // and written the snapshot rows after that; the successor may start before the wire table is written: the steps in flight have

@@ -96,7 +96,7 @@ __device__ __forceinline__ void lds_sync() {
 // column waves now publish a frame's decisions (every row's matched column + the taken columns, 65 bytes, by wave 0) and go on;
 // the ninth wave applies them after the next frame's barrier -- the same barrier, no other synchronisation -- from a double-
 // buffered detection chunk.  Same arithmetic on the same values in the same order per row: results are bit-identical.
-template <bool MULTIWAVE, int DREG, int REP, int PIPE = 0>
+template <bool MULTIWAVE, int DREG, int REP, int PIPE = 0, bool INIT_LDS = false>
 __device__ __forceinline__ void tracker_body(const av_tracker_cfg& cfg, int n_frames, int dcap, const int32_t* __restrict__ det_n,
                                const int32_t* __restrict__ det_box, const int32_t* __restrict__ det_cls,
                                const double* __restrict__ det_conf, int tcap, unsigned char* __restrict__ state_all,
@@ -112,9 +112,13 @@ __device__ __forceinline__ void tracker_body(const av_tracker_cfg& cfg, int n_fr
     // after that -- the successor launch waits for the record, not for the outputs
     // det_sf0 >= 0 (replica kernel): the detection arrays are indexed from this frame slot instead of s * n_frames (the one-launch
     // time-step hands over the LDS copy its detector role wrote, slot 0)
-    // init_src: where the stream's header and rows are read from at entry instead of its state record (the one-launch time-step of
-    // step.hip hands over an LDS copy); everything is written to the state record as always -- coherent_out: with device-scope
-    // (write-through) stores, for a successor launch already in flight, possibly on another XCD
+    // init_src: where the stream's header and rows are read from at entry instead of its state record; everything is written to the
+    // state record as always -- coherent_out: with device-scope (write-through) stores, for a successor launch already in flight,
+    // possibly on another XCD
+    // INIT_LDS (the one-launch time-step of step.hip): init_src is a copy in THIS WORKGROUP'S LDS, behind a barrier the caller has
+    // passed -- a compile-time property, so the header and the rows come in with ds_read instructions (one lgkmcnt wait, no vmcnt:
+    // a wave's outstanding global stores are not waited for).  As a run-time select between an LDS and a global pointer they were
+    // flat loads, in front of which the compiler drains vmcnt.
     constexpr bool REPL = REP > 1;
     static_assert(!(REPL && MULTIWAVE), "replica waves hold the whole table: tcap must be 64");
     static_assert(REP == 1 || REP == 8, "the exchange buffers are laid out for 8 columns");
@@ -168,19 +172,39 @@ __device__ __forceinline__ void tracker_body(const av_tracker_cfg& cfg, int n_fr
 
     const int* hdr_in = init_src ? reinterpret_cast<const int*>(init_src) : hdr;
     const av_track_row* rows_in = init_src ? reinterpret_cast<const av_track_row*>(init_src + HDR_INTS * 4) : rows;
-    int T = hdr_in[0], next_id = hdr_in[1], frame_count = hdr_in[2], status = hdr_in[3];
+    int T, next_id, frame_count, status;
     Row r{};
-    if (row < T) {
-        const av_track_row g = rows_in[row];
+    auto take = [&](const av_track_row& g) {
         r.id = g.id, r.x1 = g.x1, r.y1 = g.y1, r.x2 = g.x2, r.y2 = g.y2, r.cls = g.cls;
         r.age = g.age, r.hits = g.hits, r.misses = g.misses, r.slot = g.slot, r.hlen = g.hist_len;
         r.hpos = g.hist_len % L;
         r.conf = g.conf, r.vx = g.vx, r.vy = g.vy;
+    };
+    if (INIT_LDS) {
+        typedef __attribute__((address_space(3))) const int lds_i32;
+        typedef int v4i32 __attribute__((ext_vector_type(4)));
+        typedef __attribute__((address_space(3))) const v4i32 lds_v4i32;
+        static_assert(sizeof(av_track_row) == 4 * sizeof(v4i32), "a row is four 16-byte LDS reads");
+        lds_i32* h3 = (lds_i32*)init_src;
+        T = h3[0], next_id = h3[1], frame_count = h3[2], status = h3[3];
+        if (row < T) {
+            lds_v4i32* q3 = (lds_v4i32*)(init_src + HDR_INTS * 4) + 4 * row;
+            const v4i32 q[4] = {q3[0], q3[1], q3[2], q3[3]};
+            av_track_row g;
+            __builtin_memcpy(&g, q, sizeof(g));
+            take(g);
+        }
+    } else {
+        T = hdr_in[0], next_id = hdr_in[1], frame_count = hdr_in[2], status = hdr_in[3];
+        if (row < T) {
+            const av_track_row g = rows_in[row];
+            take(g);
+        }
+        // Retire the table loads here (global memory only: LDS reads count in lgkmcnt).  Otherwise the compiler places their
+        // wait at the first use inside the frame loop, where (vmcnt counts loads and stores in order) it would also drain the
+        // previous frame's output stores on every iteration.
+        __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0), expcnt/lgkmcnt untouched
     }
-    // Retire the table loads here.  Otherwise the compiler places their wait at the first use inside
-    // the frame loop, where (vmcnt counts loads and stores in order) it would also drain the previous
-    // frame's output stores on every iteration.
-    __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0), expcnt/lgkmcnt untouched
     if (row < 32) sh.slot_bits[row] = 0;
     lds_sync<MULTIWAVE>();
     if (row < T) atomicOr(&sh.slot_bits[r.slot >> 5], 1u << (r.slot & 31));

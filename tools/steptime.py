@@ -19,7 +19,7 @@ lp.seq_flags[base:base + 64].zero_(); torch.cuda.synchronize()
 t0 = time.perf_counter(); lp.enqueue_steps(N); lp.synchronize(); dt = (time.perf_counter() - t0) / N * 1e6
 st = lp.seq_flags[base:base + 64].cpu().numpy().view(np.uint64).reshape(2, 16).astype(np.float64)
 print("depth %d: %.2f us per step (with the clock stamps)" % (D, dt))
-names = [["detections", "wait for predecessor", "record -> LDS (+barrier)", "tracker frame, record out + acknowledged, counter, outputs", "-", "-", "-", "-"],
+names = [["detections, their output arrays stored", "wait for predecessor", "record -> LDS (+barrier)", "tracker frame, record out + acknowledged, counter, outputs", "-", "-", "-", "-"],
          ["-", "wait for predecessor", "record -> LDS", "Kalman chain part, record stores issued", "barrier: planner released (start state in LDS)",
           "record acknowledged, counter stored", "planner (wave 0: phase-1 barrier, its trajectories)",
           "Kalman tail part (on the planner's first pair wave; beside the above)"]]
