@@ -634,6 +634,39 @@ int av_rig_track(av_ctx* ctx, av_stream_t stream, const av_rig_track_cfg* cfg, i
                  int ocap_out, double* obstacles, int32_t* n_obs, int32_t* obs_slot, int32_t* match, int32_t* n_skip,
                  int32_t* n_drop);
 
+/* ---- The rig's surround view (opt-in): a vehicle's K rectified frames stitched into one top-down panel --------------------------
+ * av_ground_warp gives one panel per camera, each in its own camera's road frame.  av_rig_surround gives one panel per VEHICLE in
+ * the vehicle's frame: every pixel from the cameras that see that road point, through the mounts and the cameras' ginv.  float64,
+ * every operation rounded on its own (no FMA), in the order written.  Panel pixel (r, c) of vehicle v shows the vehicle-frame
+ * road point
+ *   X = x_far - ((double)r + 0.5) * m_per_px;   Y = (((double)c + 0.5) - (double)gw / 2.0) * m_per_px
+ * For camera k = 0 .. n_cams - 1 of the vehicle (entry v * n_cams + k of mounts, ground and bgr: av_rig_fuse's convention), with
+ * the mount (cs, sn, mx, my) and q = ground[v * n_cams + k].ginv:
+ *   dx = X - mx;  dy = Y - my;  f = cs*dx + sn*dy;  l = cs*dy - sn*dx              (CameraRig.from_vehicle's order)
+ *   U, V, D, u, v, tu, tv exactly as av_ground_warp has them for the road point (f, l)
+ *   camera k CONTRIBUTES when D > 0 && f >= 0 && f <= max_range && 0 <= tu <= (w-1) * 65536 && 0 <= tv <= (h-1) * 65536
+ *   (a NaN fails); its channels p_k are av_ground_warp's bilinear taps at (tu, tv)
+ * blend 0, feather -- a weight that is the distance to the frame's border in whole pixels, plus one, in integers:
+ *   bu = min(tu, (w-1) * 65536 - tu);  bv = min(tv, (h-1) * 65536 - tv);  wt_k = (min(bu, bv) >> 16) + 1
+ *   per channel  out = (2 * sum(wt_k * p_k) + sum(wt_k)) / (2 * sum(wt_k))   over the contributing cameras, integer division
+ *   (the sums fit 32 bits: 8 cameras x 16384 x 255)
+ * blend 1, nearest -- the contributing camera with the smallest d2 = f*f + l*l gives the pixel; equal d2: the smallest k.
+ * No contributing camera: fill.  cover[v][r][c] has bit k set where camera k contributes (under either blend), 0 where none does. */
+typedef struct {
+    double x_far;        /* vehicle-frame forward coordinate of the panel's top edge, metres; finite */
+    double m_per_px;     /* > 0, finite */
+    int32_t blend;       /* 0: feather, 1: nearest */
+    uint8_t fill[3];     /* b, g, r where no camera sees the road point */
+    uint8_t reserved;    /* 0 */
+} av_surround_cfg;       /* 24 bytes */
+/*   mounts DEVICE [V][K]; ground DEVICE [V*K]; bgr [V*K][h][w][3]: RECTIFIED frames; out [V][gh][gw][3]; cover [V][gh][gw] or NULL
+ * AV_EINVAL before any launch and before the context is looked at: a null pointer other than cover and stream; n_vehicles < 1;
+ * n_cams not in 1..8; h or w not in 1..32768; gh or gw < 1; n_vehicles or ceil(gh / 16) above 65535; m_per_px not > 0 and finite;
+ * x_far not finite; blend not 0 or 1; reserved not 0; out or cover overlapping bgr. */
+int av_rig_surround(av_ctx* ctx, av_stream_t stream, const av_surround_cfg* cfg, int n_vehicles, int n_cams,
+                    const av_rig_mount* mounts, const av_ground_cfg* ground, int h, int w, const uint8_t* bgr, int gh, int gw,
+                    uint8_t* out, uint8_t* cover);
+
 /* generate_polynomial_trajectory for arbitrary (lateral offset, target speed) pairs (:126-204).
  *   state [n_traj][4], end_lateral_offset [n_traj], target_velocity [n_traj] -> waypoints [n_traj][n][6] */
 int av_planner_generate(av_ctx* ctx, av_stream_t stream, int n_traj, const double* state,
@@ -1141,6 +1174,37 @@ int av_resize_into(av_ctx* ctx, av_stream_t stream, const uint8_t* src, int sh, 
 int av_raster_draw_to(av_ctx* ctx, av_stream_t stream, int n_images, int h, int w, const uint8_t* src, int src_pitch_px, uint8_t* dst,
                       int dst_pitch_px, int dst_x0, const av_prim* prims, int prim_cap, const int32_t* n_prims, const int32_t* verts,
                       int vert_cap);
+
+/* The overlay of a rig's surround view: what the ego loop planned around as a primitive list over av_rig_surround's panel (paint it
+ * with av_raster_draw).  A fixed layout of
+ * av_rig_view_prim_cap() slots per vehicle, unused slots type 0, n_prims[v] = that number; in order:
+ *   rcap - 1      the reference path: segment i joins ref_path[v][i] and [i + 1], i + 1 < clamp(n_ref[v], 0, rcap); AV_PRIM_SEG,
+ *                 thickness 1, (b, g, r) = (0, 255, 255).  ref_path and n_ref may be NULL (together)
+ *   n_points - 1  the planned trajectory: the waypoints of candidate order[v][0] (an index outside 0 .. n_cand - 1: none), fields 0
+ *                 and 1 of consecutive ones joined; thickness 3, green (0, 255, 0).  waypoints and order may be NULL (together)
+ *   2 * ocap      per obstacle row i < clamp(n_obs[v], 0, ocap) of (x, y, r[, vx, vy]): slot 2i an AV_PRIM_RING about (x, y) of
+ *                 radius p = max(1, (int)floor(r / m_per_px + 0.5)) (type 0 unless that floor is <= 32767; a NaN fails), slot
+ *                 2i + 1 with ncol 5 an AV_PRIM_SEG of thickness 1 from (x, y) to where the obstacle is one second on,
+ *                 (x + vx, y + vy), with ncol 3 type 0.  Colour: av_bev_build's agent colour ((ids[v][i] % 6) + 6) % 6, without
+ *                 ids red (0, 0, 255)
+ *   1             the ego vehicle: an AV_PRIM_QUAD with the vehicle-frame corners (2.25, -0.9) (2.25, 0.9) (-2.25, 0.9)
+ *                 (-2.25, -0.9), white
+ * A world point (wx, wy) is placed with (x0, y0, hd, .) = plan_state[v] (float64, no FMA):
+ *   dx = wx - x0;  dy = wy - y0;  ch = cos(hd);  sh = sin(hd);  X = dx*ch + dy*sh;  Y = dy*ch - dx*sh       (the vehicle frame)
+ *   pc = floor(Y / m_per_px + (double)gw / 2.0);  pr = floor((x_far - X) / m_per_px)                        (column, row)
+ * and is drawable when pc and pr are both finite and within -32768 .. 32767; a primitive with an undrawable point is type 0.
+ *   plan_state [V][4]; obstacles [V][ocap][ncol], n_obs [V], ids [V][ocap] or NULL; ref_path [V][rcap][2], n_ref [V];
+ *   waypoints [V][n_cand][n_points][6], order [V][n_cand] (av_planner_plan's, one state per vehicle); prims [V][prim_cap]
+ * Only cfg's x_far and m_per_px are read.  AV_EINVAL before any launch and before the context is looked at: n_vehicles not in
+ * 1..65535; gh or gw not in 1..8191; ncol not 3 or 5; ocap, rcap, n_cand or n_points < 1; prim_cap below av_rig_view_prim_cap() or
+ * above 65535; m_per_px not > 0 and finite, x_far not finite; one of ref_path / n_ref or of waypoints / order without the other;
+ * any other null pointer except ids and stream. */
+int av_rig_view_prim_cap(int ocap, int rcap, int n_points);    /* (rcap-1) + (n_points-1) + 2*ocap + 1; 0 for an argument < 1 */
+int av_rig_view_build(av_ctx* ctx, av_stream_t stream, const av_surround_cfg* cfg, int n_vehicles, int gh, int gw,
+                      const double* plan_state, int ncol, int ocap, const double* obstacles, const int32_t* n_obs,
+                      const int32_t* ids, int rcap, const double* ref_path, const int32_t* n_ref,
+                      int n_cand, int n_points, const double* waypoints, const int32_t* order,
+                      av_prim* prims, int prim_cap, int32_t* n_prims);
 
 /* ---- the demo's annotated view (demo.py:122-150), composed on the device ---------------------------------------------------------
  * av_camview_build writes, one workgroup per camera, the primitive list of the camera view from what a camera loop's step left in

@@ -70,6 +70,15 @@ class RigCfg(C.Structure):
     _fields_ = [("merge_scale", C.c_double), ("merge_min", C.c_double)]
 
 
+class SurroundCfg(C.Structure):
+    """av_surround_cfg: the surround panel's geometry (x_far metres at the top edge, m_per_px), blend (0 feather, 1 nearest) and the
+    fill colour (b, g, r); 24 bytes."""
+    _fields_ = [("x_far", C.c_double), ("m_per_px", C.c_double), ("blend", C.c_int32), ("fill", C.c_uint8 * 3), ("reserved", C.c_uint8)]
+
+
+SURROUND_BLENDS = {"feather": 0, "nearest": 1}
+
+
 class RigTrackCfg(C.Structure):
     """av_rig_track_cfg: the vehicle-frame tracker's filter, gate and life cycle (seconds, metres); 72 bytes."""
     _fields_ = [("dt", C.c_double), ("q_accel", C.c_double), ("r_meas", C.c_double), ("r_range", C.c_double), ("p0_pos", C.c_double),
@@ -319,6 +328,11 @@ _SIGS = [
     ("av_rig_track_reset", C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
     ("av_rig_track", C.c_int, [vp, vp, C.POINTER(RigTrackCfg), C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp,
                                vp, vp, vp, vp]),
+    ("av_rig_surround", C.c_int, [vp, vp, C.POINTER(SurroundCfg), C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp,
+                                  vp]),
+    ("av_rig_view_prim_cap", C.c_int, [C.c_int, C.c_int, C.c_int]),
+    ("av_rig_view_build", C.c_int, [vp, vp, C.POINTER(SurroundCfg), C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int,
+                                    vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]),
     ("av_hot_step", C.c_int, [vp, vp, C.POINTER(StepLoop), C.POINTER(StepSet), vp, C.c_int, C.c_int]),
     ("av_hot_step_fits", C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     ("av_hot_step_plan", C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),

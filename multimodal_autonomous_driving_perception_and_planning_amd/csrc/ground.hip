@@ -5,7 +5,8 @@
 // (bev_renderer.py:207-208), the map av_obstacle_cfg carries.  A flat road seen by a pinhole camera is a plane-to-plane
 // projection, so image (u, v, 1) and road (forward, lateral, 1) are related by a 3 x 3 matrix up to scale; av_ground_cfg holds it
 // and its true inverse, so that one sign convention (D > 0: below the horizon, in front of the camera) holds in both directions.
-// The projection of image points is in ground_dev.h (obstacles.hip, bridge.hip use it); this file has the pixel kernel.
+// The projection of image points is in ground_dev.h (obstacles.hip, bridge.hip use it), and so is a panel pixel's sampling, which
+// surround.hip shares; this file has the pixel kernel.
 //
 // av_ground_warp, mapping: a thread makes four adjacent pixels of one panel row and stores them as 12 bytes at once (tail of a
 // row: byte by byte); a 256-thread workgroup covers a tile of 64 columns x 16 rows, because vertically adjacent panel pixels read
@@ -13,7 +14,7 @@
 // a tile's taps share cache lines in both directions.  Per pixel: the road point of the pixel's centre through ginv in float64
 // (header's operation order), the source position rounded to 1/65536 pixel, then rasterdev::resize_channel's bilinear rule.
 #include "common.h"
-#include "raster_dev.h"
+#include "ground_dev.h"
 
 #include <cmath>
 #include <cstring>
@@ -25,18 +26,8 @@ constexpr int TILE_W = 64, TILE_H = 16, PX = 4;     // pixels per tile row, rows
 // one panel pixel as b | g << 8 | r << 16; `fill` where the road point is at or above the horizon, behind the camera or outside the frame
 __device__ __forceinline__ unsigned warp_pixel(const double* __restrict__ q, const uint8_t* __restrict__ src, int h, int w, double f,
                                                double l, unsigned fill) {
-    const double U = (q[0] * f + q[1] * l) + q[2], V = (q[3] * f + q[4] * l) + q[5], D = (q[6] * f + q[7] * l) + q[8];
-    if (!(D > 0.0)) return fill;
-    const double u = U / D, v = V / D;
-    const double tu = floor(u * 65536.0 + 0.5), tv = floor(v * 65536.0 + 0.5);
-    // (a NaN fails; inside these bounds both are exact integers below 2^47)
-    if (!(tu >= 0.0 && tu <= (double)(w - 1) * 65536.0 && tv >= 0.0 && tv <= (double)(h - 1) * 65536.0)) return fill;
-    const long long iu = (long long)tu, iv = (long long)tv;
-    rasterdev::ResizeTap t;
-    t.x0 = (int)(iu >> 16), t.wx = (int)(iu & 65535), t.x1 = min(t.x0 + 1, w - 1);      // 0 <= x0 <= w - 1
-    t.y0 = (int)(iv >> 16), t.wy = (int)(iv & 65535), t.y1 = min(t.y0 + 1, h - 1);      // 0 <= y0 <= h - 1
-    return (unsigned)rasterdev::resize_channel(src, w, t, 0) | ((unsigned)rasterdev::resize_channel(src, w, t, 1) << 8) |
-           ((unsigned)rasterdev::resize_channel(src, w, t, 2) << 16);
+    long long iu, iv;
+    return grounddev::warp_position(q, h, w, f, l, iu, iv) ? grounddev::warp_sample(src, h, w, iu, iv) : fill;
 }
 
 __global__ void __launch_bounds__(256) ground_warp_kernel(const av_ground_cfg* __restrict__ ground, int h, int w,

@@ -1,8 +1,10 @@
 // The ground-plane camera model's device side (include/avhot.h: av_ground_cfg): the projection of an image point onto the road,
-// shared by the ground forms of av_track_obstacles (obstacles.hip) and av_lane_paths (bridge.hip).  float64, every operation
-// rounded on its own, in the order the header states.
+// shared by the ground forms of av_track_obstacles (obstacles.hip) and av_lane_paths (bridge.hip), and the way back, a road point's
+// place in the frame and the picture there, shared by av_ground_warp (ground.hip) and av_rig_surround (surround.hip).  float64,
+// every operation rounded on its own, in the order the header states.
 #pragma once
 #include "common.h"
+#include "raster_dev.h"
 
 namespace grounddev {
 
@@ -30,6 +32,29 @@ __device__ __forceinline__ RoadJac jacobian(const double* __restrict__ g, const 
     j.dfu = (g[0] - p.f * g[6]) / p.D, j.dfv = (g[1] - p.f * g[7]) / p.D;
     j.dlu = (g[3] - p.l * g[6]) / p.D, j.dlv = (g[4] - p.l * g[7]) / p.D;
     return j;
+}
+
+// the frame position of road point (f, l) through q = av_ground_cfg.ginv, in 1/65536 pixels (av_ground_warp's tu, tv): false where
+// the point is at or above the horizon, behind the camera or outside the h x w frame (a NaN fails); inside, both are exact integers
+// below 2^47
+__device__ __forceinline__ bool warp_position(const double* __restrict__ q, int h, int w, double f, double l, long long& iu,
+                                              long long& iv) {
+    const double U = (q[0] * f + q[1] * l) + q[2], V = (q[3] * f + q[4] * l) + q[5], D = (q[6] * f + q[7] * l) + q[8];
+    if (!(D > 0.0)) return false;
+    const double u = U / D, v = V / D;
+    const double tu = floor(u * 65536.0 + 0.5), tv = floor(v * 65536.0 + 0.5);
+    if (!(tu >= 0.0 && tu <= (double)(w - 1) * 65536.0 && tv >= 0.0 && tv <= (double)(h - 1) * 65536.0)) return false;
+    iu = (long long)tu, iv = (long long)tv;
+    return true;
+}
+
+// the picture at such a position as b | g << 8 | r << 16: rasterdev::resize_channel's bilinear rule
+__device__ __forceinline__ unsigned warp_sample(const uint8_t* __restrict__ src, int h, int w, long long iu, long long iv) {
+    rasterdev::ResizeTap t;
+    t.x0 = (int)(iu >> 16), t.wx = (int)(iu & 65535), t.x1 = min(t.x0 + 1, w - 1);      // 0 <= x0 <= w - 1
+    t.y0 = (int)(iv >> 16), t.wy = (int)(iv & 65535), t.y1 = min(t.y0 + 1, h - 1);      // 0 <= y0 <= h - 1
+    return (unsigned)rasterdev::resize_channel(src, w, t, 0) | ((unsigned)rasterdev::resize_channel(src, w, t, 1) << 8) |
+           ((unsigned)rasterdev::resize_channel(src, w, t, 2) << 16);
 }
 
 }  // namespace grounddev

@@ -18,6 +18,8 @@
 #include "common.h"
 #include "raster_dev.h"
 
+#include <cmath>
+
 namespace {
 
 using namespace rasterdev;
@@ -371,6 +373,98 @@ __global__ void __launch_bounds__(256) bev_build_kernel(int n_streams, int n_fra
     }
 }
 
+// ---- the overlay of a rig's surround view (av_rig_surround's panel, surround.hip) -------------------------------------------------
+// One workgroup per vehicle writes what the ego loop planned around as a primitive list in fixed slot ranges (unused slots stay
+// type 0): the reference path, the planned trajectory, a ring and a velocity segment per obstacle, the ego vehicle.  World points go
+// through the ego start state into the vehicle frame and from there to the panel's pixels, in the header's operation order.
+struct SurroundGeom {
+    double x0, y0, ch, sh, x_far, m, half_w;
+};
+// vehicle-frame road point -> panel pixel (column, row); false when it cannot be drawn (a NaN fails)
+__device__ __forceinline__ bool sv_place_vehicle(const SurroundGeom& g, double X, double Y, int& pc, int& pr) {
+    const double c = floor(Y / g.m + g.half_w), r = floor((g.x_far - X) / g.m);
+    if (!(c >= -32768.0 && c <= 32767.0 && r >= -32768.0 && r <= 32767.0)) return false;
+    pc = (int)c, pr = (int)r;
+    return true;
+}
+__device__ __forceinline__ bool sv_place(const SurroundGeom& g, double wx, double wy, int& pc, int& pr) {
+    const double dx = wx - g.x0, dy = wy - g.y0;
+    return sv_place_vehicle(g, dx * g.ch + dy * g.sh, dy * g.ch - dx * g.sh, pc, pr);
+}
+__device__ __forceinline__ av_prim sv_seg(const SurroundGeom& g, double ax, double ay, double bx, double by, int th, unsigned bgr) {
+    int x0, y0, x1, y1;
+    if (!sv_place(g, ax, ay, x0, y0) || !sv_place(g, bx, by, x1, y1)) return av_prim{};
+    return mk(AV_PRIM_SEG, x0, y0, x1, y1, th, bgr);
+}
+
+__global__ void __launch_bounds__(256) rig_view_build_kernel(av_surround_cfg cfg, int gw, const double* __restrict__ plan_state, int ncol,
+                                                             int ocap, const double* __restrict__ obstacles,
+                                                             const int32_t* __restrict__ n_obs, const int32_t* __restrict__ ids, int rcap,
+                                                             const double* __restrict__ ref_path, const int32_t* __restrict__ n_ref,
+                                                             int n_cand, int n_pts, const double* __restrict__ wp,
+                                                             const int32_t* __restrict__ order, int prim_cap, av_prim* __restrict__ prims,
+                                                             int32_t* __restrict__ n_prims) {
+    const int v = blockIdx.x, tid = threadIdx.x;
+    const double* ps = plan_state + (size_t)v * 4;
+    SurroundGeom g;
+    g.x0 = ps[0], g.y0 = ps[1], g.ch = cos(ps[2]), g.sh = sin(ps[2]);
+    g.x_far = cfg.x_far, g.m = cfg.m_per_px, g.half_w = (double)gw / 2.0;
+    av_prim* out = prims + (size_t)v * prim_cap;
+    int base = 0;
+    // ---- the reference path: segment i joins points i and i + 1 ---------------------------------------------------------
+    const int nr = ref_path ? min(max(n_ref[v], 0), rcap) : 0;
+    for (int i = tid; i < rcap - 1; i += 256) {
+        av_prim q{};
+        if (i + 1 < nr) {
+            const double* a = ref_path + ((size_t)v * rcap + i) * 2;
+            q = sv_seg(g, a[0], a[1], a[2], a[3], 1, 0xFFFF00u);                 // (0, 255, 255) in BGR
+        }
+        out[base + i] = q;
+    }
+    base += rcap - 1;
+    // ---- the planned trajectory: rank 0 of the stable order ---------------------------------------------------------------
+    const int best = wp ? order[(size_t)v * n_cand] : -1;
+    for (int i = tid; i < n_pts - 1; i += 256) {
+        av_prim q{};
+        if (best >= 0 && best < n_cand) {
+            const double* a = wp + (((size_t)v * n_cand + best) * n_pts + i) * 6;
+            q = sv_seg(g, a[0], a[1], a[6], a[7], 3, 0x00FF00u);
+        }
+        out[base + i] = q;
+    }
+    base += n_pts - 1;
+    // ---- the obstacles: a ring of the obstacle's radius and its way in one second -----------------------------------------
+    const unsigned agent_cols[6] = {0x00FF00u, 0x0000FFu, 0xFF0000u, 0x00FFFFu, 0xFF00FFu, 0xFFFF00u};     // bev_build_kernel's
+    const int no = min(max(n_obs[v], 0), ocap);
+    for (int i = tid; i < ocap; i += 256) {
+        av_prim ring{}, seg{};
+        if (i < no) {
+            const double* o = obstacles + ((size_t)v * ocap + i) * ncol;
+            const unsigned col = ids ? agent_cols[((ids[(size_t)v * ocap + i] % 6) + 6) % 6] : 0xFF0000u;  // (0, 0, 255) in BGR
+            const double pf = floor(o[2] / g.m + 0.5);
+            int cx, cy;
+            if (pf <= 32767.0 && sv_place(g, o[0], o[1], cx, cy)) ring = mk(AV_PRIM_RING, cx, cy, 0, 0, pf < 1.0 ? 1 : (int)pf, col);
+            if (ncol == 5) seg = sv_seg(g, o[0], o[1], o[0] + o[3], o[1] + o[4], 1, col);
+        }
+        out[base + 2 * i] = ring, out[base + 2 * i + 1] = seg;
+    }
+    base += 2 * ocap;
+    // ---- the ego vehicle: 4.5 m x 1.8 m about the vehicle frame's origin ---------------------------------------------------
+    if (tid == 0) {
+        av_prim q{};
+        int x[4], y[4];
+        const double cx[4] = {2.25, 2.25, -2.25, -2.25}, cy[4] = {-0.9, 0.9, 0.9, -0.9};
+        bool ok = true;
+        for (int k = 0; k < 4; ++k) ok = sv_place_vehicle(g, cx[k], cy[k], x[k], y[k]) && ok;
+        if (ok) {
+            q = mk(AV_PRIM_QUAD, x[0], y[0], x[1], y[1], 0, 0xFFFFFFu);
+            q.x2 = x[2], q.y2 = y[2], q.x3 = x[3], q.y3 = y[3];
+        }
+        out[base] = q;
+        n_prims[v] = base + 1;
+    }
+}
+
 // f-4: planar YUV 4:2:0 (I420) -> interleaved BGR, the pixel work of video ingest (what a decoder hands
 // over; cv2.VideoCapture.read returns BGR, video_loader.py:96-106).  ITU-R BT.601 limited range in OpenCV's 20-bit fixed
 // point (cvtColor COLOR_YUV2BGR_I420: CY 1220542, CUB 2116026, CUG -409993, CVG -852492, CVR 1673527), restated from its
@@ -454,6 +548,37 @@ int av_bev_build(av_ctx* ctx, av_stream_t stream, const av_bev_cfg* cfg, int n_s
     hipLaunchKernelGGL(bev_build_kernel, dim3(n_streams), dim3(256), 0, as_stream(stream), n_streams, n_frames, frame, *cfg, tcap,
                        trajectory_length, snap, snap_n, (const uint8_t*)tracker_state, av_tracker_state_bytes(tcap, trajectory_length),
                        vstate, waypoints, order, ctx->n_cand, ctx->n_points, prim_cap, prims, n_prims);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
+int av_rig_view_prim_cap(int ocap, int rcap, int n_points) {
+    if (ocap < 1 || rcap < 1 || n_points < 1) return 0;
+    const long long need = ((long long)rcap - 1) + ((long long)n_points - 1) + 2LL * ocap + 1;
+    return need <= 2147483647LL ? (int)need : 0;
+}
+
+int av_rig_view_build(av_ctx* ctx, av_stream_t stream, const av_surround_cfg* cfg, int n_vehicles, int gh, int gw,
+                      const double* plan_state, int ncol, int ocap, const double* obstacles, const int32_t* n_obs, const int32_t* ids,
+                      int rcap, const double* ref_path, const int32_t* n_ref, int n_cand, int n_points, const double* waypoints,
+                      const int32_t* order, av_prim* prims, int prim_cap, int32_t* n_prims) {
+    AV_REQUIRE(n_vehicles >= 1 && n_vehicles <= 65535, AV_EINVAL, "av_rig_view_build: n_vehicles must be in 1..65535");
+    AV_REQUIRE(gh >= 1 && gw >= 1 && gh < 8192 && gw < 8192, AV_EINVAL, "av_rig_view_build: panel size %dx%d not below 8192 (the rasteriser's)",
+               gw, gh);
+    AV_REQUIRE(ncol == 3 || ncol == 5, AV_EINVAL, "av_rig_view_build: ncol %d is neither 3 (x, y, r) nor 5 (x, y, r, vx, vy)", ncol);
+    AV_REQUIRE(ocap >= 1 && rcap >= 1 && n_cand >= 1 && n_points >= 1, AV_EINVAL,
+               "av_rig_view_build: ocap, rcap, n_cand and n_points must be >= 1");
+    const int need = av_rig_view_prim_cap(ocap, rcap, n_points);
+    AV_REQUIRE(need > 0 && prim_cap >= need && prim_cap <= 65535, AV_EINVAL, "av_rig_view_build: prim_cap %d, need %d (<= 65535)", prim_cap,
+               need);
+    AV_REQUIRE(cfg, AV_EINVAL, "av_rig_view_build: null cfg");
+    AV_REQUIRE(cfg->m_per_px > 0.0 && std::isfinite(cfg->m_per_px) && std::isfinite(cfg->x_far), AV_EINVAL,
+               "av_rig_view_build: cfg m_per_px must be > 0 and finite, x_far finite");
+    AV_REQUIRE((ref_path == nullptr) == (n_ref == nullptr), AV_EINVAL, "av_rig_view_build: ref_path and n_ref come together");
+    AV_REQUIRE((waypoints == nullptr) == (order == nullptr), AV_EINVAL, "av_rig_view_build: waypoints and order come together");
+    AV_REQUIRE(ctx && plan_state && obstacles && n_obs && prims && n_prims, AV_EINVAL, "av_rig_view_build: null argument");
+    hipLaunchKernelGGL(rig_view_build_kernel, dim3((unsigned)n_vehicles), dim3(256), 0, as_stream(stream), *cfg, gw, plan_state, ncol, ocap,
+                       obstacles, n_obs, ids, rcap, ref_path, n_ref, n_cand, n_points, waypoints, order, prim_cap, prims, n_prims);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }

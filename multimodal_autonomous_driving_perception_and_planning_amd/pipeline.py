@@ -1346,7 +1346,7 @@ class RigLoop:
         (av_lane_paths_ground through rig.vehicle_calibration(lane_camera)), None for no path; its mount may not be yawed beyond
         +-pi/2, since a path behind the vehicle is none.  fuse_kw: av_rig_cfg's merge_scale and merge_min (1.0, 1.0 m).  Everything
         else is CameraLoop's; kf_kw and planner_kw go to the ego loop.  The one-launch step, the overlapped loop, graph capture, tags
-        and views are refused by name.
+        and the per-camera annotated views are refused by name; the rig's own picture is enqueue_surround_view().
         track=True: a tracking.RigTracker follows the fused lists (av_rig_track behind av_rig_fuse, on the ego stream) and the
         ego loop plans around its confirmed tracks -- ids that persist across frames and cameras, coasting through the frames in
         which no camera sees an object.  rig_track_kw: RigTracker's settings (av_rig_track_cfg's fields; dt defaults to the ego
@@ -1429,6 +1429,8 @@ class RigLoop:
             self.n_ref = torch.zeros(V, dtype=i32, device=d)
             self.lane_offset = torch.full((V,), float("nan"), dtype=f64, device=d)
             self.ego.set_reference_paths(self.ref_paths, self.n_ref)
+        self.surround_view = self.surround_cover = None     # enqueue_surround_view
+        self._surround = self._surround_key = self._surround_ids = None
         self._stepped = False
         torch.cuda.current_stream(d).synchronize()          # the buffers are filled before the loops' streams touch them
 
@@ -1495,6 +1497,47 @@ class RigLoop:
         self._stepped = True
         if sync:
             self.synchronize()
+
+    def enqueue_surround_view(self, gh=800, gw=800, x_far=40.0, m_per_px=0.1, fill=(0, 0, 0), blend="feather", overlay=True):
+        """The rig's own picture of the last step(), on the ego stream (call it behind step(); the next camera half waits for that
+        stream): self.surround_view uint8 [V, gh, gw, 3], every vehicle's K frames (cams.cam.frames: rectified, read and never
+        written) stitched into one top-down panel in the vehicle's frame -- row 0 at x_far metres ahead, m_per_px metres per pixel,
+        the forward axis down the middle column, `fill` where no camera sees the road, blend "feather" or "nearest"
+        (visualization.SurroundView, av_rig_surround) -- and self.surround_cover uint8 [V, gh, gw], bit k where camera k saw the
+        pixel.  overlay: what the ego loop planned around is drawn over the panel (av_rig_view_build, av_raster_draw): the tracked
+        list coloured by track id with track=True, else the fused list, each obstacle a ring of its radius and, with velocities, its
+        way in one second; the lane camera's reference path; the best trajectory; the ego vehicle."""
+        from .visualization.surround_view import SurroundView, check_panel, surround_cfg
+        if not self._stepped:
+            raise RuntimeError("enqueue_surround_view draws what a step() left behind: call it after one")
+        if not isinstance(overlay, (bool, np.bool_)):
+            raise ValueError("RigLoop: overlay is True or False")
+        check_panel(self.V, self.h, self.w, gh, gw)
+        surround_cfg(x_far, m_per_px, fill, blend)                                  # (ValueError for a setting outside its range)
+        ego, V = self.ego, self.V
+        key = (int(gh), int(gw), float(x_far), float(m_per_px), tuple(int(c) for c in fill), blend)
+        with torch.cuda.stream(ego.stream):                 # the view's buffers and the ids below are made on the stream that fills them
+            if getattr(self, "_surround_key", None) != key:
+                self._surround = SurroundView(self.rig, V, self.h, self.w, gh=key[0], gw=key[1], x_far=key[2], m_per_px=key[3],
+                                              fill=key[4], blend=blend, ctx=ego.ctx)
+                self._surround_key = key
+            sv = self._surround
+            sv.render(self.cams.cam.frames, stream=ego._s)
+            self.surround_view, self.surround_cover = sv.panel, sv.cover
+            if not overlay:
+                return
+            ids = None
+            if self.tracker is not None:
+                t = self.tracker
+                obstacles, n_obs = t.obstacles, t.n_obs
+                # the id of the slot behind each row (RigTracker.tracks()' first field), gathered on the device
+                slot_ids = t.state[:, nat.RIG_TRACK_HDR_BYTES:].reshape(V, t.tcap, nat.RIG_TRACK_SLOT_BYTES)[:, :, :4].contiguous()
+                slot_ids = slot_ids.view(torch.int32).reshape(V, t.tcap)
+                ids = self._surround_ids = torch.gather(slot_ids, 1, t.obs_slot.clamp(0, t.tcap - 1).long()).contiguous()
+            else:
+                obstacles, n_obs = self.obstacles, self.n_obs.view(V)
+            sv.draw(ego.plan_state, obstacles, n_obs, ids=ids, ref_path=self.ref_paths, n_ref=self.n_ref, waypoints=ego.wp,
+                    order=ego.order, stream=ego._s)
 
     def capture(self):
         raise RuntimeError("RigLoop: graph capture is out of scope")
