@@ -136,7 +136,8 @@ class LaneBatch:
     """One av_lane_detect batch on cuda:0: the workspace (zero-filled by av_lane_workspace_init), the per-frame
     state / poly / pts / info / conf tensors and, by default, the configuration lane_detector.py uses (HoughLinesP 50, 50,
     150; smoothing 0.7).  `bgr`: frames as a list of arrays, a u8 device tensor [S][h][w][3], or None (run() is then given one,
-    or the batch only runs the Hough / fit stages on lists written by load_points / load_segments)."""
+    or the batch only runs the Hough / fit stages on lists written by load_points / load_segments, or the pixel stages on gray
+    images written by load_gray)."""
 
     def __init__(self, S, h, w, MS, bgr=None, threshold=50, min_line_length=50, max_line_gap=150, smoothing=0.7):
         import torch
@@ -154,15 +155,22 @@ class LaneBatch:
         self.conf = torch.zeros(S, 2, dtype=torch.float64, device=dev)
         self.cfg = nat.LaneCfg(threshold, min_line_length, max_line_gap, MS, smoothing)
 
-    def run(self, stages, bgr=None):
-        """av_lane_detect on the whole batch (default ROI), then a device synchronize."""
+    def run(self, stages, bgr=None, roi_rows=None):
+        """av_lane_detect on the whole batch, then a device synchronize.  roi_rows: None (the default trapezoid) or the caller's ROI,
+        int32 [h][2] = inclusive [xl, xr] per row (xl > xr: an empty row), shared by the frames of the batch."""
         import ctypes as C
         import torch
         nat = self.nat
-        if bgr is None and self.bgr is None and (stages & 16):
-            self.bgr = torch.zeros(256, dtype=torch.uint8, device=self.ws.device)      # never read: the pixel stages do not run
+        if bgr is None and self.bgr is None and (stages & (16 | 64)):
+            self.bgr = torch.zeros(256, dtype=torch.uint8, device=self.ws.device)      # never read: no BGR stage runs
+        roi = None
+        if roi_rows is not None:
+            roi_rows = np.ascontiguousarray(roi_rows, np.int32)
+            assert roi_rows.shape == (self.h, 2)
+            roi = torch.as_tensor(roi_rows).to(self.ws.device)
         nat.check(self.L.av_lane_detect(self.ctx.handle, self.sh, C.byref(self.cfg), self.S, self.h, self.w,
-                                        nat.ptr(self.bgr if bgr is None else bgr), None, nat.ptr(self.ws), nat.ptr(self.state),
+                                        nat.ptr(self.bgr if bgr is None else bgr), nat.ptr(roi) if roi is not None else None,
+                                        nat.ptr(self.ws), nat.ptr(self.state),
                                         nat.ptr(self.poly), nat.ptr(self.pts), nat.ptr(self.info), nat.ptr(self.conf), stages))
         torch.cuda.synchronize()
 
@@ -185,6 +193,20 @@ class LaneBatch:
         raw = np.ascontiguousarray(arr).view(np.uint8).reshape(-1)
         assert offset + raw.size <= nb
         self.ws[off + offset:off + offset + raw.size].copy_(torch.as_tensor(raw))
+
+    def load_gray(self, s, image, lo, hi):
+        """Frame s's input of a given-gray call (stage bit 64): the u8 image (view 0) and its Canny thresholds (view 4: lo, hi as
+        doubles)."""
+        image = np.array(image, np.uint8)               # a writable copy: torch.as_tensor refuses read-only arrays
+        assert image.shape == (self.h, self.w)
+        self._put(0, s * self.h * self.w, image)
+        self._put(4, 32 * s, np.array([lo, hi], np.float64))
+
+    def points(self, s):
+        """Frame s's point list as the pixel stages left it (views 9 / 10): uint32 x | y << 16."""
+        n = int(self.view(10, np.int32, (self.S,))[s])
+        assert 0 <= n <= self.h * self.w
+        return self.view(9, np.uint32, (self.S, self.h * self.w))[s, :n].copy()
 
     def load_points(self, s, edge_map):
         """Frame s's Hough input as the pixel stages would leave it for `edge_map` (u8 [h][w], non-zero = edge): the row-major
