@@ -1032,8 +1032,9 @@ int av_tags_pack(av_ctx* ctx, av_stream_t stream, int n_streams, int n_frames, c
                  const av_scene_row* scene, const int32_t* det_n, const int32_t* det_cls, int max_det, const uint8_t* elem_table,
                  int n_elem, uint64_t* out_mask, double* out_speed);
 /* The log: log_mask u64 [S][cap], log_speed f64 [S][cap], log_n int32 [S], dropped int32 [S], the caller's, zeroed to start with.
- * av_taglog_append copies mask / speed [S][W] behind log_n[s] and advances log_n on the device (no host synchronisation: it can
+ * An append copies mask / speed [S][W] behind log_n[s] and advances log_n on the device (no host synchronisation: it can
  * sit in a step).  A frame that does not fit is not written and counted in dropped[s]; log_n never exceeds cap. */
+/* av_taglog_append_ex (below) with cols = log_cols = NULL. */
 int av_taglog_append(av_ctx* ctx, av_stream_t stream, int n_streams, int n_frames, const uint64_t* mask, const double* speed,
                      int cap, uint64_t* log_mask, double* log_speed, int32_t* log_n, int32_t* dropped);
 /* Queries cut a stream's log into chunks of AV_TAGLOG_CHUNK frames, one wave each, and hand what a chunk needs of the chunks before
@@ -1043,14 +1044,16 @@ int av_taglog_append(av_ctx* ctx, av_stream_t stream, int n_streams, int n_frame
  * the range is clamped to [0, log_n[s]) (first = 0, last = cap: the whole log). */
 #define AV_TAGLOG_CHUNK 1024
 size_t av_taglog_workspace_bytes(int n_streams, int cap);
-/*   out_idx int32 [S][out_cap] the matching frame indices, increasing; out_n [S] the number of matches, which may exceed out_cap;
- *   rows at or past min(out_n, out_cap) are not written */
+/* A search leaves out_idx int32 [S][out_cap], the matching frame indices, increasing, and out_n [S], the number of matches, which
+ * may exceed out_cap; rows at or past min(out_n, out_cap) are not written. */
+/* av_taglog_search_where (below) with the three masks, no numeric bound and log_speed = log_cols = NULL. */
 int av_taglog_search(av_ctx* ctx, av_stream_t stream, int n_streams, int cap, const uint64_t* log_mask, const int32_t* log_n,
                      uint64_t all, uint64_t any, uint64_t none, int first, int last, void* workspace, int out_cap,
                      int32_t* out_idx, int32_t* out_n);
 /* get_event_segments (auto_tagger.py:281-310): the maximal runs of matching frames with last - first + 1 >= min_duration, in
  * order, as out_seg int32 [S][seg_cap][2] (first, last); a run that reaches the end of the range is closed there.  out_n [S] is
  * the number of such runs, which may exceed seg_cap; rows at or past min(out_n, seg_cap) are not written. */
+/* av_taglog_segments_where (below) with the three masks, no numeric bound and log_speed = log_cols = NULL. */
 int av_taglog_segments(av_ctx* ctx, av_stream_t stream, int n_streams, int cap, const uint64_t* log_mask, const int32_t* log_n,
                        uint64_t all, uint64_t any, uint64_t none, int first, int last, int min_duration, void* workspace,
                        int seg_cap, int32_t* out_seg, int32_t* out_n);
@@ -1079,8 +1082,8 @@ typedef struct av_taglog_cols {
  *   out_cols  av_taglog_cols [S][W] */
 int av_tags_cols(av_ctx* ctx, av_stream_t stream, int n_streams, int n_frames, const av_maneuver_row* maneuver,
                  const av_interaction_summary* inter_summary, const av_scene_row* scene, av_taglog_cols* out_cols);
-/* av_taglog_append with the records moved in the same launch to the same positions.  cols [S][W] and log_cols [S][cap] are both
- * NULL (then it leaves exactly what av_taglog_append leaves) or both given. */
+/* The append, with the records moved in the same launch to the same positions.  cols [S][W] and log_cols [S][cap] are both NULL
+ * (a log without records) or both given. */
 int av_taglog_append_ex(av_ctx* ctx, av_stream_t stream, int n_streams, int n_frames, const uint64_t* mask, const double* speed,
                         const av_taglog_cols* cols, int cap, uint64_t* log_mask, double* log_speed, av_taglog_cols* log_cols,
                         int32_t* log_n, int32_t* dropped);

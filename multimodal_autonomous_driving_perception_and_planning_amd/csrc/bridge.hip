@@ -10,7 +10,8 @@
 // frame and the maneuver tagger a lateral offset in metres (get_lane_center_offset, lane_detector.py:253-272).  av_lane_paths
 // samples the centre line between the two fits at the reference's own rows (lane_detector.py:164: from the bottom of the frame up
 // to 0.6 h) and places every sample the way av_track_obstacles places a track's centre, with the same av_obstacle_cfg scales, so
-// tracks and lanes land in one road plane.
+// tracks and lanes land in one road plane.  av_lane_paths_ground is the same kernel body with the samples sent through a camera's
+// ground-plane homography instead (lane_paths_kernel<VIA>, as obstacles.hip chooses its placement).
 //
 // Mapping (both, as obstacles.hip): one wave per frame / stream, lane = list entry, rounds of 64; kept entries are compacted in
 // list order by ballot + prefix count.  float64 in the operation order include/avhot.h states (-ffp-contract=off: no FMA).
@@ -18,6 +19,7 @@
 #include "ground_dev.h"
 
 #include <cmath>
+#include <type_traits>
 
 namespace {
 
@@ -77,57 +79,16 @@ __global__ void __launch_bounds__(256) dets_to_tracker_kernel(int n_frames, int 
     }
 }
 
-__global__ void __launch_bounds__(256) lane_paths_kernel(av_obstacle_cfg cfg, int n_streams, int h, int w, int n_points,
+// One wave per stream, lane = sample.  VIA says how a sample (xc, y) of the centre line becomes (lateral, forward) metres:
+// av_obstacle_cfg, the linear scales of av_track_obstacles; or const av_ground_cfg*, the ground-plane homography of the stream's
+// camera, where the path is cut at the first sample that leaves the road (horizon, range).
+template <typename VIA>
+__global__ void __launch_bounds__(256) lane_paths_kernel(VIA via, int n_streams, int h, int w, int n_points,
                                                          const double* __restrict__ poly, const int32_t* __restrict__ pts,
                                                          const int32_t* __restrict__ info, const double* __restrict__ plan_state,
                                                          int ref_stride, int rcap, double* __restrict__ ref_path,
                                                          int32_t* __restrict__ n_ref, double* __restrict__ lane_offset) {
-    const int lane = threadIdx.x & 63;
-    const long long sl = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (sl >= n_streams) return;
-    const size_t s = (size_t)sl;
-    const bool valid = info[s * 8] != 0 && info[s * 8 + 1] != 0;
-    if (!valid) {
-        if (lane == 0) {
-            n_ref[s] = 0;
-            if (lane_offset) lane_offset[s] = __longlong_as_double(0x7ff8000000000000ll);
-        }
-        return;
-    }
-    if (lane == 0) {
-        n_ref[s] = n_points;
-        if (lane_offset) {
-            const int32_t* p = pts + s * 200;                       // [2][50][2]: x of point 49 of either side
-            const long long sum = (long long)p[49 * 2] + (long long)p[100 + 49 * 2];
-            lane_offset[s] = ((double)w / 2.0 - (double)sum / 2.0) * cfg.x_scale;
-        }
-    }
-    if (lane >= n_points) return;
-    const double* st = plan_state + s * (size_t)ref_stride * 4;     // the first frame of the stream's window
-    const double x0 = st[0], y0 = st[1], hd = st[2];
-    double sn, cs, s2, c2;
-    sincos(hd, &sn, &cs);
-    sincos(hd + 1.5707963267948966, &s2, &c2);                      // heading + np.pi/2  (motion_planner.py:179)
-    const double* pl = poly + s * 6;
-    const double step = (0.4 * (double)h) / (double)(n_points - 1);
-    const double y = (double)h - (double)lane * step;
-    const double xl = (pl[0] * y + pl[1]) * y + pl[2];
-    const double xr = (pl[3] * y + pl[4]) * y + pl[5];
-    const double xc = (xl + xr) / 2.0;
-    const double l = (xc - cfg.x_center) * cfg.x_scale, fw = cfg.y_far - y * cfg.y_scale;
-    double* o = ref_path + (s * (size_t)rcap + lane) * 2;           // lane < n_points <= rcap
-    o[0] = (x0 + fw * cs) + l * c2;
-    o[1] = (y0 + fw * sn) + l * s2;
-}
-
-// av_lane_paths through a camera: rows and centre abscissa as above, every sample through the ground-plane homography of its
-// stream, the path cut where the first sample leaves the road (horizon, range).  One wave per stream, lane = sample.
-__global__ void __launch_bounds__(256) lane_paths_ground_kernel(const av_ground_cfg* __restrict__ ground, int n_streams, int h, int w,
-                                                                int n_points, const double* __restrict__ poly,
-                                                                const int32_t* __restrict__ pts, const int32_t* __restrict__ info,
-                                                                const double* __restrict__ plan_state, int ref_stride, int rcap,
-                                                                double* __restrict__ ref_path, int32_t* __restrict__ n_ref,
-                                                                double* __restrict__ lane_offset) {
+    constexpr bool GROUND = std::is_same<VIA, const av_ground_cfg*>::value;
     const int lane = threadIdx.x & 63;
     const long long sl = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (sl >= n_streams) return;
@@ -141,13 +102,16 @@ __global__ void __launch_bounds__(256) lane_paths_ground_kernel(const av_ground_
         }
         return;
     }
-    const av_ground_cfg* cam = ground + s;
     if (lane == 0 && lane_offset) {
         const int32_t* p = pts + s * 200;                           // [2][50][2]: x of point 49 of either side
         const long long sum = (long long)p[49 * 2] + (long long)p[100 + 49 * 2];
-        const grounddev::RoadPoint a = grounddev::project(cam->g, cam->max_range, (double)w / 2.0, (double)h);
-        const grounddev::RoadPoint b = grounddev::project(cam->g, cam->max_range, (double)sum / 2.0, (double)h);
-        lane_offset[s] = (a.on_road && b.on_road) ? a.l - b.l : nan;
+        if constexpr (GROUND) {
+            const grounddev::RoadPoint a = grounddev::project(via[s].g, via[s].max_range, (double)w / 2.0, (double)h);
+            const grounddev::RoadPoint b = grounddev::project(via[s].g, via[s].max_range, (double)sum / 2.0, (double)h);
+            lane_offset[s] = (a.on_road && b.on_road) ? a.l - b.l : nan;
+        } else {
+            lane_offset[s] = ((double)w / 2.0 - (double)sum / 2.0) * via.x_scale;
+        }
     }
     const double* pl = poly + s * 6;
     const double step = (0.4 * (double)h) / (double)(n_points - 1);
@@ -155,11 +119,18 @@ __global__ void __launch_bounds__(256) lane_paths_ground_kernel(const av_ground_
     const double xl = (pl[0] * y + pl[1]) * y + pl[2];
     const double xr = (pl[3] * y + pl[4]) * y + pl[5];
     const double xc = (xl + xr) / 2.0;
-    const grounddev::RoadPoint q = grounddev::project(cam->g, cam->max_range, xc, y);
-    // the longest prefix of samples that are all on the road: the lanes below the first that is not
-    const unsigned long long bad = __ballot(lane < n_points && !q.on_road);
-    int m = bad ? __ffsll((long long)bad) - 1 : n_points;
-    m = m >= 2 ? m : 0;
+    double l, fw;
+    int m = n_points;
+    if constexpr (GROUND) {
+        const grounddev::RoadPoint q = grounddev::project(via[s].g, via[s].max_range, xc, y);
+        // the longest prefix of samples that are all on the road: the lanes below the first that is not (every lane votes)
+        const unsigned long long bad = __ballot(lane < n_points && !q.on_road);
+        m = bad ? __ffsll((long long)bad) - 1 : n_points;
+        m = m >= 2 ? m : 0;
+        l = q.l, fw = q.f;
+    } else {
+        l = (xc - via.x_center) * via.x_scale, fw = via.y_far - y * via.y_scale;
+    }
     if (lane == 0) n_ref[s] = m;
     if (lane >= m) return;
     const double* st = plan_state + s * (size_t)ref_stride * 4;     // the first frame of the stream's window
@@ -168,8 +139,27 @@ __global__ void __launch_bounds__(256) lane_paths_ground_kernel(const av_ground_
     sincos(hd, &sn, &cs);
     sincos(hd + 1.5707963267948966, &s2, &c2);                      // heading + np.pi/2  (motion_planner.py:179)
     double* o = ref_path + (s * (size_t)rcap + lane) * 2;           // lane < m <= n_points <= rcap
-    o[0] = (x0 + q.f * cs) + q.l * c2;
-    o[1] = (y0 + q.f * sn) + q.l * s2;
+    o[0] = (x0 + fw * cs) + l * c2;
+    o[1] = (y0 + fw * sn) + l * s2;
+}
+
+// `given` is the caller's pointer: the scales are host memory and go to the kernel by value, the ground table is on the device
+inline av_obstacle_cfg kernel_arg(const av_obstacle_cfg* cfg) { return *cfg; }
+inline const av_ground_cfg* kernel_arg(const av_ground_cfg* ground) { return ground; }
+
+template <typename GIVEN>
+int lane_paths_launch(const char* who, av_ctx* ctx, av_stream_t stream, const GIVEN* given, int n_streams, int h, int w, int n_points,
+                      const double* poly, const int32_t* pts, const int32_t* info, const double* plan_state, int ref_stride, int rcap,
+                      double* ref_path, int32_t* n_ref, double* lane_offset) {
+    AV_REQUIRE(ctx && given && poly && pts && info && plan_state && ref_path && n_ref, AV_EINVAL, "%s: null argument", who);
+    AV_REQUIRE(n_streams > 0 && h > 0 && w > 0 && ref_stride > 0, AV_EINVAL, "%s: n_streams, h, w and ref_stride must be > 0", who);
+    AV_REQUIRE(n_points >= 2 && n_points <= 64 && n_points <= rcap, AV_EINVAL,
+               "%s: n_points %d not in [2, min(64, rcap %d)] (one wave per stream)", who, n_points, rcap);
+    using VIA = decltype(kernel_arg(given));
+    hipLaunchKernelGGL(lane_paths_kernel<VIA>, dim3((n_streams + 3) / 4), dim3(256), 0, as_stream(stream), kernel_arg(given), n_streams,
+                       h, w, n_points, poly, pts, info, plan_state, ref_stride, rcap, ref_path, n_ref, lane_offset);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
 }
 
 }  // namespace
@@ -191,28 +181,13 @@ extern "C" int av_dets_to_tracker(av_ctx* ctx, av_stream_t stream, int n_frames,
 extern "C" int av_lane_paths(av_ctx* ctx, av_stream_t stream, const av_obstacle_cfg* cfg, int n_streams, int h, int w, int n_points,
                              const double* poly, const int32_t* pts, const int32_t* info, const double* plan_state, int ref_stride,
                              int rcap, double* ref_path, int32_t* n_ref, double* lane_offset) {
-    AV_REQUIRE(ctx && cfg && poly && pts && info && plan_state && ref_path && n_ref, AV_EINVAL, "av_lane_paths: null argument");
-    AV_REQUIRE(n_streams > 0 && h > 0 && w > 0 && ref_stride > 0, AV_EINVAL,
-               "av_lane_paths: n_streams, h, w and ref_stride must be > 0");
-    AV_REQUIRE(n_points >= 2 && n_points <= 64 && n_points <= rcap, AV_EINVAL,
-               "av_lane_paths: n_points %d not in [2, min(64, rcap %d)] (one wave per stream)", n_points, rcap);
-    hipLaunchKernelGGL(lane_paths_kernel, dim3((n_streams + 3) / 4), dim3(256), 0, as_stream(stream), *cfg, n_streams, h, w, n_points,
-                       poly, pts, info, plan_state, ref_stride, rcap, ref_path, n_ref, lane_offset);
-    AV_LAUNCH_CHECK();
-    return AV_OK;
+    return lane_paths_launch("av_lane_paths", ctx, stream, cfg, n_streams, h, w, n_points, poly, pts, info, plan_state, ref_stride, rcap,
+                             ref_path, n_ref, lane_offset);
 }
 
 extern "C" int av_lane_paths_ground(av_ctx* ctx, av_stream_t stream, const av_ground_cfg* ground, int n_streams, int h, int w,
                                     int n_points, const double* poly, const int32_t* pts, const int32_t* info, const double* plan_state,
                                     int ref_stride, int rcap, double* ref_path, int32_t* n_ref, double* lane_offset) {
-    AV_REQUIRE(ctx && ground && poly && pts && info && plan_state && ref_path && n_ref, AV_EINVAL,
-               "av_lane_paths_ground: null argument");
-    AV_REQUIRE(n_streams > 0 && h > 0 && w > 0 && ref_stride > 0, AV_EINVAL,
-               "av_lane_paths_ground: n_streams, h, w and ref_stride must be > 0");
-    AV_REQUIRE(n_points >= 2 && n_points <= 64 && n_points <= rcap, AV_EINVAL,
-               "av_lane_paths_ground: n_points %d not in [2, min(64, rcap %d)] (one wave per stream)", n_points, rcap);
-    hipLaunchKernelGGL(lane_paths_ground_kernel, dim3((n_streams + 3) / 4), dim3(256), 0, as_stream(stream), ground, n_streams, h, w,
-                       n_points, poly, pts, info, plan_state, ref_stride, rcap, ref_path, n_ref, lane_offset);
-    AV_LAUNCH_CHECK();
-    return AV_OK;
+    return lane_paths_launch("av_lane_paths_ground", ctx, stream, ground, n_streams, h, w, n_points, poly, pts, info, plan_state,
+                             ref_stride, rcap, ref_path, n_ref, lane_offset);
 }

@@ -25,10 +25,14 @@
 //
 // Records.  A log may carry a third array, av_taglog_cols [S][cap] (80 B, array of structs): the numbers of the taggers' rows that a
 // mask cannot hold.  av_tags_cols builds them (one lane per 8-byte word of a record, so the stores are contiguous; copies only),
-// av_taglog_append_ex moves them with the masks (a stream's window of records is one contiguous run of words), the *_where queries
-// replace pass 1 by a match over masks, speeds and records -- a bounded field costs one 8-byte load out of the frame's 80 B record,
-// under a wave-uniform branch, so an unbounded query still reads 8 B per frame -- and av_taglog_gather turns a search's indices
-// into records (one lane per output word).
+// the append kernel moves them with the masks (a stream's window of records is one contiguous run of words), the match pass bounds
+// them -- a bounded field costs one 8-byte load out of the frame's 80 B record, under a wave-uniform branch -- and
+// av_taglog_gather turns a search's indices into records (one lane per output word).
+//
+// One kernel body per operation.  taglog_append_kernel<COLS> and taglog_match_kernel<BOUNDS> are each compiled twice: the <false>
+// instance never forms a pointer into the speeds or records (40 VGPRs, 8 waves / SIMD for the match; 62 and 7 with the bounds,
+// DESIGN 7k), and the host picks it when the query sets no numeric bound / the log has no records.  av_taglog_append, _search and
+// _segments are av_taglog_append_ex, _search_where and _segments_where with the records and bounds absent.
 #include "common.h"
 
 #include <cmath>
@@ -160,26 +164,6 @@ __global__ void __launch_bounds__(256) tags_pack_kernel(int n_frames, const av_m
     }
 }
 
-// ---- append ----------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) taglog_append_kernel(int n_frames, const unsigned long long* __restrict__ mask,
-                                                            const double* __restrict__ speed, int cap,
-                                                            unsigned long long* __restrict__ log_mask, double* __restrict__ log_speed,
-                                                            int32_t* __restrict__ log_n, int32_t* __restrict__ dropped) {
-    const size_t s = blockIdx.x;
-    int n0 = log_n[s];
-    n0 = n0 < 0 ? 0 : (n0 > cap ? cap : n0);
-    __syncthreads();                            // every thread has read log_n[s] before thread 0 advances it
-    const int fit = n_frames < cap - n0 ? n_frames : cap - n0;
-    for (int w = threadIdx.x; w < fit; w += blockDim.x) {                          // n0 + w < n0 + fit <= cap
-        log_mask[s * (size_t)cap + n0 + w] = mask[s * (size_t)n_frames + w];
-        log_speed[s * (size_t)cap + n0 + w] = speed[s * (size_t)n_frames + w];
-    }
-    if (threadIdx.x == 0) {
-        log_n[s] = n0 + fit;
-        dropped[s] += n_frames - fit;
-    }
-}
-
 // ---- records ---------------------------------------------------------------------------------------------------------------
 constexpr int COLS_WORDS = 10;              // av_taglog_cols in 8-byte words
 static_assert(sizeof(av_taglog_cols) == COLS_WORDS * 8, "av_taglog_cols layout");
@@ -219,13 +203,15 @@ __global__ void __launch_bounds__(256) tags_cols_kernel(long long n_words, const
     out[t] = v;
 }
 
-// av_taglog_append's kernel with the records: a stream's `fit` records are fit * 10 consecutive words on both sides.
-__global__ void __launch_bounds__(256) taglog_append_ex_kernel(int n_frames, const unsigned long long* __restrict__ mask,
-                                                               const double* __restrict__ speed,
-                                                               const unsigned long long* __restrict__ cols, int cap,
-                                                               unsigned long long* __restrict__ log_mask,
-                                                               double* __restrict__ log_speed, unsigned long long* __restrict__ log_cols,
-                                                               int32_t* __restrict__ log_n, int32_t* __restrict__ dropped) {
+// ---- append ----------------------------------------------------------------------------------------------------------------
+// COLS: with the records; a stream's `fit` records are fit * 10 consecutive words on both sides.
+template <bool COLS>
+__global__ void __launch_bounds__(256) taglog_append_kernel(int n_frames, const unsigned long long* __restrict__ mask,
+                                                            const double* __restrict__ speed, int cap,
+                                                            unsigned long long* __restrict__ log_mask, double* __restrict__ log_speed,
+                                                            int32_t* __restrict__ log_n, int32_t* __restrict__ dropped,
+                                                            const unsigned long long* __restrict__ cols,
+                                                            unsigned long long* __restrict__ log_cols) {
     const size_t s = blockIdx.x;
     int n0 = log_n[s];
     n0 = n0 < 0 ? 0 : (n0 > cap ? cap : n0);
@@ -235,7 +221,7 @@ __global__ void __launch_bounds__(256) taglog_append_ex_kernel(int n_frames, con
         log_mask[s * (size_t)cap + n0 + w] = mask[s * (size_t)n_frames + w];
         log_speed[s * (size_t)cap + n0 + w] = speed[s * (size_t)n_frames + w];
     }
-    if (cols) {
+    if constexpr (COLS) {
         const unsigned long long* src = cols + s * (size_t)n_frames * COLS_WORDS;
         unsigned long long* dst = log_cols + (s * (size_t)cap + (size_t)n0) * COLS_WORDS;
         const long long words = (long long)fit * COLS_WORDS;                       // (n0 + fit) * 10 <= cap * 10 words of the row
@@ -291,44 +277,11 @@ __device__ __forceinline__ ChunkId my_chunk(int cap) {
     return k;
 }
 
-__global__ void __launch_bounds__(256) taglog_match_kernel(int cap, const unsigned long long* __restrict__ log_mask,
-                                                           const int32_t* __restrict__ log_n, Predicate p, int first, int last,
-                                                           Workspace ws) {
-    const ChunkId k = my_chunk(cap);
-    if (!k.live) return;
-    int n = log_n[k.s];
-    n = n < 0 ? 0 : (n > cap ? cap : n);
-    const int lo = first < 0 ? 0 : first, hi = last < n ? last : n;
-    const int base = k.c * CHUNK;
-    const unsigned long long* row = log_mask + k.s * (size_t)cap;
-    unsigned long long mine = 0;                // lane r keeps round r's ballot
-    int count = 0, lastoff = -1;
-    if (base < hi && base + CHUNK > lo) {       // otherwise nothing of this chunk is in range: all bits off, no load
-        unsigned long long m[ROUNDS];
-#pragma unroll
-        for (int r = 0; r < ROUNDS; ++r) {
-            const int i = base + r * 64 + k.lane;
-            m[r] = (i >= lo && i < hi) ? row[i] : 0ull;                            // i < hi <= n <= cap
-        }
-#pragma unroll
-        for (int r = 0; r < ROUNDS; ++r) {
-            const int i = base + r * 64 + k.lane;
-            const unsigned long long on = __ballot(i >= lo && i < hi && matches(m[r], p));
-            if (k.lane == r) mine = on;
-            count += __popcll(on);
-            if (~on != 0ull) lastoff = base + r * 64 + 63 - __clzll(~on);
-        }
-    } else {
-        lastoff = base + CHUNK - 1;
-    }
-    if (k.lane < ROUNDS) ws.bits[k.sc * ROUNDS + k.lane] = mine;
-    if (k.lane == 0) ws.cnt[k.sc] = count, ws.lastoff[k.sc] = lastoff;
-}
-
-// Pass 1 of the *_where queries: taglog_match_kernel's bits / cnt / lastoff from masks, speeds and records.  Which arrays are read is
-// decided by the bounds that are set -- kernel arguments, so every such branch is wave-uniform.
+// Pass 1 of search and segments: a chunk's bits / cnt / lastoff from the masks and, BOUNDS, from speeds and records.  Which arrays
+// are read is decided by the bounds that are set -- kernel arguments, so every such branch is wave-uniform.
 struct WhereUse {
     bool speed, accel, ttc, dist, agent_ped, cyc_veh;
+    __host__ __device__ bool any() const { return speed || accel || ttc || dist || agent_ped || cyc_veh; }
 };
 __host__ __device__ inline bool is_set(double bound) { return bound == bound; }
 __host__ __device__ inline WhereUse where_use(const av_taglog_where& q) {
@@ -346,11 +299,12 @@ __device__ __forceinline__ bool at_least(double v, double bound) { return !is_se
 __device__ __forceinline__ bool at_most(double v, double bound) { return !is_set(bound) || v <= bound; }
 __device__ __forceinline__ bool count_at_least(int v, int bound) { return bound <= 0 || v >= bound; }
 
-__global__ void __launch_bounds__(256) taglog_match_where_kernel(int cap, const unsigned long long* __restrict__ log_mask,
-                                                                 const double* __restrict__ log_speed,
-                                                                 const unsigned long long* __restrict__ log_cols,
-                                                                 const int32_t* __restrict__ log_n, av_taglog_where q, int first,
-                                                                 int last, Workspace ws) {
+template <bool BOUNDS>
+__global__ void __launch_bounds__(256) taglog_match_kernel(int cap, const unsigned long long* __restrict__ log_mask,
+                                                           const double* __restrict__ log_speed,
+                                                           const unsigned long long* __restrict__ log_cols,
+                                                           const int32_t* __restrict__ log_n, av_taglog_where q, int first, int last,
+                                                           Workspace ws) {
     const ChunkId k = my_chunk(cap);
     if (!k.live) return;
     int n = log_n[k.s];
@@ -360,12 +314,13 @@ __global__ void __launch_bounds__(256) taglog_match_where_kernel(int cap, const 
     const Predicate p{q.all, q.any, q.none};
     const WhereUse use = where_use(q);
     const unsigned long long* row = log_mask + k.s * (size_t)cap;
-    const double* vrow = log_speed + k.s * (size_t)cap;
-    const unsigned long long* crow = log_cols + k.s * (size_t)cap * COLS_WORDS;
+    // <false> forms neither pointer and reads no bound (DESIGN 7k on why they stand here and not inside the `if constexpr`)
+    const double* vrow = BOUNDS ? log_speed + k.s * (size_t)cap : nullptr;
+    const unsigned long long* crow = BOUNDS ? log_cols + k.s * (size_t)cap * COLS_WORDS : nullptr;
     unsigned long long mine = 0;                // lane r keeps round r's ballot
     int count = 0, lastoff = -1;
     if (base < hi && base + CHUNK > lo) {       // otherwise nothing of this chunk is in range: all bits off, no load
-        unsigned long long m[ROUNDS];           // the masks first, as taglog_match_kernel reads them: 16 loads in flight
+        unsigned long long m[ROUNDS];           // the masks first: 16 loads in flight
 #pragma unroll
         for (int r = 0; r < ROUNDS; ++r) {
             const int i = base + r * 64 + k.lane;
@@ -376,24 +331,26 @@ __global__ void __launch_bounds__(256) taglog_match_where_kernel(int cap, const 
             const int i = base + r * 64 + k.lane;
             const bool in = i >= lo && i < hi;                                     // every load below: i < hi <= n <= cap
             bool ok = in && matches(m[r], p);
-            const unsigned long long* rec = crow + (size_t)(in ? i : 0) * COLS_WORDS;      // read under `in` only
-            if (use.speed) {
-                const double v = in ? vrow[i] : 0.0;
-                ok = ok && at_least(v, q.speed_min) && at_most(v, q.speed_max);
-            }
-            if (use.accel) {
-                const double v = __longlong_as_double((long long)(in ? rec[W_ACCEL] : 0ull));
-                ok = ok && at_least(v, q.accel_min) && at_most(v, q.accel_max);
-            }
-            if (use.ttc) ok = ok && at_most(__longlong_as_double((long long)(in ? rec[W_TTC] : 0ull)), q.ttc_max);
-            if (use.dist) ok = ok && at_most(__longlong_as_double((long long)(in ? rec[W_DIST] : 0ull)), q.distance_max);
-            if (use.agent_ped) {
-                const unsigned long long v = in ? rec[W_AGENT_PED] : 0ull;
-                ok = ok && count_at_least((int)(unsigned)v, q.agents_min) && count_at_least((int)(unsigned)(v >> 32), q.pedestrians_min);
-            }
-            if (use.cyc_veh) {
-                const unsigned long long v = in ? rec[W_CYC_VEH] : 0ull;
-                ok = ok && count_at_least((int)(unsigned)v, q.cyclists_min) && count_at_least((int)(unsigned)(v >> 32), q.vehicles_min);
+            if constexpr (BOUNDS) {
+                const unsigned long long* rec = crow + (size_t)(in ? i : 0) * COLS_WORDS;      // read under `in` only
+                if (use.speed) {
+                    const double v = in ? vrow[i] : 0.0;
+                    ok = ok && at_least(v, q.speed_min) && at_most(v, q.speed_max);
+                }
+                if (use.accel) {
+                    const double v = __longlong_as_double((long long)(in ? rec[W_ACCEL] : 0ull));
+                    ok = ok && at_least(v, q.accel_min) && at_most(v, q.accel_max);
+                }
+                if (use.ttc) ok = ok && at_most(__longlong_as_double((long long)(in ? rec[W_TTC] : 0ull)), q.ttc_max);
+                if (use.dist) ok = ok && at_most(__longlong_as_double((long long)(in ? rec[W_DIST] : 0ull)), q.distance_max);
+                if (use.agent_ped) {
+                    const unsigned long long v = in ? rec[W_AGENT_PED] : 0ull;
+                    ok = ok && count_at_least((int)(unsigned)v, q.agents_min) && count_at_least((int)(unsigned)(v >> 32), q.pedestrians_min);
+                }
+                if (use.cyc_veh) {
+                    const unsigned long long v = in ? rec[W_CYC_VEH] : 0ull;
+                    ok = ok && count_at_least((int)(unsigned)v, q.cyclists_min) && count_at_least((int)(unsigned)(v >> 32), q.vehicles_min);
+                }
             }
             const unsigned long long on = __ballot(ok);
             if (k.lane == r) mine = on;
@@ -568,6 +525,83 @@ __global__ void __launch_bounds__(FOLD_WAVES * 64) taglog_stats_fold_kernel(int 
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
 inline dim3 chunk_grid(int n_streams, int cap) { return dim3((unsigned)((n_chunks_of(cap) + 3) / 4), (unsigned)n_streams); }
+inline const unsigned long long* words(const void* p) { return reinterpret_cast<const unsigned long long*>(p); }
+inline unsigned long long* words(void* p) { return reinterpret_cast<unsigned long long*>(p); }
+
+// what a log's arrays and a query over them are, as the entry points receive them
+struct Query {
+    const char* who;                            // the entry that was called, for its error texts
+    av_ctx* ctx;
+    av_stream_t stream;
+    int n_streams, cap;
+    const uint64_t* log_mask;
+    const double* log_speed;
+    const av_taglog_cols* log_cols;
+    const int32_t* log_n;
+    const av_taglog_where* where;
+    int first, last;
+    void* workspace;
+};
+// the mask-only entries' predicate: no numeric bound set
+inline av_taglog_where masks_only(uint64_t all, uint64_t any, uint64_t none) {
+    const double unset = __builtin_nan("");
+    return av_taglog_where{all, any, none, unset, unset, unset, unset, unset, unset, 0, 0, 0, 0};
+}
+
+// Pass 1 of every query, behind the checks all of them share; 0 or the error code.  out / out_cap / out_n: the query's output.
+int launch_match(const Query& q, int out_cap, const void* out, const int32_t* out_n) {
+    AV_REQUIRE(q.ctx && q.log_mask && q.log_n && q.where && q.workspace && out_n && (out || out_cap == 0), AV_EINVAL,
+               "%s: null argument", q.who);
+    AV_REQUIRE(q.n_streams > 0 && q.cap > 0, AV_EINVAL, "%s: n_streams and cap must be > 0", q.who);
+    AV_REQUIRE(out_cap >= 0, AV_EINVAL, "%s: the output capacity %d is negative", q.who, out_cap);
+    const WhereUse use = where_use(*q.where);
+    AV_REQUIRE(q.log_speed || !use.speed, AV_EINVAL, "%s: a speed bound without log_speed", q.who);
+    AV_REQUIRE(q.log_cols || !(use.accel || use.ttc || use.dist || use.agent_ped || use.cyc_veh), AV_EINVAL,
+               "%s: a bound on a record's field without log_cols", q.who);
+    const auto kernel = use.any() ? taglog_match_kernel<true> : taglog_match_kernel<false>;
+    hipLaunchKernelGGL(kernel, chunk_grid(q.n_streams, q.cap), dim3(256), 0, as_stream(q.stream), q.cap, words(q.log_mask), q.log_speed,
+                       words(q.log_cols), q.log_n, *q.where, q.first, q.last, carve(q.workspace, q.n_streams, q.cap));
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
+// match, then the ordered write
+int run_search(const Query& q, int out_cap, int32_t* out_idx, int32_t* out_n) {
+    const int rc = launch_match(q, out_cap, out_idx, out_n);
+    if (rc != AV_OK) return rc;
+    hipLaunchKernelGGL(taglog_search_write_kernel, chunk_grid(q.n_streams, q.cap), dim3(256), 0, as_stream(q.stream), q.cap,
+                       carve(q.workspace, q.n_streams, q.cap), out_cap, out_idx, out_n);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
+// match, count the kept runs per chunk, write them
+int run_segments(const Query& q, int min_duration, int seg_cap, int32_t* out_seg, int32_t* out_n) {
+    const int rc = launch_match(q, seg_cap, out_seg, out_n);
+    if (rc != AV_OK) return rc;
+    const Workspace ws = carve(q.workspace, q.n_streams, q.cap);
+    const dim3 grid = chunk_grid(q.n_streams, q.cap);
+    hipLaunchKernelGGL(taglog_segments_kernel<false>, grid, dim3(256), 0, as_stream(q.stream), q.cap, ws, min_duration, seg_cap, out_seg,
+                       out_n);
+    AV_LAUNCH_CHECK();
+    hipLaunchKernelGGL(taglog_segments_kernel<true>, grid, dim3(256), 0, as_stream(q.stream), q.cap, ws, min_duration, seg_cap, out_seg,
+                       out_n);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
+int run_append(const char* who, av_ctx* ctx, av_stream_t stream, int n_streams, int n_frames, const uint64_t* mask, const double* speed,
+               const av_taglog_cols* cols, int cap, uint64_t* log_mask, double* log_speed, av_taglog_cols* log_cols, int32_t* log_n,
+               int32_t* dropped) {
+    AV_REQUIRE(ctx && mask && speed && log_mask && log_speed && log_n && dropped, AV_EINVAL, "%s: null argument", who);
+    AV_REQUIRE((cols == nullptr) == (log_cols == nullptr), AV_EINVAL, "%s: cols and log_cols are given together or not at all", who);
+    AV_REQUIRE(n_streams > 0 && n_frames > 0 && cap > 0, AV_EINVAL, "%s: n_streams, n_frames and cap must be > 0", who);
+    const auto kernel = cols ? taglog_append_kernel<true> : taglog_append_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)n_streams), dim3(256), 0, as_stream(stream), n_frames, words(mask), speed, cap, words(log_mask),
+                       log_speed, log_n, dropped, words(cols), words(log_cols));
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
 
 }  // namespace
 
@@ -596,7 +630,7 @@ extern "C" int av_tags_pack(av_ctx* ctx, av_stream_t stream, int n_streams, int 
     AV_REQUIRE(frames <= 0x7fffffffll, AV_EINVAL, "av_tags_pack: n_streams * n_frames does not fit an int");
     hipLaunchKernelGGL(tags_pack_kernel, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, as_stream(stream), (int)frames, maneuver,
                        inter_rows, inter_summary, snap_n, tcap, scene, det_n, det_cls, max_det, elem_table, n_elem,
-                       reinterpret_cast<unsigned long long*>(out_mask), out_speed);
+                       words(out_mask), out_speed);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }
@@ -604,53 +638,47 @@ extern "C" int av_tags_pack(av_ctx* ctx, av_stream_t stream, int n_streams, int 
 extern "C" int av_taglog_append(av_ctx* ctx, av_stream_t stream, int n_streams, int n_frames, const uint64_t* mask,
                                 const double* speed, int cap, uint64_t* log_mask, double* log_speed, int32_t* log_n,
                                 int32_t* dropped) {
-    AV_REQUIRE(ctx && mask && speed && log_mask && log_speed && log_n && dropped, AV_EINVAL, "av_taglog_append: null argument");
-    AV_REQUIRE(n_streams > 0 && n_frames > 0 && cap > 0, AV_EINVAL, "av_taglog_append: n_streams, n_frames and cap must be > 0");
-    hipLaunchKernelGGL(taglog_append_kernel, dim3((unsigned)n_streams), dim3(256), 0, as_stream(stream), n_frames,
-                       reinterpret_cast<const unsigned long long*>(mask), speed, cap, reinterpret_cast<unsigned long long*>(log_mask),
-                       log_speed, log_n, dropped);
-    AV_LAUNCH_CHECK();
-    return AV_OK;
+    return run_append("av_taglog_append", ctx, stream, n_streams, n_frames, mask, speed, nullptr, cap, log_mask, log_speed, nullptr, log_n,
+                      dropped);
+}
+
+extern "C" int av_taglog_append_ex(av_ctx* ctx, av_stream_t stream, int n_streams, int n_frames, const uint64_t* mask,
+                                   const double* speed, const av_taglog_cols* cols, int cap, uint64_t* log_mask, double* log_speed,
+                                   av_taglog_cols* log_cols, int32_t* log_n, int32_t* dropped) {
+    return run_append("av_taglog_append_ex", ctx, stream, n_streams, n_frames, mask, speed, cols, cap, log_mask, log_speed, log_cols,
+                      log_n, dropped);
 }
 
 extern "C" int av_taglog_search(av_ctx* ctx, av_stream_t stream, int n_streams, int cap, const uint64_t* log_mask,
                                 const int32_t* log_n, uint64_t all, uint64_t any, uint64_t none, int first, int last, void* workspace,
                                 int out_cap, int32_t* out_idx, int32_t* out_n) {
-    AV_REQUIRE(ctx && log_mask && log_n && workspace && out_n && (out_idx || out_cap == 0), AV_EINVAL,
-               "av_taglog_search: null argument");
-    AV_REQUIRE(n_streams > 0 && cap > 0, AV_EINVAL, "av_taglog_search: n_streams and cap must be > 0");
-    AV_REQUIRE(out_cap >= 0, AV_EINVAL, "av_taglog_search: out_cap %d is negative", out_cap);
-    const Workspace ws = carve(workspace, n_streams, cap);
-    const Predicate p{all, any, none};
-    hipLaunchKernelGGL(taglog_match_kernel, chunk_grid(n_streams, cap), dim3(256), 0, as_stream(stream), cap,
-                       reinterpret_cast<const unsigned long long*>(log_mask), log_n, p, first, last, ws);
-    AV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(taglog_search_write_kernel, chunk_grid(n_streams, cap), dim3(256), 0, as_stream(stream), cap, ws, out_cap,
-                       out_idx, out_n);
-    AV_LAUNCH_CHECK();
-    return AV_OK;
+    const av_taglog_where where = masks_only(all, any, none);
+    return run_search({"av_taglog_search", ctx, stream, n_streams, cap, log_mask, nullptr, nullptr, log_n, &where, first, last, workspace},
+                      out_cap, out_idx, out_n);
+}
+
+extern "C" int av_taglog_search_where(av_ctx* ctx, av_stream_t stream, int n_streams, int cap, const uint64_t* log_mask,
+                                      const double* log_speed, const av_taglog_cols* log_cols, const int32_t* log_n,
+                                      const av_taglog_where* where, int first, int last, void* workspace, int out_cap,
+                                      int32_t* out_idx, int32_t* out_n) {
+    return run_search({"av_taglog_search_where", ctx, stream, n_streams, cap, log_mask, log_speed, log_cols, log_n, where, first, last,
+                       workspace}, out_cap, out_idx, out_n);
 }
 
 extern "C" int av_taglog_segments(av_ctx* ctx, av_stream_t stream, int n_streams, int cap, const uint64_t* log_mask,
                                   const int32_t* log_n, uint64_t all, uint64_t any, uint64_t none, int first, int last,
                                   int min_duration, void* workspace, int seg_cap, int32_t* out_seg, int32_t* out_n) {
-    AV_REQUIRE(ctx && log_mask && log_n && workspace && out_n && (out_seg || seg_cap == 0), AV_EINVAL,
-               "av_taglog_segments: null argument");
-    AV_REQUIRE(n_streams > 0 && cap > 0, AV_EINVAL, "av_taglog_segments: n_streams and cap must be > 0");
-    AV_REQUIRE(seg_cap >= 0, AV_EINVAL, "av_taglog_segments: seg_cap %d is negative", seg_cap);
-    const Workspace ws = carve(workspace, n_streams, cap);
-    const Predicate p{all, any, none};
-    const dim3 grid = chunk_grid(n_streams, cap);
-    hipLaunchKernelGGL(taglog_match_kernel, grid, dim3(256), 0, as_stream(stream), cap,
-                       reinterpret_cast<const unsigned long long*>(log_mask), log_n, p, first, last, ws);
-    AV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(taglog_segments_kernel<false>, grid, dim3(256), 0, as_stream(stream), cap, ws, min_duration, seg_cap, out_seg,
-                       out_n);
-    AV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(taglog_segments_kernel<true>, grid, dim3(256), 0, as_stream(stream), cap, ws, min_duration, seg_cap, out_seg,
-                       out_n);
-    AV_LAUNCH_CHECK();
-    return AV_OK;
+    const av_taglog_where where = masks_only(all, any, none);
+    return run_segments({"av_taglog_segments", ctx, stream, n_streams, cap, log_mask, nullptr, nullptr, log_n, &where, first, last,
+                         workspace}, min_duration, seg_cap, out_seg, out_n);
+}
+
+extern "C" int av_taglog_segments_where(av_ctx* ctx, av_stream_t stream, int n_streams, int cap, const uint64_t* log_mask,
+                                        const double* log_speed, const av_taglog_cols* log_cols, const int32_t* log_n,
+                                        const av_taglog_where* where, int first, int last, int min_duration, void* workspace,
+                                        int seg_cap, int32_t* out_seg, int32_t* out_n) {
+    return run_segments({"av_taglog_segments_where", ctx, stream, n_streams, cap, log_mask, log_speed, log_cols, log_n, where, first,
+                         last, workspace}, min_duration, seg_cap, out_seg, out_n);
 }
 
 extern "C" int av_taglog_stats(av_ctx* ctx, av_stream_t stream, int n_streams, int cap, const uint64_t* log_mask,
@@ -659,18 +687,12 @@ extern "C" int av_taglog_stats(av_ctx* ctx, av_stream_t stream, int n_streams, i
     AV_REQUIRE(n_streams > 0 && cap > 0, AV_EINVAL, "av_taglog_stats: n_streams and cap must be > 0");
     const Workspace ws = carve(workspace, n_streams, cap);
     hipLaunchKernelGGL(taglog_stats_chunk_kernel, chunk_grid(n_streams, cap), dim3(256), 0, as_stream(stream), cap,
-                       reinterpret_cast<const unsigned long long*>(log_mask), log_speed, log_n, ws);
+                       words(log_mask), log_speed, log_n, ws);
     AV_LAUNCH_CHECK();
     hipLaunchKernelGGL(taglog_stats_fold_kernel, dim3((unsigned)n_streams), dim3(FOLD_WAVES * 64), 0, as_stream(stream), cap, ws, out);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }
-
-// ---- records: host ---------------------------------------------------------------------------------------------------------
-namespace {
-inline const unsigned long long* words(const void* p) { return reinterpret_cast<const unsigned long long*>(p); }
-inline unsigned long long* words(void* p) { return reinterpret_cast<unsigned long long*>(p); }
-}  // namespace
 
 extern "C" int av_tags_cols(av_ctx* ctx, av_stream_t stream, int n_streams, int n_frames, const av_maneuver_row* maneuver,
                             const av_interaction_summary* inter_summary, const av_scene_row* scene, av_taglog_cols* out_cols) {
@@ -681,69 +703,6 @@ extern "C" int av_tags_cols(av_ctx* ctx, av_stream_t stream, int n_streams, int 
     const long long n_words = frames * COLS_WORDS;
     hipLaunchKernelGGL(tags_cols_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, as_stream(stream), n_words,
                        words(maneuver), words(inter_summary), words(scene), words(out_cols));
-    AV_LAUNCH_CHECK();
-    return AV_OK;
-}
-
-extern "C" int av_taglog_append_ex(av_ctx* ctx, av_stream_t stream, int n_streams, int n_frames, const uint64_t* mask,
-                                   const double* speed, const av_taglog_cols* cols, int cap, uint64_t* log_mask, double* log_speed,
-                                   av_taglog_cols* log_cols, int32_t* log_n, int32_t* dropped) {
-    AV_REQUIRE(ctx && mask && speed && log_mask && log_speed && log_n && dropped, AV_EINVAL, "av_taglog_append_ex: null argument");
-    AV_REQUIRE((cols == nullptr) == (log_cols == nullptr), AV_EINVAL,
-               "av_taglog_append_ex: cols and log_cols are given together or not at all");
-    AV_REQUIRE(n_streams > 0 && n_frames > 0 && cap > 0, AV_EINVAL, "av_taglog_append_ex: n_streams, n_frames and cap must be > 0");
-    hipLaunchKernelGGL(taglog_append_ex_kernel, dim3((unsigned)n_streams), dim3(256), 0, as_stream(stream), n_frames, words(mask),
-                       speed, words(cols), cap, words(log_mask), log_speed, words(log_cols), log_n, dropped);
-    AV_LAUNCH_CHECK();
-    return AV_OK;
-}
-
-namespace {
-// what both *_where queries check and launch first; 0 or the error code
-int launch_match_where(const char* who, av_ctx* ctx, av_stream_t stream, int n_streams, int cap, const uint64_t* log_mask,
-                       const double* log_speed, const av_taglog_cols* log_cols, const int32_t* log_n, const av_taglog_where* where,
-                       int first, int last, void* workspace, int out_cap, const void* out, const int32_t* out_n) {
-    AV_REQUIRE(ctx && log_mask && log_n && where && workspace && out_n && (out || out_cap == 0), AV_EINVAL, "%s: null argument", who);
-    AV_REQUIRE(n_streams > 0 && cap > 0, AV_EINVAL, "%s: n_streams and cap must be > 0", who);
-    AV_REQUIRE(out_cap >= 0, AV_EINVAL, "%s: the output capacity %d is negative", who, out_cap);
-    const WhereUse use = where_use(*where);
-    AV_REQUIRE(log_speed || !use.speed, AV_EINVAL, "%s: a speed bound without log_speed", who);
-    AV_REQUIRE(log_cols || !(use.accel || use.ttc || use.dist || use.agent_ped || use.cyc_veh), AV_EINVAL,
-               "%s: a bound on a record's field without log_cols", who);
-    hipLaunchKernelGGL(taglog_match_where_kernel, chunk_grid(n_streams, cap), dim3(256), 0, as_stream(stream), cap, words(log_mask),
-                       log_speed, words(log_cols), log_n, *where, first, last, carve(workspace, n_streams, cap));
-    AV_LAUNCH_CHECK();
-    return AV_OK;
-}
-}  // namespace
-
-extern "C" int av_taglog_search_where(av_ctx* ctx, av_stream_t stream, int n_streams, int cap, const uint64_t* log_mask,
-                                      const double* log_speed, const av_taglog_cols* log_cols, const int32_t* log_n,
-                                      const av_taglog_where* where, int first, int last, void* workspace, int out_cap,
-                                      int32_t* out_idx, int32_t* out_n) {
-    const int rc = launch_match_where("av_taglog_search_where", ctx, stream, n_streams, cap, log_mask, log_speed, log_cols, log_n, where,
-                                      first, last, workspace, out_cap, out_idx, out_n);
-    if (rc != AV_OK) return rc;
-    hipLaunchKernelGGL(taglog_search_write_kernel, chunk_grid(n_streams, cap), dim3(256), 0, as_stream(stream), cap,
-                       carve(workspace, n_streams, cap), out_cap, out_idx, out_n);
-    AV_LAUNCH_CHECK();
-    return AV_OK;
-}
-
-extern "C" int av_taglog_segments_where(av_ctx* ctx, av_stream_t stream, int n_streams, int cap, const uint64_t* log_mask,
-                                        const double* log_speed, const av_taglog_cols* log_cols, const int32_t* log_n,
-                                        const av_taglog_where* where, int first, int last, int min_duration, void* workspace,
-                                        int seg_cap, int32_t* out_seg, int32_t* out_n) {
-    const int rc = launch_match_where("av_taglog_segments_where", ctx, stream, n_streams, cap, log_mask, log_speed, log_cols, log_n,
-                                      where, first, last, workspace, seg_cap, out_seg, out_n);
-    if (rc != AV_OK) return rc;
-    const Workspace ws = carve(workspace, n_streams, cap);
-    const dim3 grid = chunk_grid(n_streams, cap);
-    hipLaunchKernelGGL(taglog_segments_kernel<false>, grid, dim3(256), 0, as_stream(stream), cap, ws, min_duration, seg_cap, out_seg,
-                       out_n);
-    AV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(taglog_segments_kernel<true>, grid, dim3(256), 0, as_stream(stream), cap, ws, min_duration, seg_cap, out_seg,
-                       out_n);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }

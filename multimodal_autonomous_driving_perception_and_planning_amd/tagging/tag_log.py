@@ -1,8 +1,8 @@
 """TagLog -- AutoTagger's bookkeeping (src/tagging/auto_tagger.py:112-310) for S streams, resident on the device.
 
 A logged frame is one 64-bit mask over the fixed vocabulary TAGS (include/avhot.h: AV_TAG_*) plus the frame's speed.  The
-log is appended by av_tags_pack + av_taglog_append from the three taggers' rows in HBM (HotLoop.enqueue_tags,
-CameraLoop(tags=...)) and queried by kernels (av_taglog_search / _segments / _stats); only the answers come back to the host.
+log is appended by av_tags_pack + av_taglog_append_ex from the three taggers' rows in HBM (HotLoop.enqueue_tags,
+CameraLoop(tags=...)) and queried by kernels (av_taglog_search_where / _segments_where / _stats); only the answers come back to the host.
 The query surface carries the reference's names with a stream axis added; searches return frame indices, not FrameTags.
 
 TagLog(columns=True) also keeps a record per frame (av_taglog_cols: the confidences, the acceleration, min_ttc, the closest
@@ -162,12 +162,7 @@ class TagLog:
             raise ValueError("masks and speeds are [n_streams, W]")
         if (cols is not None) != self.columns:
             raise ValueError("a log with columns takes the frames' records with every append, a log without takes none")
-        if not self.columns:
-            nat.check(self.L.av_taglog_append(self.ctx.handle, self._s(stream), self.S, int(m.shape[1]), nat.ptr(m), nat.ptr(v),
-                                              self.cap, nat.ptr(self.mask), nat.ptr(self.speed), nat.ptr(self.log_n),
-                                              nat.ptr(self.dropped)))
-            return
-        c = self._cols_to_dev(cols, int(m.shape[1]))
+        c = self._cols_to_dev(cols, int(m.shape[1])) if self.columns else None
         nat.check(self.L.av_taglog_append_ex(self.ctx.handle, self._s(stream), self.S, int(m.shape[1]), nat.ptr(m), nat.ptr(v),
                                              nat.ptr(c), self.cap, nat.ptr(self.mask), nat.ptr(self.speed), nat.ptr(self.cols),
                                              nat.ptr(self.log_n), nat.ptr(self.dropped)))
@@ -261,35 +256,8 @@ class TagLog:
         res = [np.zeros((0,) if width == 1 else (0, width), np.int32) for _ in range(self.S)]
         return res if stream is None else res[stream]
 
-    def search_masks(self, all_=0, any_=0, none=0, stream=None, first=0, last=None):
-        """Frame indices with (m & all_) == all_, (any_ == 0 or m & any_) and not m & none, inside [first, last): one int32
-        array for a given stream, a list of S for None."""
-        last = self.cap if last is None else int(last)
-
-        def call(cap, out):
-            nat.check(self.L.av_taglog_search(self.ctx.handle, self._s(), self.S, self.cap, nat.ptr(self.mask), nat.ptr(self.log_n),
-                                              all_, any_, none, int(first), last, nat.ptr(self.ws), cap, nat.ptr(out),
-                                              nat.ptr(self._out_n)))
-        return self._query("search", 1, call, stream)
-
-    def segment_masks(self, all_=0, any_=0, none=0, min_duration=5, stream=None, first=0, last=None):
-        """Maximal runs of matching frames at least min_duration long: int32 [n, 2] (first, last) per stream."""
-        last = self.cap if last is None else int(last)
-
-        def call(cap, out):
-            nat.check(self.L.av_taglog_segments(self.ctx.handle, self._s(), self.S, self.cap, nat.ptr(self.mask), nat.ptr(self.log_n),
-                                                all_, any_, none, int(first), last, int(min_duration), nat.ptr(self.ws), cap,
-                                                nat.ptr(out), nat.ptr(self._out_n)))
-        return self._query("segments", 2, call, stream)
-
-    # ---- numeric queries and records -----------------------------------------------------------------------------------
-    def _run_where(self, where, stream, first, last, min_duration=None):
-        """search_where (min_duration None) / segments_where through _query; None where no frame can match (see _predicate)."""
-        q, on_cols = _where(**where)
-        if on_cols and not self.columns:
-            raise ValueError("a bound on acceleration, TTC, distance or an agent count needs TagLog(columns=True)")
-        if q is None:
-            return None
+    def _run(self, q, stream, first, last, min_duration=None):
+        """The search (min_duration None) or the segment query of the av_taglog_where `q`, through _query."""
         last = self.cap if last is None else int(last)
         head = lambda: (self.ctx.handle, self._s(), self.S, self.cap, nat.ptr(self.mask), nat.ptr(self.speed),  # noqa: E731
                         nat.ptr(self.cols), nat.ptr(self.log_n), C.byref(q), int(first), last)
@@ -304,25 +272,42 @@ class TagLog:
             return self._query("search", 1, search, stream)
         return self._query("segments", 2, segments, stream)
 
+    def search_masks(self, all_=0, any_=0, none=0, stream=None, first=0, last=None):
+        """Frame indices with (m & all_) == all_, (any_ == 0 or m & any_) and not m & none, inside [first, last): one int32
+        array for a given stream, a list of S for None."""
+        q = _where()[0]                     # every bound unset
+        q.all, q.any, q.none = all_, any_, none
+        return self._run(q, stream, first, last)
+
+    def segment_masks(self, all_=0, any_=0, none=0, min_duration=5, stream=None, first=0, last=None):
+        """Maximal runs of matching frames at least min_duration long: int32 [n, 2] (first, last) per stream."""
+        q = _where()[0]
+        q.all, q.any, q.none = all_, any_, none
+        return self._run(q, stream, first, last, int(min_duration))
+
+    # ---- numeric queries and records -----------------------------------------------------------------------------------
+    def _run_where(self, stream, first, last, min_duration, *where, **where_kw):
+        """_run of _where(*where, **where_kw); None where no frame can match (see _predicate)."""
+        q, on_cols = _where(*where, **where_kw)
+        if on_cols and not self.columns:
+            raise ValueError("a bound on acceleration, TTC, distance or an agent count needs TagLog(columns=True)")
+        return None if q is None else self._run(q, stream, first, last, min_duration)
+
     def search_where(self, tags=(), match_all=True, none=(), speed=None, acceleration=None, max_ttc=None, max_distance=None,
                      min_agents=0, min_pedestrians=0, min_cyclists=0, min_vehicles=0, stream=None, first=0, last=None):
         """Frame indices carrying `tags` (all of them, or any under match_all=False; unknown tags as in search_by_tags) and none of
         `none`, with speed / acceleration inside (lo, hi) (None = open end), min_ttc <= max_ttc, closest distance <= max_distance
         and at least the given agent counts.  A frame without the bounded value (min_ttc None, no maneuver row) does not match."""
-        where = dict(tags=tags, match_all=match_all, none=none, speed=speed, acceleration=acceleration, max_ttc=max_ttc,
-                     max_distance=max_distance, min_agents=min_agents, min_pedestrians=min_pedestrians, min_cyclists=min_cyclists,
-                     min_vehicles=min_vehicles)
-        res = self._run_where(where, stream, first, last)
+        res = self._run_where(stream, first, last, None, tags, match_all, none, speed, acceleration, max_ttc, max_distance, min_agents,
+                              min_pedestrians, min_cyclists, min_vehicles)                # _where's order
         return self._empty(1, stream) if res is None else res
 
     def segments_where(self, tags=(), match_all=True, none=(), speed=None, acceleration=None, max_ttc=None, max_distance=None,
                        min_agents=0, min_pedestrians=0, min_cyclists=0, min_vehicles=0, stream=None, first=0, last=None,
                        min_duration=5):
         """Maximal runs of frames matching search_where's predicate, at least min_duration long: int32 [n, 2] per stream."""
-        where = dict(tags=tags, match_all=match_all, none=none, speed=speed, acceleration=acceleration, max_ttc=max_ttc,
-                     max_distance=max_distance, min_agents=min_agents, min_pedestrians=min_pedestrians, min_cyclists=min_cyclists,
-                     min_vehicles=min_vehicles)
-        res = self._run_where(where, stream, first, last, int(min_duration))
+        res = self._run_where(stream, first, last, int(min_duration), tags, match_all, none, speed, acceleration, max_ttc, max_distance,
+                              min_agents, min_pedestrians, min_cyclists, min_vehicles)
         return self._empty(2, stream) if res is None else res
 
     def record_dtype(self):
@@ -367,7 +352,7 @@ class TagLog:
 
     def records_where(self, stream=None, first=0, last=None, **where):
         """The frames search_where(**where) finds, as records: the indices go from the search to the gather on the device."""
-        found = self._run_where(where, None, first, last)
+        found = self._run_where(None, first, last, None, **where)
         if found is None:
             res = [np.zeros(0, self.record_dtype()) for _ in range(self.S)]
         else:                               # _query left the indices in its output buffer and their counts in _out_n

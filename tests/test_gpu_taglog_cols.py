@@ -3,7 +3,8 @@ _segments_where, av_taglog_gather; tagging/tag_log.py; database/tag_database.py)
 
 (1) av_tags_cols with each row group absent in turn; (2) av_taglog_append_ex without records against av_taglog_append, and with
 records across the capacity; (3) search_where / segments_where on streams of every boundary length, each bound alone and all
-together; (4) av_taglog_gather; (5) TagDatabase.save_tag_log against the per-frame path; (6) HotLoop with a log with columns.
+together, and the mask-only entries against the _where entries given the same masks; (4) av_taglog_gather;
+(5) TagDatabase.save_tag_log against the per-frame path; (6) HotLoop with a log with columns.
 Every comparison is exact -- doubles by their bits: no value is computed, only copied or compared.
 """
 import ctypes as C
@@ -346,6 +347,61 @@ def test_where_contract_and_argument_checks(env):
         plain.append(np.zeros((3, 2), np.uint64), np.zeros((3, 2)), np.zeros((3, 2), D.COLS))
     with pytest.raises(ValueError):
         log.append(np.zeros((3, 2), np.uint64), np.zeros((3, 2)))
+
+
+@gpu
+def test_mask_entries_equal_where_entries(env):
+    """av_taglog_search / _segments against av_taglog_search_where / _segments_where given the same three masks, every double bound
+    NaN, every count bound 0 and no speeds or records: the translation the mask-only entries perform.  Streams of 0, 1025 (one frame
+    into a second chunk) and 4097 frames (a partial fifth chunk, in a second workgroup)."""
+    torch, nat, L, ctx = env
+    from multimodal_autonomous_driving_perception_and_planning_amd.tagging import tag_log as tl
+    lengths = (0, 1025, 4097)
+    masks, speeds, _ = _streams(lengths, seed=sum(lengths))
+    log = tl.TagLog(3, CAP, ctx=ctx)
+    _fill(env, log, masks, speeds, None)
+    day, fog, rain = (tl.tag_mask([t]) for t in ("day", "fog", "rain"))
+    predicates = [(day, 0, fog), (0, fog | rain, 0), (0, 0, 0)]
+    windows = [(0, CAP), (1010, 1040), (-5, INT32_MAX), (1024, 1024)]
+    P, sh = nat.ptr, nat.stream_handle()
+    n_a, n_b = (torch.zeros(3, dtype=torch.int32, device="cuda:0") for _ in range(2))
+    nan = float("nan")
+    checked = 0
+    for k, (all_, any_, none) in enumerate(predicates):
+        q = nat.TaglogWhere(all_, any_, none, nan, nan, nan, nan, nan, nan, 0, 0, 0, 0)
+        for first, last in windows:
+            for cap in (4, CAP):
+                for md in (None, 1, 5):                                 # None: the search
+                    shape = (3, cap) if md is None else (3, cap, 2)
+                    a, b = (torch.full(shape, -7, dtype=torch.int32, device="cuda:0") for _ in range(2))
+                    if md is None:
+                        ra = L.av_taglog_search(ctx.handle, sh, 3, CAP, P(log.mask), P(log.log_n), all_, any_, none, first, last, P(log.ws),
+                                                cap, P(a), P(n_a))
+                        rb = L.av_taglog_search_where(ctx.handle, sh, 3, CAP, P(log.mask), None, None, P(log.log_n), C.byref(q), first, last,
+                                                      P(log.ws), cap, P(b), P(n_b))
+                    else:
+                        ra = L.av_taglog_segments(ctx.handle, sh, 3, CAP, P(log.mask), P(log.log_n), all_, any_, none, first, last, md,
+                                                  P(log.ws), cap, P(a), P(n_a))
+                        rb = L.av_taglog_segments_where(ctx.handle, sh, 3, CAP, P(log.mask), None, None, P(log.log_n), C.byref(q), first,
+                                                        last, md, P(log.ws), cap, P(b), P(n_b))
+                    assert ra == 0 and rb == 0, L.av_last_error_string()
+                    torch.cuda.synchronize()
+                    na, nb, ha, hb = n_a.cpu().tolist(), n_b.cpu().tolist(), a.cpu().numpy(), b.cpu().numpy()
+                    case = (k, first, last, cap, md)
+                    assert na == nb, case
+                    for s in range(3):
+                        rows = min(na[s], cap)
+                        assert np.array_equal(ha[s, :rows], hb[s, :rows]), case + (s,)
+                        assert (ha[s, rows:] == -7).all() and (hb[s, rows:] == -7).all(), case + (s,)
+                    if k == 0:                                          # not two empty answers: the restatement's counts
+                        ref = R.search if md is None else R.segments
+                        kw = dict(all_=all_, any_=any_, none=none, first=first, last=last)
+                        if md is not None:
+                            kw["min_duration"] = md
+                        want = [len(ref(masks[s], **kw)) for s in range(3)]
+                        assert na == want, case
+                        checked += sum(want)
+    assert checked > 0
 
 
 # ---- (4) av_taglog_gather --------------------------------------------------------------------------------------------------
