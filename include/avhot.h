@@ -522,6 +522,14 @@ int av_track_obstacles_ground_lens(av_ctx* ctx, av_stream_t stream, const av_obs
                                    const av_lens_cfg* lens, int cam_stride, int mode, double frame_rate, int n_states, int tcap,
                                    const av_track_row* snap, const int32_t* snap_n, const double* filt, const double* plan_state,
                                    int ocap, double* obstacles, int32_t* n_obs, int32_t* n_off);
+/* av_track_obstacles_ground (lens NULL) or av_track_obstacles_ground_lens (lens given) with a class lane: the same kernel, which
+ * writes beside every obstacle row o of state f the class of the tracker row behind it, obs_cls[f][o] = row.cls, whatever its
+ * value.  obs_cls int32 [n_states][ocap] or NULL (then exactly the call without it); entries at or past n_obs[f] are not written.
+ * Every other argument, output and check as there. */
+int av_track_obstacles_ground_cls(av_ctx* ctx, av_stream_t stream, const av_obstacle_cfg* cfg, const av_ground_cfg* ground,
+                                  const av_lens_cfg* lens, int cam_stride, int mode, double frame_rate, int n_states, int tcap,
+                                  const av_track_row* snap, const int32_t* snap_n, const double* filt, const double* plan_state,
+                                  int ocap, double* obstacles, int32_t* n_obs, int32_t* n_off, int32_t* obs_cls);
 
 /* ---- Camera rigs (opt-in): K cameras per vehicle, their obstacle lists fused on the road ------------------------------------------
  * A mount places a camera's road frame (x forward, y lateral from the camera's ground point) in the vehicle's: a rotation by the
@@ -567,6 +575,16 @@ typedef struct {
 int av_rig_fuse(av_ctx* ctx, av_stream_t stream, const av_rig_cfg* cfg, int n_vehicles, int n_cams, const av_rig_mount* mounts,
                 int ncol, int ocap_in, const double* cam_obs, const int32_t* cam_n, const double* plan_state, int ocap,
                 double* obstacles, int32_t* n_obs, int32_t* views, int32_t* n_skip);
+/* av_rig_fuse with a class lane: cam_cls int32 [V*K][ocap_in] beside cam_obs (av_track_obstacles_ground_cls's obs_cls), cls int32
+ * [V][ocap] beside obstacles, given together or both NULL (then exactly av_rig_fuse).  The association does not look at the classes:
+ * obstacles, n_obs, views and n_skip are av_rig_fuse's bit for bit.  A cluster carries (best_w, cls): a new cluster takes its
+ * member's w and class; an absorbed candidate with w > best_w (strictly) replaces both -- the class comes from the camera that sees
+ * the object nearest, from the earlier camera among equals.  Class values travel as they are, negatives included; cls[v][i] is
+ * cluster i's, entries at or past n_obs[v] are not written. */
+int av_rig_fuse_cls(av_ctx* ctx, av_stream_t stream, const av_rig_cfg* cfg, int n_vehicles, int n_cams, const av_rig_mount* mounts,
+                    int ncol, int ocap_in, const double* cam_obs, const int32_t* cam_n, const int32_t* cam_cls,
+                    const double* plan_state, int ocap, double* obstacles, int32_t* n_obs, int32_t* views, int32_t* n_skip,
+                    int32_t* cls);
 
 /* ---- Vehicle-frame tracks (opt-in): av_rig_fuse's lists followed over time -------------------------------------------------------
  * A multi-object tracker in the planner's frame, one frame per call, with a state of its own per vehicle and a constant-velocity
@@ -591,7 +609,8 @@ typedef struct {
 /* Persistent per-vehicle state (device).  Layout, for vehicle v with capacity tcap (1 .. 512), 16-byte aligned:
  *   int32 hdr[16]                  hdr[0] = status, hdr[1] = the next id (1 after a reset), hdr[2] = frames seen,
  *                                  hdr[3] = live tracks; the rest 0
- *   slot[tcap], 96 bytes each:     int32 id (-1: free), hits, misses, age, views, views_ever, reserved[2] (0);
+ *   slot[tcap], 96 bytes each:     int32 id (-1: free), hits, misses, age, views, views_ever, reserved[2] (0; the first is
+ *                                  av_rig_track_cls's class word, class id + 1, which av_rig_track carries unchanged);
  *                                  double x[4] (x, y, vx, vy); double p[3] (P_pos, P_pos,vel, P_vel); double r (the radius)
  * x and y never mix and share F, Q, R and the initial variances, so the covariance is two equal 2 x 2 blocks, one per axis, as in
  * av_track_filter_update.  status bit0: a row found no free slot and was dropped (sticky until the next reset).
@@ -633,6 +652,16 @@ int av_rig_track(av_ctx* ctx, av_stream_t stream, const av_rig_track_cfg* cfg, i
                  const double* obs_in, const int32_t* n_in, const int32_t* views_in, const double* plan_state, void* state,
                  int ocap_out, double* obstacles, int32_t* n_obs, int32_t* obs_slot, int32_t* match, int32_t* n_skip,
                  int32_t* n_drop);
+/* av_rig_track with a class lane: cls_in int32 [V][ocap_in] beside obs_in (av_rig_fuse_cls's cls), cls_out int32 [V][ocap_out]
+ * beside obstacles, each or NULL; with both NULL exactly av_rig_track.  The slot's first reserved word holds cls1 = class id + 1,
+ * 0: no class known.  With cls_in given: a matched slot (step 4) or a birth (step 6) whose row has class c >= 0 sets cls1 = c + 1
+ * (the latest observation wins); a row with c < 0 leaves a matched slot's word alone and gives a newborn 0.  A slot freed in step 5
+ * gets 0 like its other words.  With cls_in NULL the word is carried unchanged.  Step 7 writes cls_out[v][o] = cls1 - 1 beside
+ * output row o (-1: no class known).  The association does not look at the classes. */
+int av_rig_track_cls(av_ctx* ctx, av_stream_t stream, const av_rig_track_cfg* cfg, int n_vehicles, int tcap, int ncol, int ocap_in,
+                     const double* obs_in, const int32_t* n_in, const int32_t* views_in, const int32_t* cls_in,
+                     const double* plan_state, void* state, int ocap_out, double* obstacles, int32_t* n_obs, int32_t* obs_slot,
+                     int32_t* match, int32_t* n_skip, int32_t* n_drop, int32_t* cls_out);
 
 /* ---- The rig's surround view (opt-in): a vehicle's K rectified frames stitched into one top-down panel --------------------------
  * av_ground_warp gives one panel per camera, each in its own camera's road frame.  av_rig_surround gives one panel per VEHICLE in
@@ -996,6 +1025,70 @@ int av_interaction_detect(av_ctx* ctx, av_stream_t stream, const av_interaction_
                           const uint8_t* has_state, const double* vy, void* state, av_interaction_row* rows,
                           av_interaction_summary* summary);
 
+/* ---- Interaction tags of a rig (opt-in): the rules above on av_rig_track's vehicle-frame tracks -----------------------------------
+ * av_interaction_detect guesses a distance from the box height and "in front" from the image centre.  Behind av_rig_track the
+ * quantities themselves are there -- a position in metres, a filtered velocity on the road, an id that survives camera hand-overs,
+ * objects beside and behind the vehicle -- so this tagger is the library's own: the reference's types, confidences, risk levels and
+ * thresholds (interaction_detector.py:117-125: 3 / 10 / 8 / 15 / 5 / 30 m, 3.0 s / 1.5 s) on metric inputs, plus the four types a
+ * forward camera can never produce (being_followed, vehicle_cut_out, passing, being_passed).  yielding and merging are not produced.
+ * Cut-in is tested ahead of following, unlike the reference: a vehicle that has just entered the corridor is a cut-in for as long as
+ * its oldest remembered offset lies outside the corridor, and is followed after that.  float64, every operation rounded on its own
+ * (no FMA), in the order written. */
+typedef struct {
+    double dt;                /* 1/30   seconds per frame */
+    double corridor_half;     /* 1.75   |lateral| below this is the ego's path, metres */
+    double adjacent_half;     /* 5.25   |lateral| below this (and not in the path) is the neighbouring lane, metres */
+    double alongside;         /* 10.0   |forward| below this is beside the ego, metres */
+    double pass_speed;        /* 1.0    forward speed difference that counts as passing, m/s; all five finite and > 0 */
+    int32_t min_hits;         /* the tracker's (av_rig_track_cfg); >= 1 */
+    int32_t reserved;
+    int32_t class_kind[16];   /* av_interaction_cfg's table and meaning, indexed by the track's class id */
+} av_rig_interact_cfg;        /* 112 bytes */
+/* Persistent per-vehicle state (device), for capacity tcap (1 .. 512): int64 frames, 8 bytes of 0, then per slot of the tracker
+ * { int32 id, int32 cnt, double lat[30] } (248 bytes): the ring of the slot's lateral offsets.  av_rig_interact_reset sets frames
+ * to 0, every id to -1 and every other byte to 0. */
+size_t av_rig_interact_state_bytes(int tcap);          /* 16 + 248 * tcap; 0 for tcap outside 1 .. 512 */
+int av_rig_interact_reset(av_ctx* ctx, av_stream_t stream, int n_vehicles, int tcap, void* state);
+/* One frame per vehicle.  track_state is av_rig_track's state of the same tcap, read only; (x0, y0, h, v0) = plan_state[v].  Slot t
+ * of the tracker (id, hits, cls1 = its class word, x, y, vx, vy) is an agent when id >= 0 and hits >= min_hits (coasting tracks
+ * included: the planner sees them too).  Per agent:
+ *   cs = cos h;  sn = sin h;  c2 = cos(h + pi/2);  s2 = sin(h + pi/2)                                      (av_rig_fuse's)
+ *   ex = x - x0;  ey = y - y0;  X = ex*cs + ey*sn;  Y = ex*c2 + ey*s2                                      forward, lateral
+ *   rvx = vx - v0*cs;  rvy = vy - v0*sn;  RVX = rvx*cs + rvy*sn                                            relative to the ego
+ *   d = sqrt(ex*ex + ey*ey);  closing = d > 0 ? -((ex*rvx + ey*rvy) / d) : 0                               > 0: the range shrinks
+ *   ttc = closing > 0.1 ? d / closing : none                                                               (_calculate_ttc)
+ *   ring: c = (stored id == id) ? cnt : 0;  lat[c % 30] = Y;  cnt = c + 1;  stored id = id;  hl = min(cnt, 30);
+ *         Y0 = the oldest of the last hl entries (lat[0] while cnt <= 30, else lat[cnt % 30])
+ *   ahead = X > 0;  in_path = |Y| < corridor_half;  beside = !in_path && |Y| < adjacent_half
+ *   kind = class_kind[cls1 - 1] for cls1 in 1..16, else 0
+ * Rules, the first hit wins (type, confidence, risk; risk 0 low, 1 medium, 2 high, 3 critical):
+ *   1   d < 3                                                        near_miss 9, 0.9, critical
+ *   2a  kind 1, d < 10, ahead && in_path                             pedestrian_crossing 6, 0.8, high if d < 8 else medium
+ *   2b  kind 1, d < 10, otherwise                                    pedestrian_waiting 7, 0.6, low; relative_speed 0, no ttc
+ *   3   kind 2, d < 15                                               cyclist_nearby 8, 0.7, medium if d < 8 else low; no ttc
+ *   4a  kind 3, hl >= 10, d < 15, ahead, in_path, |Y0| >= corridor_half    vehicle_cut_in 4, 0.7, medium
+ *   4b  kind 3, hl >= 10, d < 15, ahead, !in_path, |Y0| < corridor_half    vehicle_cut_out 5, 0.7, low
+ *   4c  kind 3, in_path, 5 < d < 30, ahead                           following_vehicle 1, 0.75, medium if d < 10 else low; high if
+ *                                                                    ttc given and < 3
+ *   4d  kind 3, in_path, 5 < d < 30, not ahead                       being_followed 2, 0.75, low; high if ttc given and < 3
+ *   4e  kind 3, beside, |X| < alongside, RVX < -pass_speed           passing 11, 0.7, low
+ *   4f  kind 3, beside, |X| < alongside, RVX > pass_speed            being_passed 12, 0.7, low
+ * rows[v][t], slot-indexed: an agent's row holds type (-1: no rule hit), risk, agent_id = id, cls = cls1 - 1, confidence,
+ * distance = d, and with a type relative_speed = closing and ttc (NaN: none) unless the rule says otherwise; without a type
+ * relative_speed 0, ttc NaN.  A slot that is no agent gets type -1, risk 0, agent_id -1, cls -1, 0.0 and ttc NaN.
+ * summary[v]: the counts by kind as av_interaction_detect counts them (vehicle_count: kinds 3 and 4); n_interactions = the rows
+ * with a type; closest_distance = the smallest d, inf without agents; min_ttc = the smallest ttc over the agents, NaN when none has
+ * one; primary_row / primary_type = the interaction with the highest risk, then the highest confidence, then the smallest slot (-1, -1
+ * without one) -- a numeric order, not the reference's sort on the risk's name, because this tagger is the library's own;
+ * overall_risk = 3 when an interaction exists and min_ttc < 1.5, else the largest risk (0 without interactions);
+ * timestamp = (double)frames * dt, then frames += 1.
+ *   track_state [V] x av_rig_track_state_bytes(tcap); plan_state [V][4]; state [V] x av_rig_interact_state_bytes(tcap)
+ *   rows av_interaction_row [V][tcap]; summary av_interaction_summary [V]
+ * AV_EINVAL before any launch and before the context is looked at: n_vehicles < 1; tcap not in 1..512; a cfg double that is not
+ * finite and > 0 (the message names the field); min_hits < 1; a null pointer other than stream. */
+int av_rig_interact(av_ctx* ctx, av_stream_t stream, const av_rig_interact_cfg* cfg, int n_vehicles, int tcap, const void* track_state,
+                    const double* plan_state, void* state, av_interaction_row* rows, av_interaction_summary* summary);
+
 /* ---- tag log: per-frame tag masks, search, event segments, statistics -----------------------------------------
  * Replaces AutoTagger's bookkeeping (src/tagging/auto_tagger.py:112-310: all_tags, tag_counts, search_by_tag(s),
  * get_high_risk_frames, get_event_segments, get_tag_statistics) for S streams, on the device.  A logged frame is one 64-bit mask
@@ -1031,6 +1124,13 @@ int av_tags_pack(av_ctx* ctx, av_stream_t stream, int n_streams, int n_frames, c
                  const av_interaction_row* inter_rows, const av_interaction_summary* inter_summary, const int32_t* snap_n, int tcap,
                  const av_scene_row* scene, const int32_t* det_n, const int32_t* det_cls, int max_det, const uint8_t* elem_table,
                  int n_elem, uint64_t* out_mask, double* out_speed);
+/* av_tags_pack's maneuver and interaction groups for slot-indexed rows (av_rig_interact's): inter_rows [S][W][tcap] with any tcap in
+ * 1..512 and no snap_n -- every row with 0 <= type < 13 and confidence > 0.5 sets its bit, a row of type -1 none.  No scene group.
+ * The same kernel.  AV_EINVAL: n_streams or n_frames < 1; inter_rows and inter_summary not given together; tcap outside 1..512
+ * with them; a null ctx, out_mask or out_speed. */
+int av_tags_pack_slots(av_ctx* ctx, av_stream_t stream, int n_streams, int n_frames, const av_maneuver_row* maneuver,
+                       const av_interaction_row* inter_rows, const av_interaction_summary* inter_summary, int tcap,
+                       uint64_t* out_mask, double* out_speed);
 /* The log: log_mask u64 [S][cap], log_speed f64 [S][cap], log_n int32 [S], dropped int32 [S], the caller's, zeroed to start with.
  * An append copies mask / speed [S][W] behind log_n[s] and advances log_n on the device (no host synchronisation: it can
  * sit in a step).  A frame that does not fit is not written and counted in dropped[s]; log_n never exceeds cap. */

@@ -93,6 +93,18 @@ RIG_TRACK_SLOT_FIELDS = [("id", "<i4"), ("hits", "<i4"), ("misses", "<i4"), ("ag
                          ("reserved", "<i4", (2,)), ("x", "<f8", (4,)), ("p", "<f8", (3,)), ("r", "<f8")]           # 96 bytes
 
 
+class RigInteractCfg(C.Structure):
+    """av_rig_interact_cfg: the rig tagger's frame time, lane geometry (metres), passing speed, the tracker's min_hits and the
+    class table of av_interaction_cfg; 112 bytes."""
+    _fields_ = [("dt", C.c_double), ("corridor_half", C.c_double), ("adjacent_half", C.c_double), ("alongside", C.c_double),
+                ("pass_speed", C.c_double), ("min_hits", C.c_int32), ("reserved", C.c_int32), ("class_kind", C.c_int32 * 16)]
+
+
+RIG_INTERACT_HDR_BYTES = 16
+RIG_INTERACT_SLOT_BYTES = 248
+RIG_INTERACT_SLOT_FIELDS = [("id", "<i4"), ("cnt", "<i4"), ("lat", "<f8", (30,))]                                    # 248 bytes
+
+
 class TrackFilterCfg(C.Structure):
     """av_track_filter_cfg: the per-track constant-velocity Kalman filter's noise and initial variances (px, frames)."""
     _fields_ = [("q_accel", C.c_double), ("r_meas", C.c_double), ("p0_pos", C.c_double), ("p0_vel", C.c_double)]
@@ -322,6 +334,16 @@ _SIGS = [
     ("av_remap", C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.POINTER(C.c_uint8), vp]),
     ("av_track_obstacles_ground_lens", C.c_int, [vp, vp, C.POINTER(ObstacleCfg), vp, vp, C.c_int, C.c_int, C.c_double, C.c_int,
                                                  C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp]),
+    ("av_track_obstacles_ground_cls", C.c_int, [vp, vp, C.POINTER(ObstacleCfg), vp, vp, C.c_int, C.c_int, C.c_double, C.c_int,
+                                                C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]),
+    ("av_rig_fuse_cls", C.c_int, [vp, vp, C.POINTER(RigCfg), C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp,
+                                  vp, vp, vp]),
+    ("av_rig_track_cls", C.c_int, [vp, vp, C.POINTER(RigTrackCfg), C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int,
+                                   vp, vp, vp, vp, vp, vp, vp]),
+    ("av_rig_interact_state_bytes", C.c_size_t, [C.c_int]),
+    ("av_rig_interact_reset", C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
+    ("av_rig_interact", C.c_int, [vp, vp, C.POINTER(RigInteractCfg), C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    ("av_tags_pack_slots", C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp]),
     ("av_rig_fuse", C.c_int, [vp, vp, C.POINTER(RigCfg), C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp,
                               vp]),
     ("av_rig_track_state_bytes", C.c_size_t, [C.c_int]),

@@ -27,6 +27,9 @@
 // The lens form (av_track_obstacles_ground_lens) takes the rows in RAW pixels: the foot is undistorted first (lens_dev.h: six
 // Newton iterations on the Brown-Conrady model of the state's camera), a foot with no valid preimage is off the road, and the
 // pixel velocity goes through the undistortion's Jacobian before the projection's.
+//
+// The class form (av_track_obstacles_ground_cls) is either of the two with an int32 lane beside the obstacle rows: a kept lane also
+// writes its row's class, for the fuse and the tracker behind it (rig.hip, rigtrack.hip) to carry on.
 #include "common.h"
 #include "ground_dev.h"
 #include "lens_dev.h"
@@ -44,11 +47,13 @@ struct Ground {
     const av_ground_cfg* table;     // device [n_cams]
     int cam_stride;                 // state f uses table[f / cam_stride]
     int32_t* n_off;                 // [n_states] or NULL
+    int32_t* obs_cls;               // [n_states][ocap] or NULL: the class of the row behind each obstacle
 };
 struct GroundLens {
     const av_ground_cfg* table;     // as Ground
     int cam_stride;
     int32_t* n_off;
+    int32_t* obs_cls;
     const av_lens_cfg* lens;        // device [n_cams], beside table: the rows are raw pixels
 };
 
@@ -90,8 +95,10 @@ __global__ void __launch_bounds__(256) track_obstacles_kernel(av_obstacle_cfg cf
         const int i = b + lane;
         bool keep = false, off_road = false;
         double ox = 0.0, oy = 0.0, rad = 0.0, ovx = 0.0, ovy = 0.0;
+        int cls = 0;
         if (i < n) {
             const av_track_row r = rows[i];
+            cls = r.cls;
 #pragma unroll
             for (int k = 0; k < 16; ++k) rad = r.cls == k ? cfg.radius[k] : rad;      // (ids outside 0..15 keep 0: no obstacle)
             keep = (r.flags & 1) && rad > 0.0;
@@ -153,9 +160,13 @@ __global__ void __launch_bounds__(256) track_obstacles_kernel(av_obstacle_cfg cf
         if constexpr (GROUND) off += __popcll(__ballot(off_road));
         const unsigned long long m = __ballot(keep);
         if (keep) {
-            double* o = out + (size_t)(count + __popcll(m & ((1ull << lane) - 1ull))) * OS;     // < n <= tcap <= ocap
+            const size_t at = (size_t)(count + __popcll(m & ((1ull << lane) - 1ull)));          // < n <= tcap <= ocap
+            double* o = out + at * OS;
             o[0] = ox, o[1] = oy, o[2] = rad;
             if constexpr (MOVING) o[3] = ovx, o[4] = ovy;
+            if constexpr (GROUND) {
+                if (via.obs_cls) via.obs_cls[(size_t)f * ocap + at] = cls;
+            }
         }
         count += __popcll(m);
     }
@@ -204,42 +215,52 @@ extern "C" int av_track_obstacles_filtered(av_ctx* ctx, av_stream_t stream, cons
                                             filt, "av_track_obstacles_filtered");
 }
 
-extern "C" int av_track_obstacles_ground(av_ctx* ctx, av_stream_t stream, const av_obstacle_cfg* cfg, const av_ground_cfg* ground,
-                                         int cam_stride, int mode, double frame_rate, int n_states, int tcap, const av_track_row* snap,
-                                         const int32_t* snap_n, const double* filt, const double* plan_state, int ocap,
-                                         double* obstacles, int32_t* n_obs, int32_t* n_off) {
-    const char* who = "av_track_obstacles_ground";
+// the three ground entries: lens NULL for rectified rows, obs_cls NULL for no class lane
+static int track_obstacles_ground(const char* who, av_ctx* ctx, av_stream_t stream, const av_obstacle_cfg* cfg,
+                                  const av_ground_cfg* ground, const av_lens_cfg* lens, int cam_stride, int mode, double frame_rate,
+                                  int n_states, int tcap, const av_track_row* snap, const int32_t* snap_n, const double* filt,
+                                  const double* plan_state, int ocap, double* obstacles, int32_t* n_obs, int32_t* n_off,
+                                  int32_t* obs_cls) {
     AV_REQUIRE(ground, AV_EINVAL, "%s: null argument", who);
     AV_REQUIRE(cam_stride >= 1, AV_EINVAL, "%s: cam_stride must be >= 1", who);
     AV_REQUIRE(mode >= STATIC && mode <= FILTERED, AV_EINVAL, "%s: mode %d not in 0..2", who, mode);
     AV_REQUIRE((mode == FILTERED) == (filt != nullptr), AV_EINVAL, "%s: filt goes with mode 2 and with no other", who);
-    const Ground via{ground, cam_stride, n_off};
-    if (mode == FILTERED)
-        return track_obstacles_launch<FILTERED>(ctx, stream, cfg, frame_rate, n_states, tcap, snap, snap_n, plan_state, ocap, obstacles,
-                                                n_obs, filt, who, via);
-    if (mode == MOVING_ROWS)
-        return track_obstacles_launch<MOVING_ROWS>(ctx, stream, cfg, frame_rate, n_states, tcap, snap, snap_n, plan_state, ocap,
-                                                   obstacles, n_obs, nullptr, who, via);
-    return track_obstacles_launch<STATIC>(ctx, stream, cfg, 0.0, n_states, tcap, snap, snap_n, plan_state, ocap, obstacles, n_obs,
-                                          nullptr, who, via);
+    auto launch = [&](auto via) {
+        if (mode == FILTERED)
+            return track_obstacles_launch<FILTERED>(ctx, stream, cfg, frame_rate, n_states, tcap, snap, snap_n, plan_state, ocap,
+                                                    obstacles, n_obs, filt, who, via);
+        if (mode == MOVING_ROWS)
+            return track_obstacles_launch<MOVING_ROWS>(ctx, stream, cfg, frame_rate, n_states, tcap, snap, snap_n, plan_state, ocap,
+                                                       obstacles, n_obs, nullptr, who, via);
+        return track_obstacles_launch<STATIC>(ctx, stream, cfg, 0.0, n_states, tcap, snap, snap_n, plan_state, ocap, obstacles, n_obs,
+                                              nullptr, who, via);
+    };
+    if (lens) return launch(GroundLens{ground, cam_stride, n_off, obs_cls, lens});
+    return launch(Ground{ground, cam_stride, n_off, obs_cls});
+}
+
+extern "C" int av_track_obstacles_ground(av_ctx* ctx, av_stream_t stream, const av_obstacle_cfg* cfg, const av_ground_cfg* ground,
+                                         int cam_stride, int mode, double frame_rate, int n_states, int tcap, const av_track_row* snap,
+                                         const int32_t* snap_n, const double* filt, const double* plan_state, int ocap,
+                                         double* obstacles, int32_t* n_obs, int32_t* n_off) {
+    return track_obstacles_ground("av_track_obstacles_ground", ctx, stream, cfg, ground, nullptr, cam_stride, mode, frame_rate, n_states,
+                                  tcap, snap, snap_n, filt, plan_state, ocap, obstacles, n_obs, n_off, nullptr);
 }
 
 extern "C" int av_track_obstacles_ground_lens(av_ctx* ctx, av_stream_t stream, const av_obstacle_cfg* cfg, const av_ground_cfg* ground,
                                               const av_lens_cfg* lens, int cam_stride, int mode, double frame_rate, int n_states,
                                               int tcap, const av_track_row* snap, const int32_t* snap_n, const double* filt,
                                               const double* plan_state, int ocap, double* obstacles, int32_t* n_obs, int32_t* n_off) {
-    const char* who = "av_track_obstacles_ground_lens";
-    AV_REQUIRE(ground && lens, AV_EINVAL, "%s: null argument", who);
-    AV_REQUIRE(cam_stride >= 1, AV_EINVAL, "%s: cam_stride must be >= 1", who);
-    AV_REQUIRE(mode >= STATIC && mode <= FILTERED, AV_EINVAL, "%s: mode %d not in 0..2", who, mode);
-    AV_REQUIRE((mode == FILTERED) == (filt != nullptr), AV_EINVAL, "%s: filt goes with mode 2 and with no other", who);
-    const GroundLens via{ground, cam_stride, n_off, lens};
-    if (mode == FILTERED)
-        return track_obstacles_launch<FILTERED>(ctx, stream, cfg, frame_rate, n_states, tcap, snap, snap_n, plan_state, ocap, obstacles,
-                                                n_obs, filt, who, via);
-    if (mode == MOVING_ROWS)
-        return track_obstacles_launch<MOVING_ROWS>(ctx, stream, cfg, frame_rate, n_states, tcap, snap, snap_n, plan_state, ocap,
-                                                   obstacles, n_obs, nullptr, who, via);
-    return track_obstacles_launch<STATIC>(ctx, stream, cfg, 0.0, n_states, tcap, snap, snap_n, plan_state, ocap, obstacles, n_obs,
-                                          nullptr, who, via);
+    AV_REQUIRE(lens, AV_EINVAL, "av_track_obstacles_ground_lens: null argument");
+    return track_obstacles_ground("av_track_obstacles_ground_lens", ctx, stream, cfg, ground, lens, cam_stride, mode, frame_rate,
+                                  n_states, tcap, snap, snap_n, filt, plan_state, ocap, obstacles, n_obs, n_off, nullptr);
+}
+
+extern "C" int av_track_obstacles_ground_cls(av_ctx* ctx, av_stream_t stream, const av_obstacle_cfg* cfg, const av_ground_cfg* ground,
+                                             const av_lens_cfg* lens, int cam_stride, int mode, double frame_rate, int n_states,
+                                             int tcap, const av_track_row* snap, const int32_t* snap_n, const double* filt,
+                                             const double* plan_state, int ocap, double* obstacles, int32_t* n_obs, int32_t* n_off,
+                                             int32_t* obs_cls) {
+    return track_obstacles_ground("av_track_obstacles_ground_cls", ctx, stream, cfg, ground, lens, cam_stride, mode, frame_rate,
+                                  n_states, tcap, snap, snap_n, filt, plan_state, ocap, obstacles, n_obs, n_off, obs_cls);
 }

@@ -6,7 +6,7 @@
 // squared distance on the road in place of the IoU.  Semantics and operation order: include/avhot.h.
 //
 // Mapping: one 512-thread workgroup per vehicle, cameras visited in turn (a round).  The clusters (at most 8 x 64 = 512, ten
-// doubles each) and the round's candidates (at most 64) live in LDS, 54 KB in all; the rows themselves are read once, up front,
+// doubles each, with the class lane's weight and class) and the round's candidates (at most 64) live in LDS, 60 KB in all; the rows themselves are read once, up front,
 // wave k taking camera k's list and holding it in registers until its round.  Thread (j, s) = (tid & 63, tid >> 6) owns
 // candidate j's view of cluster slice s (clusters s, s + 8, ...): it keeps the nearest admissible cluster of its slice that is
 // still free.  A wave therefore reads one cluster at a time, the same for all its lanes (an LDS broadcast).  A match iteration:
@@ -36,7 +36,12 @@ struct Shared {
     int32_t best_i[SLICES][MAX_IN];
     int32_t n_cand, n_clusters, win_i, win_j;
     int32_t skipped[MAX_CAMS];                                               // per camera: rows not taken
+    // the class lane (av_rig_fuse_cls): the class of the member with the largest weight, the earliest among equals
+    double best_w[MAX_CL];
+    int32_t cls[MAX_CL];
+    int32_t ccls[MAX_IN];
 };
+static_assert(sizeof(Shared) <= 64 * 1024, "the fuse kernel's static LDS");
 
 // candidate j against the still-free clusters s, s + 8, ... < m0: the nearest admissible one, the smallest index among equals
 __device__ __forceinline__ void scan_slice(const Shared& sh, const av_rig_cfg& cfg, int s, int m0, double x, double y, double r,
@@ -54,7 +59,8 @@ __global__ void __launch_bounds__(THREADS) rig_fuse_kernel(av_rig_cfg cfg, int n
                                                            int ocap_in, const double* __restrict__ cam_obs,
                                                            const int32_t* __restrict__ cam_n, const double* __restrict__ plan_state,
                                                            int ocap, double* __restrict__ obstacles, int32_t* __restrict__ n_obs,
-                                                           int32_t* __restrict__ views, int32_t* __restrict__ n_skip) {
+                                                           int32_t* __restrict__ views, int32_t* __restrict__ n_skip,
+                                                           const int32_t* __restrict__ cam_cls, int32_t* __restrict__ cls) {
     constexpr bool MOVING = NCOL == 5;
     __shared__ Shared sh;
     const int tid = (int)threadIdx.x, j = tid & 63, s = tid >> 6;
@@ -66,6 +72,7 @@ __global__ void __launch_bounds__(THREADS) rig_fuse_kernel(av_rig_cfg cfg, int n
     bool keep = false;
     int slot = 0, n_kept = 0;       // the row's place among its camera's kept rows; their number
     double qX = 0.0, qY = 0.0, qr = 0.0, qw = 0.0, qVX = 0.0, qVY = 0.0;
+    int qcls = 0;
     if (s < n_cams) {
         const size_t list = v * (size_t)n_cams + (size_t)s;
         int n = cam_n[list];
@@ -75,6 +82,7 @@ __global__ void __launch_bounds__(THREADS) rig_fuse_kernel(av_rig_cfg cfg, int n
             const double* row = cam_obs + (list * (size_t)ocap_in + (size_t)j) * NCOL;       // does not wait for the count's)
             const double x = row[0], y = row[1];
             qr = row[2];
+            if (cam_cls) qcls = cam_cls[list * (size_t)ocap_in + (size_t)j];
             keep = j < n && std::isfinite(x) && std::isfinite(y) && std::isfinite(qr) && qr > 0.0;
             double vx = 0.0, vy = 0.0;
             if constexpr (MOVING) {
@@ -105,7 +113,7 @@ __global__ void __launch_bounds__(THREADS) rig_fuse_kernel(av_rig_cfg cfg, int n
         // ---- the round's candidates: wave k hands over its kept rows, compacted in row order ----
         if (s == k) {
             if (keep) {
-                sh.cX[slot] = qX, sh.cY[slot] = qY, sh.cr[slot] = qr, sh.cw[slot] = qw;
+                sh.cX[slot] = qX, sh.cY[slot] = qY, sh.cr[slot] = qr, sh.cw[slot] = qw, sh.ccls[slot] = qcls;
                 if constexpr (MOVING) sh.cVX[slot] = qVX, sh.cVY[slot] = qVY;
             }
             sh.match[j] = -1;
@@ -171,10 +179,12 @@ __global__ void __launch_bounds__(THREADS) rig_fuse_kernel(av_rig_cfg cfg, int n
                     }
                     sh.r[mi] = fmax(sh.r[mi], r);
                     sh.views[mi] |= 1 << k;
+                    if (w > sh.best_w[mi]) sh.best_w[mi] = w, sh.cls[mi] = sh.ccls[j];
                 } else {
                     const int ni = m0 + __popcll(fm & ((1ull << j) - 1ull));             // < m0 + nc <= (k + 1) * 64 <= 512
                     sh.sw[ni] = w, sh.sx[ni] = w * x, sh.sy[ni] = w * y;
                     sh.X[ni] = x, sh.Y[ni] = y, sh.r[ni] = r, sh.views[ni] = 1 << k;
+                    sh.best_w[ni] = w, sh.cls[ni] = sh.ccls[j];
                     if constexpr (MOVING) {
                         const double cvx = sh.cVX[j], cvy = sh.cVY[j];
                         sh.svx[ni] = w * cvx, sh.svy[ni] = w * cvy, sh.VX[ni] = cvx, sh.VY[ni] = cvy;
@@ -199,6 +209,7 @@ __global__ void __launch_bounds__(THREADS) rig_fuse_kernel(av_rig_cfg cfg, int n
             o[4] = vf * sn + vl * s2;
         }
         if (views) views[v * (size_t)ocap + (size_t)tid] = sh.views[tid];
+        if (cls) cls[v * (size_t)ocap + (size_t)tid] = sh.cls[tid];
     }
     if (tid == 0) {
         n_obs[v] = m;
@@ -212,24 +223,41 @@ __global__ void __launch_bounds__(THREADS) rig_fuse_kernel(av_rig_cfg cfg, int n
 
 }  // namespace
 
+static int rig_fuse(const char* who, av_ctx* ctx, av_stream_t stream, const av_rig_cfg* cfg, int n_vehicles, int n_cams,
+                    const av_rig_mount* mounts, int ncol, int ocap_in, const double* cam_obs, const int32_t* cam_n,
+                    const double* plan_state, int ocap, double* obstacles, int32_t* n_obs, int32_t* views, int32_t* n_skip,
+                    const int32_t* cam_cls, int32_t* cls) {
+    AV_REQUIRE(ctx && cfg && mounts && cam_obs && cam_n && plan_state && obstacles && n_obs, AV_EINVAL, "%s: null argument", who);
+    AV_REQUIRE((cam_cls != nullptr) == (cls != nullptr), AV_EINVAL, "%s: cam_cls and cls are given together or not at all", who);
+    AV_REQUIRE(n_vehicles >= 1, AV_EINVAL, "%s: n_vehicles must be >= 1", who);
+    AV_REQUIRE(n_cams >= 1 && n_cams <= MAX_CAMS, AV_EINVAL, "%s: n_cams %d not in 1..%d", who, n_cams, MAX_CAMS);
+    AV_REQUIRE(ocap_in >= 1 && ocap_in <= MAX_IN, AV_EINVAL, "%s: ocap_in %d not in 1..%d", who, ocap_in, MAX_IN);
+    AV_REQUIRE(ncol == 3 || ncol == 5, AV_EINVAL, "%s: ncol %d is neither 3 (x, y, r) nor 5 (x, y, r, vx, vy)", who, ncol);
+    AV_REQUIRE(ocap >= n_cams * ocap_in, AV_EINVAL, "%s: ocap %d < n_cams * ocap_in = %d (no obstacle is ever dropped)", who, ocap,
+               n_cams * ocap_in);
+    AV_REQUIRE(std::isfinite(cfg->merge_scale) && std::isfinite(cfg->merge_min) && cfg->merge_scale >= 0.0 && cfg->merge_min >= 0.0,
+               AV_EINVAL, "%s: merge_scale and merge_min must be >= 0 and finite", who);
+    if (ncol == 5)
+        hipLaunchKernelGGL(rig_fuse_kernel<5>, dim3((unsigned)n_vehicles), dim3(THREADS), 0, as_stream(stream), *cfg, n_cams, mounts,
+                           ocap_in, cam_obs, cam_n, plan_state, ocap, obstacles, n_obs, views, n_skip, cam_cls, cls);
+    else
+        hipLaunchKernelGGL(rig_fuse_kernel<3>, dim3((unsigned)n_vehicles), dim3(THREADS), 0, as_stream(stream), *cfg, n_cams, mounts,
+                           ocap_in, cam_obs, cam_n, plan_state, ocap, obstacles, n_obs, views, n_skip, cam_cls, cls);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
 extern "C" int av_rig_fuse(av_ctx* ctx, av_stream_t stream, const av_rig_cfg* cfg, int n_vehicles, int n_cams,
                            const av_rig_mount* mounts, int ncol, int ocap_in, const double* cam_obs, const int32_t* cam_n,
                            const double* plan_state, int ocap, double* obstacles, int32_t* n_obs, int32_t* views, int32_t* n_skip) {
-    AV_REQUIRE(ctx && cfg && mounts && cam_obs && cam_n && plan_state && obstacles && n_obs, AV_EINVAL, "av_rig_fuse: null argument");
-    AV_REQUIRE(n_vehicles >= 1, AV_EINVAL, "av_rig_fuse: n_vehicles must be >= 1");
-    AV_REQUIRE(n_cams >= 1 && n_cams <= MAX_CAMS, AV_EINVAL, "av_rig_fuse: n_cams %d not in 1..%d", n_cams, MAX_CAMS);
-    AV_REQUIRE(ocap_in >= 1 && ocap_in <= MAX_IN, AV_EINVAL, "av_rig_fuse: ocap_in %d not in 1..%d", ocap_in, MAX_IN);
-    AV_REQUIRE(ncol == 3 || ncol == 5, AV_EINVAL, "av_rig_fuse: ncol %d is neither 3 (x, y, r) nor 5 (x, y, r, vx, vy)", ncol);
-    AV_REQUIRE(ocap >= n_cams * ocap_in, AV_EINVAL, "av_rig_fuse: ocap %d < n_cams * ocap_in = %d (no obstacle is ever dropped)", ocap,
-               n_cams * ocap_in);
-    AV_REQUIRE(std::isfinite(cfg->merge_scale) && std::isfinite(cfg->merge_min) && cfg->merge_scale >= 0.0 && cfg->merge_min >= 0.0,
-               AV_EINVAL, "av_rig_fuse: merge_scale and merge_min must be >= 0 and finite");
-    if (ncol == 5)
-        hipLaunchKernelGGL(rig_fuse_kernel<5>, dim3((unsigned)n_vehicles), dim3(THREADS), 0, as_stream(stream), *cfg, n_cams, mounts,
-                           ocap_in, cam_obs, cam_n, plan_state, ocap, obstacles, n_obs, views, n_skip);
-    else
-        hipLaunchKernelGGL(rig_fuse_kernel<3>, dim3((unsigned)n_vehicles), dim3(THREADS), 0, as_stream(stream), *cfg, n_cams, mounts,
-                           ocap_in, cam_obs, cam_n, plan_state, ocap, obstacles, n_obs, views, n_skip);
-    AV_LAUNCH_CHECK();
-    return AV_OK;
+    return rig_fuse("av_rig_fuse", ctx, stream, cfg, n_vehicles, n_cams, mounts, ncol, ocap_in, cam_obs, cam_n, plan_state, ocap,
+                    obstacles, n_obs, views, n_skip, nullptr, nullptr);
+}
+
+extern "C" int av_rig_fuse_cls(av_ctx* ctx, av_stream_t stream, const av_rig_cfg* cfg, int n_vehicles, int n_cams,
+                               const av_rig_mount* mounts, int ncol, int ocap_in, const double* cam_obs, const int32_t* cam_n,
+                               const int32_t* cam_cls, const double* plan_state, int ocap, double* obstacles, int32_t* n_obs,
+                               int32_t* views, int32_t* n_skip, int32_t* cls) {
+    return rig_fuse("av_rig_fuse_cls", ctx, stream, cfg, n_vehicles, n_cams, mounts, ncol, ocap_in, cam_obs, cam_n, plan_state, ocap,
+                    obstacles, n_obs, views, n_skip, cam_cls, cls);
 }

@@ -18,6 +18,9 @@
 // rows each lie nearest to their own track is done in one round.  (A first version ran the pass serially, one pair per iteration
 // with a workgroup-wide minimum: DESIGN.md section 7p has both timings.)  Births and the output compaction are ballots and prefix
 // counts over the waves.  float64, -ffp-contract=off: every operation rounded on its own.
+//
+// The class form (av_rig_track_cls) is the same kernel with an int32 lane beside the rows: a slot's first reserved word holds the
+// class of its latest classified row plus one, and the word travels with the slot's other integers.  The association never reads it.
 #include "rig_dev.h"
 
 #include <cmath>
@@ -28,7 +31,7 @@ namespace {
 
 constexpr int MAX_T = 512, MAX_IN = 512, MAX_WAVES = 8;
 constexpr int HDR_BYTES = 64;          // int32 hdr[16]: status, next id, frames, live
-constexpr int SLOT_BYTES = 96;         // int32 id, hits, misses, age, views, views_ever, 2 reserved; double x[4], p[3], r
+constexpr int SLOT_BYTES = 96;         // int32 id, hits, misses, age, views, views_ever, 2 reserved (the first: class + 1); double x[4], p[3], r
 static_assert(HDR_BYTES % 16 == 0 && SLOT_BYTES % 16 == 0, "slots are read and written 16 bytes at a time");
 
 __host__ __device__ inline size_t state_bytes(int tcap) { return (size_t)HDR_BYTES + (size_t)tcap * SLOT_BYTES; }
@@ -37,6 +40,7 @@ struct Shared {
     double X[MAX_T], Y[MAX_T], R[MAX_T];                                     // the slots, predicted
     double cX[MAX_IN], cY[MAX_IN], cR[MAX_IN], cVX[MAX_IN], cVY[MAX_IN];     // the kept rows, at their row index
     int32_t cViews[MAX_IN];
+    int32_t cCls[MAX_IN];                                                    // (av_rig_track_cls: the rows' classes)
     int32_t taken[MAX_T];                                                    // the slot takes no (further) row: free, or matched
     int32_t row_taken[MAX_IN];                                               // the row takes no (further) slot: not kept, or matched
     int32_t row_best[MAX_IN];                                                // a round's post: the slot row j would take, -1: none
@@ -86,7 +90,8 @@ __global__ void __launch_bounds__(MAX_T) rig_track_kernel(av_rig_track_cfg cfg, 
                                                          const double* __restrict__ plan_state, unsigned char* __restrict__ state,
                                                          int ocap_out, double* __restrict__ obstacles, int32_t* __restrict__ n_obs,
                                                          int32_t* __restrict__ obs_slot, int32_t* __restrict__ match,
-                                                         int32_t* __restrict__ n_skip, int32_t* __restrict__ n_drop) {
+                                                         int32_t* __restrict__ n_skip, int32_t* __restrict__ n_drop,
+                                                         const int32_t* __restrict__ cls_in, int32_t* __restrict__ cls_out) {
     constexpr bool MOVING = NCOL == 5;
     __shared__ Shared sh;
     const int tid = (int)threadIdx.x, lane = tid & 63, w = tid >> 6, nw = (int)blockDim.x >> 6;
@@ -99,14 +104,15 @@ __global__ void __launch_bounds__(MAX_T) rig_track_kernel(av_rig_track_cfg cfg, 
     const bool own = tid < tcap;                                             // this thread owns slot tid
     // ---- slot tid: load, predict, post ----
     int id = -1, hits = 0, misses = 0, age = 0, views = 0, views_ever = 0;
+    unsigned cls1 = 0;                                                       // the slot's first reserved word: class + 1, 0: none known
     double x = 0.0, y = 0.0, vx = 0.0, vy = 0.0, pa = 0.0, pb = 0.0, pc = 0.0, rad = 0.0;
     unsigned char* const mine = st + HDR_BYTES + (size_t)tid * SLOT_BYTES;   // (only dereferenced when own)
     if (own) {
         const int4 i0 = *reinterpret_cast<const int4*>(mine);
-        const int2 i1 = *reinterpret_cast<const int2*>(mine + 16);
+        const int4 i1 = *reinterpret_cast<const int4*>(mine + 16);
         const double2 d0 = *reinterpret_cast<const double2*>(mine + 32), d1 = *reinterpret_cast<const double2*>(mine + 48);
         const double2 d2 = *reinterpret_cast<const double2*>(mine + 64), d3 = *reinterpret_cast<const double2*>(mine + 80);
-        id = i0.x, hits = i0.y, misses = i0.z, age = i0.w, views = i1.x, views_ever = i1.y;
+        id = i0.x, hits = i0.y, misses = i0.z, age = i0.w, views = i1.x, views_ever = i1.y, cls1 = (unsigned)i1.z;
         x = d0.x, y = d0.y, vx = d1.x, vy = d1.y, pa = d2.x, pb = d2.y, pc = d3.x, rad = d3.y;
         if (id >= 0) {                                                       // x <- F x, P <- F P F^T + Q
             const double dt = cfg.dt, dt2 = dt * dt;
@@ -136,8 +142,9 @@ __global__ void __launch_bounds__(MAX_T) rig_track_kernel(av_rig_track_cfg cfg, 
             keep = keep && std::isfinite(zvx) && std::isfinite(zvy);
         }
         const int zviews = views_in ? views_in[v * (size_t)ocap_in + (size_t)tid] : 0;
+        const int zcls = cls_in ? cls_in[v * (size_t)ocap_in + (size_t)tid] : -1;
         if (keep) {
-            sh.cX[tid] = zx, sh.cY[tid] = zy, sh.cR[tid] = zr, sh.cViews[tid] = zviews;
+            sh.cX[tid] = zx, sh.cY[tid] = zy, sh.cR[tid] = zr, sh.cViews[tid] = zviews, sh.cCls[tid] = zcls;
             if constexpr (MOVING) sh.cVX[tid] = zvx, sh.cVY[tid] = zvy;
         }
         sh.row_taken[tid] = !keep;
@@ -189,11 +196,12 @@ __global__ void __launch_bounds__(MAX_T) rig_track_kernel(av_rig_track_cfg cfg, 
             rad = sh.cR[j];
             hits += 1, misses = 0;
             views = sh.cViews[j], views_ever |= views;
+            if (cls_in && sh.cCls[j] >= 0) cls1 = (unsigned)sh.cCls[j] + 1u;  // the latest observation wins; a row without a class leaves it
             if (match) match[v * (size_t)ocap_in + (size_t)j] = id;
         } else {
             misses += 1, views = 0;
             if (misses > cfg.max_age) {
-                id = -1, hits = misses = age = views_ever = 0;
+                id = -1, hits = misses = age = views_ever = 0, cls1 = 0u;
                 x = y = vx = vy = pa = pb = pc = rad = 0.0;
             }
         }
@@ -223,6 +231,7 @@ __global__ void __launch_bounds__(MAX_T) rig_track_kernel(av_rig_track_cfg cfg, 
         pa = cfg.p0_pos, pb = 0.0, pc = cfg.p0_vel;
         hits = 1, misses = 0, age = 0;
         views = views_ever = sh.cViews[j];
+        if (cls_in) cls1 = sh.cCls[j] >= 0 ? (unsigned)sh.cCls[j] + 1u : 0u;
     }
     // ---- the state back; the confirmed slots, compacted in slot order ----
     const bool live = own && id >= 0, conf = live && hits >= cfg.min_hits;
@@ -233,7 +242,7 @@ __global__ void __launch_bounds__(MAX_T) rig_track_kernel(av_rig_track_cfg cfg, 
     }
     if (own) {
         *reinterpret_cast<int4*>(mine) = make_int4(id, hits, misses, age);
-        *reinterpret_cast<int4*>(mine + 16) = make_int4(views, views_ever, 0, 0);
+        *reinterpret_cast<int4*>(mine + 16) = make_int4(views, views_ever, (int)cls1, 0);
         double2* const o = reinterpret_cast<double2*>(mine + 32);
         o[0] = make_double2(x, y), o[1] = make_double2(vx, vy), o[2] = make_double2(pa, pb), o[3] = make_double2(pc, rad);
     }
@@ -246,6 +255,7 @@ __global__ void __launch_bounds__(MAX_T) rig_track_kernel(av_rig_track_cfg cfg, 
         o[0] = x, o[1] = y, o[2] = rad;
         if constexpr (MOVING) o[3] = vx, o[4] = vy;
         if (obs_slot) obs_slot[v * (size_t)ocap_out + (size_t)out_row] = tid;
+        if (cls_out) cls_out[v * (size_t)ocap_out + (size_t)out_row] = (int)(cls1 - 1u);
     }
     if (tid == 0) {
         int n_live = 0, n_skipped = 0;
@@ -289,35 +299,51 @@ int av_rig_track_reset(av_ctx* ctx, av_stream_t stream, int n_vehicles, int tcap
     return AV_OK;
 }
 
-int av_rig_track(av_ctx* ctx, av_stream_t stream, const av_rig_track_cfg* cfg, int n_vehicles, int tcap, int ncol, int ocap_in,
+static int rig_track(const char* who, av_ctx* ctx, av_stream_t stream, const av_rig_track_cfg* cfg, int n_vehicles, int tcap, int ncol, int ocap_in,
                  const double* obs_in, const int32_t* n_in, const int32_t* views_in, const double* plan_state, void* state,
                  int ocap_out, double* obstacles, int32_t* n_obs, int32_t* obs_slot, int32_t* match, int32_t* n_skip,
-                 int32_t* n_drop) {
-    AV_REQUIRE(n_vehicles >= 1, AV_EINVAL, "av_rig_track: n_vehicles must be >= 1");
-    AV_REQUIRE(tcap_ok(tcap), AV_EINVAL, "av_rig_track: tcap %d not in 1..%d", tcap, MAX_T);
-    AV_REQUIRE(ncol == 3 || ncol == 5, AV_EINVAL, "av_rig_track: ncol %d is neither 3 (x, y, r) nor 5 (x, y, r, vx, vy)", ncol);
-    AV_REQUIRE(ocap_in >= 1 && ocap_in <= MAX_IN, AV_EINVAL, "av_rig_track: ocap_in %d not in 1..%d", ocap_in, MAX_IN);
-    AV_REQUIRE(ocap_out >= tcap, AV_EINVAL, "av_rig_track: ocap_out %d < tcap %d (every track may be confirmed)", ocap_out, tcap);
-    AV_REQUIRE(cfg, AV_EINVAL, "av_rig_track: null cfg");
+                 int32_t* n_drop, const int32_t* cls_in, int32_t* cls_out) {
+    AV_REQUIRE(n_vehicles >= 1, AV_EINVAL, "%s: n_vehicles must be >= 1", who);
+    AV_REQUIRE(tcap_ok(tcap), AV_EINVAL, "%s: tcap %d not in 1..%d", who, tcap, MAX_T);
+    AV_REQUIRE(ncol == 3 || ncol == 5, AV_EINVAL, "%s: ncol %d is neither 3 (x, y, r) nor 5 (x, y, r, vx, vy)", who, ncol);
+    AV_REQUIRE(ocap_in >= 1 && ocap_in <= MAX_IN, AV_EINVAL, "%s: ocap_in %d not in 1..%d", who, ocap_in, MAX_IN);
+    AV_REQUIRE(ocap_out >= tcap, AV_EINVAL, "%s: ocap_out %d < tcap %d (every track may be confirmed)", who, ocap_out, tcap);
+    AV_REQUIRE(cfg, AV_EINVAL, "%s: null cfg", who);
     const double* d = &cfg->dt;
     for (int i = 0; i < 8; ++i)
-        AV_REQUIRE(std::isfinite(d[i]) && d[i] >= 0.0, AV_EINVAL, "av_rig_track: cfg double %d (dt, q_accel, r_meas, r_range, p0_pos, "
-                   "p0_vel, gate_scale, gate_min) must be finite and >= 0", i);
-    AV_REQUIRE(cfg->dt > 0.0 && cfg->r_meas > 0.0, AV_EINVAL, "av_rig_track: cfg dt and r_meas must be > 0");
-    AV_REQUIRE(cfg->max_age >= 0 && cfg->min_hits >= 1, AV_EINVAL, "av_rig_track: cfg max_age must be >= 0 and min_hits >= 1");
-    AV_REQUIRE(ctx && obs_in && n_in && plan_state && state && obstacles && n_obs, AV_EINVAL, "av_rig_track: null argument");
+        AV_REQUIRE(std::isfinite(d[i]) && d[i] >= 0.0, AV_EINVAL, "%s: cfg double %d (dt, q_accel, r_meas, r_range, p0_pos, "
+                   "p0_vel, gate_scale, gate_min) must be finite and >= 0", who, i);
+    AV_REQUIRE(cfg->dt > 0.0 && cfg->r_meas > 0.0, AV_EINVAL, "%s: cfg dt and r_meas must be > 0", who);
+    AV_REQUIRE(cfg->max_age >= 0 && cfg->min_hits >= 1, AV_EINVAL, "%s: cfg max_age must be >= 0 and min_hits >= 1", who);
+    AV_REQUIRE(ctx && obs_in && n_in && plan_state && state && obstacles && n_obs, AV_EINVAL, "%s: null argument", who);
     const int most = tcap > ocap_in ? tcap : ocap_in;
     const unsigned threads = (unsigned)((most + 63) / 64 * 64);
     if (ncol == 5)
         hipLaunchKernelGGL(rig_track_kernel<5>, dim3((unsigned)n_vehicles), dim3(threads), 0, as_stream(stream), *cfg, tcap, ocap_in,
                            obs_in, n_in, views_in, plan_state, (unsigned char*)state, ocap_out, obstacles, n_obs, obs_slot, match, n_skip,
-                           n_drop);
+                           n_drop, cls_in, cls_out);
     else
         hipLaunchKernelGGL(rig_track_kernel<3>, dim3((unsigned)n_vehicles), dim3(threads), 0, as_stream(stream), *cfg, tcap, ocap_in,
                            obs_in, n_in, views_in, plan_state, (unsigned char*)state, ocap_out, obstacles, n_obs, obs_slot, match, n_skip,
-                           n_drop);
+                           n_drop, cls_in, cls_out);
     AV_LAUNCH_CHECK();
     return AV_OK;
+}
+
+int av_rig_track(av_ctx* ctx, av_stream_t stream, const av_rig_track_cfg* cfg, int n_vehicles, int tcap, int ncol, int ocap_in,
+                 const double* obs_in, const int32_t* n_in, const int32_t* views_in, const double* plan_state, void* state,
+                 int ocap_out, double* obstacles, int32_t* n_obs, int32_t* obs_slot, int32_t* match, int32_t* n_skip,
+                 int32_t* n_drop) {
+    return rig_track("av_rig_track", ctx, stream, cfg, n_vehicles, tcap, ncol, ocap_in, obs_in, n_in, views_in, plan_state, state,
+                     ocap_out, obstacles, n_obs, obs_slot, match, n_skip, n_drop, nullptr, nullptr);
+}
+
+int av_rig_track_cls(av_ctx* ctx, av_stream_t stream, const av_rig_track_cfg* cfg, int n_vehicles, int tcap, int ncol, int ocap_in,
+                     const double* obs_in, const int32_t* n_in, const int32_t* views_in, const int32_t* cls_in,
+                     const double* plan_state, void* state, int ocap_out, double* obstacles, int32_t* n_obs, int32_t* obs_slot,
+                     int32_t* match, int32_t* n_skip, int32_t* n_drop, int32_t* cls_out) {
+    return rig_track("av_rig_track_cls", ctx, stream, cfg, n_vehicles, tcap, ncol, ocap_in, obs_in, n_in, views_in, plan_state, state,
+                     ocap_out, obstacles, n_obs, obs_slot, match, n_skip, n_drop, cls_in, cls_out);
 }
 
 }  // extern "C"

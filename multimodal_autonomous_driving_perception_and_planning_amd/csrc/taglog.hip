@@ -149,11 +149,17 @@ __global__ void __launch_bounds__(256) tags_pack_kernel(int n_frames, const av_m
         m |= 1ull << AV_TAG_HAS_INTERACTION;
         const int risk = isum[f].overall_risk;
         if (risk >= 1 && risk <= 3) m |= 1ull << (AV_TAG_RISK + risk - 1);
-        int n = snap_n[f];
-        n = n < 0 ? 0 : (n > tcap ? tcap : n);                                     // tcap == 64: one round
-        if (lane < n) {
-            const av_interaction_row& r = irows[f * (size_t)tcap + lane];
-            if (r.type >= 0 && r.type < 13 && r.confidence > 0.5) hi |= 1u << (AV_TAG_INTERACTION - 32 + r.type);
+        int n = tcap;                                                              // av_tags_pack_slots: every row
+        if (snap_n) {
+            n = snap_n[f];
+            n = n < 0 ? 0 : (n > tcap ? tcap : n);
+        }
+        for (int b = 0; b < n; b += 64) {                                          // (av_tags_pack's tcap is 64: one round)
+            const int i = b + lane;
+            if (i < n) {
+                const av_interaction_row& r = irows[f * (size_t)tcap + i];
+                if (r.type >= 0 && r.type < 13 && r.confidence > 0.5) hi |= 1u << (AV_TAG_INTERACTION - 32 + r.type);
+            }
         }
     }
     lo = wave_or_u32(lo);
@@ -631,6 +637,22 @@ extern "C" int av_tags_pack(av_ctx* ctx, av_stream_t stream, int n_streams, int 
     hipLaunchKernelGGL(tags_pack_kernel, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, as_stream(stream), (int)frames, maneuver,
                        inter_rows, inter_summary, snap_n, tcap, scene, det_n, det_cls, max_det, elem_table, n_elem,
                        words(out_mask), out_speed);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
+extern "C" int av_tags_pack_slots(av_ctx* ctx, av_stream_t stream, int n_streams, int n_frames, const av_maneuver_row* maneuver,
+                                  const av_interaction_row* inter_rows, const av_interaction_summary* inter_summary, int tcap,
+                                  uint64_t* out_mask, double* out_speed) {
+    AV_REQUIRE(n_streams > 0 && n_frames > 0, AV_EINVAL, "av_tags_pack_slots: n_streams and n_frames must be > 0");
+    AV_REQUIRE((inter_rows != nullptr) == (inter_summary != nullptr), AV_EINVAL,
+               "av_tags_pack_slots: inter_rows and inter_summary are given together or not at all");
+    AV_REQUIRE(!inter_rows || (tcap >= 1 && tcap <= 512), AV_EINVAL, "av_tags_pack_slots: tcap %d not in 1..512", tcap);
+    const long long frames = (long long)n_streams * n_frames;
+    AV_REQUIRE(frames <= 0x7fffffffll, AV_EINVAL, "av_tags_pack_slots: n_streams * n_frames does not fit an int");
+    AV_REQUIRE(ctx && out_mask && out_speed, AV_EINVAL, "av_tags_pack_slots: null argument");
+    hipLaunchKernelGGL(tags_pack_kernel, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, as_stream(stream), (int)frames, maneuver,
+                       inter_rows, inter_summary, nullptr, tcap, nullptr, nullptr, nullptr, 0, nullptr, 0, words(out_mask), out_speed);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }

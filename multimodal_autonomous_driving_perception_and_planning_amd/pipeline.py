@@ -557,10 +557,13 @@ class HotLoop:
         self.ref_paths, self.n_ref = paths, n_ref
         self._drop_graphs()
 
-    def enqueue_obstacles(self, stream=None):
+    def enqueue_obstacles(self, stream=None, obs_cls=None):
         """obstacles="tracks" / "moving_tracks" / "filtered_tracks": the window's snapshot tables and start states (and, filtered,
         self.track_filt) -> self.obstacles / self.n_obs (av_track_obstacles / _moving / _filtered); call where the tracker's, the
-        track filter's and the Kalman filter's outputs are complete (after the join)."""
+        track filter's and the Kalman filter's outputs are complete (after the join).  obs_cls (a loop with a calibration only):
+        int32 [S, W, tcap], filled with the class of the track behind every obstacle row (av_track_obstacles_ground_cls)."""
+        if obs_cls is not None and self.ground is None:
+            raise RuntimeError("enqueue_obstacles(obs_cls=...) needs a loop with a calibration")
         if self._obs_mode not in ("tracks", "moving_tracks", "filtered_tracks"):
             raise RuntimeError('enqueue_obstacles needs HotLoop(obstacles="tracks"), "moving_tracks" or "filtered_tracks"')
         if self.ground is not None:
@@ -569,7 +572,9 @@ class HotLoop:
                     nat.ptr(self.track_filt) if mode == 2 else None, nat.ptr(self.plan_state), self.tcap, nat.ptr(self.obstacles),
                     nat.ptr(self.n_obs), nat.ptr(self.n_off))
             head = (self.ctx.handle, stream or self._s, C.byref(self.ocfg), nat.ptr(self.ground))
-            if self.lens is not None:
+            if obs_cls is not None:
+                nat.check(self.L.av_track_obstacles_ground_cls(*head, nat.ptr(self.lens), *tail, nat.ptr(obs_cls)))
+            elif self.lens is not None:
                 nat.check(self.L.av_track_obstacles_ground_lens(*head, nat.ptr(self.lens), *tail))
             else:
                 nat.check(self.L.av_track_obstacles_ground(*head, *tail))
@@ -1334,23 +1339,29 @@ class RigLoop:
 
     _OUT_OF_SCOPE = {"fused_step": "the one-launch step plans without obstacles", "overlap": "the overlapped loop plans without obstacles",
                      "graph": "graph capture of a RigLoop is not supported", "graphs": "graph capture of a RigLoop is not supported",
-                     "tags": "the taggers describe one camera, not a rig", "tag_capacity": "the taggers describe one camera, not a rig",
-                     "tag_columns": "the taggers describe one camera, not a rig", "view": "the annotated views describe one camera, not a rig",
+                     "view": "the annotated views describe one camera, not a rig",
                      "views": "the annotated views describe one camera, not a rig"}
 
     def __init__(self, n_vehicles, rig, h=720, w=1280, model="random:0", precision="fp16", dcap=64, obstacles="moving_tracks",
                  class_map="reference", lane_camera=0, fuse_kw=None, tracker_kw=None, kf_kw=None, planner_kw=None, obstacle_kw=None,
-                 track_filter_kw=None, names=None, device=0, track=False, rig_track_kw=None, **other):
+                 track_filter_kw=None, names=None, device=0, track=False, rig_track_kw=None, tags=None, tag_capacity=4096,
+                 tag_columns=False, **other):
         """rig: a perception.CameraRig.  obstacles: "moving_tracks", "filtered_tracks" or "tracks", CameraLoop's modes (a rig
         without obstacles has nothing to fuse).  lane_camera: the index of the camera whose lane fit is the vehicle's reference path
         (av_lane_paths_ground through rig.vehicle_calibration(lane_camera)), None for no path; its mount may not be yawed beyond
         +-pi/2, since a path behind the vehicle is none.  fuse_kw: av_rig_cfg's merge_scale and merge_min (1.0, 1.0 m).  Everything
-        else is CameraLoop's; kf_kw and planner_kw go to the ego loop.  The one-launch step, the overlapped loop, graph capture, tags
+        else is CameraLoop's; kf_kw and planner_kw go to the ego loop.  The one-launch step, the overlapped loop, graph capture
         and the per-camera annotated views are refused by name; the rig's own picture is enqueue_surround_view().
         track=True: a tracking.RigTracker follows the fused lists (av_rig_track behind av_rig_fuse, on the ego stream) and the
         ego loop plans around its confirmed tracks -- ids that persist across frames and cameras, coasting through the frames in
         which no camera sees an object.  rig_track_kw: RigTracker's settings (av_rig_track_cfg's fields; dt defaults to the ego
-        Kalman filter's) and tcap (default min(512, K * the cameras' tcap))."""
+        Kalman filter's) and tcap (default min(512, K * the cameras' tcap)).
+        tags="motion" (with track=True only: the rig's taggers read the vehicle-frame tracks): every step logs one tag mask per
+        vehicle into self.tag_log (a TagLog of tag_capacity frames per vehicle on the ego stream; tag_columns: with the per-frame
+        records), with no host round trip -- the class of every track travels beside the obstacle rows through the cameras' lists,
+        the fuse and the tracker (the _cls entry points), the maneuver tagger runs on the ego filter's output with the lane
+        camera's offset, and, when class_map is the reference map (CameraLoop's rule), av_rig_interact tags the tracks
+        (self.tagger, a tagging.RigInteractionDetector).  tags="all" is refused: the scene classifier describes one camera."""
         from .perception.calibration import CameraRig, ground_table
         from .tracking.rig_tracker import RigTracker, check_shape, rig_track_cfg
         for k in other:
@@ -1391,6 +1402,14 @@ class RigLoop:
                 if isinstance(track_tcap, bool) or not isinstance(track_tcap, (int, np.integer)):
                     raise ValueError("RigLoop: rig_track_kw's tcap is an integer")
                 check_shape(V, track_tcap, 3)
+        if tags not in (None, "motion", "all"):
+            raise ValueError('RigLoop: tags is None or "motion"')
+        if tags == "all":
+            raise ValueError('RigLoop: tags="all" is out of scope (the scene classifier describes one camera, not a rig)')
+        if tags is not None and not track:
+            raise ValueError("RigLoop: tags need track=True: the rig's taggers read the vehicle-frame tracks")
+        if tags is not None and (isinstance(tag_capacity, bool) or not isinstance(tag_capacity, (int, np.integer)) or tag_capacity < 1):
+            raise ValueError("RigLoop: tag_capacity is an integer >= 1")
         self.V, self.K, self.rig, self.h, self.w, self.lane_camera = V, K, rig, h, w, lane_camera
         self.cams = CameraLoop(V * K, h=h, w=w, model=model, precision=precision, dcap=dcap, obstacles=obstacles, class_map=class_map,
                                device=device, tracker_kw=tracker_kw, planner_kw=planner_kw, obstacle_kw=obstacle_kw, names=names,
@@ -1432,6 +1451,20 @@ class RigLoop:
         self.surround_view = self.surround_cover = None     # enqueue_surround_view
         self._surround = self._surround_key = self._surround_ids = None
         self._stepped = False
+        self.tags, self.tag_log, self.tagger = tags, None, None
+        if tags is not None:
+            from .perception.detector import ObjectDetector
+            from .tagging.rig_interaction_detector import RigInteractionDetector
+            from .tagging.tag_log import TagLog
+            # the class lanes beside the cameras' lists and the fused list (the tracker holds its own, tracker.cls)
+            self.cam_cls = torch.full((V * K, 1, self.tcap), -1, dtype=i32, device=d)
+            self.fused_cls = torch.full((V, K * self.tcap), -1, dtype=i32, device=d)
+            cm = self.cams.class_map
+            if isinstance(cm, np.ndarray) and np.array_equal(cm, reference_class_map(self.cams.cam.yolo.names)):
+                self.tagger = RigInteractionDetector(V, self.tracker.tcap, class_names=ObjectDetector.CLASSES, ctx=self.ego.ctx,
+                                                     dt=float(self.ego.kcfg.dt), min_hits=int(self.tracker.cfg.min_hits))
+            self.tag_log = TagLog(V, int(tag_capacity), device=d.index, ctx=self.ego.ctx, stream=self.ego.stream,
+                                  columns=bool(tag_columns))
         torch.cuda.current_stream(d).synchronize()          # the buffers are filled before the loops' streams touch them
 
     def load_measurements(self, z):
@@ -1440,8 +1473,15 @@ class RigLoop:
 
     def enqueue_fuse(self, stream=None):
         """The cameras' lists (self.cams.hot.obstacles / n_obs) and the ego start states -> self.obstacles / n_obs / views / n_skip
-        (av_rig_fuse); call behind the cameras' enqueue_obstacles and the ego's enqueue_kf."""
+        (av_rig_fuse); call behind the cameras' enqueue_obstacles and the ego's enqueue_kf.  With tags also self.cam_cls ->
+        self.fused_cls (av_rig_fuse_cls)."""
         hot, ego = self.cams.hot, self.ego
+        if self.tags is not None:
+            nat.check(self.L.av_rig_fuse_cls(ego.ctx.handle, stream or ego._s, C.byref(self.fcfg), self.V, self.K, nat.ptr(self.mounts),
+                                             self.cols, self.tcap, nat.ptr(hot.obstacles), nat.ptr(hot.n_obs), nat.ptr(self.cam_cls),
+                                             nat.ptr(ego.plan_state), self.K * self.tcap, nat.ptr(self.obstacles), nat.ptr(self.n_obs),
+                                             nat.ptr(self.views), nat.ptr(self.n_skip), nat.ptr(self.fused_cls)))
+            return
         nat.check(self.L.av_rig_fuse(ego.ctx.handle, stream or ego._s, C.byref(self.fcfg), self.V, self.K, nat.ptr(self.mounts), self.cols,
                                      self.tcap, nat.ptr(hot.obstacles), nat.ptr(hot.n_obs), nat.ptr(ego.plan_state), self.K * self.tcap,
                                      nat.ptr(self.obstacles), nat.ptr(self.n_obs), nat.ptr(self.views), nat.ptr(self.n_skip)))
@@ -1451,7 +1491,22 @@ class RigLoop:
         n_skip / n_drop (av_rig_track); call behind enqueue_fuse on the same stream."""
         if self.tracker is None:
             raise RuntimeError("enqueue_rig_track needs RigLoop(track=True)")
-        self.tracker.update(self.obstacles, self.n_obs, self.ego.plan_state, views=self.views, stream=stream or self.ego._s)
+        self.tracker.update(self.obstacles, self.n_obs, self.ego.plan_state, views=self.views, stream=stream or self.ego._s,
+                            cls=self.fused_cls if self.tags is not None else None)
+
+    def enqueue_tags(self, stream=None):
+        """tags="motion": the maneuver tagger on the ego filter's output (with the lane camera's offset), the rig tagger on the
+        tracker's state, and one mask (and record) per vehicle into self.tag_log; call behind enqueue_rig_track and
+        enqueue_lane_paths on the same stream."""
+        if self.tags is None:
+            raise RuntimeError('enqueue_tags needs RigLoop(track=True, tags="motion")')
+        ego, s = self.ego, stream or self.ego._s
+        with torch.cuda.stream(ego._torch_stream(stream)):      # the maneuver stage's buffers, made at the first call, are filled there
+            ego.enqueue_maneuver(stream=s, lane_offset=self.lane_offset)
+        rows = summary = None
+        if self.tagger is not None:
+            rows, summary = self.tagger.detect(self.tracker, ego.plan_state, stream=s)
+        self.tag_log.pack_and_append(1, maneuver=ego.maneuver, inter_rows=rows, inter_summary=summary, stream=s)
 
     def enqueue_lane_paths(self, stream=None):
         """The lane camera's fits, gathered on the device, and the ego start states -> self.ref_paths / n_ref / lane_offset
@@ -1486,7 +1541,8 @@ class RigLoop:
         hot.enqueue_track(s)
         if hot.track_filter is not None:
             hot.enqueue_track_filter(s)
-        hot.enqueue_obstacles(s)                # hot.plan_state is zero: every list in its camera's own road frame
+        # hot.plan_state is zero: every list in its camera's own road frame
+        hot.enqueue_obstacles(s, obs_cls=self.cam_cls if self.tags is not None else None)
         ego.enqueue_kf()
         self.enqueue_fuse()
         if self.tracker is not None:
@@ -1494,6 +1550,8 @@ class RigLoop:
         if self.lane_camera is not None:
             self.enqueue_lane_paths()
         ego.enqueue_plan_each()
+        if self.tags is not None:
+            self.enqueue_tags()
         self._stepped = True
         if sync:
             self.synchronize()
@@ -1552,7 +1610,10 @@ class RigLoop:
         each obstacle row, -1 past n_obs), match [V, K * tcap] (the id each fused row went to), n_drop [V] and rig_tracks
         (RigTracker.tracks())) plus
         cam_obstacles [V, K, tcap, cols], cam_n_obs [V, K], n_off [V, K] (the cameras' own lists), views [V, K * tcap] (the mask of the
-        cameras that saw each fused obstacle), n_skip [V] and, with a lane camera, ref_paths [V, 50, 2], n_ref [V], lane_offset [V]."""
+        cameras that saw each fused obstacle), n_skip [V] and, with a lane camera, ref_paths [V, 50, 2], n_ref [V], lane_offset [V].
+        With tags: track_cls [V, tcap] and fused_cls [V, K * tcap] (the class id behind each tracked / fused row, -1 past the count),
+        interactions (one tagging.InteractionTags per vehicle) and interaction_summary (av_interaction_summary [V]); the last two are
+        None when class_map is not the reference map."""
         self.synchronize()
         hot, V, K = self.cams.hot, self.V, self.K
         out = self.ego.results()
@@ -1569,6 +1630,16 @@ class RigLoop:
             written = np.arange(t.tcap)[None, :] < n[:, None]
             out["track_ids"] = np.where(written, np.take_along_axis(out["rig_tracks"]["id"], np.where(written, slot, 0), axis=1), -1)
             out["match"], out["n_drop"] = t.match.cpu().numpy(), t.n_drop.cpu().numpy()
+            if self.tags is not None:
+                # the class behind each tracked / fused obstacle row, -1 past the counts (and for a track whose class is not known)
+                out["track_cls"] = np.where(written, t.cls.cpu().numpy(), -1)
+                fused = np.arange(K * self.tcap)[None, :] < out["fused_n_obs"].reshape(V, 1)
+                out["fused_cls"] = np.where(fused, self.fused_cls.cpu().numpy(), -1)
+                out["interactions"] = out["interaction_summary"] = None
+                if self.tagger is not None:
+                    out["interactions"] = self.tagger.results()
+                    out["interaction_summary"] = (self.tagger.summary.cpu().numpy().reshape(V, -1)
+                                                  .view(np.dtype(nat.INTERACTION_SUMMARY_FIELDS)).reshape(V))
         if self.lane_camera is not None:
             out["ref_paths"], out["n_ref"] = self.ref_paths.cpu().numpy(), self.n_ref.cpu().numpy()
             out["lane_offset"] = self.lane_offset.cpu().numpy()

@@ -171,7 +171,9 @@ class TagLog:
                         det_n=None, det_cls=None, elem_table=None, stream=None):
         """The taggers' rows of [S][window] frames (device tensors, uint8 views of the row structs as the stages leave them; each
         group may be None) -> masks and speeds (av_tags_pack) and, for a log with columns, records (av_tags_cols) -> the log.  The
-        window's masks, speeds and records stay in self.win_mask / win_speed / win_cols."""
+        window's masks, speeds and records stay in self.win_mask / win_speed / win_cols.  Interaction rows with snap_n=None are
+        slot-indexed ([S][window][tcap] with any tcap in 1 .. 512, av_rig_interact's) and go through av_tags_pack_slots, which takes
+        no scene group."""
         W = int(window)
         if self._win is None or self._win[0].shape[1] != W:
             self._win = (torch.empty(self.S, W, dtype=torch.int64, device=self.dev),
@@ -182,9 +184,15 @@ class TagLog:
         n_elem = int(elem_table.numel()) if elem_table is not None else 0
         tcap = int(inter_rows.shape[2]) if inter_rows is not None else 0
         st = self._s(stream)
-        nat.check(self.L.av_tags_pack(self.ctx.handle, st, self.S, W, nat.ptr(maneuver), nat.ptr(inter_rows), nat.ptr(inter_summary),
-                                      nat.ptr(snap_n), tcap, nat.ptr(scene_rows), nat.ptr(det_n), nat.ptr(det_cls), max_det,
-                                      nat.ptr(elem_table), n_elem, nat.ptr(wm), nat.ptr(wv)))
+        if inter_rows is not None and snap_n is None:
+            if scene_rows is not None or det_n is not None or det_cls is not None or elem_table is not None:
+                raise ValueError("slot-indexed interaction rows (snap_n=None) come without a scene group")
+            nat.check(self.L.av_tags_pack_slots(self.ctx.handle, st, self.S, W, nat.ptr(maneuver), nat.ptr(inter_rows),
+                                                nat.ptr(inter_summary), tcap, nat.ptr(wm), nat.ptr(wv)))
+        else:
+            nat.check(self.L.av_tags_pack(self.ctx.handle, st, self.S, W, nat.ptr(maneuver), nat.ptr(inter_rows), nat.ptr(inter_summary),
+                                          nat.ptr(snap_n), tcap, nat.ptr(scene_rows), nat.ptr(det_n), nat.ptr(det_cls), max_det,
+                                          nat.ptr(elem_table), n_elem, nat.ptr(wm), nat.ptr(wv)))
         if self.columns:
             nat.check(self.L.av_tags_cols(self.ctx.handle, st, self.S, W, nat.ptr(maneuver), nat.ptr(inter_summary),
                                           nat.ptr(scene_rows), nat.ptr(wc)))

@@ -73,6 +73,7 @@ class RigTracker:
         self.n_skip = torch.zeros(self.V, dtype=i32, device=d)
         self.n_drop = torch.zeros(self.V, dtype=i32, device=d)
         self.match = None                                   # int32 [V, ocap_in], sized by the first update
+        self.cls = torch.full((self.V, self.tcap), -1, dtype=i32, device=d)     # update(cls=...): the class behind each output row
         self.reset()
 
     @staticmethod
@@ -83,13 +84,16 @@ class RigTracker:
         """Every slot free, the next id 1, status 0 (stream-ordered)."""
         nat.check(self.L.av_rig_track_reset(self.ctx.handle, self._stream(stream), self.V, self.tcap, nat.ptr(self.state)))
 
-    def update(self, obstacles, n_obs, plan_state, views=None, stream=None):
+    def update(self, obstacles, n_obs, plan_state, views=None, stream=None, cls=None):
         """One frame.  obstacles: float64 [V, ocap_in, ncol] (or av_rig_fuse's [V, 1, ocap_in, ncol]), n_obs int32 [V] (or [V, 1]),
         plan_state float64 [V, 4] (or [V, 1, 4]), views int32 [V, ocap_in] or None: contiguous device tensors.  Fills
         self.obstacles [V, tcap, ncol] / n_obs [V] (the confirmed tracks, coasting ones at their predicted place), obs_slot
         [V, tcap] (the slot behind each row), match [V, ocap_in] (the id each input row went to; -1: skipped, -2: dropped for want
         of a slot), n_skip and n_drop [V]; rows past a count keep what they held.  Enqueued on `stream` (a torch stream or a raw
-        handle; default: the current one).  Returns self.obstacles, self.n_obs."""
+        handle; default: the current one).  cls: int32 [V, ocap_in], the rows' class ids (av_rig_fuse_cls's), or None: with it the
+        tracks carry the class of their latest classified row (av_rig_track_cls) and self.cls [V, tcap] holds the class behind each
+        output row, -1 for none known; without it the call is av_rig_track and self.cls is not written.  Returns self.obstacles,
+        self.n_obs."""
         import torch
         f64, i32 = torch.float64, torch.int32
         ok = lambda t, dt: torch.is_tensor(t) and t.is_cuda and t.is_contiguous() and t.dtype == dt          # noqa: E731
@@ -106,8 +110,17 @@ class RigTracker:
             raise ValueError("RigTracker.update: plan_state is a contiguous float64 device tensor [V, 4]")
         if views is not None and not (ok(views, i32) and tuple(views.shape) == (self.V, ocap_in)):
             raise ValueError("RigTracker.update: views is None or a contiguous int32 device tensor [V, ocap_in]")
+        if cls is not None and not (ok(cls, i32) and tuple(cls.shape) == (self.V, ocap_in)):
+            raise ValueError("RigTracker.update: cls is None or a contiguous int32 device tensor [V, ocap_in]")
         if self.match is None or self.match.shape[1] != ocap_in:
             self.match = torch.full((self.V, ocap_in), -1, dtype=i32, device=self.dev)
+        if cls is not None:
+            nat.check(self.L.av_rig_track_cls(self.ctx.handle, self._stream(stream), C.byref(self.cfg), self.V, self.tcap, self.ncol,
+                                              ocap_in, nat.ptr(obstacles), nat.ptr(n_obs), nat.ptr(views), nat.ptr(cls),
+                                              nat.ptr(plan_state), nat.ptr(self.state), self.tcap, nat.ptr(self.obstacles),
+                                              nat.ptr(self.n_obs), nat.ptr(self.obs_slot), nat.ptr(self.match), nat.ptr(self.n_skip),
+                                              nat.ptr(self.n_drop), nat.ptr(self.cls)))
+            return self.obstacles, self.n_obs
         nat.check(self.L.av_rig_track(self.ctx.handle, self._stream(stream), C.byref(self.cfg), self.V, self.tcap, self.ncol, ocap_in,
                                       nat.ptr(obstacles), nat.ptr(n_obs), nat.ptr(views), nat.ptr(plan_state), nat.ptr(self.state),
                                       self.tcap, nat.ptr(self.obstacles), nat.ptr(self.n_obs), nat.ptr(self.obs_slot),
@@ -130,10 +143,11 @@ class RigTracker:
     def tracks(self):
         """Host view of the state: structured array [V, tcap] with the slot's fields (id, hits, misses, age, views, views_ever,
         reserved, x[4], p[3], r) and pos_sigma = sqrt(2 P_pos), vel_sigma = sqrt(2 P_vel), the two uncertainties VehicleState
-        carries.  id -1: a free slot.  Synchronises."""
+        carries, and cls, the track's class id (reserved[0] - 1; -1: none known).  id -1: a free slot.  Synchronises."""
         raw = self._host_state()[:, nat.RIG_TRACK_HDR_BYTES:].copy().view(np.dtype(nat.RIG_TRACK_SLOT_FIELDS)).reshape(self.V, self.tcap)
-        out = np.zeros(raw.shape, np.dtype(nat.RIG_TRACK_SLOT_FIELDS + [("pos_sigma", "<f8"), ("vel_sigma", "<f8")]))
+        out = np.zeros(raw.shape, np.dtype(nat.RIG_TRACK_SLOT_FIELDS + [("pos_sigma", "<f8"), ("vel_sigma", "<f8"), ("cls", "<i4")]))
         for name in raw.dtype.names:
             out[name] = raw[name]
         out["pos_sigma"], out["vel_sigma"] = np.sqrt(2.0 * raw["p"][..., 0]), np.sqrt(2.0 * raw["p"][..., 2])
+        out["cls"] = raw["reserved"][..., 0] - 1
         return out
