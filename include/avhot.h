@@ -1609,6 +1609,124 @@ int av_hot_step_seq(av_ctx* ctx, av_stream_t stream, const av_step_loop* loop, c
 int av_hot_steps_seq(av_ctx* ctx, int depth, const av_stream_t* streams, const av_step_loop* loop, const av_step_set* sets,
                      const double* z_steps, void* wire_steps, int stream0, int frame0, int32_t* seq_flags, int seq0, int n_steps);
 
+/* ---- Ground odometry (opt-in): the ego measurement of av_kf_step from the road pixels of two consecutive frames -----------------
+ * The reference synthesises z = [x, y, vx, vy] on the host (video_loader.py:166-205: generate_ego_motion); recorded video has no
+ * such array.  Four stages, each an entry of its own, and av_egoflow_update, which enqueues all four for a loop.
+ *
+ * Geometry: a gray bird's-eye patch uint8 [gh][gw] per camera, av_ground_warp's: pixel (r, c) shows the road point
+ *   f = f_far - ((double)r + 0.5) * m_per_px;   l = (((double)c + 0.5) - (double)gw / 2.0) * m_per_px
+ * Tiles of T x T pixels (T = tile) with a search range of R pixels (R = search): tile (ty, tx) has its first pixel at
+ *   y0 = R + ty * T, x0 = R + tx * T;   tiles_y = (gh - 2 R) / T, tiles_x = (gw - 2 R) / T (integer division),
+ *   n_tiles = tiles_y * tiles_x, tile index = ty * tiles_x + tx; its centre is the road point
+ *   f = f_far - ((double)y0 + (double)T / 2.0) * m_per_px;   l = (((double)x0 + (double)T / 2.0) - (double)gw / 2.0) * m_per_px
+ * Checked by every entry (AV_EINVAL, before any launch): gh, gw in 1 .. 4096; T a multiple of 4, 4 <= T <= 32; 1 <= R <= 15; at least one
+ * tile fits (tiles_y, tiles_x >= 1) and n_tiles <= 65535; m_per_px > 0 and finite, f_far finite; frame_rate > 0 and finite;
+ * min_texture >= 0; 0 <= gate_px <= 2 R; inlier_px > 0 and finite; min_inliers >= 1; n_cams in 1 .. 65535. */
+typedef struct {
+    int32_t gh, gw;            /* patch rows, columns (256, 256) */
+    int32_t tile, search;      /* T (16), R (12) */
+    double f_far, m_per_px;    /* row 0's far edge in metres ahead; metres per patch pixel (0.1) */
+    double frame_rate;         /* frames / s (30): z's velocity = displacement * frame_rate */
+    int32_t min_texture;       /* a tile with less texture is not accepted (2 T T) */
+    int32_t gate_px;           /* the vote's gate (3) */
+    double inlier_px;          /* residual limit of the fit, patch pixels (1.0) */
+    int32_t min_inliers;       /* fewer inliers: not valid (8) */
+    int32_t reserved;          /* 0 */
+} av_egoflow_cfg;              /* 64 bytes */
+
+/* One row per tile.  flags bit 0: accepted (match), bit 1: live (match), bit 2: inside the vote's gate (solve), bit 3: inlier of the
+ * final fit (solve).  A tile that is not live has every other field of the match 0 except f, l. */
+#define AV_EGOFLOW_ACCEPTED 1
+#define AV_EGOFLOW_LIVE 2
+#define AV_EGOFLOW_GATED 4
+#define AV_EGOFLOW_INLIER 8
+typedef struct {
+    int32_t flags;
+    int32_t dy, dx;            /* the best candidate, patch pixels */
+    int32_t sad;               /* its sum of absolute differences */
+    int32_t texture;
+    int32_t reserved;          /* 0 */
+    double sub_dy, sub_dx;     /* sub-pixel offsets to add to dy, dx; in [-0.5, 0.5], 0 where not defined */
+    double f, l;               /* the tile's centre, metres */
+} av_egoflow_tile;             /* 56 bytes */
+
+typedef struct {
+    double t_f, t_l, omega;    /* the camera's motion between the two frames in the PREVIOUS frame's road frame: metres, radians */
+    double rms;                /* of the inliers' residuals, metres */
+    int32_t n_accepted, n_gated, n_inliers, valid;
+    int32_t vote_dy, vote_dx;  /* the vote's mode (0, 0 where no tile is accepted) */
+    int32_t reserved[2];
+} av_egoflow_motion;           /* 64 bytes */
+
+/* Persistent per-camera state (device; settable from the host between calls): the pose of the camera's ground point in the world
+ * and the number of frames seen since the reset.  All zero = reset. */
+typedef struct {
+    double x, y, psi;
+    int32_t frames, reserved;
+} av_egoflow_state;            /* 32 bytes */
+
+int av_egoflow_tiles(const av_egoflow_cfg* cfg, int* tiles_y, int* tiles_x);   /* host only: the checks above and the tile grid */
+
+/* Stage 1, patch: per patch pixel the road point as above, then through ground[k].ginv exactly av_ground_warp's position rule (U, V,
+ * D, u, v, tu, tv and its two refusals) and its bilinear sample (b, g, r); then the lane front end's gray
+ *   gray = (1868 b + 9617 g + 4899 r + 8192) >> 14
+ * A pixel the position rule refuses is INVALID: its gray is 0 and its validity bit is 0.
+ *   ground DEVICE [n_cams]; bgr [n_cams][h][w][3] RECTIFIED frames; patch [n_cams][gh][gw];
+ *   valid uint32 [n_cams][gh][vw], vw = (gw + 31) / 32: bit (c & 31) of word c >> 5 is pixel (r, c)'s; bits at c >= gw are 0 */
+int av_egoflow_patch(av_ctx* ctx, av_stream_t stream, const av_egoflow_cfg* cfg, const av_ground_cfg* ground, int n_cams, int h,
+                     int w, const uint8_t* bgr, uint8_t* patch, uint32_t* valid);
+
+/* Stage 2, match (the hot kernel): cur, prev [n_cams][gh][gw] gray patches (any bytes: hand-made ones are fine), valid as above,
+ * tiles [n_cams][n_tiles].  Per tile, integers throughout:
+ *   live     = every pixel of rows y0 - R .. y0 + T + R - 1, columns x0 - R .. x0 + T + R - 1 is valid
+ *   SAD(dy, dx) = sum over i, j in 0 .. T-1 of |cur[y0+i][x0+j] - prev[y0+dy+i][x0+dx+j]|,   dy, dx in -R .. R
+ *   best     = the smallest SAD; among equals the first in row-major (dy, dx) order (dy = -R first, then dx = -R first)
+ *   texture  = sum over i in 0 .. T-1, j in 0 .. T-2 of |cur[y0+i][x0+j] - cur[y0+i][x0+j+1]|
+ *            + sum over i in 0 .. T-2, j in 0 .. T-1 of |cur[y0+i][x0+j] - cur[y0+i+1][x0+j]|
+ *   accepted = live && texture >= min_texture && |dy| < R && |dx| < R
+ *   sub-pixel, per axis, only where the best is not on that axis's border (|d| < R; else 0), float64:
+ *     sm = SAD at d - 1, s0 = the best SAD, sp = SAD at d + 1 (the other axis at the best);
+ *     den = (double)(sm - 2 s0 + sp) * 2.0;   sub = den > 0 ? (double)(sm - sp) / den : 0
+ * So the road texture under cur's pixel (y, x) was under prev's pixel (y + dy + sub_dy, x + dx + sub_dx). */
+int av_egoflow_match(av_ctx* ctx, av_stream_t stream, const av_egoflow_cfg* cfg, int n_cams, const uint8_t* cur, const uint8_t* prev,
+                     const uint32_t* valid, av_egoflow_tile* tiles);
+
+/* Stage 3, solve: one wave per camera; reads the match's fields of tiles, sets flag bits 2 and 3, writes motion [n_cams].
+ *   vote: the histogram of the ACCEPTED tiles' (dy, dx); the mode (my, mx) is the fullest bin, among equals the first in row-major
+ *         (dy, dx) order.  No accepted tile: motion all 0.
+ *   gate: gated = accepted && |dy - my| <= gate_px && |dx - mx| <= gate_px
+ *   a tile's displacement in metres (the road point seen at p = (f, l) now was at p + d in the previous frame's road frame):
+ *         d_f = -((double)dy + sub_dy) * m_per_px;   d_l = ((double)dx + sub_dx) * m_per_px
+ *   fit over a set of tiles, the small-angle rigid motion d = t + omega J p, J p = (-l, f), float64:
+ *         n = the count; Sf = sum f; Sl = sum l; Q = sum (f f + l l); B1 = sum d_f; B2 = sum d_l; B3 = sum (f d_l - l d_f)
+ *         (each lane sums its own tiles in index order, then a fixed tree over the 64 lanes: sums may differ from a sequential
+ *         sum in the last bits)
+ *         elimination, t first: den = (Q - (Sl Sl) / n) - (Sf Sf) / n;   singular unless n >= 1 and den > 1e-9 * Q   (the pivot test)
+ *         omega = ((B3 + (Sl B1) / n) - (Sf B2) / n) / den;   t_f = (B1 + omega Sl) / n;   t_l = (B2 - omega Sf) / n
+ *   first fit over the gated tiles; residual r_f = d_f - (t_f - omega l), r_l = d_l - (t_l + omega f);
+ *   inlier = gated && !(r_f r_f + r_l r_l > (inlier_px m_per_px)^2);  second fit over the inliers: t_f, t_l, omega;
+ *   rms = sqrt(sum over the inliers of the second fit's (r_f r_f + r_l r_l) / n_inliers)
+ *   valid = neither fit singular && n_inliers >= min_inliers.  A singular first fit: no inliers, t_f = t_l = omega = rms = 0; a
+ *   singular second fit leaves them 0 too. */
+int av_egoflow_solve(av_ctx* ctx, av_stream_t stream, const av_egoflow_cfg* cfg, int n_cams, av_egoflow_tile* tiles,
+                     av_egoflow_motion* motion);
+
+/* Stage 4, measure: state [n_cams] is advanced, z [n_cams][4] and mode [n_cams] are what av_kf_step reads (window 1).
+ *   use = motion.valid && state.frames >= 1       (the first frame after a reset has no predecessor)
+ *   use: c = cos(psi), s = sin(psi);  Dx = t_f c - t_l s;  Dy = t_f s + t_l c;  x += Dx;  y += Dy;  psi += omega;
+ *        z = [x, y, Dx * frame_rate, Dy * frame_rate];  mode = 1
+ *   else: the pose stays;  z = [x, y, 0, 0];  mode = 2 (the filter predicts)
+ *   frames += 1 either way. */
+int av_egoflow_measure(av_ctx* ctx, av_stream_t stream, const av_egoflow_cfg* cfg, int n_cams, const av_egoflow_motion* motion,
+                       av_egoflow_state* state, double* z, uint8_t* mode);
+
+/* All four stages, enqueued on `stream`; no allocation, no host round trip.  patches [n_cams][2][gh][gw] is the ping-pong pair:
+ * frame number state[k].frames of camera k is written to slot frames & 1 and matched against the other slot (on the first frame
+ * that slot holds whatever it held; the measure stage ignores the outcome).  valid, tiles, motion as in the stages. */
+int av_egoflow_update(av_ctx* ctx, av_stream_t stream, const av_egoflow_cfg* cfg, const av_ground_cfg* ground, int n_cams, int h,
+                      int w, const uint8_t* bgr, uint8_t* patches, uint32_t* valid, av_egoflow_tile* tiles, av_egoflow_motion* motion,
+                      av_egoflow_state* state, double* z, uint8_t* mode);
+
 #ifdef __cplusplus
 }
 #endif

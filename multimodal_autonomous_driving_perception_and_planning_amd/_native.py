@@ -79,6 +79,24 @@ class SurroundCfg(C.Structure):
 SURROUND_BLENDS = {"feather": 0, "nearest": 1}
 
 
+class EgoflowCfg(C.Structure):
+    """av_egoflow_cfg: the ground odometry's patch geometry, tile size T, search range R and the solver's settings; 64 bytes."""
+    _fields_ = [("gh", C.c_int32), ("gw", C.c_int32), ("tile", C.c_int32), ("search", C.c_int32), ("f_far", C.c_double),
+                ("m_per_px", C.c_double), ("frame_rate", C.c_double), ("min_texture", C.c_int32), ("gate_px", C.c_int32),
+                ("inlier_px", C.c_double), ("min_inliers", C.c_int32), ("reserved", C.c_int32)]
+
+
+EGOFLOW_ACCEPTED, EGOFLOW_LIVE, EGOFLOW_GATED, EGOFLOW_INLIER = 1, 2, 4, 8       # av_egoflow_tile.flags
+EGOFLOW_TILE_FIELDS = [("flags", "<i4"), ("dy", "<i4"), ("dx", "<i4"), ("sad", "<i4"), ("texture", "<i4"), ("reserved", "<i4"),
+                       ("sub_dy", "<f8"), ("sub_dx", "<f8"), ("f", "<f8"), ("l", "<f8")]                              # 56 bytes
+EGOFLOW_TILE_BYTES = 56
+EGOFLOW_MOTION_FIELDS = [("t_f", "<f8"), ("t_l", "<f8"), ("omega", "<f8"), ("rms", "<f8"), ("n_accepted", "<i4"), ("n_gated", "<i4"),
+                         ("n_inliers", "<i4"), ("valid", "<i4"), ("vote_dy", "<i4"), ("vote_dx", "<i4"), ("reserved", "<i4", (2,))]
+EGOFLOW_MOTION_BYTES = 64
+EGOFLOW_STATE_FIELDS = [("x", "<f8"), ("y", "<f8"), ("psi", "<f8"), ("frames", "<i4"), ("reserved", "<i4")]          # 32 bytes
+EGOFLOW_STATE_BYTES = 32
+
+
 class RigTrackCfg(C.Structure):
     """av_rig_track_cfg: the vehicle-frame tracker's filter, gate and life cycle (seconds, metres); 72 bytes."""
     _fields_ = [("dt", C.c_double), ("q_accel", C.c_double), ("r_meas", C.c_double), ("r_range", C.c_double), ("p0_pos", C.c_double),
@@ -434,6 +452,12 @@ _SIGS = [
     ("av_taglog_segments_where", C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, C.POINTER(TaglogWhere), C.c_int, C.c_int,
                                            C.c_int, vp, C.c_int, vp, vp]),
     ("av_taglog_gather", C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp]),
+    ("av_egoflow_tiles", C.c_int, [C.POINTER(EgoflowCfg), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("av_egoflow_patch", C.c_int, [vp, vp, C.POINTER(EgoflowCfg), vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    ("av_egoflow_match", C.c_int, [vp, vp, C.POINTER(EgoflowCfg), C.c_int, vp, vp, vp, vp]),
+    ("av_egoflow_solve", C.c_int, [vp, vp, C.POINTER(EgoflowCfg), C.c_int, vp, vp]),
+    ("av_egoflow_measure", C.c_int, [vp, vp, C.POINTER(EgoflowCfg), C.c_int, vp, vp, vp, vp]),
+    ("av_egoflow_update", C.c_int, [vp, vp, C.POINTER(EgoflowCfg), vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
 ]
 
 # entry points added by later translation units; bound when present in the header list below

@@ -1,5 +1,6 @@
 from .calibration import CameraCalibration, CameraRig, LensModel
 from .detector import Detection, ObjectDetector
+from .ground_odometry import GroundOdometry
 from .lane_detector import LaneDetector, LaneLine
 
-__all__ = ["ObjectDetector", "LaneDetector", "Detection", "LaneLine", "CameraCalibration", "LensModel", "CameraRig"]
+__all__ = ["ObjectDetector", "LaneDetector", "Detection", "LaneLine", "CameraCalibration", "LensModel", "CameraRig", "GroundOdometry"]

@@ -136,6 +136,7 @@ class HotLoop:
         self._obstacle_kw = dict(obstacle_kw or {})
         self._src = self._class_map = self.det_dropped = None       # set_detections
         self._lanes = self.lane_offset = None                       # set_lane_inputs
+        self._meas = None                                           # set_measurement_source
         self._ext_streams = {}
         self.tag_log = None                                         # enable_tag_log
         self.calibration = self.ground = self.n_off = self.lens = self.lenses = None
@@ -303,10 +304,36 @@ class HotLoop:
                                            nat.ptr(self.trk_state), nat.ptr(self.snap), nat.ptr(self.snap_n),
                                            nat.ptr(self.det2trk)))
 
+    def set_measurement_source(self, z, mode, producer=None):
+        """The Kalman stage reads the ego measurement from the caller's device tensors instead of load_measurements' buffer: z
+        float64 [S, W, 4] and mode uint8 [S, W] (av_kf_step's: 1 = step(z), 2 = step(None), ...), written on the device by a stage
+        ahead of it (perception.GroundOdometry).  producer: a callable(stream) that enqueues that stage; enqueue_kf calls it on
+        its own stream in front of av_kf_step, so the stage runs beside the tracker's branch.  (None, None) puts the loop's own
+        buffer back.  The one-launch step and the overlapped loop read their own buffer sets: refused there."""
+        if z is None and mode is None:
+            self._meas = None
+            self._drop_graphs()
+            return
+        if self.fused_step or self.overlap != 1:
+            raise RuntimeError("set_measurement_source needs the stage launches, HotLoop(fused_step=False): the one-launch step and "
+                               "overlap > 1 read the ego measurement from their own buffer sets (load_measurements)")
+        if (z is None or mode is None or z.dtype != torch.float64 or mode.dtype != torch.uint8 or z.device != self.dev
+                or mode.device != self.dev or tuple(z.shape) != (self.S, self.W, 4) or tuple(mode.shape) != (self.S, self.W)
+                or not z.is_contiguous() or not mode.is_contiguous()):
+            raise ValueError("set_measurement_source: device tensors z float64 [%d, %d, 4] and mode uint8 [%d, %d], contiguous"
+                             % (self.S, self.W, self.S, self.W))
+        self._meas = (z, mode, producer)
+        self._drop_graphs()
+
     def enqueue_kf(self, stream=None):
         self._serial_only("enqueue_kf")
+        z, mode = self.z, None
+        if self._meas is not None:
+            z, mode, producer = self._meas
+            if producer is not None:
+                producer(stream or self._s)
         nat.check(self.L.av_kf_step(self.ctx.handle, stream or self._s, C.byref(self.kcfg), self.S, self.W,
-                                    nat.ptr(self.z), None, nat.ptr(self.kf_state), nat.ptr(self.vstate),
+                                    nat.ptr(z), nat.ptr(mode), nat.ptr(self.kf_state), nat.ptr(self.vstate),
                                     nat.ptr(self.plan_state)))
 
     def enqueue_maneuver(self, stream=None, lane_offset=None):
@@ -1110,7 +1137,8 @@ class CameraLoop:
 
     def __init__(self, n_streams, h=720, w=1280, model="random:0", precision="fp16", dcap=64, obstacles="moving_tracks",
                  class_map="reference", device=0, tracker_kw=None, kf_kw=None, planner_kw=None, obstacle_kw=None, tags=None,
-                 tag_capacity=4096, view=None, tag_columns=False, names=None, track_filter_kw=None, calibration=None):
+                 tag_capacity=4096, view=None, tag_columns=False, names=None, track_filter_kw=None, calibration=None, ego=None,
+                 ego_kw=None):
         """model, names: PerceptionLoop's (any YOLOv8 n / s / m model, e.g. "random:0:s"; names for a checkpoint without them).
         class_map: "reference" (the detector's class names -> the reference's eight ids, everything else skipped:
         reference_class_map), None (raw ids) or an explicit int table.  With names that match none of the reference's eight (a
@@ -1133,11 +1161,22 @@ class CameraLoop:
         (enqueue_view): "camera" leaves self.view_cam (uint8 [S, h, w, 3]: the frames with detections, lane area, tracks,
         info panel and detection summary as demo.py:124-136 draws them), "demo" leaves self.view (uint8 [S, th, tw, 3]: that picture
         beside the BEV panel, labelled, as create_side_by_side joins them).  The frames themselves are not touched.  The info
-        panel's "FPS" line shows self.view_fps (0.0 until set)."""
+        panel's "FPS" line shows self.view_fps (0.0 until set).
+        ego: None -- the Kalman stage's measurement is the caller's (load_measurements) -- or "ground_flow": it is measured from
+        the road pixels of consecutive rectified frames (self.ego, a perception.GroundOdometry with ego_kw's settings, DESIGN 7s;
+        needs calibration=).  The stage runs on the hot stream behind the wait for the camera half, in front of the Kalman stage,
+        which reads its z and mode in place; load_measurements then raises, and results() has ego_motion [S, 3], ego_valid [S],
+        ego_pose [S, 3] and ego_inliers [S]."""
         if tags not in (None, "motion", "all"):
             raise ValueError('tags is None, "motion" or "all"')
         if view not in (None, "camera", "demo"):
             raise ValueError('view is None, "camera" or "demo"')
+        if ego not in (None, "ground_flow"):
+            raise ValueError('ego is None or "ground_flow"')
+        if ego is None and ego_kw is not None:
+            raise ValueError('ego_kw belongs to ego="ground_flow"')
+        if ego is not None and calibration is None:
+            raise ValueError('ego="ground_flow" needs calibration=: the road is seen through the camera model')
         self.S, self.h, self.w = n_streams, h, w
         lenses = None
         if calibration is not None:
@@ -1163,6 +1202,12 @@ class CameraLoop:
         self.hot.set_detections(c.det_n.view(S, 1), c.det_box.view(S, 1, c.max_det, 4), c.det_conf.view(S, 1, c.max_det),
                                 c.det_cls.view(S, 1, c.max_det), class_map=class_map)
         self.hot.set_lane_inputs(c.poly, c.pts, c.info)
+        self.ego = None
+        if ego is not None:
+            from .perception.ground_odometry import GroundOdometry
+            self.ego = GroundOdometry(calibration, n_streams, h, w, device=device, ctx=self.cam.ctx, **(ego_kw or {}))
+            self.hot.set_measurement_source(self.ego.z.view(S, 1, 4), self.ego.mode.view(S, 1),
+                                            producer=lambda stream: self.ego.enqueue(c.frames, stream))
         self._stepped = False
         self.tags, self.tag_log = tags, None
         if tags is not None:
@@ -1285,6 +1330,8 @@ class CameraLoop:
 
     def load_measurements(self, z):
         """z: float64 [S, 1, 4] (or [S, 4]) ego measurements of the next step (HotLoop.load_measurements)."""
+        if self.ego is not None:
+            raise RuntimeError('CameraLoop(ego="ground_flow") measures the ego motion from the frames: there is nothing to load')
         self.hot.load_measurements(z)
 
     def step(self, sync=False, frames=None):
@@ -1326,8 +1373,13 @@ class CameraLoop:
         self.hot.synchronize()
 
     def results(self):
-        """HotLoop.results() of the last step: with det_dropped [S, 1], ref_paths [S, 50, 2], n_ref [S] and lane_offset [S]."""
-        return self.hot.results()
+        """HotLoop.results() of the last step: with det_dropped [S, 1], ref_paths [S, 50, 2], n_ref [S] and lane_offset [S]; with
+        ego="ground_flow" also ego_motion [S, 3] (t_f, t_l, omega), ego_valid [S], ego_pose [S, 3] and ego_inliers [S]."""
+        out = self.hot.results()
+        if self.ego is not None:
+            e = self.ego.results()
+            out["ego_motion"], out["ego_valid"], out["ego_pose"], out["ego_inliers"] = e["motion"], e["valid"], e["pose"], e["n_inliers"]
+        return out
 
 
 class RigLoop:
