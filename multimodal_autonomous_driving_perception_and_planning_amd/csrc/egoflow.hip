@@ -62,7 +62,9 @@ int geometry(const av_egoflow_cfg* c, const char* who, Geom* g) {
 __device__ __forceinline__ int slot_of(const av_egoflow_state* __restrict__ st, int cam) { return st ? (st[cam].frames & 1) : 0; }
 
 // ---- stage 1: patch ------------------------------------------------------------------------------------------------------------
-// a wave makes 64 adjacent pixels of one patch row: one byte per lane, and the wave's ballot is the row's two validity words
+// a wave makes 64 adjacent pixels of one patch row: one byte per lane, and the wave's ballot is the row's two validity words.
+// WIDE: the frames are at least two pixels wide (the bilinear sample's packed form)
+template <bool WIDE>
 __global__ void __launch_bounds__(256) egoflow_patch_kernel(const av_ground_cfg* __restrict__ ground, int h, int w,
                                                             const uint8_t* __restrict__ bgr, Geom g, double f_far, double m_per_px,
                                                             uint8_t* __restrict__ patch, size_t cam_stride,
@@ -79,7 +81,7 @@ __global__ void __launch_bounds__(256) egoflow_patch_kernel(const av_ground_cfg*
         long long iu, iv;
         ok = grounddev::warp_position(ground[cam].ginv, h, w, f, l, iu, iv);
         if (ok) {
-            const unsigned p = grounddev::warp_sample(bgr + (size_t)cam * h * w * 3, h, w, iu, iv);
+            const unsigned p = grounddev::warp_sample<WIDE>(bgr + (size_t)cam * h * w * 3, h, w, iu, iv);
             gray = (1868u * (p & 255u) + 9617u * ((p >> 8) & 255u) + 4899u * ((p >> 16) & 255u) + 8192u) >> 14;
         }
     }
@@ -368,7 +370,8 @@ __global__ void __launch_bounds__(64) egoflow_measure_kernel(int n_cams, double 
 int launch_patch(av_stream_t stream, const av_egoflow_cfg* c, const Geom& g, const av_ground_cfg* ground, int n_cams, int h, int w,
                  const uint8_t* bgr, uint8_t* patch, size_t cam_stride, const av_egoflow_state* st, uint32_t* valid) {
     const dim3 grid((unsigned)((g.gw + 63) / 64), (unsigned)((g.gh + 3) / 4), (unsigned)n_cams);
-    hipLaunchKernelGGL(egoflow_patch_kernel, grid, dim3(256), 0, as_stream(stream), ground, h, w, bgr, g, c->f_far, c->m_per_px, patch,
+    const auto kernel = w >= 2 ? egoflow_patch_kernel<true> : egoflow_patch_kernel<false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, as_stream(stream), ground, h, w, bgr, g, c->f_far, c->m_per_px, patch,
                        cam_stride, st, valid);
     AV_LAUNCH_CHECK();
     return AV_OK;

@@ -1,10 +1,10 @@
 // The ground-plane camera model's device side (include/avhot.h: av_ground_cfg): the projection of an image point onto the road,
 // shared by the ground forms of av_track_obstacles (obstacles.hip) and av_lane_paths (bridge.hip), and the way back, a road point's
-// place in the frame and the picture there, shared by av_ground_warp (ground.hip) and av_rig_surround (surround.hip).  float64,
-// every operation rounded on its own, in the order the header states.
+// place in the frame and the picture there (resample_dev.h's sample), shared by av_ground_warp (ground.hip), av_rig_surround
+// (surround.hip) and the odometry's patch stage (egoflow.hip).  float64, every operation rounded on its own, in the header's order.
 #pragma once
 #include "common.h"
-#include "raster_dev.h"
+#include "resample_dev.h"
 
 namespace grounddev {
 
@@ -48,13 +48,10 @@ __device__ __forceinline__ bool warp_position(const double* __restrict__ q, int 
     return true;
 }
 
-// the picture at such a position as b | g << 8 | r << 16: rasterdev::resize_channel's bilinear rule
+// the picture at such a position as b | g << 8 | r << 16: resample_dev.h's bilinear sample (WIDE: its packed form, needs w >= 2)
+template <bool WIDE>
 __device__ __forceinline__ unsigned warp_sample(const uint8_t* __restrict__ src, int h, int w, long long iu, long long iv) {
-    rasterdev::ResizeTap t;
-    t.x0 = (int)(iu >> 16), t.wx = (int)(iu & 65535), t.x1 = min(t.x0 + 1, w - 1);      // 0 <= x0 <= w - 1
-    t.y0 = (int)(iv >> 16), t.wy = (int)(iv & 65535), t.y1 = min(t.y0 + 1, h - 1);      // 0 <= y0 <= h - 1
-    return (unsigned)rasterdev::resize_channel(src, w, t, 0) | ((unsigned)rasterdev::resize_channel(src, w, t, 1) << 8) |
-           ((unsigned)rasterdev::resize_channel(src, w, t, 2) << 16);
+    return resample::bilinear_bgr<WIDE>(src, h, w, iu, iv);
 }
 
 }  // namespace grounddev

@@ -6,21 +6,20 @@
 // 1/65536 pixels, and the per-frame kernel is integer only: 8 bytes of table in, four taps, 3 bytes out per pixel.  The tables
 // need the FORWARD model only (rectified pixel -> raw position); the Newton inverse of lens_dev.h serves points (obstacles.hip).
 //
-// av_remap, mapping: av_ground_warp's.  A thread makes four adjacent pixels of one output row from 32 contiguous table bytes and
-// stores them as 12 bytes at once (tail of a row: entry by entry, byte by byte); a 256-thread workgroup covers 64 columns x 16
-// rows, so that the taps of a tile share cache lines in both directions.  The two taps of a source row are fetched together (six
-// contiguous bytes: row_taps).  Every source index is derived from an entry that has passed the range check against (sw, sh): a
-// foreign table cannot make the kernel read outside bgr.
+// av_remap: resample_dev.h's tile, store and bilinear sample (its packed form: the two taps of a source row fetched together).  A
+// thread makes four adjacent pixels of one output row from 32 contiguous table bytes (tail of a row: entry by entry).  Every source
+// index is derived from an entry that has passed the range check against (sw, sh): a foreign table cannot make the kernel read
+// outside bgr.  The table builders use the tile's constants with a rule of their own: one column and four rows per thread.
 #include "common.h"
 #include "lens_dev.h"
-#include "raster_dev.h"
+#include "resample_dev.h"
 
 #include <cmath>
 #include <cstring>
 
 namespace {
 
-constexpr int TILE_W = 64, TILE_H = 16, PX = 4;     // pixels per tile row, rows per tile, pixels per thread
+using resample::PX, resample::TILE_H, resample::TILE_W;
 constexpr int MAX_SIDE = 32768;                     // (side - 1) * 65536 fits an int32
 
 // rectified pixel (u, v) of lens L -> the map entry of the raw position
@@ -74,52 +73,12 @@ __global__ void __launch_bounds__(256) lens_map_ground_kernel(const av_lens_cfg*
     }
 }
 
-// The two horizontally adjacent taps of one source row as b | g << 8 | r << 16 each.  They are six contiguous bytes, fetched as a
-// 4-byte and a 2-byte load at whatever alignment they have (two loads per row in place of five byte and short gathers): pixels
-// xa = min(x0, sw - 2) and xa + 1, so that at the frame's right edge, where x1 == x0 == sw - 1, nothing past the row is read.
-// Needs sw >= 2; bytes [3 xa, 3 xa + 6) lie inside the row because xa + 1 <= sw - 1.
-struct RowTaps {
-    unsigned p0, p1;
-};
-__device__ __forceinline__ RowTaps row_taps(const uint8_t* __restrict__ row, int x0, int sw) {
-    const int xa = min(x0, sw - 2);
-    unsigned lo;
-    unsigned short hi;
-    __builtin_memcpy(&lo, row + (size_t)xa * 3, 4);
-    __builtin_memcpy(&hi, row + (size_t)xa * 3 + 4, 2);
-    RowTaps t;
-    t.p1 = (lo >> 24) | ((unsigned)hi << 8);
-    t.p0 = x0 == xa ? (lo & 0xffffffu) : t.p1;
-    return t;
-}
-
-// rasterdev::resize_channel's rule on one channel of the four taps, in unsigned arithmetic: the horizontal blends are below 2^24,
-// the vertical one is a 32 x 32 -> 64 bit multiply-add; the same integers as the rule's 64-bit products, term by term
-__device__ __forceinline__ unsigned blend(unsigned p00, unsigned p01, unsigned p10, unsigned p11, unsigned wx, unsigned wy) {
-    const unsigned top = p00 * (65536u - wx) + p01 * wx, bot = p10 * (65536u - wx) + p11 * wx;
-    return (unsigned)(((unsigned long long)top * (65536u - wy) + (unsigned long long)bot * wy + (1ull << 31)) >> 32);
-}
-
-// one output pixel as b | g << 8 | r << 16 from a table entry; lim = ((sw - 1) << 16, (sh - 1) << 16).  WIDE: sw >= 2 (row_taps)
+// one output pixel as b | g << 8 | r << 16 from a table entry; lim = ((sw - 1) << 16, (sh - 1) << 16).  WIDE: sw >= 2
 template <bool WIDE>
 __device__ __forceinline__ unsigned remap_pixel(const uint8_t* __restrict__ src, int sh, int sw, unsigned lim_u, unsigned lim_v,
                                                 int32_t tu, int32_t tv, unsigned fill) {
     if ((unsigned)tu > lim_u || (unsigned)tv > lim_v) return fill;      // (a negative entry is a large unsigned)
-    rasterdev::ResizeTap t;
-    t.x0 = tu >> 16, t.wx = tu & 65535, t.x1 = min(t.x0 + 1, sw - 1);     // 0 <= x0 <= sw - 1
-    t.y0 = tv >> 16, t.wy = tv & 65535, t.y1 = min(t.y0 + 1, sh - 1);     // 0 <= y0 <= sh - 1
-    if constexpr (WIDE) {
-        const RowTaps a = row_taps(src + (size_t)t.y0 * sw * 3, t.x0, sw), b = row_taps(src + (size_t)t.y1 * sw * 3, t.x0, sw);
-        unsigned px = 0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            px |= blend((a.p0 >> (8 * k)) & 255u, (a.p1 >> (8 * k)) & 255u, (b.p0 >> (8 * k)) & 255u, (b.p1 >> (8 * k)) & 255u,
-                        (unsigned)t.wx, (unsigned)t.wy) << (8 * k);
-        return px;
-    } else {
-        return (unsigned)rasterdev::resize_channel(src, sw, t, 0) | ((unsigned)rasterdev::resize_channel(src, sw, t, 1) << 8) |
-               ((unsigned)rasterdev::resize_channel(src, sw, t, 2) << 16);
-    }
+    return resample::bilinear_bgr<WIDE>(src, sh, sw, tu, tv);
 }
 
 template <bool WIDE>
@@ -127,15 +86,12 @@ __global__ void __launch_bounds__(256) remap_kernel(const int32_t* __restrict__ 
                                                     const uint8_t* __restrict__ bgr, int dh, int dw, unsigned fill,
                                                     uint8_t* __restrict__ out) {
     const int cam = blockIdx.z;
-    const int r = blockIdx.y * TILE_H + (int)(threadIdx.x / (TILE_W / PX));
-    const long long c0l = (long long)blockIdx.x * TILE_W + (int)(threadIdx.x % (TILE_W / PX)) * PX;
-    if (r >= dh || c0l >= dw) return;
-    const int c0 = (int)c0l;
+    int r, c0, npx;
+    if (!resample::tile_thread(dh, dw, r, c0, npx)) return;
     const uint8_t* src = bgr + (size_t)cam * sh * sw * 3;
     const size_t px0 = (size_t)r * dw + c0;                          // r < dh, c0 < dw
     const int32_t* mp = map + ((size_t)(cam / cam_stride) * dh * dw + px0) * 2;
     const unsigned lim_u = (unsigned)(sw - 1) << 16, lim_v = (unsigned)(sh - 1) << 16;      // sw, sh <= 32768
-    const int npx = min(PX, dw - c0);
     uint8_t* o = out + ((size_t)cam * dh * dw + px0) * 3;
     if (npx == PX) {
         int32_t e[2 * PX];
@@ -143,22 +99,14 @@ __global__ void __launch_bounds__(256) remap_kernel(const int32_t* __restrict__ 
         unsigned px[PX];
 #pragma unroll
         for (int j = 0; j < PX; ++j) px[j] = remap_pixel<WIDE>(src, sh, sw, lim_u, lim_v, e[2 * j], e[2 * j + 1], fill);
-        const unsigned words[3] = {px[0] | (px[1] << 24), (px[1] >> 8) | (px[2] << 16), (px[2] >> 16) | (px[3] << 8)};
-        __builtin_memcpy(o, words, 12);                             // one 12-byte store, at any alignment
+        resample::store_px4(o, px, PX);
     } else {
-        for (int j = 0; j < npx; ++j) {                             // c0 + j < dw: nothing past the row's end is read or written
-            const unsigned p = remap_pixel<WIDE>(src, sh, sw, lim_u, lim_v, mp[2 * j], mp[2 * j + 1], fill);
-            o[j * 3] = (uint8_t)p, o[j * 3 + 1] = (uint8_t)(p >> 8), o[j * 3 + 2] = (uint8_t)(p >> 16);
-        }
+        for (int j = 0; j < npx; ++j)                               // c0 + j < dw: nothing past the row's end is read or written
+            resample::store_px1(o + j * 3, remap_pixel<WIDE>(src, sh, sw, lim_u, lim_v, mp[2 * j], mp[2 * j + 1], fill));
     }
 }
 
 bool finite4(const double* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]) && std::isfinite(v[3]); }
-
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
 
 }  // namespace
 
@@ -196,9 +144,8 @@ extern "C" int av_lens_map_rectify(av_ctx* ctx, av_stream_t stream, const av_len
     AV_REQUIRE(ctx && lens && map, AV_EINVAL, "av_lens_map_rectify: null argument");
     AV_REQUIRE(n_maps >= 1 && h >= 1 && w >= 1 && h <= MAX_SIDE && w <= MAX_SIDE, AV_EINVAL,
                "av_lens_map_rectify: n_maps must be >= 1, h and w in 1 .. %d", MAX_SIDE);
-    const long long tiles_y = ((long long)h + TILE_H - 1) / TILE_H;
-    AV_REQUIRE(n_maps <= 65535 && tiles_y <= 65535, AV_EINVAL, "av_lens_map_rectify: more than 65535 maps or tile rows");
-    const dim3 grid((unsigned)((w + TILE_W - 1) / TILE_W), (unsigned)tiles_y, (unsigned)n_maps);
+    dim3 grid;
+    if (int rc = resample::tile_grid(w, h, n_maps, "av_lens_map_rectify", "maps", &grid)) return rc;
     hipLaunchKernelGGL(lens_map_rectify_kernel, grid, dim3(256), 0, as_stream(stream), lens, h, w, map);
     AV_LAUNCH_CHECK();
     return AV_OK;
@@ -210,9 +157,8 @@ extern "C" int av_lens_map_ground(av_ctx* ctx, av_stream_t stream, const av_lens
     AV_REQUIRE(n_maps >= 1 && gh >= 1 && gw >= 1, AV_EINVAL, "av_lens_map_ground: n_maps, gh and gw must be >= 1");
     AV_REQUIRE(m_per_px > 0.0 && std::isfinite(m_per_px) && std::isfinite(f_far), AV_EINVAL,
                "av_lens_map_ground: m_per_px must be > 0 and finite, f_far finite");
-    const long long tiles_y = ((long long)gh + TILE_H - 1) / TILE_H;
-    AV_REQUIRE(n_maps <= 65535 && tiles_y <= 65535, AV_EINVAL, "av_lens_map_ground: more than 65535 maps or tile rows");
-    const dim3 grid((unsigned)(((long long)gw + TILE_W - 1) / TILE_W), (unsigned)tiles_y, (unsigned)n_maps);
+    dim3 grid;
+    if (int rc = resample::tile_grid(gw, gh, n_maps, "av_lens_map_ground", "maps", &grid)) return rc;
     hipLaunchKernelGGL(lens_map_ground_kernel, grid, dim3(256), 0, as_stream(stream), lens, ground, gh, gw, f_far, m_per_px, map);
     AV_LAUNCH_CHECK();
     return AV_OK;
@@ -224,17 +170,14 @@ extern "C" int av_remap(av_ctx* ctx, av_stream_t stream, const int32_t* map, int
     AV_REQUIRE(n_cams >= 1 && dh >= 1 && dw >= 1, AV_EINVAL, "av_remap: n_cams, dh and dw must be >= 1");
     AV_REQUIRE(sh >= 1 && sw >= 1 && sh <= MAX_SIDE && sw <= MAX_SIDE, AV_EINVAL, "av_remap: sh and sw must be in 1 .. %d", MAX_SIDE);
     AV_REQUIRE(cam_stride >= 1, AV_EINVAL, "av_remap: cam_stride must be >= 1");
-    const long long tiles_y = ((long long)dh + TILE_H - 1) / TILE_H;
-    AV_REQUIRE(n_cams <= 65535 && tiles_y <= 65535, AV_EINVAL, "av_remap: more than 65535 cameras or tile rows");
+    dim3 grid;
+    if (int rc = resample::tile_grid(dw, dh, n_cams, "av_remap", "cameras", &grid)) return rc;
     const size_t out_bytes = (size_t)n_cams * dh * dw * 3, n_maps = ((size_t)n_cams + cam_stride - 1) / cam_stride;
-    AV_REQUIRE(!overlap(out, out_bytes, bgr, (size_t)n_cams * sh * sw * 3), AV_EINVAL, "av_remap: out overlaps bgr");
-    AV_REQUIRE(!overlap(out, out_bytes, map, n_maps * dh * dw * 8), AV_EINVAL, "av_remap: out overlaps map");
-    const unsigned fc = (unsigned)fill[0] | ((unsigned)fill[1] << 8) | ((unsigned)fill[2] << 16);
-    const dim3 grid((unsigned)(((long long)dw + TILE_W - 1) / TILE_W), (unsigned)tiles_y, (unsigned)n_cams);
-    if (sw >= 2)
-        hipLaunchKernelGGL(remap_kernel<true>, grid, dim3(256), 0, as_stream(stream), map, cam_stride, sh, sw, bgr, dh, dw, fc, out);
-    else        // a source one pixel wide: tap by tap
-        hipLaunchKernelGGL(remap_kernel<false>, grid, dim3(256), 0, as_stream(stream), map, cam_stride, sh, sw, bgr, dh, dw, fc, out);
+    AV_REQUIRE(!resample::overlap(out, out_bytes, bgr, (size_t)n_cams * sh * sw * 3), AV_EINVAL, "av_remap: out overlaps bgr");
+    AV_REQUIRE(!resample::overlap(out, out_bytes, map, n_maps * dh * dw * 8), AV_EINVAL, "av_remap: out overlaps map");
+    const unsigned fc = resample::pack_bgr(fill);
+    const auto kernel = sw >= 2 ? remap_kernel<true> : remap_kernel<false>;      // a source one pixel wide: tap by tap
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, as_stream(stream), map, cam_stride, sh, sw, bgr, dh, dw, fc, out);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }

@@ -4,12 +4,11 @@
 // ginv, and the cameras that see it are blended (feather: weights that fall to one at the frame's border, so a seam fades instead
 // of cutting) or the nearest one is taken.
 //
-// Mapping: ground_warp_kernel's.  A thread makes four adjacent pixels of one panel row and stores them as 12 bytes at once (tail
-// of a row: byte by byte), and their cover bytes as 4 at once when the rows are a multiple of four wide; a 256-thread workgroup
-// covers 64 columns x 16 rows, since neighbouring panel pixels read neighbouring source pixels of whichever camera sees them.
-// grid.z is the vehicle; the loop over the K cameras runs inside the thread, with the four pixels' running sums in registers, and
-// a camera's mount, ginv and max_range are the same for the whole workgroup: scalar loads.  No LDS.  The per-pixel sampling is
-// ground_dev.h's, the one copy av_ground_warp uses.
+// resample_dev.h's tile and store: a thread makes four adjacent pixels of one panel row, and stores their cover bytes as 4 at once
+// when the rows are a multiple of four wide; neighbouring panel pixels read neighbouring source pixels of whichever camera sees
+// them.  grid.z is the vehicle; the loop over the K cameras runs inside the thread, with the four pixels' running sums in
+// registers, and a camera's mount, ginv and max_range are the same for the whole workgroup: scalar loads.  No LDS.  The per-pixel
+// position and sample are ground_dev.h's, which av_ground_warp uses too.
 #include "common.h"
 #include "ground_dev.h"
 
@@ -17,20 +16,13 @@
 
 namespace {
 
-constexpr int TILE_W = 64, TILE_H = 16, PX = 4;     // pixels per tile row, rows per tile, pixels per thread
+using resample::PX;
 constexpr int MAX_CAMS = 8, MAX_SIDE = 32768;
 
-// the four pixels' 12 bytes and cover bytes, or the row's tail byte by byte
+// the four pixels and their cover bytes
 __device__ __forceinline__ void store_pixels(uint8_t* __restrict__ o, uint8_t* __restrict__ cv, const unsigned (&px)[PX],
                                              const unsigned (&mask)[PX], int npx, bool cover4) {
-    if (npx == PX) {
-        const unsigned words[3] = {px[0] | (px[1] << 24), (px[1] >> 8) | (px[2] << 16), (px[2] >> 16) | (px[3] << 8)};
-        __builtin_memcpy(o, words, 12);                             // one 12-byte store, at any alignment
-    } else {
-#pragma unroll
-        for (int j = 0; j < PX - 1; ++j)
-            if (j < npx) o[j * 3] = (uint8_t)px[j], o[j * 3 + 1] = (uint8_t)(px[j] >> 8), o[j * 3 + 2] = (uint8_t)(px[j] >> 16);
-    }
+    resample::store_px4(o, px, npx);
     if (!cv) return;
     if (cover4) {                                                   // gw % 4 == 0: every thread has four pixels
         const unsigned word = mask[0] | (mask[1] << 8) | (mask[2] << 16) | (mask[3] << 24);
@@ -42,17 +34,14 @@ __device__ __forceinline__ void store_pixels(uint8_t* __restrict__ o, uint8_t* _
     }
 }
 
-template <bool NEAREST>
+template <bool NEAREST, bool WIDE>        // WIDE: the frames are at least two pixels wide, the sample's packed form
 __global__ void __launch_bounds__(256) rig_surround_kernel(int n_cams, const av_rig_mount* __restrict__ mounts,
                                                            const av_ground_cfg* __restrict__ ground, int h, int w,
                                                            const uint8_t* __restrict__ bgr, int gh, int gw, double x_far, double m_per_px,
                                                            unsigned fill, uint8_t* __restrict__ out, uint8_t* __restrict__ cover) {
     const int veh = blockIdx.z;
-    const int r = blockIdx.y * TILE_H + (int)(threadIdx.x / (TILE_W / PX));
-    const long long c0l = (long long)blockIdx.x * TILE_W + (int)(threadIdx.x % (TILE_W / PX)) * PX;
-    if (r >= gh || c0l >= gw) return;
-    const int c0 = (int)c0l;
-    const int npx = min(PX, gw - c0);
+    int r, c0, npx;
+    if (!resample::tile_thread(gh, gw, r, c0, npx)) return;
     const size_t frame = (size_t)h * w * 3;
     const double X = x_far - ((double)r + 0.5) * m_per_px;
     double Y[PX];
@@ -94,7 +83,7 @@ __global__ void __launch_bounds__(256) rig_surround_kernel(int n_cams, const av_
                 const double d2 = f * f + l * l;
                 if (mask[j] == 0u || d2 < best[j]) best[j] = d2, bu[j] = iu, bv[j] = iv, bk[j] = k;    // equal d2: the smaller k stays
             } else {
-                const unsigned p = grounddev::warp_sample(src, h, w, iu, iv);
+                const unsigned p = grounddev::warp_sample<WIDE>(src, h, w, iu, iv);
                 const long long eu = min(iu, lim_u - iu), ev = min(iv, lim_v - iv);
                 const unsigned wt = (unsigned)(min(eu, ev) >> 16) + 1u;                    // 1 .. 16384
                 sw[j] += wt, last[j] = p;
@@ -108,7 +97,7 @@ __global__ void __launch_bounds__(256) rig_surround_kernel(int n_cams, const av_
         px[j] = fill;
         if (mask[j] == 0u) continue;
         if constexpr (NEAREST) {
-            px[j] = grounddev::warp_sample(bgr + ((size_t)veh * n_cams + bk[j]) * frame, h, w, bu[j], bv[j]);
+            px[j] = grounddev::warp_sample<WIDE>(bgr + ((size_t)veh * n_cams + bk[j]) * frame, h, w, bu[j], bv[j]);
         } else {
             const unsigned d = 2u * sw[j];                                                  // <= 2 x 8 x 16384
             // one camera alone (most of a panel): (2 wt p + wt) / (2 wt) is p itself, without the three divisions
@@ -119,11 +108,6 @@ __global__ void __launch_bounds__(256) rig_surround_kernel(int n_cams, const av_
     }
     const size_t at = ((size_t)veh * gh + r) * gw + c0;              // r < gh, c0 + npx <= gw
     store_pixels(out + at * 3, cover ? cover + at : nullptr, px, mask, npx, gw % PX == 0);
-}
-
-bool overlap(const void* a, unsigned __int128 na, const void* b, unsigned __int128 nb) {
-    const unsigned __int128 pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
 }
 
 }  // namespace
@@ -137,8 +121,8 @@ extern "C" int av_rig_surround(av_ctx* ctx, av_stream_t stream, const av_surroun
     AV_REQUIRE(h >= 1 && w >= 1 && h <= MAX_SIDE && w <= MAX_SIDE, AV_EINVAL, "av_rig_surround: frame size h %d, w %d not in 1..%d", h, w,
                MAX_SIDE);
     AV_REQUIRE(gh >= 1 && gw >= 1, AV_EINVAL, "av_rig_surround: panel size gh and gw must be >= 1");
-    const long long tiles_y = ((long long)gh + TILE_H - 1) / TILE_H;
-    AV_REQUIRE(n_vehicles <= 65535 && tiles_y <= 65535, AV_EINVAL, "av_rig_surround: more than 65535 vehicles or tile rows");
+    dim3 grid;
+    if (int rc = resample::tile_grid(gw, gh, n_vehicles, "av_rig_surround", "vehicles", &grid)) return rc;
     AV_REQUIRE(cfg, AV_EINVAL, "av_rig_surround: null cfg");
     AV_REQUIRE(cfg->m_per_px > 0.0 && std::isfinite(cfg->m_per_px), AV_EINVAL, "av_rig_surround: cfg m_per_px must be > 0 and finite");
     AV_REQUIRE(std::isfinite(cfg->x_far), AV_EINVAL, "av_rig_surround: cfg x_far must be finite");
@@ -148,17 +132,13 @@ extern "C" int av_rig_surround(av_ctx* ctx, av_stream_t stream, const av_surroun
     AV_REQUIRE(ctx && mounts && ground && bgr && out, AV_EINVAL, "av_rig_surround: null argument");
     {
         const unsigned __int128 panel = (unsigned __int128)n_vehicles * gh * gw, frames = (unsigned __int128)n_vehicles * n_cams * h * w * 3;
-        AV_REQUIRE(!overlap(out, panel * 3, bgr, frames), AV_EINVAL, "av_rig_surround: out overlaps bgr");
-        AV_REQUIRE(!cover || !overlap(cover, panel, bgr, frames), AV_EINVAL, "av_rig_surround: cover overlaps bgr");
+        AV_REQUIRE(!resample::overlap(out, panel * 3, bgr, frames), AV_EINVAL, "av_rig_surround: out overlaps bgr");
+        AV_REQUIRE(!cover || !resample::overlap(cover, panel, bgr, frames), AV_EINVAL, "av_rig_surround: cover overlaps bgr");
     }
-    const unsigned fc = (unsigned)cfg->fill[0] | ((unsigned)cfg->fill[1] << 8) | ((unsigned)cfg->fill[2] << 16);
-    const dim3 grid((unsigned)(((long long)gw + TILE_W - 1) / TILE_W), (unsigned)tiles_y, (unsigned)n_vehicles);
-    if (cfg->blend == 1)
-        hipLaunchKernelGGL(rig_surround_kernel<true>, grid, dim3(256), 0, as_stream(stream), n_cams, mounts, ground, h, w, bgr, gh, gw,
-                           cfg->x_far, cfg->m_per_px, fc, out, cover);
-    else
-        hipLaunchKernelGGL(rig_surround_kernel<false>, grid, dim3(256), 0, as_stream(stream), n_cams, mounts, ground, h, w, bgr, gh, gw,
-                           cfg->x_far, cfg->m_per_px, fc, out, cover);
+    const auto kernel = cfg->blend == 1 ? (w >= 2 ? rig_surround_kernel<true, true> : rig_surround_kernel<true, false>)
+                                        : (w >= 2 ? rig_surround_kernel<false, true> : rig_surround_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, as_stream(stream), n_cams, mounts, ground, h, w, bgr, gh, gw,
+                       cfg->x_far, cfg->m_per_px, resample::pack_bgr(cfg->fill), out, cover);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }

@@ -13,6 +13,7 @@ import pytest
 from tests import egoflow_cases as cases
 from tests import egoflow_ref as ref
 from tests import ground_ref as gr
+from tests import narrow_cases as narrow
 
 gpu = pytest.mark.gpu
 
@@ -133,28 +134,36 @@ def _patch_cals():
 
 
 @gpu
-@pytest.mark.parametrize("gh,gw,f_far", [(40, 150, 9.0), (72, 66, 6.9)], ids=["40x150", "72x66_behind_the_camera"])
-def test_patch_against_the_warp_and_the_gray_formula(env, gh, gw, f_far):
-    """Frames rendered through from_pose cameras (noise above the horizon); the second geometry's last rows lie behind the camera."""
+@pytest.mark.parametrize("gh,gw,f_far,source", [(40, 150, 9.0, None), (72, 66, 6.9, None), (8, 12, 4.0, (5, 2)), (8, 12, 4.0, (5, 1))],
+                         ids=["40x150", "72x66_behind_the_camera", "source_two_wide", "source_one_wide"])
+def test_patch_against_the_warp_and_the_gray_formula(env, gh, gw, f_far, source):
+    """Frames rendered through from_pose cameras (noise above the horizon); the second geometry's last rows lie behind the camera.
+    The last two: tests/narrow_cases.py's affine cameras over noise frames two pixels and one pixel wide (the entry takes them)."""
     torch, nat, L, ctx = env
-    cals, rng = _patch_cals(), np.random.default_rng(3)
-    c = ref.cfg(gh=gh, gw=gw, f_far=f_far, m_per_px=0.1, tile=8, search=4)
-    frames = np.stack([cases.render_frame(cal, PATCH_H, PATCH_W, (2.0 * k, 1.0, 0.1 * k), rng) for k, cal in enumerate(cals)])
-    frames[..., 0] = frames[..., 0] // 2 + 17                                   # three different channels: the gray's weights count
-    frames[..., 2] = 255 - frames[..., 2]
+    if source is None:
+        cals, rng, h, w, m_per_px = _patch_cals(), np.random.default_rng(3), PATCH_H, PATCH_W, 0.1
+        c = ref.cfg(gh=gh, gw=gw, f_far=f_far, m_per_px=m_per_px, tile=8, search=4)
+        frames = np.stack([cases.render_frame(cal, h, w, (2.0 * k, 1.0, 0.1 * k), rng) for k, cal in enumerate(cals)])
+        frames[..., 0] = frames[..., 0] // 2 + 17                               # three different channels: the gray's weights count
+        frames[..., 2] = 255 - frames[..., 2]
+    else:
+        (h, w), m_per_px = source, 0.5
+        cals = narrow.models(h, w, gh, gw, f_far, m_per_px)
+        c = ref.cfg(gh=gh, gw=gw, f_far=f_far, m_per_px=m_per_px, tile=4, search=2)
+        frames = narrow.frames(len(cals), h, w, 4)
     n = len(cals)
     table = _dev(env, np.frombuffer(b"".join(bytes(k.cfg()) for k in cals), np.uint8).reshape(n, 160).copy())
     patch = torch.full((n, gh, gw), 0xAB, dtype=torch.uint8, device="cuda")
     valid = torch.full((n, gh, (gw + 31) // 32), -1, dtype=torch.int32, device="cuda")
     d_frames = _dev(env, frames)
-    nat.check(L.av_egoflow_patch(ctx.handle, _stream(env), C.byref(_ccfg(nat, c)), nat.ptr(table), n, PATCH_H, PATCH_W, nat.ptr(d_frames),
+    nat.check(L.av_egoflow_patch(ctx.handle, _stream(env), C.byref(_ccfg(nat, c)), nat.ptr(table), n, h, w, nat.ptr(d_frames),
                                  nat.ptr(patch), nat.ptr(valid)))
     _sync(env)
     got_p, got_v = patch.cpu().numpy(), valid.cpu().numpy().view(np.uint32)
     seen = []
     for k, cal in enumerate(cals):
         cam = gr.cam_of(cal.cfg())
-        assert gr.warp_margin(cam, PATCH_H, PATCH_W, gh, gw, f_far, 0.1)[0] > 1e-6          # no position on a rounding threshold
+        assert gr.warp_margin(cam, h, w, gh, gw, f_far, m_per_px)[0] > 1e-6     # no position on a rounding threshold
         want_p, want_v = ref.patch(cam, frames[k], c)
         assert np.array_equal(got_v[k], ref.pack_valid(want_v)), k
         assert np.array_equal(got_p[k], want_p), k

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from tests import ground_ref as gr
+from tests import narrow_cases as narrow
 
 gpu = pytest.mark.gpu
 SENT = -777.25
@@ -289,6 +290,27 @@ def test_ground_warp_crop_copy(env):
                             (1, 2, 3)))
     assert np.array_equal(got[0], src[0, 7:16, 5:18])
     assert np.array_equal(got[1, 3:, :8], src[1, 0:6, 22:30]) and (got[1, :3] == (1, 2, 3)).all() and (got[1, :, 8:] == (1, 2, 3)).all()
+
+
+@gpu
+@pytest.mark.parametrize("h,w", narrow.SHAPES)
+def test_ground_warp_narrow_sources(env, h, w):
+    """Sources one and two pixels wide or high, two cameras each, onto a 4 x 7 panel (one full four-pixel group and a tail of
+    three): the frames at which the sample's packed form must not be taken, or must clamp its loads at the row's end.  The
+    restatement alone leaves at least a quarter of each panel other than fill, at non-integer positions."""
+    P = narrow.PANEL
+    cals, src, fill = narrow.models(h, w), narrow.frames(2, h, w, 25), (0, 0, 0)
+    case = _Warp(env, cals, src, P["gh"], P["gw"], P["f_far"], P["m_per_px"], fill)
+    want = case.want()
+    for k, cal in enumerate(cals):
+        assert (want[k] != 0).any(-1).mean() >= 0.25, k
+        D, su, sv = gr.warp_positions(gr.cam_of(cal.cfg()), h, w, P["gh"], P["gw"], P["f_far"], P["m_per_px"])
+        inside = (np.floor(su) >= 0) & (np.floor(su) <= (w - 1) * 65536) & (np.floor(sv) >= 0) & (np.floor(sv) <= (h - 1) * 65536)
+        assert (D > 0).all() and np.array_equal(inside, (want[k] != 0).any(-1))
+        weights = (np.floor(su[inside]).astype(np.int64) & 65535) if w > 1 else (np.floor(sv[inside]).astype(np.int64) & 65535)
+        assert (weights != 0).all()                                   # between pixels, along a side that has two
+        assert gr.warp_margin(gr.cam_of(cal.cfg()), h, w, **P)[0] > 0.25
+    _check_warp(case)
 
 
 @gpu
