@@ -1727,6 +1727,65 @@ int av_egoflow_update(av_ctx* ctx, av_stream_t stream, const av_egoflow_cfg* cfg
                       int w, const uint8_t* bgr, uint8_t* patches, uint32_t* valid, av_egoflow_tile* tiles, av_egoflow_motion* motion,
                       av_egoflow_state* state, double* z, uint8_t* mode);
 
+/* ---- Rig odometry (opt-in): a vehicle's ego motion from the road pixels of all K cameras of its rig ------------------------------
+ * The patch and match stages are av_egoflow_patch and av_egoflow_match over V * K cameras (camera k of vehicle v is camera
+ * v * K + k, as in av_rig_fuse).  The solve below fits every camera's tiles together in the VEHICLE frame: a wide baseline for the
+ * yaw, the motion of the vehicle's origin rather than of a camera's ground point (the lever arm falls out of the algebra), a
+ * measurement when no single camera has enough tiles, and a camera whose whole patch shows another vehicle is dropped.
+ *
+ * av_rig_egoflow_solve: one workgroup per vehicle, one wave per camera; reads the match's fields of tiles [V*K][n_tiles], sets flag
+ * bits 2 and 3, writes motion [V] and info [V].  float64, every operation rounded on its own (no FMA), in the order written.
+ *   1. vote and gate, per camera: exactly av_egoflow_solve's vote, mode and gate on that camera's table, its "accepted" included
+ *      (the (dy, dx) of cameras with different yaws cannot share a histogram).  Bit 2 on the gated tiles; info.cam_accepted[k],
+ *      cam_gated[k], cam_vote_dy[k], cam_vote_dx[k].
+ *   2. rows in the vehicle frame: a gated tile with centre (f, l) and av_egoflow_solve's displacement (d_f, d_l) under the mount
+ *      (c, s, mx, my) of its camera, as av_rig_fuse writes it:
+ *        X = (mx + c*f) - s*l;   Y = (my + s*f) + c*l;   DX = c*d_f - s*d_l;   DY = s*d_f + c*d_l
+ *      The model is D = T + Omega J P, the camera's small-angle form: with d = t + omega J p in the camera's frame and
+ *      P = M + R p, D = R d, it gives T = R t - omega J M and Omega = omega.
+ *   3. fit(set): av_egoflow_solve's fit with (X, Y, DX, DY) for (f, l, d_f, d_l) and the same pivot test.  Each camera's sums as
+ *      there (per lane in tile order, then the wave's fixed tree); the cameras' sums added in the order k = 0 .. K - 1.
+ *   4. hypotheses: h_0 = fit(all gated rows of the vehicle), h_(1+k) = fit(camera k's gated rows); singular ones are dropped.
+ *      count_i = the number of the vehicle's gated rows with !(r_X r_X + r_Y r_Y > (inlier_px m_per_px)^2) under h_i, where
+ *      r_X = DX - (T_f - Omega Y), r_Y = DY - (T_l + Omega X).  info.hyp_count[i] = count_i, or -1 where h_i was dropped or is
+ *      absent (i > K).  The best hypothesis has the largest count, among equals the smallest i: info.hypothesis.  None regular:
+ *      motion all 0 except n_accepted and n_gated, info.hypothesis = -1, no bit 3.
+ *   5. final fit: inliers = the gated rows within the limit under the best hypothesis (bit 3); info.cam_inliers[k]; info.views
+ *      has bit k set when camera k has at least one inlier.  B = fit(inliers): t_f, t_l, omega (the motion of the vehicle's origin
+ *      in the previous frame's VEHICLE frame); rms over the inliers under B (the cameras' sums of squares added in the order
+ *      k = 0 .. K - 1); n_inliers the count; valid = B regular && n_inliers >= min_inliers.  B singular: t_f = t_l = omega = rms = 0.
+ *      n_accepted and n_gated are the cameras' sums; vote_dy = vote_dx = 0.
+ * With K = 1 and the identity mount (1, 0, 0, 0) this is av_egoflow_solve step for step: X = f and DX = d_f exactly, h_0 = h_1.
+ *   mounts DEVICE [V][K]; tiles [V*K][n_tiles]; motion [V]; info [V]
+ * AV_EINVAL before any launch: a null pointer; n_vehicles < 1; n_cams not in 1 .. 8; n_vehicles * n_cams > 65535; a cfg that
+ * av_egoflow_tiles refuses. */
+typedef struct {
+    int32_t hypothesis;        /* the best hypothesis: 0 pooled, 1 + k camera k's, -1 none regular */
+    int32_t views;             /* bit k: camera k has an inlier */
+    int32_t reserved[2];       /* 0 */
+    int32_t cam_accepted[8], cam_gated[8], cam_inliers[8];     /* per camera; 0 at k >= K */
+    int32_t cam_vote_dy[8], cam_vote_dx[8];                    /* every camera's own mode; 0 at k >= K */
+    int32_t hyp_count[9];      /* count_i; -1: dropped or absent */
+    int32_t pad;               /* 0 */
+} av_rig_egoflow_info;         /* 216 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(av_rig_egoflow_info) == 216, "av_rig_egoflow_info is 54 int32");
+#else
+_Static_assert(sizeof(av_rig_egoflow_info) == 216, "av_rig_egoflow_info is 54 int32");
+#endif
+int av_rig_egoflow_solve(av_ctx* ctx, av_stream_t stream, const av_egoflow_cfg* cfg, int n_vehicles, int n_cams,
+                         const av_rig_mount* mounts, av_egoflow_tile* tiles, av_egoflow_motion* motion, av_rig_egoflow_info* info);
+
+/* av_egoflow_update for a rig, enqueued on `stream`; no allocation, no host round trip: the patch and match stages over the V * K
+ * cameras, av_rig_egoflow_solve, and av_egoflow_measure's stage over the V vehicles.  state [V], z [V][4] and mode [V] are the
+ * VEHICLE's: the pose is that of the vehicle's origin.  patches [V*K][2][gh][gw] is the ping-pong pair; every camera's slot follows
+ * its vehicle's frame counter, state[cam / K].frames & 1.  ground DEVICE [V*K], bgr [V*K][h][w][3] RECTIFIED frames, valid
+ * [V*K][gh][vw], tiles [V*K][n_tiles], motion [V], info [V].  The solve's checks, and h, w >= 1. */
+int av_rig_egoflow_update(av_ctx* ctx, av_stream_t stream, const av_egoflow_cfg* cfg, const av_ground_cfg* ground,
+                          const av_rig_mount* mounts, int n_vehicles, int n_cams, int h, int w, const uint8_t* bgr, uint8_t* patches,
+                          uint32_t* valid, av_egoflow_tile* tiles, av_egoflow_motion* motion, av_rig_egoflow_info* info,
+                          av_egoflow_state* state, double* z, uint8_t* mode);
+
 #ifdef __cplusplus
 }
 #endif

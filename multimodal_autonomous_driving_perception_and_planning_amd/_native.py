@@ -95,6 +95,10 @@ EGOFLOW_MOTION_FIELDS = [("t_f", "<f8"), ("t_l", "<f8"), ("omega", "<f8"), ("rms
 EGOFLOW_MOTION_BYTES = 64
 EGOFLOW_STATE_FIELDS = [("x", "<f8"), ("y", "<f8"), ("psi", "<f8"), ("frames", "<i4"), ("reserved", "<i4")]          # 32 bytes
 EGOFLOW_STATE_BYTES = 32
+RIG_EGOFLOW_INFO_FIELDS = [("hypothesis", "<i4"), ("views", "<i4"), ("reserved", "<i4", (2,)), ("cam_accepted", "<i4", (8,)),
+                           ("cam_gated", "<i4", (8,)), ("cam_inliers", "<i4", (8,)), ("cam_vote_dy", "<i4", (8,)),
+                           ("cam_vote_dx", "<i4", (8,)), ("hyp_count", "<i4", (9,)), ("pad", "<i4")]      # av_rig_egoflow_info
+RIG_EGOFLOW_INFO_BYTES = 216
 
 
 class RigTrackCfg(C.Structure):
@@ -458,6 +462,9 @@ _SIGS = [
     ("av_egoflow_solve", C.c_int, [vp, vp, C.POINTER(EgoflowCfg), C.c_int, vp, vp]),
     ("av_egoflow_measure", C.c_int, [vp, vp, C.POINTER(EgoflowCfg), C.c_int, vp, vp, vp, vp]),
     ("av_egoflow_update", C.c_int, [vp, vp, C.POINTER(EgoflowCfg), vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
+    ("av_rig_egoflow_solve", C.c_int, [vp, vp, C.POINTER(EgoflowCfg), C.c_int, C.c_int, vp, vp, vp, vp]),
+    ("av_rig_egoflow_update", C.c_int, [vp, vp, C.POINTER(EgoflowCfg), vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp,
+                                        vp, vp, vp, vp]),
 ]
 
 # entry points added by later translation units; bound when present in the header list below

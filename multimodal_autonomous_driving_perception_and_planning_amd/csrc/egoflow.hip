@@ -6,7 +6,9 @@
 //            (2R+1)^2 candidates per tile: the hot kernel
 //   solve    vote, gate, least-squares rigid motion with one rejection round: one wave per camera
 //   measure  pose integration and the (z, mode) the Kalman stage reads
-// The header states every stage's arithmetic; DESIGN.md 7s has the layout and the measurements.
+// The header states every stage's arithmetic; DESIGN.md 7s has the layout and the measurements.  egoflow_dev.h declares what
+// rigflow.hip (a rig's cameras fitted together) shares: the checked geometry, the patch, match and measure launches,
+// and the solve's pieces.
 //
 // match, mapping: one wave per tile, four tiles per workgroup, each wave with its own LDS region and no data shared between waves:
 //   cur  T*T bytes          the tile, packed four pixels to a word
@@ -19,23 +21,13 @@
 // absolute differences to the candidate's accumulator.  Lanes with consecutive dx read the same or adjacent words of one window row.
 // The kernel is a template over T/4 so that these loops unroll.  The argmin is a wave minimum of (SAD << 10 | c): the smallest SAD,
 // and among equals the smallest c, which is the first in row-major (dy, dx) order.
-#include "common.h"
+#include "egoflow_dev.h"
 #include "ground_dev.h"
 
 #include <cmath>
 
-namespace {
+namespace egoflow {
 
-constexpr int MATCH_WAVES = 4;                  // tiles per workgroup of the match kernel
-constexpr int MAX_T = 32, MAX_R = 15, MAX_SIDE = 4096, MAX_BINS = (2 * MAX_R + 1) * (2 * MAX_R + 1);
-constexpr int MATCH_K = (MAX_BINS + 63) / 64;   // candidates per lane of the match kernel, at most
-
-struct Geom {
-    int gh, gw, vw;                             // patch rows, columns, validity words per row
-    int T, R, ty, tx, n_tiles;
-};
-
-// the header's checks; *g only on success
 int geometry(const av_egoflow_cfg* c, const char* who, Geom* g) {
     AV_REQUIRE(c, AV_EINVAL, "%s: null cfg", who);
     AV_REQUIRE(c->gh >= 1 && c->gw >= 1 && c->gh <= MAX_SIDE && c->gw <= MAX_SIDE, AV_EINVAL, "%s: gh and gw must be 1 .. %d", who,
@@ -58,8 +50,20 @@ int geometry(const av_egoflow_cfg* c, const char* who, Geom* g) {
     return AV_OK;
 }
 
-// the slot of the ping-pong pair that camera `cam`'s current frame uses (0 for the stage entries, which have no state)
-__device__ __forceinline__ int slot_of(const av_egoflow_state* __restrict__ st, int cam) { return st ? (st[cam].frames & 1) : 0; }
+}  // namespace egoflow
+
+namespace {
+
+using namespace egoflow;
+
+constexpr int MATCH_WAVES = 4;                  // tiles per workgroup of the match kernel
+constexpr int MATCH_K = (MAX_BINS + 63) / 64;   // candidates per lane of the match kernel, at most
+
+// the slot of the ping-pong pair that camera `cam`'s current frame uses (0 for the stage entries, which have no state): the frame
+// counter is that of state cam / per (per cameras share a state: a rig's follow their vehicle's)
+__device__ __forceinline__ int slot_of(const av_egoflow_state* __restrict__ st, int cam, int per) {
+    return st ? (st[cam / per].frames & 1) : 0;
+}
 
 // ---- stage 1: patch ------------------------------------------------------------------------------------------------------------
 // a wave makes 64 adjacent pixels of one patch row: one byte per lane, and the wave's ballot is the row's two validity words.
@@ -68,7 +72,8 @@ template <bool WIDE>
 __global__ void __launch_bounds__(256) egoflow_patch_kernel(const av_ground_cfg* __restrict__ ground, int h, int w,
                                                             const uint8_t* __restrict__ bgr, Geom g, double f_far, double m_per_px,
                                                             uint8_t* __restrict__ patch, size_t cam_stride,
-                                                            const av_egoflow_state* __restrict__ st, uint32_t* __restrict__ valid) {
+                                                            const av_egoflow_state* __restrict__ st, int cams_per_state,
+                                                            uint32_t* __restrict__ valid) {
     const int cam = blockIdx.z, lane = lane_id();
     const int r = blockIdx.y * 4 + (int)(threadIdx.x >> 6);
     const int c = blockIdx.x * 64 + lane;
@@ -86,7 +91,7 @@ __global__ void __launch_bounds__(256) egoflow_patch_kernel(const av_ground_cfg*
         }
     }
     const unsigned long long bits = __ballot(ok);
-    if (c < g.gw) patch[(size_t)cam * cam_stride + (size_t)slot_of(st, cam) * g.gh * g.gw + (size_t)r * g.gw + c] = (uint8_t)gray;
+    if (c < g.gw) patch[(size_t)cam * cam_stride + (size_t)slot_of(st, cam, cams_per_state) * g.gh * g.gw + (size_t)r * g.gw + c] = (uint8_t)gray;
     if (valid) {
         const int w0 = (int)blockIdx.x * 2;                         // w0 < vw, since the block has a column below gw
         uint32_t* vr = valid + ((size_t)cam * g.gh + r) * g.vw;
@@ -115,7 +120,7 @@ template <int TW>
 __global__ void __launch_bounds__(64 * MATCH_WAVES) egoflow_match_kernel(Geom g, int min_texture, double f_far, double m_per_px,
                                                                          const uint8_t* __restrict__ cur_base,
                                                                          const uint8_t* __restrict__ prev_base, size_t cam_stride,
-                                                                         const av_egoflow_state* __restrict__ st,
+                                                                         const av_egoflow_state* __restrict__ st, int cams_per_state,
                                                                          const uint32_t* __restrict__ valid,
                                                                          av_egoflow_tile* __restrict__ tiles) {
     extern __shared__ __align__(16) uint8_t lds[];
@@ -128,7 +133,7 @@ __global__ void __launch_bounds__(64 * MATCH_WAVES) egoflow_match_kernel(Geom g,
     uint32_t* curw = reinterpret_cast<uint32_t*>(mine);                             // [T][TW]
     uint32_t* winw = reinterpret_cast<uint32_t*>(mine + T * T);                     // [W2][WPW] + 1
     int* sadv = reinterpret_cast<int*>(mine + T * T + W2 * WPW * 4 + 4);            // [C]
-    const int slot = slot_of(st, cam);
+    const int slot = slot_of(st, cam, cams_per_state);
     const size_t plane = (size_t)g.gh * g.gw;
     const uint8_t* cur = cur_base + (size_t)cam * cam_stride + (size_t)slot * plane;
     const uint8_t* prev = prev_base + (size_t)cam * cam_stride + (st ? (size_t)(slot ^ 1) * plane : (size_t)0);
@@ -244,75 +249,31 @@ __global__ void __launch_bounds__(64 * MATCH_WAVES) egoflow_match_kernel(Geom g,
 }
 
 // ---- stage 3: solve ------------------------------------------------------------------------------------------------------------
-struct Fit {
-    double tf, tl, om;
-    int n;
-    bool ok;
-};
-struct Disp {
-    double df, dl;
-};
-__device__ __forceinline__ Disp displacement(const av_egoflow_tile& t, double m_per_px) {
-    return Disp{-((double)t.dy + t.sub_dy) * m_per_px, ((double)t.dx + t.sub_dx) * m_per_px};
-}
-__device__ __forceinline__ double residual2(const av_egoflow_tile& t, const Disp& d, const Fit& fit) {
-    const double rf = d.df - (fit.tf - fit.om * t.l), rl = d.dl - (fit.tl + fit.om * t.f);
-    return rf * rf + rl * rl;
-}
-// the header's fit from one lane's partial sums
-__device__ __forceinline__ Fit fit_of(int n_lane, double sf, double sl, double q, double b1, double b2, double b3) {
-    Fit r{0.0, 0.0, 0.0, wave_sum_i(n_lane), false};
-    const double Sf = wave_sum_dpp(sf), Sl = wave_sum_dpp(sl), Q = wave_sum_dpp(q);
-    const double B1 = wave_sum_dpp(b1), B2 = wave_sum_dpp(b2), B3 = wave_sum_dpp(b3);
-    if (r.n < 1) return r;
-    const double n = (double)r.n;
-    const double den = (Q - (Sl * Sl) / n) - (Sf * Sf) / n;
-    if (!(den > 1e-9 * Q)) return r;
-    r.om = ((B3 + (Sl * B1) / n) - (Sf * B2) / n) / den;
-    r.tf = (B1 + r.om * Sl) / n;
-    r.tl = (B2 - r.om * Sf) / n;
-    r.ok = true;
-    return r;
-}
-
+// (the pieces -- accepted, vote, displacement, the fit's elimination, the residual -- are egoflow_dev.h's, shared with rigflow.hip)
 __global__ void __launch_bounds__(64) egoflow_solve_kernel(int n_tiles, int R, int gate, double m_per_px, double thr2, int min_inliers,
                                                            av_egoflow_tile* __restrict__ tiles, av_egoflow_motion* __restrict__ motion) {
     __shared__ int hist[MAX_BINS];
-    const int cam = blockIdx.x, lane = lane_id(), C1 = 2 * R + 1, C = C1 * C1;
+    const int cam = blockIdx.x, lane = lane_id(), C1 = 2 * R + 1;
     av_egoflow_tile* tl = tiles + (size_t)cam * n_tiles;
-    // a row counts as accepted only with (dy, dx) inside the search range: the histogram's bounds do not rest on the caller's rows
-    auto accepted = [&](const av_egoflow_tile& t) { return (t.flags & AV_EGOFLOW_ACCEPTED) && abs(t.dy) <= R && abs(t.dx) <= R; };
-    for (int b = lane; b < C; b += 64) hist[b] = 0;
-    __syncthreads();
-    int n_acc = 0;
-    for (int k = lane; k < n_tiles; k += 64) {
-        const av_egoflow_tile t = tl[k];
-        if (accepted(t)) atomicAdd(&hist[(t.dy + R) * C1 + (t.dx + R)], 1), ++n_acc;
-    }
-    n_acc = wave_sum_i(n_acc);
-    __syncthreads();
-    unsigned key = 0;                                               // count << 10 | (1023 - bin): the fullest bin, then the first
-    for (int b = lane; b < C; b += 64)
-        if (hist[b] > 0) key = max(key, ((unsigned)hist[b] << 10) | (unsigned)(1023 - b));
-    key = wave_max_u32(key);
-    const int bin = key ? 1023 - (int)(key & 1023u) : R * C1 + R;
+    int n_acc;
+    const int bin = vote(hist, tl, n_tiles, R, lane, n_acc);
     const int my = bin / C1 - R, mx = bin % C1 - R;
-    auto gated = [&](const av_egoflow_tile& t) { return accepted(t) && abs(t.dy - my) <= gate && abs(t.dx - mx) <= gate; };
+    auto gated = [&](const av_egoflow_tile& t) { return accepted(t, R) && abs(t.dy - my) <= gate && abs(t.dx - mx) <= gate; };
 
     // the two fits: over the gated tiles, then over the first fit's inliers
     Fit fit[2] = {{0.0, 0.0, 0.0, 0, false}, {0.0, 0.0, 0.0, 0, false}};
     for (int pass = 0; pass < 2; ++pass) {
         if (pass == 1 && !fit[0].ok) break;                         // (uniform)
         int n = 0;
-        double sf = 0.0, sl = 0.0, q = 0.0, b1 = 0.0, b2 = 0.0, b3 = 0.0;
+        Sums s{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         for (int k = lane; k < n_tiles; k += 64) {
             const av_egoflow_tile t = tl[k];
             if (!gated(t)) continue;
             const Disp d = displacement(t, m_per_px);
-            if (pass == 1 && residual2(t, d, fit[0]) > thr2) continue;
-            ++n, sf += t.f, sl += t.l, q += t.f * t.f + t.l * t.l, b1 += d.df, b2 += d.dl, b3 += t.f * d.dl - t.l * d.df;
+            if (pass == 1 && residual2(t.f, t.l, d, fit[0]) > thr2) continue;
+            ++n, add_row(s, t.f, t.l, d);
         }
-        fit[pass] = fit_of(n, sf, sl, q, b1, b2, b3);
+        fit[pass] = fit_of_sums(wave_sum_i(n), wave_sums(s));
     }
     // flags, and the rms of the final fit's residuals over its tiles
     int n_gated = 0;
@@ -323,9 +284,9 @@ __global__ void __launch_bounds__(64) egoflow_solve_kernel(int n_tiles, int R, i
         if (gated(t)) {
             fl |= AV_EGOFLOW_GATED, ++n_gated;
             const Disp d = displacement(t, m_per_px);
-            if (fit[0].ok && !(residual2(t, d, fit[0]) > thr2)) {
+            if (fit[0].ok && !(residual2(t.f, t.l, d, fit[0]) > thr2)) {
                 fl |= AV_EGOFLOW_INLIER;
-                if (fit[1].ok) ss += residual2(t, d, fit[1]);
+                if (fit[1].ok) ss += residual2(t.f, t.l, d, fit[1]);
             }
         }
         tl[k].flags = fl;
@@ -367,36 +328,43 @@ __global__ void __launch_bounds__(64) egoflow_measure_kernel(int n_cams, double 
 }
 
 // ---- launches (arguments already checked) -----------------------------------------------------------------------------------------
-int launch_patch(av_stream_t stream, const av_egoflow_cfg* c, const Geom& g, const av_ground_cfg* ground, int n_cams, int h, int w,
-                 const uint8_t* bgr, uint8_t* patch, size_t cam_stride, const av_egoflow_state* st, uint32_t* valid) {
-    const dim3 grid((unsigned)((g.gw + 63) / 64), (unsigned)((g.gh + 3) / 4), (unsigned)n_cams);
-    const auto kernel = w >= 2 ? egoflow_patch_kernel<true> : egoflow_patch_kernel<false>;
-    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, as_stream(stream), ground, h, w, bgr, g, c->f_far, c->m_per_px, patch,
-                       cam_stride, st, valid);
-    AV_LAUNCH_CHECK();
-    return AV_OK;
-}
-int launch_match(av_stream_t stream, const av_egoflow_cfg* c, const Geom& g, int n_cams, const uint8_t* cur, const uint8_t* prev,
-                 size_t cam_stride, const av_egoflow_state* st, const uint32_t* valid, av_egoflow_tile* tiles) {
-    const dim3 grid((unsigned)((g.n_tiles + MATCH_WAVES - 1) / MATCH_WAVES), (unsigned)n_cams);
-    const size_t lds = (size_t)MATCH_WAVES * match_wave_bytes(g.T, g.R);                  // at most 4 * 8848 bytes
-#define EGO_MATCH(TW)                                                                                                             \
-    case TW:                                                                                                                      \
-        hipLaunchKernelGGL(egoflow_match_kernel<TW>, grid, dim3(64 * MATCH_WAVES), lds, as_stream(stream), g, c->min_texture, c->f_far, \
-                           c->m_per_px, cur, prev, cam_stride, st, valid, tiles);                                                \
-        break;
-    switch (g.T / 4) {                                              // T is a multiple of 4 in 4 .. 32
-        EGO_MATCH(1) EGO_MATCH(2) EGO_MATCH(3) EGO_MATCH(4) EGO_MATCH(5) EGO_MATCH(6) EGO_MATCH(7) EGO_MATCH(8)
-    }
-#undef EGO_MATCH
-    AV_LAUNCH_CHECK();
-    return AV_OK;
-}
 int launch_solve(av_stream_t stream, const av_egoflow_cfg* c, const Geom& g, int n_cams, av_egoflow_tile* tiles,
                  av_egoflow_motion* motion) {
     const double thr = c->inlier_px * c->m_per_px;
     hipLaunchKernelGGL(egoflow_solve_kernel, dim3((unsigned)n_cams), dim3(64), 0, as_stream(stream), g.n_tiles, g.R, c->gate_px,
                        c->m_per_px, thr * thr, c->min_inliers, tiles, motion);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
+}  // namespace
+
+namespace egoflow {
+
+int launch_patch(av_stream_t stream, const av_egoflow_cfg* c, const Geom& g, const av_ground_cfg* ground, int n_cams, int h, int w,
+                 const uint8_t* bgr, uint8_t* patch, size_t cam_stride, const av_egoflow_state* st, int cams_per_state,
+                 uint32_t* valid) {
+    const dim3 grid((unsigned)((g.gw + 63) / 64), (unsigned)((g.gh + 3) / 4), (unsigned)n_cams);
+    const auto kernel = w >= 2 ? egoflow_patch_kernel<true> : egoflow_patch_kernel<false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, as_stream(stream), ground, h, w, bgr, g, c->f_far, c->m_per_px, patch,
+                       cam_stride, st, cams_per_state, valid);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+int launch_match(av_stream_t stream, const av_egoflow_cfg* c, const Geom& g, int n_cams, const uint8_t* cur, const uint8_t* prev,
+                 size_t cam_stride, const av_egoflow_state* st, int cams_per_state, const uint32_t* valid,
+                 av_egoflow_tile* tiles) {
+    const dim3 grid((unsigned)((g.n_tiles + MATCH_WAVES - 1) / MATCH_WAVES), (unsigned)n_cams);
+    const size_t lds = (size_t)MATCH_WAVES * match_wave_bytes(g.T, g.R);                  // at most 4 * 8848 bytes
+#define EGO_MATCH(TW)                                                                                                             \
+    case TW:                                                                                                                      \
+        hipLaunchKernelGGL(egoflow_match_kernel<TW>, grid, dim3(64 * MATCH_WAVES), lds, as_stream(stream), g, c->min_texture, c->f_far, \
+                           c->m_per_px, cur, prev, cam_stride, st, cams_per_state, valid, tiles);                                \
+        break;
+    switch (g.T / 4) {                                              // T is a multiple of 4 in 4 .. 32
+        EGO_MATCH(1) EGO_MATCH(2) EGO_MATCH(3) EGO_MATCH(4) EGO_MATCH(5) EGO_MATCH(6) EGO_MATCH(7) EGO_MATCH(8)
+    }
+#undef EGO_MATCH
     AV_LAUNCH_CHECK();
     return AV_OK;
 }
@@ -408,7 +376,8 @@ int launch_measure(av_stream_t stream, const av_egoflow_cfg* c, int n_cams, cons
     return AV_OK;
 }
 
-}  // namespace
+
+}  // namespace egoflow
 
 #define EGO_CAMS(who) AV_REQUIRE(n_cams >= 1 && n_cams <= 65535, AV_EINVAL, who ": n_cams must be 1 .. 65535")
 
@@ -427,7 +396,7 @@ extern "C" int av_egoflow_patch(av_ctx* ctx, av_stream_t stream, const av_egoflo
     AV_REQUIRE(h >= 1 && w >= 1, AV_EINVAL, "av_egoflow_patch: h and w must be >= 1");
     Geom g;
     if (int rc = geometry(cfg, "av_egoflow_patch", &g)) return rc;
-    return launch_patch(stream, cfg, g, ground, n_cams, h, w, bgr, patch, (size_t)g.gh * g.gw, nullptr, valid);
+    return launch_patch(stream, cfg, g, ground, n_cams, h, w, bgr, patch, (size_t)g.gh * g.gw, nullptr, 1, valid);
 }
 
 extern "C" int av_egoflow_match(av_ctx* ctx, av_stream_t stream, const av_egoflow_cfg* cfg, int n_cams, const uint8_t* cur,
@@ -436,7 +405,7 @@ extern "C" int av_egoflow_match(av_ctx* ctx, av_stream_t stream, const av_egoflo
     EGO_CAMS("av_egoflow_match");
     Geom g;
     if (int rc = geometry(cfg, "av_egoflow_match", &g)) return rc;
-    return launch_match(stream, cfg, g, n_cams, cur, prev, (size_t)g.gh * g.gw, nullptr, valid, tiles);
+    return launch_match(stream, cfg, g, n_cams, cur, prev, (size_t)g.gh * g.gw, nullptr, 1, valid, tiles);
 }
 
 extern "C" int av_egoflow_solve(av_ctx* ctx, av_stream_t stream, const av_egoflow_cfg* cfg, int n_cams, av_egoflow_tile* tiles,
@@ -466,8 +435,8 @@ extern "C" int av_egoflow_update(av_ctx* ctx, av_stream_t stream, const av_egofl
     Geom g;
     if (int rc = geometry(cfg, "av_egoflow_update", &g)) return rc;
     const size_t pair = (size_t)2 * g.gh * g.gw;
-    if (int rc = launch_patch(stream, cfg, g, ground, n_cams, h, w, bgr, patches, pair, state, valid)) return rc;
-    if (int rc = launch_match(stream, cfg, g, n_cams, patches, patches, pair, state, valid, tiles)) return rc;
+    if (int rc = launch_patch(stream, cfg, g, ground, n_cams, h, w, bgr, patches, pair, state, 1, valid)) return rc;
+    if (int rc = launch_match(stream, cfg, g, n_cams, patches, patches, pair, state, 1, valid, tiles)) return rc;
     if (int rc = launch_solve(stream, cfg, g, n_cams, tiles, motion)) return rc;
     return launch_measure(stream, cfg, n_cams, motion, state, z, mode);
 }

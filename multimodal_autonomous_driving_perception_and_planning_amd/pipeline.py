@@ -1397,7 +1397,7 @@ class RigLoop:
     def __init__(self, n_vehicles, rig, h=720, w=1280, model="random:0", precision="fp16", dcap=64, obstacles="moving_tracks",
                  class_map="reference", lane_camera=0, fuse_kw=None, tracker_kw=None, kf_kw=None, planner_kw=None, obstacle_kw=None,
                  track_filter_kw=None, names=None, device=0, track=False, rig_track_kw=None, tags=None, tag_capacity=4096,
-                 tag_columns=False, **other):
+                 tag_columns=False, ego=None, ego_kw=None, **other):
         """rig: a perception.CameraRig.  obstacles: "moving_tracks", "filtered_tracks" or "tracks", CameraLoop's modes (a rig
         without obstacles has nothing to fuse).  lane_camera: the index of the camera whose lane fit is the vehicle's reference path
         (av_lane_paths_ground through rig.vehicle_calibration(lane_camera)), None for no path; its mount may not be yawed beyond
@@ -1413,7 +1413,13 @@ class RigLoop:
         records), with no host round trip -- the class of every track travels beside the obstacle rows through the cameras' lists,
         the fuse and the tracker (the _cls entry points), the maneuver tagger runs on the ego filter's output with the lane
         camera's offset, and, when class_map is the reference map (CameraLoop's rule), av_rig_interact tags the tracks
-        (self.tagger, a tagging.RigInteractionDetector).  tags="all" is refused: the scene classifier describes one camera."""
+        (self.tagger, a tagging.RigInteractionDetector).  tags="all" is refused: the scene classifier describes one camera.
+        ego: None -- the ego Kalman stage's measurement is the caller's (load_measurements) -- or "ground_flow": it is measured
+        from the road pixels of all K cameras' consecutive rectified frames, fitted together in the vehicle frame
+        (self.odometry, a perception.RigOdometry with ego_kw's settings; a rig with lenses is refused, as
+        CameraLoop(ego=) refuses one).  The stages are enqueued on the ego stream in front of av_kf_step, which reads their z and
+        mode in place; load_measurements then raises, and results() has ego_motion [V, 3], ego_valid [V], ego_pose [V, 3] (the
+        vehicle origin's), ego_inliers [V] and ego_views [V] (bit k: camera k has an inlier)."""
         from .perception.calibration import CameraRig, ground_table
         from .tracking.rig_tracker import RigTracker, check_shape, rig_track_cfg
         for k in other:
@@ -1422,6 +1428,13 @@ class RigLoop:
             raise TypeError("RigLoop() got an unexpected keyword argument %r" % k)
         if not isinstance(rig, CameraRig):
             raise ValueError("RigLoop: rig is a perception.CameraRig")
+        if ego not in (None, "ground_flow"):
+            raise ValueError('RigLoop: ego is None or "ground_flow"')
+        if ego is None and ego_kw is not None:
+            raise ValueError('RigLoop: ego_kw belongs to ego="ground_flow"')
+        if ego is not None:
+            from .perception.ground_odometry import egoflow_cfg
+            egoflow_cfg(**(ego_kw or {}))                                           # (ValueError for a bad geometry)
         if obstacles not in ("moving_tracks", "filtered_tracks", "tracks"):
             raise ValueError('RigLoop: obstacles is "moving_tracks", "filtered_tracks" or "tracks"')
         V, K = int(n_vehicles), rig.K
@@ -1503,6 +1516,12 @@ class RigLoop:
         self.surround_view = self.surround_cover = None     # enqueue_surround_view
         self._surround = self._surround_key = self._surround_ids = None
         self._stepped = False
+        self.odometry = None
+        if ego is not None:
+            from .perception.rig_odometry import RigOdometry
+            self.odometry = RigOdometry(rig, V, h, w, device=device, ctx=self.ego.ctx, **(ego_kw or {}))
+            self.ego.set_measurement_source(self.odometry.z.view(V, 1, 4), self.odometry.mode.view(V, 1),
+                                            producer=lambda stream: self.odometry.enqueue(self.cams.cam.frames, stream))
         self.tags, self.tag_log, self.tagger = tags, None, None
         if tags is not None:
             from .perception.detector import ObjectDetector
@@ -1521,6 +1540,8 @@ class RigLoop:
 
     def load_measurements(self, z):
         """z: float64 [V, 1, 4] (or [V, 4]) ego measurements of the next step (HotLoop.load_measurements)."""
+        if self.odometry is not None:
+            raise RuntimeError('RigLoop(ego="ground_flow") measures the ego motion from the frames: there is nothing to load')
         self.ego.load_measurements(z)
 
     def enqueue_fuse(self, stream=None):
@@ -1665,10 +1686,15 @@ class RigLoop:
         cameras that saw each fused obstacle), n_skip [V] and, with a lane camera, ref_paths [V, 50, 2], n_ref [V], lane_offset [V].
         With tags: track_cls [V, tcap] and fused_cls [V, K * tcap] (the class id behind each tracked / fused row, -1 past the count),
         interactions (one tagging.InteractionTags per vehicle) and interaction_summary (av_interaction_summary [V]); the last two are
-        None when class_map is not the reference map."""
+        None when class_map is not the reference map.
+        With ego="ground_flow": ego_motion [V, 3] (t_f, t_l, omega), ego_valid [V], ego_pose [V, 3], ego_inliers [V], ego_views [V]."""
         self.synchronize()
         hot, V, K = self.cams.hot, self.V, self.K
         out = self.ego.results()
+        if self.odometry is not None:
+            e = self.odometry.results()
+            out["ego_motion"], out["ego_valid"], out["ego_pose"] = e["motion"], e["valid"], e["pose"]
+            out["ego_inliers"], out["ego_views"] = e["n_inliers"], e["views"]
         out["cam_obstacles"] = hot.obstacles.cpu().numpy().reshape(V, K, self.tcap, self.cols)
         out["cam_n_obs"] = hot.n_obs.cpu().numpy().reshape(V, K)
         out["n_off"] = hot.n_off.cpu().numpy().reshape(V, K)
