@@ -1786,6 +1786,102 @@ int av_rig_egoflow_update(av_ctx* ctx, av_stream_t stream, const av_egoflow_cfg*
                           uint32_t* valid, av_egoflow_tile* tiles, av_egoflow_motion* motion, av_rig_egoflow_info* info,
                           av_egoflow_state* state, double* z, uint8_t* mode);
 
+/* ---- Road memory (opt-in): the surround panel's unseen pixels from earlier frames, through the measured pose --------------------
+ * av_rig_surround stitches what the cameras see NOW; where none looks (under the vehicle, beside its sills) the panel has a hole.
+ * The road there was in view some frames ago.  Per vehicle a WORLD-anchored rolling canvas takes every frame's seen panel pixels
+ * through the pose the odometry integrated (av_egoflow_state), and the panel's unseen pixels are read back out of it: a pixel is
+ * resampled exactly twice, whatever its age.  Three stages, each an entry of its own, and av_roadmem_step, which enqueues all
+ * three.  All positions float64, every operation rounded on its own (no FMA), in the order written.
+ *
+ * World cells of pitch m = cfg.m_per_px: cell (i, j), i and j integers of either sign, has its centre at
+ *   xc = ((double)i + 0.5) * m;   yc = ((double)j + 0.5) * m
+ * Canvas, per vehicle: canvas uint8 [V][N][N][4] (b, g, r, 0: a cell is one aligned 32-bit word) and stamp uint32 [V][N][N]
+ * (0: never seen; else the vehicle's frame counter when the cell was last written).  Cell (i, j) lives at [i mod N][j mod N], the
+ * mathematical (non-negative) mod.  The window of a vehicle is i in i0 .. i0 + N - 1, j in j0 .. j0 + N - 1, with
+ *   i0 = (int32)floor(x / m) - N / 2;   j0 = (int32)floor(y / m) - N / 2          (x, y: the pose of this frame)
+ * The panel is av_rig_surround's: gh x gw pixels of pm = cfg.panel_m_per_px metres, row 0 at x_far metres ahead. */
+typedef struct {
+    int32_t n;                 /* N: a multiple of 16 in 16 .. 4096 */
+    int32_t max_age;           /* a cell older than this many frames is not read back; >= 0 */
+    double m_per_px;           /* the cells' pitch m, metres; > 0, finite */
+    int32_t gh, gw;            /* the panel's rows and columns; >= 1 */
+    double x_far;              /* the panel's x_far; finite */
+    double panel_m_per_px;     /* the panel's pitch pm; > 0, finite */
+    uint8_t fill[3];           /* b, g, r of an unseen pixel that is not remembered */
+    uint8_t reserved[5];       /* 0 */
+} av_roadmem_cfg;              /* 48 bytes */
+/* Persistent per-vehicle state (device): the window's origin, the frame counter F and the status.  All zero = reset.  status bit 0:
+ * the pose was out of range on the last frame: !(|x / m| <= 2^30 && |y / m| <= 2^30), a NaN among them.  Such a frame is a reset:
+ * nothing is written to canvas or stamp, and the state becomes {0, 0, 0, 1}. */
+typedef struct {
+    int32_t i0, j0, frames, status;
+} av_roadmem_state;            /* 16 bytes */
+typedef struct {
+    double x, y, cs, sn;       /* the vehicle origin's place in the world, cos and sin of its heading */
+    int32_t reset, reserved;   /* reset != 0: what the canvas holds no longer lies where the pose says */
+} av_roadmem_pose;             /* 40 bytes */
+
+/* Host only.  AV_EINVAL for a null cfg, n not a multiple of 16 in 16 .. 4096, max_age < 0, m_per_px or panel_m_per_px not > 0 and
+ * finite, x_far not finite, gh or gw < 1, a reserved byte not 0.  Every device entry below makes these checks before any launch and
+ * before the context is looked at, and refuses a null pointer other than stream (and mode), n_vehicles outside 1 .. 65535, and a
+ * panel that shares a byte with canvas or stamp. */
+int av_roadmem_check(const av_roadmem_cfg* cfg);
+
+/* Stage 1, pose: pose[v] = {x, y copied from state[v]; cs = cos(psi); sn = sin(psi); reset = (mode != NULL && mode[v] == 2); 0}.
+ * The frame on which the odometry measured nothing (av_egoflow_measure's mode 2, the first frame among them) is a reset: the
+ * integrated pose did not follow the vehicle over it.  The only transcendental calls of the road memory are here; the pixel stages
+ * take (x, y, cs, sn) as given, the way av_rig_surround takes the mounts'.
+ *   state [V] (the odometry's, read), mode [V] or NULL, pose [V] */
+int av_roadmem_pose_from(av_ctx* ctx, av_stream_t stream, int n_vehicles, const av_egoflow_state* state, const uint8_t* mode,
+                         av_roadmem_pose* pose);
+
+/* Stage 2, update (the hot kernel).  Per vehicle, with the state {i0, j0, frames, status} of the previous frame and this frame's
+ * pose: out of range (above): state = {0, 0, 0, 1}, nothing else.  Otherwise
+ *   fresh = reset || frames == 0;   F = fresh ? 1 : frames + 1;   (i0n, j0n) = the window's origin from the pose
+ * and for every cell (i, j) of the NEW window:
+ *   1 entered = fresh || i < i0 || i >= i0 + N || j < j0 || j >= j0 + N        (the OLD origin); entered: stamp = 0
+ *   2 dx = xc - x;  dy = yc - y;  X = cs*dx + sn*dy;  Y = cs*dy - sn*dx             (av_rig_surround's mount order)
+ *   3 pr = (x_far - X) / pm - 0.5;  pc = Y / pm + (double)gw / 2.0 - 0.5;  tr = floor(pr * 65536.0 + 0.5);  tc likewise
+ *     inside = 0 <= tr <= (gh-1) * 65536 && 0 <= tc <= (gw-1) * 65536               (a NaN fails)
+ *   4 r0 = tr >> 16, wr = tr & 65535, r1 = min(r0 + 1, gh - 1); c0, wc, c1 likewise
+ *     seen = inside && cover[r0][c0] != 0 && cover[r0][c1] != 0 && cover[r1][c0] != 0 && cover[r1][c1] != 0
+ *   5 seen: each channel av_ground_warp's bilinear rule on the four panel taps,
+ *       ((p00 (65536-wc) + p01 wc)(65536-wr) + (p10 (65536-wc) + p11 wc) wr + 2^31) >> 32,
+ *     byte 3 = 0, stamp = F (a cell that entered and is seen on the same frame ends with F).  Not seen: the colour stays.
+ * then state = {i0n, j0n, F, 0}.
+ *   pose [V]; panel [V][gh][gw][3]: the stitched panel BEFORE any fill, read; cover [V][gh][gw], read; state [V]; canvas; stamp
+ * The counter is 32 bits: a vehicle is reset before 2^31 frames. */
+int av_roadmem_update(av_ctx* ctx, av_stream_t stream, const av_roadmem_cfg* cfg, int n_vehicles, const av_roadmem_pose* pose,
+                      const uint8_t* panel, const uint8_t* cover, av_roadmem_state* state, uint8_t* canvas, uint32_t* stamp);
+
+/* Stage 3, fill: the state is the one av_roadmem_update left for this frame (i0, j0, F = frames), the pose the same.  For every
+ * panel pixel (r, c):
+ *   cover != 0: age = 0, the pixel is not touched.
+ *   cover == 0:
+ *   1 X = x_far - ((double)r + 0.5) * pm;   Y = (((double)c + 0.5) - (double)gw / 2.0) * pm         (av_rig_surround's)
+ *   2 xw = (x + cs*X) - sn*Y;   yw = (y + sn*X) + cs*Y
+ *   3 ti = floor((xw / m - 0.5) * 65536.0 + 0.5);  tj likewise from yw;  ia = ti >> 16 (arithmetic, of a 64-bit integer: the floor
+ *     for negatives), wi = ti & 65535;  ja, wj likewise
+ *   4 remembered = F != 0 && ia >= i0 && ia + 1 < i0 + N && ja >= j0 && ja + 1 < j0 + N    (tested on ti, tj as doubles: a NaN or a
+ *       position outside 64 bits fails) && the four cells (ia | ia + 1, ja | ja + 1) have stamp != 0
+ *       && F - min(stamp) <= max_age
+ *   5 remembered: each channel the bilinear rule above on the four cells, weights wj across and wi down;
+ *       age = min(F - min(stamp), 254)
+ *   6 else: the pixel becomes fill, age = 255
+ *   panel [V][gh][gw][3] in place; age [V][gh][gw].  Also AV_EINVAL: ceil(gh / 16) above 65535 (av_rig_surround's tile mapping). */
+int av_roadmem_fill(av_ctx* ctx, av_stream_t stream, const av_roadmem_cfg* cfg, int n_vehicles, const av_roadmem_pose* pose,
+                    const av_roadmem_state* state, const uint8_t* canvas, const uint32_t* stamp, const uint8_t* cover, uint8_t* panel,
+                    uint8_t* age);
+
+/* Stages 1 - 3 enqueued on `stream`; no allocation, no host round trip.  ego_state [V] and mode [V] (or NULL) are the odometry's
+ * (av_rig_egoflow_update's or av_egoflow_update's state and mode), pose [V] is written and then read. */
+int av_roadmem_step(av_ctx* ctx, av_stream_t stream, const av_roadmem_cfg* cfg, int n_vehicles, const av_egoflow_state* ego_state,
+                    const uint8_t* mode, av_roadmem_pose* pose, uint8_t* panel, const uint8_t* cover, av_roadmem_state* state,
+                    uint8_t* canvas, uint32_t* stamp, uint8_t* age);
+/* Zeroes the state of vehicle `vehicle` (0 .. n_vehicles - 1), or of every vehicle with -1: one hipMemsetAsync on `stream`.  The
+ * canvas needs no clearing: after a reset every cell enters. */
+int av_roadmem_reset(av_ctx* ctx, av_stream_t stream, int n_vehicles, int vehicle, av_roadmem_state* state);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,6 +101,19 @@ RIG_EGOFLOW_INFO_FIELDS = [("hypothesis", "<i4"), ("views", "<i4"), ("reserved",
 RIG_EGOFLOW_INFO_BYTES = 216
 
 
+class RoadmemCfg(C.Structure):
+    """av_roadmem_cfg: the road memory's canvas (n cells a side, of m_per_px metres), max_age in frames, the surround panel's
+    geometry (gh, gw, x_far, panel_m_per_px) and the fill colour (b, g, r); 48 bytes."""
+    _fields_ = [("n", C.c_int32), ("max_age", C.c_int32), ("m_per_px", C.c_double), ("gh", C.c_int32), ("gw", C.c_int32),
+                ("x_far", C.c_double), ("panel_m_per_px", C.c_double), ("fill", C.c_uint8 * 3), ("reserved", C.c_uint8 * 5)]
+
+
+ROADMEM_STATE_FIELDS = [("i0", "<i4"), ("j0", "<i4"), ("frames", "<i4"), ("status", "<i4")]                          # 16 bytes
+ROADMEM_STATE_BYTES = 16
+ROADMEM_POSE_FIELDS = [("x", "<f8"), ("y", "<f8"), ("cs", "<f8"), ("sn", "<f8"), ("reset", "<i4"), ("reserved", "<i4")]   # 40 bytes
+ROADMEM_POSE_BYTES = 40
+
+
 class RigTrackCfg(C.Structure):
     """av_rig_track_cfg: the vehicle-frame tracker's filter, gate and life cycle (seconds, metres); 72 bytes."""
     _fields_ = [("dt", C.c_double), ("q_accel", C.c_double), ("r_meas", C.c_double), ("r_range", C.c_double), ("p0_pos", C.c_double),
@@ -465,6 +478,12 @@ _SIGS = [
     ("av_rig_egoflow_solve", C.c_int, [vp, vp, C.POINTER(EgoflowCfg), C.c_int, C.c_int, vp, vp, vp, vp]),
     ("av_rig_egoflow_update", C.c_int, [vp, vp, C.POINTER(EgoflowCfg), vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp,
                                         vp, vp, vp, vp]),
+    ("av_roadmem_check", C.c_int, [C.POINTER(RoadmemCfg)]),
+    ("av_roadmem_pose_from", C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
+    ("av_roadmem_update", C.c_int, [vp, vp, C.POINTER(RoadmemCfg), C.c_int, vp, vp, vp, vp, vp, vp]),
+    ("av_roadmem_fill", C.c_int, [vp, vp, C.POINTER(RoadmemCfg), C.c_int, vp, vp, vp, vp, vp, vp, vp]),
+    ("av_roadmem_step", C.c_int, [vp, vp, C.POINTER(RoadmemCfg), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    ("av_roadmem_reset", C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
 ]
 
 # entry points added by later translation units; bound when present in the header list below

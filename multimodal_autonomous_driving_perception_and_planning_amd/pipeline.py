@@ -1515,6 +1515,7 @@ class RigLoop:
             self.ego.set_reference_paths(self.ref_paths, self.n_ref)
         self.surround_view = self.surround_cover = None     # enqueue_surround_view
         self._surround = self._surround_key = self._surround_ids = None
+        self.surround_age = self.road_memory = None         # enqueue_surround_view(memory=True)
         self._stepped = False
         self.odometry = None
         if ego is not None:
@@ -1629,7 +1630,8 @@ class RigLoop:
         if sync:
             self.synchronize()
 
-    def enqueue_surround_view(self, gh=800, gw=800, x_far=40.0, m_per_px=0.1, fill=(0, 0, 0), blend="feather", overlay=True):
+    def enqueue_surround_view(self, gh=800, gw=800, x_far=40.0, m_per_px=0.1, fill=(0, 0, 0), blend="feather", overlay=True,
+                              memory=False, memory_kw=None):
         """The rig's own picture of the last step(), on the ego stream (call it behind step(); the next camera half waits for that
         stream): self.surround_view uint8 [V, gh, gw, 3], every vehicle's K frames (cams.cam.frames: rectified, read and never
         written) stitched into one top-down panel in the vehicle's frame -- row 0 at x_far metres ahead, m_per_px metres per pixel,
@@ -1637,8 +1639,23 @@ class RigLoop:
         (visualization.SurroundView, av_rig_surround) -- and self.surround_cover uint8 [V, gh, gw], bit k where camera k saw the
         pixel.  overlay: what the ego loop planned around is drawn over the panel (av_rig_view_build, av_raster_draw): the tracked
         list coloured by track id with track=True, else the fused list, each obstacle a ring of its radius and, with velocities, its
-        way in one second; the lane camera's reference path; the best trajectory; the ego vehicle."""
+        way in one second; the lane camera's reference path; the best trajectory; the ego vehicle.
+        memory=True (with ego="ground_flow" only: the measured pose anchors it): the pixels no camera sees -- the road under the
+        vehicle, beside its sills -- are filled from earlier frames between the stitch and the overlay (self.road_memory, a
+        visualization.RoadMemory with memory_kw's size, cell_m, max_age and fill: a world-anchored canvas per vehicle, DESIGN 7u;
+        av_roadmem_step on the odometry's own state and mode, no host round trip), and self.surround_age uint8 [V, gh, gw] is 0
+        where a camera sees the pixel, its age in frames where it is remembered, 255 where it is `fill`; surround_cover stays the
+        cameras'.  The frame on which the odometry measured nothing starts the canvas anew.  While memory is on neither the
+        geometry nor fill, blend or memory_kw may change between calls."""
         from .visualization.surround_view import SurroundView, check_panel, surround_cfg
+        if not isinstance(memory, (bool, np.bool_)):
+            raise ValueError("RigLoop: memory is True or False")
+        if memory_kw is not None and not memory:
+            raise ValueError("RigLoop: memory_kw belongs to memory=True")
+        if memory_kw is not None and not (isinstance(memory_kw, dict) and set(memory_kw) <= {"size", "cell_m", "max_age", "fill"}):
+            raise ValueError("RigLoop: memory_kw is None or a dict of size, cell_m, max_age and fill")
+        if memory and self.odometry is None:
+            raise ValueError('RigLoop: memory=True needs ego="ground_flow": there is no measured pose to anchor the road memory to')
         if not self._stepped:
             raise RuntimeError("enqueue_surround_view draws what a step() left behind: call it after one")
         if not isinstance(overlay, (bool, np.bool_)):
@@ -1647,14 +1664,23 @@ class RigLoop:
         surround_cfg(x_far, m_per_px, fill, blend)                                  # (ValueError for a setting outside its range)
         ego, V = self.ego, self.V
         key = (int(gh), int(gw), float(x_far), float(m_per_px), tuple(int(c) for c in fill), blend)
+        if memory:
+            from .visualization.road_memory import roadmem_cfg
+            mkw = dict(dict(fill=key[4]), **(memory_kw or {}))
+            roadmem_cfg(key[0], key[1], key[2], key[3], **mkw)                      # (ValueError for a bad geometry)
+            key = key + (tuple(sorted((k, tuple(v) if k == "fill" else v) for k, v in mkw.items())),)
+            if getattr(self, "_surround_key", None) is not None and len(self._surround_key) == len(key) and self._surround_key != key:
+                raise ValueError("RigLoop: the surround view's settings (geometry, fill, blend, memory_kw) may not change while memory is "
+                                 "on: the canvas and what it remembers belong to them")
         with torch.cuda.stream(ego.stream):                 # the view's buffers and the ids below are made on the stream that fills them
             if getattr(self, "_surround_key", None) != key:
                 self._surround = SurroundView(self.rig, V, self.h, self.w, gh=key[0], gw=key[1], x_far=key[2], m_per_px=key[3],
-                                              fill=key[4], blend=blend, ctx=ego.ctx)
+                                              fill=key[4], blend=blend, ctx=ego.ctx, memory=mkw if memory else None)
                 self._surround_key = key
             sv = self._surround
-            sv.render(self.cams.cam.frames, stream=ego._s)
+            sv.render(self.cams.cam.frames, stream=ego._s, ego=(self.odometry.state, self.odometry.mode) if memory else None)
             self.surround_view, self.surround_cover = sv.panel, sv.cover
+            self.surround_age, self.road_memory = sv.age, sv.memory
             if not overlay:
                 return
             ids = None

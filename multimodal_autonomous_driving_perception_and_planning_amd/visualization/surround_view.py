@@ -51,17 +51,25 @@ def check_panel(n_vehicles, h, w, gh, gw):
 
 class SurroundView:
     def __init__(self, rig, n_vehicles, h, w, gh=800, gw=800, x_far=40.0, m_per_px=0.1, fill=(0, 0, 0), blend="feather", ctx=None,
-                 device=0):
+                 device=0, memory=None):
         """rig: a perception.CameraRig; n_vehicles rigs of it, frames of h x w pixels (RECTIFIED: a camera's lens plays no part
         here).  The panel is gh x gw pixels of m_per_px metres, its top edge x_far metres ahead of the vehicle's origin and the
         vehicle's forward axis down the middle column (so x_far = gh * m_per_px / 2 puts the vehicle in the centre).  fill: (b, g, r)
-        where no camera sees the road; blend: "feather" or "nearest"."""
+        where no camera sees the road; blend: "feather" or "nearest".  memory: None, or a dict of RoadMemory's settings (size,
+        cell_m, max_age, fill -- the panel's by default; {} for the defaults): render(..., ego=) then fills the pixels no camera
+        sees from earlier frames (self.memory, a visualization.RoadMemory) and self.age says how old each pixel is."""
         import torch
         from ..perception.calibration import CameraRig, ground_table
         if not isinstance(rig, CameraRig):
             raise ValueError("SurroundView: rig is a perception.CameraRig")
         check_panel(n_vehicles, h, w, gh, gw)
         self.cfg = surround_cfg(x_far, m_per_px, fill, blend)
+        if memory is not None:
+            from .road_memory import roadmem_cfg
+            if not isinstance(memory, dict) or not set(memory) <= {"size", "cell_m", "max_age", "fill"}:
+                raise ValueError("SurroundView: memory is None or a dict of size, cell_m, max_age and fill")
+            memory = dict(dict(fill=fill), **memory)
+            roadmem_cfg(gh, gw, x_far, m_per_px, **memory)                         # (ValueError for a bad geometry, without a GPU)
         if not torch.cuda.is_available():
             raise RuntimeError("SurroundView needs a HIP device; this package has no CPU path")
         self.rig, self.V, self.K, self.h, self.w, self.gh, self.gw = rig, int(n_vehicles), rig.K, int(h), int(w), int(gh), int(gw)
@@ -74,17 +82,30 @@ class SurroundView:
         self.cover = torch.zeros(self.V, self.gh, self.gw, dtype=torch.uint8, device=d)
         self.prims = self.n_prims = None                    # the overlay's list, sized by the first draw()
         self._prim_shape = None
+        self.memory = self.age = None
+        if memory is not None:
+            from .road_memory import RoadMemory
+            self.memory = RoadMemory(self.V, self.gh, self.gw, x_far, m_per_px, ctx=self.ctx, **memory)
+            self.age = self.memory.age
         torch.cuda.current_stream(d).synchronize()          # the buffers are zero-filled before another stream writes them
 
     @staticmethod
     def _stream(stream):
         return stream if isinstance(stream, C.c_void_p) else nat.stream_handle(stream)
 
-    def render(self, frames, stream=None):
+    def render(self, frames, stream=None, ego=None):
         """frames: a contiguous uint8 device tensor [V * K, h, w, 3] (camera k of vehicle v is frame v * K + k), read and never
         written.  Fills self.panel [V, gh, gw, 3] and self.cover [V, gh, gw] (bit k: camera k saw the pixel).  Enqueued on `stream`
-        (a torch stream or a raw handle; default: the current one).  Returns self.panel."""
+        (a torch stream or a raw handle; default: the current one).  Returns self.panel.
+        With memory=: ego = (state, mode), the odometry's device tensors of these frames (RigOdometry.state uint8 [V, 32] and
+        .mode uint8 [V], or None for mode); the pixels no camera sees are then filled from the road memory and self.age uint8
+        [V, gh, gw] is 0 where a camera sees the pixel, its age in frames where it is remembered and 255 where it is `fill`;
+        self.cover stays the cameras' cover."""
         import torch
+        if (ego is not None) != (self.memory is not None):
+            raise ValueError("SurroundView.render: ego=(state, mode) comes with memory=, and memory= needs it")
+        if ego is not None and not (isinstance(ego, (tuple, list)) and len(ego) == 2):
+            raise ValueError("SurroundView.render: ego is (state, mode)")
         if not (torch.is_tensor(frames) and frames.is_cuda and frames.is_contiguous() and frames.dtype == torch.uint8
                 and tuple(frames.shape) == (self.V * self.K, self.h, self.w, 3)):
             raise ValueError("SurroundView.render: frames is a contiguous uint8 device tensor [%d, %d, %d, 3]"
@@ -92,6 +113,8 @@ class SurroundView:
         nat.check(self.L.av_rig_surround(self.ctx.handle, self._stream(stream), C.byref(self.cfg), self.V, self.K, nat.ptr(self.mounts),
                                          nat.ptr(self.ground), self.h, self.w, nat.ptr(frames), self.gh, self.gw, nat.ptr(self.panel),
                                          nat.ptr(self.cover)))
+        if self.memory is not None:
+            self.memory.step(self.panel, self.cover, ego[0], mode=ego[1], stream=self._stream(stream))
         return self.panel
 
     def draw(self, plan_state, obstacles, n_obs, ids=None, ref_path=None, n_ref=None, waypoints=None, order=None, stream=None):
