@@ -1882,6 +1882,161 @@ int av_roadmem_step(av_ctx* ctx, av_stream_t stream, const av_roadmem_cfg* cfg, 
  * canvas needs no clearing: after a reset every cell enters. */
 int av_roadmem_reset(av_ctx* ctx, av_stream_t stream, int n_vehicles, int vehicle, av_roadmem_state* state);
 
+/* ---- Road lanes (opt-in): the lane boundaries in metres from the Hough segments of all K cameras of a rig ------------------------
+ * Every camera's lane chain leaves its Hough segments in the lane workspace (AV_LANE_VIEW_SEGMENTS / _NSEG).  av_road_lanes carries
+ * them onto the road and through the mounts into the VEHICLE frame (av_rig_fuse's: X forward, Y lateral, positive towards image
+ * right), pools them over the cameras, finds the lane boundaries Y = a0 + a1 X + a2 X^2 there by two votes and a gated refit,
+ * picks the ego lane, follows it from frame to frame through the measured ego motion and writes the planner's reference path and
+ * the maneuver tagger's offset; no host round trip.  One workgroup per vehicle, one wave per camera.  float64, every operation
+ * rounded on its own (no FMA), in the order written; model(a, X) = (a0 + a1*X) + a2*(X*X).
+ *
+ * Sums: a "sum over the rows" below is taken per lane (lane = i & 63 of the row index i, rows of a lane in ascending i, starting
+ * from the first term), then over the 64 lanes of the camera's wave by the fixed tree of av_egoflow_solve (adjacent pairs, six
+ * levels; a lane without a term holds 0.0), then over the cameras in the order k = 0 .. K - 1 starting from camera 0's sum. */
+typedef struct {
+    double min_len;            /* 0.5   m: a shorter segment is no row */
+    double slope_max;          /* 0.5:  |dY| <= slope_max dX */
+    double vote_len;           /* 0.25  m per vote */
+    double x_vote;             /* 15    m: the rows that vote have Xm <= x_vote */
+    double slope_tol;          /* 0.15 */
+    double y_max;              /* 8     m: the offset histogram covers [-y_max, y_max) */
+    double min_sep;            /* 2.0   m between accepted offset peaks */
+    double gate;               /* 0.4   m */
+    double span_quad;          /* 10    m: the X extent from which a boundary is fitted as a quadratic */
+    double w_min, w_max;       /* 2.5, 5.0 m: a lane's width */
+    double default_width;      /* 3.5   m */
+    double alpha;              /* 0.7:  the weight of the prediction in the smoothed fit */
+    double jump;               /* 1.0   m */
+    double path_near, path_far;/* 2, 40 m */
+    int32_t min_votes;         /* 16 */
+    int32_t max_coast;         /* 10 frames */
+    int32_t one_sided;         /* 1: a lone side gives the other at the last width */
+    int32_t n_points;          /* 50; 2 .. 64 */
+} av_road_lanes_cfg;           /* 144 bytes */
+#define AV_ROAD_LANES_MAX_BOUNDS 8
+#define AV_ROAD_BOUND_QUAD 1       /* av_road_lane_bound.flags: the last fit was quadratic */
+#define AV_ROAD_BOUND_KEPT 2       /* in some round the fit was singular or the boundary had no member: it kept its model */
+#define AV_ROAD_BOUND_LEFT 4       /* the ego lane's measured left boundary */
+#define AV_ROAD_BOUND_RIGHT 8      /* the ego lane's measured right boundary */
+typedef struct {
+    double a0, a1, a2;
+    double x_min, x_max;       /* of its members' end points */
+    double length;             /* the members' summed length, metres */
+    int32_t n_members;
+    int32_t views;             /* bit k: camera k contributed a member */
+    int32_t flags;
+    int32_t reserved;          /* 0 */
+} av_road_lane_bound;          /* 64 bytes */
+#define AV_ROAD_LANE 1             /* av_road_lanes_row.status: there is a lane (both sides) */
+#define AV_ROAD_ONE_SIDED 2        /* one side is the other shifted by the width */
+#define AV_ROAD_COAST_LEFT 4       /* the left side is its prediction */
+#define AV_ROAD_COAST_RIGHT 8
+#define AV_ROAD_CHANGE_LEFT 16     /* both sides jumped towards -Y by a lane's width */
+#define AV_ROAD_CHANGE_RIGHT 32
+#define AV_ROAD_NO_VOTER 64        /* the frame had no voter: no measurement */
+typedef struct {
+    double left[3], right[3], centre[3];
+    double width;
+    double lane_offset;        /* -centre[0]; NaN without a lane */
+    double heading;            /* -atan(centre[1]) */
+    double curvature;          /* (2 centre[2]) / (q sqrt(q)), q = 1 + centre[1]^2 */
+    int32_t n_bounds, lane_count, lane_index, views, status, reserved;
+} av_road_lanes_row;           /* 128 bytes */
+typedef struct {
+    int32_t cam_rows[8];       /* rows per camera; 0 at k >= K */
+    int32_t n_over;            /* segments beyond scap */
+    int32_t n_off;             /* segments with an end point not on_road */
+    int32_t n_short;           /* on the road, shorter than min_len */
+    int32_t n_steep;           /* long enough, dX == 0 or |dY| > slope_max dX */
+    int32_t n_voters;          /* rows with Xm <= x_vote */
+    int32_t dir_bin;           /* the direction vote's peak, -1 without a voter */
+    int32_t n_cand;            /* the offset vote's candidate peaks */
+    int32_t n_peaks;           /* ... accepted (<= 8) */
+    double m_star;             /* 0 without a voter */
+} av_road_lanes_info;          /* 72 bytes */
+/* Persistent per-vehicle state (device).  All zero = reset. */
+typedef struct {
+    double left[3], right[3];  /* the smoothed polynomials */
+    double width;              /* the last smoothed width of a measured pair */
+    double xmax_left, xmax_right;
+    int32_t has_left, has_right, miss_left, miss_right, has_width, frames;
+} av_road_lanes_state;         /* 96 bytes */
+
+/* The stage per vehicle v, camera k of it being list v * n_cams + k (ground, segments, nseg) with the mount mounts[v][k]:
+ * 1 rows.  n = clamp(nseg, 0, max_segments); camera k contributes segments i = 0 .. min(n, scap) - 1; info.n_over sums
+ *   max(n - scap, 0).  A segment (x1, y1, x2, y2), int32 rectified pixels taken as doubles: both end points by av_ground_cfg's
+ *   projection (f, l, on_road), then X = (mx + c*f) - s*l;  Y = (my + s*f) + c*l.  The end points are swapped when X2 < X1; then
+ *     dX = X2 - X1;  dY = Y2 - Y1;  len = sqrt(dX*dX + dY*dY)
+ *   not both on_road: n_off.  Else !(len >= min_len): n_short.  Else !(dX > 0 && |dY| <= slope_max*dX): n_steep.  Else a row:
+ *     m = dY / dX;  Xm = (X1 + X2) * 0.5;  Ym = (Y1 + Y2) * 0.5;  w = (int)min(max(floor(len / vote_len), 1.0), 255.0)
+ * 2 direction vote.  voters = rows with Xm <= x_vote.  bin_m = clamp((int)floor((m + slope_max) * (32.0 / slope_max)), 0, 63);
+ *   h[bin_m] += w;  h'[i] = h[i-1] + 2 h[i] + h[i+1] (zeros outside);  the peak pm: the largest h', among equals the smallest i.
+ *   m* = (sum over the voters with |bin_m - pm| <= 1 of (double)w * m) / (double)(the sum of their w).  No voter: no boundary,
+ *   status bit AV_ROAD_NO_VOTER, step 6 with neither side measured.
+ * 3 offset vote.  Voters with |m - m*| <= slope_tol:  b = Ym - m* * Xm;  t = (b + y_max) * (32.0 / y_max);  they vote when
+ *   t >= 0 && t < 64, bin_b = (int)floor(t), with w; h' as above.  Candidates: h'[i] >= min_votes && h'[i] > h'[i-1] &&
+ *   h'[i] >= h'[i+1].  Repeatedly the candidate with the largest h' (among equals the smallest i) is accepted and every candidate
+ *   j with (double)|j - i| * (y_max / 32.0) < min_sep leaves, until none remains or 8 are accepted.  Boundaries p = 0 .. in
+ *   ascending bin:  a0 = (sum over those voters with |bin_b - peak_p| <= 1 of (double)w * b) / (double)(sum of their w), a1 = m*,
+ *   a2 = 0.
+ * 4 grow and refit, rounds r = 0, 1, 2 with the range x_vote, 2.0 * x_vote, unbounded.  A row with Xm <= range (round 2: every
+ *   row) is admissible for p when r1 = |Y1 - model(p, X1)| <= gate and r2 = |Y2 - model(p, X2)| <= gate; it joins the admissible
+ *   p with the smallest max(r1, r2), among equals the smallest p.  Per boundary, the sums over its members, each member adding its
+ *   two end points in the order 1, 2 with the weight len:
+ *     S0 += len; S1 += len*X; S2 += len*(X*X); S3 += len*((X*X)*X); S4 += len*((X*X)*(X*X)); T0 += len*Y; T1 += len*(X*Y);
+ *     T2 += len*((X*X)*Y)
+ *   n = its members, x_min = min X1, x_max = max X2, views.  n == 0: the model stays, AV_ROAD_BOUND_KEPT.  Else, quadratic when
+ *   n >= 3 && x_max - x_min >= span_quad:
+ *     c11 = S2 - (S1*S1)/S0;  c12 = S3 - (S1*S2)/S0;  c22 = S4 - (S2*S2)/S0;  d1 = T1 - (S1*T0)/S0;  d2 = T2 - (S2*T0)/S0
+ *     singular unless c11 > 1e-9 * S2;   e22 = c22 - (c12*c12)/c11;   singular unless e22 > 1e-9 * S4   (av_egoflow_solve's test)
+ *     a2 = (d2 - (c12*d1)/c11) / e22;   a1 = (d1 - c12*a2) / c11;   a0 = ((T0 - a1*S1) - a2*S2) / S0
+ *   else a line: c11, d1 and its pivot test as above;  a1 = d1 / c11;  a0 = (T0 - a1*S1) / S0;  a2 = 0.
+ *   Singular: the model stays, AV_ROAD_BOUND_KEPT.  After round 2 a boundary with n == 0 is dropped, the others keep their order:
+ *   bounds[v][0 .. n_bounds-1] with length = S0 * 0.5; entries at or past n_bounds are zero.
+ * 5 the ego lane.  L = the boundary with the largest a0 < 0, R = the one with the smallest a0 >= 0 (among equals the smallest
+ *   index).  With both and !(w_min <= a0_R - a0_L <= w_max) the farther one is not measured: R when -a0_L <= a0_R, else L.
+ *   A measured side's flags take AV_ROAD_BOUND_LEFT / _RIGHT.
+ * 6 following.  mv = motion != NULL && motion[v].valid != 0.  pred(a) with (t_f, t_l, omega) of motion[v] when mv:
+ *     a0' = ((a0 + a1*t_f) + a2*(t_f*t_f)) - t_l;   a1' = (a1 + (2.0*a2)*t_f) - omega;   a2' = a2;   xmax' = xmax - t_f
+ *   else a and xmax themselves.  Per side, left first:
+ *     measured, has history: d = new_a0 - a0';  |d| <= jump: a_i = alpha*a_i' + (1.0 - alpha)*new_a_i;  else a = new, the side
+ *       "jumped by d".  Measured without history: a = new.  Either way xmax = the boundary's x_max, has = 1, miss = 0.
+ *     not measured, has history: miss += 1;  miss > max_coast: the side is gone (all its fields 0);  else a = a', xmax = xmax',
+ *       AV_ROAD_COAST_LEFT / _RIGHT.
+ *   Both measured: state.width = right a0 - left a0 (smoothed), has_width = 1.  Both jumped, both d < 0 (left) or both d > 0
+ *   (right), and both |d| in [w_min, w_max]: AV_ROAD_CHANGE_LEFT / _RIGHT.  frames += 1.
+ *   Exactly one side measured, the other without history after the above, and cfg.one_sided: the other side of the OUTPUT (not of
+ *   the state) is the measured side's smoothed fit with a0 -/+ W (left = right - W, right = left + W), W = state.width if has_width
+ *   else default_width, and its xmax; AV_ROAD_ONE_SIDED.  There is a lane (AV_ROAD_LANE) when both sides of the output exist.
+ * 7 outputs.  row: left, right (zeros for a missing side), and with a lane centre_i = (left_i + right_i) * 0.5, width =
+ *   right_0 - left_0, lane_offset, heading, curvature as in the struct (without: 0, lane_offset NaN); n_bounds; views = the OR of the
+ *   measured sides' boundaries' views.  The chain: from a measured L the boundaries at index L-1, L-2, ... continue it while
+ *   a0[j+1] - a0[j] lies in [w_min, w_max]; from a measured R likewise upwards; lane_index = the left count,
+ *   lane_count = 1 + both counts with a lane, else both 0.
+ *   The path: x_end = min(path_far, min(xmax_left, xmax_right));  n_ref = n_points when there is a lane and
+ *   x_end - path_near >= 1.0, else 0;  step = (x_end - path_near) / (double)(n_points - 1);  X_i = path_near + (double)i*step;
+ *   Y_i = model(centre, X_i), placed as av_rig_fuse places a cluster with (x0, y0, h) = plan_state[v]:
+ *     ref_path[v][i] = ((x0 + X cos h) + Y cos(h + pi/2), (y0 + X sin h) + Y sin(h + pi/2));  rows at or past n_ref are not written.
+ *   lane_offset[v] = row.lane_offset.  bounds [V][8], info [V], row [V], n_ref [V], lane_offset [V] are always written.
+ *
+ *   ground DEVICE [V*K]; mounts DEVICE [V][K]; segments int32 [V*K][max_segments][4]; nseg int32 [V*K]; motion [V] or NULL;
+ *   plan_state [V][4]; state [V]; bounds [V][8]; info [V]; row [V]; ref_path [V][rcap][2]; n_ref [V]; lane_offset [V]
+ * AV_EINVAL before any launch: a null pointer other than motion; n_vehicles outside 1 .. 65535; n_cams outside 1 .. 8;
+ * max_segments < 1; scap outside 1 .. 256; cfg.n_points outside 2 .. min(rcap, 64); a cfg that av_road_lanes_check refuses.  The
+ * arguments are checked before the context is looked at. */
+/* Host only.  AV_EINVAL for a null cfg; a double not finite; min_len, vote_len, x_vote, slope_tol, y_max, min_sep, gate, span_quad,
+ * w_min, default_width, jump not > 0; slope_max not in (0, 4]; w_max < w_min; alpha not in [0, 1); path_near < 0 or path_far <=
+ * path_near; min_votes < 1; max_coast < 0; one_sided not 0 or 1; n_points not in 2 .. 64. */
+int av_road_lanes_check(const av_road_lanes_cfg* cfg);
+size_t av_road_lanes_state_bytes(void);        /* sizeof(av_road_lanes_state) */
+int av_road_lanes(av_ctx* ctx, av_stream_t stream, const av_road_lanes_cfg* cfg, int n_vehicles, int n_cams,
+                  const av_ground_cfg* ground, const av_rig_mount* mounts, int max_segments, int scap, const int32_t* segments,
+                  const int32_t* nseg, const av_egoflow_motion* motion, const double* plan_state, av_road_lanes_state* state,
+                  av_road_lane_bound* bounds, av_road_lanes_info* info, av_road_lanes_row* row, int rcap, double* ref_path,
+                  int32_t* n_ref, double* lane_offset);
+/* Zeroes the state of vehicle `vehicle` (0 .. n_vehicles - 1), or of every vehicle with -1: one hipMemsetAsync on `stream`. */
+int av_road_lanes_reset(av_ctx* ctx, av_stream_t stream, int n_vehicles, int vehicle, av_road_lanes_state* state);
+
 #ifdef __cplusplus
 }
 #endif

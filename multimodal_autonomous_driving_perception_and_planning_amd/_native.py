@@ -114,6 +114,36 @@ ROADMEM_POSE_FIELDS = [("x", "<f8"), ("y", "<f8"), ("cs", "<f8"), ("sn", "<f8"),
 ROADMEM_POSE_BYTES = 40
 
 
+class RoadLanesCfg(C.Structure):
+    """av_road_lanes_cfg: the road-lane stage's row tests, votes, gate, lane widths, smoothing and path (metres); 144 bytes."""
+    _fields_ = [(k, C.c_double) for k in ("min_len", "slope_max", "vote_len", "x_vote", "slope_tol", "y_max", "min_sep", "gate",
+                                          "span_quad", "w_min", "w_max", "default_width", "alpha", "jump", "path_near", "path_far")] + [
+        (k, C.c_int32) for k in ("min_votes", "max_coast", "one_sided", "n_points")]
+
+
+ROAD_LANES_DEFAULTS = dict(min_len=0.5, slope_max=0.5, vote_len=0.25, x_vote=15.0, slope_tol=0.15, y_max=8.0, min_sep=2.0, gate=0.4,
+                           span_quad=10.0, w_min=2.5, w_max=5.0, default_width=3.5, alpha=0.7, jump=1.0, path_near=2.0, path_far=40.0,
+                           min_votes=16, max_coast=10, one_sided=1, n_points=50)
+ROAD_LANES_MAX_BOUNDS, ROAD_LANES_MAX_SCAP = 8, 256
+ROAD_BOUND_QUAD, ROAD_BOUND_KEPT, ROAD_BOUND_LEFT, ROAD_BOUND_RIGHT = 1, 2, 4, 8                      # av_road_lane_bound.flags
+(ROAD_LANE, ROAD_ONE_SIDED, ROAD_COAST_LEFT, ROAD_COAST_RIGHT, ROAD_CHANGE_LEFT, ROAD_CHANGE_RIGHT,
+ ROAD_NO_VOTER) = 1, 2, 4, 8, 16, 32, 64                                                               # av_road_lanes_row.status
+ROAD_LANE_BOUND_FIELDS = [("a0", "<f8"), ("a1", "<f8"), ("a2", "<f8"), ("x_min", "<f8"), ("x_max", "<f8"), ("length", "<f8"),
+                          ("n_members", "<i4"), ("views", "<i4"), ("flags", "<i4"), ("reserved", "<i4")]               # 64 bytes
+ROAD_LANE_BOUND_BYTES = 64
+ROAD_LANES_ROW_FIELDS = [("left", "<f8", (3,)), ("right", "<f8", (3,)), ("centre", "<f8", (3,)), ("width", "<f8"),
+                         ("lane_offset", "<f8"), ("heading", "<f8"), ("curvature", "<f8"), ("n_bounds", "<i4"), ("lane_count", "<i4"),
+                         ("lane_index", "<i4"), ("views", "<i4"), ("status", "<i4"), ("reserved", "<i4")]               # 128 bytes
+ROAD_LANES_ROW_BYTES = 128
+ROAD_LANES_INFO_FIELDS = [("cam_rows", "<i4", (8,)), ("n_over", "<i4"), ("n_off", "<i4"), ("n_short", "<i4"), ("n_steep", "<i4"),
+                          ("n_voters", "<i4"), ("dir_bin", "<i4"), ("n_cand", "<i4"), ("n_peaks", "<i4"), ("m_star", "<f8")]  # 72 bytes
+ROAD_LANES_INFO_BYTES = 72
+ROAD_LANES_STATE_FIELDS = [("left", "<f8", (3,)), ("right", "<f8", (3,)), ("width", "<f8"), ("xmax_left", "<f8"), ("xmax_right", "<f8"),
+                           ("has_left", "<i4"), ("has_right", "<i4"), ("miss_left", "<i4"), ("miss_right", "<i4"), ("has_width", "<i4"),
+                           ("frames", "<i4")]                                                                         # 96 bytes
+ROAD_LANES_STATE_BYTES = 96
+
+
 class RigTrackCfg(C.Structure):
     """av_rig_track_cfg: the vehicle-frame tracker's filter, gate and life cycle (seconds, metres); 72 bytes."""
     _fields_ = [("dt", C.c_double), ("q_accel", C.c_double), ("r_meas", C.c_double), ("r_range", C.c_double), ("p0_pos", C.c_double),
@@ -484,6 +514,11 @@ _SIGS = [
     ("av_roadmem_fill", C.c_int, [vp, vp, C.POINTER(RoadmemCfg), C.c_int, vp, vp, vp, vp, vp, vp, vp]),
     ("av_roadmem_step", C.c_int, [vp, vp, C.POINTER(RoadmemCfg), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     ("av_roadmem_reset", C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
+    ("av_road_lanes_check", C.c_int, [C.POINTER(RoadLanesCfg)]),
+    ("av_road_lanes_state_bytes", C.c_size_t, []),
+    ("av_road_lanes", C.c_int, [vp, vp, C.POINTER(RoadLanesCfg), C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp,
+                                vp, C.c_int, vp, vp, vp]),
+    ("av_road_lanes_reset", C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
 ]
 
 # entry points added by later translation units; bound when present in the header list below

@@ -1397,7 +1397,7 @@ class RigLoop:
     def __init__(self, n_vehicles, rig, h=720, w=1280, model="random:0", precision="fp16", dcap=64, obstacles="moving_tracks",
                  class_map="reference", lane_camera=0, fuse_kw=None, tracker_kw=None, kf_kw=None, planner_kw=None, obstacle_kw=None,
                  track_filter_kw=None, names=None, device=0, track=False, rig_track_kw=None, tags=None, tag_capacity=4096,
-                 tag_columns=False, ego=None, ego_kw=None, **other):
+                 tag_columns=False, ego=None, ego_kw=None, lanes=None, lanes_kw=None, **other):
         """rig: a perception.CameraRig.  obstacles: "moving_tracks", "filtered_tracks" or "tracks", CameraLoop's modes (a rig
         without obstacles has nothing to fuse).  lane_camera: the index of the camera whose lane fit is the vehicle's reference path
         (av_lane_paths_ground through rig.vehicle_calibration(lane_camera)), None for no path; its mount may not be yawed beyond
@@ -1419,7 +1419,14 @@ class RigLoop:
         (self.odometry, a perception.RigOdometry with ego_kw's settings; a rig with lenses is refused, as
         CameraLoop(ego=) refuses one).  The stages are enqueued on the ego stream in front of av_kf_step, which reads their z and
         mode in place; load_measurements then raises, and results() has ego_motion [V, 3], ego_valid [V], ego_pose [V, 3] (the
-        vehicle origin's), ego_inliers [V] and ego_views [V] (bit k: camera k has an inlier)."""
+        vehicle origin's), ego_inliers [V] and ego_views [V] (bit k: camera k has an inlier).
+        lanes: None -- the reference path is the lane camera's, above -- or "road": the lane boundaries are found in metres in the
+        vehicle frame from the Hough segments of all K cameras (self.road_lanes, a perception.RoadLanes with lanes_kw's settings:
+        av_road_lanes_cfg's fields and scap), read in place from the cameras' lane workspace and followed from frame to
+        frame through the measured ego motion when ego="ground_flow".  It fills ref_paths / n_ref / lane_offset in the lane camera's
+        place, so lane_camera stays None or its default, and results() gains lane_bounds, lane_left, lane_right, lane_width,
+        lane_heading, lane_curvature, lane_count, lane_index, lane_views and lane_status.  A rig with lenses is welcome: the lane
+        chain sees rectified frames, so its segments are rectified pixels."""
         from .perception.calibration import CameraRig, ground_table
         from .tracking.rig_tracker import RigTracker, check_shape, rig_track_cfg
         for k in other:
@@ -1440,6 +1447,24 @@ class RigLoop:
         V, K = int(n_vehicles), rig.K
         if V < 1:
             raise ValueError("RigLoop: n_vehicles must be >= 1")
+        if lanes not in (None, "road"):
+            raise ValueError('RigLoop: lanes is None or "road"')
+        if lanes is None and lanes_kw is not None:
+            raise ValueError('RigLoop: lanes_kw belongs to lanes="road"')
+        if lanes is not None:
+            from .perception.road_lanes import check_shape as check_lanes_shape, road_lanes_cfg
+            if lanes_kw is not None and not isinstance(lanes_kw, dict):
+                raise ValueError("RigLoop: lanes_kw is None or a dict of av_road_lanes_cfg's fields and scap")
+            if lane_camera is not None and not (isinstance(lane_camera, (int, np.integer)) and not isinstance(lane_camera, bool)
+                                                and lane_camera == 0):
+                raise ValueError('RigLoop: lanes="road" takes the lanes from every camera and lane_camera=%r asks for one camera\'s: '
+                                 "leave lane_camera at None or its default" % (lane_camera,))
+            lane_camera = None
+            lkw = dict(lanes_kw or {})
+            lanes_scap = lkw.pop("scap", None)
+            road_lanes_cfg(**lkw)                                                   # (ValueError for a setting outside its range)
+            if lanes_scap is not None:
+                check_lanes_shape(V, K, 1 << 20, lanes_scap)
         if lane_camera is not None:
             if not (isinstance(lane_camera, (int, np.integer)) and 0 <= lane_camera < K):
                 raise ValueError("RigLoop: lane_camera is None or a camera index 0 .. %d" % (K - 1))
@@ -1512,6 +1537,20 @@ class RigLoop:
             self.ref_paths = torch.zeros(V, 50, 2, dtype=f64, device=d)
             self.n_ref = torch.zeros(V, dtype=i32, device=d)
             self.lane_offset = torch.full((V,), float("nan"), dtype=f64, device=d)
+            self.ego.set_reference_paths(self.ref_paths, self.n_ref)
+        self.road_lanes = None
+        if lanes is not None:
+            from .perception.road_lanes import RoadLanes
+            cam = self.cams.cam
+            self.road_lanes = RoadLanes(rig, V, h, w, max_segments=cam.ms, scap=min(256, cam.ms) if lanes_scap is None else int(lanes_scap),
+                                        ctx=self.ego.ctx, device=device, **lkw)
+            # the cameras' segment lists and counts where the lane chain leaves them: views into its workspace, no copy
+            off, nb = C.c_size_t(), C.c_size_t()
+            nat.check(self.L.av_lane_workspace_view(nat.LANE_VIEW_SEGMENTS, V * K, h, w, cam.ms, C.byref(off), C.byref(nb)))
+            self.lane_segments = cam.ws[off.value:off.value + nb.value].view(i32).view(V * K, cam.ms, 4)
+            nat.check(self.L.av_lane_workspace_view(nat.LANE_VIEW_NSEG, V * K, h, w, cam.ms, C.byref(off), C.byref(nb)))
+            self.lane_nseg = cam.ws[off.value:off.value + nb.value].view(i32).view(V * K)
+            self.ref_paths, self.n_ref, self.lane_offset = self.road_lanes.ref_paths, self.road_lanes.n_ref, self.road_lanes.lane_offset
             self.ego.set_reference_paths(self.ref_paths, self.n_ref)
         self.surround_view = self.surround_cover = None     # enqueue_surround_view
         self._surround = self._surround_key = self._surround_ids = None
@@ -1596,6 +1635,15 @@ class RigLoop:
                                               nat.ptr(self._poly), nat.ptr(self._pts), nat.ptr(self._info), nat.ptr(ego.plan_state), 1,
                                               50, nat.ptr(self.ref_paths), nat.ptr(self.n_ref), nat.ptr(self.lane_offset)))
 
+    def enqueue_road_lanes(self, stream=None):
+        """lanes="road": every camera's Hough segments (read in place from the lane workspace), the mounts, the odometry's motion
+        (ego="ground_flow") and the ego start states -> self.ref_paths / n_ref / lane_offset and self.road_lanes' rows
+        (av_road_lanes); call behind the camera half and the ego's enqueue_kf."""
+        if self.road_lanes is None:
+            raise RuntimeError('enqueue_road_lanes needs RigLoop(lanes="road")')
+        self.road_lanes.update(self.lane_segments, self.lane_nseg, plan_state=self.ego.plan_state,
+                               motion=self.odometry.motion if self.odometry is not None else None, stream=stream or self.ego._s)
+
     def step(self, frames=None, sync=False):
         """The camera half for V * K frames (frames: PerceptionLoop.enqueue_frames', [V * K, h, w, 3]); then on the ego loop's
         stream the cameras' detections -> tracker [-> track filter] -> camera-frame obstacle lists, the ego Kalman stage, av_rig_fuse,
@@ -1623,6 +1671,8 @@ class RigLoop:
             self.enqueue_rig_track()
         if self.lane_camera is not None:
             self.enqueue_lane_paths()
+        if self.road_lanes is not None:
+            self.enqueue_road_lanes()
         ego.enqueue_plan_each()
         if self.tags is not None:
             self.enqueue_tags()
@@ -1709,7 +1759,9 @@ class RigLoop:
         each obstacle row, -1 past n_obs), match [V, K * tcap] (the id each fused row went to), n_drop [V] and rig_tracks
         (RigTracker.tracks())) plus
         cam_obstacles [V, K, tcap, cols], cam_n_obs [V, K], n_off [V, K] (the cameras' own lists), views [V, K * tcap] (the mask of the
-        cameras that saw each fused obstacle), n_skip [V] and, with a lane camera, ref_paths [V, 50, 2], n_ref [V], lane_offset [V].
+        cameras that saw each fused obstacle), n_skip [V] and, with a lane camera or lanes="road", ref_paths [V, 50, 2] (n_points
+        of them with lanes="road"), n_ref [V], lane_offset [V]; with lanes="road" also lane_bounds [V, 8] (av_road_lane_bound),
+        lane_left / lane_right [V, 3], lane_width, lane_heading, lane_curvature, lane_count, lane_index, lane_views, lane_status [V].
         With tags: track_cls [V, tcap] and fused_cls [V, K * tcap] (the class id behind each tracked / fused row, -1 past the count),
         interactions (one tagging.InteractionTags per vehicle) and interaction_summary (av_interaction_summary [V]); the last two are
         None when class_map is not the reference map.
@@ -1744,7 +1796,14 @@ class RigLoop:
                     out["interactions"] = self.tagger.results()
                     out["interaction_summary"] = (self.tagger.summary.cpu().numpy().reshape(V, -1)
                                                   .view(np.dtype(nat.INTERACTION_SUMMARY_FIELDS)).reshape(V))
-        if self.lane_camera is not None:
+        if self.lane_camera is not None or self.road_lanes is not None:
             out["ref_paths"], out["n_ref"] = self.ref_paths.cpu().numpy(), self.n_ref.cpu().numpy()
             out["lane_offset"] = self.lane_offset.cpu().numpy()
+        if self.road_lanes is not None:
+            rows = self.road_lanes.lanes()
+            out["lane_bounds"] = self.road_lanes.bounds()
+            out["lane_left"], out["lane_right"], out["lane_width"] = rows["left"].copy(), rows["right"].copy(), rows["width"].copy()
+            out["lane_heading"], out["lane_curvature"] = rows["heading"].copy(), rows["curvature"].copy()
+            out["lane_count"], out["lane_index"] = rows["lane_count"].copy(), rows["lane_index"].copy()
+            out["lane_views"], out["lane_status"] = rows["views"].copy(), rows["status"].copy()
         return out
