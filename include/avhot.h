@@ -2037,6 +2037,131 @@ int av_road_lanes(av_ctx* ctx, av_stream_t stream, const av_road_lanes_cfg* cfg,
 /* Zeroes the state of vehicle `vehicle` (0 .. n_vehicles - 1), or of every vehicle with -1: one hipMemsetAsync on `stream`. */
 int av_road_lanes_reset(av_ctx* ctx, av_stream_t stream, int n_vehicles, int vehicle, av_road_lanes_state* state);
 
+/* ---- Road marks (opt-in): what each lane boundary is -- solid or dashed, white or yellow -- read from the pictures ----------------
+ * av_road_lanes knows where every boundary lies; av_road_marks walks along each of them in the rectified frames of the rig's K
+ * cameras and reads the paint.  Positions are float64, every operation rounded on its own (no FMA), in the order written; every
+ * decision is taken in integers.  The host turns the four lengths of the settings into sample counts once:
+ *   count(len) = (int)floor(len / ds + 0.5)                 (gap_solid_n, gap_dash_n, min_seen_n, min_paint_n; each 1 .. 65536) */
+typedef struct {
+    double x_near;             /* 4.0   m: the near edge of the first sample, ahead of the vehicle's origin */
+    double ds;                 /* 0.1   m: sample spacing along X */
+    double dl;                 /* 0.05  m: tap spacing across the line */
+    double gap_solid;          /* 0.5   m: a boundary without a measured gap this long is solid */
+    double gap_dash;           /* 1.5   m: a dashed boundary has a measured gap at least this long */
+    double min_seen;           /* 8.0   m of seen samples, below which the type is unknown */
+    double min_paint;          /* 2.0   m of paint samples, likewise */
+    int32_t n_samples;         /* 210;  1 .. 512 */
+    int32_t core;              /* 5:    taps |j| <= core belong to the marking; >= 0 */
+    int32_t shoulder0;         /* 9 */
+    int32_t shoulder1;         /* 13:   core < shoulder0 <= shoulder1 <= 16; taps shoulder0 <= |j| <= shoulder1 are the background */
+    int32_t contrast;          /* 40    gray levels; 1 .. 255 */
+    int32_t yellow_tenths;     /* 7;    0 .. 10 */
+    int32_t hold;              /* 3     frames; >= 1 */
+    int32_t forget;            /* 30    frames; >= 1 */
+} av_road_marks_cfg;           /* 88 bytes */
+#define AV_ROAD_MARKS_MAX_SAMPLES 512
+#define AV_ROAD_MARK_UNKNOWN 0     /* av_road_mark.type */
+#define AV_ROAD_MARK_SOLID 1
+#define AV_ROAD_MARK_DASHED 2
+#define AV_ROAD_MARK_WHITE 1       /* av_road_mark.colour; 0 with type UNKNOWN */
+#define AV_ROAD_MARK_YELLOW 2
+#define AV_ROAD_MARK_AMBIGUOUS 1   /* av_road_mark.flags: enough paint, a measured gap of gap_solid or more, and not dashed */
+typedef struct {
+    int32_t type, colour, flags;
+    int32_t n_seen, n_paint;   /* samples */
+    int32_t n_runs;            /* paint runs */
+    int32_t longest_gap;       /* the longest measured gap, samples */
+    int32_t n_gaps;            /* measured gaps */
+    int32_t n_dashes;          /* complete paint runs */
+    int32_t contrast;          /* the rounded mean of peak - bg over the paint samples; 0 without one */
+    int32_t views;             /* bit k: a seen sample was read from camera k */
+    int32_t reserved;          /* 0 */
+    double dash_m, gap_m;      /* the mean complete run and the mean measured gap, metres; 0 without one */
+} av_road_mark;                /* 64 bytes */
+typedef struct {
+    int32_t type, colour;      /* published */
+    int32_t observed, observed_colour;     /* this frame's */
+    int32_t run;               /* how many frames in a row the candidate pair has been observed */
+    int32_t bound;             /* the boundary observed, -1 without one */
+} av_road_marks_side;          /* 24 bytes */
+typedef struct {
+    av_road_marks_side left, right;
+    int32_t may_change_left, may_change_right;     /* 1: the published type is dashed, 0: solid, -1: unknown */
+    int32_t reserved[2];       /* 0 */
+} av_road_marks_row;           /* 64 bytes */
+/* Persistent per-vehicle state (device).  All zero = reset. */
+typedef struct {
+    int32_t type, colour;      /* published */
+    int32_t cand_type, cand_colour, run;           /* the last non-UNKNOWN observation and its run length */
+    int32_t since;             /* frames since the last non-UNKNOWN observation */
+} av_road_marks_side_state;    /* 24 bytes */
+typedef struct {
+    av_road_marks_side_state left, right;
+    int32_t frames;
+    int32_t reserved[3];       /* 0 */
+} av_road_marks_state;         /* 64 bytes */
+
+/* The stage for vehicle v, boundary b < nb = clamp(lanes[v].n_bounds, 0, 8) with (a0, a1, a2, x_min, x_max) = bounds[v][b], camera k
+ * of the vehicle being entry v * n_cams + k of mounts, ground and bgr (av_rig_surround's convention):
+ * 1 per sample i = 0 .. n_samples - 1:
+ *     X = x_near + ((double)i + 0.5) * ds;   Yc = (a0 + a1*X) + a2*(X*X);   tap j = -shoulder1 .. shoulder1:  Y_j = Yc + (double)j * dl
+ *   A tap in camera k, with the mount (cs, sn, mx, my), q = ground.ginv: av_rig_surround's
+ *     dx = X - mx;  dy = Y_j - my;  f = cs*dx + sn*dy;  l = cs*dy - sn*dx
+ *   and av_ground_warp's U, V, D, u, v, tu, tv for the road point (f, l); it PASSES when D > 0 && 0 <= tu <= (w-1) * 65536 &&
+ *   0 <= tv <= (h-1) * 65536 (a NaN fails).  Camera k SEES the sample when both end taps j = -shoulder1 and j = shoulder1 pass and
+ *   have 0 <= f <= max_range.  The taps lie on one straight line of the road, so they lie on one in the picture, and the frame is
+ *   convex: every tap between two that pass passes too.  (Only the roundings of u, v could break this, along the frame's very
+ *   border; a tap between the ends that does not pass reads as b = g = r = 0, so nothing outside the frame is ever read.)
+ *   The sample is read from the seeing camera with the smallest d2 = f*f + l*l of the centre tap j = 0; equal d2: the smallest k
+ *   (av_rig_surround's nearest blend).  seen_i = some camera sees it && X >= x_min && X <= x_max.
+ *   A seen sample's taps with |j| <= core or shoulder0 <= |j| <= shoulder1 are av_ground_warp's bilinear taps (b, g, r) at
+ *   (tu, tv) of that camera, and  gray = (1868*b + 9617*g + 4899*r + 8192) >> 14   (the lane front end's luma).
+ *     peak = the largest gray over |j| <= core, among equals the smallest j; (pb, pg, pr) that tap's channels
+ *     bg   = (2 * S + n) / (2 * n), S the sum of gray over the n = 2 * (shoulder1 - shoulder0 + 1) shoulder taps, integer division
+ *     paint_i = seen_i && peak - bg >= contrast
+ *   Over the paint samples: sum_b += pb; sum_g += pg; sum_r += pr; sum_c += peak - bg.  views: bit k where a seen sample was read
+ *   from camera k.
+ * 2 per boundary, on the bit strings seen and paint.  n_seen, n_paint: their counts.  A paint RUN is a maximal run of paint
+ *   samples; n_runs.  A GAP is the stretch between two consecutive runs; it is MEASURED when every sample of it is seen (a gap
+ *   across a stretch no camera sees is no gap): n_gaps, longest_gap, gap_m = ((double)(sum of their lengths) / (double)n_gaps) * ds.
+ *   A run is COMPLETE when the sample before its first and the sample after its last exist and are seen (they are not paint):
+ *   n_dashes, dash_m = ((double)(sum of their lengths) / (double)n_dashes) * ds.  Without one, 0.0.
+ *     type = UNKNOWN                            when n_seen < min_seen_n || n_paint < min_paint_n
+ *            else SOLID                         when longest_gap < gap_solid_n
+ *            else DASHED                        when n_runs >= 2 && longest_gap >= gap_dash_n
+ *            else UNKNOWN, flags AMBIGUOUS
+ *     colour = 0 with type UNKNOWN, else YELLOW when 10 * sum_b < yellow_tenths * min(sum_g, sum_r), else WHITE
+ *     contrast = (2 * sum_c + n_paint) / (2 * n_paint), 0 without paint.
+ *   marks[v][b]; profile[v][b][0] = the seen bits, [v][b][1] = the paint bits, sample i in bit i & 31 of word i >> 5.  Rows at
+ *   b >= nb (marks and profile) are zero.
+ * 3 per vehicle, from frame to frame.  If lanes[v].status has AV_ROAD_CHANGE_LEFT (the vehicle entered the lane on its left: its
+ *   old left boundary is now its right one), state.right = state.left and state.left = zero; else with AV_ROAD_CHANGE_RIGHT the
+ *   mirror image.  A side observes the first boundary b < nb whose flags carry AV_ROAD_BOUND_LEFT (_RIGHT): its (type, colour);
+ *   without one (coasting, the derived side of a one-sided lane, no lane) it observes UNKNOWN.  Then, per side:
+ *     observed type != UNKNOWN:  since = 0;  the pair equals (cand_type, cand_colour): run = min(run + 1, 1 << 30);  else cand =
+ *       the pair, run = 1.  run >= hold: (type, colour) = cand.
+ *     observed UNKNOWN:  since = min(since + 1, 1 << 30);  since >= forget: the side's state is zero (it publishes UNKNOWN).
+ *       Otherwise nothing changes: the candidate and its run survive the frame.
+ *   frames += 1.  sides[v]: per side the published pair, the observed pair, run and the boundary's index;
+ *   may_change_left / _right from the published type of that side.
+ *
+ *   mounts DEVICE [V][K]; ground DEVICE [V*K]; bgr [V*K][h][w][3]: RECTIFIED frames; bounds [V][8]; lanes [V]; state [V];
+ *   marks [V][8]; sides [V]; profile uint32 [V][8][2][16] or NULL.  Two launches on `stream`: one workgroup per (vehicle, boundary)
+ *   with one thread per sample (two rounds above 256), then one thread per vehicle.
+ * AV_EINVAL before any launch and before the context is looked at: a cfg that av_road_marks_check refuses; n_vehicles outside
+ * 1 .. 65535; n_cams outside 1 .. 8; h or w outside 1 .. 32768; a null pointer other than profile and stream. */
+/* Host only.  AV_EINVAL for a null cfg; a double not finite; ds, dl, gap_solid, gap_dash, min_seen, min_paint not > 0; gap_dash <
+ * gap_solid; a count(len) outside 1 .. 65536; n_samples outside 1 .. 512; core < 0; not core < shoulder0 <= shoulder1 <= 16;
+ * contrast outside 1 .. 255; yellow_tenths outside 0 .. 10; hold or forget < 1. */
+int av_road_marks_check(const av_road_marks_cfg* cfg);
+size_t av_road_marks_state_bytes(void);        /* sizeof(av_road_marks_state) */
+int av_road_marks(av_ctx* ctx, av_stream_t stream, const av_road_marks_cfg* cfg, int n_vehicles, int n_cams,
+                  const av_rig_mount* mounts, const av_ground_cfg* ground, int h, int w, const uint8_t* bgr,
+                  const av_road_lane_bound* bounds, const av_road_lanes_row* lanes, av_road_marks_state* state, av_road_mark* marks,
+                  av_road_marks_row* sides, uint32_t* profile);
+/* Zeroes the state of vehicle `vehicle` (0 .. n_vehicles - 1), or of every vehicle with -1: one hipMemsetAsync on `stream`. */
+int av_road_marks_reset(av_ctx* ctx, av_stream_t stream, int n_vehicles, int vehicle, av_road_marks_state* state);
+
 #ifdef __cplusplus
 }
 #endif

@@ -144,6 +144,34 @@ ROAD_LANES_STATE_FIELDS = [("left", "<f8", (3,)), ("right", "<f8", (3,)), ("widt
 ROAD_LANES_STATE_BYTES = 96
 
 
+class RoadMarksCfg(C.Structure):
+    """av_road_marks_cfg: the road-mark stage's sample grid (metres), tap pattern, contrast, run thresholds (metres), colour rule and
+    the frames a side's type is held and remembered; 88 bytes."""
+    _fields_ = [(k, C.c_double) for k in ("x_near", "ds", "dl", "gap_solid", "gap_dash", "min_seen", "min_paint")] + [
+        (k, C.c_int32) for k in ("n_samples", "core", "shoulder0", "shoulder1", "contrast", "yellow_tenths", "hold", "forget")]
+
+
+ROAD_MARKS_DEFAULTS = dict(x_near=4.0, ds=0.1, dl=0.05, gap_solid=0.5, gap_dash=1.5, min_seen=8.0, min_paint=2.0, n_samples=210, core=5,
+                           shoulder0=9, shoulder1=13, contrast=40, yellow_tenths=7, hold=3, forget=30)
+ROAD_MARKS_MAX_SAMPLES = 512
+ROAD_MARK_UNKNOWN, ROAD_MARK_SOLID, ROAD_MARK_DASHED = 0, 1, 2                                          # av_road_mark.type
+ROAD_MARK_WHITE, ROAD_MARK_YELLOW = 1, 2                                                                # av_road_mark.colour
+ROAD_MARK_AMBIGUOUS = 1                                                                                 # av_road_mark.flags
+ROAD_MARK_TYPES, ROAD_MARK_COLOURS = ("unknown", "solid", "dashed"), ("none", "white", "yellow")
+ROAD_MARK_FIELDS = [(k, "<i4") for k in ("type", "colour", "flags", "n_seen", "n_paint", "n_runs", "longest_gap", "n_gaps", "n_dashes",
+                                         "contrast", "views", "reserved")] + [("dash_m", "<f8"), ("gap_m", "<f8")]   # 64 bytes
+ROAD_MARK_BYTES = 64
+ROAD_MARKS_SIDE_FIELDS = [(k, "<i4") for k in ("type", "colour", "observed", "observed_colour", "run", "bound")]  # 24 bytes
+ROAD_MARKS_ROW_FIELDS = [("left", ROAD_MARKS_SIDE_FIELDS), ("right", ROAD_MARKS_SIDE_FIELDS), ("may_change_left", "<i4"),
+                         ("may_change_right", "<i4"), ("reserved", "<i4", (2,))]                                    # 64 bytes
+ROAD_MARKS_ROW_BYTES = 64
+ROAD_MARKS_SIDE_STATE_FIELDS = [(k, "<i4") for k in ("type", "colour", "cand_type", "cand_colour", "run", "since")]  # 24 bytes
+ROAD_MARKS_STATE_FIELDS = [("left", ROAD_MARKS_SIDE_STATE_FIELDS), ("right", ROAD_MARKS_SIDE_STATE_FIELDS), ("frames", "<i4"),
+                           ("reserved", "<i4", (3,))]                                                               # 64 bytes
+ROAD_MARKS_STATE_BYTES = 64
+ROAD_MARKS_PROFILE_WORDS = 16                                                           # uint32 words per bit string: 512 samples
+
+
 class RigTrackCfg(C.Structure):
     """av_rig_track_cfg: the vehicle-frame tracker's filter, gate and life cycle (seconds, metres); 72 bytes."""
     _fields_ = [("dt", C.c_double), ("q_accel", C.c_double), ("r_meas", C.c_double), ("r_range", C.c_double), ("p0_pos", C.c_double),
@@ -519,6 +547,10 @@ _SIGS = [
     ("av_road_lanes", C.c_int, [vp, vp, C.POINTER(RoadLanesCfg), C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp,
                                 vp, C.c_int, vp, vp, vp]),
     ("av_road_lanes_reset", C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
+    ("av_road_marks_check", C.c_int, [C.POINTER(RoadMarksCfg)]),
+    ("av_road_marks_state_bytes", C.c_size_t, []),
+    ("av_road_marks", C.c_int, [vp, vp, C.POINTER(RoadMarksCfg), C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
+    ("av_road_marks_reset", C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
 ]
 
 # entry points added by later translation units; bound when present in the header list below

@@ -1397,7 +1397,7 @@ class RigLoop:
     def __init__(self, n_vehicles, rig, h=720, w=1280, model="random:0", precision="fp16", dcap=64, obstacles="moving_tracks",
                  class_map="reference", lane_camera=0, fuse_kw=None, tracker_kw=None, kf_kw=None, planner_kw=None, obstacle_kw=None,
                  track_filter_kw=None, names=None, device=0, track=False, rig_track_kw=None, tags=None, tag_capacity=4096,
-                 tag_columns=False, ego=None, ego_kw=None, lanes=None, lanes_kw=None, **other):
+                 tag_columns=False, ego=None, ego_kw=None, lanes=None, lanes_kw=None, marks=False, marks_kw=None, **other):
         """rig: a perception.CameraRig.  obstacles: "moving_tracks", "filtered_tracks" or "tracks", CameraLoop's modes (a rig
         without obstacles has nothing to fuse).  lane_camera: the index of the camera whose lane fit is the vehicle's reference path
         (av_lane_paths_ground through rig.vehicle_calibration(lane_camera)), None for no path; its mount may not be yawed beyond
@@ -1426,7 +1426,12 @@ class RigLoop:
         frame through the measured ego motion when ego="ground_flow".  It fills ref_paths / n_ref / lane_offset in the lane camera's
         place, so lane_camera stays None or its default, and results() gains lane_bounds, lane_left, lane_right, lane_width,
         lane_heading, lane_curvature, lane_count, lane_index, lane_views and lane_status.  A rig with lenses is welcome: the lane
-        chain sees rectified frames, so its segments are rectified pixels."""
+        chain sees rectified frames, so its segments are rectified pixels.
+        marks=True (with lanes="road" only: the marks are read along its boundaries): every boundary is classified solid or dashed,
+        white or yellow, from the rectified frames of all K cameras, and the ego lane's two sides are held over frames
+        (self.road_marks, a perception.RoadMarks with marks_kw's settings: av_road_marks_cfg's fields), on the ego stream
+        behind the road lanes.  results() gains lane_mark_left / _right, lane_colour_left / _right, may_change_left / _right and
+        bound_marks."""
         from .perception.calibration import CameraRig, ground_table
         from .tracking.rig_tracker import RigTracker, check_shape, rig_track_cfg
         for k in other:
@@ -1465,6 +1470,18 @@ class RigLoop:
             road_lanes_cfg(**lkw)                                                   # (ValueError for a setting outside its range)
             if lanes_scap is not None:
                 check_lanes_shape(V, K, 1 << 20, lanes_scap)
+        if not isinstance(marks, (bool, np.bool_)):
+            raise ValueError("RigLoop: marks is True or False")
+        if marks and lanes is None:
+            raise ValueError('RigLoop: marks=True needs lanes="road": the marks are read along the road lanes\' boundaries')
+        if marks_kw is not None and not marks:
+            raise ValueError("RigLoop: marks_kw belongs to marks=True")
+        if marks:
+            from .perception.road_marks import check_shape as check_marks_shape, road_marks_cfg
+            if marks_kw is not None and not isinstance(marks_kw, dict):
+                raise ValueError("RigLoop: marks_kw is None or a dict of av_road_marks_cfg's fields")
+            road_marks_cfg(**(marks_kw or {}))                                      # (ValueError for a setting outside its range)
+            check_marks_shape(V, K, h, w)
         if lane_camera is not None:
             if not (isinstance(lane_camera, (int, np.integer)) and 0 <= lane_camera < K):
                 raise ValueError("RigLoop: lane_camera is None or a camera index 0 .. %d" % (K - 1))
@@ -1552,6 +1569,10 @@ class RigLoop:
             self.lane_nseg = cam.ws[off.value:off.value + nb.value].view(i32).view(V * K)
             self.ref_paths, self.n_ref, self.lane_offset = self.road_lanes.ref_paths, self.road_lanes.n_ref, self.road_lanes.lane_offset
             self.ego.set_reference_paths(self.ref_paths, self.n_ref)
+        self.road_marks = None
+        if marks:
+            from .perception.road_marks import RoadMarks
+            self.road_marks = RoadMarks(rig, V, h, w, ctx=self.ego.ctx, device=device, **(marks_kw or {}))
         self.surround_view = self.surround_cover = None     # enqueue_surround_view
         self._surround = self._surround_key = self._surround_ids = None
         self.surround_age = self.road_memory = None         # enqueue_surround_view(memory=True)
@@ -1644,6 +1665,14 @@ class RigLoop:
         self.road_lanes.update(self.lane_segments, self.lane_nseg, plan_state=self.ego.plan_state,
                                motion=self.odometry.motion if self.odometry is not None else None, stream=stream or self.ego._s)
 
+    def enqueue_road_marks(self, stream=None):
+        """marks=True: the boundaries enqueue_road_lanes() left and the cameras' rectified frames (cams.cam.frames, read and never
+        written) -> self.road_marks' rows (av_road_marks); call behind enqueue_road_lanes() on the same stream.  The next camera half
+        waits for the ego stream before it overwrites the frames, as it does for the surround view."""
+        if self.road_marks is None:
+            raise RuntimeError('enqueue_road_marks needs RigLoop(lanes="road", marks=True)')
+        self.road_marks.update(self.cams.cam.frames, self.road_lanes.bound_rows, self.road_lanes.rows, stream=stream or self.ego._s)
+
     def step(self, frames=None, sync=False):
         """The camera half for V * K frames (frames: PerceptionLoop.enqueue_frames', [V * K, h, w, 3]); then on the ego loop's
         stream the cameras' detections -> tracker [-> track filter] -> camera-frame obstacle lists, the ego Kalman stage, av_rig_fuse,
@@ -1673,6 +1702,8 @@ class RigLoop:
             self.enqueue_lane_paths()
         if self.road_lanes is not None:
             self.enqueue_road_lanes()
+        if self.road_marks is not None:
+            self.enqueue_road_marks()
         ego.enqueue_plan_each()
         if self.tags is not None:
             self.enqueue_tags()
@@ -1762,6 +1793,9 @@ class RigLoop:
         cameras that saw each fused obstacle), n_skip [V] and, with a lane camera or lanes="road", ref_paths [V, 50, 2] (n_points
         of them with lanes="road"), n_ref [V], lane_offset [V]; with lanes="road" also lane_bounds [V, 8] (av_road_lane_bound),
         lane_left / lane_right [V, 3], lane_width, lane_heading, lane_curvature, lane_count, lane_index, lane_views, lane_status [V].
+        With marks=True: lane_mark_left / _right [V] (the ego lane's sides: 0 unknown, 1 solid, 2 dashed), lane_colour_left / _right
+        [V] (0, 1 white, 2 yellow), may_change_left / _right [V] (1 over a dashed line, 0 not over a solid one, -1 unknown) and
+        bound_marks [V, 8] (av_road_mark, beside lane_bounds).
         With tags: track_cls [V, tcap] and fused_cls [V, K * tcap] (the class id behind each tracked / fused row, -1 past the count),
         interactions (one tagging.InteractionTags per vehicle) and interaction_summary (av_interaction_summary [V]); the last two are
         None when class_map is not the reference map.
@@ -1806,4 +1840,10 @@ class RigLoop:
             out["lane_heading"], out["lane_curvature"] = rows["heading"].copy(), rows["curvature"].copy()
             out["lane_count"], out["lane_index"] = rows["lane_count"].copy(), rows["lane_index"].copy()
             out["lane_views"], out["lane_status"] = rows["views"].copy(), rows["status"].copy()
+        if self.road_marks is not None:
+            sides = self.road_marks.sides()
+            out["bound_marks"] = self.road_marks.marks()
+            out["lane_mark_left"], out["lane_mark_right"] = sides["left"]["type"].copy(), sides["right"]["type"].copy()
+            out["lane_colour_left"], out["lane_colour_right"] = sides["left"]["colour"].copy(), sides["right"]["colour"].copy()
+            out["may_change_left"], out["may_change_right"] = sides["may_change_left"].copy(), sides["may_change_right"].copy()
         return out
