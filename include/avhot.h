@@ -2162,6 +2162,92 @@ int av_road_marks(av_ctx* ctx, av_stream_t stream, const av_road_marks_cfg* cfg,
 /* Zeroes the state of vehicle `vehicle` (0 .. n_vehicles - 1), or of every vehicle with -1: one hipMemsetAsync on `stream`. */
 int av_road_marks_reset(av_ctx* ctx, av_stream_t stream, int n_vehicles, int vehicle, av_road_marks_state* state);
 
+/* ---- Lane planner (opt-in): the planner's candidates ranked against the lane boundaries and their marks ---------------------------
+ * av_planner_plan_each / _plan_moving know a reference path and obstacle discs.  av_lane_plan is a post-pass over what they wrote:
+ * it charges every candidate for the lines it crosses, by their type (av_road_marks'), for the waypoints it spends on a line and
+ * for ending on one, ranks the candidates again and says what the chosen one does.  It reads waypoints and cost and writes
+ * neither; one launch, one workgroup per vehicle.  float64, every operation rounded on its own (no FMA), in the order written;
+ * every comparison with a NaN is false. */
+typedef struct {
+    double half_width;         /* 0.9   m: the vehicle's half width (av_rig_view_build's ego quad) */
+    double x_far;              /* 40.0  m: no line is tested beyond it */
+    double w_cross[3];         /* by av_road_mark.type UNKNOWN, SOLID, DASHED: 300, 1000, 0 */
+    double w_on[3];            /* 2, 5, 0: per waypoint closer to the line than half_width */
+    double w_end;              /* 500:  where the candidate ends it stands inside a lane, whatever the line's type */
+    int32_t follow;            /* 1:    lines are taken relative to the ego lane's course */
+    int32_t reserved;          /* 0 */
+} av_lane_plan_cfg;            /* 80 bytes */
+#define AV_LANEPLAN_MAX_LINES 10
+#define AV_LANEPLAN_MAX_CAND 192
+#define AV_LANEPLAN_MAX_POINTS 256
+#define AV_LANEPLAN_SRC_LEFT 8    /* av_lane_plan_line.source: the ego lane's left side itself (coasting or derived) */
+#define AV_LANEPLAN_SRC_RIGHT 9
+typedef struct {
+    double a0, a1, a2;         /* as published: the course is not subtracted here */
+    double xe;                 /* the line is tested for 0 <= X <= xe (and x_far) */
+    int32_t type;              /* AV_ROAD_MARK_UNKNOWN / _SOLID / _DASHED */
+    int32_t source;            /* the boundary's index b, AV_LANEPLAN_SRC_LEFT / _RIGHT, -1 for an unused row */
+    int32_t reserved[2];       /* 0 */
+} av_lane_plan_line;           /* 48 bytes */
+#define AV_LANEPLAN_KEEP 0        /* av_lane_plan_row.maneuver */
+#define AV_LANEPLAN_LEFT 1
+#define AV_LANEPLAN_RIGHT 2
+#define AV_LANEPLAN_FOLLOW 1      /* av_lane_plan_row.flags: a course was subtracted */
+#define AV_LANEPLAN_CHANGED 2     /* best != base_best */
+#define AV_LANEPLAN_FORCED 4      /* the best candidate crosses a solid or an unknown line */
+#define AV_LANEPLAN_NO_LINES 8
+typedef struct {
+    int32_t best;              /* order[v][0] */
+    int32_t base_best;         /* the index of the smallest cost, among equals the smallest index */
+    int32_t maneuver;          /* from the sign of delta: 0 keep, < 0 left, > 0 right */
+    int32_t delta;             /* delta[v][best] */
+    uint32_t crossed;          /* the crossed bits (0 .. 9) of cross[v][best] */
+    uint32_t crossed_solid;    /* ... those of its lines of type SOLID */
+    uint32_t crossed_unknown;  /* ... of type UNKNOWN */
+    int32_t n_lines;
+    int32_t flags;
+    int32_t reserved;          /* 0 */
+    double base_cost, lane_cost, total;            /* cost, lane_cost and total of best */
+} av_lane_plan_row;            /* 64 bytes */
+
+/* The stage for vehicle v with (x0, y0, h) = plan_state[v][0 .. 2]:
+ * 1 the lines, at most 10, in this order.  For b < nb = clamp(lanes[v].n_bounds, 0, 8): (a0, a1, a2) and xe = x_max of bounds[v][b],
+ *   source = b; its type is sides[v].left.type (the published one: av_road_marks' hold / forget) when the boundary's flags carry
+ *   AV_ROAD_BOUND_LEFT, else sides[v].right.type with _RIGHT, else marks[v][b].type.  Then, when lanes[v].status has AV_ROAD_LANE:
+ *   if no boundary b < nb carries _LEFT, the ego side itself (coasting, or derived from the other): lanes[v].left, xe = x_far, type
+ *   sides[v].left.type, source 8; likewise the right side with source 9.  A type outside 0 .. 2 reads as UNKNOWN; with marks and
+ *   sides NULL every type is UNKNOWN.  lines[v][0 .. n_lines-1]; the rows behind are zero with source -1.
+ * 2 the course.  (c1, c2) = (lanes[v].centre[1], lanes[v].centre[2]) when cfg.follow and the status has AV_ROAD_LANE (row flag
+ *   FOLLOW), else (0, 0).  Line j is used as b1 = a1 - c1, b2 = a2 - c2: the planner's candidates are straight in the ego heading,
+ *   and their lateral profile is read as an offset from the lane's course.
+ * 3 per candidate c and line j, over the waypoints (wx, wy) = waypoints[v][c][i][0 .. 1] in ascending i, placed as av_rig_view_build
+ *   places them:
+ *     dx = wx - x0;  dy = wy - y0;  X = dx*cos h + dy*sin h;  Y = dy*cos h - dx*sin h
+ *   Waypoint i is VALID for line j when X >= 0 && X <= xe && X <= x_far.  For a valid one
+ *     e = Y - ((a0 + b1*X) + b2*(X*X));   side = e > 0;   d = half_width - |e|
+ *   crossed: two consecutive valid waypoints (in index order) differ in side.  on = the sum from 0.0, in ascending i, of
+ *   w_on[type] * (d*d) over the valid waypoints with d > 0.  end = w_end * (d*d) of the last valid waypoint when its d > 0, else 0.
+ *     term_j = ((crossed ? w_cross[type] : 0.0) + on) + end;   delta_j = side_last - side_first   (0 without a valid waypoint)
+ * 4 per candidate.  lane_cost[v][c] = 0.0 + term_0 + term_1 + ... in ascending j;  total[v][c] = cost[v][c] + lane_cost[v][c];
+ *   cross[v][c]: bit j when crossed, bit 16 + j when some valid waypoint had d > 0;  delta[v][c] = the sum of delta_j (negative: the
+ *   candidate ends further left, a lateral offset below 0 being left);  order[v][.] = the stable ascending rank of total, the
+ *   planner's own rule (a smaller total first, among equals the smaller index).  Without a line every lane cost is exactly 0.0:
+ *   total is cost and order is the planner's.
+ * 5 row[v]: see the struct; flags FOLLOW, CHANGED, FORCED (crossed_solid | crossed_unknown != 0), NO_LINES (n_lines == 0).
+ *
+ *   plan_state [V][4]; waypoints [V][C][n][6] (fields 0 and 1 are read); cost [V][C]; bounds [V][8]; lanes [V]; marks [V][8] and
+ *   sides [V], NULL only together; lines [V][10]; lane_cost, total [V][C]; order int32 [V][C]; cross uint32 [V][C]; delta int32
+ *   [V][C]; row [V].  All device memory, the outputs always written.
+ * AV_EINVAL before any launch and before the context is looked at: a cfg that av_lane_plan_check refuses; n_vehicles outside
+ * 1 .. 65535; n_cand outside 1 .. 192; n_points outside 1 .. 256; one of marks / sides without the other; any other null pointer
+ * except the stream. */
+/* Host only.  AV_EINVAL for a null cfg; a double not finite; a weight < 0; half_width or x_far not > 0; follow not 0 or 1. */
+int av_lane_plan_check(const av_lane_plan_cfg* cfg);
+int av_lane_plan(av_ctx* ctx, av_stream_t stream, const av_lane_plan_cfg* cfg, int n_vehicles, int n_cand, int n_points,
+                 const double* plan_state, const double* waypoints, const double* cost, const av_road_lane_bound* bounds,
+                 const av_road_lanes_row* lanes, const av_road_mark* marks, const av_road_marks_row* sides, av_lane_plan_line* lines,
+                 double* lane_cost, double* total, int32_t* order, uint32_t* cross, int32_t* delta, av_lane_plan_row* row);
+
 #ifdef __cplusplus
 }
 #endif

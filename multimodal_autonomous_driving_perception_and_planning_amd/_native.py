@@ -172,6 +172,28 @@ ROAD_MARKS_STATE_BYTES = 64
 ROAD_MARKS_PROFILE_WORDS = 16                                                           # uint32 words per bit string: 512 samples
 
 
+class LanePlanCfg(C.Structure):
+    """av_lane_plan_cfg: the lane planner's vehicle half width and range (metres), the weights by mark type (unknown, solid, dashed)
+    of crossing a line and of a waypoint on one, the weight of ending on one, and whether the lane's course is followed; 80 bytes."""
+    _fields_ = [("half_width", C.c_double), ("x_far", C.c_double), ("w_cross", C.c_double * 3), ("w_on", C.c_double * 3),
+                ("w_end", C.c_double), ("follow", C.c_int32), ("reserved", C.c_int32)]
+
+
+LANEPLAN_DEFAULTS = dict(half_width=0.9, x_far=40.0, w_cross=(300.0, 1000.0, 0.0), w_on=(2.0, 5.0, 0.0), w_end=500.0, follow=1)
+LANEPLAN_MAX_LINES, LANEPLAN_MAX_CAND, LANEPLAN_MAX_POINTS = 10, 192, 256
+LANEPLAN_SRC_LEFT, LANEPLAN_SRC_RIGHT = 8, 9                                                          # av_lane_plan_line.source
+LANEPLAN_KEEP, LANEPLAN_LEFT, LANEPLAN_RIGHT = 0, 1, 2                                               # av_lane_plan_row.maneuver
+LANEPLAN_FOLLOW, LANEPLAN_CHANGED, LANEPLAN_FORCED, LANEPLAN_NO_LINES = 1, 2, 4, 8                  # av_lane_plan_row.flags
+LANEPLAN_MANEUVERS = ("keep", "left", "right")
+LANEPLAN_LINE_FIELDS = [("a0", "<f8"), ("a1", "<f8"), ("a2", "<f8"), ("xe", "<f8"), ("type", "<i4"), ("source", "<i4"),
+                         ("reserved", "<i4", (2,))]                                                                  # 48 bytes
+LANEPLAN_LINE_BYTES = 48
+LANEPLAN_ROW_FIELDS = [("best", "<i4"), ("base_best", "<i4"), ("maneuver", "<i4"), ("delta", "<i4"), ("crossed", "<u4"),
+                        ("crossed_solid", "<u4"), ("crossed_unknown", "<u4"), ("n_lines", "<i4"), ("flags", "<i4"), ("reserved", "<i4"),
+                        ("base_cost", "<f8"), ("lane_cost", "<f8"), ("total", "<f8")]                                  # 64 bytes
+LANEPLAN_ROW_BYTES = 64
+
+
 class RigTrackCfg(C.Structure):
     """av_rig_track_cfg: the vehicle-frame tracker's filter, gate and life cycle (seconds, metres); 72 bytes."""
     _fields_ = [("dt", C.c_double), ("q_accel", C.c_double), ("r_meas", C.c_double), ("r_range", C.c_double), ("p0_pos", C.c_double),
@@ -551,6 +573,8 @@ _SIGS = [
     ("av_road_marks_state_bytes", C.c_size_t, []),
     ("av_road_marks", C.c_int, [vp, vp, C.POINTER(RoadMarksCfg), C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
     ("av_road_marks_reset", C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
+    ("av_lane_plan_check", C.c_int, [C.POINTER(LanePlanCfg)]),
+    ("av_lane_plan", C.c_int, [vp, vp, C.POINTER(LanePlanCfg), C.c_int, C.c_int, C.c_int] + [vp] * 14),
 ]
 
 # entry points added by later translation units; bound when present in the header list below

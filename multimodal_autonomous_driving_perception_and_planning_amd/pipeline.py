@@ -1397,7 +1397,8 @@ class RigLoop:
     def __init__(self, n_vehicles, rig, h=720, w=1280, model="random:0", precision="fp16", dcap=64, obstacles="moving_tracks",
                  class_map="reference", lane_camera=0, fuse_kw=None, tracker_kw=None, kf_kw=None, planner_kw=None, obstacle_kw=None,
                  track_filter_kw=None, names=None, device=0, track=False, rig_track_kw=None, tags=None, tag_capacity=4096,
-                 tag_columns=False, ego=None, ego_kw=None, lanes=None, lanes_kw=None, marks=False, marks_kw=None, **other):
+                 tag_columns=False, ego=None, ego_kw=None, lanes=None, lanes_kw=None, marks=False, marks_kw=None, plan=None, lane_plan_kw=None,
+                 **other):
         """rig: a perception.CameraRig.  obstacles: "moving_tracks", "filtered_tracks" or "tracks", CameraLoop's modes (a rig
         without obstacles has nothing to fuse).  lane_camera: the index of the camera whose lane fit is the vehicle's reference path
         (av_lane_paths_ground through rig.vehicle_calibration(lane_camera)), None for no path; its mount may not be yawed beyond
@@ -1431,7 +1432,13 @@ class RigLoop:
         white or yellow, from the rectified frames of all K cameras, and the ego lane's two sides are held over frames
         (self.road_marks, a perception.RoadMarks with marks_kw's settings: av_road_marks_cfg's fields), on the ego stream
         behind the road lanes.  results() gains lane_mark_left / _right, lane_colour_left / _right, may_change_left / _right and
-        bound_marks."""
+        bound_marks.
+        plan: None -- the plan is the planner's own ranking -- or "lanes" (with lanes="road" only; with or without marks=True: without,
+        every line's type is unknown): behind the planner every candidate is charged for the lane boundaries it crosses, by their
+        marks, and the candidates are ranked again (self.lane_plan, a planning.LanePlanner with lane_plan_kw's settings:
+        av_lane_plan_cfg's fields).  The planner's wp, cost and order are read and never written; results() gains lane_cost,
+        plan_total, plan_order, plan_best, plan_maneuver, plan_delta, plan_crossed, plan_flags and plan_lines, and the surround view's
+        overlay draws the trajectory chosen here."""
         from .perception.calibration import CameraRig, ground_table
         from .tracking.rig_tracker import RigTracker, check_shape, rig_track_cfg
         for k in other:
@@ -1482,6 +1489,17 @@ class RigLoop:
                 raise ValueError("RigLoop: marks_kw is None or a dict of av_road_marks_cfg's fields")
             road_marks_cfg(**(marks_kw or {}))                                      # (ValueError for a setting outside its range)
             check_marks_shape(V, K, h, w)
+        if plan not in (None, "lanes"):
+            raise ValueError('RigLoop: plan is None or "lanes"')
+        if plan is not None and lanes is None:
+            raise ValueError('RigLoop: plan="lanes" needs lanes="road": the candidates are ranked against the road lanes\' boundaries')
+        if lane_plan_kw is not None and plan is None:
+            raise ValueError('RigLoop: lane_plan_kw belongs to plan="lanes"')
+        if plan is not None:
+            from .planning.lane_planner import lane_plan_cfg
+            if lane_plan_kw is not None and not isinstance(lane_plan_kw, dict):
+                raise ValueError("RigLoop: lane_plan_kw is None or a dict of av_lane_plan_cfg's fields")
+            lane_plan_cfg(**(lane_plan_kw or {}))                                   # (ValueError for a setting outside its range)
         if lane_camera is not None:
             if not (isinstance(lane_camera, (int, np.integer)) and 0 <= lane_camera < K):
                 raise ValueError("RigLoop: lane_camera is None or a camera index 0 .. %d" % (K - 1))
@@ -1573,6 +1591,10 @@ class RigLoop:
         if marks:
             from .perception.road_marks import RoadMarks
             self.road_marks = RoadMarks(rig, V, h, w, ctx=self.ego.ctx, device=device, **(marks_kw or {}))
+        self.lane_plan = None
+        if plan is not None:
+            from .planning.lane_planner import LanePlanner
+            self.lane_plan = LanePlanner(V, self.ego.n_cand, self.ego.n_points, ctx=self.ego.ctx, device=device, **(lane_plan_kw or {}))
         self.surround_view = self.surround_cover = None     # enqueue_surround_view
         self._surround = self._surround_key = self._surround_ids = None
         self.surround_age = self.road_memory = None         # enqueue_surround_view(memory=True)
@@ -1673,6 +1695,17 @@ class RigLoop:
             raise RuntimeError('enqueue_road_marks needs RigLoop(lanes="road", marks=True)')
         self.road_marks.update(self.cams.cam.frames, self.road_lanes.bound_rows, self.road_lanes.rows, stream=stream or self.ego._s)
 
+    def enqueue_lane_plan(self, stream=None):
+        """plan="lanes": the planner's candidates (ego.wp, ego.cost: read and never written), the boundaries enqueue_road_lanes() left
+        and, with marks=True, the marks of enqueue_road_marks() -> self.lane_plan's outputs (av_lane_plan); call behind
+        ego.enqueue_plan_each() on the same stream."""
+        if self.lane_plan is None:
+            raise RuntimeError('enqueue_lane_plan needs RigLoop(lanes="road", plan="lanes")')
+        ego, rm = self.ego, self.road_marks
+        self.lane_plan.rank(ego.plan_state, ego.wp, ego.cost, self.road_lanes.bound_rows, self.road_lanes.rows,
+                            marks=rm.mark_rows if rm is not None else None, sides=rm.side_rows if rm is not None else None,
+                            stream=stream or ego._s)
+
     def step(self, frames=None, sync=False):
         """The camera half for V * K frames (frames: PerceptionLoop.enqueue_frames', [V * K, h, w, 3]); then on the ego loop's
         stream the cameras' detections -> tracker [-> track filter] -> camera-frame obstacle lists, the ego Kalman stage, av_rig_fuse,
@@ -1705,6 +1738,8 @@ class RigLoop:
         if self.road_marks is not None:
             self.enqueue_road_marks()
         ego.enqueue_plan_each()
+        if self.lane_plan is not None:
+            self.enqueue_lane_plan()
         if self.tags is not None:
             self.enqueue_tags()
         self._stepped = True
@@ -1775,7 +1810,7 @@ class RigLoop:
             else:
                 obstacles, n_obs = self.obstacles, self.n_obs.view(V)
             sv.draw(ego.plan_state, obstacles, n_obs, ids=ids, ref_path=self.ref_paths, n_ref=self.n_ref, waypoints=ego.wp,
-                    order=ego.order, stream=ego._s)
+                    order=self.lane_plan.order if self.lane_plan is not None else ego.order, stream=ego._s)
 
     def capture(self):
         raise RuntimeError("RigLoop: graph capture is out of scope")
@@ -1796,6 +1831,9 @@ class RigLoop:
         With marks=True: lane_mark_left / _right [V] (the ego lane's sides: 0 unknown, 1 solid, 2 dashed), lane_colour_left / _right
         [V] (0, 1 white, 2 yellow), may_change_left / _right [V] (1 over a dashed line, 0 not over a solid one, -1 unknown) and
         bound_marks [V, 8] (av_road_mark, beside lane_bounds).
+        With plan="lanes": lane_cost and plan_total [V, C], plan_order [V, C] (cost and order stay the planner's), plan_best,
+        plan_maneuver (0 keep, 1 left, 2 right), plan_delta, plan_crossed (bit j: line j), plan_flags [V] (av_lane_plan_row's) and
+        plan_lines [V, 10] (av_lane_plan_line).
         With tags: track_cls [V, tcap] and fused_cls [V, K * tcap] (the class id behind each tracked / fused row, -1 past the count),
         interactions (one tagging.InteractionTags per vehicle) and interaction_summary (av_interaction_summary [V]); the last two are
         None when class_map is not the reference map.
@@ -1846,4 +1884,10 @@ class RigLoop:
             out["lane_mark_left"], out["lane_mark_right"] = sides["left"]["type"].copy(), sides["right"]["type"].copy()
             out["lane_colour_left"], out["lane_colour_right"] = sides["left"]["colour"].copy(), sides["right"]["colour"].copy()
             out["may_change_left"], out["may_change_right"] = sides["may_change_left"].copy(), sides["may_change_right"].copy()
+        if self.lane_plan is not None:
+            p = self.lane_plan.results()
+            out["lane_cost"], out["plan_total"], out["plan_order"] = p["lane_cost"], p["total"], p["order"]
+            out["plan_best"], out["plan_maneuver"] = p["rows"]["best"].copy(), p["rows"]["maneuver"].copy()
+            out["plan_delta"], out["plan_crossed"] = p["rows"]["delta"].copy(), p["rows"]["crossed"].copy()
+            out["plan_flags"], out["plan_lines"] = p["rows"]["flags"].copy(), p["lines"]
         return out
