@@ -846,6 +846,17 @@ int av_yolo_keep_logits(av_yolo* h, int enable);
  * anchor as the head wrote them: box float32 [A][4], confidence float32 [A], class int32 [A]; 120-122 = the same from the
  * stand-alone decode of the kept logits). */
 int av_yolo_tensor(const av_yolo* h, int id, void** ptr, int* H, int* W, int* C, int* cstride, int* coff);
+/* Test hook: the tail of av_yolo_forward on the caller's candidates instead of the head's.  cand_box float32 [batch][n_anchors][4]
+ * (xyxy in network pixels), cand_conf float32 [batch][n_anchors], cand_cls int32 [batch][n_anchors], all on the device, in the
+ * handle's geometry (av_yolo_dims); conf_thres / iou_thres / max_det and det_* as in av_yolo_forward, with its argument checks.
+ * The launches are the forward's own (one internal function serves both): the same sort kernel by anchor count, the same gain and
+ * padding, the handle's sort scratch -- hence AV_ESTATE while a deferred tail of the handle is pending (av_yolo_join_tail first).
+ * What the tail computes, here as in the forward: a confidence outside (conf_thres, 1], NaN included, is not a candidate; the
+ * candidates are taken in descending confidence, equal confidences in ascending anchor order; a box is dropped when an earlier KEPT box
+ * of its class has IoU > iou_thres with it (0/0 of two zero-area boxes is NaN: not dropped); the first max_det kept boxes are
+ * mapped back to the frame.  det_n[b] rows of image b are written; rows at and beyond det_n[b] are not written. */
+int av_yolo_tail(av_yolo* h, av_stream_t stream, const float* cand_box, const float* cand_conf, const int32_t* cand_cls,
+                 float conf_thres, float iou_thres, int max_det, int32_t* det_n, float* det_box, float* det_conf, int32_t* det_cls);
 /* Test hook: the ops of the network as av_yolo_create built them, one per layer in execution order (what a forward under
  * AVHOT_YOLO_NO_FUSE launches one by one), so that a test can read one layer's operands and output back and evaluate that layer alone
  * (tests/test_gpu_yolo_layers.py does, in float64).  The query reads host memory only: it launches nothing, copies nothing and does

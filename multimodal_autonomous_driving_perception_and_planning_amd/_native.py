@@ -522,6 +522,7 @@ _SIGS = [
     ("av_yolo_defer_tail", C.c_int, [vp, C.c_int]),
     ("av_yolo_join_tail", C.c_int, [vp, vp]),
     ("av_yolo_tensor", C.c_int, [vp, C.c_int, C.POINTER(vp)] + [C.POINTER(C.c_int)] * 5),
+    ("av_yolo_tail", C.c_int, [vp, vp, vp, vp, vp, C.c_float, C.c_float, C.c_int, vp, vp, vp, vp]),
     ("av_yolo_op_count", C.c_int, [vp, C.POINTER(C.c_int)]),
     ("av_yolo_op", C.c_int, [vp, C.c_int, C.POINTER(YoloOpInfo)]),
     ("av_yolo_plan_count", C.c_int, [vp, C.POINTER(C.c_int)]),

@@ -3222,6 +3222,28 @@ int av_yolo_plan_step(const av_yolo* h, int k, av_yolo_step_info* info) {
     return AV_OK;
 }
 
+// The tail of a forward on `st`: threshold + sort, then greedy NMS + scale_boxes, of the candidates cbox / cconf / ccls ([B][A] in the
+// handle's geometry) through the handle's scratch (sbox / sidx / scount).  av_yolo_forward passes the head's candidates, av_yolo_tail
+// the caller's.
+static int launch_tail(Yolo& y, hipStream_t st, const float* cbox, const float* cconf, const int* ccls, float conf_thres, float iou_thres,
+                       int max_det, int32_t* det_n, float* det_box, float* det_conf, int32_t* det_cls) {
+    const int B = y.B;
+    {
+        const int rounds = (y.A + 1023) / 1024;
+        if (rounds <= 7) hipLaunchKernelGGL(nms_sort_kernel<8>, dim3(B), dim3(1024), rs_lds(rounds, 8), st, y.A, rounds, conf_thres, cbox, cconf, ccls, y.sbox, y.sidx, y.scount);
+        else hipLaunchKernelGGL(nms_sort_kernel<7>, dim3(B), dim3(1024), rs_lds(rounds, 7), st, y.A, rounds, conf_thres, cbox, cconf, ccls, y.sbox, y.sidx, y.scount);
+    }
+    AV_LAUNCH_CHECK();
+    // gain/pad of ultralytics scale_boxes
+    const float gain = std::fmin((float)y.H / y.inH, (float)y.W / y.inW);
+    const float padx = (float)std::lround((y.W - y.inW * gain) / 2 - 0.1), pady = (float)std::lround((y.H - y.inH * gain) / 2 - 0.1);
+    const size_t nms_lds = (size_t)max_det * 24;
+    hipLaunchKernelGGL(nms_greedy_kernel, dim3(B), dim3(64 * NMS_WAVES), nms_lds, st, y.A, max_det, iou_thres, y.sbox, y.scount, y.sidx,
+                       cbox, cconf, ccls, gain, padx, pady, (float)y.inW, (float)y.inH, det_n, det_box, det_conf, det_cls);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
 int av_yolo_forward(av_yolo* h, av_stream_t stream, const uint8_t* bgr, float conf_thres, float iou_thres, int max_det,
                     int32_t* det_n, float* det_box, float* det_conf, int32_t* det_cls) {
     AV_REQUIRE(h && bgr && det_n && det_box && det_conf && det_cls, AV_EINVAL, "av_yolo_forward: null argument");
@@ -3289,23 +3311,25 @@ int av_yolo_forward(av_yolo* h, av_stream_t stream, const uint8_t* bgr, float co
         AV_LAUNCH_CHECK();
     }
     {
-        const int rounds = (y.A + 1023) / 1024;
-        if (rounds <= 7) hipLaunchKernelGGL(nms_sort_kernel<8>, dim3(B), dim3(1024), rs_lds(rounds, 8), st, y.A, rounds, conf_thres, y.cbox, y.cconf, y.ccls, y.sbox, y.sidx, y.scount);
-        else hipLaunchKernelGGL(nms_sort_kernel<7>, dim3(B), dim3(1024), rs_lds(rounds, 7), st, y.A, rounds, conf_thres, y.cbox, y.cconf, y.ccls, y.sbox, y.sidx, y.scount);
+        const int rc = launch_tail(y, st, y.cbox, y.cconf, y.ccls, conf_thres, iou_thres, max_det, det_n, det_box, det_conf, det_cls);
+        if (rc != AV_OK) return rc;
     }
-    AV_LAUNCH_CHECK();
-    // gain/pad of ultralytics scale_boxes
-    const float gain = std::fmin((float)y.H / y.inH, (float)y.W / y.inW);
-    const float padx = (float)std::lround((y.W - y.inW * gain) / 2 - 0.1), pady = (float)std::lround((y.H - y.inH * gain) / 2 - 0.1);
-    const size_t nms_lds = (size_t)max_det * 24;
-    hipLaunchKernelGGL(nms_greedy_kernel, dim3(B), dim3(64 * NMS_WAVES), nms_lds, st, y.A, max_det, iou_thres, y.sbox, y.scount, y.sidx,
-                       y.cbox, y.cconf, y.ccls, gain, padx, pady, (float)y.inW, (float)y.inH, det_n, det_box, det_conf, det_cls);
-    AV_LAUNCH_CHECK();
     if (y.defer_tail) {
         AV_HIP(hipEventRecord(y.ev_tail, st));
         y.tail_pending = true;
     }
     return AV_OK;
+}
+
+// test hook: the forward's tail on the caller's candidates
+int av_yolo_tail(av_yolo* h, av_stream_t stream, const float* cand_box, const float* cand_conf, const int32_t* cand_cls, float conf_thres,
+                 float iou_thres, int max_det, int32_t* det_n, float* det_box, float* det_conf, int32_t* det_cls) {
+    AV_REQUIRE(h && cand_box && cand_conf && cand_cls && det_n && det_box && det_conf && det_cls, AV_EINVAL, "av_yolo_tail: null argument");
+    AV_REQUIRE(max_det > 0 && max_det <= 2500 && conf_thres > 0.f, AV_EINVAL,
+               "av_yolo_tail: max_det must be in [1,2500] (kept boxes live in LDS) and conf_thres > 0");
+    Yolo& y = h->y;
+    AV_REQUIRE(!y.tail_pending, AV_ESTATE, "av_yolo_tail: a deferred tail of this handle is pending (it uses the same scratch): av_yolo_join_tail first");
+    return launch_tail(y, as_stream(stream), cand_box, cand_conf, cand_cls, conf_thres, iou_thres, max_det, det_n, det_box, det_conf, det_cls);
 }
 
 int av_yolo_keep_logits(av_yolo* h, int enable) {

@@ -478,6 +478,30 @@ class YoloV8:
             out.append(info)
         return out
 
+    def tail(self, box, conf, cls, conf_thres=CONF_THRES, iou_thres=IOU_THRES, max_det=MAX_DET, out=None):
+        """The forward's threshold + sort + NMS + scale_boxes on given candidates (test hook av_yolo_tail): box float32 [batch, A, 4] in
+        network pixels, conf float32 [batch, A], cls int32 [batch, A] (A = dims()[2]), as arrays or device tensors.  out: the device
+        tensors (n int32 [batch], box float32 [batch, max_det, 4], conf float32 [batch, max_det], cls int32 [batch, max_det]) the
+        library writes; default: fresh ones filled with zeros.  -> host copies of the four; rows at and beyond n[b] are not written."""
+        d, A = self._dev, self.dims()[2]
+
+        def up(a, dtype, shape):
+            np_dtype = np.float32 if dtype == torch.float32 else np.int32
+            t = a if torch.is_tensor(a) else torch.as_tensor(np.array(a, np_dtype))    # (a writable copy: as_tensor refuses read-only arrays)
+            t = t.to(d.device).contiguous()
+            if t.dtype != dtype or tuple(t.shape) != shape:
+                raise ValueError("candidates must be %s %s, got %s %s" % (dtype, shape, t.dtype, tuple(t.shape)))
+            return t
+        B = self.batch
+        cb, cc, ck = up(box, torch.float32, (B, A, 4)), up(conf, torch.float32, (B, A)), up(cls, torch.int32, (B, A))
+        if out is None:
+            out = (d.zeros(B, torch.int32), d.zeros((B, max_det, 4), torch.float32), d.zeros((B, max_det), torch.float32),
+                   d.zeros((B, max_det), torch.int32))
+        nat.check(d.lib.av_yolo_tail(self._h, d.stream, nat.ptr(cb), nat.ptr(cc), nat.ptr(ck), conf_thres, iou_thres, int(max_det),
+                                     *[nat.ptr(t) for t in out]))
+        d.sync()
+        return tuple(t.cpu().numpy() for t in out)
+
     def plan(self):
         """The launches of a forward as they are planned now, in order (test hook av_yolo_plan_step): a list of nat.YoloStepInfo.
         Reads nothing from the device."""
